@@ -9,20 +9,27 @@ MLPs with the method's uncertainty head) -> front-to-back composite with varianc
 HBM before the timed region; synthetic seeded data, random-init weights of the nerfacto shape.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--method active|mcdropout|laplace|splat|ensemble] [--mc-samples 8]
+                    [--full] [--dump-outputs DIR]
 
 Without --method the headline is the north-star target config (BASELINE.json configs[2]): nerfacto-mcdropout with
-K = 8 fused passes; active-nerfacto, nerfacto-laplace and active-splatfacto follow as `sub_records` of the same line.
+K = 8 fused passes.  A plain run sets up, warms up, times the K steps and prints the headline fields (metric, value, unit,
+higher_is_better, dtype, ms_per_step, config) and nothing else.  --full adds what is measured or checked besides the
+headline, as the default line carried it before the option existed: per-kernel HIP-event times and `roofline`,
+`wider_arithmetic`, `cpu_baseline`, `parity_at_bench_size`, `step_wall_ms`, and (without --method) the headline's
+workload in its other arithmetic and on tcnn-layout tables, active-nerfacto, nerfacto-laplace, active-splatfacto and the
+ensemble as `sub_records`.
+--dump-outputs DIR writes the arrays the timed path returned in its last step as DIR/<name>.npy (dump_outputs).
 
 N>1 runs one rank per GPU under torch.distributed.run: either the caller launches it that way, or plain
 `python bench.py --gpus N` starts `python -m torch.distributed.run --nproc-per-node N bench.py <same args>` itself as
 a child process (before this process has touched the GPU) and relays rank 0's JSON line and the child's exit code.
 Rays are independent, so ranks render different cameras of the orbit with replicated weights and no data-path
-collective ("weak" scaling); the barrier + max-over-ranks timing uses RCCL.  The default run also carries
+collective ("weak" scaling); the barrier + max-over-ranks timing uses RCCL.  The default --full run also carries
 `sub_records.ensemble`: the 8-member nerfacto ensemble of BASELINE.json configs[3], members sharded over the ranks
 (8 / N per GPU), per-pixel moments through ONE all_to_all + ONE all_gather over RCCL -- strong scaling, the north-star's
 ">= 6x at 8 GPUs" figure is value(N=8) / value(N=1) of that record.
-Prints ONE JSON line on rank 0 (contract in the task statement), carrying `roofline` for the
-dominant kernel and `cpu_baseline` (the CPU oracle timed on a bounded sample of the same rays).
+Prints ONE JSON line on rank 0; with --full it carries `roofline` for the dominant kernel and `cpu_baseline` (the CPU
+oracle timed on a bounded sample of the same rays).
 """
 import argparse
 import gc
@@ -100,6 +107,37 @@ def _issue_profile(method, K):
     return j
 
 
+DUMP_LIMIT_BYTES = 63_000_000    # --dump-outputs: under 64 MB in all, .npy headers included
+
+
+def dump_outputs(out, path, H, W, seed=0):
+    """--dump-outputs: the tensors of one step's output dict as <path>/<name>.npy, float32 (float64 stays float64), so
+    that two builds can be compared output for output.  Called right after the timed loop, before anything else renders.
+    Images [H,W,C] are written as [H*W,C] rows; if all of it would exceed DUMP_LIMIT_BYTES, every image keeps the same
+    fixed, seeded sample of pixel rows (sorted), as many as fit.  Other tensors are written whole."""
+    import numpy as np
+    imgs, rest = {}, {}
+    for k, v in out.items():
+        if not torch.is_tensor(v):
+            continue
+        v = v.detach()
+        v = v.to(torch.float64 if v.dtype == torch.float64 else torch.float32)
+        if v.dim() >= 2 and tuple(v.shape[:2]) == (H, W):
+            imgs[k] = v.reshape(H * W, -1)
+        else:
+            rest[k] = v
+    row_bytes = sum(v.shape[1] * v.element_size() for v in imgs.values())
+    fixed = sum(v.numel() * v.element_size() for v in rest.values())
+    if imgs and fixed + row_bytes * H * W > DUMP_LIMIT_BYTES:
+        n = max(0, (DUMP_LIMIT_BYTES - fixed) // row_bytes)
+        ids = np.sort(np.random.default_rng(seed).choice(H * W, size=n, replace=False))
+        sel = torch.from_numpy(ids).to(next(iter(imgs.values())).device)
+        imgs = {k: v.index_select(0, sel) for k, v in imgs.items()}
+    os.makedirs(path, exist_ok=True)
+    for k, v in {**imgs, **rest}.items():
+        np.save(os.path.join(path, f"{k}.npy"), v.cpu().numpy())
+
+
 # _timed_region_gc: every timed loop below is bracketed by gc.freeze() / gc.unfreeze().  CPython's full (generation-2)
 # collection walks every tracked object of the process -- after `import torch` that is 15 - 120 ms during which the host
 # issues nothing -- and WHEN it runs depends on allocation counts: frame 42 of a 400-frame soak took 60 - 91 ms instead of 45
@@ -107,10 +145,12 @@ def _issue_profile(method, K):
 # with the long-lived objects frozen, or the collector off, no frame of 2 x 400 exceeded 47.1 ms).  freeze() moves what exists
 # after the warm-up into the permanent generation: the collector keeps running, on the young objects only.  No work is skipped.
 def run_nerf(args, method, K, steps, warmup, rank, world, dev, dist, exact_check=True, want_cpu=True, precision=None,
-             grid=None, grid_precision=None):
-    """One NeRF method through the whole frame path; returns the record (headline fields + roofline + cpu_baseline).
+             grid=None, grid_precision=None, full=True, dump_dir=None):
+    """One NeRF method through the whole frame path; returns the record (headline fields; with `full` also per-kernel
+    times, roofline, wider_arithmetic + cpu_baseline where asked for).
     grid / grid_precision (default: args): "tcnn" = the tiny-cuda-nn table layout the reference's default
-    implementation trains with, "f16" = in tcnn's own half arithmetic (half2 rows)."""
+    implementation trains with, "f16" = in tcnn's own half arithmetic (half2 rows).
+    dump_dir: rank 0 writes the last timed step's outputs there (dump_outputs)."""
     from uncertainty_nerf_gs_amd import ops, render, synthetic
     grid = grid or args.grid
     grid_precision = grid_precision or (args.grid_precision or ("f16" if grid == "tcnn" else "f32"))
@@ -151,7 +191,7 @@ def run_nerf(args, method, K, steps, warmup, rank, world, dev, dist, exact_check
     for i in range(warmup):
         out = frame(i)
     sync_all()
-    ops.TIMER = ops.KernelTimer(prealloc=64 * steps)
+    ops.TIMER = ops.KernelTimer(prealloc=64 * steps) if full else None
     gc.freeze()   # see _timed_region_gc
     t0 = time.perf_counter()
     marks = []
@@ -168,6 +208,8 @@ def run_nerf(args, method, K, steps, warmup, rank, world, dev, dist, exact_check
         tt = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
+    if dump_dir and rank == 0:
+        dump_outputs(out, dump_dir, H, W)
     assert torch.isfinite(out["rgb"]).all()
     mrays = H * W * steps * world / elapsed / 1e6
 
@@ -175,7 +217,7 @@ def run_nerf(args, method, K, steps, warmup, rank, world, dev, dist, exact_check
     # arithmetic (f16 -> split-f16, split-f16 -> exact fp32-input MFMA), and how far the headline image is from that one.
     exact = None
     head_prec = scene.field.precision
-    if head_prec in ("f16x2", "f16") and exact_check:
+    if head_prec in ("f16x2", "f16") and exact_check and full:
         wider = "fp32" if head_prec == "f16x2" else "f16x2"
         scene.field.precision = wider
         n_alt = max(1, min(steps, 3))
@@ -216,7 +258,7 @@ def run_nerf(args, method, K, steps, warmup, rank, world, dev, dist, exact_check
                            "precision (forced autocast fp16, mcdropout_models.py:86-92; tcnn FullyFusedMLP)" if single
                            else "exact fp32 (v_mfma_f32_32x32x2_f32)")
     rec["precision"] = scene.field.precision
-    if rank != 0:
+    if rank != 0 or not full:
         return rec
     ksum = timer.summary()
     alg = _alg(method, K, row_bytes)
@@ -365,6 +407,13 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline does not need: per-kernel times and roofline, "
+                         "wider_arithmetic, cpu_baseline, parity_at_bench_size, step_wall_ms and, without --method, the "
+                         "sub_records (several minutes)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the arrays the timed path returned in its last step to DIR/<name>.npy (float32 / float64, "
+                         "at most 64 MB in all: a fixed, seeded sample of the pixels when the frame is larger)")
     ap.add_argument("--method", default=None, choices=["active", "mcdropout", "laplace", "splat", "ensemble"],
                     help="default: nerfacto-mcdropout K=8 (the north-star target config) as the headline, with active / "
                          "laplace / splat sub-records in the same line")
@@ -389,11 +438,12 @@ def main():
     ap.add_argument("--exact-fp32", action="store_true",
                     help="dense layers on the exact fp32-input MFMA kernels instead of the split-f16 ones")
     ap.add_argument("--no-exact-check", action="store_true",
-                    help="skip the extra exact-fp32 frames rendered after the timed region")
-    ap.add_argument("--no-sub-records", action="store_true", help="headline only (default run: skip active / laplace / splat)")
+                    help="--full: skip the extra exact-fp32 frames rendered after the timed region")
+    ap.add_argument("--no-sub-records", action="store_true",
+                    help="--full: headline only (default run: skip active / laplace / splat)")
     ap.add_argument("--no-trained-like-parity", action="store_true",
-                    help="skip the trained-like-scene leg of parity_at_bench_size (two more oracle passes, ~25 s)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+                    help="--full: skip the trained-like-scene leg of parity_at_bench_size (two more oracle passes, ~25 s)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip cpu_baseline and parity_at_bench_size")
     ap.add_argument("--cpu-seconds", type=float, default=30.0, help="cpu_baseline: time cap of the oracle leg")
     ap.add_argument("--cpu-chunks", type=int, default=16, help="cpu_baseline: 1024-ray chunks of the frame the oracle renders "
                     "(the same sample every run, so parity_at_bench_size is comparable between runs; ~12 s on 16 host threads)")
@@ -436,26 +486,28 @@ def main():
 
     default_run = args.method is None
     method = args.method or "mcdropout"
+    full, dump_dir = args.full, args.dump_outputs
     if method == "splat":
-        line = bench_splat(args, rank, world, dev, dist, args.steps, args.warmup)
+        line = bench_splat(args, rank, world, dev, dist, args.steps, args.warmup, full=full, dump_dir=dump_dir)
         if rank == 0:
             emit(line)
     elif method == "ensemble":
-        line = bench_ensemble(args, rank, world, dev, dist, args.steps, args.warmup)
+        line = bench_ensemble(args, rank, world, dev, dist, args.steps, args.warmup, full=full, dump_dir=dump_dir)
         if rank == 0:
             line.update(comm)
             emit(line)
     else:
         K = args.mc_samples if method == "mcdropout" else 0
-        rec = run_nerf(args, method, K, args.steps, args.warmup, rank, world, dev, dist, exact_check=not args.no_exact_check)
+        rec = run_nerf(args, method, K, args.steps, args.warmup, rank, world, dev, dist, exact_check=not args.no_exact_check,
+                       want_cpu=full, full=full, dump_dir=dump_dir)
         subs = None
-        if default_run and not args.no_sub_records and args.members % world == 0:
+        if full and default_run and not args.no_sub_records and args.members % world == 0:
             # BASELINE.json configs[3] at every N: the M-member nerfacto ensemble sharded over the ranks (strong scaling)
             ens = bench_ensemble(args, rank, world, dev, dist, 3, 1)
             torch.cuda.synchronize()
             if rank == 0:
                 subs = {"ensemble": {k: ens[k] for k in ("value", "unit", "ms_per_step", "steps", "warmup", "scaling", "config", "exchange")}}
-        if default_run and not args.no_sub_records and world == 1:
+        if full and default_run and not args.no_sub_records and world == 1:
             # the other single-GPU configs of BASELINE.json, each with its own per-kernel times (fewer steps: the
             # default run must stay within minutes); the headline above is the north-star target config
             # the headline's workload with the dense layers at the REFERENCE's own eval precision (opt-in, --precision f16):
@@ -490,10 +542,11 @@ def main():
                 "config": {"workload": rec["workload"], "rays_per_step": H * W, "samples_per_ray": [256, 96, 48],
                            "hash_grid": rec["hash_grid"], "dense_layers": rec["dense_layers"],
                            "parallelism": f"views x{world}" if world > 1 else "single"},
-                "roofline": rec["roofline"], "cpu_baseline": rec["cpu_baseline"],
-                "parity_at_bench_size": rec["parity_at_bench_size"], "wider_arithmetic": rec["wider_arithmetic"],
-                "step_wall_ms": rec["step_wall_ms"],
             }
+            if full:
+                line.update({"roofline": rec["roofline"], "cpu_baseline": rec["cpu_baseline"],
+                             "parity_at_bench_size": rec["parity_at_bench_size"], "wider_arithmetic": rec["wider_arithmetic"],
+                             "step_wall_ms": rec["step_wall_ms"]})
             line.update(comm)
             if subs is not None:
                 line["sub_records"] = subs
@@ -521,12 +574,13 @@ def nerfacto_member_state_dict(t):
     return {"_model." + k: v for k, v in sd.items()}
 
 
-def bench_ensemble(args, rank, world, dev, dist, steps, warmup):
+def bench_ensemble(args, rank, world, dev, dist, steps, warmup, full=True, dump_dir=None):
     """config 3: M-member nerfacto ensemble (ensemble_pipeline.py:144-191), members sharded over the ranks
     (M/N per GPU; 1 per GPU at N = M = 8).  Members are plain `nerfacto` models (ensemble_utils.py:149-150) loaded from
     checkpoints in upstream's key layout.  Every rank renders the SAME camera with its own members, then the per-pixel
     moments are formed exactly (two-pass) on pixel slices: one all_to_all + one all_gather over RCCL.  Strong scaling:
-    the frame's total work (M renders) is fixed, so value = frame rays / time grows with N."""
+    the frame's total work (M renders) is fixed, so value = frame rays / time grows with N.  `full`: also the exchange
+    record (ensemble_exchange_record)."""
     from uncertainty_nerf_gs_amd import ensemble, models, plugin, synthetic
     M = args.members
     assert M % world == 0, "members must divide evenly over the ranks"
@@ -568,11 +622,13 @@ def bench_ensemble(args, rank, world, dev, dist, steps, warmup):
         tt = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
+    if dump_dir and rank == 0:
+        dump_outputs(out, dump_dir, H, W)
     assert torch.isfinite(out["rgb"]).all() and "rgb_std" in out
-    exchange = ensemble_exchange_record(pipe, cams[0], M, world, dev, dist, elapsed / steps * 1e3)
+    exchange = ensemble_exchange_record(pipe, cams[0], M, world, dev, dist, elapsed / steps * 1e3) if full else None
     del pipe, members
     torch.cuda.empty_cache()
-    return {
+    line = {
         "exchange": exchange,
         "metric": "Mrays/s (+var), Mip-NeRF360-shaped 1080p, M-member ensemble", "value": H * W * steps / elapsed / 1e6,
         "unit": "Mrays/s", "n_gpus": world, "steps": steps, "warmup": warmup,
@@ -584,6 +640,10 @@ def bench_ensemble(args, rank, world, dev, dist, steps, warmup):
                                    if world > 1 else "single GPU: members rendered in sequence, moments on the device")},
         "roofline": None, "cpu_baseline": None,
     }
+    if not full:
+        for k in ("exchange", "roofline", "cpu_baseline"):
+            del line[k]
+    return line
 
 
 def ensemble_exchange_record(pipe, cam, M, world, dev, dist, frame_ms):
@@ -642,10 +702,11 @@ def ensemble_exchange_record(pipe, cam, M, world, dev, dist, frame_ms):
             tdist.destroy_process_group()
 
 
-def bench_splat(args, rank, world, dev, dist, steps, warmup):
+def bench_splat(args, rank, world, dev, dist, steps, warmup, full=True, dump_dir=None):
     """config 5: active-splatfacto, N splats (SURVEY.md 8d synthetic set), 1080p, per-splat variance.
     A step = one frame: project + SH/beta + ONE bin-and-sort + 5-channel raster + depth-variance raster.
-    Ranks render different views of the orbit with replicated splats (view-batch DP, no collective)."""
+    Ranks render different views of the orbit with replicated splats (view-batch DP, no collective).
+    `full`: per-kernel times and the roofline (two more projections of pose 0 count the intersections)."""
     from uncertainty_nerf_gs_amd import ops, splat, synthetic
     gp = {k: v.to(dev) for k, v in synthetic.make_splat_tensors(seed=7, N=args.splats).items()}
     H, W = args.height, args.width
@@ -668,7 +729,7 @@ def bench_splat(args, rank, world, dev, dist, steps, warmup):
     for i in range(warmup):
         out = frame(i)
     sync_all()
-    ops.TIMER = ops.KernelTimer(prealloc=32 * steps)
+    ops.TIMER = ops.KernelTimer(prealloc=32 * steps) if full else None
     gc.freeze()   # _timed_region_gc
     t0 = time.perf_counter()
     for i in range(steps):
@@ -681,7 +742,19 @@ def bench_splat(args, rank, world, dev, dist, steps, warmup):
         tt = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
+    if dump_dir and rank == 0:
+        dump_outputs(out, dump_dir, H, W)
     assert torch.isfinite(out["rgb"]).all()
+    head = {
+        "metric": "Mrays/s (+var) [pixels of an active-splatfacto frame], 1080p", "value": H * W * steps * world / elapsed / 1e6,
+        "unit": "Mrays/s", "n_gpus": world, "steps": steps, "warmup": warmup,
+        "ms_per_step": elapsed / steps * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": "f32", "data": "synthetic",
+        "config": {"workload": f"active-splatfacto {W}x{H}, N={args.splats} splats, rgb+beta+depth+depth_var",
+                   "parallelism": f"views x{world}" if world > 1 else "single"},
+    }
+    if rank == 0 and not full:
+        return head
     if rank == 0:
         ksum = timer.summary()
         dom = max(ksum, key=lambda k: ksum[k]["total_ms"])
@@ -752,12 +825,7 @@ def bench_splat(args, rank, world, dev, dist, steps, warmup):
                 if dom == "splat_bin_sort" and ts:
                     traffic = ts["fetch_bytes"] + ts["write_bytes"]
         line = {
-            "metric": "Mrays/s (+var) [pixels of an active-splatfacto frame], 1080p", "value": H * W * steps * world / elapsed / 1e6,
-            "unit": "Mrays/s", "n_gpus": world, "steps": steps, "warmup": warmup,
-            "ms_per_step": elapsed / steps * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": "f32", "data": "synthetic",
-            "config": {"workload": f"active-splatfacto {W}x{H}, N={args.splats} splats, rgb+beta+depth+depth_var",
-                       "parallelism": f"views x{world}" if world > 1 else "single"},
+            **head,
             "roofline": {"kernel": dom,
                          **({"bound": "valu-issue", "unit": "Gcycle/s", "peak": ISSUE_PEAK_GCYC,
                              "achieved": iss["issue_cycles_per_launch"] / (ksum[dom]["avg_ms"] * 1e-3) / 1e9,

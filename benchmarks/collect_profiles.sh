@@ -33,7 +33,7 @@ margs() {  # profile id -> bench.py arguments
 stats() {  # profile id
     local m=$1; shift
     rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/${m}_stats" -- \
-        python3 "$ROOT/bench.py" $(margs $m) --steps 4 --warmup 1 --no-cpu-baseline --no-exact-check "$@" > "$OUT/${m}_stats.log" 2>&1
+        python3 "$ROOT/bench.py" $(margs $m) --steps 4 --warmup 1 --no-cpu-baseline --no-exact-check --full "$@" > "$OUT/${m}_stats.log" 2>&1
     local f
     f=$(find "$OUT/${m}_stats" -name '*kernel_stats.csv' | head -1)
     [ -n "$f" ] && cp "$f" "$DST/${TAG}_${m}_kernel_stats.csv"
@@ -68,5 +68,5 @@ python3 "$ROOT/benchmarks/summarize_pmc.py" summary "$DST" "$TAG"
 # the default line (what the driver runs), outside the profiler -- with THIS run's traffic_* / issue_* profiles in place, so that
 # its roofline block reads counters of the sources it times (bench.py ignores profiles of another source digest)
 cp "$DST"/traffic_*.json "$DST"/issue_*.json "$ROOT/profiles/" 2>/dev/null
-cd "$ROOT" && python3 bench.py > "$DST/${TAG}_default_bench.json" 2> "$OUT/default_bench.err"
+cd "$ROOT" && python3 bench.py --full > "$DST/${TAG}_default_bench.json" 2> "$OUT/default_bench.err"
 ls -la "$DST"

@@ -17,6 +17,6 @@ for m in active mcdropout; do
     f=$(find "$OUT/planes_${m}_$c" -name '*counter_collection.csv' | head -1)
     [ -n "$f" ] && python3 "$ROOT/benchmarks/summarize_pmc.py" reduce "$f" "$DST/${TAG}_planes_${m}_pmc_$c.csv"
   done
-  cd "$ROOT" && python3 bench.py --method "$m" --steps 5 --warmup 2 --no-cpu-baseline --no-exact-check > "$DST/${TAG}_planes_${m}_bench.json" 2>/dev/null; cd /tmp
+  cd "$ROOT" && python3 bench.py --method "$m" --steps 5 --warmup 2 --no-cpu-baseline --no-exact-check --full > "$DST/${TAG}_planes_${m}_bench.json" 2>/dev/null; cd "$TMPDIR"
 done
 grep -h "field_kernel\|composite" "$DST"/${TAG}_planes_*_pmc_*.csv

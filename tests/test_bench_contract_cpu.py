@@ -1,5 +1,5 @@
 """bench.py's output contract, checked on the committed line of the latest profiled run (profiles/*_default_bench.json
-is the stdout line of `python bench.py` on MI355X) and on the script's command line -- no GPU needed."""
+is the stdout line of `python bench.py --full` on MI355X) and on the script's command line -- no GPU needed."""
 import glob
 import json
 import os
@@ -166,3 +166,47 @@ def test_parity_record_is_zero_for_identical_frames_and_well_conditioned():
     worse = {k: v.clone() for k, v in got.items()}
     worse["rgb_std"] = ref["rgb_std"].flip(0).clone()
     assert bench.parity_record(worse, ids, {"fp32": ref}, "f16")["inside_gates"] is False
+
+
+def _bench_module():
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    return bench
+
+
+def test_dump_outputs_is_bounded_and_samples_the_same_pixels(tmp_path):
+    """--dump-outputs: a 1080p output dict is larger than the 64 MB bound, so every image keeps the same fixed, seeded
+    sample of pixel rows; images are written as [pixels, C] float32, float64 stays float64, other tensors whole."""
+    import numpy as np
+    import torch
+    bench = _bench_module()
+    H, W = 1080, 1920
+    g = torch.Generator().manual_seed(0)
+    out = {"rgb": torch.rand(H, W, 3, generator=g), "rgb_std": torch.rand(H, W, 3, generator=g),
+           "accumulation": torch.arange(H * W, dtype=torch.float32).reshape(H, W, 1), "depth": torch.rand(H, W, 1, generator=g).double(),
+           "background": torch.tensor([0.1, 0.2, 0.3]), "not_a_tensor": None}
+    for d in ("a", "b"):
+        bench.dump_outputs(out, str(tmp_path / d), H, W)
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == ["accumulation.npy", "background.npy", "depth.npy", "rgb.npy", "rgb_std.npy"]
+    assert sum(os.path.getsize(tmp_path / "a" / n) for n in names) <= 64 * 10 ** 6
+    for n in names:
+        assert np.array_equal(np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)), n
+    rgb, depth = np.load(tmp_path / "a" / "rgb.npy"), np.load(tmp_path / "a" / "depth.npy")
+    assert rgb.dtype == np.float32 and depth.dtype == np.float64 and rgb.shape[1] == 3 and depth.shape[1] == 1
+    assert H * W // 2 < rgb.shape[0] == depth.shape[0] < H * W
+    # the rows are pixels of the frame (accumulation holds the pixel index here), in order, the same ones in every image
+    ids = np.load(tmp_path / "a" / "accumulation.npy")[:, 0].astype(np.int64)
+    assert (np.diff(ids) > 0).all() and np.array_equal(rgb, out["rgb"].reshape(-1, 3).numpy()[ids])
+    assert np.array_equal(np.load(tmp_path / "a" / "background.npy"), out["background"].numpy())
+    # a small frame is written whole
+    small = {k: v[:32, :48] for k, v in out.items() if k not in ("background", "not_a_tensor")}
+    bench.dump_outputs(small, str(tmp_path / "s"), 32, 48)
+    assert np.array_equal(np.load(tmp_path / "s" / "rgb.npy"), small["rgb"].reshape(-1, 3).numpy())
+
+
+def test_full_is_off_by_default_and_dump_outputs_takes_a_directory():
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=300)
+    assert p.returncode == 0 and "--full" in p.stdout and "--dump-outputs DIR" in p.stdout
