@@ -58,6 +58,11 @@ for m in $ALL; do
 done
 for m in $ALL; do
     pmc $m sq SQ_INSTS_VALU SQ_INSTS_MFMA SQ_ACTIVE_INST_VALU SQ_VALU_MFMA_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_INSTS_VMEM_RD GRBM_GUI_ACTIVE
+    case $m in
+        mcdropout*)   # the K-pass kernels' stall split: where the issue lane's idle cycles go, and whether LDS is the limit
+            pmc $m stall SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_WAVE_CYCLES SQ_WAVES GRBM_GUI_ACTIVE
+            pmc $m lds SQ_INSTS_LDS SQ_ACTIVE_INST_LDS SQ_WAIT_INST_LDS SQ_LDS_BANK_CONFLICT SQ_INSTS_SALU ;;
+    esac
 done
 if [ -z "${ONLY:-}" ]; then
 pmc splat lds SQ_INSTS_LDS SQ_ACTIVE_INST_LDS SQ_LDS_BANK_CONFLICT SQ_INSTS_SALU SQ_WAVES

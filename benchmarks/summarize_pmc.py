@@ -83,7 +83,7 @@ def summary(d, tag):
     for method in ("active", "active_f16", "mcdropout", "mcdropout_f16", "mcdropout_f16_tcnn", "mcdropout_f16_tcnn32", "laplace", "splat"):
         kernels = defaultdict(dict)
         for fn in sorted(os.listdir(d)):
-            m = re.match(rf"{tag}_{method}_pmc_(fetch|write|sq|lds|ta|tcc)\.csv$", fn)
+            m = re.match(rf"{tag}_{method}_pmc_(fetch|write|sq|stall|lds|ta|tcc)\.csv$", fn)
             if not m:
                 continue
             with open(os.path.join(d, fn), newline="") as f:

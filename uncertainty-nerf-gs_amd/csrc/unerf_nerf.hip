@@ -2141,9 +2141,12 @@ __device__ __forceinline__ f32x16 mf_dropout_keep(f32x16 v, const uint32_t (&st)
     return v;
 }
 typedef short i16x2 __attribute__((ext_vector_type(2)));
+// keep test of the two units of a mask word: unit kept <=> its half of the difference is negative
+__device__ __forceinline__ uint32_t mf16_keep_diff(uint32_t word, uint32_t thr_pk) {
+    return __builtin_bit_cast(uint32_t, __builtin_elementwise_sub_sat(__builtin_bit_cast(i16x2, word), __builtin_bit_cast(i16x2, thr_pk)));
+}
 __device__ __forceinline__ uint32_t mf16_keep_mask(uint32_t word, uint32_t thr_pk) {
-    const i16x2 d = __builtin_elementwise_sub_sat(__builtin_bit_cast(i16x2, word), __builtin_bit_cast(i16x2, thr_pk));
-    return __builtin_bit_cast(uint32_t, d >> (short)15);
+    return __builtin_bit_cast(uint32_t, __builtin_bit_cast(i16x2, mf16_keep_diff(word, thr_pk)) >> (short)15);
 }
 // sigmoid on the hardware exp / rcp (v_exp_f32, v_rcp_f32: ~1e-7 relative each) instead of the ~25-instruction
 // exact expf + IEEE division
@@ -2226,6 +2229,27 @@ __device__ __forceinline__ void mf16_split_relu(const f32x16& v, int s, f16x8& h
         hv[p] = __builtin_bit_cast(uint32_t, __builtin_elementwise_max(__builtin_bit_cast(i16x2, w), z));
     }
     hi = __builtin_bit_cast(f16x8, hv);
+}
+// ... and the keep masks of a dropout site with it, one instruction per two units (cvt, sub, bitop3, max): a dropped unit
+// (keep difference d = sub_sat(word, thr) >= 0, sign clear) gets its sign bit set, and the integer max maps it to +0 with
+// the negatives.  max_i16(x | (~d & 0x80008000), 0) = max_i16(x, 0) & (d >> 15) for every x, NaNs included: the same bits
+// as mf16_split_relu + mf16_apply_masks in one instruction less.  d: the four words' mf16_keep_diff.
+__device__ __forceinline__ void mf16_split_relu_drop(const f32x16& v, int s, const u32x4& d, f16x8& hi) {
+    u32x4 hv;
+#pragma unroll
+    for (int p = 0; p < 4; ++p) {
+        const unerf_v2f pr = {v[8 * s + 2 * p], v[8 * s + 2 * p + 1]};
+        const uint32_t w = __builtin_bit_cast(uint32_t, __builtin_convertvector(pr, f16x2)) | (~d[p] & 0x80008000u);
+        const i16x2 z = {0, 0};
+        hv[p] = __builtin_bit_cast(uint32_t, __builtin_elementwise_max(__builtin_bit_cast(i16x2, w), z));
+    }
+    hi = __builtin_bit_cast(f16x8, hv);
+}
+// one lane's 16-byte operand quad from the LDS blob (every slab offset is a multiple of 16 bytes and the dynamic LDS base is
+// 16-byte aligned).  Without the stated alignment the compiler reads some quads (the trunk-out and colour-2 slabs) as two
+// ds_read2_b32 + two address adds: 4 VALU and 4 LDS instructions per pass more in the K-pass kernel.
+__device__ __forceinline__ f16x8 mf16_lds_op(const float* p) {
+    return *reinterpret_cast<const f16x8*>(__builtin_assume_aligned(p, 16));
 }
 // acc += W(slab) x B: small terms first
 template <bool F1 = false>
@@ -2329,8 +2353,7 @@ __device__ __forceinline__ void mf16_apply_masks(f16x8& hi, f16x8& lo, const uin
 // UNERF_KPASS_FILL: the keep test of eight words in its two halves, so that the halves can sit in different MFMA shadows
 __device__ __forceinline__ void mf16_keep_sub(const uint32_t (&w)[8], uint32_t thr_pk, uint32_t (&d)[8]) {
 #pragma unroll
-    for (int q = 0; q < 8; ++q)
-        d[q] = __builtin_bit_cast(uint32_t, __builtin_elementwise_sub_sat(__builtin_bit_cast(i16x2, w[q]), __builtin_bit_cast(i16x2, thr_pk)));
+    for (int q = 0; q < 8; ++q) d[q] = mf16_keep_diff(w[q], thr_pk);
 }
 __device__ __forceinline__ void mf16_keep_sign(uint32_t (&d)[8]) {
 #pragma unroll
@@ -2351,8 +2374,9 @@ __device__ __forceinline__ void mf_pin8(uint32_t (&x)[8]) {
 // DROP: masks are generated (MCDROPOUT with K > 0 and p > 0).  A compile-time flag: as a run-time (uniform) flag every
 // k-step of the masked layers carried a branch and the operand quads were copied to merge the two paths.
 template <int MODE, int TCNN, bool SITES = false, bool DROP = false, bool F1 = false>
-// (the single-product K-pass kernel at 3 waves per SIMD -- 168 VGPRs, 96 B of scratch, trunk operands re-read from LDS --
-// was measured and lost: 4.84 vs 3.89 ms per launch, same box, profiles/r3_exp_f16_single_occ3.json)
+// (the single-product K-pass kernel at 3 waves per SIMD was measured twice and lost both times: round 3, 168 VGPRs, 96 B of
+// scratch, trunk operands re-read from LDS -- 4.84 vs 3.89 ms per launch, profiles/r3_exp_f16_single_occ3.json; round 7,
+// 163 VGPRs, no scratch, the SH k-step of colour 0 recomputed per pass -- 12.71 - 12.88 vs 12.44 - 12.56 ms, docs/experiments.md 7.1)
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((MODE == UNERF_FIELD_ACTIVE && TCNN != 1) ? 3 : 2)))
 void field_kernel_mfma16(FieldArgs a, uint32_t num_tiles, FastDiv div_s) {
     extern __shared__ float lds[];
@@ -2510,7 +2534,7 @@ void field_kernel_mfma16(FieldArgs a, uint32_t num_tiles, FastDiv div_s) {
                     a0 = ta0[st];
                     a1 = F1 ? ta0[st] : ta1[st];
                 } else {
-                    a0 = *reinterpret_cast<const f16x8*>(lds + (4 + st) * 512 + lane * 4);
+                    a0 = mf16_lds_op(lds + (4 + st) * 512 + lane * 4);
                     a1 = F1 ? a0 : *reinterpret_cast<const f16x8*>(lds + (4 + st) * 512 + 256 + lane * 4);
                 }
                 if (F1) {
@@ -2524,7 +2548,7 @@ void field_kernel_mfma16(FieldArgs a, uint32_t num_tiles, FastDiv div_s) {
                 }
             }
             if (FOLD) t = mf16_fold_rows(t);
-            if (FILL) {   // behind the trunk's four MFMAs: this pass' head words tested (first half), then stepped for the next pass
+            if (FILL) {   // behind the trunk's four MFMAs: this pass' head words tested (mf16_split_relu_drop), then stepped for the next pass
                 MF_FENCE();
                 mf16_keep_sub(mk2, a.keep_pk, am_h0);
                 mf16_keep_sub(mk3, a.keep_pk, am_h1);
@@ -2549,13 +2573,6 @@ void field_kernel_mfma16(FieldArgs a, uint32_t num_tiles, FastDiv div_s) {
                 f1_bad |= c0[0] != c0[0];
                 c0 = mf_relu(c0);
                 c1 = mf_relu(c1);
-            }
-            if (FILL) {   // behind colour 0's two MFMAs: the head masks' second half
-                MF_FENCE();
-                mf16_keep_sign(am_h0);
-                mf16_keep_sign(am_h1);
-                mf_pin8(am_h0); mf_pin8(am_h1);
-                MF_FENCE();
             }
             // colour 1: 64 -> 64, ReLU
             f32x16 d0 = mf16_bias(lds, 5, h), d1 = mf16_bias(lds, 6, h);
@@ -2600,15 +2617,17 @@ void field_kernel_mfma16(FieldArgs a, uint32_t num_tiles, FastDiv div_s) {
                 for (int r = 0; r < 16; ++r) o4[r] = 0.f;
 #pragma unroll
                 for (int st = 0; st < 4; ++st) {
-                    f16x8 bhi, blo;
-                    mf16_split_relu(st < 2 ? d0 : d1, st & 1, bhi);
-                    blo = bhi;
-                    if (FILL) {
-                        const uint32_t (&am)[8] = st < 2 ? am_h0 : am_h1;
-                        const u32x4 m = {am[4 * (st & 1)], am[4 * (st & 1) + 1], am[4 * (st & 1) + 2], am[4 * (st & 1) + 3]};
-                        bhi = __builtin_bit_cast(f16x8, __builtin_bit_cast(u32x4, bhi) & m);
-                    } else if (drop_head1) mf16_apply_masks<true>(bhi, blo, st < 2 ? mk2 : mk3, st & 1, a.keep_pk);
-                    const f16x8 aw = *reinterpret_cast<const f16x8*>(lds + UNERF_MFMA_BLOB_FLOATS + st * 256 + lane * 4);
+                    f16x8 bhi;
+                    if (FILL || drop_head1) {
+                        const uint32_t (&w)[8] = FILL ? (st < 2 ? am_h0 : am_h1) : (st < 2 ? mk2 : mk3);
+                        u32x4 dd;
+#pragma unroll
+                        for (int p = 0; p < 4; ++p) dd[p] = FILL ? w[4 * (st & 1) + p] : mf16_keep_diff(w[4 * (st & 1) + p], a.keep_pk);
+                        mf16_split_relu_drop(st < 2 ? d0 : d1, st & 1, dd, bhi);
+                    } else {
+                        mf16_split_relu(st < 2 ? d0 : d1, st & 1, bhi);
+                    }
+                    const f16x8 aw = mf16_lds_op(lds + UNERF_MFMA_BLOB_FLOATS + st * 256 + lane * 4);
                     o4 = __builtin_amdgcn_mfma_f32_32x32x16_f16(aw, bhi, o4, 0, 0, 0);
                 }
                 if (FILL) {   // behind colour 2's four MFMAs: the next pass' trunk masks
