@@ -595,6 +595,76 @@ int unerf_splat_normalize_outputs(float* img, int stride, int ch, const float* f
 int unerf_splat_depth_sqdiff(const float* xys, const float* depths, const float* depth_img, int stride, int ch,
                              int H, int W, int64_t N, float* sq_diff_out, void* stream);
 
+/* ---------------------------------------------------------------- splats, B views per call --
+ * B cameras of ONE splat set and ONE image size H x W in each launch: the evaluation loop over a test set's cameras
+ * (scripts/eval_uncertainty.py:896-904, which calls ActiveSplatfactoModel.get_outputs once per camera,
+ * activesplatfacto_model.py:155 asserts one camera) rendered a batch at a time.  Every view's outputs are BIT-identical to the
+ * single-view entry points above with that view's camera.  Per-view arrays are view-major: [B, N, ...] / [B, H, W, ...], view v
+ * at offset v N / v H W.  Limits: 1 <= B <= UNERF_SPLAT_MAX_VIEWS; B N < UNERF_SPLAT_MAX_BATCH_SPLATS (2^29: ids v N + i are
+ * int32 and the rasteriser forms 3 id in 32 bits); the batch's intersections sum to < 2^31 (int32 ids and bins).
+ * views_host: B records of UNERF_SPLAT_VIEW_FLOATS HOST floats, [world-to-camera rows 0..2 (12, row-major), fx, fy, cx, cy,
+ * camera position (3)] -- the viewmat / intrinsics / cam_pos of the single-view calls. */
+#define UNERF_SPLAT_MAX_VIEWS 16
+#define UNERF_SPLAT_VIEW_FLOATS 19
+#define UNERF_SPLAT_MAX_BATCH_SPLATS (1ll << 29)
+/* largest image unerf_splat_bin_sort_batch serves, in tiles (1080p at block_width 16: 8,160) */
+#define UNERF_SPLAT_BATCH_MAX_TILES 11999
+
+/* :221-234 as unerf_splat_project_raw, for B views in one launch: each splat's parameters are read once.  Outputs [B,N,...];
+ * opacities_out [B,N] (with opacity_logits; antialiased: times each view's compensation); cov3d [B,N,6] may be NULL. */
+int unerf_splat_project_batch(const float* means3d, const float* log_scales, float glob_scale, const float* raw_quats,
+                              const float* views_host, int B, int H, int W, int block_width, float clip_thresh, int64_t N,
+                              const float* opacity_logits, int antialiased, float* opacities_out, float* xys, float* depths,
+                              int32_t* radii, float* conics, float* compensation, int32_t* num_tiles_hit, float* cov3d,
+                              void* stream);
+
+/* :242-256, :286 as unerf_splat_shade_inputs, for B views in one launch (the camera positions of views_host): the SH
+ * coefficients are read once.  compensation [B,N] (may be NULL), depths [B,N]; rows_out [B,N,C], opacities_out [B,N]. */
+int unerf_splat_shade_inputs_batch(int degree, const float* means3d, const float* views_host, int B, const float* features_dc,
+                                   const float* features_rest, const float* log_unc, float beta_min,
+                                   const float* opacity_logits, const float* compensation, const float* depths, int64_t N,
+                                   int C, float* rows_out, float* opacities_out, void* stream);
+
+/* Workspace of unerf_splat_count_intersects_batch / unerf_splat_bin_sort_batch for B views of N splats and num_intersects
+ * pairs over all views; -1 outside the limits above. */
+int64_t unerf_splat_sort_workspace_bytes_batch(int B, int64_t N, int64_t num_intersects);
+
+/* compute_cumulative_intersects for a batch: ONE inclusive scan over the B N tile counts -> cum_tiles_hit [B,N], and the
+ * batch's one host read-back, summary [2B] i32 DEVICE: summary[v] = view v's intersections, summary[B + v] = 1 when some
+ * radius of view v is > 0 (radii [B,N] may be NULL: then summary[B + v] = (summary[v] > 0)) -- with tight counts a view can
+ * have no intersections and still be "visible" (its splats all fainter than 1/255): the reference then rasterises a frame
+ * in which nothing blends instead of returning get_empty_outputs (activesplatfacto_model.py:239-240).  Async. */
+int unerf_splat_count_intersects_batch(const int32_t* num_tiles_hit, const int32_t* radii, int B, int64_t N,
+                                       int32_t* cum_tiles_hit, int32_t* summary, void* workspace, int64_t workspace_bytes,
+                                       void* stream);
+
+/* unerf_splat_bin_sort for a batch.  isects_host: the B per-view totals of the summary (HOST int64).  gaussian_ids_sorted
+ * [sum of isects_host] holds ids v N + i, view after view, each view in its single-view order; tile_bins [B, tiles, 2] of view
+ * v index that whole array.  Serves at most UNERF_SPLAT_BATCH_MAX_TILES tiles (the staged tile sort's
+ * LDS tables); gsplat's 64-bit isect ids are not produced. */
+int unerf_splat_bin_sort_batch(const float* xys, const float* depths, const int32_t* radii, const int32_t* cum_tiles_hit,
+                               int B, int64_t N, const int64_t* isects_host, int H, int W, int block_width,
+                               const float* tight_conics, const float* tight_opacities, int32_t* gaussian_ids_sorted,
+                               int32_t* tile_bins, void* workspace, int64_t workspace_bytes, void* stream);
+
+/* unerf_splat_rasterize for a batch (grid: tiles x B): tile_bins [B,tiles,2] and ids of unerf_splat_bin_sort_batch; xys,
+ * conics, colors, opacities [B,N,...]; background [C] shared; stop_idx / out_img / final_T / final_idx [B,H,W,...];
+ * chan_max [B]: each view's own maximum (the reference normalises every image by its own max()). */
+int unerf_splat_rasterize_batch(const int32_t* gaussian_ids_sorted, const int32_t* tile_bins, const float* xys,
+                                const float* conics, const float* colors, const float* opacities, const float* background,
+                                int B, int C, int H, int W, int block_width, const int32_t* stop_idx, int flags,
+                                int max_channel, float* chan_max, float* out_img, float* final_T, int32_t* final_idx,
+                                void* stream);
+
+/* unerf_splat_normalize_outputs for a batch: img [B,HW,stride], final_T [B,HW], scratch_max [B], outputs [B,HW,...]. */
+int unerf_splat_normalize_outputs_batch(float* img, int stride, int ch, const float* final_T, int B, int64_t HW,
+                                        const float* scratch_max, float* rgb_out, float* acc_out, int sq_ch, float* sq_out,
+                                        float* sqrt_out, void* stream);
+
+/* unerf_splat_depth_sqdiff for a batch: xys [B,N,2], depths [B,N], depth_img [B,H,W,stride], sq_diff_out [B,N]. */
+int unerf_splat_depth_sqdiff_batch(const float* xys, const float* depths, const float* depth_img, int stride, int ch, int B,
+                                   int H, int W, int64_t N, float* sq_diff_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -16,13 +16,23 @@ static inline unsigned blocks_for(int64_t n, int per_block) { return (unsigned)(
 // ======================================================================================
 // projection
 // ======================================================================================
+// one camera of a projection: world-to-camera rows and the intrinsics
+struct ProjCam {
+    float V[12];
+    float fx, fy, cx, cy;
+};
+// NV: camera records the launch carries -- 1 for the single-view entry points (their kernel arguments stay as small as
+// before), UNERF_SPLAT_MAX_VIEWS for unerf_splat_project_batch
+template <int NV>
 struct ProjArgs {
     const float* means;
     const float* scales;
     float glob_scale;
     const float* quats;
-    float V[12];
-    float fx, fy, cx, cy;
+    // the views of the launch (1: unerf_splat_project*; up to UNERF_SPLAT_MAX_VIEWS: unerf_splat_project_batch).  Every output
+    // is [nv, N, ...]: view v's rows start at v N
+    int nv;
+    ProjCam cam[NV];
     int H, W, bw;
     float clip;
     int64_t N;
@@ -128,10 +138,25 @@ __device__ __forceinline__ int tight_count(const TightSplat& t, int bw, int x0, 
 // RAW: `scales` / `quats` are the model's parameters as stored -- log-scales and unnormalised quaternions -- and the
 // reference's per-frame torch prologue (activesplatfacto_model.py:221-223: torch.exp(scales_crop),
 // quats_crop / quats_crop.norm(dim=-1, keepdim=True)) happens here instead of in three elementwise launches.
-template <bool RAW>
-__global__ __launch_bounds__(256) void project_kernel(ProjArgs a) {
+// MULTI (unerf_splat_project_batch): the splat's parameters are read ONCE, before the loop over the launch's views; without it
+// (one view) they are read where the single-view kernel always read them -- the quaternion and scales behind the near-plane
+// test, so a culled splat costs only its mean.
+template <bool RAW, bool MULTI = false>
+__global__ __launch_bounds__(256) void project_kernel(ProjArgs<MULTI ? UNERF_SPLAT_MAX_VIEWS : 1> a) {
     int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= a.N) return;
+    const float p0 = a.means[i * 3], p1 = a.means[i * 3 + 1], p2 = a.means[i * 3 + 2];
+    float q4[4], s3[3];
+    auto load_shape = [&]() {
+        q4[0] = a.quats[i * 4]; q4[1] = a.quats[i * 4 + 1]; q4[2] = a.quats[i * 4 + 2]; q4[3] = a.quats[i * 4 + 3];
+        s3[0] = a.scales[i * 3]; s3[1] = a.scales[i * 3 + 1]; s3[2] = a.scales[i * 3 + 2];
+    };
+    if (MULTI) load_shape();
+    const float opl = (MULTI && a.opl) ? a.opl[i] : 0.f;
+    const int nv = MULTI ? a.nv : 1;
+    for (int v = 0; v < nv; ++v) {
+    const ProjCam& cam = a.cam[v];
+    const int64_t o = (int64_t)v * a.N + i;
     // gsplat allocates every output zero-filled and a culled splat keeps the zeros of whatever it had not reached yet.  Every
     // output is held in a register (zero until computed) and stored ONCE at the end -- zero-filling the 15 dwords first and
     // overwriting them for visible splats wrote the arrays twice (WRITE_SIZE 119 MB for 60 MB of outputs).
@@ -139,19 +164,19 @@ __global__ __launch_bounds__(256) void project_kernel(ProjArgs a) {
     int o_radius = 0, o_tiles = 0;
     float opac = 0.f, o_opac = 0.f;
     if (a.opl) {   // uniform.  sigmoid(opacities) (:256); "antialiased" multiplies the compensation in below (:252-254)
-        opac = unerf_sigmoid(a.opl[i]);
+        opac = unerf_sigmoid(MULTI ? opl : a.opl[i]);
         o_opac = a.antialiased ? 0.f : opac;
     }
     auto per_splat = [&]() {
-    const float p0 = a.means[i * 3], p1 = a.means[i * 3 + 1], p2 = a.means[i * 3 + 2];
-    const float* V = a.V;
+    const float* V = cam.V;
     float tx = ((V[0] * p0 + V[1] * p1) + V[2] * p2) + V[3];
     float ty = ((V[4] * p0 + V[5] * p1) + V[6] * p2) + V[7];
     float tz = ((V[8] * p0 + V[9] * p1) + V[10] * p2) + V[11];
     if (tz <= a.clip) return;      // (leaves the lambda: the stores are below)
 
     // scale_rot_to_cov3d
-    float qw = a.quats[i * 4], qx = a.quats[i * 4 + 1], qy = a.quats[i * 4 + 2], qz = a.quats[i * 4 + 3];
+    if (!MULTI) load_shape();
+    float qw = q4[0], qx = q4[1], qy = q4[2], qz = q4[3];
     if (RAW) {   // the model's normalisation (a true division, as torch's), then gsplat's own below
         const float qn = sqrtf(((qw * qw + qx * qx) + qy * qy) + qz * qz);
         qw = qw / qn; qx = qx / qn; qy = qy / qn; qz = qz / qn;
@@ -161,7 +186,7 @@ __global__ __launch_bounds__(256) void project_kernel(ProjArgs a) {
     float Rm[9] = {1.f - 2.f * (y * y + z * z), 2.f * (x * y - w * z),       2.f * (x * z + w * y),
                    2.f * (x * y + w * z),       1.f - 2.f * (x * x + z * z), 2.f * (y * z - w * x),
                    2.f * (x * z - w * y),       2.f * (y * z + w * x),       1.f - 2.f * (x * x + y * y)};
-    float sc0 = a.scales[i * 3], sc1 = a.scales[i * 3 + 1], sc2 = a.scales[i * 3 + 2];
+    float sc0 = s3[0], sc1 = s3[1], sc2 = s3[2];
     if (RAW) { sc0 = expf(sc0); sc1 = expf(sc1); sc2 = expf(sc2); }
     float s0 = a.glob_scale * sc0, s1 = a.glob_scale * sc1, s2 = a.glob_scale * sc2;
     float M[9];
@@ -180,14 +205,13 @@ __global__ __launch_bounds__(256) void project_kernel(ProjArgs a) {
     o_cov[0] = Sg[0]; o_cov[1] = Sg[1]; o_cov[2] = Sg[2]; o_cov[3] = Sg[4]; o_cov[4] = Sg[5]; o_cov[5] = Sg[8];
     // symmetric V from the 6 stored entries (as gsplat rebuilds it)
     float C3[9] = {Sg[0], Sg[1], Sg[2], Sg[1], Sg[4], Sg[5], Sg[2], Sg[5], Sg[8]};
-
     // project_cov3d_ewa
-    float tan_fovx = 0.5f * (float)a.W / a.fx, tan_fovy = 0.5f * (float)a.H / a.fy;
+    float tan_fovx = 0.5f * (float)a.W / cam.fx, tan_fovy = 0.5f * (float)a.H / cam.fy;
     float lim_x = 1.3f * tan_fovx, lim_y = 1.3f * tan_fovy;
     float ex = tz * fminf(lim_x, fmaxf(-lim_x, tx / tz));
     float ey = tz * fminf(lim_y, fmaxf(-lim_y, ty / tz));
     float rz = 1.f / tz, rz2 = rz * rz;
-    float J00 = a.fx * rz, J02 = (-a.fx * ex) * rz2, J11 = a.fy * rz, J12 = (-a.fy * ey) * rz2;
+    float J00 = cam.fx * rz, J02 = (-cam.fx * ex) * rz2, J11 = cam.fy * rz, J12 = (-cam.fy * ey) * rz2;
     float T0[3], T1[3];
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
@@ -219,10 +243,10 @@ __global__ __launch_bounds__(256) void project_kernel(ProjArgs a) {
     float radius = ceilf(3.f * sqrtf(fmaxf(v1, v2)));
     // project_pix
     float rw = 1.f / (tz + 1e-6f);
-    float u = (tx * rw) * a.fx + a.cx, v = (ty * rw) * a.fy + a.cy;
+    float u = (tx * rw) * cam.fx + cam.cx, vv = (ty * rw) * cam.fy + cam.cy;
     int tbx = (a.W + a.bw - 1) / a.bw, tby = (a.H + a.bw - 1) / a.bw;
     int x0, y0, x1, y1;
-    tile_bbox(u, v, radius, a.bw, tbx, tby, x0, y0, x1, y1);
+    tile_bbox(u, vv, radius, a.bw, tbx, tby, x0, y0, x1, y1);
     int area = (x1 - x0) * (y1 - y0);
     if (area <= 0) return;
     if (a.opl) {
@@ -230,27 +254,30 @@ __global__ __launch_bounds__(256) void project_kernel(ProjArgs a) {
             opac = opac * comp;
             o_opac = opac;
         }
-        area = tight_count(tight_splat(u, v, opac, cc * inv_det, -cb * inv_det, ca * inv_det), a.bw, x0, y0, x1, y1);
+        area = tight_count(tight_splat(u, vv, opac, cc * inv_det, -cb * inv_det, ca * inv_det), a.bw, x0, y0, x1, y1);
     }
     o_tiles = area;
     o_depth = tz;
     o_radius = (int)radius;
     o_xy[0] = u;
-    o_xy[1] = v;
+    o_xy[1] = vv;
     o_comp = comp;
     };
     per_splat();
-    a.radii[i] = o_radius;
-    a.tiles[i] = o_tiles;
-    a.xys[i * 2] = o_xy[0];
-    a.xys[i * 2 + 1] = o_xy[1];
-    a.depths[i] = o_depth;
-    a.comp[i] = o_comp;
+    a.radii[o] = o_radius;
+    a.tiles[o] = o_tiles;
+    a.xys[o * 2] = o_xy[0];
+    a.xys[o * 2 + 1] = o_xy[1];
+    a.depths[o] = o_depth;
+    a.comp[o] = o_comp;
 #pragma unroll
-    for (int c = 0; c < 3; ++c) a.conics[i * 3 + c] = o_conic[c];
+    for (int c = 0; c < 3; ++c) a.conics[o * 3 + c] = o_conic[c];
+    if (a.cov3d) {   // uniform (unerf_splat_project_batch: may be NULL)
 #pragma unroll
-    for (int c = 0; c < 6; ++c) a.cov3d[i * 6 + c] = o_cov[c];
-    if (a.opl) a.opac_out[i] = o_opac;
+        for (int c = 0; c < 6; ++c) a.cov3d[o * 6 + c] = o_cov[c];
+    }
+    if (a.opl) a.opac_out[o] = o_opac;
+    }
 }
 
 static int splat_project_impl(bool raw, const float* opacity_logits, int antialiased, float* opacities_out,
@@ -264,10 +291,12 @@ static int splat_project_impl(bool raw, const float* opacity_logits, int antiali
                   "splat_project: null pointer");
     UNERF_REQUIRE(H > 0 && W > 0 && block_width > 0 && block_width <= 16 && N >= 0, "splat_project: bad H/W/block/N");
     if (N == 0) return UNERF_OK;
-    ProjArgs a;
+    ProjArgs<1> a;
     a.means = means3d; a.scales = scales; a.glob_scale = glob_scale; a.quats = quats;
-    for (int k = 0; k < 12; ++k) a.V[k] = viewmat[k];
-    a.fx = fx; a.fy = fy; a.cx = cx; a.cy = cy; a.H = H; a.W = W; a.bw = block_width; a.clip = clip_thresh; a.N = N;
+    a.nv = 1;
+    for (int k = 0; k < 12; ++k) a.cam[0].V[k] = viewmat[k];
+    a.cam[0].fx = fx; a.cam[0].fy = fy; a.cam[0].cx = cx; a.cam[0].cy = cy;
+    a.H = H; a.W = W; a.bw = block_width; a.clip = clip_thresh; a.N = N;
     a.xys = xys; a.depths = depths; a.radii = radii; a.conics = conics; a.comp = compensation;
     a.tiles = num_tiles_hit; a.cov3d = cov3d;
     a.opl = opacity_logits; a.opac_out = opacities_out; a.antialiased = antialiased;
@@ -296,6 +325,42 @@ extern "C" int unerf_splat_project_raw(const float* means3d, const float* log_sc
                               clip_thresh, N, xys, depths, radii, conics, compensation, num_tiles_hit, cov3d, stream);
 }
 
+// view records (unerf.h: UNERF_SPLAT_VIEW_FLOATS floats per view) -> the launch's cameras
+static void proj_cams(ProjArgs<UNERF_SPLAT_MAX_VIEWS>& a, const float* views, int B) {
+    a.nv = B;
+    for (int v = 0; v < B; ++v) {
+        const float* r = views + (size_t)v * UNERF_SPLAT_VIEW_FLOATS;
+        for (int k = 0; k < 12; ++k) a.cam[v].V[k] = r[k];
+        a.cam[v].fx = r[12]; a.cam[v].fy = r[13]; a.cam[v].cx = r[14]; a.cam[v].cy = r[15];
+    }
+}
+
+extern "C" int unerf_splat_project_batch(const float* means3d, const float* log_scales, float glob_scale, const float* raw_quats,
+                                         const float* views_host, int B, int H, int W, int block_width, float clip_thresh,
+                                         int64_t N, const float* opacity_logits, int antialiased, float* opacities_out,
+                                         float* xys, float* depths, int32_t* radii, float* conics, float* compensation,
+                                         int32_t* num_tiles_hit, float* cov3d, void* stream) {
+    UNERF_REQUIRE(views_host, "splat_project_batch: null pointer (views_host)");
+    UNERF_REQUIRE(B >= 1 && B <= UNERF_SPLAT_MAX_VIEWS, "splat_project_batch: B=%d outside [1,%d]", B, UNERF_SPLAT_MAX_VIEWS);
+    UNERF_REQUIRE(N >= 0 && (int64_t)B * N < UNERF_SPLAT_MAX_BATCH_SPLATS, "splat_project_batch: B*N = %lld outside [0,2^29)",
+                  (long long)B * (long long)N);
+    UNERF_REQUIRE(N == 0 || (means3d && log_scales && raw_quats && xys && depths && radii && conics && compensation &&
+                             num_tiles_hit),
+                  "splat_project_batch: null pointer");
+    UNERF_REQUIRE(!opacity_logits || opacities_out || N == 0, "splat_project_batch: opacity_logits without opacities_out");
+    UNERF_REQUIRE(H > 0 && W > 0 && block_width > 0 && block_width <= 16, "splat_project_batch: bad H/W/block");
+    if (N == 0) return UNERF_OK;
+    ProjArgs<UNERF_SPLAT_MAX_VIEWS> a;
+    a.means = means3d; a.scales = log_scales; a.glob_scale = glob_scale; a.quats = raw_quats;
+    proj_cams(a, views_host, B);
+    a.H = H; a.W = W; a.bw = block_width; a.clip = clip_thresh; a.N = N;
+    a.xys = xys; a.depths = depths; a.radii = radii; a.conics = conics; a.comp = compensation;
+    a.tiles = num_tiles_hit; a.cov3d = cov3d;
+    a.opl = opacity_logits; a.opac_out = opacities_out; a.antialiased = antialiased;
+    hipLaunchKernelGGL((project_kernel<true, true>), dim3(blocks_for(N, 256)), dim3(256), 0, (hipStream_t)stream, a);
+    return unerf_check_launch("splat_project_batch");
+}
+
 // ======================================================================================
 // SH colours (+0.5, clamp>=0) and beta = softplus(log_unc) + beta_min
 // ======================================================================================
@@ -312,13 +377,33 @@ struct ShadePack {
     float* opacities;              // [N] out
     int C;                         // row length: 4 = rgb + depth, 5 = rgb + beta + depth
 };
+// the camera positions of the launch's views: 1, or up to UNERF_SPLAT_MAX_VIEWS (unerf_splat_shade_inputs_batch, PACK only:
+// view v's rows, opacities, compensations and depths start at v N)
+template <int NV>
+struct ShadeCams {
+    int nv;
+    float pos[NV][3];
+};
+template <int NV>
+static ShadeCams<NV> shade_cams(const float* p, int nv, int stride) {
+    ShadeCams<NV> c;
+    c.nv = nv;
+    for (int v = 0; v < nv; ++v)
+        for (int k = 0; k < 3; ++k) c.pos[v][k] = p[(size_t)v * stride + k];
+    return c;
+}
 
 // STAGE (SPLIT rows, degree 3, 16-byte aligned features_rest): the workgroup's 256 rows of 180 B are one contiguous 46-KB
 // block -- it is read with coalesced 16-byte loads into LDS and every thread takes its 45 floats from there (stride 45
 // words: conflict-free), instead of 12 loads per thread that touch 64 cache lines each (87 us for 208 MB: 2.4 TB/s).
-template <bool SPLIT, bool PACK, bool STAGE = false>
-__global__ __launch_bounds__(256) void sh_colors_kernel(int degree, const float* __restrict__ means, float cxp,
-                                                        float cyp, float czp, const float* __restrict__ coeffs,
+// MULTI (unerf_splat_shade_inputs_batch): the view loop runs over cams.nv views; without it over view 0 only -- the same
+// instruction stream and registers as before the loop existed (the loop kept live across views costs the single-view
+// kernel 11 VGPRs and two waves per SIMD).
+// (waves per SIMD: the single-view kernels' as they were before the view loop existed)
+template <bool SPLIT, bool PACK, bool STAGE = false, bool MULTI = false>
+__global__ __launch_bounds__(256, MULTI ? 1 : STAGE ? 3 : (SPLIT && !PACK) ? 6 : 7) void sh_colors_kernel(int degree, const float* __restrict__ means,
+                                                        ShadeCams<MULTI ? UNERF_SPLAT_MAX_VIEWS : 1> cams,
+                                                        const float* __restrict__ coeffs,
                                                         const float* __restrict__ rest,
                                                         const float* __restrict__ log_unc, float beta_min, int64_t N,
                                                         float* __restrict__ colors, float* __restrict__ beta,
@@ -372,11 +457,25 @@ __global__ __launch_bounds__(256) void sh_colors_kernel(int degree, const float*
             k[4 * q] = v.x; k[4 * q + 1] = v.y; k[4 * q + 2] = v.z; k[4 * q + 3] = v.w;
         }
     }
+    // Every per-splat input is read once; each view of the launch gets its own view directions, colours and rows.  MULTI
+    // loads the mean, log-uncertainty and opacity logit here, in front of the view loop; one view keeps the single-view
+    // kernel's loads where they always were (its registers and occupancy are unchanged).
+    float mp[3] = {0.f, 0.f, 0.f}, lu = 0.f, ol = 0.f;
+    if (MULTI) {
+        if (degree >= 1) { mp[0] = means[i * 3]; mp[1] = means[i * 3 + 1]; mp[2] = means[i * 3 + 2]; }
+        if (PACK && pk.C == 5) lu = log_unc[i];
+        if (PACK && pk.opacity_logits) ol = pk.opacity_logits[i];
+    }
+    const int nv = MULTI ? cams.nv : 1;
+    for (int vw = 0; vw < nv; ++vw) {
+    const float cxp = cams.pos[vw][0], cyp = cams.pos[vw][1], czp = cams.pos[vw][2];
+    const int64_t iv = (int64_t)vw * N + i;
     float col[3];
 #pragma unroll
     for (int c = 0; c < 3; ++c) col[c] = C0 * k[c];
     if (degree >= 1) {
-        float vx = means[i * 3] - cxp, vy = means[i * 3 + 1] - cyp, vz = means[i * 3 + 2] - czp;
+        float vx = (MULTI ? mp[0] : means[i * 3]) - cxp, vy = (MULTI ? mp[1] : means[i * 3 + 1]) - cyp,
+              vz = (MULTI ? mp[2] : means[i * 3 + 2]) - czp;
         float nrm = sqrtf((vx * vx + vy * vy) + vz * vz);
         float x = vx / nrm, y = vy / nrm, z = vz / nrm;
         float xx = x * x, xy = x * y, xz = x * z, yy = y * y, yz = y * z, zz = z * z;
@@ -397,7 +496,7 @@ __global__ __launch_bounds__(256) void sh_colors_kernel(int degree, const float*
             }
         }
     }
-    const int64_t row = PACK ? i * pk.C : i * 3;
+    const int64_t row = PACK ? iv * pk.C : i * 3;
     if (degree < 0) {  // config.sh_degree == 0: rgbs = sigmoid(features_dc) (activesplatfacto_model.py:247-248)
 #pragma unroll
         for (int c = 0; c < 3; ++c) colors[row + c] = unerf_sigmoid(k[c]);
@@ -406,14 +505,15 @@ __global__ __launch_bounds__(256) void sh_colors_kernel(int degree, const float*
         for (int c = 0; c < 3; ++c) colors[row + c] = fmaxf(col[c] + 0.5f, 0.f);
     }
     if (PACK) {
-        if (pk.C == 5) colors[row + 3] = unerf_softplus(log_unc[i]) + beta_min;
-        colors[row + pk.C - 1] = pk.depths[i];
+        if (pk.C == 5) colors[row + 3] = unerf_softplus(MULTI ? lu : log_unc[i]) + beta_min;
+        colors[row + pk.C - 1] = pk.depths[iv];
         if (pk.opacity_logits) {   // uniform
-            const float o = unerf_sigmoid(pk.opacity_logits[i]);
-            pk.opacities[i] = pk.compensation ? o * pk.compensation[i] : o;
+            const float o = unerf_sigmoid(MULTI ? ol : pk.opacity_logits[i]);
+            pk.opacities[iv] = pk.compensation ? o * pk.compensation[iv] : o;
         }
     } else if (beta) {
         beta[i] = unerf_softplus(log_unc[i]) + beta_min;
+    }
     }
 }
 
@@ -426,7 +526,7 @@ extern "C" int unerf_splat_sh_colors(int degree, const float* means3d, const flo
     UNERF_REQUIRE(((uintptr_t)sh_coeffs & 15u) == 0, "splat_sh_colors: sh_coeffs must be 16-byte aligned");
     if (N <= 0) return UNERF_OK;
     hipLaunchKernelGGL((sh_colors_kernel<false, false>), dim3(blocks_for(N, 256)), dim3(256), 0, (hipStream_t)stream,
-                       degree, means3d, cam_pos[0], cam_pos[1], cam_pos[2], sh_coeffs, nullptr, log_unc, beta_min, N,
+                       degree, means3d, shade_cams<1>(cam_pos, 1, 3), sh_coeffs, nullptr, log_unc, beta_min, N,
                        colors_out, beta_out, ShadePack{});
     return unerf_check_launch("splat_sh_colors");
 }
@@ -440,7 +540,7 @@ extern "C" int unerf_splat_sh_colors_split(int degree, const float* means3d, con
     UNERF_REQUIRE(!beta_out || log_unc || N <= 0, "splat_sh_colors_split: beta_out without log_unc");
     if (N <= 0) return UNERF_OK;
     hipLaunchKernelGGL((sh_colors_kernel<true, false>), dim3(blocks_for(N, 256)), dim3(256), 0, (hipStream_t)stream,
-                       degree, means3d, cam_pos[0], cam_pos[1], cam_pos[2], features_dc, features_rest, log_unc, beta_min,
+                       degree, means3d, shade_cams<1>(cam_pos, 1, 3), features_dc, features_rest, log_unc, beta_min,
                        N, colors_out, beta_out, ShadePack{});
     return unerf_check_launch("splat_sh_colors_split");
 }
@@ -461,14 +561,44 @@ extern "C" int unerf_splat_shade_inputs(int degree, const float* means3d, const 
     pk.C = C;
     if (degree >= 3 && ((uintptr_t)features_rest & 15u) == 0) {      // rows staged through LDS (see sh_colors_kernel)
         hipLaunchKernelGGL((sh_colors_kernel<true, true, true>), dim3(blocks_for(N, 256)), dim3(256), 0, (hipStream_t)stream, degree,
-                           means3d, cam_pos[0], cam_pos[1], cam_pos[2], features_dc, features_rest, log_unc, beta_min, N,
+                           means3d, shade_cams<1>(cam_pos, 1, 3), features_dc, features_rest, log_unc, beta_min, N,
                            rows_out, nullptr, pk);
     } else {
         hipLaunchKernelGGL((sh_colors_kernel<true, true>), dim3(blocks_for(N, 256)), dim3(256), 0, (hipStream_t)stream, degree,
-                           means3d, cam_pos[0], cam_pos[1], cam_pos[2], features_dc, features_rest, log_unc, beta_min, N,
+                           means3d, shade_cams<1>(cam_pos, 1, 3), features_dc, features_rest, log_unc, beta_min, N,
                            rows_out, nullptr, pk);
     }
     return unerf_check_launch("splat_shade_inputs");
+}
+
+extern "C" int unerf_splat_shade_inputs_batch(int degree, const float* means3d, const float* views_host, int B,
+                                              const float* features_dc, const float* features_rest, const float* log_unc,
+                                              float beta_min, const float* opacity_logits, const float* compensation,
+                                              const float* depths, int64_t N, int C, float* rows_out, float* opacities_out,
+                                              void* stream) {
+    UNERF_REQUIRE(views_host, "splat_shade_inputs_batch: null pointer (views_host)");
+    UNERF_REQUIRE(B >= 1 && B <= UNERF_SPLAT_MAX_VIEWS, "splat_shade_inputs_batch: B=%d outside [1,%d]", B, UNERF_SPLAT_MAX_VIEWS);
+    UNERF_REQUIRE(N >= 0 && (int64_t)B * N < UNERF_SPLAT_MAX_BATCH_SPLATS, "splat_shade_inputs_batch: B*N = %lld outside [0,2^29)",
+                  (long long)B * (long long)N);
+    UNERF_REQUIRE(N == 0 || (means3d && features_dc && depths && rows_out), "splat_shade_inputs_batch: null pointer");
+    UNERF_REQUIRE(!opacity_logits || opacities_out || N == 0, "splat_shade_inputs_batch: opacity_logits without opacities_out");
+    UNERF_REQUIRE(degree >= -1 && degree <= 3, "splat_shade_inputs_batch: degree %d outside [-1,3]", degree);
+    UNERF_REQUIRE(degree <= 0 || N == 0 || features_rest, "splat_shade_inputs_batch: degree %d needs features_rest", degree);
+    UNERF_REQUIRE(C == 4 || C == 5, "splat_shade_inputs_batch: C=%d, rows are [rgb, depth] (4) or [rgb, beta, depth] (5)", C);
+    UNERF_REQUIRE(C == 4 || log_unc || N == 0, "splat_shade_inputs_batch: C=5 needs log_unc");
+    if (N == 0) return UNERF_OK;
+    ShadePack pk;
+    pk.opacity_logits = opacity_logits; pk.compensation = compensation; pk.depths = depths; pk.opacities = opacities_out;
+    pk.C = C;
+    const ShadeCams<UNERF_SPLAT_MAX_VIEWS> cams = shade_cams<UNERF_SPLAT_MAX_VIEWS>(views_host + 16, B, UNERF_SPLAT_VIEW_FLOATS);
+    if (degree >= 3 && ((uintptr_t)features_rest & 15u) == 0) {
+        hipLaunchKernelGGL((sh_colors_kernel<true, true, true, true>), dim3(blocks_for(N, 256)), dim3(256), 0, (hipStream_t)stream, degree,
+                           means3d, cams, features_dc, features_rest, log_unc, beta_min, N, rows_out, nullptr, pk);
+    } else {
+        hipLaunchKernelGGL((sh_colors_kernel<true, true, false, true>), dim3(blocks_for(N, 256)), dim3(256), 0, (hipStream_t)stream, degree,
+                           means3d, cams, features_dc, features_rest, log_unc, beta_min, N, rows_out, nullptr, pk);
+    }
+    return unerf_check_launch("splat_shade_inputs_batch");
 }
 
 // ======================================================================================
@@ -478,7 +608,7 @@ static inline int64_t align256(int64_t x) { return (x + 255) & ~(int64_t)255; }
 #define SCAN_BLOCK 1024    // own_inclusive_scan: elements per workgroup
 #define SCAN_DIRECT_BLOCKS 4096   // up to this many blocks (4 M elements) every block re-sums the earlier blocks' sums itself
 #define TS_SEG 32          // one-pass tile sort (below): the prefix over chunks runs in 32 independent row segments
-#define TS_MAX_T1 12000    // tiles + 1 sentinel: the whole-key counters + 16 waves' digit counters must fit 64 KB of LDS (beyond: rocprim)
+#define TS_MAX_T1 (UNERF_SPLAT_BATCH_MAX_TILES + 1)    // 12,000 = tiles + 1 sentinel: the whole-key counters + 16 waves' digit counters must fit 64 KB of LDS (beyond: rocprim)
 struct TileSortPlan {
     int chunk, nblk, rows, T1;
 };
@@ -518,6 +648,44 @@ static RsTilePlan rs_tile_plan(int64_t I, int T1) {
     return p;
 }
 
+// Segments of a staged pass: segment g holds the chunks [cb[g], cb[g + 1]) and the pairs [pb[g], pb[g + 1]) of the stream, and
+// is sorted on its own (its digit prefixes, totals and output slots stay inside it).  One segment: a single view; a batch of
+// views: one segment per view, so every view's pairs leave in the order a single-view sort gives them.
+// S: segments the launch can carry -- 1 for the single-view sort (kernel arguments of the old size), UNERF_SPLAT_MAX_VIEWS for
+// unerf_splat_bin_sort_batch
+template <int S>
+struct RsSegs {
+    int n;
+    int cb[S + 1];
+    int64_t pb[S + 1];
+};
+static RsSegs<1> rs_one_seg(int nchunk, int64_t n) {
+    RsSegs<1> s;
+    s.n = 1; s.cb[0] = 0; s.cb[1] = nchunk; s.pb[0] = 0; s.pb[1] = n;
+    return s;
+}
+// the segment of chunk c (uniform) and the chunk's pairs [k0, k1).  SEG = false (one segment, chunks from pair 0): the
+// single-view kernels' own arithmetic, nothing looked up
+template <bool SEG, int S>
+__device__ __forceinline__ int rs_seg_of(const RsSegs<S>& s, int c) {
+    int g = 0;
+    if (SEG)
+        while (g + 1 < s.n && c >= s.cb[g + 1]) ++g;
+    return g;
+}
+template <bool SEG, int S>
+__device__ __forceinline__ void rs_chunk_range(const RsSegs<S>& s, int g, int c, int chunk, int64_t& k0, int64_t& k1) {
+    if (!SEG) {
+        k0 = (int64_t)c * chunk;
+        k1 = (k0 + chunk < s.pb[1]) ? k0 + chunk : s.pb[1];
+        return;
+    }
+    const int64_t e = s.pb[g + 1];
+    k0 = s.pb[g] + (int64_t)(c - s.cb[g]) * chunk;
+    if (k0 > e) k0 = e;
+    k1 = (k0 + chunk < e) ? k0 + chunk : e;
+}
+
 static int tile_bits(int H, int W, int bw) {   // bits of the largest key: tiles - 1, and `tiles` itself (the sentinel)
     int64_t tiles = (int64_t)((W + bw - 1) / bw) * ((H + bw - 1) / bw);
     int b = 1;
@@ -543,34 +711,41 @@ static hipError_t depth_sort_pairs(void* tmp, size_t& tmp_bytes, const uint32_t*
 struct SortWs {
     int64_t tmp, dkey_in, dkey_out, id_in, order, counts, cum, tkey_in, tkey_out, val_in, val_mid, ts_table, ts_segsum, ts_start, ds_table, ds_total, total;
 };
-static SortWs sort_ws_layout(int64_t N, int64_t I) {
+// batch (unerf_splat_*_batch, any B >= 1): N splats in each of B views, I pairs over all views.  Each view's chunks of the tile
+// passes are padded to a multiple of 16 (a whole-key histogram workgroup never straddles two views): at most 16 B chunks more
+// than the single-view plan, and as many whole-key rows more (rs_tile_tables_fit checks a batch's actual plan against this).
+static SortWs sort_ws_layout(int64_t N, int64_t I, int B = 1, bool batch = false) {
+    const int64_t NB = N * B;
     size_t scan_tmp = 0, sortN_tmp = 0, sortI_tmp = 0;
-    (void)hipcub::DeviceScan::InclusiveSum(nullptr, scan_tmp, (const int32_t*)nullptr, (int32_t*)nullptr, (int)N);
-    (void)depth_sort_pairs(nullptr, sortN_tmp, nullptr, nullptr, nullptr, nullptr, N, 0);
+    (void)hipcub::DeviceScan::InclusiveSum(nullptr, scan_tmp, (const int32_t*)nullptr, (int32_t*)nullptr, (int)NB);
+    (void)depth_sort_pairs(nullptr, sortN_tmp, nullptr, nullptr, nullptr, nullptr, NB, 0);
     if (I > 0)
         (void)hipcub::DeviceRadixSort::SortPairs(nullptr, sortI_tmp, (const uint32_t*)nullptr, (uint32_t*)nullptr,
                                                  (const int32_t*)nullptr, (int32_t*)nullptr, (int)I, 0, 32);
     (void)hipGetLastError();
     size_t tmp = scan_tmp > sortN_tmp ? scan_tmp : sortN_tmp;
     tmp = tmp > sortI_tmp ? tmp : sortI_tmp;
-    const size_t own_scan = (size_t)((N + SCAN_BLOCK - 1) / SCAN_BLOCK + 1) * 4;      // own_inclusive_scan's block sums
+    const size_t own_scan = (size_t)((NB + SCAN_BLOCK - 1) / SCAN_BLOCK + 1) * 4;      // own_inclusive_scan's block sums
     tmp = tmp > own_scan ? tmp : own_scan;
     SortWs w;
     int64_t off = 0;
     auto take = [&](int64_t bytes) { int64_t o = off; off += align256(bytes); return o; };
     w.tmp = take((int64_t)tmp);
-    w.dkey_in = take(N * 4); w.dkey_out = take(N * 4); w.id_in = take(N * 4); w.order = take(N * 4);
-    w.counts = take(N * 4); w.cum = take(N * 4);
+    w.dkey_in = take(NB * 4); w.dkey_out = take(NB * 4); w.id_in = take(NB * 4); w.order = take(NB * 4);
+    w.counts = take(NB * 4); w.cum = take(NB * 4);
     w.tkey_in = take(I * 4); w.tkey_out = take(I * 4); w.val_in = take(I * 4); w.val_mid = take(I * 4);
     // the one-pass tile sort's tables, sized for the largest tile count it serves (the image size is not known here)
     const TileSortPlan tp = tile_sort_plan(I, TS_MAX_T1 - 1);
     const RsTilePlan lp = rs_tile_plan(I, TS_MAX_T1);     // the two-pass sort's tables: 2 x [128][nchunk] + [nhw][T1]
-    const int64_t onepass_bytes = (int64_t)tp.rows * TS_MAX_T1 * 4, lsd_bytes = ((int64_t)256 * lp.nchunk + (int64_t)lp.nhw * TS_MAX_T1) * 4;
+    const int64_t nchunk = lp.nchunk + (batch ? 16 * B : 0), nhw = batch ? nchunk / 16 + B : lp.nhw;
+    const int64_t onepass_bytes = (int64_t)tp.rows * TS_MAX_T1 * 4, lsd_bytes = ((int64_t)256 * nchunk + nhw * TS_MAX_T1) * 4;
     w.ts_table = take(onepass_bytes > lsd_bytes ? onepass_bytes : lsd_bytes);
-    w.ts_segsum = take((int64_t)TS_SEG * TS_MAX_T1 * 4);
-    w.ts_start = take((int64_t)(2 * TS_MAX_T1 + 2) * 4);     // start [T1 + 1] + total [T1]
-    w.ds_table = take((int64_t)256 * ((N + RS_M_DEPTH - 1) / RS_M_DEPTH) * 4);     // the depth sort's [256][chunks] counters
-    w.ds_total = take(256 * 4);
+    // one-pass: segsum [TS_SEG][T1]; two-pass: dtotal [2][B][256] + total [B][16][T1]
+    const int64_t segsum_words = (int64_t)TS_SEG * TS_MAX_T1, lsd_words = (int64_t)512 * B + (int64_t)16 * B * TS_MAX_T1;
+    w.ts_segsum = take((segsum_words > lsd_words ? segsum_words : lsd_words) * 4);
+    w.ts_start = take((int64_t)(TS_MAX_T1 + 1 + (int64_t)B * (TS_MAX_T1 + 1)) * 4);     // start [B][T1 + 1] + total [T1]
+    w.ds_table = take((int64_t)256 * B * ((N + RS_M_DEPTH - 1) / RS_M_DEPTH) * 4);     // the depth sort's [256][chunks] counters
+    w.ds_total = take((int64_t)256 * B * 4);
     w.total = off + 1024;
     return w;
 }
@@ -579,6 +754,14 @@ extern "C" int64_t unerf_splat_sort_workspace_bytes(int64_t N, int64_t I) {
     if (N < 1) N = 1;
     if (I < 0) I = 0;
     return sort_ws_layout(N, I).total;
+}
+
+extern "C" int64_t unerf_splat_sort_workspace_bytes_batch(int B, int64_t N, int64_t num_intersects) {
+    if (B < 1 || B > UNERF_SPLAT_MAX_VIEWS || N < 0 || num_intersects < 0 || num_intersects >= (1ll << 31) ||
+        (int64_t)B * N >= UNERF_SPLAT_MAX_BATCH_SPLATS)
+        return -1;
+    if (N < 1) N = 1;
+    return sort_ws_layout(N, num_intersects, B, true).total;
 }
 
 // ---- inclusive scan of N int32 in two launches -------------------------------------------------------------------------------
@@ -697,6 +880,46 @@ extern "C" int unerf_splat_count_intersects(const int32_t* num_tiles_hit, int64_
         return UNERF_ERR_HIP;
     }
     return unerf_check_launch("splat_count_intersects");
+}
+
+// The per-view numbers a batch's ONE host read-back carries: summary[v] = view v's intersections (the difference of the
+// inclusive scan over the B N tile counts at the view's ends), summary[B + v] = 1 when some splat of view v has a radius > 0.
+// That flag is known from the total when it is non-zero; otherwise (tight lists can be empty while splats are "visible"
+// by radius) the view's radii are searched, by the workgroups of grid.x, each OR-ing its finding in.  summary[B ..] is
+// zeroed by the caller.
+__global__ __launch_bounds__(256) void count_summary_kernel(const int32_t* __restrict__ cum, const int32_t* __restrict__ radii,
+                                                            int64_t N, int B, int32_t* __restrict__ summary) {
+    const int v = blockIdx.y;
+    const int64_t e = (int64_t)(v + 1) * N - 1;
+    const uint32_t tot = (uint32_t)cum[e] - (v > 0 ? (uint32_t)cum[e - N] : 0u);
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        summary[v] = (int32_t)tot;
+        if (tot != 0u || !radii) summary[B + v] = tot != 0u ? 1 : 0;
+    }
+    if (tot != 0u || !radii) return;     // (uniform)
+    const int32_t* r = radii + (int64_t)v * N;
+    int found = 0;
+    for (int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x; k < N; k += (int64_t)gridDim.x * 256) found |= r[k] > 0;
+    if (__syncthreads_or(found) && threadIdx.x == 0) atomicOr(&summary[B + v], 1);
+}
+
+extern "C" int unerf_splat_count_intersects_batch(const int32_t* num_tiles_hit, const int32_t* radii, int B, int64_t N,
+                                                  int32_t* cum_tiles_hit, int32_t* summary, void* workspace,
+                                                  int64_t workspace_bytes, void* stream) {
+    UNERF_REQUIRE(num_tiles_hit && cum_tiles_hit && summary && workspace, "splat_count_intersects_batch: null pointer");
+    UNERF_REQUIRE(B >= 1 && B <= UNERF_SPLAT_MAX_VIEWS, "splat_count_intersects_batch: B=%d outside [1,%d]", B,
+                  UNERF_SPLAT_MAX_VIEWS);
+    UNERF_REQUIRE(N >= 1 && (int64_t)B * N < UNERF_SPLAT_MAX_BATCH_SPLATS, "splat_count_intersects_batch: bad N (B*N = %lld)",
+                  (long long)B * (long long)N);
+    UNERF_REQUIRE(workspace_bytes >= (int64_t)blocks_for((int64_t)B * N, SCAN_BLOCK) * 4,
+                  "splat_count_intersects_batch: workspace %lld bytes too small", (long long)workspace_bytes);
+    hipStream_t st = (hipStream_t)stream;
+    own_inclusive_scan(num_tiles_hit, cum_tiles_hit, (int64_t)B * N, reinterpret_cast<int32_t*>(workspace), st);
+    if (hipMemsetAsync(summary + B, 0, (size_t)B * sizeof(int32_t), st) != hipSuccess)
+        return unerf_check_launch("splat_count_intersects_batch memset");
+    const unsigned gx = radii ? (blocks_for(N, 256) < 64u ? blocks_for(N, 256) : 64u) : 1u;
+    hipLaunchKernelGGL(count_summary_kernel, dim3(gx, B), dim3(256), 0, st, cum_tiles_hit, radii, N, B, summary);
+    return unerf_check_launch("splat_count_intersects_batch");
 }
 
 // depth key of every splat (culled ones last) + identity payload
@@ -906,11 +1129,18 @@ __global__ __launch_bounds__(256) void tile_segscan_kernel(uint32_t* __restrict_
 
 // one workgroup: the exclusive prefix of the tile totals over the tiles -> start[t] (start[T1] = all pairs), and the
 // tile_bins the rasteriser reads.  A tile's total is the sum of NSEG partial rows total[s][t] (1: already summed).
-template <int NSEG>
+// One workgroup per view of a batch (blockIdx.x; `base` = its pairs' first slot, read from base_of[view] when given): the
+// view's NSEG partial rows, starts and bins follow the previous view's.
+template <int NSEG, int S = 1>
 __global__ __launch_bounds__(1024) void tile_scan_kernel(const uint32_t* __restrict__ total, int T1, int tiles,
-                                                         uint32_t* __restrict__ start, int32_t* __restrict__ bins) {
+                                                         uint32_t* __restrict__ start, int32_t* __restrict__ bins,
+                                                         RsSegs<S> base_of) {
     extern __shared__ uint32_t s_tot[];      // [T1] tile totals, then [16] wave sums
     uint32_t* s_w = s_tot + T1;
+    const int g = blockIdx.x;
+    total += (size_t)g * NSEG * T1;
+    start += (size_t)g * (T1 + 1);
+    bins += (size_t)g * tiles * 2;
     for (int t = threadIdx.x; t < T1; t += 1024) {      // (coalesced over the tiles, segment by segment)
         uint32_t n = 0u;
 #pragma unroll
@@ -934,7 +1164,7 @@ __global__ __launch_bounds__(1024) void tile_scan_kernel(const uint32_t* __restr
     uint32_t before = 0u;
 #pragma unroll
     for (int w = 0; w < 16; ++w) before += w < wv ? s_w[w] : 0u;
-    uint32_t run = before + incl - mine;
+    uint32_t run = (uint32_t)base_of.pb[g] + before + incl - mine;
     for (int t = t0; t < t1; ++t) {
         const uint32_t n = s_tot[t];
         start[t] = run;
@@ -1056,8 +1286,8 @@ __device__ __forceinline__ void rs_wave_order() {
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
-template <typename TKey, bool FULL>
-__global__ __launch_bounds__(1024) void rs_hist_kernel(const TKey* __restrict__ keys, int64_t n, int chunk, int nchunk, uint32_t kmax,
+template <typename TKey, bool FULL, bool SEG = false>
+__global__ __launch_bounds__(1024) void rs_hist_kernel(const TKey* __restrict__ keys, RsSegs<SEG ? UNERF_SPLAT_MAX_VIEWS : 1> segs, int chunk, int nchunk, uint32_t kmax,
                                                       int shift, int B, int cpw, uint32_t* __restrict__ table, uint32_t* __restrict__ full) {
     extern __shared__ uint32_t s_rs[];       // [waves][256] digit counters, then FULL: [kmax + 1] whole-key counters of the workgroup
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, wpb = (int)(blockDim.x >> 6);
@@ -1074,14 +1304,22 @@ __global__ __launch_bounds__(1024) void rs_hist_kernel(const TKey* __restrict__ 
         if (c >= nchunk) break;                   // (uniform per wave)
 #pragma unroll
         for (int i = 0; i < 4; ++i) dig[lane + 64 * i] = 0u;
-        const int64_t k0 = (int64_t)c * chunk, k1 = (k0 + chunk < n) ? k0 + chunk : n;
-        const int64_t nvec = (k1 - k0) / PER;
-        const uint4* kv = reinterpret_cast<const uint4*>(keys + k0);      // chunks are multiples of 256 keys: aligned
+        int64_t k0, k1;
+        rs_chunk_range<SEG>(segs, rs_seg_of<SEG>(segs, c), c, chunk, k0, k1);
         auto count = [&](uint32_t key) {
             const uint32_t kq = key < kmax ? key : kmax;
             atomicAdd(&dig[(kq >> shift) & dmask], 1u);
             if (FULL) atomicAdd(&fh[kq], 1u);
         };
+        // a segment's first chunk starts where the view before it ended: the keys up to the next 16-byte boundary one by one
+        // (a single segment's chunks are multiples of 256 keys: none)
+        if (SEG) {
+            const int64_t ka = ((k0 + PER - 1) / PER) * PER < k1 ? ((k0 + PER - 1) / PER) * PER : k1;
+            for (int64_t k = k0 + lane; k < ka; k += 64) count((uint32_t)keys[k]);
+            k0 = ka;
+        }
+        const int64_t nvec = (k1 - k0) / PER;
+        const uint4* kv = reinterpret_cast<const uint4*>(keys + k0);
         for (int64_t v0 = 0; v0 < nvec; v0 += 256) {      // four 16-byte loads per lane in flight
             uint4 q[4];
 #pragma unroll
@@ -1118,22 +1356,31 @@ __global__ __launch_bounds__(1024) void rs_hist_kernel(const TKey* __restrict__ 
     }
 }
 
-// column sums of the whole-key histogram rows, by row segment: seg[s][t] = sum of rows [s rps, (s + 1) rps) of column t
-__global__ __launch_bounds__(256) void rs_colsum_kernel(const uint32_t* __restrict__ full, int rows, int rps, int T1,
+// column sums of the whole-key histogram rows, by row segment: seg[g][s][t] = sum of rows [r0 + s rps, r0 + (s + 1) rps) of
+// column t, where segment g (blockIdx.z) owns the histogram rows (16 chunks each) [cb[g] / 16, ceil(cb[g + 1] / 16))
+template <int S>
+__global__ __launch_bounds__(256) void rs_colsum_kernel(const uint32_t* __restrict__ full, RsSegs<S> segs, int T1,
                                                         uint32_t* __restrict__ seg) {
-    const int t = blockIdx.x * 256 + threadIdx.x, sg = blockIdx.y;
+    const int t = blockIdx.x * 256 + threadIdx.x, sg = blockIdx.y, g = blockIdx.z;
     if (t >= T1) return;
-    const int r0 = sg * rps, r1 = (r0 + rps < rows) ? r0 + rps : rows;
+    const int rlo = segs.cb[g] / 16, rows = (segs.cb[g + 1] + 15) / 16;
+    const int rps = (rows - rlo + 15) / 16;
+    const int r0 = rlo + sg * rps, r1 = (r0 + rps < rows) ? r0 + rps : rows;
     uint32_t sum = 0u;
 #pragma unroll 8
     for (int r = r0; r < r1; ++r) sum += full[(size_t)r * T1 + t];
-    seg[(size_t)sg * T1 + t] = sum;
+    seg[((size_t)g * 16 + sg) * T1 + t] = sum;
 }
 
 // one workgroup per digit: exclusive prefix of its row over the chunks (in place) and the digit's total
-__global__ __launch_bounds__(1024) void rs_rowscan_kernel(uint32_t* __restrict__ table, int nchunk, uint32_t* __restrict__ dtotal) {
+// (grid.y: the segments -- segment g scans its own chunks and leaves its totals in dtotal[g][256])
+template <int S>
+__global__ __launch_bounds__(1024) void rs_rowscan_kernel(uint32_t* __restrict__ table, int nchunk_all, RsSegs<S> segs,
+                                                          uint32_t* __restrict__ dtotal) {
     __shared__ uint32_t s_w[16];
-    uint32_t* row = table + (size_t)blockIdx.x * nchunk;
+    const int g = blockIdx.y;
+    uint32_t* row = table + (size_t)blockIdx.x * nchunk_all + segs.cb[g];
+    const int nchunk = segs.cb[g + 1] - segs.cb[g];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     uint32_t carry = 0u;
     for (int base = 0; base < nchunk; base += 1024) {
@@ -1158,7 +1405,7 @@ __global__ __launch_bounds__(1024) void rs_rowscan_kernel(uint32_t* __restrict__
         carry += all;
         __syncthreads();
     }
-    if (threadIdx.x == 0) dtotal[blockIdx.x] = carry;
+    if (threadIdx.x == 0) dtotal[(size_t)g * 256 + blockIdx.x] = carry;
 }
 
 // one wave per chunk of M pairs: rank, stage in LDS in digit order, write out digit run by digit run.  DMAX = digit values the
@@ -1173,8 +1420,9 @@ struct RsLds {
 };
 // COUNTS (the depth sort's last pass): also writes, in output order, how many tiles each splat hits -- num_tiles_hit recovered from
 // its inclusive scan, 0 for culled splats -- the gather a separate kernel used to make (21 us, waiting on three random reads per splat).
-template <typename TKey, int M, int DMAX, bool KEYS_OUT, bool COUNTS = false>
-__global__ __launch_bounds__(256) void rs_scatter_kernel(const TKey* __restrict__ keys, const int32_t* __restrict__ vals, int64_t n,
+template <typename TKey, int M, int DMAX, bool KEYS_OUT, bool COUNTS = false, bool SEG = false>
+__global__ __launch_bounds__(256) void rs_scatter_kernel(const TKey* __restrict__ keys, const int32_t* __restrict__ vals,
+                                                         RsSegs<SEG ? UNERF_SPLAT_MAX_VIEWS : 1> segs,
                                                          int nchunk, uint32_t kmax, int shift, int B,
                                                          const uint32_t* __restrict__ table, const uint32_t* __restrict__ dtotal,
                                                          TKey* __restrict__ keys_out, int32_t* __restrict__ vals_out,
@@ -1184,6 +1432,12 @@ __global__ __launch_bounds__(256) void rs_scatter_kernel(const TKey* __restrict_
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int c = (int)blockIdx.x * (int)(blockDim.x >> 6) + wv;      // (1 - 4 waves per workgroup: the launcher's choice)
     if (c >= nchunk) return;
+    const int sgi = rs_seg_of<SEG>(segs, c);
+    int64_t k0, k1;
+    rs_chunk_range<SEG>(segs, sgi, c, M, k0, k1);
+    if (SEG && k1 <= k0) return;             // (a padding chunk of a segment: no pairs)
+    const int cend = SEG ? segs.cb[sgi + 1] : nchunk;
+    if (SEG) dtotal += (size_t)sgi * 256;
     uint32_t* cur = s_rs + (size_t)wv * RsLds<M, DMAX, TKey>::WAVE_WORDS;
     uint32_t* delta = cur + DMAX;
     uint32_t* pw = delta + DMAX;             // [DMAX][2]
@@ -1202,7 +1456,7 @@ __global__ __launch_bounds__(256) void rs_scatter_kernel(const TKey* __restrict_
             if (d < B) {
                 tot[i] = dtotal[d];
                 pre[i] = table[(size_t)d * nchunk + c];
-                cnt[i] = (c + 1 < nchunk ? table[(size_t)d * nchunk + c + 1] : tot[i]) - pre[i];
+                cnt[i] = (c + 1 < cend ? table[(size_t)d * nchunk + c + 1] : tot[i]) - pre[i];
             }
             tsum += tot[i];
             csum += cnt[i];
@@ -1213,7 +1467,7 @@ __global__ __launch_bounds__(256) void rs_scatter_kernel(const TKey* __restrict_
             const uint32_t v0 = __shfl_up(ti, d, 64), v1 = __shfl_up(ci, d, 64);
             if (lane >= d) { ti += v0; ci += v1; }
         }
-        uint32_t gb = ti - tsum, lb = ci - csum;
+        uint32_t gb = (SEG ? (uint32_t)segs.pb[sgi] : 0u) + ti - tsum, lb = ci - csum;
 #pragma unroll
         for (int i = 0; i < DPL; ++i) {
             const int d = DPL * lane + i;
@@ -1226,8 +1480,7 @@ __global__ __launch_bounds__(256) void rs_scatter_kernel(const TKey* __restrict_
         }
         rs_wave_order();
     }
-    const int64_t k0 = (int64_t)c * M;
-    const int m = (int)((n - k0 < M) ? n - k0 : M);       // pairs of this chunk
+    const int m = (int)(k1 - k0);                         // pairs of this chunk
     // every pair of the chunk is requested before the first is ranked (2 registers per vector: the ranking below is a chain
     // of LDS round trips, a global load inside it would cost its whole latency once per vector)
     constexpr int NV = M / 64;
@@ -1328,8 +1581,9 @@ static int bin_sort_impl(const float* xys, const float* depths, const int32_t* r
         uint32_t* table0 = base;                                        // [B0][nchunk]
         uint32_t* table1 = table0 + (size_t)128 * rp.nchunk;            // [B1][nchunk]
         uint32_t* full = table1 + (size_t)128 * rp.nchunk;              // [nhw][T1]
-        uint32_t* dtotal = reinterpret_cast<uint32_t*>(ws + L.ts_segsum);      // [128] + [128]
-        uint32_t* total = dtotal + 256;                                 // [T1]
+        uint32_t* dtotal = reinterpret_cast<uint32_t*>(ws + L.ts_segsum);      // [256] + [256] (one segment)
+        uint32_t* total = dtotal + 512;                                 // [16][T1]
+        const RsSegs<1> one = rs_one_seg(rp.nchunk, I);
         uint32_t* start = reinterpret_cast<uint32_t*>(ws + L.ts_start);
         TKey* tk_mid = tk_out;
         int32_t* v_mid = reinterpret_cast<int32_t*>(ws + L.val_mid);
@@ -1339,29 +1593,28 @@ static int bin_sort_impl(const float* xys, const float* depths, const int32_t* r
         const int hgrid = (rp.nchunk + 3) / 4;      // digit-only histogram: one chunk per wave, four waves per workgroup
         const size_t lds_sc = swpb * (size_t)RsLds<RS_M_TILE, 128, TKey>::WAVE_WORDS * sizeof(uint32_t);
         if (rp.b0 == 0) {      // <= 128 keys: one pass
-            hipLaunchKernelGGL((rs_hist_kernel<TKey, true>), dim3(rp.nhw), dim3(1024), lds_full, st, tk_in, I, RS_M_TILE, rp.nchunk, kmax, 0,
+            hipLaunchKernelGGL((rs_hist_kernel<TKey, true>), dim3(rp.nhw), dim3(1024), lds_full, st, tk_in, one, RS_M_TILE, rp.nchunk, kmax, 0,
                                rp.B1, 1, table1, full);
-            hipLaunchKernelGGL(rs_rowscan_kernel, dim3(rp.B1), dim3(1024), 0, st, table1, rp.nchunk, dtotal + 128);
-            hipLaunchKernelGGL((rs_scatter_kernel<TKey, RS_M_TILE, 128, false>), dim3(sgrid), dim3(64 * swpb), lds_sc, st, tk_in, v_in, I, rp.nchunk, kmax,
-                               0, rp.B1, table1, dtotal + 128, (TKey*)nullptr, gaussian_ids_sorted);
+            hipLaunchKernelGGL(rs_rowscan_kernel<1>, dim3(rp.B1), dim3(1024), 0, st, table1, rp.nchunk, one, dtotal + 256);
+            hipLaunchKernelGGL((rs_scatter_kernel<TKey, RS_M_TILE, 128, false>), dim3(sgrid), dim3(64 * swpb), lds_sc, st, tk_in, v_in, one, rp.nchunk, kmax,
+                               0, rp.B1, table1, dtotal + 256, (TKey*)nullptr, gaussian_ids_sorted);
         } else {
-            hipLaunchKernelGGL((rs_hist_kernel<TKey, true>), dim3(rp.nhw), dim3(1024), lds_full, st, tk_in, I, RS_M_TILE, rp.nchunk, kmax, 0,
+            hipLaunchKernelGGL((rs_hist_kernel<TKey, true>), dim3(rp.nhw), dim3(1024), lds_full, st, tk_in, one, RS_M_TILE, rp.nchunk, kmax, 0,
                                rp.B0, 1, table0, full);
-            hipLaunchKernelGGL(rs_rowscan_kernel, dim3(rp.B0), dim3(1024), 0, st, table0, rp.nchunk, dtotal);
-            hipLaunchKernelGGL((rs_scatter_kernel<TKey, RS_M_TILE, 128, true>), dim3(sgrid), dim3(64 * swpb), lds_sc, st, tk_in, v_in, I, rp.nchunk, kmax,
+            hipLaunchKernelGGL(rs_rowscan_kernel<1>, dim3(rp.B0), dim3(1024), 0, st, table0, rp.nchunk, one, dtotal);
+            hipLaunchKernelGGL((rs_scatter_kernel<TKey, RS_M_TILE, 128, true>), dim3(sgrid), dim3(64 * swpb), lds_sc, st, tk_in, v_in, one, rp.nchunk, kmax,
                                0, rp.B0, table0, dtotal, tk_mid, v_mid);
-            hipLaunchKernelGGL((rs_hist_kernel<TKey, false>), dim3(hgrid), dim3(256), lds_dig, st, tk_mid, I, RS_M_TILE, rp.nchunk, kmax,
+            hipLaunchKernelGGL((rs_hist_kernel<TKey, false>), dim3(hgrid), dim3(256), lds_dig, st, tk_mid, one, RS_M_TILE, rp.nchunk, kmax,
                                rp.b0, rp.B1, 1, table1, (uint32_t*)nullptr);
-            hipLaunchKernelGGL(rs_rowscan_kernel, dim3(rp.B1), dim3(1024), 0, st, table1, rp.nchunk, dtotal + 128);
-            hipLaunchKernelGGL((rs_scatter_kernel<TKey, RS_M_TILE, 128, false>), dim3(sgrid), dim3(64 * swpb), lds_sc, st, tk_mid, v_mid, I, rp.nchunk,
-                               kmax, rp.b0, rp.B1, table1, dtotal + 128, (TKey*)nullptr, gaussian_ids_sorted);
+            hipLaunchKernelGGL(rs_rowscan_kernel<1>, dim3(rp.B1), dim3(1024), 0, st, table1, rp.nchunk, one, dtotal + 256);
+            hipLaunchKernelGGL((rs_scatter_kernel<TKey, RS_M_TILE, 128, false>), dim3(sgrid), dim3(64 * swpb), lds_sc, st, tk_mid, v_mid, one, rp.nchunk,
+                               kmax, rp.b0, rp.B1, table1, dtotal + 256, (TKey*)nullptr, gaussian_ids_sorted);
         }
         // tile totals (column sums of the whole-key histograms) -> tile starts and the tile_bins
-        {   // (16 row segments summed in parallel; tile_scan_kernel adds them up per tile)
-            const int rps = (rp.nhw + 15) / 16;
-            hipLaunchKernelGGL(rs_colsum_kernel, dim3(blocks_for(T1, 256), 16), dim3(256), 0, st, full, rp.nhw, rps, T1, total);
-        }
-        hipLaunchKernelGGL(tile_scan_kernel<16>, dim3(1), dim3(1024), ((size_t)T1 + 16) * sizeof(uint32_t), st, total, T1, tiles, start, tile_bins);
+        // (16 row segments summed in parallel; tile_scan_kernel adds them up per tile)
+        hipLaunchKernelGGL(rs_colsum_kernel<1>, dim3(blocks_for(T1, 256), 16, 1), dim3(256), 0, st, full, one, T1, total);
+        hipLaunchKernelGGL(tile_scan_kernel<16>, dim3(1), dim3(1024), ((size_t)T1 + 16) * sizeof(uint32_t), st, total, T1, tiles, start, tile_bins,
+                           one);
         if (isect_ids_sorted)
             hipLaunchKernelGGL(tile_isect_ids_kernel, dim3(blocks_for(I, 256)), dim3(256), 0, st, start, T1,
                                gaussian_ids_sorted, depths, I, isect_ids_sorted);
@@ -1378,7 +1631,8 @@ static int bin_sort_impl(const float* xys, const float* depths, const int32_t* r
         hipLaunchKernelGGL(tile_colsum_kernel, dim3(blocks_for(tp.T1, 256), TS_SEG), dim3(256), 0, st, table, rps, tp.T1, segsum);
         uint32_t* total = start + tp.T1 + 1;
         hipLaunchKernelGGL(tile_segscan_kernel, dim3(blocks_for(tp.T1, 256)), dim3(256), 0, st, segsum, tp.T1, total);
-        hipLaunchKernelGGL(tile_scan_kernel<1>, dim3(1), dim3(1024), ((size_t)tp.T1 + 16) * sizeof(uint32_t), st, total, tp.T1, tiles, start, tile_bins);
+        hipLaunchKernelGGL(tile_scan_kernel<1>, dim3(1), dim3(1024), ((size_t)tp.T1 + 16) * sizeof(uint32_t), st, total, tp.T1, tiles, start, tile_bins,
+                           rs_one_seg(tp.nblk, I));
         hipLaunchKernelGGL(tile_apply_kernel, dim3(blocks_for(tp.T1, 256), TS_SEG), dim3(256), 0, st, table, rps, tp.T1, segsum,
                            start);
         hipLaunchKernelGGL((tile_scatter_kernel<TKey>), dim3(UNERF_SPLAT_XCD ? ((tp.nblk + 7) / 8) * 8 : tp.nblk), dim3(64), lds, st,
@@ -1441,17 +1695,18 @@ extern "C" int unerf_splat_bin_sort(const float* xys, const float* depths, const
         uint32_t* dtotal = reinterpret_cast<uint32_t*>(ws + L.ds_total);
         const size_t lds_sc = 4 * (size_t)RsLds<RS_M_DEPTH, 256, uint32_t>::WAVE_WORDS * sizeof(uint32_t), lds_dig = 1024 * sizeof(uint32_t);
         hipLaunchKernelGGL(depth_keys_kernel, dim3(blocks_for(N, 256)), dim3(256), 0, st, depths, radii, N, dk_out, order);
+        const RsSegs<1> one = rs_one_seg(nchunk, N);
         uint32_t* kin = dk_out; uint32_t* kout = dk_in;
         int32_t* vin = order; int32_t* vout = id_in;
         for (int p = 0; p < 4; ++p) {      // (dk_out, order) -> (dk_in, id_in) -> (dk_out, order) -> (dk_in, id_in) -> order
-            hipLaunchKernelGGL((rs_hist_kernel<uint32_t, false>), dim3(hgrid), dim3(256), lds_dig, st, kin, N, RS_M_DEPTH, nchunk, 0xFFFFFFFFu,
+            hipLaunchKernelGGL((rs_hist_kernel<uint32_t, false>), dim3(hgrid), dim3(256), lds_dig, st, kin, one, RS_M_DEPTH, nchunk, 0xFFFFFFFFu,
                                8 * p, 256, 1, table, (uint32_t*)nullptr);
-            hipLaunchKernelGGL(rs_rowscan_kernel, dim3(256), dim3(1024), 0, st, table, nchunk, dtotal);
+            hipLaunchKernelGGL(rs_rowscan_kernel<1>, dim3(256), dim3(1024), 0, st, table, nchunk, one, dtotal);
             if (p < 3)
-                hipLaunchKernelGGL((rs_scatter_kernel<uint32_t, RS_M_DEPTH, 256, true>), dim3(grid), dim3(256), lds_sc, st, kin, vin, N, nchunk,
+                hipLaunchKernelGGL((rs_scatter_kernel<uint32_t, RS_M_DEPTH, 256, true>), dim3(grid), dim3(256), lds_sc, st, kin, vin, one, nchunk,
                                    0xFFFFFFFFu, 8 * p, 256, table, dtotal, kout, vout);
             else
-                hipLaunchKernelGGL((rs_scatter_kernel<uint32_t, RS_M_DEPTH, 256, false, true>), dim3(grid), dim3(256), lds_sc, st, kin, vin, N, nchunk,
+                hipLaunchKernelGGL((rs_scatter_kernel<uint32_t, RS_M_DEPTH, 256, false, true>), dim3(grid), dim3(256), lds_sc, st, kin, vin, one, nchunk,
                                    0xFFFFFFFFu, 8 * p, 256, table, dtotal, (uint32_t*)nullptr, order, radii, cum_tiles_hit, counts);
             uint32_t* tk = kin; kin = kout; kout = tk;
             int32_t* tv = vin; vin = vout; vout = tv;
@@ -1486,6 +1741,147 @@ extern "C" int unerf_splat_bin_sort(const float* xys, const float* depths, const
                                        own_sort, isect_ids_sorted, gaussian_ids_sorted, tile_bins, ws, L, tmp_bytes, st);
     return bin_sort_impl<uint32_t>(xys, depths, radii, order, cum_sorted, tight_conics, tight_opacities, N, I, block_width, tbx, tby, bits,
                                    own_sort, isect_ids_sorted, gaussian_ids_sorted, tile_bins, ws, L, tmp_bytes, st);
+}
+
+// B views of one splat set in the same launches (unerf_splat_bin_sort_batch).  The splats of all views are one stream of B N
+// (view-major: id v N + i); every staged pass runs segment by segment (RsSegs: one segment per view), so each view's order is
+// exactly its single-view order -- depth, then splat index on ties; tile, then depth order -- and its pairs leave contiguous,
+// view after view.  The keys stay the per-view tile ids (13 bits at 1080p): a combined (view, tile) key would outgrow the LDS
+// tables from two 1080p views on.
+extern "C" int unerf_splat_bin_sort_batch(const float* xys, const float* depths, const int32_t* radii,
+                                          const int32_t* cum_tiles_hit, int B, int64_t N, const int64_t* isects_host, int H,
+                                          int W, int block_width, const float* tight_conics, const float* tight_opacities,
+                                          int32_t* gaussian_ids_sorted, int32_t* tile_bins, void* workspace,
+                                          int64_t workspace_bytes, void* stream) {
+    UNERF_REQUIRE(xys && depths && radii && cum_tiles_hit && isects_host && tile_bins && workspace,
+                  "splat_bin_sort_batch: null pointer");
+    UNERF_REQUIRE((tight_conics == nullptr) == (tight_opacities == nullptr),
+                  "splat_bin_sort_batch: tight lists need both the conics and the opacities the tile counts were made with");
+    UNERF_REQUIRE(B >= 1 && B <= UNERF_SPLAT_MAX_VIEWS, "splat_bin_sort_batch: B=%d outside [1,%d]", B, UNERF_SPLAT_MAX_VIEWS);
+    UNERF_REQUIRE(N >= 1 && (int64_t)B * N < UNERF_SPLAT_MAX_BATCH_SPLATS, "splat_bin_sort_batch: bad N (B*N = %lld)",
+                  (long long)B * (long long)N);
+    UNERF_REQUIRE(block_width >= 1 && block_width <= 16 && H > 0 && W > 0, "splat_bin_sort_batch: bad block_width/H/W");
+    int64_t I = 0;
+    for (int v = 0; v < B; ++v) {
+        UNERF_REQUIRE(isects_host[v] >= 0 && isects_host[v] < (1ll << 31), "splat_bin_sort_batch: view %d: %lld intersections", v,
+                      (long long)isects_host[v]);
+        I += isects_host[v];
+    }
+    UNERF_REQUIRE(I < (1ll << 31), "splat_bin_sort_batch: %lld intersections over the batch, the ids are int32 (< 2^31)",
+                  (long long)I);
+    const int tbx = (W + block_width - 1) / block_width, tby = (H + block_width - 1) / block_width, tiles = tbx * tby;
+    UNERF_REQUIRE(tiles <= UNERF_SPLAT_BATCH_MAX_TILES, "splat_bin_sort_batch: %d tiles, the batched tile sort serves up to %d",
+                  tiles, UNERF_SPLAT_BATCH_MAX_TILES);
+    UNERF_REQUIRE(I == 0 || gaussian_ids_sorted, "splat_bin_sort_batch: null output");
+    const SortWs L = sort_ws_layout(N, I, B, true);
+    {   // the tile passes' tables for this batch's own chunk plan must fit what the layout reserved for them
+        int64_t nchunk = 0;
+        for (int v = 0; v < B; ++v) nchunk += ((isects_host[v] + RS_M_TILE - 1) / RS_M_TILE + 15) / 16 * 16;
+        const int64_t need = ((int64_t)256 * nchunk + (nchunk / 16) * (tiles + 1)) * 4;
+        UNERF_REQUIRE(need <= L.ts_segsum - L.ts_table,
+                      "splat_bin_sort_batch: tile tables of %lld bytes exceed the %lld the workspace layout reserves (internal)",
+                      (long long)need, (long long)(L.ts_segsum - L.ts_table));
+    }
+    UNERF_REQUIRE(workspace_bytes >= L.total,
+                  "splat_bin_sort_batch: workspace %lld < %lld bytes (unerf_splat_sort_workspace_bytes_batch)",
+                  (long long)workspace_bytes, (long long)L.total);
+    hipStream_t st = (hipStream_t)stream;
+    if (hipMemsetAsync(tile_bins, 0, (size_t)B * tiles * 2 * sizeof(int32_t), st) != hipSuccess)
+        return unerf_check_launch("splat_bin_sort_batch memset");
+    if (I == 0) return UNERF_OK;
+    const int64_t NB = (int64_t)B * N;
+    char* ws = (char*)workspace;
+    uint32_t* dk_in = reinterpret_cast<uint32_t*>(ws + L.dkey_in);
+    uint32_t* dk_out = reinterpret_cast<uint32_t*>(ws + L.dkey_out);
+    int32_t* id_in = reinterpret_cast<int32_t*>(ws + L.id_in);
+    int32_t* order = reinterpret_cast<int32_t*>(ws + L.order);
+    int32_t* counts = reinterpret_cast<int32_t*>(ws + L.counts);
+    int32_t* cum_sorted = reinterpret_cast<int32_t*>(ws + L.cum);
+    // 1. each view's splats in depth order, view after view: four staged 8-bit LSD passes, segment by segment
+    {
+        const int cpv = (int)((N + RS_M_DEPTH - 1) / RS_M_DEPTH), nchunk = B * cpv, grid = (nchunk + 3) / 4;
+        RsSegs<UNERF_SPLAT_MAX_VIEWS> sg;
+        sg.n = B;
+        for (int v = 0; v <= B; ++v) { sg.cb[v] = v * cpv; sg.pb[v] = (int64_t)v * N; }
+        uint32_t* table = reinterpret_cast<uint32_t*>(ws + L.ds_table);
+        uint32_t* dtotal = reinterpret_cast<uint32_t*>(ws + L.ds_total);
+        const size_t lds_sc = 4 * (size_t)RsLds<RS_M_DEPTH, 256, uint32_t>::WAVE_WORDS * sizeof(uint32_t), lds_dig = 1024 * sizeof(uint32_t);
+        hipLaunchKernelGGL(depth_keys_kernel, dim3(blocks_for(NB, 256)), dim3(256), 0, st, depths, radii, NB, dk_out, order);
+        uint32_t* kin = dk_out; uint32_t* kout = dk_in;
+        int32_t* vin = order; int32_t* vout = id_in;
+        for (int p = 0; p < 4; ++p) {
+            hipLaunchKernelGGL((rs_hist_kernel<uint32_t, false, true>), dim3(grid), dim3(256), lds_dig, st, kin, sg, RS_M_DEPTH, nchunk, 0xFFFFFFFFu,
+                               8 * p, 256, 1, table, (uint32_t*)nullptr);
+            hipLaunchKernelGGL(rs_rowscan_kernel<UNERF_SPLAT_MAX_VIEWS>, dim3(256, B), dim3(1024), 0, st, table, nchunk, sg, dtotal);
+            if (p < 3)
+                hipLaunchKernelGGL((rs_scatter_kernel<uint32_t, RS_M_DEPTH, 256, true, false, true>), dim3(grid), dim3(256), lds_sc, st, kin, vin, sg, nchunk,
+                                   0xFFFFFFFFu, 8 * p, 256, table, dtotal, kout, vout);
+            else
+                hipLaunchKernelGGL((rs_scatter_kernel<uint32_t, RS_M_DEPTH, 256, false, true, true>), dim3(grid), dim3(256), lds_sc, st, kin, vin, sg, nchunk,
+                                   0xFFFFFFFFu, 8 * p, 256, table, dtotal, (uint32_t*)nullptr, order, radii, cum_tiles_hit, counts);
+            uint32_t* tk = kin; kin = kout; kout = tk;
+            int32_t* tv = vin; vin = vout; vout = tv;
+        }
+        int rc = unerf_check_launch("splat_bin_sort_batch depth sort");
+        if (rc) return rc;
+    }
+    // 2. where each splat's intersections start: one scan over the B N depth-ordered counts (views stay contiguous)
+    own_inclusive_scan(counts, cum_sorted, NB, reinterpret_cast<int32_t*>(ws + L.tmp), st);
+    // 3. emission in that order, then the two staged tile passes segment by segment (view v's pairs: [pb[v], pb[v + 1]))
+    uint16_t* tk_in = reinterpret_cast<uint16_t*>(ws + L.tkey_in);
+    uint16_t* tk_mid = reinterpret_cast<uint16_t*>(ws + L.tkey_out);
+    int32_t* v_in = reinterpret_cast<int32_t*>(ws + L.val_in);
+    int32_t* v_mid = reinterpret_cast<int32_t*>(ws + L.val_mid);
+    if (tight_conics)
+        hipLaunchKernelGGL((map_intersects_kernel<uint16_t, 8>), dim3(blocks_for(NB, 32)), dim3(256), 0, st, xys, radii, order,
+                           cum_sorted, NB, block_width, tbx, tby, tight_conics, tight_opacities, tk_in, v_in);
+    else
+        hipLaunchKernelGGL((map_intersects_kernel<uint16_t, 16>), dim3(blocks_for(NB, 16)), dim3(256), 0, st, xys, radii, order,
+                           cum_sorted, NB, block_width, tbx, tby, tight_conics, tight_opacities, tk_in, v_in);
+    const int T1 = tiles + 1;
+    const RsTilePlan rp = rs_tile_plan(I, T1);      // (digit split only: the chunks are laid out per view below)
+    RsSegs<UNERF_SPLAT_MAX_VIEWS> sg;
+    sg.n = B; sg.cb[0] = 0; sg.pb[0] = 0;
+    for (int v = 0; v < B; ++v) {
+        const int64_t c = (isects_host[v] + RS_M_TILE - 1) / RS_M_TILE;
+        sg.cb[v + 1] = sg.cb[v] + (int)(((c + 15) / 16) * 16);      // whole histogram workgroups per view
+        sg.pb[v + 1] = sg.pb[v] + isects_host[v];
+    }
+    const int nchunk = sg.cb[B], nhw = nchunk / 16;
+    uint32_t* table0 = reinterpret_cast<uint32_t*>(ws + L.ts_table);     // [B0][nchunk]
+    uint32_t* table1 = table0 + (size_t)128 * nchunk;                      // [B1][nchunk]
+    uint32_t* full = table1 + (size_t)128 * nchunk;                        // [nhw][T1]
+    uint32_t* dtotal0 = reinterpret_cast<uint32_t*>(ws + L.ts_segsum);    // [B][256] per pass
+    uint32_t* dtotal1 = dtotal0 + (size_t)256 * B;
+    uint32_t* total = dtotal1 + (size_t)256 * B;                           // [B][16][T1]
+    uint32_t* start = reinterpret_cast<uint32_t*>(ws + L.ts_start);       // [B][T1 + 1]
+    const uint32_t kmax = (uint32_t)tiles;
+    const size_t lds_full = (16 * 256 + (size_t)T1) * sizeof(uint32_t), lds_dig = 1024 * sizeof(uint32_t);
+    const size_t lds_sc = (size_t)RsLds<RS_M_TILE, 128, uint16_t>::WAVE_WORDS * sizeof(uint32_t);
+    const int hgrid = (nchunk + 3) / 4;
+    if (rp.b0 == 0) {      // <= 128 keys: one pass
+        hipLaunchKernelGGL((rs_hist_kernel<uint16_t, true, true>), dim3(nhw), dim3(1024), lds_full, st, tk_in, sg, RS_M_TILE, nchunk, kmax, 0,
+                           rp.B1, 1, table1, full);
+        hipLaunchKernelGGL(rs_rowscan_kernel<UNERF_SPLAT_MAX_VIEWS>, dim3(rp.B1, B), dim3(1024), 0, st, table1, nchunk, sg, dtotal1);
+        hipLaunchKernelGGL((rs_scatter_kernel<uint16_t, RS_M_TILE, 128, false, false, true>), dim3(nchunk), dim3(64), lds_sc, st, tk_in, v_in, sg, nchunk, kmax,
+                           0, rp.B1, table1, dtotal1, (uint16_t*)nullptr, gaussian_ids_sorted);
+    } else {
+        hipLaunchKernelGGL((rs_hist_kernel<uint16_t, true, true>), dim3(nhw), dim3(1024), lds_full, st, tk_in, sg, RS_M_TILE, nchunk, kmax, 0,
+                           rp.B0, 1, table0, full);
+        hipLaunchKernelGGL(rs_rowscan_kernel<UNERF_SPLAT_MAX_VIEWS>, dim3(rp.B0, B), dim3(1024), 0, st, table0, nchunk, sg, dtotal0);
+        hipLaunchKernelGGL((rs_scatter_kernel<uint16_t, RS_M_TILE, 128, true, false, true>), dim3(nchunk), dim3(64), lds_sc, st, tk_in, v_in, sg, nchunk, kmax,
+                           0, rp.B0, table0, dtotal0, tk_mid, v_mid);
+        hipLaunchKernelGGL((rs_hist_kernel<uint16_t, false, true>), dim3(hgrid), dim3(256), lds_dig, st, tk_mid, sg, RS_M_TILE, nchunk, kmax,
+                           rp.b0, rp.B1, 1, table1, (uint32_t*)nullptr);
+        hipLaunchKernelGGL(rs_rowscan_kernel<UNERF_SPLAT_MAX_VIEWS>, dim3(rp.B1, B), dim3(1024), 0, st, table1, nchunk, sg, dtotal1);
+        hipLaunchKernelGGL((rs_scatter_kernel<uint16_t, RS_M_TILE, 128, false, false, true>), dim3(nchunk), dim3(64), lds_sc, st, tk_mid, v_mid, sg, nchunk,
+                           kmax, rp.b0, rp.B1, table1, dtotal1, (uint16_t*)nullptr, gaussian_ids_sorted);
+    }
+    // 4. per view: tile totals -> tile starts (from the view's first slot) and its tile_bins
+    hipLaunchKernelGGL(rs_colsum_kernel<UNERF_SPLAT_MAX_VIEWS>, dim3(blocks_for(T1, 256), 16, B), dim3(256), 0, st, full, sg, T1, total);
+    hipLaunchKernelGGL((tile_scan_kernel<16, UNERF_SPLAT_MAX_VIEWS>), dim3(B), dim3(1024), ((size_t)T1 + 16) * sizeof(uint32_t), st, total, T1, tiles, start,
+                       tile_bins, sg);
+    return unerf_check_launch("splat_bin_sort_batch");
 }
 
 // ======================================================================================
@@ -1556,6 +1952,15 @@ __global__ __launch_bounds__(256) void raster_kernel(RasterArgs a) {
     __shared__ uint16_t s_list[4][256];
     const int bw = a.bw;
     const int tbx = (a.W + bw - 1) / bw;
+    {   // view blockIdx.z of a batch (unerf_splat_rasterize_batch): its bins, images and maximum; the ids index the whole batch
+        const int64_t vw = blockIdx.z, hw = (int64_t)a.H * a.W;
+        a.bins += vw * 2 * tbx * (int64_t)((a.H + bw - 1) / bw);
+        a.out += vw * hw * C;
+        a.finalT += vw * hw;
+        if (a.final_idx) a.final_idx += vw * hw;
+        if (BOUNDED) a.stop_idx += vw * hw;
+        if (a.chan_max) a.chan_max += vw;
+    }
     // XCD-aware tile order (UNERF_SPLAT_XCD): every XCD rasterises a contiguous eighth of the row-major tile list -- a band of
     // the image -- so the splats its tiles gather (neighbouring tiles share most of theirs) are looked up in ONE L2 instead
     // of all eight.  Pure scheduling: a tile is computed exactly as before.
@@ -1708,24 +2113,23 @@ __global__ __launch_bounds__(256) void raster_kernel(RasterArgs a) {
     }
 }
 
-extern "C" int unerf_splat_rasterize(const int32_t* gaussian_ids_sorted, const int32_t* tile_bins, const float* xys,
-                                     const float* conics, const float* colors, const float* opacities,
-                                     const float* background, int C, int H, int W, int block_width,
-                                     const int32_t* stop_idx, int flags, int max_channel, float* chan_max, float* out_img,
-                                     float* final_T, int32_t* final_idx, void* stream) {
+static int splat_rasterize_impl(const char* what, int B, const int32_t* gaussian_ids_sorted, const int32_t* tile_bins, const float* xys,
+                                const float* conics, const float* colors, const float* opacities, const float* background, int C,
+                                int H, int W, int block_width, const int32_t* stop_idx, int flags, int max_channel, float* chan_max,
+                                float* out_img, float* final_T, int32_t* final_idx, void* stream) {
     UNERF_REQUIRE(tile_bins && xys && conics && colors && opacities && out_img && final_T,
-                  "splat_rasterize: null pointer");
-    UNERF_REQUIRE(C >= 1 && C <= 8, "splat_rasterize: C=%d outside [1,8]", C);
-    UNERF_REQUIRE(block_width >= 1 && block_width <= 16 && H > 0 && W > 0, "splat_rasterize: bad block_width/H/W");
-    UNERF_REQUIRE((flags & ~UNERF_RASTER_NO_CULL) == 0, "splat_rasterize: unknown flags %d", flags);
-    UNERF_REQUIRE(!chan_max || (max_channel >= 0 && max_channel < C), "splat_rasterize: max_channel %d outside [0,%d)",
+                  "%s: null pointer", what);
+    UNERF_REQUIRE(C >= 1 && C <= 8, "%s: C=%d outside [1,8]", what, C);
+    UNERF_REQUIRE(block_width >= 1 && block_width <= 16 && H > 0 && W > 0, "%s: bad block_width/H/W", what);
+    UNERF_REQUIRE((flags & ~UNERF_RASTER_NO_CULL) == 0, "%s: unknown flags %d", what, flags);
+    UNERF_REQUIRE(!chan_max || (max_channel >= 0 && max_channel < C), "%s: max_channel %d outside [0,%d)", what,
                   max_channel, C);
     RasterArgs a;
     a.ids = gaussian_ids_sorted; a.bins = tile_bins; a.xys = xys; a.conics = conics; a.colors = colors;
     a.opac = opacities; a.bg = background; a.H = H; a.W = W; a.bw = block_width; a.out = out_img; a.finalT = final_T;
     a.final_idx = final_idx; a.stop_idx = stop_idx; a.cull = (flags & UNERF_RASTER_NO_CULL) ? 0 : 1;
     a.chan_max = reinterpret_cast<unsigned int*>(chan_max); a.max_ch = chan_max ? max_channel : -1;
-    dim3 grid((W + block_width - 1) / block_width, (H + block_width - 1) / block_width), block(256);
+    dim3 grid((W + block_width - 1) / block_width, (H + block_width - 1) / block_width, B), block(256);
 #if UNERF_SPLAT_XCD
     {   // linear ids 0 .. 8 ceil(ntile / 8) - 1 must exist: one more grid column covers the padding (tby >= 1 workgroups more)
         const unsigned ntile = grid.x * grid.y, need = ((ntile + 7u) / 8u) * 8u;
@@ -1752,7 +2156,26 @@ extern "C" int unerf_splat_rasterize(const int32_t* gaussian_ids_sorted, const i
             break;
     }
 #undef UNERF_RASTER_CASE
-    return unerf_check_launch("splat_rasterize");
+    return unerf_check_launch(what);
+}
+
+extern "C" int unerf_splat_rasterize(const int32_t* gaussian_ids_sorted, const int32_t* tile_bins, const float* xys,
+                                     const float* conics, const float* colors, const float* opacities,
+                                     const float* background, int C, int H, int W, int block_width,
+                                     const int32_t* stop_idx, int flags, int max_channel, float* chan_max, float* out_img,
+                                     float* final_T, int32_t* final_idx, void* stream) {
+    return splat_rasterize_impl("splat_rasterize", 1, gaussian_ids_sorted, tile_bins, xys, conics, colors, opacities, background, C, H,
+                                W, block_width, stop_idx, flags, max_channel, chan_max, out_img, final_T, final_idx, stream);
+}
+
+extern "C" int unerf_splat_rasterize_batch(const int32_t* gaussian_ids_sorted, const int32_t* tile_bins, const float* xys,
+                                           const float* conics, const float* colors, const float* opacities,
+                                           const float* background, int B, int C, int H, int W, int block_width,
+                                           const int32_t* stop_idx, int flags, int max_channel, float* chan_max,
+                                           float* out_img, float* final_T, int32_t* final_idx, void* stream) {
+    UNERF_REQUIRE(B >= 1 && B <= UNERF_SPLAT_MAX_VIEWS, "splat_rasterize_batch: B=%d outside [1,%d]", B, UNERF_SPLAT_MAX_VIEWS);
+    return splat_rasterize_impl("splat_rasterize_batch", B, gaussian_ids_sorted, tile_bins, xys, conics, colors, opacities, background,
+                                C, H, W, block_width, stop_idx, flags, max_channel, chan_max, out_img, final_T, final_idx, stream);
 }
 
 // ======================================================================================
@@ -1815,6 +2238,14 @@ __global__ __launch_bounds__(256) void norm_outputs_kernel(float* __restrict__ i
                                                            float* __restrict__ sqrt_out) {
     int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= HW) return;
+    {   // view blockIdx.y of a batch: its image, transmittances, outputs and maximum
+        const int64_t vw = blockIdx.y;
+        img += vw * HW * stride; finalT += vw * HW; mx += vw;
+        if (rgb_out) rgb_out += vw * HW * 3;
+        if (acc_out) acc_out += vw * HW;
+        if (sq_out) sq_out += vw * HW;
+        if (sqrt_out) sqrt_out += vw * HW;
+    }
     const float alpha = 1.f - finalT[i];
     const float v = img[i * stride + ch];
     const float nv = (alpha > 0.f) ? v / alpha : mx[0];
@@ -1847,12 +2278,31 @@ extern "C" int unerf_splat_normalize_outputs(float* img, int stride, int ch, con
     return unerf_check_launch("splat_normalize_outputs");
 }
 
+extern "C" int unerf_splat_normalize_outputs_batch(float* img, int stride, int ch, const float* final_T, int B, int64_t HW,
+                                                   const float* scratch_max, float* rgb_out, float* acc_out, int sq_ch,
+                                                   float* sq_out, float* sqrt_out, void* stream) {
+    UNERF_REQUIRE(img && final_T && scratch_max, "splat_normalize_outputs_batch: null pointer");
+    UNERF_REQUIRE(B >= 1 && B <= UNERF_SPLAT_MAX_VIEWS, "splat_normalize_outputs_batch: B=%d outside [1,%d]", B, UNERF_SPLAT_MAX_VIEWS);
+    UNERF_REQUIRE(stride >= 1 && ch >= 0 && ch < stride && HW >= 0, "splat_normalize_outputs_batch: bad stride/ch");
+    UNERF_REQUIRE(!rgb_out || (stride >= 3 && ch >= 3), "splat_normalize_outputs_batch: rgb_out needs channels 0..2 beside channel ch");
+    UNERF_REQUIRE(!sq_out || (sq_ch >= 0 && sq_ch < stride && sq_ch != ch), "splat_normalize_outputs_batch: bad sq_ch");
+    if (HW == 0) return UNERF_OK;
+    hipLaunchKernelGGL(norm_outputs_kernel, dim3(blocks_for(HW, 256), B), dim3(256), 0, (hipStream_t)stream, img, stride, ch, final_T, HW,
+                       scratch_max, rgb_out, acc_out, sq_ch, sq_out, sqrt_out);
+    return unerf_check_launch("splat_normalize_outputs_batch");
+}
+
 __global__ __launch_bounds__(256) void depth_sqdiff_kernel(const float* __restrict__ xys,
                                                            const float* __restrict__ depths,
                                                            const float* __restrict__ dimg, int stride, int ch, int H,
                                                            int W, int64_t N, float* __restrict__ out) {
     int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= N) return;
+    {   // view blockIdx.y of a batch: its splats and its depth image
+        const int64_t vw = blockIdx.y;
+        xys += vw * N * 2; depths += vw * N; out += vw * N;
+        dimg += vw * H * (int64_t)W * stride;
+    }
     float fxp = floorf(xys[i * 2]), fyp = floorf(xys[i * 2 + 1]);
     float z = depths[i];
     // reference uses strict ">0" on both axes (activesplatfacto_model.py:327-332)
@@ -1870,4 +2320,15 @@ extern "C" int unerf_splat_depth_sqdiff(const float* xys, const float* depths, c
     hipLaunchKernelGGL(depth_sqdiff_kernel, dim3(blocks_for(N, 256)), dim3(256), 0, (hipStream_t)stream, xys, depths,
                        depth_img, stride, ch, H, W, N, sq_diff_out);
     return unerf_check_launch("splat_depth_sqdiff");
+}
+
+extern "C" int unerf_splat_depth_sqdiff_batch(const float* xys, const float* depths, const float* depth_img, int stride, int ch,
+                                              int B, int H, int W, int64_t N, float* sq_diff_out, void* stream) {
+    UNERF_REQUIRE(N <= 0 || (xys && depths && depth_img && sq_diff_out), "splat_depth_sqdiff_batch: null pointer");
+    UNERF_REQUIRE(B >= 1 && B <= UNERF_SPLAT_MAX_VIEWS, "splat_depth_sqdiff_batch: B=%d outside [1,%d]", B, UNERF_SPLAT_MAX_VIEWS);
+    UNERF_REQUIRE(stride >= 1 && ch >= 0 && ch < stride && H > 0 && W > 0, "splat_depth_sqdiff_batch: bad stride/ch/H/W");
+    if (N <= 0) return UNERF_OK;
+    hipLaunchKernelGGL(depth_sqdiff_kernel, dim3(blocks_for(N, 256), B), dim3(256), 0, (hipStream_t)stream, xys, depths,
+                       depth_img, stride, ch, H, W, N, sq_diff_out);
+    return unerf_check_launch("splat_depth_sqdiff_batch");
 }

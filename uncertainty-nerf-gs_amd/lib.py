@@ -197,7 +197,21 @@ SIGNATURES = {
     "unerf_splat_alpha_normalize": (_i, [_vp, _i, _i, _vp, _i64, _vp, _i, _vp]),
     "unerf_splat_normalize_outputs": (_i, [_vp, _i, _i, _vp, _i64, _vp, _vp, _vp, _i, _vp, _vp, _vp]),
     "unerf_splat_depth_sqdiff": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i64, _vp, _vp]),
+    "unerf_splat_project_batch": (_i, [_vp, _vp, _f, _vp, _fp, _i, _i, _i, _i, _f, _i64, _vp, _i, _vp, _vp, _vp, _vp, _vp,
+                                       _vp, _vp, _vp, _vp]),
+    "unerf_splat_shade_inputs_batch": (_i, [_i, _vp, _fp, _i, _vp, _vp, _vp, _f, _vp, _vp, _vp, _i64, _i, _vp, _vp, _vp]),
+    "unerf_splat_sort_workspace_bytes_batch": (_i64, [_i, _i64, _i64]),
+    "unerf_splat_count_intersects_batch": (_i, [_vp, _vp, _i, _i64, _vp, _vp, _vp, _i64, _vp]),
+    "unerf_splat_bin_sort_batch": (_i, [_vp, _vp, _vp, _vp, _i, _i64, C.POINTER(C.c_int64), _i, _i, _i, _vp, _vp, _vp, _vp, _vp,
+                                        _i64, _vp]),
+    "unerf_splat_rasterize_batch": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _i, _vp, _vp, _vp,
+                                         _vp, _vp]),
+    "unerf_splat_normalize_outputs_batch": (_i, [_vp, _i, _i, _vp, _i, _i64, _vp, _vp, _vp, _i, _vp, _vp, _vp]),
+    "unerf_splat_depth_sqdiff_batch": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i64, _vp, _vp]),
 }
+SPLAT_MAX_VIEWS = 16                              # include/unerf.h: UNERF_SPLAT_MAX_VIEWS
+SPLAT_VIEW_FLOATS = 19                            # include/unerf.h: UNERF_SPLAT_VIEW_FLOATS
+SPLAT_BATCH_MAX_TILES = 11999                     # include/unerf.h: UNERF_SPLAT_BATCH_MAX_TILES
 
 _lib: Optional[C.CDLL] = None
 

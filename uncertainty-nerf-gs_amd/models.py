@@ -775,6 +775,49 @@ class SplatfactoModel(nn.Module, _ImageMetrics):
         self.set_crop(obb_box)
         return self.get_outputs(camera)
 
+    @torch.no_grad()
+    def get_outputs_for_cameras(self, cameras, obb_box=None, max_views: int = 8) -> List[Dict[str, Optional[torch.Tensor]]]:
+        """get_outputs_for_camera for every camera of a batch (camera_to_worlds [B,3,4]; fx, fy, cx, cy scalar or one per
+        camera; one image size), rendered max_views cameras per call (splat.active_splatfacto_outputs_batch): element i
+        equals get_outputs_for_camera(camera i, obb_box) bit for bit.  The eval loop of the reference renders its test
+        cameras one by one (scripts/eval_uncertainty.py:896-904); here they share the per-frame fixed cost.  Images of more
+        than lib.SPLAT_BATCH_MAX_TILES tiles (11,999: 2560 x 1440 has 14,400) are rendered camera by camera, with the same
+        results."""
+        c2w = torch.as_tensor(cameras.camera_to_worlds)
+        c2w = c2w[None] if c2w.dim() == 2 else c2w
+        B = c2w.shape[0]
+        if not 1 <= max_views <= _lib.SPLAT_MAX_VIEWS:
+            raise ValueError(f"max_views={max_views}: a batch holds 1 to {_lib.SPLAT_MAX_VIEWS} cameras")
+        ctype = getattr(cameras, "camera_type", None)
+        if ctype is not None:
+            types = ({int(v) for v in torch.as_tensor(ctype).reshape(-1)} if torch.is_tensor(ctype)
+                     else {int(getattr(ctype, "value", ctype))})
+            bad = sorted(types - {_lib.CAMERA_PERSPECTIVE})
+            if bad:
+                raise NotImplementedError(f"camera_type {bad[0]}: the splat models project through a pinhole (PERSPECTIVE 1) only")
+        sizes = {(int(h), int(w)) for h, w in zip(torch.as_tensor(cameras.height).reshape(-1).expand(B).tolist(),
+                                                  torch.as_tensor(cameras.width).reshape(-1).expand(B).tolist())}
+        if len(sizes) != 1:
+            raise ValueError(f"get_outputs_for_cameras renders one image size per batch, got {sorted(sizes)} (H, W)")
+        (H, W), = sizes
+        intr = {k: torch.as_tensor(getattr(cameras, k)).detach().to("cpu", torch.float64).reshape(-1).expand(B)
+                for k in ("fx", "fy", "cx", "cy")}
+        self.set_crop(obb_box)
+        n = min(self.step // self.config.sh_degree_interval, self.config.sh_degree) if self.config.sh_degree > 0 else 0
+        gp = {k: v.detach() for k, v in self.gauss_params.items()}
+        crop_ids = None
+        if self.crop_box is not None and not self.training:                     # :174-180, once for all cameras
+            crop_ids = self.crop_box.within(gp["means"]).squeeze()
+        outs: List[Dict[str, Optional[torch.Tensor]]] = []
+        for b0 in range(0, B, max_views):
+            sl = slice(b0, min(b0 + max_views, B))
+            outs += splat.active_splatfacto_outputs_batch(
+                gp, c2w[sl, :3, :4], intr["fx"][sl], intr["fy"][sl], intr["cx"][sl], intr["cy"][sl], H, W,
+                background=self.background_color.to(gp["means"].device), beta_min=getattr(self.config, "beta_min", 0.01),
+                sh_degree=n, rasterize_mode=self.config.rasterize_mode, crop_ids=crop_ids,
+                config_sh_degree=self.config.sh_degree)
+        return outs
+
     # -- the two helpers the eval script calls on splat models (scripts/eval_uncertainty.py:321-322, 676-677) --
     def get_gt_img(self, image: torch.Tensor) -> torch.Tensor:
         """[UPSTREAM SplatfactoModel.get_gt_img] uint8 -> float / 255, then the training-resolution downscale,

@@ -10,7 +10,7 @@ import ctypes as C
 import threading
 import os
 from dataclasses import dataclass
-from typing import Dict, Optional, Tuple
+from typing import Dict, List, Optional, Tuple
 
 import torch
 
@@ -1227,17 +1227,19 @@ class SplatCount:
     device idling through a full stream synchronisation and the launch latency of everything behind it."""
 
     _side: Dict = {}
-    # A small RING of pinned int32 words per device: a count may be started and awaited later (pipelined frames, ensemble
-    # members, threads), so two can be in flight; each takes the next word, and wait() caches its value on first return --
-    # a word is reused only RING counts later (a count still unawaited by then is refused: it would read another's value)
+    # A small RING of pinned int32 slots (WORDS words each) per device: a count may be started and awaited later (pipelined
+    # frames, ensemble members, threads), so two can be in flight; each takes the next slot, and wait() caches its value on
+    # first return -- a slot is reused only RING counts later (a count still unawaited by then is refused: it would read
+    # another's value)
     RING = 8
+    WORDS = 1
     _pinned: Dict = {}
     _next: Dict = {}
     _owner: Dict = {}
 
     _events: Dict = {}
     # slot allocation is the one piece of state threads share: two threads counting on one device would otherwise take the
-    # same ring word (and its event pair) and each could read the other's count
+    # same ring slot (and its event pair) and each could read the other's count
     _lock = threading.Lock()
 
     def __init__(self, num_tiles_hit: torch.Tensor, defer_copy: bool = False):
@@ -1247,34 +1249,42 @@ class SplatCount:
         lib = _l.load()
         self.N, self.dev = num_tiles_hit.shape[0], num_tiles_hit.device
         self.cum = torch.empty(self.N, device=self.dev, dtype=torch.int32)
-        self._value: Optional[int] = None
-        self._copy_started = False
         with _ctx(self.dev):
             ws0 = torch.empty(int(lib.unerf_splat_sort_workspace_bytes(self.N, 0)), device=self.dev, dtype=torch.uint8)
             _run("splat_count", lambda: lib.unerf_splat_count_intersects(_p(num_tiles_hit, torch.int32), self.N,
                                                                          _p(self.cum, torch.int32), _p(ws0, torch.uint8),
                                                                          ws0.numel(), _stream()))
+        self._start(ws0, self.cum[-1:], self.cum, 1, defer_copy)
+
+    def _start(self, ws0: torch.Tensor, src: torch.Tensor, keep: torch.Tensor, words: int, defer_copy: bool) -> None:
+        """behind the scan just queued: take this count's ring slot, mark the scan's end on the caller's stream; src = the
+        device words to read back, keep = the tensor whose storage the side stream reads"""
+        import weakref
+        cls = type(self)
+        self._value = None
+        self._copy_started = False
+        self._src, self._keep = src, keep
+        with _ctx(self.dev):
             key = self.dev.index if self.dev.index is not None else torch.cuda.current_device()
             self._key = key
-            import weakref
             with SplatCount._lock:
                 if key not in SplatCount._side:
                     SplatCount._side[key] = torch.cuda.Stream(device=self.dev)
-                if key not in SplatCount._pinned:
-                    SplatCount._pinned[key] = torch.empty(SplatCount.RING, dtype=torch.int32, pin_memory=True)
-                    SplatCount._next[key], SplatCount._owner[key] = 0, [None] * SplatCount.RING
-                    # one (scan done, copy done) event pair per ring word, made once: an event is reusable once awaited
-                    SplatCount._events[key] = [(torch.cuda.Event(), torch.cuda.Event()) for _ in range(SplatCount.RING)]
-                slot = SplatCount._next[key]
-                prev = SplatCount._owner[key][slot]
+                if key not in cls._pinned:
+                    cls._pinned[key] = torch.empty(cls.RING, cls.WORDS, dtype=torch.int32, pin_memory=True)
+                    cls._next[key], cls._owner[key] = 0, [None] * cls.RING
+                    # one (scan done, copy done) event pair per ring slot, made once: an event is reusable once awaited
+                    cls._events[key] = [(torch.cuda.Event(), torch.cuda.Event()) for _ in range(cls.RING)]
+                slot = cls._next[key]
+                prev = cls._owner[key][slot]
                 prev = prev() if prev is not None else None
                 if prev is not None and prev._value is None:
-                    raise _l.UnerfError(f"SplatCount: {SplatCount.RING} counts started on this device without wait(): await "
+                    raise _l.UnerfError(f"{cls.__name__}: {cls.RING} counts started on this device without wait(): await "
                                         "them before starting more")
-                SplatCount._owner[key][slot] = weakref.ref(self)
-                SplatCount._next[key] = (slot + 1) % SplatCount.RING
-            self._host = SplatCount._pinned[key][slot:slot + 1]
-            self._ready, self._done = SplatCount._events[key][slot]
+                cls._owner[key][slot] = weakref.ref(self)
+                cls._next[key] = (slot + 1) % cls.RING
+            self._host = cls._pinned[key][slot, :words]
+            self._ready, self._done = cls._events[key][slot]
             self._ready.record(torch.cuda.current_stream())
             self._ws0 = ws0     # keeps the scan's scratch alive until the count is known
         if not defer_copy:
@@ -1289,15 +1299,18 @@ class SplatCount:
         with _ctx(self.dev):
             with torch.cuda.stream(side):
                 side.wait_event(self._ready)
-                self._host.copy_(self.cum[-1:], non_blocking=True)
+                self._host.copy_(self._src, non_blocking=True)
                 self._done.record(side)
-            self.cum.record_stream(side)
+            self._keep.record_stream(side)
 
-    def wait(self) -> int:
+    def _decode(self, host: List[int]):
+        return host[0]
+
+    def wait(self):
         if self._value is None:
             self.start_copy()
             self._done.synchronize()
-            self._value = int(self._host[0])
+            self._value = self._decode([int(x) for x in self._host.tolist()])
         return self._value
 
 
@@ -1389,4 +1402,158 @@ def splat_depth_sqdiff(xys, depths, depth_img: torch.Tensor, ch: int) -> torch.T
     with _ctx(xys.device):
         _run("splat_depth_sqdiff", lambda: lib.unerf_splat_depth_sqdiff(_p(xys), _p(depths), _p(depth_img), Cn, ch, H, W, xys.shape[0], _p(out),
                                               _stream()))
+    return out
+
+
+# ---------------------------------------------------------------- splats, B views per call ---------------
+# (include/unerf.h, "splats, B views per call": per-view tensors are view-major [B, N, ...] / [B, H, W, ...])
+
+def splat_view_records(viewmats, fxs, fys, cxs, cys, cam_pos) -> "C.Array":
+    """B host records of UNERF_SPLAT_VIEW_FLOATS floats: world-to-camera rows 0..2, fx, fy, cx, cy, camera position"""
+    B = len(viewmats)
+    rec = (C.c_float * (B * _l.SPLAT_VIEW_FLOATS))()
+    for v in range(B):
+        row = [float(x) for x in viewmats[v][:3, :4].reshape(-1)] + [float(fxs[v]), float(fys[v]), float(cxs[v]), float(cys[v])]
+        row += [float(x) for x in cam_pos[v].reshape(-1)[:3]]
+        for k, x in enumerate(row):
+            rec[v * _l.SPLAT_VIEW_FLOATS + k] = x
+    return rec
+
+
+def splat_project_batch(means3d, log_scales, raw_quats, views, B: int, H: int, W: int, block_width: int = 16,
+                        clip_thresh: float = 0.01, opacity_logits=None, antialiased: bool = False, glob_scale: float = 1.0):
+    """splat_project(raw=True) for the B cameras of `views` (splat_view_records) in one launch -> (xys [B,N,2], depths [B,N],
+    radii, conics [B,N,3], compensation, num_tiles_hit, opacities [B,N] | None); no cov3d"""
+    lib = _l.load()
+    N, dev = means3d.shape[0], means3d.device
+    xys = torch.empty(B, N, 2, device=dev)
+    depths = torch.empty(B, N, device=dev)
+    radii = torch.empty(B, N, device=dev, dtype=torch.int32)
+    conics = torch.empty(B, N, 3, device=dev)
+    comp = torch.empty(B, N, device=dev)
+    tiles = torch.empty(B, N, device=dev, dtype=torch.int32)
+    opac = torch.empty(B, N, device=dev) if opacity_logits is not None else None
+    with _ctx(dev):
+        _run("splat_project_batch", lambda: lib.unerf_splat_project_batch(
+            _p(means3d), _p(log_scales), glob_scale, _p(raw_quats), views, B, H, W, block_width, clip_thresh, N,
+            _p(opacity_logits), 1 if antialiased else 0, _p(opac), _p(xys), _p(depths), _p(radii, torch.int32), _p(conics),
+            _p(comp), _p(tiles, torch.int32), None, _stream()))
+    return xys, depths, radii, conics, comp, tiles, opac
+
+
+def splat_shade_inputs_batch(degree: int, means3d, views, B: int, features_dc, features_rest, log_unc, beta_min: float,
+                             opacity_logits, compensation, depths):
+    """splat_shade_inputs for the B camera positions of `views` in one launch -> (rows [B,N,C], opacities [B,N] | None)"""
+    lib = _l.load()
+    N, dev = means3d.shape[0], means3d.device
+    Cn = 5 if log_unc is not None else 4
+    rows = torch.empty(B, N, Cn, device=dev)
+    opac = torch.empty(B, N, device=dev) if opacity_logits is not None else None
+    with _ctx(dev):
+        _run("splat_shade_inputs_batch", lambda: lib.unerf_splat_shade_inputs_batch(
+            degree, _p(means3d), views, B, _p(features_dc), _p(features_rest), _p(log_unc), beta_min, _p(opacity_logits),
+            _p(compensation), _p(depths), N, Cn, _p(rows), _p(opac), _stream()))
+    return rows, opac
+
+
+class SplatCountBatch(SplatCount):
+    """SplatCount for B views: one scan over the B N tile counts, and ONE read-back per batch -- the per-view intersection
+    totals and "some radius > 0" flags (unerf_splat_count_intersects_batch's summary) -- through a pinned ring of its own
+    (slots of 2 UNERF_SPLAT_MAX_VIEWS words), the side stream and the slot lock of SplatCount.  wait() -> (per-view totals,
+    per-view "some radius > 0")."""
+
+    WORDS = 2 * _l.SPLAT_MAX_VIEWS
+    _pinned: Dict = {}
+    _next: Dict = {}
+    _owner: Dict = {}
+    _events: Dict = {}
+
+    def __init__(self, num_tiles_hit: torch.Tensor, radii: Optional[torch.Tensor] = None, defer_copy: bool = False):
+        lib = _l.load()
+        self.B, self.N = num_tiles_hit.shape
+        self.dev = num_tiles_hit.device
+        self.cum = torch.empty(self.B, self.N, device=self.dev, dtype=torch.int32)
+        self.summary = torch.empty(2 * self.B, device=self.dev, dtype=torch.int32)
+        with _ctx(self.dev):
+            # the scan's scratch: its block sums, one int32 per 1,024 counts
+            ws0 = torch.empty(max((self.B * self.N + 1023) // 1024, 1) * 4, device=self.dev, dtype=torch.uint8)
+            _run("splat_count_batch", lambda: lib.unerf_splat_count_intersects_batch(
+                _p(num_tiles_hit, torch.int32), _p(radii, torch.int32), self.B, self.N, _p(self.cum, torch.int32),
+                _p(self.summary, torch.int32), _p(ws0, torch.uint8), ws0.numel(), _stream()))
+        self._start(ws0, self.summary, self.summary, 2 * self.B, defer_copy)
+
+    def _decode(self, host: List[int]):
+        return host[:self.B], [bool(x) for x in host[self.B:]]
+
+
+def splat_bin_sort_batch(xys, depths, radii, count: SplatCountBatch, H: int, W: int, block_width: int = 16,
+                         tight: Optional[Tuple[torch.Tensor, torch.Tensor]] = None):
+    """-> (per-view totals, per-view "visible" flags, gaussian_ids_sorted [sum of totals] (ids v N + i, view after view),
+    tile_bins [B,tiles,2]).  The batch's one host read-back is count.wait()."""
+    lib = _l.load()
+    B, N = radii.shape
+    dev = xys.device
+    tbx, tby = (W + block_width - 1) // block_width, (H + block_width - 1) // block_width
+    totals, visible = count.wait()
+    I = sum(totals)
+    isects = (C.c_int64 * B)(*totals)
+    with _ctx(dev):
+        ws = torch.empty(max(int(lib.unerf_splat_sort_workspace_bytes_batch(B, N, min(I, (1 << 31) - 1))), 1), device=dev,
+                         dtype=torch.uint8)
+        gids = torch.empty(max(I, 1), device=dev, dtype=torch.int32)
+        bins = torch.empty(B, tbx * tby, 2, device=dev, dtype=torch.int32)
+        _run("splat_bin_sort_batch", lambda: lib.unerf_splat_bin_sort_batch(
+            _p(xys), _p(depths), _p(radii, torch.int32), _p(count.cum, torch.int32), B, N, isects, H, W, block_width,
+            _p(tight[0]) if tight else None, _p(tight[1]) if tight else None, _p(gids, torch.int32), _p(bins, torch.int32),
+            _p(ws, torch.uint8), ws.numel(), _stream()))
+    return totals, visible, gids, bins
+
+
+def splat_rasterize_batch(gaussian_ids_sorted, tile_bins, xys, conics, colors, opacities, H: int, W: int,
+                          background: Optional[torch.Tensor] = None, block_width: int = 16, want_final_idx: bool = False,
+                          stop_idx: Optional[torch.Tensor] = None, chan_max: Optional[Tuple[int, torch.Tensor]] = None):
+    """splat_rasterize for B views (grid: tiles x B): colors [B,N,C] -> (out [B,H,W,C], final_T [B,H,W], final_idx | None);
+    chan_max = (channel, B zeroed device floats): each view's own maximum"""
+    lib = _l.load()
+    B, _, Cn = colors.shape
+    dev = xys.device
+    out = torch.empty(B, H, W, Cn, device=dev)
+    fT = torch.empty(B, H, W, device=dev)
+    fidx = torch.empty(B, H, W, device=dev, dtype=torch.int32) if want_final_idx else None
+    if gaussian_ids_sorted.numel() == 0:
+        gaussian_ids_sorted = torch.zeros(1, device=dev, dtype=torch.int32)
+    with _ctx(dev):
+        _run(f"splat_rasterize_batch_c{Cn}", lambda: lib.unerf_splat_rasterize_batch(
+            _p(gaussian_ids_sorted, torch.int32), _p(tile_bins, torch.int32), _p(xys), _p(conics), _p(colors), _p(opacities),
+            _p(background), B, Cn, H, W, block_width, _p(stop_idx, torch.int32), 0, chan_max[0] if chan_max else -1,
+            _p(chan_max[1]) if chan_max else None, _p(out), _p(fT), _p(fidx, torch.int32), _stream()))
+    return out, fT, fidx
+
+
+def splat_normalize_outputs_batch(img: torch.Tensor, ch: int, final_T: torch.Tensor, max_ready: torch.Tensor, rgb: bool = False,
+                                  acc: bool = False, sq_ch: Optional[int] = None, sqrt: bool = False):
+    """splat_normalize_outputs for B views: img [B,H,W,C], max_ready [B] -> outputs [B,H,W,...]"""
+    lib = _l.load()
+    B, H, W, Cn = img.shape
+    dev = img.device
+    rgb_o = torch.empty(B, H, W, 3, device=dev) if rgb else None
+    acc_o = torch.empty(B, H, W, 1, device=dev) if acc else None
+    sq_o = torch.empty(B, H, W, 1, device=dev) if sq_ch is not None else None
+    sqrt_o = torch.empty(B, H, W, 1, device=dev) if sqrt else None
+    with _ctx(dev):
+        _run("splat_normalize_outputs_batch", lambda: lib.unerf_splat_normalize_outputs_batch(
+            _p(img), Cn, ch, _p(final_T), B, H * W, _p(max_ready), _p(rgb_o), _p(acc_o), -1 if sq_ch is None else sq_ch,
+            _p(sq_o), _p(sqrt_o), _stream()))
+    return rgb_o, acc_o, sq_o, sqrt_o
+
+
+def splat_depth_sqdiff_batch(xys, depths, depth_img: torch.Tensor, ch: int) -> torch.Tensor:
+    """splat_depth_sqdiff for B views: xys [B,N,2], depths [B,N], depth_img [B,H,W,C] -> [B,N]"""
+    lib = _l.load()
+    B, H, W, Cn = depth_img.shape
+    N = xys.shape[1]
+    out = torch.empty(B, N, device=xys.device)
+    with _ctx(xys.device):
+        _run("splat_depth_sqdiff_batch", lambda: lib.unerf_splat_depth_sqdiff_batch(
+            _p(xys), _p(depths), _p(depth_img), Cn, ch, B, H, W, N, _p(out), _stream()))
     return out

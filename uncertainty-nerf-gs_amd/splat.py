@@ -8,7 +8,7 @@ the data-dependent depth-variance pass (it needs the finished depth image, :336)
 """
 from __future__ import annotations
 
-from typing import Dict, Optional
+from typing import Dict, List, Optional
 
 import torch
 
@@ -142,3 +142,95 @@ def active_splatfacto_outputs(gp: Dict[str, torch.Tensor], c2w: torch.Tensor, fx
     return {"rgb": rgb, "depth": img[..., 4:5], "accumulation": alpha,
             "background": background, "uncertainty": unc, "rgb_var": rgb_var, "rgb_std": unc,
             "depth_var": dv, "depth_std": dstd}
+
+
+def _per_view(x, B: int, name: str) -> List[float]:
+    """a scalar (or one-element tensor) for every view, or B values"""
+    t = torch.as_tensor(x).detach().to("cpu", torch.float64).reshape(-1)
+    if t.numel() == 1:
+        return [float(t[0])] * B
+    if t.numel() != B:
+        raise ValueError(f"{name}: {t.numel()} values for {B} cameras (give one, or one per camera)")
+    return [float(v) for v in t]
+
+
+def active_splatfacto_outputs_batch(gp: Dict[str, torch.Tensor], c2ws: torch.Tensor, fx, fy, cx, cy, H: int, W: int,
+                                    background: torch.Tensor, beta_min: float = 0.01, sh_degree: int = 3,
+                                    rasterize_mode: str = "classic", block_width: int = 16,
+                                    crop_ids: Optional[torch.Tensor] = None, config_sh_degree: Optional[int] = None,
+                                    tight: bool = True) -> List[Dict[str, Optional[torch.Tensor]]]:
+    """active_splatfacto_outputs for B cameras of one splat set and one image size, in the same launches: c2ws [B,3|4,4];
+    fx, fy, cx, cy: scalars or B values.  Returns B dicts, element v BIT-identical to active_splatfacto_outputs with camera v
+    (empty_outputs for a view that sees nothing, the rasterised all-faint frame, the crop applied once for all views).
+    The batch reads its per-view intersection totals back in one copy (SplatCountBatch); B <= lib.SPLAT_MAX_VIEWS.
+    Images of more than lib.SPLAT_BATCH_MAX_TILES tiles (e.g. 2560 x 1440 at block_width 16) are beyond the batched tile
+    sort: their views are rendered one by one with active_splatfacto_outputs (same results, no shared launches)."""
+    _l.require_gpu()
+    c2ws = c2ws.detach().to("cpu", torch.float32)
+    if c2ws.dim() == 2:
+        c2ws = c2ws[None]
+    B = c2ws.shape[0]
+    if not 1 <= B <= _l.SPLAT_MAX_VIEWS:
+        raise ValueError(f"active_splatfacto_outputs_batch: {B} cameras, a batch holds 1 to {_l.SPLAT_MAX_VIEWS}")
+    fxs, fys, cxs, cys = (_per_view(v, B, n) for v, n in ((fx, "fx"), (fy, "fy"), (cx, "cx"), (cy, "cy")))
+    if ((W + block_width - 1) // block_width) * ((H + block_width - 1) // block_width) > _l.SPLAT_BATCH_MAX_TILES:
+        return [active_splatfacto_outputs(gp, c2ws[v], fxs[v], fys[v], cxs[v], cys[v], H, W, background, beta_min=beta_min,
+                                          sh_degree=sh_degree, rasterize_mode=rasterize_mode, block_width=block_width,
+                                          crop_ids=crop_ids, config_sh_degree=config_sh_degree, tight=tight)
+                for v in range(B)]
+    background = background.to(gp["means"].device, torch.float32)
+    if rasterize_mode not in ("classic", "antialiased"):
+        raise ValueError(f"Unknown rasterize_mode: {rasterize_mode}")
+    if gp["means"].shape[0] == 0:
+        return [empty_outputs(W, H, background) for _ in range(B)]
+    if crop_ids is not None:
+        crop_ids = crop_ids.reshape(-1).to(gp["means"].device)
+        if int(crop_ids.sum().item()) == 0:
+            return [empty_outputs(W, H, background) for _ in range(B)]
+        gp = {k: v[crop_ids].contiguous() for k, v in gp.items()}
+    means = gp["means"].contiguous()
+    dev = means.device
+    views = ops.splat_view_records([viewmat_from_c2w(c) for c in c2ws], fxs, fys, cxs, cys, [c[:3, 3] for c in c2ws])
+    logits = gp["opacities"].reshape(-1).contiguous()
+    xys, depths, radii, conics, comp, tiles, opac = ops.splat_project_batch(
+        means, gp["scales"].contiguous(), gp["quats"].contiguous(), views, B, H, W, block_width,
+        opacity_logits=logits if tight else None, antialiased=rasterize_mode == "antialiased")
+    count = ops.SplatCountBatch(tiles, radii if tight else None, defer_copy=True)
+    if config_sh_degree is not None and config_sh_degree <= 0:
+        sh_degree = -1
+    plain = "log_uncertainties" not in gp
+    cols, opac2 = ops.splat_shade_inputs_batch(sh_degree, means, views, B, gp["features_dc"].contiguous(),
+                                               gp["features_rest"].contiguous(),
+                                               None if plain else gp["log_uncertainties"].reshape(-1).contiguous(), beta_min,
+                                               None if tight else logits, comp if rasterize_mode == "antialiased" else None,
+                                               depths)
+    count.start_copy()
+    opac = opac if tight else opac2
+    totals, visible, gids, bins = ops.splat_bin_sort_batch(xys, depths, radii, count, H, W, block_width,
+                                                           tight=(conics, opac) if tight else None)
+    # per view as the single-view call decides: no intersections and (with tight lists) no radius > 0 -> get_empty_outputs
+    empty = [totals[v] == 0 and not (tight and visible[v]) for v in range(B)]
+    if all(empty):
+        return [empty_outputs(W, H, background) for _ in range(B)]
+    Cn = cols.shape[2]
+    bg = torch.zeros(Cn, device=dev)
+    bg[:3] = background
+    mx = torch.zeros(2, B, device=dev)          # each view's own channel maxima of the two passes
+    if plain:
+        img, fT, _ = ops.splat_rasterize_batch(gids, bins, xys, conics, cols, opac, H, W, bg, block_width, chan_max=(3, mx[0]))
+        rgb, alpha, _, _ = ops.splat_normalize_outputs_batch(img, 3, fT, mx[0], rgb=True, acc=True)
+        return [empty_outputs(W, H, background) if empty[v] else
+                {"rgb": rgb[v], "depth": img[v, ..., 3:4], "accumulation": alpha[v], "background": background}
+                for v in range(B)]
+    img, fT, fidx = ops.splat_rasterize_batch(gids, bins, xys, conics, cols, opac, H, W, bg, block_width, want_final_idx=True,
+                                              chan_max=(4, mx[0]))
+    rgb, alpha, rgb_var, _ = ops.splat_normalize_outputs_batch(img, 4, fT, mx[0], rgb=True, acc=True, sq_ch=3)
+    sq = ops.splat_depth_sqdiff_batch(xys, depths, img, 4)
+    dv, fT2, _ = ops.splat_rasterize_batch(gids, bins, xys, conics, sq[..., None], opac, H, W, None, block_width,
+                                           stop_idx=fidx, chan_max=(0, mx[1]))
+    _, _, _, dstd = ops.splat_normalize_outputs_batch(dv, 0, fT2, mx[1], sqrt=True)
+    return [empty_outputs(W, H, background) if empty[v] else
+            {"rgb": rgb[v], "depth": img[v, ..., 4:5], "accumulation": alpha[v], "background": background,
+             "uncertainty": img[v, ..., 3:4], "rgb_var": rgb_var[v], "rgb_std": img[v, ..., 3:4], "depth_var": dv[v],
+             "depth_std": dstd[v]}
+            for v in range(B)]
