@@ -400,6 +400,44 @@ int unerf_field_fwd(const float* origins, const float* directions, const float* 
                     const float* features /* NULL, or the planes written by unerf_field_gather */,
                     float* density, float* rgb, float* aux, float* aux2, void* stream);
 
+/* MCDROPOUT under EXPLICIT keep masks (the exact-parity mode: replay masks recorded from the reference's nn.Dropout
+ * modules, or the generator's own masks exported by unerf_mc_keep_bits).  Host struct. */
+typedef struct {
+    /* DEVICE bit arrays, one per Dropout site, indexed by log2 of the UNERF_DROP_* bit:
+       [0] TRUNK, [1] HEAD0, [2] HEAD1, [3] HEADIN.  NULL = that site is not active.
+       Each is [K][pass_stride][W] uint32, W = ceil(n_units / 32); bit (u & 31) of word (u >> 5) set = unit u KEPT.
+       n_units: hidden (TRUNK), hidden_color (HEAD0, HEAD1).  Bits at and above n_units are ignored. */
+    const uint32_t* site[4];
+    int64_t pass_stride;     /* samples between pass k and pass k + 1 of every array */
+    int64_t sample_offset;   /* sample index of (ray 0, sample 0) of this call: sample (r, s) reads row sample_offset + r*S + s */
+} unerf_keep_masks;
+
+/* unerf_field_fwd with the keep decision of every (pass, sample, unit) LOADED from `masks` instead of drawn by the counter
+ * generator: pass k of sample (r, s) keeps unit u of a site iff its bit is set.  p->p_drop still gives the scale
+ * 1/(1-p); p->seed is not read; ray_offset is only the image_width tile hint here.  Same kernels, same arithmetic: with
+ * the masks unerf_mc_keep_bits writes for (seed, ray_offset * S) the outputs equal unerf_field_fwd's bit for bit.
+ * Served by the matrix kernels (every precision, both grid layouts, every output layout) and the VALU kernel at
+ * nerfacto's widths, sites TRUNK / HEAD0 / HEAD1 in any combination.  Refused before any launch: mode != MCDROPOUT,
+ * K <= 0, an active site (drop_sites; 0 = TRUNK | HEAD1) without its array, an array for a site that is not active,
+ * pass_stride < sample_offset + R*S, UNERF_DROP_HEADIN and the any-width kernel (both out of scope: there is no
+ * fall-back to generator masks). */
+int unerf_field_fwd_masked(const float* origins, const float* directions, const float* sbins, int64_t R, int S,
+                           float near_plane, float far_plane, int spacing, int64_t ray_offset,
+                           const unerf_field_params* p /* host struct */, const float* features,
+                           float* density, float* rgb, float* aux, float* aux2,
+                           const unerf_keep_masks* masks /* host struct */, void* stream);
+
+/* keep [rows][n_units] uint8 (non-zero = kept: the bytes of a torch bool tensor) -> bits [rows][W] uint32 in the layout of
+ * unerf_keep_masks (bits at and above n_units written 0).  n_units in [1, 4096]. */
+int unerf_pack_keep_bits(const uint8_t* keep, int64_t rows, int n_units, uint32_t* bits, void* stream);
+
+/* The masks the counter generator makes for samples [first_sample, first_sample + n_samples), passes 0..K-1, of mask stream
+ * stream_id (TRUNK 0, HEAD1 1, HEAD0 2, HEADIN 3), as bits [K][pass_stride][W] in the layout of unerf_keep_masks
+ * (pass_stride >= n_samples; row i = sample first_sample + i).  n_units <= 128.  Made by the functions the field kernels
+ * use (csrc/unerf_common.hpp); unerf_field_fwd numbers its samples from ray_offset * S. */
+int unerf_mc_keep_bits(uint32_t seed, int K, int64_t first_sample, int64_t n_samples, int stream_id, int n_units,
+                       float p_drop, uint32_t* bits, int64_t pass_stride, void* stream);
+
 /* Level-major form of the same HashEncoding lookup for the main field: writes the features of the
  * R*S final samples as planes [L][R*S][2] (level, sample, feature).  Each level table is 4 MiB --
  * one XCD's L2 -- so sweeping level by level runs the gathers out of L2 instead of the Infinity

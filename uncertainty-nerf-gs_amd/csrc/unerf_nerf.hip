@@ -1141,6 +1141,30 @@ struct FieldArgs {
     uint32_t chunk0;        // ... and ray_offset as a 32-bit ray index (the sample counter bound keeps it below 2^31)
 };
 
+// EXPLICIT keep masks (unerf_field_fwd_masked): a kernel argument of the XM instantiations only -- the default kernels keep
+// their argument list.  Bit arrays as include/unerf.h: unerf_keep_masks lays them out ([K][pass_stride][W] uint32, bit u of
+// a row set = unit u kept); all three sites here are 64 units wide, W = 2.
+struct KeepArgs {
+    const uint32_t* site[3];   // UNERF_DROP_TRUNK, _HEAD0, _HEAD1 (NULL: site not active)
+    int64_t pass_stride;       // rows between two passes
+    int64_t sample_offset;     // row of (ray 0, sample 0) of this launch
+};
+#define XM_WORDS 2   // uint32 words per row of a 64-unit site
+// The mask WORD of a unit pair from its two keep bits: kept -> the half 0x8000 (the most negative signed 16-bit number),
+// dropped -> 0x7FFF (the largest).  Such a word passes / fails unerf_keep_lo / unerf_keep_hi / mf16_keep_diff exactly as
+// the bits say at every threshold thr_s in (-32768, 32767] (the host sets thr_s = 0 in this mode), so everything behind
+// the making of the words -- selects, AND masks, the sign trick of mf16_split_relu_drop -- is the generator path's code.
+__device__ __forceinline__ uint32_t xm_word(uint32_t bits, int pos) {
+    return 0x7FFF7FFFu + ((bits >> pos) & 1u) + (((bits >> (pos + 1)) & 1u) << 16);
+}
+// The XM kernels are the SAME __global__ templates as the default ones with one trailing argument (a parameter pack that is
+// empty in the default instantiations, which therefore keep their argument list and their code): xm_of() names it.
+__device__ __forceinline__ const KeepArgs& xm_of(const KeepArgs& x) { return x; }
+// first word of the row of sample n (r * S + s of this launch) at pass k
+__device__ __forceinline__ const uint32_t* xm_row(const KeepArgs& x, int site, int k, int64_t n) {
+    return x.site[site] + ((int64_t)k * x.pass_stride + x.sample_offset + n) * XM_WORDS;
+}
+
 // Bin edge -> Euclidean distance.  unerf_field_fwd(near_plane < 0) sets s_near = -1: sbins then already holds
 // Euclidean edges (RaySamples.frustums.starts / ends of a caller-made sampler) and passes through untouched.
 __device__ __forceinline__ float field_bin_edge(const FieldArgs& a, float b) {
@@ -1290,6 +1314,27 @@ __device__ __forceinline__ void dense_lds_dropout(const float* __restrict__ Wt, 
         }
     }
 }
+// the same layer (64 inputs) under EXPLICIT keep bits: `row` = this sample's two words of the site at this pass; the word of
+// unit pair j is made of its two bits (xm_word) and takes the same tests, selects and multiply-adds in the same order
+template <int OUT>
+__device__ __forceinline__ void dense_lds_keepbits(const float* __restrict__ Wt, const float* __restrict__ b,
+                                                   const float* act, int lane, const uint32_t* row, int32_t thr_hi,
+                                                   float scale, float (&acc)[OUT]) {
+#pragma unroll
+    for (int o = 0; o < OUT; ++o) acc[o] = b[o];
+    const uint32_t bits[XM_WORDS] = {row[0], row[1]};
+    for (int j = 0; j < 32; ++j) {
+        const uint32_t rnd = xm_word(j < 16 ? bits[0] : bits[1], (2 * j) & 31);
+        float x0 = act[(2 * j) * 64 + lane];
+        x0 = unerf_keep_lo(rnd, thr_hi) ? x0 * scale : 0.f;
+#pragma unroll
+        for (int o = 0; o < OUT; ++o) acc[o] = fmaf(x0, Wt[(2 * j) * OUT + o], acc[o]);
+        float x1 = act[(2 * j + 1) * 64 + lane];
+        x1 = unerf_keep_hi(rnd, thr_hi) ? x1 * scale : 0.f;
+#pragma unroll
+        for (int o = 0; o < OUT; ++o) acc[o] = fmaf(x1, Wt[(2 * j + 1) * OUT + o], acc[o]);
+    }
+}
 
 template <int N>
 __device__ __forceinline__ void store_act(float* act, int lane, const float (&v)[N], int row0, bool relu) {
@@ -1297,8 +1342,10 @@ __device__ __forceinline__ void store_act(float* act, int lane, const float (&v)
     for (int o = 0; o < N; ++o) act[(row0 + o) * 64 + lane] = relu ? fmaxf(v[o], 0.f) : v[o];
 }
 
-template <int MODE>
-__global__ __launch_bounds__(64) void field_kernel(FieldArgs a) {
+// XA = KeepArgs: explicit keep masks (MCDROPOUT)
+template <int MODE, typename... XA>
+__global__ __launch_bounds__(64) void field_kernel(FieldArgs a, XA... xa) {
+    constexpr bool XM = sizeof...(XA) != 0;
     extern __shared__ float lds[];
     float* A = lds;                 // [64][64]
     float* Bf = lds + 64 * 64;      // [64][64] (MCDROPOUT only)
@@ -1383,6 +1430,10 @@ __global__ __launch_bounds__(64) void field_kernel(FieldArgs a) {
         for (int k = 0; k < passes; ++k) {
             const uint32_t base = unerf_mc_pre(unerf_mc_key(a.p.seed, 0u), sidx);   // dense_lds_dropout derives both half bases
             float o1[16];
+            if constexpr (XM) {
+                if (a.drop_sites & UNERF_DROP_TRUNK) dense_lds_keepbits<16>(a.p.w1t, a.p.b1, A, lane, xm_row(xm_of(xa...), 0, k, n), a.keep_hi, a.drop_scale, o1);
+                else dense_lds<64, 16>(a.p.w1t, a.p.b1, A, lane, o1);
+            } else
             if (a.drop_sites & UNERF_DROP_TRUNK) dense_lds_dropout<16>(a.p.w1t, a.p.b1, A, lane, base, k, 0u, a.keep_hi, a.drop_scale, o1);
             else dense_lds<64, 16>(a.p.w1t, a.p.b1, A, lane, o1);
             float density = a.p.average_init_density * expf(o1[0]) * sel;
@@ -1398,13 +1449,18 @@ __global__ __launch_bounds__(64) void field_kernel(FieldArgs a) {
             store_act<64>(Bf, lane, acc, 0, true);
             if (a.drop_sites & UNERF_DROP_HEAD0) {
                 float acc2[64];
-                dense_lds_dropout<64>(a.p.h1t, a.p.hb1, Bf, lane, base, k, 2u, a.keep_hi, a.drop_scale, acc2);
+                if constexpr (XM) dense_lds_keepbits<64>(a.p.h1t, a.p.hb1, Bf, lane, xm_row(xm_of(xa...), 1, k, n), a.keep_hi, a.drop_scale, acc2);
+                else dense_lds_dropout<64>(a.p.h1t, a.p.hb1, Bf, lane, base, k, 2u, a.keep_hi, a.drop_scale, acc2);
                 store_act<64>(Bf, lane, acc2, 0, true);
             } else {
                 dense_lds<64, 64>(a.p.h1t, a.p.hb1, Bf, lane, acc);
                 store_act<64>(Bf, lane, acc, 0, true);
             }
             float c[3];
+            if constexpr (XM) {
+                if (a.drop_sites & UNERF_DROP_HEAD1) dense_lds_keepbits<3>(a.p.h2t, a.p.hb2, Bf, lane, xm_row(xm_of(xa...), 2, k, n), a.keep_hi, a.drop_scale, c);
+                else dense_lds<64, 3>(a.p.h2t, a.p.hb2, Bf, lane, c);
+            } else
             if (a.drop_sites & UNERF_DROP_HEAD1) dense_lds_dropout<3>(a.p.h2t, a.p.hb2, Bf, lane, base, k, 1u, a.keep_hi, a.drop_scale, c);
             else dense_lds<64, 3>(a.p.h2t, a.p.hb2, Bf, lane, c);
             if (valid && a.p.packed_out) {
@@ -1734,6 +1790,13 @@ __device__ __forceinline__ void mf_mask_words_at(uint32_t (&st)[8], int blk, int
     mf_mask_init(st, blk, h, base_h, stream_id);
     for (int q = 0; q < k; ++q) mf_mask_step(st);
 }
+// EXPLICIT keep masks: the same eight words of block blk made of the sample's keep bits (`row`: xm_row) -- word q covers the
+// units mf_mask_init states, 32 blk + 2 (q & 1) + 8 (q >> 1) + 4 h and the one after it
+__device__ __forceinline__ void mf_xm_words(uint32_t (&st)[8], const uint32_t* row, int blk, int h) {
+    const uint32_t bits = row[blk] >> (4 * h);
+#pragma unroll
+    for (int q = 0; q < 8; ++q) st[q] = xm_word(bits, 2 * (q & 1) + 8 * (q >> 1));
+}
 __device__ __forceinline__ f32x16 mf_dropout(f32x16 v, const uint32_t (&st)[8], int32_t thr_hi, float scale) {
 #pragma unroll
     for (int q = 0; q < 8; ++q) {
@@ -1935,12 +1998,13 @@ __device__ __forceinline__ f32x16 mf_gather_feats_pipe(const FieldArgs& a, float
     return feat;
 }
 
-template <int MODE, bool FEAT_IN, int TCNN = 0>
+template <int MODE, bool FEAT_IN, int TCNN = 0, typename... XA>   // XA = KeepArgs: explicit keep masks (MCDROPOUT)
 // ACTIVE is bound by the gather (texture-address unit): three waves per SIMD (<= 168 VGPRs) hide more of
 // its latency than two (measured 21.7 vs 23.7 ms/frame when a 176-VGPR build lost the third wave); the
 // K-pass mode needs the registers instead.
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((MODE == UNERF_FIELD_ACTIVE && TCNN != 1) ? 3 : 2)))
-void field_kernel_mfma(FieldArgs a, uint32_t num_tiles, FastDiv div_s) {
+void field_kernel_mfma(FieldArgs a, uint32_t num_tiles, FastDiv div_s, XA... xa) {
+    constexpr bool XM = sizeof...(XA) != 0;
     extern __shared__ float lds[];
     {
         const float4* src = reinterpret_cast<const float4*>(a.p.mfma_blob);
@@ -2021,8 +2085,8 @@ void field_kernel_mfma(FieldArgs a, uint32_t num_tiles, FastDiv div_s) {
         const bool drop = (MODE == UNERF_FIELD_MCDROPOUT) && a.drop_on;
         const uint32_t sidx = (uint32_t)((uint64_t)a.ray_offset * (uint64_t)a.S + (uint64_t)n);
         uint32_t mk0[8], mk1[8], mk2[8], mk3[8];  // this lane's mask words: trunk blk 0/1, head blk 0/1
-        const uint32_t base0 = drop ? unerf_mc_base_h(unerf_mc_pre(unerf_mc_key(a.p.seed, 0u), sidx), (uint32_t)h) : 0u;   // this lane half's
-        if (drop) {
+        const uint32_t base0 = (drop && !XM) ? unerf_mc_base_h(unerf_mc_pre(unerf_mc_key(a.p.seed, 0u), sidx), (uint32_t)h) : 0u;   // this lane half's
+        if (drop && !XM) {
             mf_mask_init(mk0, 0, h, base0, 0u);
             mf_mask_init(mk1, 1, h, base0, 0u);
             mf_mask_init(mk2, 0, h, base0, 1u);
@@ -2032,7 +2096,16 @@ void field_kernel_mfma(FieldArgs a, uint32_t num_tiles, FastDiv div_s) {
             asm volatile("" : "+v"(lane));  // same reason: keep the fragment reads inside the pass
             f32x16 m0 = hid0, m1 = hid1;
             if (drop) {
-                if (k > 0) {
+                if constexpr (XM) {   // this pass' words from the keep bits instead of a generator step
+                    if (a.drop_sites & UNERF_DROP_TRUNK) {
+                        mf_xm_words(mk0, xm_row(xm_of(xa...), 0, k, n), 0, h);
+                        mf_xm_words(mk1, xm_row(xm_of(xa...), 0, k, n), 1, h);
+                    }
+                    if (a.drop_sites & UNERF_DROP_HEAD1) {
+                        mf_xm_words(mk2, xm_row(xm_of(xa...), 2, k, n), 0, h);
+                        mf_xm_words(mk3, xm_row(xm_of(xa...), 2, k, n), 1, h);
+                    }
+                } else if (k > 0) {
                     mf_mask_step(mk0);
                     mf_mask_step(mk1);
                     mf_mask_step(mk2);
@@ -2058,9 +2131,11 @@ void field_kernel_mfma(FieldArgs a, uint32_t num_tiles, FastDiv div_s) {
             c1 = mf_relu(c1);
             if (drop && (a.drop_sites & UNERF_DROP_HEAD0)) {   // rgb_dropout_layers contains 1: Dropout in front of Linear 1
                 uint32_t mw[8];
-                mf_mask_words_at(mw, 0, h, base0, 2u, k);
+                if constexpr (XM) mf_xm_words(mw, xm_row(xm_of(xa...), 1, k, n), 0, h);
+                else mf_mask_words_at(mw, 0, h, base0, 2u, k);
                 c0 = mf_dropout(c0, mw, a.keep_hi, a.drop_scale);
-                mf_mask_words_at(mw, 1, h, base0, 2u, k);
+                if constexpr (XM) mf_xm_words(mw, xm_row(xm_of(xa...), 1, k, n), 1, h);
+                else mf_mask_words_at(mw, 1, h, base0, 2u, k);
                 c1 = mf_dropout(c1, mw, a.keep_hi, a.drop_scale);
             }
             // colour 1: 64 -> 64, ReLU
@@ -2373,12 +2448,15 @@ __device__ __forceinline__ void mf_pin8(uint32_t (&x)[8]) {
 // they cost that kernel 50 VGPRs and 84 bytes of scratch (K = 8 field kernel 50 -> 55.6 ms).
 // DROP: masks are generated (MCDROPOUT with K > 0 and p > 0).  A compile-time flag: as a run-time (uniform) flag every
 // k-step of the masked layers carried a branch and the operand quads were copied to merge the two paths.
-template <int MODE, int TCNN, bool SITES = false, bool DROP = false, bool F1 = false>
+// XA = KeepArgs: explicit keep masks (unerf_field_fwd_masked), on the general SITES form
+template <int MODE, int TCNN, bool SITES = false, bool DROP = false, bool F1 = false, typename... XA>
 // (the single-product K-pass kernel at 3 waves per SIMD was measured twice and lost both times: round 3, 168 VGPRs, 96 B of
 // scratch, trunk operands re-read from LDS -- 4.84 vs 3.89 ms per launch, profiles/r3_exp_f16_single_occ3.json; round 7,
 // 163 VGPRs, no scratch, the SH k-step of colour 0 recomputed per pass -- 12.71 - 12.88 vs 12.44 - 12.56 ms, docs/experiments.md 7.1)
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((MODE == UNERF_FIELD_ACTIVE && TCNN != 1) ? 3 : 2)))
-void field_kernel_mfma16(FieldArgs a, uint32_t num_tiles, FastDiv div_s) {
+void field_kernel_mfma16(FieldArgs a, uint32_t num_tiles, FastDiv div_s, XA... xa) {
+    constexpr bool XM = sizeof...(XA) != 0;
+    static_assert(!XM || (SITES && DROP && MODE == UNERF_FIELD_MCDROPOUT), "explicit keep masks ride on the general SITES path");
     extern __shared__ float lds[];
     {
         const float4* src = reinterpret_cast<const float4*>(a.p.mfma16_blob);
@@ -2482,7 +2560,7 @@ void field_kernel_mfma16(FieldArgs a, uint32_t num_tiles, FastDiv div_s) {
         uint32_t base0_h0 = 0u;   // SITES only: the sample's base hash stays live across the passes
         const bool drop_trunk = SITES ? (drop && (a.drop_sites & UNERF_DROP_TRUNK)) : drop;
         const bool drop_head1 = SITES ? (drop && (a.drop_sites & UNERF_DROP_HEAD1)) : drop;
-        if (drop) {
+        if (drop && !XM) {
             const uint32_t base0 = unerf_mc_base_h(unerf_mc_pre(unerf_mc_key(a.p.seed, 0u), sidx), (uint32_t)h);   // this lane half's
             if (SITES) base0_h0 = base0;
             mf_mask_init(mk0, 0, h, base0, 0u);
@@ -2505,7 +2583,16 @@ void field_kernel_mfma16(FieldArgs a, uint32_t num_tiles, FastDiv div_s) {
         }
         for (int k = 0; k < passes; ++k) {
             asm volatile("" : "+v"(lane));
-            if (!FILL && drop && k > 0) {
+            if constexpr (XM) {   // this pass' words from the keep bits instead of a generator step
+                if (drop_trunk) {
+                    mf_xm_words(mk0, xm_row(xm_of(xa...), 0, k, n), 0, h);
+                    mf_xm_words(mk1, xm_row(xm_of(xa...), 0, k, n), 1, h);
+                }
+                if (drop_head1) {
+                    mf_xm_words(mk2, xm_row(xm_of(xa...), 2, k, n), 0, h);
+                    mf_xm_words(mk3, xm_row(xm_of(xa...), 2, k, n), 1, h);
+                }
+            } else if (!FILL && drop && k > 0) {
                 mf_mask_step(mk0);
                 mf_mask_step(mk1);
                 mf_mask_step(mk2);
@@ -2583,7 +2670,8 @@ void field_kernel_mfma16(FieldArgs a, uint32_t num_tiles, FastDiv div_s) {
                     if (F1) mf16_split_relu(st < 2 ? c0 : c1, st & 1, bhi);
                     else mf16_split<F1>(st < 2 ? c0 : c1, st & 1, bhi, blo);
                     uint32_t mw[8];
-                    mf_mask_words_at(mw, st >> 1, h, base0_h0, 2u, k);
+                    if constexpr (XM) mf_xm_words(mw, xm_row(xm_of(xa...), 1, k, n), st >> 1, h);
+                    else mf_mask_words_at(mw, st >> 1, h, base0_h0, 2u, k);
                     mf16_apply_masks<F1>(bhi, blo, mw, st & 1, a.keep_pk);
                     mf16_mac2<F1>(lds, 12 + 2 * st, 12 + 2 * st + 1, lane, bhi, blo, d0, d1);
                 }
@@ -3374,17 +3462,18 @@ static int mfma_grid_for(Kern kernel, int64_t num_tiles, size_t lds_bytes) {
 #define MF_LDS_FP32 ((size_t)UNERF_MFMA_BLOB_FLOATS * 4)
 #define MF_LDS_F16 MF_LDS_FP32
 #define MF_LDS_F16S ((size_t)UNERF_MFMA16_BLOB_FLOATS * 4)   // the "f16" form of field_kernel_mfma16: + the colour-2 slabs
-template <typename Kern>
-static void launch_matrix_kernel(Kern kernel, size_t lds_bytes, FieldArgs& a, hipStream_t st) {
+template <typename Kern, typename... Extra>   // extra: the KeepArgs of the explicit-mask kernels
+static void launch_matrix_kernel(Kern kernel, size_t lds_bytes, FieldArgs& a, hipStream_t st, Extra... extra) {
     const int64_t tiles = make_tiles(a, a.p.image_width);
     hipLaunchKernelGGL(kernel, dim3(mfma_grid_for(kernel, tiles, lds_bytes)), dim3(256), lds_bytes, st, a, (uint32_t)tiles,
-                       make_fastdiv((uint32_t)a.S));
+                       make_fastdiv((uint32_t)a.S), extra...);
 }
 
-extern "C" int unerf_field_fwd(const float* origins, const float* directions, const float* sbins, int64_t R, int S,
-                               float near_plane, float far_plane, int spacing, int64_t ray_offset, const unerf_field_params* p,
-                               const float* features, float* density, float* rgb, float* aux, float* aux2,
-                               void* stream) {
+// masks = NULL: unerf_field_fwd.  Else unerf_field_fwd_masked: MC-dropout under explicit keep masks.
+static int field_fwd_impl(const float* origins, const float* directions, const float* sbins, int64_t R, int S,
+                          float near_plane, float far_plane, int spacing, int64_t ray_offset, const unerf_field_params* p,
+                          const float* features, float* density, float* rgb, float* aux, float* aux2,
+                          const unerf_keep_masks* masks, void* stream) {
     UNERF_REQUIRE(p && (R == 0 || (origins && directions && sbins && (density || p->packed_out) && rgb)), "field_fwd: null pointer");
     UNERF_REQUIRE(!p->packed_out || (p->mode != UNERF_FIELD_LAPLACE && !p->sample_major),
                   "field_fwd: packed_out rows are written by the ACTIVE / MCDROPOUT kernels in the ray-major layout only");
@@ -3416,6 +3505,29 @@ extern "C" int unerf_field_fwd(const float* origins, const float* directions, co
                   "field_fwd: sample index exceeds 32 bits (RNG counter)");
     UNERF_REQUIRE(!p->sample_major || (p->mode != UNERF_FIELD_LAPLACE && (p->mfma16_blob || p->mfma_blob)),
                   "field_fwd: sample_major planes are written by the ACTIVE / MCDROPOUT matrix kernels only");
+    KeepArgs xm = {};
+    if (masks) {   // explicit keep masks: every refusal before any launch; never a fall-back to the generator
+        UNERF_REQUIRE(p->mode == UNERF_FIELD_MCDROPOUT, "field_fwd_masked: explicit keep masks are an MCDROPOUT mode (mode=%d)", p->mode);
+        UNERF_REQUIRE(p->K > 0, "field_fwd_masked: K=%d, explicit keep masks need K >= 1 passes", p->K);
+        UNERF_REQUIRE(p->p_drop >= 0.f && p->p_drop < 1.f, "field_fwd_masked: bad p_drop");
+        UNERF_REQUIRE((p->drop_sites & ~(UNERF_DROP_TRUNK | UNERF_DROP_HEAD0 | UNERF_DROP_HEAD1 | UNERF_DROP_HEADIN)) == 0,
+                      "field_fwd_masked: unknown bits in drop_sites=%d", p->drop_sites);
+        UNERF_REQUIRE(!(p->drop_sites & UNERF_DROP_HEADIN),
+                      "field_fwd_masked: UNERF_DROP_HEADIN is out of scope of the explicit-mask mode (not built; no generator fall-back)");
+        UNERF_REQUIRE(!generic, "field_fwd_masked: the any-width kernel is out of scope of the explicit-mask mode "
+                                "(nerfacto widths 64 / 64 / 15 / 2 and L = 16 only; no generator fall-back)");
+        const int sites = p->drop_sites ? p->drop_sites : (UNERF_DROP_TRUNK | UNERF_DROP_HEAD1);
+        static const char* const names[4] = {"TRUNK", "HEAD0", "HEAD1", "HEADIN"};
+        for (int i = 0; i < 4; ++i) {
+            UNERF_REQUIRE(!((sites >> i) & 1) || masks->site[i], "field_fwd_masked: site %s is active (drop_sites=%d) but its mask array is NULL", names[i], sites);
+            UNERF_REQUIRE(((sites >> i) & 1) || !masks->site[i], "field_fwd_masked: a mask array for site %s, which is not active (drop_sites=%d)", names[i], sites);
+        }
+        UNERF_REQUIRE(masks->sample_offset >= 0 && masks->pass_stride >= masks->sample_offset + R * (int64_t)S,
+                      "field_fwd_masked: pass_stride=%lld < sample_offset + R*S = %lld + %lld", (long long)masks->pass_stride,
+                      (long long)masks->sample_offset, (long long)(R * (int64_t)S));
+        xm.site[0] = masks->site[0]; xm.site[1] = masks->site[1]; xm.site[2] = masks->site[2];
+        xm.pass_stride = masks->pass_stride; xm.sample_offset = masks->sample_offset;
+    }
     if (R == 0) return UNERF_OK;
     FieldArgs a;
     a.origins = origins; a.dirs = directions; a.sbins = sbins; a.R = R; a.S = S;
@@ -3436,6 +3548,12 @@ extern "C" int unerf_field_fwd(const float* origins, const float* directions, co
         const int32_t thr_s = (int32_t)(thr < 65536 ? thr : 65535) - 32768;
         a.keep_hi = (int32_t)((uint32_t)thr_s << 16);
         a.keep_pk = ((uint32_t)thr_s & 0xFFFFu) * 0x10001u;
+    }
+    if (masks) {   // the words are made of the keep bits (xm_word): on at every p, and any threshold in (-32768, 32767] reads them
+        a.drop_on = 1;
+        a.drop_sites = p->drop_sites ? p->drop_sites : (UNERF_DROP_TRUNK | UNERF_DROP_HEAD1);
+        a.keep_hi = 0;
+        a.keep_pk = 0u;
     }
     a.drop_scale = 1.f / (1.f - p->p_drop);
     dim3 grid(blocks_for(R * (int64_t)S, 64)), block(64);
@@ -3507,7 +3625,24 @@ extern "C" int unerf_field_fwd(const float* origins, const float* directions, co
             UNERF_REQUIRE(p->K >= 0 && p->p_drop >= 0.f && p->p_drop < 1.f, "field_fwd MCDROPOUT: bad K/p_drop");
             UNERF_REQUIRE((p->drop_sites & ~(UNERF_DROP_TRUNK | UNERF_DROP_HEAD0 | UNERF_DROP_HEAD1 | UNERF_DROP_HEADIN)) == 0,
                           "field_fwd MCDROPOUT: unknown bits in drop_sites=%d", p->drop_sites);
-            if (a.drop_sites & UNERF_DROP_HEADIN) {   // dropout on the head's inputs: the VALU kernel (include/unerf.h)
+            if (masks) {   // explicit keep masks: the same kernel selection, each in its XM instantiation (general SITES form)
+                if (p->mfma16_blob && !features && f1) {
+                    if (tc == 2) launch_matrix_kernel(field_kernel_mfma16<UNERF_FIELD_MCDROPOUT, 2, true, true, true, KeepArgs>, MF_LDS_F16S, a, st, xm);
+                    else if (tc) launch_matrix_kernel(field_kernel_mfma16<UNERF_FIELD_MCDROPOUT, 1, true, true, true, KeepArgs>, MF_LDS_F16S, a, st, xm);
+                    else launch_matrix_kernel(field_kernel_mfma16<UNERF_FIELD_MCDROPOUT, 0, true, true, true, KeepArgs>, MF_LDS_F16S, a, st, xm);
+                } else if (p->mfma16_blob && !features) {
+                    if (tc == 2) launch_matrix_kernel(field_kernel_mfma16<UNERF_FIELD_MCDROPOUT, 2, true, true, false, KeepArgs>, MF_LDS_F16S, a, st, xm);
+                    else if (tc) launch_matrix_kernel(field_kernel_mfma16<UNERF_FIELD_MCDROPOUT, 1, true, true, false, KeepArgs>, MF_LDS_F16S, a, st, xm);
+                    else launch_matrix_kernel(field_kernel_mfma16<UNERF_FIELD_MCDROPOUT, 0, true, true, false, KeepArgs>, MF_LDS_F16S, a, st, xm);
+                } else if (p->mfma_blob) {
+                    if (features) launch_matrix_kernel(field_kernel_mfma<UNERF_FIELD_MCDROPOUT, true, 0, KeepArgs>, MF_LDS_FP32, a, st, xm);
+                    else if (tc == 2) launch_matrix_kernel(field_kernel_mfma<UNERF_FIELD_MCDROPOUT, false, 2, KeepArgs>, MF_LDS_FP32, a, st, xm);
+                    else if (tc) launch_matrix_kernel(field_kernel_mfma<UNERF_FIELD_MCDROPOUT, false, 1, KeepArgs>, MF_LDS_FP32, a, st, xm);
+                    else launch_matrix_kernel(field_kernel_mfma<UNERF_FIELD_MCDROPOUT, false, 0, KeepArgs>, MF_LDS_FP32, a, st, xm);
+                } else {
+                    hipLaunchKernelGGL((field_kernel<UNERF_FIELD_MCDROPOUT, KeepArgs>), grid, block, 2 * 64 * 64 * 4, st, a, xm);
+                }
+            } else if (a.drop_sites & UNERF_DROP_HEADIN) {   // dropout on the head's inputs: the VALU kernel (include/unerf.h)
                 UNERF_REQUIRE(p->h0_full_t && p->hb0_raw && p->app_embed,
                               "field_fwd MCDROPOUT: UNERF_DROP_HEADIN needs h0_full_t / hb0_raw / app_embed");
                 UNERF_REQUIRE(!features && !p->sample_major,
@@ -3579,7 +3714,101 @@ extern "C" int unerf_field_fwd(const float* origins, const float* directions, co
             unerf_set_error("field_fwd: unknown mode %d", p->mode);
             return UNERF_ERR_ARG;
     }
-    return unerf_check_launch("field_fwd");
+    return unerf_check_launch(masks ? "field_fwd_masked" : "field_fwd");
+}
+
+extern "C" int unerf_field_fwd(const float* origins, const float* directions, const float* sbins, int64_t R, int S,
+                               float near_plane, float far_plane, int spacing, int64_t ray_offset, const unerf_field_params* p,
+                               const float* features, float* density, float* rgb, float* aux, float* aux2,
+                               void* stream) {
+    return field_fwd_impl(origins, directions, sbins, R, S, near_plane, far_plane, spacing, ray_offset, p, features, density, rgb,
+                          aux, aux2, nullptr, stream);
+}
+
+extern "C" int unerf_field_fwd_masked(const float* origins, const float* directions, const float* sbins, int64_t R, int S,
+                                      float near_plane, float far_plane, int spacing, int64_t ray_offset,
+                                      const unerf_field_params* p, const float* features, float* density, float* rgb, float* aux,
+                                      float* aux2, const unerf_keep_masks* masks, void* stream) {
+    UNERF_REQUIRE(masks, "field_fwd_masked: null masks (unerf_field_fwd is the generator path)");
+    return field_fwd_impl(origins, directions, sbins, R, S, near_plane, far_plane, spacing, ray_offset, p, features, density, rgb,
+                          aux, aux2, masks, stream);
+}
+
+// --------------------------------------------------------------------------------------
+// 5c'. Keep-mask bit arrays (include/unerf.h: unerf_keep_masks).  One thread per output word.
+// --------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void pack_keep_bits_kernel(const uint8_t* __restrict__ keep, int64_t rows, int n_units, int W,
+                                                             uint32_t* __restrict__ bits) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= rows * W) return;
+    const int64_t row = i / W;
+    const int w = (int)(i - row * W);
+    const uint8_t* src = keep + row * n_units + 32 * w;
+    const int n = n_units - 32 * w < 32 ? n_units - 32 * w : 32;
+    uint32_t word = 0u;
+    for (int b = 0; b < n; ++b) word |= (src[b] != 0 ? 1u : 0u) << b;
+    bits[i] = word;
+}
+
+extern "C" int unerf_pack_keep_bits(const uint8_t* keep, int64_t rows, int n_units, uint32_t* bits, void* stream) {
+    UNERF_REQUIRE(rows >= 0 && n_units >= 1 && n_units <= 4096, "pack_keep_bits: rows=%lld, n_units=%d outside [1,4096]", (long long)rows, n_units);
+    if (rows == 0) return UNERF_OK;
+    UNERF_REQUIRE(keep && bits, "pack_keep_bits: null pointer");
+    const int W = (n_units + 31) / 32;
+    UNERF_REQUIRE(rows * W < (1ll << 39), "pack_keep_bits: %lld words exceed the launch grid", (long long)(rows * W));
+    hipLaunchKernelGGL(pack_keep_bits_kernel, dim3(blocks_for(rows * W, 256)), dim3(256), 0, (hipStream_t)stream, keep, rows,
+                       n_units, W, bits);
+    return unerf_check_launch("pack_keep_bits");
+}
+
+// The counter generator's own masks as bit arrays: word w of a sample covers unit pairs 16 w .. 16 w + 15, made and stepped
+// by the functions the field kernels use (unerf_mc_pre / unerf_mc_base_h / unerf_mask_word0 / unerf_mask_step) and tested
+// by unerf_keep_lo / unerf_keep_hi.  keep_all: p = 0 (the field kernels generate no masks then).
+__global__ __launch_bounds__(256) void mc_keep_bits_kernel(uint32_t seed, int K, int64_t first_sample, int64_t n_samples,
+                                                           uint32_t stream_id, int n_units, int W, int32_t thr_hi, int keep_all,
+                                                           uint32_t* __restrict__ bits, int64_t pass_stride) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n_samples * W) return;
+    const int64_t smp = i / W;
+    const int w = (int)(i - smp * W);
+    const uint32_t pre = unerf_mc_pre(unerf_mc_key(seed, 0u), (uint32_t)(uint64_t)(first_sample + smp));
+    const uint32_t bh[2] = {unerf_mc_base_h(pre, 0u), unerf_mc_base_h(pre, 1u)};
+    uint32_t word[16];
+#pragma unroll
+    for (int q = 0; q < 16; ++q) {
+        const uint32_t j = 16u * (uint32_t)w + (uint32_t)q;
+        word[q] = unerf_mask_word0(bh[(j >> 1) & 1u], stream_id, j);
+    }
+    const uint32_t valid = n_units - 32 * w >= 32 ? 0xFFFFFFFFu : ((1u << (n_units - 32 * w)) - 1u);
+    for (int k = 0; k < K; ++k) {
+        uint32_t out = 0u;
+#pragma unroll
+        for (int q = 0; q < 16; ++q) {
+            if (k > 0) word[q] = unerf_mask_step(word[q]);
+            out |= (unerf_keep_lo(word[q], thr_hi) ? 1u : 0u) << (2 * q);
+            out |= (unerf_keep_hi(word[q], thr_hi) ? 1u : 0u) << (2 * q + 1);
+        }
+        bits[((int64_t)k * pass_stride + smp) * W + w] = (keep_all ? 0xFFFFFFFFu : out) & valid;
+    }
+}
+
+extern "C" int unerf_mc_keep_bits(uint32_t seed, int K, int64_t first_sample, int64_t n_samples, int stream_id, int n_units,
+                                  float p_drop, uint32_t* bits, int64_t pass_stride, void* stream) {
+    UNERF_REQUIRE(K >= 1 && n_samples >= 0 && first_sample >= 0, "mc_keep_bits: bad K=%d / first_sample / n_samples", K);
+    UNERF_REQUIRE(stream_id >= 0 && stream_id <= 3 && n_units >= 1 && n_units <= 128,
+                  "mc_keep_bits: stream_id=%d outside [0,3] or n_units=%d outside [1,128] (mask stream layout)", stream_id, n_units);
+    UNERF_REQUIRE(p_drop >= 0.f && p_drop < 1.f, "mc_keep_bits: bad p_drop");
+    UNERF_REQUIRE(pass_stride >= n_samples, "mc_keep_bits: pass_stride=%lld < n_samples=%lld", (long long)pass_stride, (long long)n_samples);
+    UNERF_REQUIRE((uint64_t)(first_sample + n_samples) < (1ull << 32), "mc_keep_bits: sample index exceeds 32 bits (RNG counter)");
+    if (n_samples == 0) return UNERF_OK;
+    UNERF_REQUIRE(bits, "mc_keep_bits: null pointer");
+    const long thr = lrint((1.0 - (double)p_drop) * 65536.0);   // as unerf_field_fwd
+    const int32_t thr_s = (int32_t)(thr < 65536 ? thr : 65535) - 32768;
+    const int W = (n_units + 31) / 32;
+    hipLaunchKernelGGL(mc_keep_bits_kernel, dim3(blocks_for(n_samples * W, 256)), dim3(256), 0, (hipStream_t)stream, seed, K,
+                       first_sample, n_samples, (uint32_t)stream_id, n_units, W, (int32_t)((uint32_t)thr_s << 16),
+                       thr >= 65536 ? 1 : 0, bits, pass_stride);
+    return unerf_check_launch("mc_keep_bits");
 }
 
 // --------------------------------------------------------------------------------------

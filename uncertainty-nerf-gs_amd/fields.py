@@ -329,11 +329,11 @@ class _NerfactoFieldBase(nn.Module, _FieldBuffers):
             self._dev, self._dev_kw = self.to_device(device, **kw), dict(kw)
         return self._dev
 
-    def _run(self, ray_samples, ray_offset: int = 0, **dev_kw):
+    def _run(self, ray_samples, ray_offset: int = 0, keep_masks=None, **dev_kw):
         _l.require_gpu()
         o, d, eb = ray_samples_to_bins(ray_samples)
         f = self._field_dev(o.device, **dev_kw)
-        return f, ops.field_fwd(o, d, eb, f, 0.0, 0.0, ray_offset, euclidean_bins=True)
+        return f, ops.field_fwd(o, d, eb, f, 0.0, 0.0, ray_offset, euclidean_bins=True, keep_masks=keep_masks)
 
     @torch.no_grad()
     def forward(self, ray_samples, compute_normals: bool = False) -> Dict:
@@ -445,10 +445,13 @@ class NerfactoMCDropoutField(_NerfactoFieldBase):
         return {"mc_samples": 0}   # eval-mode Dropout is the identity; the K stochastic passes are the Model's job
 
     @torch.no_grad()
-    def forward_passes(self, ray_samples, mc_samples: int, seed: int = 0, ray_offset: int = 0) -> Dict:
+    def forward_passes(self, ray_samples, mc_samples: int, seed: int = 0, ray_offset: int = 0,
+                       keep_masks: Optional[ops.KeepMasks] = None) -> Dict:
         """The K dropout passes of mcdropout_models.py:116-119 on one RaySamples, fused (grid lookup and the first
-        layer shared): {DENSITY [K,R,S,1], RGB [K,R,S,3]}; masks keyed by (seed, pass, ray_offset*S + sample)."""
-        f, (density, rgb, _, _) = self._run(ray_samples, ray_offset, mc_samples=mc_samples, seed=seed)
+        layer shared): {DENSITY [K,R,S,1], RGB [K,R,S,3]}; masks keyed by (seed, pass, ray_offset*S + sample) -- or,
+        with keep_masks, the explicit masks of an ops.KeepMasks (row keep_masks.sample_offset + ray * S + sample:
+        masks recorded from the reference's Dropout modules and packed with ops.pack_keep_bits, or ops.mc_keep_bits)."""
+        f, (density, rgb, _, _) = self._run(ray_samples, ray_offset, keep_masks=keep_masks, mc_samples=mc_samples, seed=seed)
         return {FieldHeadNames.DENSITY: density.unsqueeze(-1), FieldHeadNames.RGB: rgb}
 
 

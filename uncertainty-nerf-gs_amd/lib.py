@@ -140,6 +140,11 @@ class FieldParams(C.Structure):
     ]
 
 
+class KeepMasks(C.Structure):
+    """include/unerf.h: unerf_keep_masks (explicit MC-dropout keep masks, unerf_field_fwd_masked)"""
+    _fields_ = [("site", C.c_void_p * 4), ("pass_stride", C.c_int64), ("sample_offset", C.c_int64)]
+
+
 ABI_VERSION = 1420                                # include/unerf.h: UNERF_ABI_VERSION (struct layouts / argument lists)
 FIELD_ACTIVE, FIELD_MCDROPOUT, FIELD_LAPLACE = 0, 1, 2
 SPACING_PIECEWISE, SPACING_UNIFORM = 0, 1         # include/unerf.h: UNERF_SPACING_*
@@ -171,6 +176,10 @@ SIGNATURES = {
                                         _i64, _i64, _vp]),
     "unerf_field_fwd": (_i, [_vp, _vp, _vp, _i64, _i, _f, _f, _i, _i64, C.POINTER(FieldParams), _vp, _vp, _vp, _vp, _vp,
                              _vp]),
+    "unerf_field_fwd_masked": (_i, [_vp, _vp, _vp, _i64, _i, _f, _f, _i, _i64, C.POINTER(FieldParams), _vp, _vp, _vp, _vp, _vp,
+                                    C.POINTER(KeepMasks), _vp]),
+    "unerf_pack_keep_bits": (_i, [_vp, _i64, _i, _vp, _vp]),
+    "unerf_mc_keep_bits": (_i, [_u32, _i, _i64, _i64, _i, _i, _f, _vp, _i64, _vp]),
     "unerf_field_gather": (_i, [_vp, _vp, _vp, _i64, _i, _f, _f, _i, _vp, _vp, _i, _i, _vp, _vp]),
     "unerf_laplace_depth_weights": (_i, [_vp, _vp, _vp, _i64, _i, _f, _f, _i, _vp, _i, _u32, _i64, _vp, _vp]),
     "unerf_laplace_ggn_workspace_bytes": (C.c_size_t, [_i64, _i]),

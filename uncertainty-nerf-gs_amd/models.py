@@ -408,8 +408,9 @@ class _NerfactoBase(nn.Module, _ImageMetrics):
         self._kept_workspace = None
         self._dev_scene = None
 
-    def _begin_render(self, scene: NerfSceneDev) -> None:
-        """once per get_outputs_for_camera / get_outputs_for_camera_ray_bundle / get_outputs call"""
+    def _begin_render(self, scene: NerfSceneDev, total_rays: int = 0, chunk_rays: int = 0) -> None:
+        """once per get_outputs_for_camera / get_outputs_for_camera_ray_bundle / get_outputs call: the rays of the frame
+        and the rays per reference eval chunk (the whole bundle for get_outputs)"""
 
     # -- rendering ----------------------------------------------------------------------------
     def _render_kwargs(self) -> Dict[str, Any]:
@@ -423,7 +424,7 @@ class _NerfactoBase(nn.Module, _ImageMetrics):
         c2w, cam = _camera_args(camera)
         obb = None if obb_box is None else (ops.world_to_box(obb_box.R, obb_box.T), torch.as_tensor(obb_box.S).detach().cpu())
         scene = self.device_scene()
-        self._begin_render(scene)
+        self._begin_render(scene, int(cam["H"]) * int(cam["W"]), scene.chunk_rays)
         return render.render_camera(scene, c2w, rays_per_launch=self.rays_per_launch, obb=obb,
                                     **cam, **self._render_kwargs())
 
@@ -444,7 +445,7 @@ class _NerfactoBase(nn.Module, _ImageMetrics):
         origins = origins.to(device=scene0.device, dtype=torch.float32)
         directions = directions.to(device=scene0.device, dtype=torch.float32)
         scene = self.device_scene(origins.device)
-        self._begin_render(scene)
+        self._begin_render(scene, H * W, scene.chunk_rays)
         o, d = origins.reshape(-1, 3).contiguous(), directions.reshape(-1, 3).contiguous()
         init = None
         if nears is not None and fars is not None:
@@ -485,7 +486,7 @@ class _NerfactoBase(nn.Module, _ImageMetrics):
             o, d = ray_bundle.origins, ray_bundle.directions
             nears, fars = getattr(ray_bundle, "nears", None), getattr(ray_bundle, "fars", None)
         scene = self.device_scene(o.device if o.is_cuda else None)
-        self._begin_render(scene)
+        self._begin_render(scene, o.reshape(-1, 3).shape[0], max(o.reshape(-1, 3).shape[0], 1))
         o = o.reshape(-1, 3).to(device=scene.device, dtype=torch.float32).contiguous()
         d = d.reshape(-1, 3).to(device=scene.device, dtype=torch.float32).contiguous()
         init = None
@@ -549,15 +550,80 @@ def frame_seed(base_seed: int, frame: int) -> int:
     return h32((base_seed & 0xFFFFFFFF) ^ h32(frame + 0x9E3779B9))
 
 
+def iter_torch_keep_draws(K: int, total_rays: int, S: int, chunk_rays: int, drop_sites: int, p_drop: float,
+                          generator: Optional[torch.Generator] = None, hidden: int = 64, hidden_color: int = 64):
+    """The keep masks of one frame drawn as the reference's nn.Dropout modules draw them, IN THE ORDER its modules consume
+    torch's generator (mcdropout_models.py:116-119): pass k outermost (the whole camera bundle is rendered per pass),
+    inside it the chunks of `chunk_rays` rays in order, inside a chunk the active Dropout modules in forward order --
+    trunk [chunk * S, hidden], then HEAD0, then HEAD1 [chunk * S, hidden_color] (the proposal networks hold none).
+    nn.Dropout in train mode draws empty_like(x).bernoulli_(1 - p): with a CPU generator seeded s these are the masks the
+    reference's modules make on the CPU after torch.manual_seed(s).  Runs on the generator's device (None: the CPU's
+    global generator); no GPU needed.  Yields (k, first_ray, n_rays, site index 0 / 1 / 2, keep bool [n_rays * S, units])."""
+    dev = torch.device("cpu") if generator is None else generator.device
+    sites = drop_sites if drop_sites else (_lib.DROP_TRUNK | _lib.DROP_HEAD1)
+    if sites & _lib.DROP_HEADIN:
+        raise _lib.UnerfError("dropout_masks='torch': the DROP_HEADIN site has no explicit-mask mode")
+    for k in range(K):
+        for start in range(0, total_rays, chunk_rays):
+            n = min(chunk_rays, total_rays - start)
+            for i, units in enumerate((hidden, hidden_color, hidden_color)):
+                if (sites >> i) & 1:
+                    noise = torch.empty(n * S, units, dtype=torch.float32, device=dev).bernoulli_(1.0 - p_drop, generator=generator)
+                    yield k, start, n, i, noise != 0
+
+
+def torch_keep_mask_bytes(K: int, total_rays: int, S: int, drop_sites: int) -> int:
+    """bytes of a frame's packed keep masks (64-unit sites: 8 bytes per pass, sample and site)"""
+    sites = drop_sites if drop_sites else (_lib.DROP_TRUNK | _lib.DROP_HEAD1)
+    return K * total_rays * S * 8 * bin(sites & 7).count("1")
+
+
+def draw_torch_keep_masks(device, K: int, total_rays: int, S: int, chunk_rays: int, drop_sites: int, p_drop: float,
+                          generator: Optional[torch.Generator] = None) -> ops.KeepMasks:
+    """iter_torch_keep_draws packed chunk by chunk (ops.pack_keep_bits) into the frame-wide bit arrays of an
+    ops.KeepMasks on `device` (row = ray * S + sample): the bytes of a draw never exist for more than one chunk."""
+    sites = ops.FieldDev._sites(drop_sites)
+    stride = total_rays * S
+    bits = [torch.empty(K, stride, 2, dtype=torch.int32, device=device) if (sites >> i) & 1 else None for i in range(3)]
+    for k, start, n, i, keep in iter_torch_keep_draws(K, total_rays, S, max(chunk_rays, 1), drop_sites, p_drop, generator):
+        bits[i][k, start * S:(start + n) * S] = ops.pack_keep_bits(keep.to(device))
+    return ops.KeepMasks(bits[0], bits[1], bits[2], None, stride, 0)
+
+
 class NerfactoMCDropoutModel(_NerfactoBase):
     config: NerfactoMCDropoutModelConfig
     seed: int = 0                    # base seed of the dropout-mask stream
     frame_counter: int = 0           # renders made so far: every render draws fresh masks (frame_seed)
     fresh_masks_per_render: bool = True
+    # "counter": the kernels' own counter generator (default).  "torch": every frame's masks are drawn with torch's
+    # Bernoulli in the order the reference's Dropout modules consume the generator (iter_torch_keep_draws), packed to
+    # bits and replayed through the explicit-mask kernels (unerf_field_fwd_masked).
+    dropout_masks: str = "counter"
+    mask_generator: Optional[torch.Generator] = None     # "torch": None = torch's global CPU generator
+    mask_budget_bytes: int = 1 << 34                     # "torch": a frame whose packed masks need more raises (1080p, K = 8: 12.7 GB)
+    _frame_masks: Optional[ops.KeepMasks] = None
 
-    def _begin_render(self, scene: NerfSceneDev) -> None:
+    def _begin_render(self, scene: NerfSceneDev, total_rays: int = 0, chunk_rays: int = 0) -> None:
+        if self.dropout_masks not in ("counter", "torch"):
+            raise ValueError(f"dropout_masks={self.dropout_masks!r}: expected 'counter' or 'torch'")
+        self._frame_masks = None
+        if self.dropout_masks == "torch" and scene.field.K > 0 and scene.field.p_drop > 0.0:
+            self._frame_masks = self._draw_frame_masks(scene, total_rays, chunk_rays)
         scene.field.seed = frame_seed(self.seed, self.frame_counter if self.fresh_masks_per_render else 0)
         self.frame_counter += 1
+
+    def _draw_frame_masks(self, scene: NerfSceneDev, total_rays: int, chunk_rays: int) -> ops.KeepMasks:
+        f, S = scene.field, scene.num_nerf
+        if f.any_width:
+            raise _lib.UnerfError("dropout_masks='torch': the any-width kernel has no explicit-mask mode")
+        need = torch_keep_mask_bytes(f.K, total_rays, S, f.drop_sites)
+        if need > self.mask_budget_bytes:
+            raise _lib.UnerfError(f"dropout_masks='torch': the packed keep masks of this frame need {need} bytes "
+                                  f"(K={f.K} x {total_rays} rays x {S} samples), mask_budget_bytes={self.mask_budget_bytes}")
+        return draw_torch_keep_masks(scene.device, f.K, total_rays, S, chunk_rays, f.drop_sites, f.p_drop, self.mask_generator)
+
+    def _render_kwargs(self) -> Dict[str, Any]:
+        return {} if self._frame_masks is None else {"keep_masks": self._frame_masks}
 
     def reference_precision(self) -> str:
         """mcdropout_models.py:86-92: `forward` wraps every render in torch.autocast(enabled=True) -- the Linear layers run

@@ -945,17 +945,98 @@ def supports_packed(field: "FieldDev") -> bool:
     return field.mode in (_l.FIELD_ACTIVE, _l.FIELD_MCDROPOUT) and not field.any_width
 
 
+# ---- explicit MC-dropout keep masks (include/unerf.h: unerf_keep_masks) ----------------------------------
+MASK_STREAMS = (0, 2, 1)      # the generator's mask stream of sites TRUNK, HEAD0, HEAD1 (include/unerf.h: drop_sites)
+
+
+@dataclass
+class KeepMasks:
+    """Keep masks of the MC-dropout sites as bit arrays, for field_fwd(keep_masks=...) / render.*(keep_masks=...).
+    Each tensor is int32 [K, pass_stride, W] on the device (W = ceil(n_units / 32); bit u & 31 of word u >> 5 set = unit
+    u kept) or None where the site holds no Dropout.  One KeepMasks may span a whole frame: a call over rays
+    [start, start + R) reads rows sample_offset + r * S + s with sample_offset = start * S (`at`)."""
+    trunk: Optional[torch.Tensor] = None
+    head0: Optional[torch.Tensor] = None
+    head1: Optional[torch.Tensor] = None
+    headin: Optional[torch.Tensor] = None
+    pass_stride: int = 0
+    sample_offset: int = 0
+
+    def sites(self):
+        return (self.trunk, self.head0, self.head1, self.headin)
+
+    def at(self, sample_offset: int) -> "KeepMasks":
+        """the same arrays read from another first row"""
+        return KeepMasks(self.trunk, self.head0, self.head1, self.headin, self.pass_stride, int(sample_offset))
+
+    def nbytes(self) -> int:
+        return sum(t.numel() * 4 for t in self.sites() if t is not None)
+
+    def cstruct(self, K: int) -> _l.KeepMasks:
+        cs = _l.KeepMasks()
+        for i, t in enumerate(self.sites()):
+            if t is None:
+                continue
+            if t.dim() != 3 or t.shape[0] < K or t.shape[1] != self.pass_stride or t.shape[2] != 2:
+                raise _l.UnerfError(f"KeepMasks: site {i} has shape {tuple(t.shape)}, expected [K >= {K}, pass_stride = "
+                                    f"{self.pass_stride}, 2] (64-unit sites: two words per row)")
+            cs.site[i] = _p(t, torch.int32, "keep mask bits")
+        cs.pass_stride, cs.sample_offset = int(self.pass_stride), int(self.sample_offset)
+        return cs
+
+
+def pack_keep_bits(keep: torch.Tensor) -> torch.Tensor:
+    """[..., n] bool / uint8 device tensor (non-zero = kept) -> [..., ceil(n / 32)] int32 bit words (unerf_keep_masks)"""
+    lib = _l.load()
+    if keep.dtype not in (torch.bool, torch.uint8):
+        raise _l.UnerfError(f"pack_keep_bits: dtype {keep.dtype}, expected bool or uint8")
+    n = keep.shape[-1]
+    flat = keep.contiguous().view(torch.uint8).reshape(-1, n)
+    bits = torch.empty(flat.shape[0], (n + 31) // 32, device=keep.device, dtype=torch.int32)
+    with _ctx(keep.device):
+        _run("pack_keep_bits", lambda: lib.unerf_pack_keep_bits(_p(flat, torch.uint8), flat.shape[0], n, _p(bits, torch.int32),
+                                                                 _stream()))
+    return bits.reshape(*keep.shape[:-1], bits.shape[-1])
+
+
+def mc_keep_bits(field: FieldDev, first_sample: int, n_samples: int, pass_stride: Optional[int] = None) -> KeepMasks:
+    """The masks the counter generator makes for the field's K, seed, p_drop and active sites, samples
+    [first_sample, first_sample + n_samples) (field_fwd numbers its samples from ray_offset * S): row i = sample
+    first_sample + i.  The export direction, and with field_fwd(keep_masks=...) the same outputs bit for bit."""
+    lib = _l.load()
+    if field.mode != _l.FIELD_MCDROPOUT or field.K <= 0:
+        raise _l.UnerfError("mc_keep_bits: an MCDROPOUT field with K >= 1")
+    sites = FieldDev._sites(field.drop_sites)
+    if sites & _l.DROP_HEADIN or field.any_width:
+        raise _l.UnerfError("mc_keep_bits: the DROP_HEADIN site and the any-width kernel have no explicit-mask mode")
+    stride = int(n_samples if pass_stride is None else pass_stride)
+    dev = field.w0t.device
+    out = []
+    with _ctx(dev):
+        for i, stream_id in enumerate(MASK_STREAMS):
+            if not (sites >> i) & 1:
+                out.append(None)
+                continue
+            bits = torch.zeros(field.K, stride, 2, device=dev, dtype=torch.int32)
+            _run("mc_keep_bits", lambda: lib.unerf_mc_keep_bits(field.seed & 0xFFFFFFFF, field.K, int(first_sample), int(n_samples),
+                                                                 stream_id, 64, field.p_drop, _p(bits, torch.int32), stride, _stream()))
+            out.append(bits)
+    return KeepMasks(out[0], out[1], out[2], None, stride, 0)
+
+
 def field_fwd(origins, directions, sbins, field: FieldDev, near: float, far: float, ray_offset: int = 0,
               features: Optional[torch.Tensor] = None, image_width: int = 0, euclidean_bins: bool = False,
               sample_major: bool = False, spacing: int = 0, nonfinite_flag: Optional[torch.Tensor] = None,
-              packed: bool = False, workspace: Optional[Workspace] = None):
+              packed: bool = False, workspace: Optional[Workspace] = None, keep_masks: Optional[KeepMasks] = None):
     """-> density [B,R,S], rgb [B,R,S,3], aux, aux2 (see include/unerf.h).  image_width > 0 tells the kernel that
     rays [ray_offset, ray_offset+R) are consecutive pixels of a row-major image (8x4-pixel tiles: same results).
     euclidean_bins: `sbins` holds Euclidean bin edges (a caller-made RaySamples) instead of spacing-domain bins.
     sample_major: the outputs are planes density [B,S,R], rgb [B,S,3,R], aux [S,R] (composite_*_planes read them).
     packed (ACTIVE / MCDROPOUT, ray-major): -> None, rows [B,R,S,4] = (sigma, r, g, b), aux, None -- one 16-byte store
     per sample; composite_var / composite_moments take the rows as `rgb` with density=None.
-    workspace: the four outputs are views of that scratch arena (valid until the next call with it)."""
+    workspace: the four outputs are views of that scratch arena (valid until the next call with it).
+    keep_masks (MCDROPOUT): explicit keep masks instead of the counter generator's (unerf_field_fwd_masked); the call
+    reads rows keep_masks.sample_offset + r * S + s, and ray_offset is then only the tile hint of image_width."""
     if euclidean_bins:
         near = -1.0
     lib = _l.load()
@@ -978,6 +1059,13 @@ def field_fwd(origins, directions, sbins, field: FieldDev, near: float, far: flo
     cs.sample_major = 1 if sample_major else 0
     cs.packed_out = 1 if packed else 0
     cs.overflow_flag = _p(nonfinite_flag, torch.int32)      # set by the f16 matrix kernels (either form) on operand overflow
+    if keep_masks is not None:
+        km = keep_masks.cstruct(B)
+        with _ctx(dev):
+            _run("field_fwd_masked", lambda: lib.unerf_field_fwd_masked(
+                _p(origins), _p(directions), _p(sbins), R, S, near, far, spacing, ray_offset, C.byref(cs), _p(features),
+                _p(density), _p(rgb), _p(aux), _p(aux2), C.byref(km), _stream()))
+        return density, rgb, aux, aux2
     with _ctx(dev):
         _run("field_fwd", lambda: lib.unerf_field_fwd(_p(origins), _p(directions), _p(sbins), R, S, near, far, spacing, ray_offset,
                                      C.byref(cs), _p(features), _p(density), _p(rgb), _p(aux), _p(aux2), _stream()))

@@ -191,7 +191,11 @@ def sampling_stage(scene: NerfSceneDev, origins, directions, clip, ray_offset: i
 def shading_stage(scene: NerfSceneDev, origins, directions, sb, prop_depths, feats, clip, ray_offset: int = 0,
                   depth_noise: Optional[torch.Tensor] = None, depth_draws: int = 100, depth_seed: int = 0,
                   keep_density: bool = False, image_width: int = 0,
-                  nonfinite_flag: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
+                  nonfinite_flag: Optional[torch.Tensor] = None,
+                  keep_masks: Optional[ops.KeepMasks] = None) -> Dict[str, torch.Tensor]:
+    """keep_masks (MCDROPOUT): the FRAME's explicit keep masks (ops.KeepMasks over all its rays, row = ray * S + sample);
+    this launch group reads them from row ray_offset * S.  The fp32 re-render of the overflow guard and the two-stream
+    path come through here with the same masks."""
     f = scene.field
     # ACTIVE / MCDROPOUT: the field kernel writes sample-major planes (whole 32-byte sectors per store) and the
     # composite walks them with a lane per ray; LAPLACE keeps the ray-major layout its depth-draw kernel reads
@@ -201,7 +205,8 @@ def shading_stage(scene: NerfSceneDev, origins, directions, sb, prop_depths, fea
     packed = scene.packed_out and not planes and ops.supports_packed(f)
     density, rgb, aux, aux2 = ops.field_fwd(origins, directions, sb, f, scene.near, scene.far, ray_offset, features=feats,
                                             image_width=image_width, sample_major=planes, spacing=scene.spacing,
-                                            nonfinite_flag=nonfinite_flag, packed=packed, workspace=scene.workspace)
+                                            nonfinite_flag=nonfinite_flag, packed=packed, workspace=scene.workspace,
+                                            keep_masks=None if keep_masks is None else keep_masks.at(ray_offset * (sb.shape[1] - 1)))
     kw = dict(clip_minmax=clip, ray_offset=ray_offset, chunk_rays=scene.chunk_rays, spacing=scene.spacing,
               background=scene.background, nonfinite_flag=nonfinite_flag)
     res: Dict[str, torch.Tensor] = {}
@@ -262,6 +267,7 @@ def render_rays(scene: NerfSceneDev, origins: torch.Tensor, directions: torch.Te
                                                    depth_var depth_std prop_depth_i (+density)
       MCDROPOUT  mcdropout_models.py:121-126       means of every key + rgb_std depth_std expected_depth_std
       LAPLACE    laplace_model.py:523-530          rgb rgb_std accumulation depth depth_std expected_depth
+    keep_masks= (MCDROPOUT, with the other shading arguments): explicit keep masks of the frame, see shading_stage.
     """
     _l.require_gpu()
     R = origins.shape[0]
@@ -280,7 +286,8 @@ def render_camera(scene: NerfSceneDev, c2w: torch.Tensor, fx: float, fy: float, 
     two streams.  obb = (world_to_box [3,4], S [3]): the oriented crop box of `obb_box` (see crop_bins).
     distortion = the camera's `distortion_params` (k1, k2, k3, k4, p1, p2) or None: the rays are bent as
     Cameras.generate_rays bends them (unerf_generate_rays).  camera_type: nerfstudio's CameraType value (perspective 1,
-    fisheye 2, equirectangular 3, orthophoto 8: include/unerf.h)."""
+    fisheye 2, equirectangular 3, orthophoto 8: include/unerf.h).
+    keep_masks= (MCDROPOUT): an ops.KeepMasks over the H*W rays of the frame instead of the counter generator's masks."""
     _l.require_gpu()
     total = H * W
     dev = scene.device
