@@ -37,7 +37,10 @@ def reduce(src, dst):
 
 
 # the dominant field kernel of a method = the first kernel name with one of these prefixes (template arguments after the
-# prefix -- tcnn / sites / drop flags -- vary with the round)
+# prefix -- tcnn / sites / drop flags -- vary with the round).  The profiler prints a symbol's template arguments by their
+# declared TYPE, not by how the host code spells them: today's kernels (TCNN an int) appear only in the first spelling of
+# each entry; the `<0, false, ...` and shorter ones are kept to re-summarise the committed profiles/ of rounds 1 - 4, whose
+# builds had TCNN as a bool or no SITES / DROP / F1 parameters yet
 FIELD_KERNELS = {"active": ("field_kernel_mfma16<0, 0, false, false, false", "field_kernel_mfma16<0, false, false, false, false", "field_kernel_mfma<0, false"),
                  "active_f16": ("field_kernel_mfma16<0, 0, false, false, true", "field_kernel_mfma16<0, false, false, false, true"),
                  "mcdropout": ("field_kernel_mfma16<1, 0, false, true, false", "field_kernel_mfma16<1, false, false, true, false",

@@ -41,3 +41,9 @@ def test_the_built_library_passes_and_its_matrix_kernels_are_found(lib):
     assert len(mk) >= 30 and any("field_kernel_mfma16" in k for k in mk) and any("laplace" in k for k in mk)
     # the rasteriser, the sorts, the proposal kernels: no matrix instruction
     assert all(v["mfma"] == 0 for k, v in stats.items() if "raster" in k or "prop_patch" in k)
+    # the host's kernel selection (unerf_nerf.hip: field_launch) instantiates the field kernels it can launch and no others:
+    # 30 field_kernel_mfma16 + 12 field_kernel_mfma + 6 + 6 Laplace + 4 field_kernel + 3 field_kernel_generic, 11 of them
+    # the explicit-mask instances (mangled names: _Z<len>field_kernel...I<template arguments>)
+    import re
+    fk = [k for k in stats if re.match(r"_Z\d+field_kernel", k)]
+    assert len(fk) == 61 and sum("8KeepArgs" in k for k in fk) == 11, (len(fk), sorted(fk))

@@ -4,6 +4,7 @@
 #include "unerf_common.hpp"
 
 #include <mutex>
+#include <type_traits>
 #include <unordered_map>
 
 #include <cmath>
@@ -2449,6 +2450,7 @@ __device__ __forceinline__ void mf_pin8(uint32_t (&x)[8]) {
 // DROP: masks are generated (MCDROPOUT with K > 0 and p > 0).  A compile-time flag: as a run-time (uniform) flag every
 // k-step of the masked layers carried a branch and the operand quads were copied to merge the two paths.
 // XA = KeepArgs: explicit keep masks (unerf_field_fwd_masked), on the general SITES form
+// Which of the three (SITES, DROP) forms a call gets: field_launch(); its LDS bytes: mf16_lds_bytes().
 template <int MODE, int TCNN, bool SITES = false, bool DROP = false, bool F1 = false, typename... XA>
 // (the single-product K-pass kernel at 3 waves per SIMD was measured twice and lost both times: round 3, 168 VGPRs, 96 B of
 // scratch, trunk operands re-read from LDS -- 4.84 vs 3.89 ms per launch, profiles/r3_exp_f16_single_occ3.json; round 7,
@@ -3459,262 +3461,293 @@ static int mfma_grid_for(Kern kernel, int64_t num_tiles, size_t lds_bytes) {
     return (int)((blocks + 7) / 8 * 8);
 }
 // one persistent matrix-kernel launch: tile map from the image_width hint, LDS = the operand blob
-#define MF_LDS_FP32 ((size_t)UNERF_MFMA_BLOB_FLOATS * 4)
-#define MF_LDS_F16 MF_LDS_FP32
-#define MF_LDS_F16S ((size_t)UNERF_MFMA16_BLOB_FLOATS * 4)   // the "f16" form of field_kernel_mfma16: + the colour-2 slabs
 template <typename Kern, typename... Extra>   // extra: the KeepArgs of the explicit-mask kernels
 static void launch_matrix_kernel(Kern kernel, size_t lds_bytes, FieldArgs& a, hipStream_t st, Extra... extra) {
     const int64_t tiles = make_tiles(a, a.p.image_width);
     hipLaunchKernelGGL(kernel, dim3(mfma_grid_for(kernel, tiles, lds_bytes)), dim3(256), lds_bytes, st, a, (uint32_t)tiles,
                        make_fastdiv((uint32_t)a.S), extra...);
 }
+// Dynamic LDS of a matrix kernel: the fp32-sized operand blob, except that field_kernel_mfma16 gets the "f16" blob
+// (+ the colour-2 slabs) when F1 or DROP (explicit masks are a DROP form).
+constexpr size_t MF_LDS_BYTES = (size_t)UNERF_MFMA_BLOB_FLOATS * 4;
+// only the F1 kernels stage the larger blob; DROP is in the rule because these launches always had this byte count (it sizes the persistent grid)
+constexpr size_t mf16_lds_bytes(bool F1, bool DROP) { return (F1 || DROP) ? (size_t)UNERF_MFMA16_BLOB_FLOATS * 4 : MF_LDS_BYTES; }
 
-// masks = NULL: unerf_field_fwd.  Else unerf_field_fwd_masked: MC-dropout under explicit keep masks.
-static int field_fwd_impl(const float* origins, const float* directions, const float* sbins, int64_t R, int S,
-                          float near_plane, float far_plane, int spacing, int64_t ray_offset, const unerf_field_params* p,
-                          const float* features, float* density, float* rgb, float* aux, float* aux2,
-                          const unerf_keep_masks* masks, void* stream) {
-    UNERF_REQUIRE(p && (R == 0 || (origins && directions && sbins && (density || p->packed_out) && rgb)), "field_fwd: null pointer");
-    UNERF_REQUIRE(!p->packed_out || (p->mode != UNERF_FIELD_LAPLACE && !p->sample_major),
+// --------------------------------------------------------------------------------------
+// 5h. Host side of the field kernels (5, 5a', 5b*): check the arguments, fill FieldArgs, select and launch.
+// The kernel selection is field_launch() with the launch_* helpers above it, and nothing else (as a table: DESIGN.md 6,
+// "Which field kernel a call runs").
+// --------------------------------------------------------------------------------------
+// a run-time value in {0, 1, 2} as a compile-time constant handed to f: the TCNN argument of the matrix kernels and the
+// UNERF_FIELD_* mode (checked before: no other value gets here)
+template <typename F>
+static void with_int3(int v, F&& f) {
+    switch (v) {
+        case 0: f(std::integral_constant<int, 0>{}); break;
+        case 1: f(std::integral_constant<int, 1>{}); break;
+        case 2: f(std::integral_constant<int, 2>{}); break;
+    }
+}
+template <typename F>
+static void with_bool(bool b, F&& f) {
+    if (b) f(std::true_type{});
+    else f(std::false_type{});
+}
+// the TCNN template argument: 0 = torch-layout grid, 1 = tcnn layout, 2 = tcnn layout with half2 rows (grid_half)
+static int tcnn_arg(const unerf_field_params& p) { return p.tcnn_levels ? (p.grid_half ? 2 : 1) : 0; }
+
+// field_kernel_mfma16<MODE, tc, SITES, DROP, f1, XA...>: every grid layout and both colour-layer forms of one (MODE, SITES, DROP)
+template <int MODE, bool SITES, bool DROP, typename... XA>
+static void launch_mfma16(FieldArgs& a, hipStream_t st, XA... xa) {
+    with_int3(tcnn_arg(a.p), [&](auto tc) {
+        with_bool(a.p.f16_single != 0, [&](auto f1) {
+            constexpr bool F1 = decltype(f1)::value;
+            launch_matrix_kernel(field_kernel_mfma16<MODE, decltype(tc)::value, SITES, DROP, F1, XA...>, mf16_lds_bytes(F1, DROP), a, st, xa...);
+        });
+    });
+}
+// field_kernel_mfma<MODE, FEAT_IN, tc, XA...>: pre-gathered features come from the torch-layout grid only (checked), so
+// FEAT_IN exists with tc = 0 alone
+template <int MODE, typename... XA>
+static void launch_mfma(FieldArgs& a, hipStream_t st, XA... xa) {
+    if (a.features) return launch_matrix_kernel(field_kernel_mfma<MODE, true, 0, XA...>, MF_LDS_BYTES, a, st, xa...);
+    with_int3(tcnn_arg(a.p), [&](auto tc) {
+        launch_matrix_kernel(field_kernel_mfma<MODE, false, decltype(tc)::value, XA...>, MF_LDS_BYTES, a, st, xa...);
+    });
+}
+// field_kernel<MODE, XA...> (VALU, one wave per 64 samples); the K passes keep a second activation buffer in LDS
+template <int MODE, typename... XA>
+static void launch_valu(FieldArgs& a, hipStream_t st, XA... xa) {
+    constexpr size_t lds_bytes = (MODE == UNERF_FIELD_MCDROPOUT ? 2 : 1) * 64 * 64 * 4;
+    hipLaunchKernelGGL((field_kernel<MODE, XA...>), dim3(blocks_for(a.R * (int64_t)a.S, 64)), dim3(64), lds_bytes, st, a, xa...);
+}
+// ACTIVE / MCDROPOUT: the family follows the operand blobs the caller packed -- split-f16 MFMA, else fp32 MFMA (the one
+// that reads pre-gathered features), else VALU.  (SITES, DROP) only reaches field_kernel_mfma16.
+template <int MODE, bool SITES, bool DROP, typename... XA>
+static void launch_by_blob(FieldArgs& a, hipStream_t st, XA... xa) {
+    if (a.p.mfma16_blob && !a.features) launch_mfma16<MODE, SITES, DROP, XA...>(a, st, xa...);
+    else if (a.p.mfma_blob) launch_mfma<MODE, XA...>(a, st, xa...);
+    else launch_valu<MODE, XA...>(a, st, xa...);
+}
+
+constexpr int DROP_SITES_KNOWN = UNERF_DROP_TRUNK | UNERF_DROP_HEAD0 | UNERF_DROP_HEAD1 | UNERF_DROP_HEADIN;
+constexpr int DROP_SITES_DEFAULT = UNERF_DROP_TRUNK | UNERF_DROP_HEAD1;   // the reference's Dropout placement
+// the site set a call asks for; FieldArgs.drop_sites is this set while masks are applied and 0 otherwise
+static int requested_drop_sites(const unerf_field_params& p) { return p.drop_sites ? p.drop_sites : DROP_SITES_DEFAULT; }
+
+// Widths left 0 are nerfacto's (only field_kernel_generic reads them).  True: the any-width slow path, widths given and
+// different from nerfacto's 64 / 64 / 15 / 2 (or L != 16)
+static bool field_set_widths(unerf_field_params& p) {
+    if (!p.hidden) p.hidden = 64;
+    if (!p.hidden_color) p.hidden_color = 64;
+    if (!p.geo_dim) p.geo_dim = 15;
+    if (!p.feat_per_level) p.feat_per_level = 2;
+    if (!p.app_dim) p.app_dim = 32;
+    const bool headin_site = p.mode == UNERF_FIELD_MCDROPOUT && (p.drop_sites & UNERF_DROP_HEADIN);
+    return p.hidden != 64 || p.hidden_color != 64 || p.geo_dim != 15 || p.feat_per_level != 2 || p.L != 16 || (p.app_dim != 32 && headin_site);
+}
+// LDS rows of the any-width kernel: the widest activation (widths range-checked before); 64 lanes x 4 buffers x 4 bytes per row
+static int generic_rows(const unerf_field_params& p) {
+    int rows = p.L * p.feat_per_level;
+    for (int v : {p.hidden, p.hidden_color, 16 + p.geo_dim + p.app_dim, 1 + p.geo_dim + 1}) rows = v > rows ? v : rows;
+    return rows;
+}
+static size_t generic_lds_bytes(int rows) { return (size_t)rows * 64 * 4 * 4; }
+
+// Job 1a, every call (a: the call's arguments as given): what is refused even when R == 0.
+static int field_check_args(const FieldArgs& a, float near_plane, bool generic, const unerf_keep_masks* masks) {
+    const unerf_field_params& p = a.p;
+    const float* features = a.features;
+    UNERF_REQUIRE(!p.packed_out || (p.mode != UNERF_FIELD_LAPLACE && !p.sample_major),
                   "field_fwd: packed_out rows are written by the ACTIVE / MCDROPOUT kernels in the ray-major layout only");
-    UNERF_REQUIRE(p->table && (p->scalings || p->tcnn_levels) && p->w0t && p->b0 && p->w1t && p->b1 && p->h0t &&
-                      p->hb0 && p->h1t && p->hb1 && p->h2t && p->hb2,
+    UNERF_REQUIRE(p.table && (p.scalings || p.tcnn_levels) && p.w0t && p.b0 && p.w1t && p.b1 && p.h0t &&
+                      p.hb0 && p.h1t && p.hb1 && p.h2t && p.hb2,
                   "field_fwd: null weight pointer");
-    // any-width slow path (field_kernel_generic): widths given and different from nerfacto's 64 / 64 / 15 / 2 (or L != 16)
-    const int gH = p->hidden ? p->hidden : 64, gHC = p->hidden_color ? p->hidden_color : 64, gG = p->geo_dim ? p->geo_dim : 15;
-    const int gF = p->feat_per_level ? p->feat_per_level : 2, gAD = p->app_dim ? p->app_dim : 32;
-    const bool headin_site = p->mode == UNERF_FIELD_MCDROPOUT && (p->drop_sites & UNERF_DROP_HEADIN);
-    const bool generic = gH != 64 || gHC != 64 || gG != 15 || gF != 2 || p->L != 16 || (gAD != 32 && headin_site);
-    UNERF_REQUIRE(generic || p->L == 16, "field_fwd: L=%d", p->L);
+    UNERF_REQUIRE(generic || p.L == 16, "field_fwd: L=%d", p.L);
     if (generic) {
-        UNERF_REQUIRE(p->L >= 1 && p->L <= 32 && (gF == 2 || gF == 4) && gH >= 1 && gH <= 256 && gHC >= 1 && gHC <= 256 && gG >= 0 && gG <= 64,
-                      "field_fwd: widths outside the any-width kernel's range (L=%d F=%d hidden=%d hidden_color=%d geo=%d)", p->L, gF, gH, gHC, gG);
-        UNERF_REQUIRE(gF == 2 || !p->tcnn_levels, "field_fwd: features_per_level = 4 is built for the torch-layout grid");
-        UNERF_REQUIRE(!features && !p->sample_major && !p->packed_out, "field_fwd: the any-width kernel writes the plain ray-major layout only");
-        UNERF_REQUIRE(p->mode != UNERF_FIELD_MCDROPOUT || (gH <= 128 && gHC <= 128 && (!headin_site || 16 + gG + gAD <= 128)),
+        UNERF_REQUIRE(p.L >= 1 && p.L <= 32 && (p.feat_per_level == 2 || p.feat_per_level == 4) && p.hidden >= 1 && p.hidden <= 256 &&
+                          p.hidden_color >= 1 && p.hidden_color <= 256 && p.geo_dim >= 0 && p.geo_dim <= 64,
+                      "field_fwd: widths outside the any-width kernel's range (L=%d F=%d hidden=%d hidden_color=%d geo=%d)", p.L,
+                      p.feat_per_level, p.hidden, p.hidden_color, p.geo_dim);
+        UNERF_REQUIRE(p.feat_per_level == 2 || !p.tcnn_levels, "field_fwd: features_per_level = 4 is built for the torch-layout grid");
+        UNERF_REQUIRE(!features && !p.sample_major && !p.packed_out, "field_fwd: the any-width kernel writes the plain ray-major layout only");
+        UNERF_REQUIRE(p.mode != UNERF_FIELD_MCDROPOUT || (p.hidden <= 128 && p.hidden_color <= 128 &&
+                                                          (!(p.drop_sites & UNERF_DROP_HEADIN) || 16 + p.geo_dim + p.app_dim <= 128)),
                       "field_fwd: a dropout site has at most 128 units (mask stream layout)");
     }
-    UNERF_REQUIRE(!features || (p->mfma_blob && p->mode != UNERF_FIELD_LAPLACE),
+    UNERF_REQUIRE(!features || (p.mfma_blob && p.mode != UNERF_FIELD_LAPLACE),
                   "field_fwd: pre-gathered features are consumed by the MFMA kernel only (ACTIVE/MCDROPOUT with mfma_blob)");
-    UNERF_REQUIRE(p->tcnn_levels || (p->log2T >= 1 && p->log2T <= 24), "field_fwd: bad log2T=%d", p->log2T);
-    UNERF_REQUIRE(!(p->tcnn_levels && features), "field_fwd: pre-gathered feature planes are built for the torch-layout grid only");
-    UNERF_REQUIRE(!p->grid_half || p->tcnn_levels, "field_fwd: grid_half (half2 rows, tcnn's half arithmetic) needs a tcnn-layout grid");
-    UNERF_REQUIRE(R >= 0 && S >= 1, "field_fwd: bad R/S");
+    UNERF_REQUIRE(p.tcnn_levels || (p.log2T >= 1 && p.log2T <= 24), "field_fwd: bad log2T=%d", p.log2T);
+    UNERF_REQUIRE(!(p.tcnn_levels && features), "field_fwd: pre-gathered feature planes are built for the torch-layout grid only");
+    UNERF_REQUIRE(!p.grid_half || p.tcnn_levels, "field_fwd: grid_half (half2 rows, tcnn's half arithmetic) needs a tcnn-layout grid");
+    UNERF_REQUIRE(a.R >= 0 && a.S >= 1, "field_fwd: bad R/S");
     UNERF_REQUIRE(!(near_plane < 0.f && features), "field_fwd: Euclidean bins (near_plane < 0) cannot be combined with pre-gathered features");
-    UNERF_REQUIRE((uint64_t)(ray_offset + R) * (uint64_t)S < (1ull << 32),
+    UNERF_REQUIRE((uint64_t)(a.ray_offset + a.R) * (uint64_t)a.S < (1ull << 32),
                   "field_fwd: sample index exceeds 32 bits (RNG counter)");
-    UNERF_REQUIRE(!p->sample_major || (p->mode != UNERF_FIELD_LAPLACE && (p->mfma16_blob || p->mfma_blob)),
+    UNERF_REQUIRE(!p.sample_major || (p.mode != UNERF_FIELD_LAPLACE && (p.mfma16_blob || p.mfma_blob)),
                   "field_fwd: sample_major planes are written by the ACTIVE / MCDROPOUT matrix kernels only");
-    KeepArgs xm = {};
+    if (p.mode == UNERF_FIELD_MCDROPOUT) {   // with or without explicit masks
+        UNERF_REQUIRE(p.K >= 0 && p.p_drop >= 0.f && p.p_drop < 1.f, "field_fwd MCDROPOUT: bad K/p_drop");
+        // (the any-width kernel tests the four known bits and has always let others through)
+        UNERF_REQUIRE(generic || (p.drop_sites & ~DROP_SITES_KNOWN) == 0, "field_fwd MCDROPOUT: unknown bits in drop_sites=%d", p.drop_sites);
+    }
     if (masks) {   // explicit keep masks: every refusal before any launch; never a fall-back to the generator
-        UNERF_REQUIRE(p->mode == UNERF_FIELD_MCDROPOUT, "field_fwd_masked: explicit keep masks are an MCDROPOUT mode (mode=%d)", p->mode);
-        UNERF_REQUIRE(p->K > 0, "field_fwd_masked: K=%d, explicit keep masks need K >= 1 passes", p->K);
-        UNERF_REQUIRE(p->p_drop >= 0.f && p->p_drop < 1.f, "field_fwd_masked: bad p_drop");
-        UNERF_REQUIRE((p->drop_sites & ~(UNERF_DROP_TRUNK | UNERF_DROP_HEAD0 | UNERF_DROP_HEAD1 | UNERF_DROP_HEADIN)) == 0,
-                      "field_fwd_masked: unknown bits in drop_sites=%d", p->drop_sites);
-        UNERF_REQUIRE(!(p->drop_sites & UNERF_DROP_HEADIN),
+        UNERF_REQUIRE(p.mode == UNERF_FIELD_MCDROPOUT, "field_fwd_masked: explicit keep masks are an MCDROPOUT mode (mode=%d)", p.mode);
+        UNERF_REQUIRE(p.K > 0, "field_fwd_masked: K=%d, explicit keep masks need K >= 1 passes", p.K);
+        UNERF_REQUIRE(!(p.drop_sites & UNERF_DROP_HEADIN),
                       "field_fwd_masked: UNERF_DROP_HEADIN is out of scope of the explicit-mask mode (not built; no generator fall-back)");
         UNERF_REQUIRE(!generic, "field_fwd_masked: the any-width kernel is out of scope of the explicit-mask mode "
                                 "(nerfacto widths 64 / 64 / 15 / 2 and L = 16 only; no generator fall-back)");
-        const int sites = p->drop_sites ? p->drop_sites : (UNERF_DROP_TRUNK | UNERF_DROP_HEAD1);
+        const int sites = requested_drop_sites(p);
         static const char* const names[4] = {"TRUNK", "HEAD0", "HEAD1", "HEADIN"};
         for (int i = 0; i < 4; ++i) {
             UNERF_REQUIRE(!((sites >> i) & 1) || masks->site[i], "field_fwd_masked: site %s is active (drop_sites=%d) but its mask array is NULL", names[i], sites);
             UNERF_REQUIRE(((sites >> i) & 1) || !masks->site[i], "field_fwd_masked: a mask array for site %s, which is not active (drop_sites=%d)", names[i], sites);
         }
-        UNERF_REQUIRE(masks->sample_offset >= 0 && masks->pass_stride >= masks->sample_offset + R * (int64_t)S,
+        UNERF_REQUIRE(masks->sample_offset >= 0 && masks->pass_stride >= masks->sample_offset + a.R * (int64_t)a.S,
                       "field_fwd_masked: pass_stride=%lld < sample_offset + R*S = %lld + %lld", (long long)masks->pass_stride,
-                      (long long)masks->sample_offset, (long long)(R * (int64_t)S));
-        xm.site[0] = masks->site[0]; xm.site[1] = masks->site[1]; xm.site[2] = masks->site[2];
-        xm.pass_stride = masks->pass_stride; xm.sample_offset = masks->sample_offset;
+                      (long long)masks->sample_offset, (long long)(a.R * (int64_t)a.S));
     }
-    if (R == 0) return UNERF_OK;
-    FieldArgs a;
-    a.origins = origins; a.dirs = directions; a.sbins = sbins; a.R = R; a.S = S;
-    UNERF_REQUIRE_SPACING(spacing); a.lin = spacing;
+    return UNERF_OK;
+}
+
+// Job 2: the derived fields of FieldArgs (nothing here can fail).
+static void field_fill_args(FieldArgs& a, float near_plane, float far_plane, int spacing, const unerf_keep_masks* masks) {
+    a.lin = spacing;
     a.s_near = near_plane < 0.f ? -1.f : unerf_spacing_of(near_plane, spacing);   // < 0: sbins are Euclidean edges
-    a.s_far = unerf_spacing_of(far_plane, spacing); a.ray_offset = ray_offset;
-    a.p = *p; a.density = density; a.rgb = rgb; a.aux = aux; a.aux2 = aux2;
+    a.s_far = unerf_spacing_of(far_plane, spacing);
     if (a.p.n_lap_rgb <= 0) a.p.n_lap_rgb = a.p.n_lap;
-    a.div_chunk = make_fastdiv(p->lap_chunk_rays > 0 ? (uint32_t)p->lap_chunk_rays : 1u);
-    a.chunk0 = (uint32_t)ray_offset;
-    a.features = features;
-    a.box = make_norm_box(p->use_aabb, p->aabb);
-    UNERF_REQUIRE(!(features && p->use_aabb), "field_fwd: pre-gathered feature planes are built for the contraction path only");
-    {   // keep iff (signed 16-bit half) < thr_s = round((1-p) 65536) - 32768; p = 0 keeps everything (no masks)
-        const long thr = lrint((1.0 - (double)p->p_drop) * 65536.0);
-        a.drop_on = (p->mode == UNERF_FIELD_MCDROPOUT && p->K > 0 && thr < 65536) ? 1 : 0;
-        a.drop_sites = a.drop_on ? (p->drop_sites ? p->drop_sites : (UNERF_DROP_TRUNK | UNERF_DROP_HEAD1)) : 0;
+    a.div_chunk = make_fastdiv(a.p.lap_chunk_rays > 0 ? (uint32_t)a.p.lap_chunk_rays : 1u);
+    a.chunk0 = (uint32_t)a.ray_offset;
+    if (a.p.mode == UNERF_FIELD_LAPLACE && a.p.lap_chunk_rays != 0) a.p.image_width = 0;   // per-chunk sample sets: 1-D tiles that never straddle two sets
+    a.box = make_norm_box(a.p.use_aabb, a.p.aabb);
+    if (masks) {   // the words are made of the keep bits (xm_word): on at every p, and any threshold in (-32768, 32767] reads them
+        a.drop_on = 1;
+        a.keep_hi = 0;
+        a.keep_pk = 0u;
+    } else {   // keep iff (signed 16-bit half) < thr_s = round((1-p) 65536) - 32768; p = 0 keeps everything (no masks)
+        const long thr = lrint((1.0 - (double)a.p.p_drop) * 65536.0);
+        a.drop_on = (a.p.mode == UNERF_FIELD_MCDROPOUT && a.p.K > 0 && thr < 65536) ? 1 : 0;
         const int32_t thr_s = (int32_t)(thr < 65536 ? thr : 65535) - 32768;
         a.keep_hi = (int32_t)((uint32_t)thr_s << 16);
         a.keep_pk = ((uint32_t)thr_s & 0xFFFFu) * 0x10001u;
     }
-    if (masks) {   // the words are made of the keep bits (xm_word): on at every p, and any threshold in (-32768, 32767] reads them
-        a.drop_on = 1;
-        a.drop_sites = p->drop_sites ? p->drop_sites : (UNERF_DROP_TRUNK | UNERF_DROP_HEAD1);
-        a.keep_hi = 0;
-        a.keep_pk = 0u;
-    }
-    a.drop_scale = 1.f / (1.f - p->p_drop);
-    dim3 grid(blocks_for(R * (int64_t)S, 64)), block(64);
-    hipStream_t st = (hipStream_t)stream;
-    const int tc = p->tcnn_levels ? (p->grid_half ? 2 : 1) : 0;   // the TCNN template argument of the matrix kernels
-    const bool f1 = p->f16_single != 0;
-    UNERF_REQUIRE(!f1 || (p->mfma16_blob && !features && (p->mode != UNERF_FIELD_LAPLACE || (p->lap16_blob && p->n_lap <= 32 * LAP_BLOCKS))),
+    a.drop_sites = a.drop_on ? requested_drop_sites(a.p) : 0;
+    a.drop_scale = 1.f / (1.f - a.p.p_drop);
+}
+
+// Job 1b, non-empty calls only (a: filled): what an empty call has never been refused for.
+static int field_check_nonempty(const FieldArgs& a, int spacing, bool generic) {
+    const unerf_field_params& p = a.p;
+    UNERF_REQUIRE_SPACING(spacing);
+    UNERF_REQUIRE(!(a.features && p.use_aabb), "field_fwd: pre-gathered feature planes are built for the contraction path only");
+    UNERF_REQUIRE(!p.f16_single || (p.mfma16_blob && !a.features && (p.mode != UNERF_FIELD_LAPLACE || (p.lap16_blob && p.n_lap <= 32 * LAP_BLOCKS))),
                   "field_fwd: f16_single needs mfma16_blob (and lap16_blob with n_lap <= 128 for LAPLACE), without pre-gathered features");
     if (generic) {
-        a.p.hidden = gH; a.p.hidden_color = gHC; a.p.geo_dim = gG; a.p.feat_per_level = gF; a.p.app_dim = gAD;
-        int rows = p->L * gF;
-        for (int v : {gH, gHC, 16 + gG + gAD, 1 + gG + 1}) rows = v > rows ? v : rows;
-        const size_t lds_bytes = (size_t)rows * 64 * 4 * 4;
+        const size_t lds_bytes = generic_lds_bytes(generic_rows(p));
         UNERF_REQUIRE(lds_bytes <= 160 * 1024, "field_fwd: %zu bytes of LDS for the any-width kernel", lds_bytes);
-        const int want1 = p->mode == UNERF_FIELD_ACTIVE ? gG + 2 : (p->mode == UNERF_FIELD_MCDROPOUT ? gG + 1 : gG);
-        UNERF_REQUIRE(p->out1 == want1, "field_fwd: out1=%d, expected %d for geo_dim=%d in this mode", p->out1, want1, gG);
-        if (a.drop_sites & UNERF_DROP_HEADIN)
-            UNERF_REQUIRE(p->h0_full_t && p->hb0_raw && p->app_embed, "field_fwd MCDROPOUT: UNERF_DROP_HEADIN needs h0_full_t / hb0_raw / app_embed");
-#define UNERF_GENERIC_LAUNCH(MODE_)                                                                                      \
-    do {                                                                                                                 \
-        if (lds_bytes > 64 * 1024)                                                                                       \
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(field_kernel_generic<MODE_>),                        \
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);                       \
-        hipLaunchKernelGGL((field_kernel_generic<MODE_>), grid, block, lds_bytes, st, a, rows);                          \
-    } while (0)
-        switch (p->mode) {
-            case UNERF_FIELD_ACTIVE:
-                UNERF_REQUIRE(aux, "field_fwd ACTIVE: aux (beta) must be non-null");
-                UNERF_GENERIC_LAUNCH(UNERF_FIELD_ACTIVE);
-                break;
-            case UNERF_FIELD_MCDROPOUT:
-                UNERF_REQUIRE(p->K >= 0 && p->p_drop >= 0.f && p->p_drop < 1.f, "field_fwd MCDROPOUT: bad K/p_drop");
-                UNERF_GENERIC_LAUNCH(UNERF_FIELD_MCDROPOUT);
-                break;
-            case UNERF_FIELD_LAPLACE:
-                UNERF_REQUIRE(aux && aux2 && p->ws_density && p->ws_rgb && p->n_lap >= 1, "field_fwd LAPLACE: need aux, aux2, ws_density, ws_rgb, n_lap>=1");
-                UNERF_REQUIRE(p->lap_chunk_rays == 0 || (ray_offset + R - 1) / p->lap_chunk_rays < p->lap_sets, "field_fwd LAPLACE: rays reach past the sample sets");
-                UNERF_GENERIC_LAUNCH(UNERF_FIELD_LAPLACE);
-                break;
-            default:
-                unerf_set_error("field_fwd: unknown mode %d", p->mode);
-                return UNERF_ERR_ARG;
-        }
-#undef UNERF_GENERIC_LAUNCH
-        return unerf_check_launch("field_fwd (any-width kernel)");
+        const int want1 = p.geo_dim + (p.mode == UNERF_FIELD_ACTIVE ? 2 : (p.mode == UNERF_FIELD_MCDROPOUT ? 1 : 0));
+        UNERF_REQUIRE(p.out1 == want1, "field_fwd: out1=%d, expected %d for geo_dim=%d in this mode", p.out1, want1, p.geo_dim);
     }
-    switch (p->mode) {
+    switch (p.mode) {
         case UNERF_FIELD_ACTIVE:
-            UNERF_REQUIRE(p->out1 == 17 && aux, "field_fwd ACTIVE: out1 must be 17 and aux (beta) non-null");
-            if (p->mfma16_blob && !features && f1) {
-                if (tc == 2) launch_matrix_kernel(field_kernel_mfma16<UNERF_FIELD_ACTIVE, 2, false, false, true>, MF_LDS_F16S, a, st);
-                else if (tc) launch_matrix_kernel(field_kernel_mfma16<UNERF_FIELD_ACTIVE, 1, false, false, true>, MF_LDS_F16S, a, st);
-                else launch_matrix_kernel(field_kernel_mfma16<UNERF_FIELD_ACTIVE, false, false, false, true>, MF_LDS_F16S, a, st);
-            } else if (p->mfma16_blob && !features) {
-                if (tc == 2) launch_matrix_kernel(field_kernel_mfma16<UNERF_FIELD_ACTIVE, 2>, MF_LDS_F16, a, st);
-                else if (tc) launch_matrix_kernel(field_kernel_mfma16<UNERF_FIELD_ACTIVE, 1>, MF_LDS_F16, a, st);
-                else launch_matrix_kernel(field_kernel_mfma16<UNERF_FIELD_ACTIVE, false>, MF_LDS_F16, a, st);
-            } else if (p->mfma_blob) {
-                if (features) launch_matrix_kernel(field_kernel_mfma<UNERF_FIELD_ACTIVE, true>, MF_LDS_FP32, a, st);
-                else if (tc == 2) launch_matrix_kernel(field_kernel_mfma<UNERF_FIELD_ACTIVE, false, 2>, MF_LDS_FP32, a, st);
-                else if (tc) launch_matrix_kernel(field_kernel_mfma<UNERF_FIELD_ACTIVE, false, 1>, MF_LDS_FP32, a, st);
-                else launch_matrix_kernel(field_kernel_mfma<UNERF_FIELD_ACTIVE, false>, MF_LDS_FP32, a, st);
-            } else {
-                hipLaunchKernelGGL((field_kernel<UNERF_FIELD_ACTIVE>), grid, block, 64 * 64 * 4, st, a);
-            }
+            if (generic) UNERF_REQUIRE(a.aux, "field_fwd ACTIVE: aux (beta) must be non-null");
+            else UNERF_REQUIRE(p.out1 == 17 && a.aux, "field_fwd ACTIVE: out1 must be 17 and aux (beta) non-null");
             break;
         case UNERF_FIELD_MCDROPOUT:
-            UNERF_REQUIRE(p->out1 == 16, "field_fwd MCDROPOUT: out1 must be 16");
-            UNERF_REQUIRE(p->K >= 0 && p->p_drop >= 0.f && p->p_drop < 1.f, "field_fwd MCDROPOUT: bad K/p_drop");
-            UNERF_REQUIRE((p->drop_sites & ~(UNERF_DROP_TRUNK | UNERF_DROP_HEAD0 | UNERF_DROP_HEAD1 | UNERF_DROP_HEADIN)) == 0,
-                          "field_fwd MCDROPOUT: unknown bits in drop_sites=%d", p->drop_sites);
-            if (masks) {   // explicit keep masks: the same kernel selection, each in its XM instantiation (general SITES form)
-                if (p->mfma16_blob && !features && f1) {
-                    if (tc == 2) launch_matrix_kernel(field_kernel_mfma16<UNERF_FIELD_MCDROPOUT, 2, true, true, true, KeepArgs>, MF_LDS_F16S, a, st, xm);
-                    else if (tc) launch_matrix_kernel(field_kernel_mfma16<UNERF_FIELD_MCDROPOUT, 1, true, true, true, KeepArgs>, MF_LDS_F16S, a, st, xm);
-                    else launch_matrix_kernel(field_kernel_mfma16<UNERF_FIELD_MCDROPOUT, 0, true, true, true, KeepArgs>, MF_LDS_F16S, a, st, xm);
-                } else if (p->mfma16_blob && !features) {
-                    if (tc == 2) launch_matrix_kernel(field_kernel_mfma16<UNERF_FIELD_MCDROPOUT, 2, true, true, false, KeepArgs>, MF_LDS_F16S, a, st, xm);
-                    else if (tc) launch_matrix_kernel(field_kernel_mfma16<UNERF_FIELD_MCDROPOUT, 1, true, true, false, KeepArgs>, MF_LDS_F16S, a, st, xm);
-                    else launch_matrix_kernel(field_kernel_mfma16<UNERF_FIELD_MCDROPOUT, 0, true, true, false, KeepArgs>, MF_LDS_F16S, a, st, xm);
-                } else if (p->mfma_blob) {
-                    if (features) launch_matrix_kernel(field_kernel_mfma<UNERF_FIELD_MCDROPOUT, true, 0, KeepArgs>, MF_LDS_FP32, a, st, xm);
-                    else if (tc == 2) launch_matrix_kernel(field_kernel_mfma<UNERF_FIELD_MCDROPOUT, false, 2, KeepArgs>, MF_LDS_FP32, a, st, xm);
-                    else if (tc) launch_matrix_kernel(field_kernel_mfma<UNERF_FIELD_MCDROPOUT, false, 1, KeepArgs>, MF_LDS_FP32, a, st, xm);
-                    else launch_matrix_kernel(field_kernel_mfma<UNERF_FIELD_MCDROPOUT, false, 0, KeepArgs>, MF_LDS_FP32, a, st, xm);
-                } else {
-                    hipLaunchKernelGGL((field_kernel<UNERF_FIELD_MCDROPOUT, KeepArgs>), grid, block, 2 * 64 * 64 * 4, st, a, xm);
-                }
-            } else if (a.drop_sites & UNERF_DROP_HEADIN) {   // dropout on the head's inputs: the VALU kernel (include/unerf.h)
-                UNERF_REQUIRE(p->h0_full_t && p->hb0_raw && p->app_embed,
+            UNERF_REQUIRE(generic || p.out1 == 16, "field_fwd MCDROPOUT: out1 must be 16");
+            if (a.drop_sites & UNERF_DROP_HEADIN) {   // dropout on the head's inputs (include/unerf.h)
+                UNERF_REQUIRE(p.h0_full_t && p.hb0_raw && p.app_embed,
                               "field_fwd MCDROPOUT: UNERF_DROP_HEADIN needs h0_full_t / hb0_raw / app_embed");
-                UNERF_REQUIRE(!features && !p->sample_major,
+                UNERF_REQUIRE(!a.features && !p.sample_major,
                               "field_fwd MCDROPOUT: UNERF_DROP_HEADIN has no feature-plane / sample-major form");
-                hipLaunchKernelGGL((field_kernel<UNERF_FIELD_MCDROPOUT>), grid, block, 2 * 64 * 64 * 4, st, a);
-            } else if (p->mfma16_blob && !features && f1) {
-                const bool head0 = a.drop_on && a.drop_sites != (UNERF_DROP_TRUNK | UNERF_DROP_HEAD1);   // non-default sites
-                if (tc == 2 && head0) launch_matrix_kernel(field_kernel_mfma16<UNERF_FIELD_MCDROPOUT, 2, true, true, true>, MF_LDS_F16S, a, st);
-                else if (tc && head0) launch_matrix_kernel(field_kernel_mfma16<UNERF_FIELD_MCDROPOUT, 1, true, true, true>, MF_LDS_F16S, a, st);
-                else if (head0) launch_matrix_kernel(field_kernel_mfma16<UNERF_FIELD_MCDROPOUT, false, true, true, true>, MF_LDS_F16S, a, st);
-                else if (tc == 2 && a.drop_on) launch_matrix_kernel(field_kernel_mfma16<UNERF_FIELD_MCDROPOUT, 2, false, true, true>, MF_LDS_F16S, a, st);
-                else if (tc && a.drop_on) launch_matrix_kernel(field_kernel_mfma16<UNERF_FIELD_MCDROPOUT, 1, false, true, true>, MF_LDS_F16S, a, st);
-                else if (a.drop_on) launch_matrix_kernel(field_kernel_mfma16<UNERF_FIELD_MCDROPOUT, false, false, true, true>, MF_LDS_F16S, a, st);
-                else if (tc == 2) launch_matrix_kernel(field_kernel_mfma16<UNERF_FIELD_MCDROPOUT, 2, false, false, true>, MF_LDS_F16S, a, st);
-                else if (tc) launch_matrix_kernel(field_kernel_mfma16<UNERF_FIELD_MCDROPOUT, 1, false, false, true>, MF_LDS_F16S, a, st);
-                else launch_matrix_kernel(field_kernel_mfma16<UNERF_FIELD_MCDROPOUT, false, false, false, true>, MF_LDS_F16S, a, st);
-            } else if (p->mfma16_blob && !features) {
-                const bool head0 = a.drop_on && a.drop_sites != (UNERF_DROP_TRUNK | UNERF_DROP_HEAD1);   // non-default sites
-                if (tc == 2 && head0) launch_matrix_kernel(field_kernel_mfma16<UNERF_FIELD_MCDROPOUT, 2, true, true>, MF_LDS_F16S, a, st);
-                else if (tc && head0) launch_matrix_kernel(field_kernel_mfma16<UNERF_FIELD_MCDROPOUT, 1, true, true>, MF_LDS_F16S, a, st);
-                else if (head0) launch_matrix_kernel(field_kernel_mfma16<UNERF_FIELD_MCDROPOUT, false, true, true>, MF_LDS_F16S, a, st);
-                else if (tc == 2 && a.drop_on) launch_matrix_kernel(field_kernel_mfma16<UNERF_FIELD_MCDROPOUT, 2, false, true>, MF_LDS_F16S, a, st);
-                else if (tc && a.drop_on) launch_matrix_kernel(field_kernel_mfma16<UNERF_FIELD_MCDROPOUT, 1, false, true>, MF_LDS_F16S, a, st);
-                else if (a.drop_on) launch_matrix_kernel(field_kernel_mfma16<UNERF_FIELD_MCDROPOUT, false, false, true>, MF_LDS_F16S, a, st);
-                else if (tc == 2) launch_matrix_kernel(field_kernel_mfma16<UNERF_FIELD_MCDROPOUT, 2>, MF_LDS_F16, a, st);
-                else if (tc) launch_matrix_kernel(field_kernel_mfma16<UNERF_FIELD_MCDROPOUT, 1>, MF_LDS_F16, a, st);
-                else launch_matrix_kernel(field_kernel_mfma16<UNERF_FIELD_MCDROPOUT, false>, MF_LDS_F16, a, st);
-            } else if (p->mfma_blob) {
-                if (features) launch_matrix_kernel(field_kernel_mfma<UNERF_FIELD_MCDROPOUT, true>, MF_LDS_FP32, a, st);
-                else if (tc == 2) launch_matrix_kernel(field_kernel_mfma<UNERF_FIELD_MCDROPOUT, false, 2>, MF_LDS_FP32, a, st);
-                else if (tc) launch_matrix_kernel(field_kernel_mfma<UNERF_FIELD_MCDROPOUT, false, 1>, MF_LDS_FP32, a, st);
-                else launch_matrix_kernel(field_kernel_mfma<UNERF_FIELD_MCDROPOUT, false>, MF_LDS_FP32, a, st);
-            } else {
-                hipLaunchKernelGGL((field_kernel<UNERF_FIELD_MCDROPOUT>), grid, block, 2 * 64 * 64 * 4, st, a);
             }
             break;
         case UNERF_FIELD_LAPLACE:
-            UNERF_REQUIRE(p->out1 == 15 && aux && aux2 && p->ws_density && p->ws_rgb && p->n_lap >= 1,
-                          "field_fwd LAPLACE: need out1=15, aux, aux2, ws_density, ws_rgb, n_lap>=1");
-            UNERF_REQUIRE(!(p->lap_blob || p->lap16_blob) || a.p.n_lap_rgb <= 32 * LAP_BLOCKS || p->n_lap > 32 * LAP_BLOCKS,
-                          "field_fwd LAPLACE: n_lap_rgb=%d rows do not fit the head blobs (at most %d); pass them as ws_* only",
-                          a.p.n_lap_rgb, 32 * LAP_BLOCKS);
-            if (p->lap_chunk_rays != 0) {   // per-chunk sample sets: 1-D tiles that never straddle two sets
-                UNERF_REQUIRE(p->lap_chunk_rays > 0 && p->lap_chunk_rays % 32 == 0 && ray_offset % 32 == 0 && p->lap_sets >= 1,
-                              "field_fwd LAPLACE: lap_chunk_rays=%d and ray_offset=%lld must be multiples of 32, lap_sets=%d >= 1",
-                              p->lap_chunk_rays, (long long)ray_offset, p->lap_sets);
-                UNERF_REQUIRE((ray_offset + R - 1) / p->lap_chunk_rays < p->lap_sets,
-                              "field_fwd LAPLACE: rays [%lld, +%lld) reach past the %d sample sets of %d rays",
-                              (long long)ray_offset, (long long)R, p->lap_sets, p->lap_chunk_rays);
-                a.p.image_width = 0;
-            }
-            if (p->mfma16_blob && p->lap16_blob && p->n_lap <= 32 * LAP_BLOCKS && f1) {
-                if (tc == 2) launch_matrix_kernel(field_kernel_mfma16_laplace<2, true>, MF_LDS_F16, a, st);
-                else if (tc) launch_matrix_kernel(field_kernel_mfma16_laplace<1, true>, MF_LDS_F16, a, st);
-                else launch_matrix_kernel(field_kernel_mfma16_laplace<false, true>, MF_LDS_F16, a, st);
-            } else if (p->mfma16_blob && p->lap16_blob && p->n_lap <= 32 * LAP_BLOCKS) {
-                if (tc == 2) launch_matrix_kernel(field_kernel_mfma16_laplace<2>, MF_LDS_F16, a, st);
-                else if (tc) launch_matrix_kernel(field_kernel_mfma16_laplace<1>, MF_LDS_F16, a, st);
-                else launch_matrix_kernel(field_kernel_mfma16_laplace<false>, MF_LDS_F16, a, st);
-            } else if (p->mfma_blob && p->lap_blob && p->n_lap <= 32 * LAP_BLOCKS) {
-                if (tc == 2) launch_matrix_kernel(field_kernel_mfma_laplace<false, 2>, MF_LDS_FP32, a, st);
-                else if (tc) launch_matrix_kernel(field_kernel_mfma_laplace<false, 1>, MF_LDS_FP32, a, st);
-                else launch_matrix_kernel(field_kernel_mfma_laplace<false>, MF_LDS_FP32, a, st);
+            if (generic) {
+                UNERF_REQUIRE(a.aux && a.aux2 && p.ws_density && p.ws_rgb && p.n_lap >= 1, "field_fwd LAPLACE: need aux, aux2, ws_density, ws_rgb, n_lap>=1");
             } else {
-                hipLaunchKernelGGL((field_kernel<UNERF_FIELD_LAPLACE>), grid, block, 64 * 64 * 4, st, a);
+                UNERF_REQUIRE(p.out1 == 15 && a.aux && a.aux2 && p.ws_density && p.ws_rgb && p.n_lap >= 1,
+                              "field_fwd LAPLACE: need out1=15, aux, aux2, ws_density, ws_rgb, n_lap>=1");
+                UNERF_REQUIRE(!(p.lap_blob || p.lap16_blob) || p.n_lap_rgb <= 32 * LAP_BLOCKS || p.n_lap > 32 * LAP_BLOCKS,
+                              "field_fwd LAPLACE: n_lap_rgb=%d rows do not fit the head blobs (at most %d); pass them as ws_* only",
+                              p.n_lap_rgb, 32 * LAP_BLOCKS);
+                UNERF_REQUIRE(p.lap_chunk_rays == 0 || (p.lap_chunk_rays > 0 && p.lap_chunk_rays % 32 == 0 && a.ray_offset % 32 == 0 && p.lap_sets >= 1),
+                              "field_fwd LAPLACE: lap_chunk_rays=%d and ray_offset=%lld must be multiples of 32, lap_sets=%d >= 1",
+                              p.lap_chunk_rays, (long long)a.ray_offset, p.lap_sets);
             }
+            UNERF_REQUIRE(p.lap_chunk_rays == 0 || (a.ray_offset + a.R - 1) / p.lap_chunk_rays < p.lap_sets,
+                          "field_fwd LAPLACE: rays [%lld, +%lld) reach past the %d sample sets of %d rays",
+                          (long long)a.ray_offset, (long long)a.R, p.lap_sets, p.lap_chunk_rays);
             break;
         default:
-            unerf_set_error("field_fwd: unknown mode %d", p->mode);
+            unerf_set_error("field_fwd: unknown mode %d", p.mode);
             return UNERF_ERR_ARG;
     }
-    return unerf_check_launch(masks ? "field_fwd_masked" : "field_fwd");
+    return UNERF_OK;
+}
+
+// Job 3: run-time values -> template arguments -> launch, each kernel family in one launch expression.
+static void field_launch(FieldArgs& a, bool generic, const unerf_keep_masks* masks, hipStream_t st) {
+    const unerf_field_params& p = a.p;
+    if (generic) {
+        const int rows = generic_rows(p);
+        const size_t lds_bytes = generic_lds_bytes(rows);
+        with_int3(p.mode, [&](auto mode) {
+            const auto kernel = field_kernel_generic<decltype(mode)::value>;
+            if (lds_bytes > 64 * 1024)
+                (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+            hipLaunchKernelGGL(kernel, dim3(blocks_for(a.R * (int64_t)a.S, 64)), dim3(64), lds_bytes, st, a, rows);
+        });
+        return;
+    }
+    switch (p.mode) {
+        case UNERF_FIELD_ACTIVE:
+            launch_by_blob<UNERF_FIELD_ACTIVE, false, false>(a, st);
+            break;
+        case UNERF_FIELD_MCDROPOUT:   // three (SITES, DROP) forms; explicit masks: the general form + the KeepArgs pack
+            if (masks)
+                launch_by_blob<UNERF_FIELD_MCDROPOUT, true, true>(a, st, KeepArgs{{masks->site[0], masks->site[1], masks->site[2]}, masks->pass_stride, masks->sample_offset});
+            else if (a.drop_sites & UNERF_DROP_HEADIN) launch_valu<UNERF_FIELD_MCDROPOUT>(a, st);   // no matrix kernel has this site
+            else if (!a.drop_on) launch_by_blob<UNERF_FIELD_MCDROPOUT, false, false>(a, st);       // K = 0 or p_drop = 0: no masks
+            else if (a.drop_sites == DROP_SITES_DEFAULT) launch_by_blob<UNERF_FIELD_MCDROPOUT, false, true>(a, st);
+            else launch_by_blob<UNERF_FIELD_MCDROPOUT, true, true>(a, st);
+            break;
+        case UNERF_FIELD_LAPLACE: {
+            const bool heads_fit = p.n_lap <= 32 * LAP_BLOCKS;   // the sample sets as head blobs
+            if (p.mfma16_blob && p.lap16_blob && heads_fit) {
+                with_int3(tcnn_arg(p), [&](auto tc) {
+                    with_bool(p.f16_single != 0, [&](auto f1) {
+                        launch_matrix_kernel(field_kernel_mfma16_laplace<decltype(tc)::value, decltype(f1)::value>, MF_LDS_BYTES, a, st);
+                    });
+                });
+            } else if (p.mfma_blob && p.lap_blob && heads_fit) {
+                with_int3(tcnn_arg(p), [&](auto tc) { launch_matrix_kernel(field_kernel_mfma_laplace<false, decltype(tc)::value>, MF_LDS_BYTES, a, st); });
+            } else {
+                launch_valu<UNERF_FIELD_LAPLACE>(a, st);
+            }
+            break;
+        }
+    }
+}
+
+// masks = NULL: unerf_field_fwd.  Else unerf_field_fwd_masked: MC-dropout under explicit keep masks, the same checks, fill
+// and selection (field_launch) with the KeepArgs pack appended to the launch.
+static int field_fwd_impl(const float* origins, const float* directions, const float* sbins, int64_t R, int S,
+                          float near_plane, float far_plane, int spacing, int64_t ray_offset, const unerf_field_params* p,
+                          const float* features, float* density, float* rgb, float* aux, float* aux2,
+                          const unerf_keep_masks* masks, void* stream) {
+    UNERF_REQUIRE(p && (R == 0 || (origins && directions && sbins && (density || p->packed_out) && rgb)), "field_fwd: null pointer");
+    FieldArgs a;
+    a.origins = origins; a.dirs = directions; a.sbins = sbins; a.R = R; a.S = S; a.ray_offset = ray_offset;
+    a.p = *p; a.density = density; a.rgb = rgb; a.aux = aux; a.aux2 = aux2; a.features = features;
+    const bool generic = field_set_widths(a.p);
+    if (int rc = field_check_args(a, near_plane, generic, masks)) return rc;
+    if (R == 0) return UNERF_OK;
+    field_fill_args(a, near_plane, far_plane, spacing, masks);
+    if (int rc = field_check_nonempty(a, spacing, generic)) return rc;
+    field_launch(a, generic, masks, (hipStream_t)stream);
+    return unerf_check_launch(generic ? "field_fwd (any-width kernel)" : masks ? "field_fwd_masked" : "field_fwd");
 }
 
 extern "C" int unerf_field_fwd(const float* origins, const float* directions, const float* sbins, int64_t R, int S,
@@ -3964,9 +3997,7 @@ extern "C" int unerf_laplace_ggn_diag(const float* origins, const float* directi
     a.keep_hi = 0; a.keep_pk = 0; a.drop_on = 0; a.drop_sites = 0; a.drop_scale = 1.f;
     a.box = make_norm_box(p->use_aabb, p->aabb);
     a.p.image_width = 0;   // 1-D tiles
-    if (p->tcnn_levels && p->grid_half) launch_matrix_kernel(field_kernel_mfma_laplace<true, 2>, MF_LDS_FP32, a, st);
-    else if (p->tcnn_levels) launch_matrix_kernel(field_kernel_mfma_laplace<true, 1>, MF_LDS_FP32, a, st);
-    else launch_matrix_kernel(field_kernel_mfma_laplace<true>, MF_LDS_FP32, a, st);
+    with_int3(tcnn_arg(a.p), [&](auto tc) { launch_matrix_kernel(field_kernel_mfma_laplace<true, decltype(tc)::value>, MF_LDS_BYTES, a, st); });
     GgnArgs g;
     g.sbins = sbins; g.R = R; g.S = S; g.s_near = a.s_near; g.s_far = a.s_far; g.lin = a.lin;
     g.sigma = sigma; g.softplus = p->lap_softplus; g.rgb = col; g.X = X; g.Hc = Hc; g.partials = partials;
