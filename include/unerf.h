@@ -517,6 +517,52 @@ int unerf_composite_moments_planes(const float* density, const float* rgb, const
  * var [N,C] (unbiased, K-1; NULL ok).  Two-pass in fp32 like torch. */
 int unerf_moments(const float* x, int K, int64_t N, int C, float* mean, float* var, void* stream);
 
+/* ------------------------------------------------- per-image eval metrics --
+ * Replaces the torch / numpy chain behind one image's entry of metrics.json: get_image_metrics_and_images_unc and
+ * get_unc_metrics_depth (scripts/eval_uncertainty.py:306-412, 647-813: error definitions, psnr, mse / rmse, Gaussian
+ * NLL, average variance), metrics/ause.py (three sparsification curves) and metrics/auce.py (99 coverages), plus the
+ * SSIM the reference reaches through model.ssim.  One call leaves ONE row of float64 partial results in device memory;
+ * the host copies it once and finishes every metric (uncertainty-nerf-gs_amd/metrics.py: finish_metrics).
+ *
+ * pred / target [n, C] (1 <= C <= 4, n C < 2^31), sigma [n] (std per pixel, shared by the channels), mask [n] or NULL
+ * (0 = the pixel is left out of everything).  p = min(pred, pred_clip_max) (+inf: no clip; rgb: 1.0).  Per valid pixel,
+ * in float32 as the host computes them: sq = sum_c (p - t)^2, ab = sum_c |p - t| (channels added left to right),
+ * var = sigma^2; every sum below is float64, reduced in a fixed order (two calls on the same inputs give equal rows).
+ * ratios_host [n_ratios] / z_host [n_z]: HOST float64 arrays, 1..128 entries each, read during the call.
+ *
+ * out [UNERF_METRICS_ROW] doubles:
+ *   [0] n_valid   [1] valid pixels with a non-finite pred / target / sigma (the sums then mean nothing; the host raises)
+ *   [2] sum sq    [3] sum ab    [4] sum var    [5] sum sigma
+ *   [6] sum over pixel-channels of ((double)t - (double)p)^2                         (psnr)
+ *   [7] sum over pixel-channels of (t - p)^2 / (2 s^2) + log s + log(2 pi) / 2, s = max(sigma, nll_min_sigma), all in
+ *       float64                                                                      (UNERF_METRICS_NLL)
+ *   [8] min p  [9] max p  [10] min target  [11] max target     (+-inf when nothing is valid)
+ *   [12] sum of the SSIM index over the (H-10) x (W-10) interior pixels and the C channels, [13] their number
+ *       (UNERF_METRICS_SSIM: 11x11 gaussian window, sigma 1.5, k1 0.01, k2 0.03, data_range = max([9] - [8], [11] - [10])
+ *       with the differences taken in float32; window sums in float64; needs mask == NULL, H W == n, min(H, W) >= 11)
+ *   [UNERF_METRICS_AUCE_OFF + k], k < n_z: number of valid pixel-channels with |t - p| / sigma <= z[k], the ratio in
+ *       float64; sigma <= 0 gives 0 for a zero residual and +inf otherwise (metrics/auce.py as one comparison per
+ *       element)                                                                     (UNERF_METRICS_AUCE)
+ *   [UNERF_METRICS_AUSE_OFF + 128 f + k], k < n_ratios, with keep_k = (int64)((1.0 - ratios[k]) * (double)n_valid)
+ *       clamped to [0, n_valid]: f = 0 the sum of the keep_k smallest sq; f = 1 of the keep_k smallest ab; f = 2 / 3 the
+ *       sum of sq / of ab over the keep_k pixels of smallest var.  "Smallest" = ascending value, ties by ascending pixel
+ *       index (a stable LSD radix sort of the bit patterns)                          (UNERF_METRICS_AUSE)
+ * Entries whose flag is not set, and every unused slot, are 0.
+ * workspace: unerf_image_metrics_workspace_bytes(n) bytes of device scratch, 8-byte aligned (about 28 n bytes).
+ * n = 0 is a successful no-op that leaves `out` alone. */
+#define UNERF_METRICS_AUSE 1
+#define UNERF_METRICS_AUCE 2
+#define UNERF_METRICS_NLL 4
+#define UNERF_METRICS_SSIM 8
+#define UNERF_METRICS_AUCE_OFF 16
+#define UNERF_METRICS_AUSE_OFF 144
+#define UNERF_METRICS_ROW 656
+size_t unerf_image_metrics_workspace_bytes(int64_t n);
+int unerf_image_metrics(const float* pred, const float* target, const float* sigma, const uint8_t* mask, int64_t n, int C,
+                        int H, int W, float pred_clip_max, float nll_min_sigma, const double* ratios_host, int n_ratios,
+                        const double* z_host, int n_z, int flags, void* workspace, size_t workspace_bytes, double* out,
+                        void* stream);
+
 /* ================================================================ splats ==
  * gsplat 0.1.11 call sites in models/activesplatfacto/activesplatfacto_model.py. */
 

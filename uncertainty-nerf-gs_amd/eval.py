@@ -31,10 +31,14 @@ from . import metrics as M
 
 
 def image_metrics_unc(outputs: Dict[str, torch.Tensor], gt_image: torch.Tensor, eval_rgb_unc: bool = True,
-                      min_rgb_std_for_nll: float = 3e-2, composite_gt: Optional[Callable] = None):
+                      min_rgb_std_for_nll: float = 3e-2, composite_gt: Optional[Callable] = None, fused: bool = False):
     """get_image_metrics_and_images_unc (eval_uncertainty.py:647-813), RGB part.
     -> (metrics_dict, curves) where curves carries the per-image sparsification / calibration curves
-    that the reference accumulates for its test-set plots."""
+    that the reference accumulates for its test-set plots.
+    fused=True: the same keys and curves from one ops.image_metrics call (HIP kernels, one row of float64 sums, one copy to
+    the host) instead of the chain of torch ops below; needs the render on a HIP device."""
+    if fused:
+        return _image_metrics_unc_fused(outputs, gt_image, eval_rgb_unc, min_rgb_std_for_nll, composite_gt)
     rgb = torch.clip(outputs["rgb"], max=1.0)
     image = gt_image.to(rgb.device)
     if "background" in outputs and composite_gt is not None:  # splatfacto: blend GT alpha with the background
@@ -67,18 +71,43 @@ def image_metrics_unc(outputs: Dict[str, torch.Tensor], gt_image: torch.Tensor, 
     return md, curves
 
 
+def _image_metrics_unc_fused(outputs, gt_image, eval_rgb_unc, min_rgb_std_for_nll, composite_gt):
+    """image_metrics_unc through the kernels.  The ground-truth composition stays in torch in front of the call
+    (elementwise, no sync); the clip of the prediction to <= 1 happens inside the kernels."""
+    from . import lib as _l, ops
+    rgb = outputs["rgb"].to(torch.float32).contiguous()
+    image = gt_image.to(rgb.device)
+    if "background" in outputs and composite_gt is not None:
+        image = composite_gt(image, outputs["background"])
+    image = image[..., :rgb.shape[-1]].to(torch.float32).contiguous()
+    H, W, Cc = rgb.shape
+    if eval_rgb_unc:
+        flags, std = _l.METRICS_ALL, outputs["rgb_std"].to(torch.float32).reshape(H, W).contiguous()
+    else:
+        flags, std = _l.METRICS_SSIM, torch.zeros(H, W, device=rgb.device)
+    row = ops.image_metrics(rgb, image, std, None, image_hw=(H, W), clip_max=1.0, nll_min_sigma=min_rgb_std_for_nll, flags=flags)
+    md, curves = M.finish_metrics(row.cpu().numpy(), Cc, "rgb", flags)
+    if not eval_rgb_unc:
+        md = {"psnr": md["psnr"], "ssim": md["ssim"]}
+    return md, curves
+
+
 def load_depth_gt(dataset_path: str, img_num: int) -> Tuple[np.ndarray, float]:
     """the two files get_unc_metrics_depth reads (eval_uncertainty.py:432-437): -> (depth_gt [H,W], scale a)"""
     a = float(np.loadtxt(os.path.join(str(dataset_path), "scale_parameters.txt"), delimiter=","))
     return np.load(os.path.join(str(dataset_path), "depth_gt_{:02d}.npy".format(img_num))), a
 
 
-def depth_metrics_unc(outputs: Dict[str, torch.Tensor], depth_gt, scale: float, min_depth_std_for_nll: float = 1.0):
+def depth_metrics_unc(outputs: Dict[str, torch.Tensor], depth_gt, scale: float, min_depth_std_for_nll: float = 1.0,
+                      fused: bool = False):
     """get_unc_metrics_depth (eval_uncertainty.py:415-644) without the plots, plus the key renaming of
     get_image_metrics_and_images_unc (:702-733).  depth / depth_std are resized to the GT map if the shapes
     differ (torchvision `resize` on a tensor = bilinear `interpolate`, no antialias), scaled by `scale`;
     NLL uses the prediction clipped to [1e-3, max GT] on the full image and is then masked by `GT > 0`;
-    errors, AUSE and AUCE use the masked, clipped prediction.  -> (metrics_dict, curves)"""
+    errors, AUSE and AUCE use the masked, clipped prediction.  -> (metrics_dict, curves)
+    fused=True: resize / scale / clip stay in torch (elementwise, `gt.max()` stays a tensor: no sync); everything behind
+    them is one ops.image_metrics call with mask = GT > 0 (the NLL-then-mask above is the masked NLL, element by
+    element).  The ground truth is taken as float32 there."""
     depth = outputs["depth"].squeeze(-1).to(torch.float32)
     depth_std = outputs["depth_std"].squeeze(-1).to(torch.float32)
     gt = torch.as_tensor(depth_gt, device=depth.device)
@@ -94,6 +123,12 @@ def depth_metrics_unc(outputs: Dict[str, torch.Tensor], depth_gt, scale: float, 
     depth = scale * depth
     depth_std = scale * depth_std
     clipped = torch.minimum(torch.clamp_min(depth, lo), hi)
+    if fused:
+        from . import lib as _l, ops
+        flags = _l.METRICS_ALL & ~_l.METRICS_SSIM
+        row = ops.image_metrics(clipped.unsqueeze(-1).contiguous(), gt.to(torch.float32).unsqueeze(-1).contiguous(),
+                                depth_std.contiguous(), (gt > 0).contiguous(), nll_min_sigma=min_depth_std_for_nll, flags=flags)
+        return M.finish_metrics(row.cpu().numpy(), 1, "depth", flags, with_psnr=False)
     nll_img = M.negative_gaussian_loglikelihood(clipped.unsqueeze(-1), gt.unsqueeze(-1), depth_std.unsqueeze(-1),
                                                 eps=min_depth_std_for_nll).reshape(clipped.shape)
     mask = gt > 0
@@ -121,9 +156,10 @@ def depth_metrics_unc(outputs: Dict[str, torch.Tensor], depth_gt, scale: float, 
 def get_average_uncertainty_metrics(get_outputs_for_camera: Callable, eval_set: Iterable[Tuple[object, torch.Tensor]],
                                     eval_rgb_unc: bool = True, min_rgb_std_for_nll: float = 3e-2,
                                     composite_gt: Optional[Callable] = None, depth_gt_fn: Optional[Callable] = None,
-                                    min_depth_std_for_nll: float = 1.0):
+                                    min_depth_std_for_nll: float = 1.0, fused: bool = False):
     """eval_uncertainty.py:816-1079.  -> (averaged metrics dict, averaged curves dict).
-    depth_gt_fn(image_index) -> (depth_gt [H,W], scale) switches the depth metrics on (eval_depth_unc)."""
+    depth_gt_fn(image_index) -> (depth_gt [H,W], scale) switches the depth metrics on (eval_depth_unc).
+    fused: the per-image metric stage through the HIP kernels (image_metrics_unc / depth_metrics_unc, fused=True)."""
     rows: List[Dict[str, float]] = []
     sums: Dict[str, np.ndarray] = {}
     for img_num, (camera, gt) in enumerate(eval_set):
@@ -133,10 +169,10 @@ def get_average_uncertainty_metrics(get_outputs_for_camera: Callable, eval_set: 
             torch.cuda.synchronize()
         render_s = time.time() - inner_start
         H, W = outputs["rgb"].shape[:2]
-        md, curves = image_metrics_unc(outputs, gt, eval_rgb_unc, min_rgb_std_for_nll, composite_gt)
+        md, curves = image_metrics_unc(outputs, gt, eval_rgb_unc, min_rgb_std_for_nll, composite_gt, fused=fused)
         if depth_gt_fn is not None:
             dgt, scale = depth_gt_fn(img_num)
-            dmd, dcurves = depth_metrics_unc(outputs, dgt, scale, min_depth_std_for_nll)
+            dmd, dcurves = depth_metrics_unc(outputs, dgt, scale, min_depth_std_for_nll, fused=fused)
             md.update(dmd)
             curves.update(dcurves)
         md["num_rays_per_sec"] = H * W / (time.time() - inner_start)
@@ -246,9 +282,10 @@ def outputs_fn_for(eval_config: EvalConfigs, model, ggn_batches=None, pipeline=N
 
 def run_eval(eval_config: EvalConfigs, model, eval_set, experiment_name: str = "", method_name: str = "",
              checkpoint: str = "", depth_gt_fn: Optional[Callable] = None, composite_gt: Optional[Callable] = None,
-             **fn_kw) -> Dict[str, float]:
+             fused: bool = False, **fn_kw) -> Dict[str, float]:
     """main() of scripts/eval_uncertainty.py:1082-1169 without nerfstudio's pipeline loading: pick the method's
-    callable, average the per-image metrics, write the metrics.json envelope to eval_config.output_path."""
+    callable, average the per-image metrics, write the metrics.json envelope to eval_config.output_path.
+    fused=True computes the per-image metrics with the HIP kernels behind ops.image_metrics (same keys; opt-in)."""
     fn = outputs_fn_for(eval_config, model, **fn_kw)
     if composite_gt is None and hasattr(model, "composite_gt"):   # splat models: GT alpha over the background
         composite_gt = model.composite_gt
@@ -257,6 +294,6 @@ def run_eval(eval_config: EvalConfigs, model, eval_set, experiment_name: str = "
     metrics, _curves = get_average_uncertainty_metrics(
         fn, eval_set, eval_rgb_unc=eval_config.eval_rgb, min_rgb_std_for_nll=eval_config.min_rgb_std_for_nll,
         composite_gt=composite_gt, depth_gt_fn=depth_gt_fn if eval_config.eval_depth else None,
-        min_depth_std_for_nll=eval_config.min_depth_std_for_nll)
+        min_depth_std_for_nll=eval_config.min_depth_std_for_nll, fused=fused)
     write_metrics_json(str(eval_config.output_path), experiment_name, method_name, checkpoint, metrics)
     return metrics

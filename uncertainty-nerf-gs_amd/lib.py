@@ -16,7 +16,7 @@ CSRC = os.path.join(_HERE, "csrc")
 INCLUDE = os.path.join(os.path.dirname(_HERE), "include")
 # UNERF_LIB: another build of the same ABI, for A/B timing on one box (benchmarks/ab_bench.sh); unset in normal use
 LIB_PATH = os.environ.get("UNERF_LIB") or os.path.join(CSRC, "libunerf.so")
-SOURCES = ["unerf_nerf.hip", "unerf_splat.hip"]
+SOURCES = ["unerf_nerf.hip", "unerf_splat.hip", "unerf_metrics.hip"]
 # -amdgpu-mfma-vgpr-form: gfx950 has one unified register file; let the MFMAs write their accumulators to
 # ordinary VGPRs so ReLU / dropout / the next layer's B operand read them without v_accvgpr_read copies
 # (97 copies per tile in the K-pass kernel, which is VALU-issue-bound; rocprof r1_04).
@@ -191,6 +191,9 @@ SIGNATURES = {
     "unerf_composite_moments_planes": (_i, [_vp, _vp, _vp, _i, _i64, _i, _f, _f, _i, _vp, _i64, _i64, _i, _fp, _vp, _vp,
                                             _vp, _vp]),
     "unerf_moments": (_i, [_vp, _i, _i64, _i, _vp, _vp, _vp]),
+    "unerf_image_metrics_workspace_bytes": (C.c_size_t, [_i64]),
+    "unerf_image_metrics": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i, _i, _f, _f, C.POINTER(C.c_double), _i, C.POINTER(C.c_double), _i,
+                                 _i, _vp, C.c_size_t, _vp, _vp]),
     "unerf_splat_project": (_i, [_vp, _vp, _f, _vp, _fp, _f, _f, _f, _f, _i, _i, _i, _f, _i64, _vp, _vp, _vp, _vp,
                                  _vp, _vp, _vp, _vp]),
     "unerf_splat_project_raw": (_i, [_vp, _vp, _f, _vp, _fp, _f, _f, _f, _f, _i, _i, _i, _f, _i64, _vp, _i, _vp, _vp, _vp,
@@ -218,6 +221,10 @@ SIGNATURES = {
     "unerf_splat_normalize_outputs_batch": (_i, [_vp, _i, _i, _vp, _i, _i64, _vp, _vp, _vp, _i, _vp, _vp, _vp]),
     "unerf_splat_depth_sqdiff_batch": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i64, _vp, _vp]),
 }
+# include/unerf.h: UNERF_METRICS_* (flags of unerf_image_metrics, layout of its row of float64 results)
+METRICS_AUSE, METRICS_AUCE, METRICS_NLL, METRICS_SSIM = 1, 2, 4, 8
+METRICS_ALL = METRICS_AUSE | METRICS_AUCE | METRICS_NLL | METRICS_SSIM
+METRICS_AUCE_OFF, METRICS_AUSE_OFF, METRICS_ROW, METRICS_MAX_CUTS = 16, 144, 656, 128
 SPLAT_MAX_VIEWS = 16                              # include/unerf.h: UNERF_SPLAT_MAX_VIEWS
 SPLAT_VIEW_FLOATS = 19                            # include/unerf.h: UNERF_SPLAT_VIEW_FLOATS
 SPLAT_BATCH_MAX_TILES = 11999                     # include/unerf.h: UNERF_SPLAT_BATCH_MAX_TILES

@@ -8,7 +8,7 @@ tensors live on; results agree with the reference implementation to ~1e-7 (golde
 from __future__ import annotations
 
 import math
-from typing import Dict, Tuple
+from typing import Dict, Optional, Tuple
 
 import numpy as np
 import torch
@@ -28,9 +28,26 @@ def _sparsification_curve(err_sorted: torch.Tensor, err_type: str) -> np.ndarray
     csum = torch.cumsum(err_sorted.to(torch.float64), dim=0)
     means = csum[(keep - 1).clamp(min=0)] / keep.clamp(min=1).to(torch.float64)
     means = torch.where(keep > 0, means, torch.full_like(means, float("nan")))
+    return _curve_of_means(means.cpu().numpy(), err_type)
+
+
+def _curve_of_means(means: np.ndarray, err_type: str) -> np.ndarray:
+    """float64 means of the kept errors (NaN where nothing is kept) -> the float32 curve: sqrt for rmse, in float64 and
+    in front of the cast.  Shared by the sort-and-cumsum path above and by finish_metrics."""
+    means = np.asarray(means, dtype=np.float64)
     if err_type == "rmse":
-        means = means.sqrt()
-    return means.to(torch.float32).cpu().numpy()
+        means = np.sqrt(means)
+    return means.astype(np.float32)
+
+
+def _ause_of_curves(oracle: np.ndarray, by_var: np.ndarray, ratios: np.ndarray = _RATIOS):
+    """the tail of metrics/ause.py:7-44: both float32 curves normalised by the larger maximum, the area between them.
+    -> (ratio_removed, oracle_curve, by_variance_curve, ause)"""
+    by_var = by_var.astype(np.float64)
+    max_val = max(float(oracle.max()), float(by_var.max()))
+    oracle = oracle / np.float32(max_val)
+    by_var = by_var / max_val
+    return ratios, oracle, by_var, _trapz(by_var - oracle, ratios)
 
 
 def ause(unc_vec: torch.Tensor, err_vec: torch.Tensor, err_type: str = "rmse"):
@@ -39,11 +56,8 @@ def ause(unc_vec: torch.Tensor, err_vec: torch.Tensor, err_type: str = "rmse"):
     err_sorted, _ = torch.sort(err_vec)
     oracle = _sparsification_curve(err_sorted, err_type)
     _, order = torch.sort(unc_vec)
-    by_var = _sparsification_curve(err_vec[order], err_type).astype(np.float64)
-    max_val = max(float(oracle.max()), float(by_var.max()))
-    oracle = oracle / np.float32(max_val)
-    by_var = by_var / max_val
-    return _RATIOS, oracle, by_var, _trapz(by_var - oracle, _RATIOS)
+    by_var = _sparsification_curve(err_vec[order], err_type)
+    return _ause_of_curves(oracle, by_var)
 
 
 def _norm_ppf(p: np.ndarray) -> np.ndarray:
@@ -89,8 +103,16 @@ def auce_torch(mean_values: torch.Tensor, sigma_values: torch.Tensor, target_val
     r = (t - m).abs()
     ratio = torch.where(sg > 0, r / sg, torch.where(r == 0, torch.zeros_like(r), torch.full_like(r, float("inf"))))
     ratio, _ = torch.sort(ratio)
-    coverage = (torch.searchsorted(ratio, z, right=True).to(torch.float64) / n).cpu().numpy()
+    # the integer counts cross to the host and are divided there: torch divides a device tensor by a host scalar as a
+    # multiplication by its reciprocal, one ulp off the reference's count / n for about half the counts
+    coverage = torch.searchsorted(ratio, z, right=True).cpu().numpy().astype(np.float64) / n
     length = (2.0 * z * sg.mean()).cpu().numpy()
+    return _auce_of_curves(coverage, length, alphas)
+
+
+def _auce_of_curves(coverage: np.ndarray, length: np.ndarray, alphas: np.ndarray) -> Dict[str, np.ndarray]:
+    """the tail of metrics/auce.py:10-57: coverage errors and the three integrals over alpha.  Shared by auce_torch and
+    finish_metrics."""
     cov_err = coverage - (1.0 - alphas)
     abs_err = np.abs(cov_err)
     neg_err = (np.abs(cov_err) - cov_err) / 2.0
@@ -165,3 +187,95 @@ def rgb_uncertainty_metrics(rgb_pred: torch.Tensor, rgb_std: torch.Tensor, rgb_g
     a = auce(rgb_pred.reshape(-1, 3).cpu().numpy(), std3.cpu().numpy(), rgb_gt.reshape(-1, 3).cpu().numpy())
     out.update({k: v for k, v in a.items() if k.startswith("auc_")})
     return out
+
+
+# ---- the fused path: one row of float64 partial results from the kernels (ops.image_metrics), finished here ----------
+
+_AUCE_TABLES = None
+
+
+def _auce_tables():
+    """(alphas, z) of metrics/auce.py:10-57, computed once: alpha = 0.01 .. 0.99, z = norm.ppf(1 - alpha / 2)"""
+    global _AUCE_TABLES
+    if _AUCE_TABLES is None:
+        alphas = np.arange(start=0.01, stop=1.0, step=0.01)
+        _AUCE_TABLES = (alphas, np.ascontiguousarray(_norm_ppf(1.0 - alphas / 2), dtype=np.float64))
+    return _AUCE_TABLES
+
+
+_AUCE_CURVES = ("coverage_values", "avg_length_values", "coverage_error_values", "abs_coverage_error_values",
+                "neg_coverage_error_values")
+
+
+def metrics_row_from_sums(n_valid: int, sum_sq: float, sum_ab: float, sum_var: float, sum_sigma: float, sum_sq64: float,
+                          nll_sum: float, pred_minmax, target_minmax, auce_counts, ause_sums, ssim_sum: float = 0.0,
+                          ssim_count: float = 0.0, nonfinite: int = 0) -> np.ndarray:
+    """a row in the layout of include/unerf.h (unerf_image_metrics) from its parts; ause_sums [4, n_ratios]"""
+    from . import lib as _l
+    row = np.zeros(_l.METRICS_ROW, dtype=np.float64)
+    row[:14] = [n_valid, nonfinite, sum_sq, sum_ab, sum_var, sum_sigma, sum_sq64, nll_sum, pred_minmax[0], pred_minmax[1],
+                target_minmax[0], target_minmax[1], ssim_sum, ssim_count]
+    auce_counts = np.asarray(auce_counts, dtype=np.float64)
+    row[_l.METRICS_AUCE_OFF:_l.METRICS_AUCE_OFF + auce_counts.size] = auce_counts
+    for f, sums in enumerate(np.asarray(ause_sums, dtype=np.float64)):
+        o = _l.METRICS_AUSE_OFF + _l.METRICS_MAX_CUTS * f
+        row[o:o + sums.size] = sums
+    return row
+
+
+def finish_metrics(row_host, channels: int, prefix: str = "rgb", flags: Optional[int] = None, ratios: np.ndarray = _RATIOS,
+                   with_psnr: bool = True):
+    """One host copy of the row ops.image_metrics left on the device -> (metrics dict, curves dict) under the key names of
+    eval.image_metrics_unc / depth_metrics_unc (`prefix` "rgb" or "depth"), pure numpy.  The means are quotients of the
+    device's float64 sums; the curve tails are the helpers `ause` and `auce_torch` end in.  Raises if the kernels counted
+    a non-finite input (the torch path's NaN ordering is not imitated)."""
+    from . import lib as _l
+    row = np.asarray(row_host, dtype=np.float64)
+    flags = _l.METRICS_ALL if flags is None else flags
+    n_valid, bad = int(row[0]), int(row[1])
+    if bad:
+        raise ValueError(f"{bad} of {n_valid} pixels have a non-finite prediction, target or standard deviation")
+    if n_valid <= 0:
+        raise ValueError("no valid pixel: nothing to average")
+    md: Dict[str, float] = {}
+    curves: Dict[str, np.ndarray] = {}
+    if with_psnr:
+        md["psnr"] = 10.0 * math.log10(1.0 / (row[6] / (n_valid * channels)))
+    if flags & _l.METRICS_SSIM:
+        md["ssim"] = float(row[12] / row[13])
+    if flags & _l.METRICS_AUSE:
+        keep = np.array([int((1 - r) * n_valid) for r in ratios], dtype=np.int64)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            means = np.where(keep > 0, row[_l.METRICS_AUSE_OFF:_l.METRICS_AUSE_OFF + 4 * _l.METRICS_MAX_CUTS]
+                             .reshape(4, _l.METRICS_MAX_CUTS)[:, :len(ratios)] / np.maximum(keep, 1), np.nan)
+        # (error type, oracle family, by-variance family): sq sorted by sq / ab by ab; sq / ab sorted by variance
+        for et, fo, fv in (("mae", 1, 3), ("mse", 0, 2), ("rmse", 0, 2)):
+            _, e, ev, a = _ause_of_curves(_curve_of_means(means[fo], et), _curve_of_means(means[fv], et), ratios)
+            md[f"{prefix}_ause_{et}"] = float(a)
+            curves[f"{prefix}_all_ause_{et}"], curves[f"{prefix}_all_var_ause_{et}"] = e, ev
+    md[f"{prefix}_mse"] = float(row[2] / n_valid)
+    md[f"{prefix}_rmse"] = float(np.sqrt(row[2] / n_valid))
+    if flags & _l.METRICS_NLL:
+        md[f"{prefix}_nll"] = float(row[7] / (n_valid * channels))
+    md[f"{prefix}_avg_var"] = float(row[4] / n_valid)
+    if flags & _l.METRICS_AUCE:
+        alphas, z = _auce_tables()
+        coverage = row[_l.METRICS_AUCE_OFF:_l.METRICS_AUCE_OFF + len(z)] / float(n_valid * channels)
+        a = _auce_of_curves(coverage, 2.0 * z * (row[5] / n_valid), alphas)
+        md[f"{prefix}_auc_abs_error"], md[f"{prefix}_auc_length"] = a["auc_abs_error_values"], a["auc_length_values"]
+        md[f"{prefix}_auc_neg_error"] = a["auc_neg_error_values"]
+        for k in _AUCE_CURVES:
+            curves[f"{prefix}_all_auce_{k}"] = a[k]
+    return md, curves
+
+
+def fused_rgb_metrics(rgb_pred: torch.Tensor, rgb_std: torch.Tensor, rgb_gt: torch.Tensor, min_rgb_std_for_nll: float = 3e-2,
+                      clip_max: float = 1.0, with_ssim: bool = True, workspace=None):
+    """`eval.image_metrics_unc`'s numbers for one image [H,W,C] on a HIP device through the fused kernels: one
+    ops.image_metrics call, one copy of its row to the host, finish_metrics.  -> (metrics dict, curves dict)"""
+    from . import lib as _l, ops
+    H, W, Cc = rgb_pred.shape
+    flags = _l.METRICS_ALL if with_ssim else _l.METRICS_ALL & ~_l.METRICS_SSIM
+    row = ops.image_metrics(rgb_pred.contiguous(), rgb_gt.contiguous(), rgb_std.reshape(H, W).contiguous(), None, image_hw=(H, W),
+                            clip_max=clip_max, nll_min_sigma=min_rgb_std_for_nll, flags=flags, workspace=workspace)
+    return finish_metrics(row.cpu().numpy(), Cc, "rgb", flags)

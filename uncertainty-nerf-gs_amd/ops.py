@@ -1222,6 +1222,60 @@ def moments(x: torch.Tensor, want_var: bool = True):
     return mean, var
 
 
+# ------------------------------------------------------- per-image eval metrics --------
+
+_METRIC_TABLES = None
+
+
+def metric_tables():
+    """the two host tables every eval image uses: AUSE fractions removed (metrics/ause.py: linspace(0, 1, 100,
+    endpoint=False)) and AUCE half-widths in sigmas (metrics/auce.py: norm.ppf(1 - alpha / 2), alpha = 0.01 .. 0.99)"""
+    global _METRIC_TABLES
+    if _METRIC_TABLES is None:
+        import numpy as np
+        from . import metrics as M
+        _METRIC_TABLES = (np.ascontiguousarray(M._RATIOS, dtype=np.float64), M._auce_tables()[1])
+    return _METRIC_TABLES
+
+
+def image_metrics(pred: torch.Tensor, target: torch.Tensor, sigma: torch.Tensor, mask: Optional[torch.Tensor] = None, *,
+                  image_hw: Optional[Tuple[int, int]] = None, clip_max: float = float("inf"), nll_min_sigma: float,
+                  flags: int, workspace: Optional[Workspace] = None, ratios=None, z=None) -> torch.Tensor:
+    """unerf_image_metrics: pred / target [..., C], sigma [...] (one std per pixel), mask [...] (bool / uint8, 0 = left
+    out) or None -> the device row of lib.METRICS_ROW float64 partial results (layout: include/unerf.h;
+    metrics.finish_metrics turns a host copy of it into the reference's per-image dictionary).  Asynchronous on the
+    current stream, no host synchronisation.  image_hw = (H, W) is needed with METRICS_SSIM.  ratios / z: float64 host
+    tables (default: metric_tables()).  workspace: scratch from that arena instead of a fresh allocation."""
+    import numpy as np
+    lib = _l.load()
+    Cc = int(pred.shape[-1])
+    n = sigma.numel()
+    if pred.numel() != n * Cc or target.shape != pred.shape:
+        raise _l.UnerfError(f"image_metrics: pred {tuple(pred.shape)}, target {tuple(target.shape)}, sigma {tuple(sigma.shape)}")
+    if mask is not None:
+        if mask.numel() != n:
+            raise _l.UnerfError(f"image_metrics: mask has {mask.numel()} entries for {n} pixels")
+        if mask.dtype == torch.bool:
+            mask = mask.view(torch.uint8)
+    H, W = (int(image_hw[0]), int(image_hw[1])) if image_hw is not None else (0, 0)
+    tr, tz = metric_tables()
+    ratios = tr if ratios is None else np.ascontiguousarray(ratios, dtype=np.float64)
+    z = tz if z is None else np.ascontiguousarray(z, dtype=np.float64)
+    dp = C.POINTER(C.c_double)
+    dev = pred.device
+    with _ctx(dev):
+        nbytes = lib.unerf_image_metrics_workspace_bytes(n)
+        words = (nbytes + 7) // 8
+        ws = (workspace.get("image_metrics", (words,), dev, dtype=torch.float64) if workspace is not None
+              else torch.empty(words, device=dev, dtype=torch.float64))
+        out = torch.zeros(_l.METRICS_ROW, device=dev, dtype=torch.float64)
+        _run("image_metrics", lambda: lib.unerf_image_metrics(
+            _p(pred, name="pred"), _p(target, name="target"), _p(sigma, name="sigma"), _p(mask, torch.uint8, "mask"), n, Cc, H, W,
+            float(clip_max), float(nll_min_sigma), ratios.ctypes.data_as(dp), int(ratios.size), z.ctypes.data_as(dp), int(z.size),
+            int(flags), _p(ws, torch.float64, "workspace"), nbytes, _p(out, torch.float64, "out"), _stream()))
+    return out
+
+
 # ---------------------------------------------------------------- splats ---------------
 
 def splat_project(means3d, scales, glob_scale: float, quats, viewmat: torch.Tensor, fx, fy, cx, cy, H: int, W: int,
