@@ -80,10 +80,23 @@ def restate_row(pred, target, sigma, mask=None, clip=float("inf"), min_sigma=3e-
     if image_hw is not None and mask is None:
         H, W = image_hw
         ssim_sum, ssim_cnt = ssim_sum_f64(p.reshape(H, W, Cc), t.reshape(H, W, Cc))
+    # nothing valid: the minima / maxima of an empty set, every sum and count 0
+    p_mm = (float(p.min()), float(p.max())) if n else (float("inf"), float("-inf"))
+    t_mm = (float(t.min()), float(t.max())) if n else (float("inf"), float("-inf"))
     row = M.metrics_row_from_sums(n, float(sq.double().sum()), float(ab.double().sum()), float(var.double().sum()),
                                   float(s64.sum()), float((d64 ** 2).sum()), float(nll_terms.sum()),
-                                  (float(p.min()), float(p.max())), (float(t.min()), float(t.max())), counts, fam, ssim_sum, ssim_cnt)
+                                  p_mm, t_mm, counts, fam, ssim_sum, ssim_cnt)
     return row, {"nll_abs_sum": float(nll_terms.abs().sum()), "n": n}
+
+
+def edge_tables():
+    """caller tables at their edges, 128 entries each (the maximum): ratios out of order with 0, 1, values outside [0, 1], a
+    duplicate and one so small that keep_k is n_valid - 1; thresholds descending and out of order with duplicates, a zero,
+    an infinity and a value below every float32 ratio"""
+    ratios = np.concatenate(([0.5, 0.0, 1.0, 1.5, -0.25, 0.5, 0.999, 1e-9], np.linspace(0.01, 0.99, 120)))
+    z = np.concatenate(([2.0, 0.0, np.inf, 1.0, 1.0, 1e-300], np.linspace(3.0, 0.01, 122)))
+    assert ratios.size == z.size == 128
+    return np.ascontiguousarray(ratios, dtype=np.float64), np.ascontiguousarray(z, dtype=np.float64)
 
 
 # ---------------------------------------------------------------- the ABI ------------------------------------------
@@ -202,4 +215,84 @@ def test_finish_metrics_raises_on_non_finite_inputs(lib):
     row, _ = restate_row(pred, gt, std, clip=1.0)
     row[1] = 2.0
     with pytest.raises(ValueError, match="non-finite"):
+        M.finish_metrics(row, 3)
+
+
+# ---------------------------------------------------------------- the restatement itself ---------------------------
+
+@pytest.mark.parametrize("n,Cc,masked,which", [(1, 3, False, "edge"), (2, 1, False, "edge"), (37, 2, True, "edge"), (300, 3, True, "edge"),
+                                               (300, 4, False, "edge"), (299, 3, True, "single"), (300, 3, False, "default")])
+def test_restate_row_handles_caller_tables_like_a_brute_force_loop(lib, n, Cc, masked, which):
+    """`restate_row` (torch.sort, cumsum, vectorised comparisons) against plain loops at the table edges the GPU tests lean
+    on: per ratio int((1 - r) n) clamped to [0, n] and the first k of a Python-sorted list of (value, index) pairs, per
+    threshold a count element by element.  The error vectors are numpy float32 here (IEEE, channels left to right), the
+    sums math.fsum (exact): 1e-12 relative covers a float64 cumsum of 300 non-negative terms (300 2^-53 = 3.4e-14);
+    counts, n_valid, minima and maxima are equal."""
+    g = torch.Generator().manual_seed(100 * n + Cc)
+    gt = torch.rand(n, Cc, generator=g)
+    std = 0.02 + 0.2 * torch.rand(n, generator=g)
+    pred = gt + std[:, None] * torch.randn(n, Cc, generator=g) + 0.05
+    std[3:60:7] = 0.0                                                      # sigma == 0 with a residual: ratio +inf, var ties
+    std[5:80:9] = 0.0
+    pred[5:80:9] = gt[5:80:9]                                              # sigma == 0 without: ratio 0, sq / ab ties
+    pred[100:140] = gt[100:140] + 0.0625                                   # equal errors across several cuts
+    mask = (torch.rand(n, generator=g) > 0.3) if masked else None
+    ratios, z = {"edge": edge_tables(), "single": (np.array([0.5]), np.array([1.0])), "default": tables()}[which]
+    clip = 1.0
+    row, ex = restate_row(pred, gt, std, mask, clip=clip, min_sigma=3e-2, ratios=ratios, z=z)
+
+    keep = np.ones(n, bool) if mask is None else mask.numpy()
+    p = np.minimum(pred.numpy(), np.float32(clip))[keep]
+    t, s = gt.numpy()[keep], std.numpy()[keep]
+    nv = int(keep.sum())
+    assert p.dtype == t.dtype == s.dtype == np.float32 and row[0] == nv == ex["n"] and row[1] == 0
+    sq, ab = np.zeros(nv, np.float32), np.zeros(nv, np.float32)
+    for c in range(Cc):
+        d = p[:, c] - t[:, c]
+        sq, ab = sq + d * d, ab + np.abs(d)
+    var = s * s
+    assert sq.dtype == ab.dtype == var.dtype == np.float32
+    by = {"sq": sorted((float(v), i) for i, v in enumerate(sq)), "ab": sorted((float(v), i) for i, v in enumerate(ab)),
+          "var": sorted((float(v), i) for i, v in enumerate(var))}
+    from uncertainty_nerf_gs_amd import lib as L
+    s0 = L.METRICS_AUSE_OFF
+    for k, r in enumerate(ratios):
+        kk = min(max(int((1 - r) * nv), 0), nv)
+        want = (math.fsum(v for v, _ in by["sq"][:kk]), math.fsum(v for v, _ in by["ab"][:kk]),
+                math.fsum(float(sq[i]) for _, i in by["var"][:kk]), math.fsum(float(ab[i]) for _, i in by["var"][:kk]))
+        for f in range(4):
+            got = row[s0 + 128 * f + k]
+            assert abs(got - want[f]) <= 1e-12 * want[f], (k, r, kk, f, got, want[f])
+            assert want[f] != 0 or got == 0
+    a0 = L.METRICS_AUCE_OFF
+    for k, zk in enumerate(z):
+        cnt = 0
+        for i in range(nv):
+            for c in range(Cc):
+                res, sg = abs(float(t[i, c]) - float(p[i, c])), float(s[i])
+                ratio = res / sg if sg > 0 else (0.0 if res == 0 else math.inf)
+                cnt += ratio <= float(zk)
+        assert row[a0 + k] == cnt, (k, zk)
+    assert np.all(row[a0 + len(z):s0] == 0)
+    for f in range(4):
+        assert np.all(row[s0 + 128 * f + len(ratios):s0 + 128 * (f + 1)] == 0)
+    if which == "edge" and nv:                                             # the edges are where they are meant to be
+        fam0 = row[s0:s0 + 128]
+        total = math.fsum(float(v) for v in sq)
+        assert fam0[2] == fam0[3] == 0.0 and abs(fam0[1] - total) <= 1e-12 * total and fam0[1] == fam0[4]
+        assert row[a0 + 2] == nv * Cc and row[a0 + 3] == row[a0 + 4] and row[a0 + 5] == row[a0 + 1]
+    assert (row[8], row[9], row[10], row[11]) == (float(p.min()), float(p.max()), float(t.min()), float(t.max()))
+    for j, v in ((2, sq), (3, ab), (4, var), (5, s)):
+        w = math.fsum(float(x) for x in v)
+        assert abs(row[j] - w) <= 1e-12 * w, j
+
+
+def test_restate_row_of_nothing_valid(lib):
+    """an all-zero mask: counts and sums 0, minima +inf, maxima -inf (the header: "+-inf when nothing is valid")"""
+    from uncertainty_nerf_gs_amd import metrics as M
+    pred, std, gt = _case(5, 7)
+    row, ex = restate_row(pred, gt, std, torch.zeros(5, 7, dtype=torch.bool), clip=1.0)
+    assert ex["n"] == 0 and tuple(row[8:12]) == (math.inf, -math.inf, math.inf, -math.inf)
+    assert np.all(np.delete(row, [8, 9, 10, 11]) == 0)
+    with pytest.raises(ValueError, match="no valid pixel"):
         M.finish_metrics(row, 3)
