@@ -53,6 +53,14 @@ def main():
     ap.add_argument("-o", "--out", required=True)
     a = ap.parse_args()
     s = open(SRC).read()
+    # the f16 matrix field kernel (the K-pass marker sits in it) is a text of its own, included under two kernel names: the
+    # copy gets it spliced in for the first name (the single-view kernels the probes time); the several-views name keeps
+    # including the product text
+    inc = '#include "unerf_field_mfma16.inc"\n'
+    inc_path = os.path.join(os.path.dirname(SRC), "unerf_field_mfma16.inc")
+    assert s.count(inc) == 2
+    first, rest = s.split(inc, 1)
+    s = first + open(inc_path).read() + rest.replace(inc, f'#include "{inc_path}"\n')
     if a.extra_valu or a.extra_mfma:
         marker = "            // [probe:kpass-pass-start]\n"
         assert s.count(marker) == 1

@@ -510,6 +510,67 @@ int unerf_composite_moments_planes(const float* density, const float* rgb, const
                                    const float* background_rgb_host, int32_t* nonfinite_flag, float* mean_out,
                                    float* var_out, void* stream);
 
+/* ------------------------------------------- several whole views per launch --
+ * A frame of a few ten thousand rays leaves most of a launch group (2^20 rays) empty; the *_views entry points take the
+ * rays of B cameras of ONE image size H x W as one launch: a tall row-major image of B H rows, launch row j = view
+ * j / (H W) at frame-local ray j mod (H W).  Everything a kernel numbers by "the ray's index inside its frame" -- the
+ * per-chunk clip bounds of the expected depth, the MC-dropout mask counter, the camera of the ray generator -- takes the
+ * frame-local index and the view's own values, so that view v of the launch is bit-identical to a launch of its own with
+ * ray_offset = 0 (and p->seed = seed[v]).  The image_width tile hints are locality hints that change no bit and keep
+ * working on the tall image with the launch-global row.  Each call refuses, before any launch: n_views outside
+ * [1, UNERF_NERF_MAX_VIEWS], rays_per_view <= 0, R != n_views * rays_per_view. */
+#define UNERF_NERF_MAX_VIEWS 16
+typedef struct {            /* host struct */
+    int32_t n_views;        /* views in this launch */
+    int64_t rays_per_view;  /* H W */
+    uint32_t seed[UNERF_NERF_MAX_VIEWS];   /* MC-dropout mask seed of each view (unerf_field_fwd_views; else ignored) */
+} unerf_ray_views;
+typedef struct {            /* host struct: one camera of unerf_generate_rays_views */
+    float c2w[12];          /* [3,4] row-major */
+    float fx, fy, cx, cy;
+    float distortion[6];    /* k1, k2, k3, k4, p1, p2; all 0 = no lens */
+} unerf_ray_camera;
+
+/* unerf_generate_rays for n_views whole frames of H x W pixels and one camera type: origins / directions
+ * [n_views H W, 3], pixel_area [n_views H W] or NULL; view v's rows are those of unerf_generate_rays(cameras[v], ...,
+ * ray_start = 0, count = H W), bit for bit. */
+int unerf_generate_rays_views(const unerf_ray_camera* cameras_host, int n_views, int camera_type, int H, int W,
+                              float* origins, float* directions, float* pixel_area, void* stream);
+
+/* unerf_weights_pdf_resample with the clip rows numbered per view: clip_minmax addresses the first view's rows,
+ * chunk c of view v is row v * ceil(rays_per_view / chunk_rays) + c (the reference chunks every camera on its own). */
+int unerf_weights_pdf_resample_views(const float* density, const float* sbins, int64_t sbins_stride, int64_t R, int n,
+                                     float near_plane, float far_plane, int spacing, const float* u, int m,
+                                     float histogram_padding, float eps, float* sbins_out, float* prop_depth_out,
+                                     float* weights_out, float* clip_minmax, const unerf_ray_views* views /* host struct */,
+                                     int64_t chunk_rays, void* stream);
+
+/* unerf_composite_var / unerf_composite_moments reading the clip rows of unerf_weights_pdf_resample_views */
+int unerf_composite_var_views(const float* density, const float* rgb, const float* beta, const float* weights_alt,
+                              const float* sbins, int B, int64_t R, int S, float near_plane, float far_plane, int spacing,
+                              const float* clip_minmax, const unerf_ray_views* views /* host struct */, int64_t chunk_rays,
+                              int background, const float* background_rgb_host, int32_t* nonfinite_flag, float* out,
+                              void* stream);
+int unerf_composite_moments_views(const float* density, const float* rgb, const float* sbins, int B, int64_t R, int S,
+                                  float near_plane, float far_plane, int spacing, const float* clip_minmax,
+                                  const unerf_ray_views* views /* host struct */, int64_t chunk_rays, int background,
+                                  const float* background_rgb_host, int32_t* nonfinite_flag, float* mean_out,
+                                  float* var_out, void* stream);
+
+/* unerf_field_fwd over several views: sample (r, s) of view v draws the masks of counter r_local * S + s under seed[v]
+ * (p->seed is not read), i.e. what unerf_field_fwd(ray_offset = 0, p->seed = seed[v]) draws for that view alone.
+ * Built for the frame kernels: ACTIVE and MCDROPOUT on the split-f16 / single-f16 matrix kernels (mfma16_blob; "f16x2" and
+ * "f16"), nerfacto's widths, the default Dropout sites, ray-major outputs (packed_out or not).  ACTIVE, and MCDROPOUT
+ * with K = 0 or p_drop = 0, have no per-view value and run the kernels of unerf_field_fwd.  Refused before any launch,
+ * with a message that says so: LAPLACE, no mfma16_blob (the exact-fp32 and VALU kernels), the any-width kernel,
+ * sample_major planes, pre-gathered features, other drop_sites than TRUNK | HEAD1, and explicit keep masks (`masks`
+ * is there to be refused by name: unerf_field_fwd_masked takes one frame, and nothing falls back to another kernel). */
+int unerf_field_fwd_views(const float* origins, const float* directions, const float* sbins, int64_t R, int S,
+                          float near_plane, float far_plane, int spacing, const unerf_ray_views* views /* host struct */,
+                          const unerf_field_params* p /* host struct */, const float* features /* must be NULL */,
+                          float* density, float* rgb, float* aux, float* aux2,
+                          const unerf_keep_masks* masks /* must be NULL */, void* stream);
+
 /* ------------------------------------------------------ moments over K --
  * Replaces torch.stack(...).mean(0) / .std(0) / .var(0) over MC passes
  * (models/mcdropout/mcdropout_models.py:121-126) and over ensemble members

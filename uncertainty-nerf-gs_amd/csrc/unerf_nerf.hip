@@ -139,6 +139,47 @@ __device__ __forceinline__ uint32_t fastdiv(uint32_t x, const FastDiv& f) {
     return f.magic ? (__umulhi(x, f.magic) >> f.shift) : x;
 }
 
+// Several whole views in one launch (include/unerf.h: unerf_ray_views): launch row j is frame-local ray j mod hw of view
+// j / hw.  A kernel argument of the *_views instantiations only (a trailing parameter pack that is empty in the
+// single-view kernels, which keep their argument list and their code).
+struct ViewMap {
+    FastDiv div_hw, div_chunk;   // by rays per view, by chunk_rays
+    uint32_t hw;
+    uint32_t cpv;                // clip rows (chunks) per view: ceil(hw / chunk_rays)
+};
+__device__ __forceinline__ void view_of(const ViewMap& m, uint32_t j, uint32_t& view, uint32_t& local) {
+    view = fastdiv(j, m.div_hw);
+    local = j - view * m.hw;
+}
+// Row of the clip buffer that launch row r reads / updates.  Single view: the chunk of frame ray ray_offset + r.
+template <typename Args>
+__device__ __forceinline__ int64_t clip_chunk(const Args& a, int64_t r) {
+    return (a.ray_offset + r) / a.chunk_rays;
+}
+template <typename Args>
+__device__ __forceinline__ int64_t clip_chunk(const Args&, int64_t r, const ViewMap& m) {
+    uint32_t view, local;
+    view_of(m, (uint32_t)r, view, local);
+    return (int64_t)(view * m.cpv + fastdiv(local, m.div_chunk));
+}
+static int check_views(const unerf_ray_views* v, int64_t R, const char* what) {
+    UNERF_REQUIRE(v, "%s: null views", what);
+    UNERF_REQUIRE(v->n_views >= 1 && v->n_views <= UNERF_NERF_MAX_VIEWS, "%s: n_views=%d outside [1,%d]", what, (int)v->n_views,
+                  UNERF_NERF_MAX_VIEWS);
+    UNERF_REQUIRE(v->rays_per_view > 0, "%s: rays_per_view=%lld must be > 0", what, (long long)v->rays_per_view);
+    UNERF_REQUIRE(R == (int64_t)v->n_views * v->rays_per_view, "%s: R=%lld is not n_views x rays_per_view = %d x %lld", what,
+                  (long long)R, (int)v->n_views, (long long)v->rays_per_view);
+    UNERF_REQUIRE(R < (1ll << 31), "%s: R=%lld rays in one launch (32-bit row index)", what, (long long)R);
+    return UNERF_OK;
+}
+static ViewMap make_view_map(const unerf_ray_views* v, int64_t chunk_rays) {
+    ViewMap m;
+    const int64_t hw = v->rays_per_view, cr = chunk_rays > 0 ? (chunk_rays < (1ll << 31) ? chunk_rays : (1ll << 31) - 1) : 1;
+    m.div_hw = make_fastdiv((uint32_t)hw); m.div_chunk = make_fastdiv((uint32_t)cr);
+    m.hw = (uint32_t)hw; m.cpv = (uint32_t)((hw + cr - 1) / cr);
+    return m;
+}
+
 // ======================================================================================
 // wave / group helpers
 // ======================================================================================
@@ -291,10 +332,8 @@ __device__ __forceinline__ void raygen_dir(const RayGenArgs& a, float u, float v
     dz = z / n;
 }
 
-__global__ __launch_bounds__(256) void raygen_kernel(RayGenArgs a) {
-    int64_t n = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (n >= a.count) return;
-    int64_t g = a.start + n;
+// pixel g of the frame -> row n of the outputs
+__device__ __forceinline__ void raygen_one(const RayGenArgs& a, int64_t g, int64_t n) {
     int i = (int)(g / a.W), j = (int)(g % a.W);
     float y = (float)i + 0.5f, x = (float)j + 0.5f;
     float u0 = (x - a.cx) / a.fx, v0 = -(y - a.cy) / a.fy;
@@ -323,6 +362,74 @@ __global__ __launch_bounds__(256) void raygen_kernel(RayGenArgs a) {
         float dyn = sqrtf((fx_ * fx_ + fy_ * fy_) + fz_ * fz_);
         a.pa[n] = dxn * dyn;
     }
+}
+
+__global__ __launch_bounds__(256) void raygen_kernel(RayGenArgs a) {
+    int64_t n = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (n >= a.count) return;
+    raygen_one(a, a.start + n, n);
+}
+
+// Several whole frames of one size and camera type (unerf_generate_rays_views): blockIdx.y = the view, so the camera is
+// block-uniform (scalar loads from the argument block) and every pixel runs raygen_one on its own view's record.
+struct RayGenCam {
+    float R[9], T[3], fx, fy, cx, cy, k1, k2, k3, k4, p1, p2;
+    int distorted;
+};
+struct RayGenViewsArgs {
+    RayGenArgs base;   // camera_type, H, W, count = H W, outputs; the camera fields are taken from cam[view]
+    RayGenCam cam[UNERF_NERF_MAX_VIEWS];
+};
+__global__ __launch_bounds__(256) void raygen_views_kernel(RayGenViewsArgs v) {
+    const int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (g >= v.base.count) return;
+    const RayGenCam& c = v.cam[blockIdx.y];
+    RayGenArgs a = v.base;
+    for (int i = 0; i < 9; ++i) a.R[i] = c.R[i];
+    for (int i = 0; i < 3; ++i) a.T[i] = c.T[i];
+    a.fx = c.fx; a.fy = c.fy; a.cx = c.cx; a.cy = c.cy;
+    a.k1 = c.k1; a.k2 = c.k2; a.k3 = c.k3; a.k4 = c.k4; a.p1 = c.p1; a.p2 = c.p2;
+    a.distorted = c.distorted;
+    raygen_one(a, g, (int64_t)blockIdx.y * v.base.count + g);
+}
+
+static int raygen_check_type(int camera_type, const char* what) {
+    UNERF_REQUIRE(camera_type == UNERF_CAMERA_PERSPECTIVE || camera_type == UNERF_CAMERA_FISHEYE ||
+                      camera_type == UNERF_CAMERA_EQUIRECTANGULAR || camera_type == UNERF_CAMERA_ORTHOPHOTO,
+                  "%s: camera_type %d is not built (PERSPECTIVE 1, FISHEYE 2, EQUIRECTANGULAR 3, ORTHOPHOTO 8)", what, camera_type);
+    return UNERF_OK;
+}
+
+extern "C" int unerf_generate_rays_views(const unerf_ray_camera* cameras, int n_views, int camera_type, int H, int W,
+                                         float* origins, float* directions, float* pixel_area, void* stream) {
+    UNERF_REQUIRE(n_views >= 1 && n_views <= UNERF_NERF_MAX_VIEWS, "generate_rays_views: n_views=%d outside [1,%d]", n_views,
+                  UNERF_NERF_MAX_VIEWS);
+    UNERF_REQUIRE(cameras && origins && directions, "generate_rays_views: null pointer");
+    if (int rc = raygen_check_type(camera_type, "generate_rays_views")) return rc;
+    UNERF_REQUIRE(H > 0 && W > 0 && (int64_t)H * W * n_views < (1ll << 31), "generate_rays_views: %d views of %dx%d", n_views, H, W);
+    RayGenViewsArgs v;
+    memset(&v, 0, sizeof(v));
+    for (int i = 0; i < n_views; ++i) {
+        const unerf_ray_camera& s = cameras[i];
+        RayGenCam& c = v.cam[i];
+        for (int r = 0; r < 3; ++r) {
+            for (int k = 0; k < 3; ++k) c.R[r * 3 + k] = s.c2w[r * 4 + k];
+            c.T[r] = s.c2w[r * 4 + 3];
+        }
+        c.fx = s.fx; c.fy = s.fy; c.cx = s.cx; c.cy = s.cy;
+        if (camera_type != UNERF_CAMERA_EQUIRECTANGULAR) {   // as unerf_generate_rays
+            for (int k = 0; k < 6; ++k) {
+                UNERF_REQUIRE(std::isfinite(s.distortion[k]), "generate_rays_views: distortion[%d] of view %d is not finite", k, i);
+                c.distorted |= s.distortion[k] != 0.f;
+            }
+            c.k1 = s.distortion[0]; c.k2 = s.distortion[1]; c.k3 = s.distortion[2]; c.k4 = s.distortion[3];
+            c.p1 = s.distortion[4]; c.p2 = s.distortion[5];
+        }
+    }
+    v.base.camera_type = camera_type; v.base.H = H; v.base.W = W; v.base.start = 0; v.base.count = (int64_t)H * W;
+    v.base.o = origins; v.base.d = directions; v.base.pa = pixel_area;
+    hipLaunchKernelGGL(raygen_views_kernel, dim3(blocks_for(v.base.count, 256), (unsigned)n_views), dim3(256), 0, (hipStream_t)stream, v);
+    return unerf_check_launch("generate_rays_views");
 }
 
 extern "C" int unerf_generate_rays(const float* c2w, float fx, float fy, float cx, float cy, const float* distortion,
@@ -896,8 +1003,8 @@ __device__ __forceinline__ void pdf_clip_commit(float* clip, int64_t chunk, unsi
     if (hi > __hip_atomic_load(c + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(c + 1, hi);
 }
 
-template <int EPL>
-__global__ __launch_bounds__(256) void pdf_kernel(PdfArgs a) {
+template <int EPL, typename... VW>   // VW = ViewMap: the clip rows are numbered per view (unerf_weights_pdf_resample_views)
+__global__ __launch_bounds__(256) void pdf_kernel(PdfArgs a, VW... vw) {
     __shared__ float s_sb[4][PDF_MAXN + 4];
     __shared__ float s_cdf[4][PDF_MAXN + 4];
     __shared__ float s_nb[4][PDF_MAXN + 4];
@@ -1038,7 +1145,7 @@ __global__ __launch_bounds__(256) void pdf_kernel(PdfArgs a) {
             const float ev = unerf_s2e(s_nb[wv][ei], a.s_near, a.s_far, a.lin);
             const float f0 = __shfl(ev, 0, 64), f1 = __shfl(ev, 1, 64), l0 = __shfl(ev, 2, 64), l1 = __shfl(ev, 3, 64);
             float first = (f0 + f1) / 2.f, last = (l0 + l1) / 2.f;
-            const int64_t chunk = (a.ray_offset + r) / a.chunk_rays;
+            const int64_t chunk = clip_chunk(a, r, vw...);
             if (chunk != cur_chunk) {
                 if (cur_chunk >= 0 && lane == 0) pdf_clip_commit(a.clip, cur_chunk, cmin, cmax);
                 cur_chunk = chunk;
@@ -1053,7 +1160,7 @@ __global__ __launch_bounds__(256) void pdf_kernel(PdfArgs a) {
     }  // rays of this block
     if (a.clip) {
         // the four waves normally sit in one chunk: merge them through LDS and send one update
-        const int64_t blk_chunk = (a.ray_offset + (int64_t)blockIdx.x * PDF_RAYS_PER_BLOCK) / a.chunk_rays;
+        const int64_t blk_chunk = clip_chunk(a, (int64_t)blockIdx.x * PDF_RAYS_PER_BLOCK, vw...);
         const bool mergeable = cur_chunk == blk_chunk;  // this wave never left the block's first chunk
         if (lane == 0) {
             s_clip[wv][0] = mergeable ? cmin : 0x7F800000u;
@@ -1069,11 +1176,12 @@ __global__ __launch_bounds__(256) void pdf_kernel(PdfArgs a) {
     }
 }
 
-extern "C" int unerf_weights_pdf_resample(const float* density, const float* sbins, int64_t sbins_stride, int64_t R,
-                                          int n, float near_plane, float far_plane, int spacing, const float* u, int m,
-                                          float histogram_padding, float eps, float* sbins_out, float* prop_depth_out,
-                                          float* weights_out, float* clip_minmax, int64_t ray_offset,
-                                          int64_t chunk_rays, void* stream) {
+// views = NULL: unerf_weights_pdf_resample
+static int pdf_resample_impl(const float* density, const float* sbins, int64_t sbins_stride, int64_t R,
+                             int n, float near_plane, float far_plane, int spacing, const float* u, int m,
+                             float histogram_padding, float eps, float* sbins_out, float* prop_depth_out,
+                             float* weights_out, float* clip_minmax, int64_t ray_offset,
+                             int64_t chunk_rays, const unerf_ray_views* views, void* stream) {
     UNERF_REQUIRE(R <= 0 || (density && sbins && u && sbins_out), "weights_pdf_resample: null pointer");
     UNERF_REQUIRE(n >= 1 && n <= PDF_MAXN, "weights_pdf_resample: n=%d outside [1,%d]", n, PDF_MAXN);
     UNERF_REQUIRE(m >= 1 && m + 1 <= PDF_MAXN, "weights_pdf_resample: m=%d outside [1,%d]", m, PDF_MAXN - 1);
@@ -1089,6 +1197,16 @@ extern "C" int unerf_weights_pdf_resample(const float* density, const float* sbi
     dim3 grid(blocks_for(R, PDF_RAYS_PER_BLOCK)), block(256);
     hipStream_t st = (hipStream_t)stream;
     int epl = (n + 63) / 64;
+    if (views && clip_minmax) {   // (without a clip buffer nothing in the kernel is numbered by the frame)
+        const ViewMap vm = make_view_map(views, chunk_rays);
+        switch (epl) {
+            case 1: hipLaunchKernelGGL((pdf_kernel<1, ViewMap>), grid, block, 0, st, a, vm); break;
+            case 2: hipLaunchKernelGGL((pdf_kernel<2, ViewMap>), grid, block, 0, st, a, vm); break;
+            case 3: hipLaunchKernelGGL((pdf_kernel<3, ViewMap>), grid, block, 0, st, a, vm); break;
+            default: hipLaunchKernelGGL((pdf_kernel<4, ViewMap>), grid, block, 0, st, a, vm); break;
+        }
+        return unerf_check_launch("weights_pdf_resample_views");
+    }
     switch (epl) {
         case 1: hipLaunchKernelGGL((pdf_kernel<1>), grid, block, 0, st, a); break;
         case 2: hipLaunchKernelGGL((pdf_kernel<2>), grid, block, 0, st, a); break;
@@ -1096,6 +1214,25 @@ extern "C" int unerf_weights_pdf_resample(const float* density, const float* sbi
         default: hipLaunchKernelGGL((pdf_kernel<4>), grid, block, 0, st, a); break;
     }
     return unerf_check_launch("weights_pdf_resample");
+}
+
+extern "C" int unerf_weights_pdf_resample(const float* density, const float* sbins, int64_t sbins_stride, int64_t R,
+                                          int n, float near_plane, float far_plane, int spacing, const float* u, int m,
+                                          float histogram_padding, float eps, float* sbins_out, float* prop_depth_out,
+                                          float* weights_out, float* clip_minmax, int64_t ray_offset,
+                                          int64_t chunk_rays, void* stream) {
+    return pdf_resample_impl(density, sbins, sbins_stride, R, n, near_plane, far_plane, spacing, u, m, histogram_padding, eps,
+                             sbins_out, prop_depth_out, weights_out, clip_minmax, ray_offset, chunk_rays, nullptr, stream);
+}
+
+extern "C" int unerf_weights_pdf_resample_views(const float* density, const float* sbins, int64_t sbins_stride, int64_t R,
+                                                int n, float near_plane, float far_plane, int spacing, const float* u, int m,
+                                                float histogram_padding, float eps, float* sbins_out, float* prop_depth_out,
+                                                float* weights_out, float* clip_minmax, const unerf_ray_views* views,
+                                                int64_t chunk_rays, void* stream) {
+    if (int rc = check_views(views, R, "weights_pdf_resample_views")) return rc;
+    return pdf_resample_impl(density, sbins, sbins_stride, R, n, near_plane, far_plane, spacing, u, m, histogram_padding, eps,
+                             sbins_out, prop_depth_out, weights_out, clip_minmax, 0, chunk_rays, views, stream);
 }
 
 // ======================================================================================
@@ -1165,6 +1302,21 @@ __device__ __forceinline__ const KeepArgs& xm_of(const KeepArgs& x) { return x; 
 __device__ __forceinline__ const uint32_t* xm_row(const KeepArgs& x, int site, int k, int64_t n) {
     return x.site[site] + ((int64_t)k * x.pass_stride + x.sample_offset + n) * XM_WORDS;
 }
+
+// SEVERAL VIEWS in one launch (unerf_field_fwd_views): a kernel argument of the views instantiations of field_kernel_mfma16
+// only, like KeepArgs.  The mask counter of a sample is numbered inside its own frame and keyed by its view's seed; a tile
+// may straddle two views, so both are per-lane values (the keys are staged in LDS and read by view index).
+struct FieldViews {
+    FastDiv div_hw;   // by rays per view
+    uint32_t hw;
+    uint32_t key[UNERF_NERF_MAX_VIEWS];   // unerf_mc_key(seed[v], 0)
+};
+__device__ __forceinline__ const FieldViews& vw_of(const FieldViews& x) { return x; }
+// which trailing argument an instantiation carries (none: the default kernels)
+template <typename... XA> struct xa_is_keep : std::false_type {};
+template <> struct xa_is_keep<KeepArgs> : std::true_type {};
+template <typename... XA> struct xa_is_views : std::false_type {};
+template <> struct xa_is_views<FieldViews> : std::true_type {};
 
 // Bin edge -> Euclidean distance.  unerf_field_fwd(near_plane < 0) sets s_near = -1: sbins then already holds
 // Euclidean edges (RaySamples.frustums.starts / ends of a caller-made sampler) and passes through untouched.
@@ -2451,390 +2603,17 @@ __device__ __forceinline__ void mf_pin8(uint32_t (&x)[8]) {
 // k-step of the masked layers carried a branch and the operand quads were copied to merge the two paths.
 // XA = KeepArgs: explicit keep masks (unerf_field_fwd_masked), on the general SITES form
 // Which of the three (SITES, DROP) forms a call gets: field_launch(); its LDS bytes: mf16_lds_bytes().
-template <int MODE, int TCNN, bool SITES = false, bool DROP = false, bool F1 = false, typename... XA>
-// (the single-product K-pass kernel at 3 waves per SIMD was measured twice and lost both times: round 3, 168 VGPRs, 96 B of
-// scratch, trunk operands re-read from LDS -- 4.84 vs 3.89 ms per launch, profiles/r3_exp_f16_single_occ3.json; round 7,
-// 163 VGPRs, no scratch, the SH k-step of colour 0 recomputed per pass -- 12.71 - 12.88 vs 12.44 - 12.56 ms, docs/experiments.md 7.1)
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((MODE == UNERF_FIELD_ACTIVE && TCNN != 1) ? 3 : 2)))
-void field_kernel_mfma16(FieldArgs a, uint32_t num_tiles, FastDiv div_s, XA... xa) {
-    constexpr bool XM = sizeof...(XA) != 0;
-    static_assert(!XM || (SITES && DROP && MODE == UNERF_FIELD_MCDROPOUT), "explicit keep masks ride on the general SITES path");
-    extern __shared__ float lds[];
-    {
-        const float4* src = reinterpret_cast<const float4*>(a.p.mfma16_blob);
-        float4* dst = reinterpret_cast<float4*>(lds);
-        for (int i = threadIdx.x; i < (F1 ? UNERF_MFMA16_BLOB_FLOATS : UNERF_MFMA_BLOB_FLOATS) / 4; i += 256) dst[i] = src[i];
-    }
-    __shared__ uint32_t s_tl[TCNN ? MF_TL_WORDS : 1];
-    if (TCNN) mf_stage_tcnn_levels<(TCNN == 2 ? 2 : 3)>(a, s_tl);
-    __syncthreads();
-    const int lane_c = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int j = lane_c & 31, h = lane_c >> 5;
-    const int64_t N = a.R * (int64_t)a.S;
-    const uint32_t mask = (1u << a.p.log2T) - 1u;
-    const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3, bpx = gridDim.x >> 3;
-    const uint32_t tpx = (num_tiles + 7u) / 8u;
-    const uint32_t tile_end = (xcd + 1) * tpx < num_tiles ? (xcd + 1) * tpx : num_tiles;
-    bool f1_bad = false;   // an f16 operand overflowed: F1 -- an output pre-activation of this lane was inf / NaN (see the
-                           // epilogue); split form -- a colour layer's pre-activations were NaN (see colour 0 below)
-    for (uint32_t tile = xcd * tpx + (uint32_t)slot * 4u + (uint32_t)wv; tile < tile_end; tile += (uint32_t)bpx * 4u) {
-        int lane = lane_c;  // opaque per iteration: keeps the (tile-invariant) LDS operand reads inside the loop
-        asm volatile("" : "+v"(lane));
-        const TileSample ts = tile_sample(a, tile, div_s, j);
-        const bool valid = ts.valid;
-        const int64_t n = ts.n;
-        const float dxr = ts.dx, dyr = ts.dy, dzr = ts.dz;
-        float px = ts.px, py = ts.py, pz = ts.pz;
-        const float sel = unerf_normalize_position(px, py, pz, a.box);
-        // packed fp32x2 blend: this kernel has the registers for it (123 VGPRs without) in every mode
-        // colour layer 0, SH half (pass-invariant): components 8h..8h+7 of this lane half, one k-step -- as a closure, so
-        // that the torch-layout kernels can run it behind the first grid loads of the tile (mf_gather_feats_pipe)
-        f32x16 csh0 = mf16_bias(lds, 3, h), csh1 = mf16_bias(lds, 4, h);
-        auto sh_layer = [&]() {
-            float sh[16];
-            float ux = (dxr + 1.f) / 2.f, uy = (dyr + 1.f) / 2.f, uz = (dzr + 1.f) / 2.f;
-            if (a.p.sh_remap) {
-                ux = ux * 2.f - 1.f;
-                uy = uy * 2.f - 1.f;
-                uz = uz * 2.f - 1.f;
-            }
-            unerf_sh16(ux, uy, uz, sh);
-            const uint32_t hm = 0u - (uint32_t)h;
-            float mine[8];
-#pragma unroll
-            for (int q = 0; q < 8; ++q)
-                mine[q] = __uint_as_float((__float_as_uint(sh[8 + q]) & hm) | (__float_as_uint(sh[q]) & ~hm));
-            f16x8 bhi, blo;
-            mf16_split8<F1>(mine, bhi, blo);
-            mf16_mac2<F1>(lds, 10, 11, lane, bhi, blo, csh0, csh1);
-        };
-        u32x8 feat_pk;
-        f32x16 feat;
-        if constexpr (TCNN == 0 && UNERF_GATHER_PIPE != 0) {
-            feat = mf_gather_feats_pipe(a, px, py, pz, h, mask, sh_layer);
-        } else {
-            feat = mf_gather_feats<true, TCNN>(a, px, py, pz, h, mask, s_tl, &feat_pk);
-            sh_layer();
-        }
-
-        // layer 0: 32 -> 64 (this half's 16 features = two k-steps), ReLU; the 64 hidden units are the trunk
-        // layer's four k-steps and do not depend on the MC pass: they are split into f16 operand quads ONCE
-        f16x8 hhi[4], hlo[4];
-        {
-            f32x16 hid0 = mf16_bias(lds, 0, h), hid1 = mf16_bias(lds, 1, h);
-#pragma unroll
-            for (int st = 0; st < 2; ++st) {
-                f16x8 bhi, blo;
-                mf16_feat_operand<TCNN, F1>(feat, feat_pk, st, bhi, blo);
-                mf16_mac2<F1, TCNN == 2>(lds, 2 * st, 2 * st + 1, lane, bhi, blo, hid0, hid1);
-            }
-            if constexpr (F1) {   // ReLU on the packed halves (relu(cvt(x)) = cvt(relu(x)): mf16_split_relu), half the instructions
-#pragma unroll
-                for (int st = 0; st < 4; ++st) {
-                    mf16_split_relu(st < 2 ? hid0 : hid1, st & 1, hhi[st]);
-                    hlo[st] = hhi[st];
-                }
-            } else {
-                hid0 = mf_relu(hid0);
-                hid1 = mf_relu(hid1);
-#pragma unroll
-                for (int st = 0; st < 4; ++st) mf16_split<F1>(st < 2 ? hid0 : hid1, st & 1, hhi[st], hlo[st]);
-            }
-        }
-
-        const int passes = (MODE == UNERF_FIELD_MCDROPOUT && a.p.K > 0) ? a.p.K : 1;
-        // variants: the trunk-out operands (4 k-steps x 2 quads = 32 VGPRs) kept in registers across the passes; the
-        // 16-row trunk-out layer of MCDROPOUT folded into two MFMAs per k-step
-        constexpr bool TRUNK_RESIDENT = UNERF_TRUNK_RESIDENT && MODE == UNERF_FIELD_MCDROPOUT && DROP && !SITES;
-        // F1: the first operand of a (folded or plain) trunk slab is W_hi, which is all the single-product form reads
-        constexpr bool FOLD = UNERF_TRUNK_FOLD && MODE == UNERF_FIELD_MCDROPOUT && !F1;
-        f16x8 ta0[4], ta1[4];   // first / second operand of trunk slab 4 + st
-        if (TRUNK_RESIDENT) {
-#pragma unroll
-            for (int st = 0; st < 4; ++st) {
-                ta0[st] = *reinterpret_cast<const f16x8*>(lds + (4 + st) * 512 + lane * 4);
-                if (!F1) ta1[st] = *reinterpret_cast<const f16x8*>(lds + (4 + st) * 512 + 256 + lane * 4);
-            }
-        }
-        constexpr bool drop = DROP;   // host: a.drop_on
-        const uint32_t sidx = (uint32_t)((uint64_t)a.ray_offset * (uint64_t)a.S + (uint64_t)n);
-        uint32_t mk0[8], mk1[8], mk2[8], mk3[8];
-        uint32_t base0_h0 = 0u;   // SITES only: the sample's base hash stays live across the passes
-        const bool drop_trunk = SITES ? (drop && (a.drop_sites & UNERF_DROP_TRUNK)) : drop;
-        const bool drop_head1 = SITES ? (drop && (a.drop_sites & UNERF_DROP_HEAD1)) : drop;
-        if (drop && !XM) {
-            const uint32_t base0 = unerf_mc_base_h(unerf_mc_pre(unerf_mc_key(a.p.seed, 0u), sidx), (uint32_t)h);   // this lane half's
-            if (SITES) base0_h0 = base0;
-            mf_mask_init(mk0, 0, h, base0, 0u);
-            mf_mask_init(mk1, 1, h, base0, 0u);
-            mf_mask_init(mk2, 0, h, base0, 1u);
-            mf_mask_init(mk3, 1, h, base0, 1u);
-        }
-        // UNERF_KPASS_FILL (F1, default sites): AND masks of the trunk for the pass about to run (am_t*), of the head for the
-        // running pass (am_h*).  The words are stepped and tested BEHIND the matrix instructions of a pass instead of in front
-        // of them: an MFMA holds the SIMD's issue for ~10 of its 32 cycles, five or six independent VALU instructions ride in
-        // its shadow for nothing (benchmarks/issue_sweep_probe.hip), and the mask arithmetic -- 96 of a pass' 216 VALU
-        // instructions -- depends on nothing the pass computes.  Same words, same tests, same bits.
-        constexpr bool FILL = UNERF_KPASS_FILL && F1 && DROP && !SITES && MODE == UNERF_FIELD_MCDROPOUT;
-        uint32_t am_t0[8], am_t1[8], am_h0[8], am_h1[8];
-        if (FILL) {
-            mf16_keep_sub(mk0, a.keep_pk, am_t0);
-            mf16_keep_sub(mk1, a.keep_pk, am_t1);
-            mf16_keep_sign(am_t0);
-            mf16_keep_sign(am_t1);
-        }
-        for (int k = 0; k < passes; ++k) {
-            asm volatile("" : "+v"(lane));
-            if constexpr (XM) {   // this pass' words from the keep bits instead of a generator step
-                if (drop_trunk) {
-                    mf_xm_words(mk0, xm_row(xm_of(xa...), 0, k, n), 0, h);
-                    mf_xm_words(mk1, xm_row(xm_of(xa...), 0, k, n), 1, h);
-                }
-                if (drop_head1) {
-                    mf_xm_words(mk2, xm_row(xm_of(xa...), 2, k, n), 0, h);
-                    mf_xm_words(mk3, xm_row(xm_of(xa...), 2, k, n), 1, h);
-                }
-            } else if (!FILL && drop && k > 0) {
-                mf_mask_step(mk0);
-                mf_mask_step(mk1);
-                mf_mask_step(mk2);
-                mf_mask_step(mk3);
-            }
-            // [probe:kpass-pass-start]
-            // Wave priority: low through the matrix layers of a pass, high from the rgb layer to the end of the pass --
-            // and, after the last pass, through the next tile's gathers.  The tail (packed-fma chains, the half exchange,
-            // exp / rcp, stores) and the gather prologue are short instruction streams that wait on latencies; letting
-            // them go first when both waves of a SIMD are ready takes 4.2 % off the K = 8 kernel (same box, six
-            // placements tried: benchmarks/multi_ab.sh, profiles/r2_exp_setprio.json); high priority for the matrix
-            // layers instead gives 1.3 %, for the prologue alone nothing.
-            __builtin_amdgcn_s_setprio(0);
-            // trunk out: 64 -> out1 rows (row 0 density, 1..15 geo, 16 beta) from the (masked) hidden operands
-            f32x16 t = mf16_bias(lds, 2, h);
-#pragma unroll
-            for (int st = 0; st < 4; ++st) {
-                f16x8 bhi = hhi[st], blo = hlo[st];
-                if (FILL) {
-                    const uint32_t (&am)[8] = st < 2 ? am_t0 : am_t1;
-                    const u32x4 m = {am[4 * (st & 1)], am[4 * (st & 1) + 1], am[4 * (st & 1) + 2], am[4 * (st & 1) + 3]};
-                    bhi = __builtin_bit_cast(f16x8, __builtin_bit_cast(u32x4, bhi) & m);
-                } else if (drop_trunk) mf16_apply_masks<F1>(bhi, blo, st < 2 ? mk0 : mk1, st & 1, a.keep_pk);
-                f16x8 a0, a1;
-                if (TRUNK_RESIDENT) {
-                    a0 = ta0[st];
-                    a1 = F1 ? ta0[st] : ta1[st];
-                } else {
-                    a0 = mf16_lds_op(lds + (4 + st) * 512 + lane * 4);
-                    a1 = F1 ? a0 : *reinterpret_cast<const f16x8*>(lds + (4 + st) * 512 + 256 + lane * 4);
-                }
-                if (F1) {
-                    t = __builtin_amdgcn_mfma_f32_32x32x16_f16(a0, bhi, t, 0, 0, 0);
-                } else if (FOLD) {
-                    t = mf16_mac_fold_ops(a0, a1, bhi, blo, t);
-                } else {   // a0 = W_hi, a1 = W_lo: small terms first
-                    t = __builtin_amdgcn_mfma_f32_32x32x16_f16(a1, bhi, t, 0, 0, 0);
-                    t = __builtin_amdgcn_mfma_f32_32x32x16_f16(a0, blo, t, 0, 0, 0);
-                    t = __builtin_amdgcn_mfma_f32_32x32x16_f16(a0, bhi, t, 0, 0, 0);
-                }
-            }
-            if (FOLD) t = mf16_fold_rows(t);
-            if (FILL) {   // behind the trunk's four MFMAs: this pass' head words tested (mf16_split_relu_drop), then stepped for the next pass
-                MF_FENCE();
-                mf16_keep_sub(mk2, a.keep_pk, am_h0);
-                mf16_keep_sub(mk3, a.keep_pk, am_h1);
-                mf_mask_step(mk2);
-                mf_mask_step(mk3);
-                mf_pin8(am_h0); mf_pin8(am_h1); mf_pin8(mk2); mf_pin8(mk3);
-                MF_FENCE();
-            }
-            // colour 0: geo rows of t (registers 0..7 = one k-step) on top of the SH partial sum, ReLU
-            f32x16 c0 = csh0, c1 = csh1;
-            {
-                f16x8 bhi, blo;
-                mf16_split<F1>(t, 0, bhi, blo);
-                mf16_mac2<F1>(lds, 8, 9, lane, bhi, blo, c0, c1);
-            }
-            if (!F1) {   // F1: ReLU on the packed f16 operands instead (mf16_split_relu: half the instructions)
-                // Split form: an activation beyond 65504 is carried as hi = +inf, lo = -inf, and EVERY unit of the layer it
-                // feeds becomes inf - inf = NaN.  Trunk overflows reach the density logit as NaN and are caught by the
-                // composite kernels; behind a ReLU they would not be -- the integer maximum below maps a NaN whose sign bit
-                // is set to 0, and the layers after it then see a plausible all-zero hidden vector.  So one accumulator of
-                // each colour layer is tested before its ReLU (all 64 are NaN or none): two compares per pass.
-                f1_bad |= c0[0] != c0[0];
-                c0 = mf_relu(c0);
-                c1 = mf_relu(c1);
-            }
-            // colour 1: 64 -> 64, ReLU
-            f32x16 d0 = mf16_bias(lds, 5, h), d1 = mf16_bias(lds, 6, h);
-            if (SITES && drop && (a.drop_sites & UNERF_DROP_HEAD0)) {   // rgb_dropout_layers contains 1 (non-default): masks on c
-#pragma unroll
-                for (int st = 0; st < 4; ++st) {
-                    f16x8 bhi, blo;
-                    if (F1) mf16_split_relu(st < 2 ? c0 : c1, st & 1, bhi);
-                    else mf16_split<F1>(st < 2 ? c0 : c1, st & 1, bhi, blo);
-                    uint32_t mw[8];
-                    if constexpr (XM) mf_xm_words(mw, xm_row(xm_of(xa...), 1, k, n), st >> 1, h);
-                    else mf_mask_words_at(mw, st >> 1, h, base0_h0, 2u, k);
-                    mf16_apply_masks<F1>(bhi, blo, mw, st & 1, a.keep_pk);
-                    mf16_mac2<F1>(lds, 12 + 2 * st, 12 + 2 * st + 1, lane, bhi, blo, d0, d1);
-                }
-            } else {
-                mf16_layer64<2, F1, F1>(lds, 12, lane, c0, c1, d0, d1);
-            }
-            // (F1 with this layer as four more k-steps on the matrix pipe -- 16 conversions + 16 packed ReLUs + 48 packed-mask
-            // instructions + 4 MFMAs instead of the 154 instructions below -- was built and measured: 3.68 vs 3.89 ms per
-            // launch, but the f16 rounding of the last layer's operands moved one MC-dropout AUSE figure past its 1e-3
-            // gate; profiles/r3_exp_f16_rgb_on_mfma.json, DESIGN.md 4.5.  The colour layer stays fp32 in every form.)
-            float o[3];
-            if constexpr (F1) {
-                // colour 2: 64 -> 3 as four more k-steps on the matrix pipe (rows 0..2 of one 32-row block; slabs behind the
-                // fp32 tail of the blob), its operands = the hidden units rounded to f16 -- which is what the reference's
-                // Linear computes under its forced autocast (mcdropout_models.py:86-92: f16 inputs and weights, fp32
-                // accumulate) and what tcnn's FullyFusedMLP does.  ReLU and the dropout masks ride on the packed halves like
-                // the trunk's: convert 0.5 + ReLU 0.5 + mask 1.5 instructions per unit instead of ReLU 1 + compare 1 +
-                // select 1 on the fp32 accumulators, and 4 MFMAs (128 issue cycles) instead of 48 packed FMAs + the half
-                // exchange.  (Round 3 measured this form at -5 % and dropped it over ONE AUSE figure at 1.04e-3 -- a gate
-                // that the reference's own two arithmetics miss by more on that target)
-                if (FILL) {   // behind colour 1's last MFMAs: the trunk words stepped for the next pass
-                    MF_FENCE();
-                    mf_mask_step(mk0);
-                    mf_mask_step(mk1);
-                    mf_pin8(mk0); mf_pin8(mk1);
-                    MF_FENCE();
-                }
-                __builtin_amdgcn_s_setprio(1);
-                f32x16 o4;
-#pragma unroll
-                for (int r = 0; r < 16; ++r) o4[r] = 0.f;
-#pragma unroll
-                for (int st = 0; st < 4; ++st) {
-                    f16x8 bhi;
-                    if (FILL || drop_head1) {
-                        const uint32_t (&w)[8] = FILL ? (st < 2 ? am_h0 : am_h1) : (st < 2 ? mk2 : mk3);
-                        u32x4 dd;
-#pragma unroll
-                        for (int p = 0; p < 4; ++p) dd[p] = FILL ? w[4 * (st & 1) + p] : mf16_keep_diff(w[4 * (st & 1) + p], a.keep_pk);
-                        mf16_split_relu_drop(st < 2 ? d0 : d1, st & 1, dd, bhi);
-                    } else {
-                        mf16_split_relu(st < 2 ? d0 : d1, st & 1, bhi);
-                    }
-                    const f16x8 aw = mf16_lds_op(lds + UNERF_MFMA_BLOB_FLOATS + st * 256 + lane * 4);
-                    o4 = __builtin_amdgcn_mfma_f32_32x32x16_f16(aw, bhi, o4, 0, 0, 0);
-                }
-                if (FILL) {   // behind colour 2's four MFMAs: the next pass' trunk masks
-                    MF_FENCE();
-                    mf16_keep_sub(mk0, a.keep_pk, am_t0);
-                    mf16_keep_sub(mk1, a.keep_pk, am_t1);
-                    mf16_keep_sign(am_t0);
-                    mf16_keep_sign(am_t1);
-                    mf_pin8(am_t0); mf_pin8(am_t1);
-                    MF_FENCE();
-                }
-                // rows 0..2 = registers 0..2 of the h = 0 half: one v_permlane32_swap each hands them to both halves
-#pragma unroll
-                for (int c = 0; c < 3; ++c) {
-                    const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(o4[c]), __float_as_uint(o4[c]), false, false);
-                    o[c] = __uint_as_float(sw[0]) + lds[MF_H2_OFF + 192 + c];
-                }
-            } else {
-            if (!F1) f1_bad |= d0[0] != d0[0];
-            d0 = mf_relu(d0);
-            d1 = mf_relu(d1);
-            if (drop_head1) {   // masks on the fp32 accumulators: one half-word compare + one select per unit
-                d0 = mf_dropout_keep(d0, mk2, a.keep_hi);
-                d1 = mf_dropout_keep(d1, mk3, a.keep_hi);
-            }
-            __builtin_amdgcn_s_setprio(1);
-            // colour 2: 64 -> 3 on the VALU in fp32 (weights pre-scaled by the dropout scale when masks are on).
-            // A SIMD has an issue lane (4 cycles per VALU instruction, ~10 per f16 MFMA) beside its matrix lane (32 per MFMA:
-            // benchmarks/issue_sweep_probe.hip), and these kernels are bound by the issue lane, so a layer belongs
-            // where it costs fewer ISSUE cycles: as four more k-steps on the matrix pipe this one took 12 MFMAs + 48 split
-            // instructions (~310 issue cycles, 29 of 32 output rows wasted), as packed fp32 FMAs it takes 48 + the half-to-half
-            // exchange (~220).  (Rounds 2 - 5 argued the same choice from "MFMA and VALU never overlap, 32 + 4 cycles".)
-            {
-                const float4* wq = reinterpret_cast<const float4*>(lds + MF_H2_OFF + h * 48);
-                // Per 32-unit block the 12 weight quads (3 channels x 4) are read into an array FIRST and the 24 packed FMAs
-                // follow.  Written as one load per use the compiler issued each ds_read_b128 directly in front of its two FMAs
-                // and waited for it: 24 exposed LDS round trips per pass (`D1 W1 v1 n0 v1` 24 times in the listing), in which
-                // both waves of a SIMD tended to sit at once -- the K-pass "f16" kernel went 16.2 -> 15.0 ms per launch with the
-                // reads grouped (profiles/r4_exp_rgb_weight_reads_*.json).  Forcing the grouping further with
-                // sched_group_barrier was slower, and issuing the three channels' chains interleaved (no `s_nop` between
-                // dependent packed FMAs, 439 instead of 476 instructions per pass) changed nothing: the other wave fills
-                // those slots (profiles/r4_exp_rgb_interleave_*.json).
-                // (the split form has no registers for 12 quads in flight -- 28 B of scratch with them -- and groups 4)
-                constexpr int CG = F1 ? 3 : 1;   // channels whose weights are read together
-                unerf_v2f acc2[3] = {{0.f, 0.f}, {0.f, 0.f}, {0.f, 0.f}};
-#pragma unroll
-                for (int blk = 0; blk < 2; ++blk) {
-                    const f32x16& dv = blk ? d1 : d0;
-#pragma unroll
-                    for (int c0g = 0; c0g < 3; c0g += CG) {
-                        float4 wv[CG][4];
-#pragma unroll
-                        for (int c = 0; c < CG; ++c)
-#pragma unroll
-                            for (int q4 = 0; q4 < 4; ++q4) wv[c][q4] = wq[blk * 24 + (c0g + c) * 4 + q4];
-#pragma unroll
-                        for (int c = 0; c < CG; ++c) {
-#pragma unroll
-                            for (int q4 = 0; q4 < 4; ++q4) {
-                                // (round 6) UNERF_RGB_SCALAR: the same four fused multiply-adds on scalar registers (1: every
-                                // mode, 2: ACTIVE only -- measured -1.8 % there and +0.7 % in the K-pass kernel, same box)
-                                if constexpr (UNERF_RGB_SCALAR == 1 || (UNERF_RGB_SCALAR == 2 && MODE == UNERF_FIELD_ACTIVE)) {
-                                    acc2[c0g + c].x = __builtin_fmaf(dv[4 * q4], wv[c][q4].x, acc2[c0g + c].x);
-                                    acc2[c0g + c].y = __builtin_fmaf(dv[4 * q4 + 1], wv[c][q4].y, acc2[c0g + c].y);
-                                    acc2[c0g + c].x = __builtin_fmaf(dv[4 * q4 + 2], wv[c][q4].z, acc2[c0g + c].x);
-                                    acc2[c0g + c].y = __builtin_fmaf(dv[4 * q4 + 3], wv[c][q4].w, acc2[c0g + c].y);
-                                } else {
-                                    acc2[c0g + c] = __builtin_elementwise_fma(unerf_v2f{dv[4 * q4], dv[4 * q4 + 1]}, unerf_v2f{wv[c][q4].x, wv[c][q4].y}, acc2[c0g + c]);
-                                    acc2[c0g + c] = __builtin_elementwise_fma(unerf_v2f{dv[4 * q4 + 2], dv[4 * q4 + 3]}, unerf_v2f{wv[c][q4].z, wv[c][q4].w}, acc2[c0g + c]);
-                                }
-                            }
-                        }
-                    }
-                }
-#pragma unroll
-                for (int c = 0; c < 3; ++c) {
-                    const float half_sum = acc2[c].x + acc2[c].y;
-                    const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(half_sum), __float_as_uint(half_sum), false, false);
-                    o[c] = (__uint_as_float(sw[0]) + __uint_as_float(sw[1])) + lds[MF_H2_OFF + 192 + c];
-                }
-            }
-            }
-            // Epilogue split over the two lane halves (both hold the three colour sums after the exchange; the density
-            // logit, row 0, lives in the h = 0 half): h = 0 finishes (density, red), h = 1 (green, blue) -- two
-            // exponentials, two reciprocals and two stores per lane instead of four, four and four on half the lanes.
-            if (valid) {
-                const OutIndex q = out_index(a, k, ts);
-                const float x = h ? o[1] : o[0];
-                const float y = h ? -o[2] : t[0];                 // h = 1: exp(-blue) for its sigmoid; h = 0: exp(logit)
-                // F1 has no lo halves to turn an operand overflow into NaN: an activation beyond 65504 becomes an f16 inf,
-                // which reaches every unit of the next layer (inf w, or inf - inf = NaN) and from there the density logit
-                // (trunk units) or the three colour sums (head units) -- but sigmoid / exp map +-inf to 0, 1, inf: plausible
-                // pixels.  So the four PRE-activation values are tested here (two per lane): two compares per pass.
-                if (F1) f1_bad |= !(fabsf(x) < INFINITY) | !(fabsf(y) < INFINITY);
-                const float ey = __expf(y);
-                const float vy = h ? __builtin_amdgcn_rcpf(1.f + ey) : a.p.average_init_density * ey * sel;
-                const float vx = mf_sigmoid_fast(x);
-                if (a.p.packed_out) {   // uniform.  (vx, vy) = (red, sigma) in the h = 0 half, (green, blue) in the h = 1 half:
-                    // one v_permlane32_swap each brings the upper half's pair down, and the lower half stores 16 bytes
-                    // (a column's two lanes are the same sample: `valid` is the same in both)
-                    const auto gx = __builtin_amdgcn_permlane32_swap(__float_as_uint(vx), __float_as_uint(vx), false, false);
-                    const auto gy = __builtin_amdgcn_permlane32_swap(__float_as_uint(vy), __float_as_uint(vy), false, false);
-                    if (h == 0) store_packed(a, k, ts.n, vy, vx, __uint_as_float(gx[1]), __uint_as_float(gy[1]));
-                } else {
-                    a.rgb[q.rgb + (h ? q.rgb_stride : 0)] = vx;
-                    float* py = h ? a.rgb + (q.rgb + 2 * q.rgb_stride) : a.density + q.dens;
-                    *py = vy;
-                }
-                if (MODE == UNERF_FIELD_ACTIVE && h == 0) a.aux[q.aux] = unerf_softplus(t[8]) + a.p.beta_min;
-            }
-        }
-    }
-    if (a.p.overflow_flag) {   // one atomic per offending wave and launch
-        const uint64_t m = __builtin_amdgcn_ballot_w64(f1_bad);
-        if (m != 0 && lane_c == (int)__builtin_ctzll(m)) atomicOr(a.p.overflow_flag, 1);
-    }
-}
+#define UNERF_MFMA16_KERNEL field_kernel_mfma16
+#define UNERF_MFMA16_VIEWS false
+#include "unerf_field_mfma16.inc"
+#undef UNERF_MFMA16_KERNEL
+#undef UNERF_MFMA16_VIEWS
+// the same kernel under the name its several-views instantiations carry (MCDROPOUT, generated masks, default sites)
+#define UNERF_MFMA16_KERNEL views_kpass_kernel_mfma16
+#define UNERF_MFMA16_VIEWS true
+#include "unerf_field_mfma16.inc"
+#undef UNERF_MFMA16_KERNEL
+#undef UNERF_MFMA16_VIEWS
 
 // --------------------------------------------------------------------------------------
 // 5b'. LAPLACE on the matrix cores.  The reference evaluates the two sampled last layers in a
@@ -3767,6 +3546,51 @@ extern "C" int unerf_field_fwd_masked(const float* origins, const float* directi
                           aux, aux2, masks, stream);
 }
 
+// Several views in one launch.  Only MCDROPOUT with generated masks reads a per-view value (counter + seed): that mode runs
+// the FieldViews instantiations of field_kernel_mfma16; everything else this entry point accepts has none and goes through
+// field_launch() with ray_offset = 0 (the tile map then works on the tall image of all views).
+extern "C" int unerf_field_fwd_views(const float* origins, const float* directions, const float* sbins, int64_t R, int S,
+                                     float near_plane, float far_plane, int spacing, const unerf_ray_views* views,
+                                     const unerf_field_params* p, const float* features, float* density, float* rgb, float* aux,
+                                     float* aux2, const unerf_keep_masks* masks, void* stream) {
+    UNERF_REQUIRE(!masks, "field_fwd_views: explicit keep masks have no views form (unerf_field_fwd_masked renders one frame per call)");
+    UNERF_REQUIRE(p, "field_fwd_views: null params");
+    if (int rc = check_views(views, R, "field_fwd_views")) return rc;
+    UNERF_REQUIRE(p->mode == UNERF_FIELD_ACTIVE || p->mode == UNERF_FIELD_MCDROPOUT,
+                  "field_fwd_views: mode %d is not built for several views (ACTIVE / MCDROPOUT only; LAPLACE renders one frame per call)", p->mode);
+    UNERF_REQUIRE(p->mfma16_blob, "field_fwd_views: built for the f16 matrix kernels (mfma16_blob, precision f16x2 / f16); the exact-fp32 "
+                                  "and VALU kernels render one frame per call");
+    UNERF_REQUIRE(!features, "field_fwd_views: pre-gathered features are not built for several views");
+    UNERF_REQUIRE(!p->sample_major, "field_fwd_views: sample_major planes are not built for several views");
+    UNERF_REQUIRE(origins && directions && sbins && (density || p->packed_out) && rgb, "field_fwd_views: null pointer");
+    FieldArgs a;
+    a.origins = origins; a.dirs = directions; a.sbins = sbins; a.R = R; a.S = S; a.ray_offset = 0;
+    a.p = *p; a.density = density; a.rgb = rgb; a.aux = aux; a.aux2 = aux2; a.features = nullptr;
+    const bool generic = field_set_widths(a.p);
+    UNERF_REQUIRE(!generic, "field_fwd_views: the any-width kernel is not built for several views (nerfacto widths 64 / 64 / 15 / 2, L = 16)");
+    UNERF_REQUIRE(p->mode != UNERF_FIELD_MCDROPOUT || requested_drop_sites(a.p) == DROP_SITES_DEFAULT,
+                  "field_fwd_views: drop_sites=%d is not built for several views (TRUNK | HEAD1 only)", p->drop_sites);
+    if (int rc = field_check_args(a, near_plane, generic, nullptr)) return rc;
+    field_fill_args(a, near_plane, far_plane, spacing, nullptr);
+    if (int rc = field_check_nonempty(a, spacing, generic)) return rc;
+    if (a.p.mode == UNERF_FIELD_MCDROPOUT && a.drop_on) {
+        FieldViews fv;
+        fv.div_hw = make_fastdiv((uint32_t)views->rays_per_view);
+        fv.hw = (uint32_t)views->rays_per_view;
+        for (int v = 0; v < UNERF_NERF_MAX_VIEWS; ++v) fv.key[v] = unerf_mc_key(views->seed[v < views->n_views ? v : 0], 0u);
+        with_int3(tcnn_arg(a.p), [&](auto tc) {
+            with_bool(a.p.f16_single != 0, [&](auto f1) {
+                constexpr bool F1 = decltype(f1)::value;
+                launch_matrix_kernel(views_kpass_kernel_mfma16<UNERF_FIELD_MCDROPOUT, decltype(tc)::value, false, true, F1, FieldViews>,
+                                     mf16_lds_bytes(F1, true), a, (hipStream_t)stream, fv);
+            });
+        });
+    } else {
+        field_launch(a, generic, nullptr, (hipStream_t)stream);
+    }
+    return unerf_check_launch("field_fwd_views");
+}
+
 // --------------------------------------------------------------------------------------
 // 5c'. Keep-mask bit arrays (include/unerf.h: unerf_keep_masks).  One thread per output word.
 // --------------------------------------------------------------------------------------
@@ -4075,9 +3899,9 @@ __device__ __forceinline__ CompGeom<SPL> composite_geom(const CompArgs& a, int64
     return gm;
 }
 
-template <int SPL, bool RAGGED = false, bool PACKED = false>
+template <int SPL, bool RAGGED = false, bool PACKED = false, typename... VW>   // VW = ViewMap: clip rows numbered per view
 __device__ __forceinline__ void composite_one(const CompArgs& a, int64_t g, int64_t r, int l16, float (&o8)[8],
-                                              const CompGeom<SPL>& gm) {
+                                              const CompGeom<SPL>& gm, const VW&... vw) {
     const int S = a.S, k0 = l16 * SPL;
     float delta[SPL], steps[SPL], dens[SPL], w[SPL];
     struct Rgb { float r, g, b; };
@@ -4186,15 +4010,15 @@ __device__ __forceinline__ void composite_one(const CompArgs& a, int64_t g, int6
     dv = group_sum<16>(dv) + 1e-5f;
     float ed = wt / (acc + 1e-10f);
     if (a.clip) {
-        int64_t chunk = (a.ray_offset + r) / a.chunk_rays;
+        int64_t chunk = clip_chunk(a, r, vw...);
         ed = fminf(fmaxf(ed, a.clip[chunk * 2 + 0]), a.clip[chunk * 2 + 1]);
     }
     o8[0] = cr; o8[1] = cg; o8[2] = cb; o8[3] = acc;
     o8[4] = depth; o8[5] = ed; o8[6] = uvar; o8[7] = dv;
 }
 
-template <int SPL, bool RAGGED, bool PACKED>
-__device__ __forceinline__ void composite_kernel_body(const CompArgs& a) {
+template <int SPL, bool RAGGED, bool PACKED, typename... VW>
+__device__ __forceinline__ void composite_kernel_body(const CompArgs& a, const VW&... vw) {
     const int l16 = threadIdx.x & 15;
     int64_t g = (int64_t)blockIdx.x * 16 + (threadIdx.x >> 4);
     const int64_t G = (int64_t)a.B * a.R;
@@ -4202,7 +4026,7 @@ __device__ __forceinline__ void composite_kernel_body(const CompArgs& a) {
     if (!ok) g = G - 1;
     float o8[8];
     const int64_t r = g % a.R;
-    composite_one<SPL, RAGGED, PACKED>(a, g, r, l16, o8, composite_geom<SPL, RAGGED>(a, r, l16));
+    composite_one<SPL, RAGGED, PACKED>(a, g, r, l16, o8, composite_geom<SPL, RAGGED>(a, r, l16), vw...);
     if (ok && l16 == 0) {
         float4* o = reinterpret_cast<float4*>(a.out + g * 8);
         o[0] = make_float4(o8[0], o8[1], o8[2], o8[3]);
@@ -4217,14 +4041,23 @@ template <int SPL, bool RAGGED = false>
 __global__ __launch_bounds__(256) void composite_kernel_packed(CompArgs a) {
     composite_kernel_body<SPL, RAGGED, true>(a);
 }
+// unerf_composite_var_views
+template <int SPL, bool RAGGED = false>
+__global__ __launch_bounds__(256) void composite_kernel_views(CompArgs a, ViewMap vm) {
+    composite_kernel_body<SPL, RAGGED, false>(a, vm);
+}
+template <int SPL, bool RAGGED = false>
+__global__ __launch_bounds__(256) void composite_kernel_packed_views(CompArgs a, ViewMap vm) {
+    composite_kernel_body<SPL, RAGGED, true>(a, vm);
+}
 
 // K-pass form: one 16-lane group walks the B <= 16 passes of a ray, lane b keeps pass b's eight
 // outputs, and the per-pixel mean and unbiased variance over the passes (two-pass, like
 // torch.stack(...).mean(0) / .var(0), mcdropout_models.py:121-126) come out of two group reductions:
 // the [B,R,8] per-pass images never touch HBM.
-template <int SPL, bool RAGGED, bool PACKED>
+template <int SPL, bool RAGGED, bool PACKED, typename... VW>
 __device__ __forceinline__ void composite_moments_body(const CompArgs& a, float* __restrict__ mean_out,
-                                                       float* __restrict__ var_out) {
+                                                       float* __restrict__ var_out, const VW&... vw) {
     const int l16 = threadIdx.x & 15;
     int64_t r = (int64_t)blockIdx.x * 16 + (threadIdx.x >> 4);
     const bool ok = r < a.R;
@@ -4235,7 +4068,7 @@ __device__ __forceinline__ void composite_moments_body(const CompArgs& a, float*
     const CompGeom<SPL> gm = composite_geom<SPL, RAGGED>(a, r, l16);   // bin edges are the same in every pass
     for (int b = 0; b < a.B; ++b) {
         float o8[8];
-        composite_one<SPL, RAGGED, PACKED>(a, (int64_t)b * a.R + r, r, l16, o8, gm);
+        composite_one<SPL, RAGGED, PACKED>(a, (int64_t)b * a.R + r, r, l16, o8, gm, vw...);
         if (l16 == b) {
 #pragma unroll
             for (int c = 0; c < 8; ++c) mine[c] = o8[c];
@@ -4267,6 +4100,17 @@ template <int SPL, bool RAGGED = false>
 __global__ __launch_bounds__(256) void composite_moments_kernel_packed(CompArgs a, float* __restrict__ mean_out,
                                                                        float* __restrict__ var_out) {
     composite_moments_body<SPL, RAGGED, true>(a, mean_out, var_out);
+}
+// unerf_composite_moments_views
+template <int SPL, bool RAGGED = false>
+__global__ __launch_bounds__(256) void composite_moments_kernel_views(CompArgs a, float* __restrict__ mean_out,
+                                                                      float* __restrict__ var_out, ViewMap vm) {
+    composite_moments_body<SPL, RAGGED, false>(a, mean_out, var_out, vm);
+}
+template <int SPL, bool RAGGED = false>
+__global__ __launch_bounds__(256) void composite_moments_kernel_packed_views(CompArgs a, float* __restrict__ mean_out,
+                                                                             float* __restrict__ var_out, ViewMap vm) {
+    composite_moments_body<SPL, RAGGED, true>(a, mean_out, var_out, vm);
 }
 
 // Samples per lane: S = 16 * SPL for SPL in {1,2,3,4,6,8,16} (every nerfacto sample count) takes the aligned
@@ -4300,10 +4144,12 @@ static inline int unerf_spl_for(int S) {
         }                                                                                                           \
     }
 
-extern "C" int unerf_composite_var(const float* density, const float* rgb, const float* beta, const float* weights_alt,
-                                   const float* sbins, int B, int64_t R, int S, float near_plane, float far_plane, int spacing,
-                                   const float* clip_minmax, int64_t ray_offset, int64_t chunk_rays, int background,
-                                   const float* background_rgb, int32_t* nonfinite_flag, float* out, void* stream) {
+// views = NULL: unerf_composite_var
+static int composite_var_impl(const float* density, const float* rgb, const float* beta, const float* weights_alt,
+                              const float* sbins, int B, int64_t R, int S, float near_plane, float far_plane, int spacing,
+                              const float* clip_minmax, int64_t ray_offset, int64_t chunk_rays, int background,
+                              const float* background_rgb, int32_t* nonfinite_flag, float* out, const unerf_ray_views* views,
+                              void* stream) {
     UNERF_REQUIRE(R == 0 || (rgb && sbins && out), "composite_var: null pointer");   // density NULL: rgb holds packed rows
     UNERF_REQUIRE(B >= 1 && R >= 0, "composite_var: bad B/R");
     UNERF_REQUIRE(S >= 1 && S <= 256, "composite_var: S=%d outside [1,256]", S);
@@ -4317,6 +4163,15 @@ extern "C" int unerf_composite_var(const float* density, const float* rgb, const
     a.flag = nonfinite_flag;
     dim3 grid(blocks_for((int64_t)B * R, 16)), block(256);
     hipStream_t st = (hipStream_t)stream;
+    if (views && clip_minmax) {   // (without a clip buffer nothing in the kernel is numbered by the frame)
+        const ViewMap vm = make_view_map(views, chunk_rays);
+        if (density) {
+            UNERF_DISPATCH_SPL(S, composite_kernel_views, grid, block, 0, st, a, vm);
+        } else {
+            UNERF_DISPATCH_SPL(S, composite_kernel_packed_views, grid, block, 0, st, a, vm);
+        }
+        return unerf_check_launch("composite_var_views");
+    }
     if (density) {
         UNERF_DISPATCH_SPL(S, composite_kernel, grid, block, 0, st, a);
     } else {
@@ -4325,10 +4180,30 @@ extern "C" int unerf_composite_var(const float* density, const float* rgb, const
     return unerf_check_launch("composite_var");
 }
 
-extern "C" int unerf_composite_moments(const float* density, const float* rgb, const float* sbins, int B, int64_t R, int S,
-                                       float near_plane, float far_plane, int spacing, const float* clip_minmax, int64_t ray_offset,
-                                       int64_t chunk_rays, int background, const float* background_rgb,
-                                       int32_t* nonfinite_flag, float* mean_out, float* var_out, void* stream) {
+extern "C" int unerf_composite_var(const float* density, const float* rgb, const float* beta, const float* weights_alt,
+                                   const float* sbins, int B, int64_t R, int S, float near_plane, float far_plane, int spacing,
+                                   const float* clip_minmax, int64_t ray_offset, int64_t chunk_rays, int background,
+                                   const float* background_rgb, int32_t* nonfinite_flag, float* out, void* stream) {
+    return composite_var_impl(density, rgb, beta, weights_alt, sbins, B, R, S, near_plane, far_plane, spacing, clip_minmax,
+                              ray_offset, chunk_rays, background, background_rgb, nonfinite_flag, out, nullptr, stream);
+}
+
+extern "C" int unerf_composite_var_views(const float* density, const float* rgb, const float* beta, const float* weights_alt,
+                                         const float* sbins, int B, int64_t R, int S, float near_plane, float far_plane,
+                                         int spacing, const float* clip_minmax, const unerf_ray_views* views, int64_t chunk_rays,
+                                         int background, const float* background_rgb, int32_t* nonfinite_flag, float* out,
+                                         void* stream) {
+    if (int rc = check_views(views, R, "composite_var_views")) return rc;
+    return composite_var_impl(density, rgb, beta, weights_alt, sbins, B, R, S, near_plane, far_plane, spacing, clip_minmax, 0,
+                              chunk_rays, background, background_rgb, nonfinite_flag, out, views, stream);
+}
+
+// views = NULL: unerf_composite_moments
+static int composite_moments_impl(const float* density, const float* rgb, const float* sbins, int B, int64_t R, int S,
+                                  float near_plane, float far_plane, int spacing, const float* clip_minmax, int64_t ray_offset,
+                                  int64_t chunk_rays, int background, const float* background_rgb,
+                                  int32_t* nonfinite_flag, float* mean_out, float* var_out, const unerf_ray_views* views,
+                                  void* stream) {
     UNERF_REQUIRE(R == 0 || (rgb && sbins && mean_out && var_out), "composite_moments: null pointer");   // density NULL: packed rows
     UNERF_REQUIRE(B >= 1 && B <= 16 && R >= 0, "composite_moments: B=%d outside [1,16] (use composite_var + moments)", B);
     UNERF_REQUIRE(S >= 1 && S <= 256, "composite_moments: S=%d outside [1,256]", S);
@@ -4342,12 +4217,39 @@ extern "C" int unerf_composite_moments(const float* density, const float* rgb, c
     a.flag = nonfinite_flag;
     dim3 grid(blocks_for(R, 16)), block(256);
     hipStream_t st = (hipStream_t)stream;
+    if (views && clip_minmax) {
+        const ViewMap vm = make_view_map(views, chunk_rays);
+        if (density) {
+            UNERF_DISPATCH_SPL(S, composite_moments_kernel_views, grid, block, 0, st, a, mean_out, var_out, vm);
+        } else {
+            UNERF_DISPATCH_SPL(S, composite_moments_kernel_packed_views, grid, block, 0, st, a, mean_out, var_out, vm);
+        }
+        return unerf_check_launch("composite_moments_views");
+    }
     if (density) {
         UNERF_DISPATCH_SPL(S, composite_moments_kernel, grid, block, 0, st, a, mean_out, var_out);
     } else {
         UNERF_DISPATCH_SPL(S, composite_moments_kernel_packed, grid, block, 0, st, a, mean_out, var_out);
     }
     return unerf_check_launch("composite_moments");
+}
+
+extern "C" int unerf_composite_moments(const float* density, const float* rgb, const float* sbins, int B, int64_t R, int S,
+                                       float near_plane, float far_plane, int spacing, const float* clip_minmax, int64_t ray_offset,
+                                       int64_t chunk_rays, int background, const float* background_rgb,
+                                       int32_t* nonfinite_flag, float* mean_out, float* var_out, void* stream) {
+    return composite_moments_impl(density, rgb, sbins, B, R, S, near_plane, far_plane, spacing, clip_minmax, ray_offset, chunk_rays,
+                                  background, background_rgb, nonfinite_flag, mean_out, var_out, nullptr, stream);
+}
+
+extern "C" int unerf_composite_moments_views(const float* density, const float* rgb, const float* sbins, int B, int64_t R, int S,
+                                             float near_plane, float far_plane, int spacing, const float* clip_minmax,
+                                             const unerf_ray_views* views, int64_t chunk_rays, int background,
+                                             const float* background_rgb, int32_t* nonfinite_flag, float* mean_out,
+                                             float* var_out, void* stream) {
+    if (int rc = check_views(views, R, "composite_moments_views")) return rc;
+    return composite_moments_impl(density, rgb, sbins, B, R, S, near_plane, far_plane, spacing, clip_minmax, 0, chunk_rays,
+                                  background, background_rgb, nonfinite_flag, mean_out, var_out, views, stream);
 }
 
 // ---- composite over sample-major planes: one lane per ray, front to back --------------------------------------

@@ -153,21 +153,66 @@ def depth_metrics_unc(outputs: Dict[str, torch.Tensor], depth_gt, scale: float, 
     return md, curves
 
 
+def _camera_size(camera) -> Tuple[int, int]:
+    one = lambda v: int(v.reshape(-1)[0].item()) if torch.is_tensor(v) else int(v)
+    return one(camera.height), one(camera.width)
+
+
+def stack_cameras(cameras: List[object]):
+    """single eval cameras of one image size -> the batch object the models' get_outputs_for_cameras take
+    (camera_to_worlds [B,3,4]; fx, fy, cx, cy one per camera; camera_type / distortion_params where any camera has them)"""
+    from types import SimpleNamespace
+    one = lambda v: float(v.reshape(-1)[0].item()) if torch.is_tensor(v) else float(v)
+    c2ws = []
+    for cam in cameras:
+        c2w = torch.as_tensor(cam.camera_to_worlds)
+        c2ws.append((c2w[0] if c2w.dim() == 3 else c2w)[:3, :4])
+    H, W = _camera_size(cameras[0])
+    batch = SimpleNamespace(camera_to_worlds=torch.stack(c2ws), height=H, width=W,
+                            **{k: torch.tensor([one(getattr(cam, k)) for cam in cameras], dtype=torch.float64)
+                               for k in ("fx", "fy", "cx", "cy")})
+    if any(getattr(cam, "camera_type", None) is not None for cam in cameras):
+        def ctype(cam):
+            t = getattr(cam, "camera_type", None)
+            if t is None:
+                return 1        # CameraType.PERSPECTIVE
+            return int(torch.as_tensor(t).reshape(-1)[0]) if torch.is_tensor(t) else int(getattr(t, "value", t))
+        batch.camera_type = torch.tensor([ctype(cam) for cam in cameras])
+    if any(getattr(cam, "distortion_params", None) is not None for cam in cameras):
+        rows = [getattr(cam, "distortion_params", None) for cam in cameras]
+        batch.distortion_params = torch.stack([torch.zeros(6) if r is None else
+                                               torch.as_tensor(r).detach().cpu().to(torch.float32).reshape(6) for r in rows])
+    return batch
+
+
 def get_average_uncertainty_metrics(get_outputs_for_camera: Callable, eval_set: Iterable[Tuple[object, torch.Tensor]],
                                     eval_rgb_unc: bool = True, min_rgb_std_for_nll: float = 3e-2,
                                     composite_gt: Optional[Callable] = None, depth_gt_fn: Optional[Callable] = None,
-                                    min_depth_std_for_nll: float = 1.0, fused: bool = False):
+                                    min_depth_std_for_nll: float = 1.0, fused: bool = False, view_batch: int = 1,
+                                    get_outputs_for_cameras: Optional[Callable] = None):
     """eval_uncertainty.py:816-1079.  -> (averaged metrics dict, averaged curves dict).
     depth_gt_fn(image_index) -> (depth_gt [H,W], scale) switches the depth metrics on (eval_depth_unc).
-    fused: the per-image metric stage through the HIP kernels (image_metrics_unc / depth_metrics_unc, fused=True)."""
+    fused: the per-image metric stage through the HIP kernels (image_metrics_unc / depth_metrics_unc, fused=True).
+    view_batch > 1: that many CONSECUTIVE eval cameras of one image size are rendered by one call of the model's
+    get_outputs_for_cameras (`get_outputs_for_cameras=`, else the method of that name on the object
+    get_outputs_for_camera is bound to) -- NeRF and splat models alike; a change of image size starts a new batch.  Same
+    metric keys; a batch's render time is shared equally between its images for the three timing keys.  The default (1) is
+    the reference's per-camera loop."""
+    if view_batch < 1:
+        raise ValueError(f"view_batch={view_batch}: at least 1")
+    if view_batch > 1 and get_outputs_for_cameras is None:
+        get_outputs_for_cameras = getattr(getattr(get_outputs_for_camera, "__self__", None), "get_outputs_for_cameras", None)
+        if get_outputs_for_cameras is None:
+            raise ValueError("view_batch > 1 needs the model's get_outputs_for_cameras (pass get_outputs_for_cameras=)")
     rows: List[Dict[str, float]] = []
     sums: Dict[str, np.ndarray] = {}
-    for img_num, (camera, gt) in enumerate(eval_set):
-        inner_start = time.time()
-        outputs = get_outputs_for_camera(camera)
+
+    def sync():
         if torch.cuda.is_available():
             torch.cuda.synchronize()
-        render_s = time.time() - inner_start
+
+    def score(img_num, outputs, gt, render_s):
+        start = time.time()
         H, W = outputs["rgb"].shape[:2]
         md, curves = image_metrics_unc(outputs, gt, eval_rgb_unc, min_rgb_std_for_nll, composite_gt, fused=fused)
         if depth_gt_fn is not None:
@@ -175,12 +220,36 @@ def get_average_uncertainty_metrics(get_outputs_for_camera: Callable, eval_set: 
             dmd, dcurves = depth_metrics_unc(outputs, dgt, scale, min_depth_std_for_nll, fused=fused)
             md.update(dmd)
             curves.update(dcurves)
-        md["num_rays_per_sec"] = H * W / (time.time() - inner_start)
+        md["num_rays_per_sec"] = H * W / (render_s + time.time() - start)
         md["fps"] = md["num_rays_per_sec"] / (H * W)
         md["render_rays_per_sec"] = H * W / render_s
         rows.append(md)
         for k, v in curves.items():
             sums[k] = sums.get(k, 0) + np.asarray(v, dtype=np.float64)
+
+    def flush(pending):     # [(image index, camera, gt)] of one image size
+        if not pending:
+            return
+        start = time.time()
+        outs = get_outputs_for_cameras(stack_cameras([cam for _, cam, _ in pending]))
+        sync()
+        share = (time.time() - start) / len(pending)
+        for (img_num, _, gt), outputs in zip(pending, outs):
+            score(img_num, outputs, gt, share)
+
+    pending: List[Tuple[int, object, torch.Tensor]] = []
+    for img_num, (camera, gt) in enumerate(eval_set):
+        if view_batch == 1:
+            start = time.time()
+            outputs = get_outputs_for_camera(camera)
+            sync()
+            score(img_num, outputs, gt, time.time() - start)
+            continue
+        if pending and (len(pending) == view_batch or _camera_size(pending[0][1]) != _camera_size(camera)):
+            flush(pending)
+            pending = []
+        pending.append((img_num, camera, gt))
+    flush(pending)
     avg = {k: float(torch.mean(torch.tensor([r[k] for r in rows], dtype=torch.float64))) for k in rows[0]}
     return avg, {k: v / len(rows) for k, v in sums.items()}
 
@@ -282,11 +351,17 @@ def outputs_fn_for(eval_config: EvalConfigs, model, ggn_batches=None, pipeline=N
 
 def run_eval(eval_config: EvalConfigs, model, eval_set, experiment_name: str = "", method_name: str = "",
              checkpoint: str = "", depth_gt_fn: Optional[Callable] = None, composite_gt: Optional[Callable] = None,
-             fused: bool = False, **fn_kw) -> Dict[str, float]:
+             fused: bool = False, view_batch: int = 1, **fn_kw) -> Dict[str, float]:
     """main() of scripts/eval_uncertainty.py:1082-1169 without nerfstudio's pipeline loading: pick the method's
     callable, average the per-image metrics, write the metrics.json envelope to eval_config.output_path.
-    fused=True computes the per-image metrics with the HIP kernels behind ops.image_metrics (same keys; opt-in)."""
+    fused=True computes the per-image metrics with the HIP kernels behind ops.image_metrics (same keys; opt-in).
+    view_batch > 1 (MCDropoutConfig, ActiveNerfactoConfig, ActiveSplatfactoConfig): that many consecutive eval cameras of
+    one size per model.get_outputs_for_cameras call (get_average_uncertainty_metrics); the Laplace and ensemble callables
+    render one camera per call whatever it is."""
     fn = outputs_fn_for(eval_config, model, **fn_kw)
+    batch_fn = None
+    if view_batch > 1 and not isinstance(eval_config, (LaplaceConfig, EnsembleConfig)):
+        batch_fn = getattr(model, "get_outputs_for_cameras", None)
     if composite_gt is None and hasattr(model, "composite_gt"):   # splat models: GT alpha over the background
         composite_gt = model.composite_gt
     if eval_config.eval_depth and depth_gt_fn is None and eval_config.dataset_path is not None:
@@ -294,6 +369,7 @@ def run_eval(eval_config: EvalConfigs, model, eval_set, experiment_name: str = "
     metrics, _curves = get_average_uncertainty_metrics(
         fn, eval_set, eval_rgb_unc=eval_config.eval_rgb, min_rgb_std_for_nll=eval_config.min_rgb_std_for_nll,
         composite_gt=composite_gt, depth_gt_fn=depth_gt_fn if eval_config.eval_depth else None,
-        min_depth_std_for_nll=eval_config.min_depth_std_for_nll, fused=fused)
+        min_depth_std_for_nll=eval_config.min_depth_std_for_nll, fused=fused,
+        view_batch=view_batch if batch_fn is not None else 1, get_outputs_for_cameras=batch_fn)
     write_metrics_json(str(eval_config.output_path), experiment_name, method_name, checkpoint, metrics)
     return metrics

@@ -17,6 +17,8 @@ INCLUDE = os.path.join(os.path.dirname(_HERE), "include")
 # UNERF_LIB: another build of the same ABI, for A/B timing on one box (benchmarks/ab_bench.sh); unset in normal use
 LIB_PATH = os.environ.get("UNERF_LIB") or os.path.join(CSRC, "libunerf.so")
 SOURCES = ["unerf_nerf.hip", "unerf_splat.hip", "unerf_metrics.hip"]
+# text included by the sources (unerf_nerf.hip compiles the f16 matrix field kernel from unerf_field_mfma16.inc under two names)
+INCLUDED = ["unerf_common.hpp", "unerf_field_mfma16.inc"]
 # -amdgpu-mfma-vgpr-form: gfx950 has one unified register file; let the MFMAs write their accumulators to
 # ordinary VGPRs so ReLU / dropout / the next layer's B operand read them without v_accvgpr_read copies
 # (97 copies per tile in the K-pass kernel, which is VALU-issue-bound; rocprof r1_04).
@@ -40,8 +42,7 @@ class UnerfError(RuntimeError):
 def _source_digest() -> str:
     import hashlib
     h = hashlib.sha256(" ".join(HIPCC_FLAGS).encode())
-    for f in [os.path.join(CSRC, s) for s in SOURCES] + [os.path.join(CSRC, "unerf_common.hpp"),
-                                                          os.path.join(INCLUDE, "unerf.h")]:
+    for f in [os.path.join(CSRC, s) for s in SOURCES + INCLUDED] + [os.path.join(INCLUDE, "unerf.h")]:
         with open(f, "rb") as fh:
             h.update(fh.read())
     return h.hexdigest()
@@ -145,6 +146,20 @@ class KeepMasks(C.Structure):
     _fields_ = [("site", C.c_void_p * 4), ("pass_stride", C.c_int64), ("sample_offset", C.c_int64)]
 
 
+NERF_MAX_VIEWS = 16                               # include/unerf.h: UNERF_NERF_MAX_VIEWS
+
+
+class RayViews(C.Structure):
+    """include/unerf.h: unerf_ray_views (several whole views of one image size in one launch)"""
+    _fields_ = [("n_views", C.c_int32), ("rays_per_view", C.c_int64), ("seed", C.c_uint32 * NERF_MAX_VIEWS)]
+
+
+class RayCamera(C.Structure):
+    """include/unerf.h: unerf_ray_camera (one camera of unerf_generate_rays_views)"""
+    _fields_ = [("c2w", C.c_float * 12), ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float),
+                ("distortion", C.c_float * 6)]
+
+
 ABI_VERSION = 1420                                # include/unerf.h: UNERF_ABI_VERSION (struct layouts / argument lists)
 FIELD_ACTIVE, FIELD_MCDROPOUT, FIELD_LAPLACE = 0, 1, 2
 SPACING_PIECEWISE, SPACING_UNIFORM = 0, 1         # include/unerf.h: UNERF_SPACING_*
@@ -190,6 +205,15 @@ SIGNATURES = {
     "unerf_composite_var_planes": (_i, [_vp, _vp, _vp, _vp, _i, _i64, _i, _f, _f, _i, _vp, _i64, _i64, _i, _fp, _vp, _vp, _vp]),
     "unerf_composite_moments_planes": (_i, [_vp, _vp, _vp, _i, _i64, _i, _f, _f, _i, _vp, _i64, _i64, _i, _fp, _vp, _vp,
                                             _vp, _vp]),
+    "unerf_generate_rays_views": (_i, [C.POINTER(RayCamera), _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "unerf_weights_pdf_resample_views": (_i, [_vp, _vp, _i64, _i64, _i, _f, _f, _i, _vp, _i, _f, _f, _vp, _vp, _vp, _vp,
+                                              C.POINTER(RayViews), _i64, _vp]),
+    "unerf_composite_var_views": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i64, _i, _f, _f, _i, _vp, C.POINTER(RayViews), _i64, _i, _fp,
+                                       _vp, _vp, _vp]),
+    "unerf_composite_moments_views": (_i, [_vp, _vp, _vp, _i, _i64, _i, _f, _f, _i, _vp, C.POINTER(RayViews), _i64, _i, _fp, _vp,
+                                           _vp, _vp, _vp]),
+    "unerf_field_fwd_views": (_i, [_vp, _vp, _vp, _i64, _i, _f, _f, _i, C.POINTER(RayViews), C.POINTER(FieldParams), _vp, _vp, _vp,
+                                   _vp, _vp, C.POINTER(KeepMasks), _vp]),
     "unerf_moments": (_i, [_vp, _i, _i64, _i, _vp, _vp, _vp]),
     "unerf_image_metrics_workspace_bytes": (C.c_size_t, [_i64]),
     "unerf_image_metrics": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i, _i, _f, _f, C.POINTER(C.c_double), _i, C.POINTER(C.c_double), _i,

@@ -78,6 +78,40 @@ def _camera_args(camera, lens: bool = True) -> Tuple[torch.Tensor, Dict[str, Any
     return c2w[:3, :4], args
 
 
+def _camera_batch(cameras) -> Tuple[torch.Tensor, int, int, List[Any]]:
+    """A batch of cameras of ONE image size (get_outputs_for_cameras: camera_to_worlds [B,3|4,4]; fx, fy, cx, cy,
+    camera_type, distortion_params one value or one per camera) -> (c2w [B,3,4], H, W, one single-camera object per view
+    that _camera_args reads like a nerfstudio camera)."""
+    from types import SimpleNamespace
+    c2w = torch.as_tensor(cameras.camera_to_worlds)
+    c2w = c2w[None] if c2w.dim() == 2 else c2w
+    B = c2w.shape[0]
+    per = lambda v: torch.as_tensor(v).detach().cpu().reshape(-1).expand(B)
+    sizes = {(int(h), int(w)) for h, w in zip(per(cameras.height).tolist(), per(cameras.width).tolist())}
+    if len(sizes) != 1:
+        raise ValueError(f"get_outputs_for_cameras renders one image size per batch, got {sorted(sizes)} (H, W)")
+    (H, W), = sizes
+    intr = {k: per(getattr(cameras, k)) for k in ("fx", "fy", "cx", "cy")}
+    ctype = getattr(cameras, "camera_type", None)
+    if ctype is not None:
+        ctype = per(ctype) if torch.is_tensor(ctype) else per(int(getattr(ctype, "value", ctype)))
+    dist = getattr(cameras, "distortion_params", None)
+    if dist is not None:
+        dist = torch.as_tensor(dist).detach().cpu().to(torch.float32)
+        if dist.numel() not in (6, 6 * B):
+            raise ValueError(f"distortion_params: expected 6 values (k1, k2, k3, k4, p1, p2) or one row of 6 per camera, got {tuple(dist.shape)}")
+        dist = dist.reshape(-1, 6).expand(B, 6)
+    singles = []
+    for v in range(B):
+        cam = SimpleNamespace(camera_to_worlds=c2w[v, :3, :4], height=H, width=W, **{k: intr[k][v] for k in intr})
+        if ctype is not None:
+            cam.camera_type = ctype[v]
+        if dist is not None:
+            cam.distortion_params = dist[v]
+        singles.append(cam)
+    return c2w[:, :3, :4], H, W, singles
+
+
 # ------------------------------------------------------------------ configs ----------------
 
 @dataclass
@@ -428,6 +462,34 @@ class _NerfactoBase(nn.Module, _ImageMetrics):
         return render.render_camera(scene, c2w, rays_per_launch=self.rays_per_launch, obb=obb,
                                     **cam, **self._render_kwargs())
 
+    def _begin_render_views(self, scene: NerfSceneDev, n_views: int) -> Tuple[bool, Optional[List[int]]]:
+        """once per get_outputs_for_cameras call -> (render the batch through render.render_cameras, mask seed per view |
+        None); False: the model renders its cameras one by one through get_outputs_for_camera"""
+        return True, None
+
+    @torch.no_grad()
+    def get_outputs_for_cameras(self, cameras, obb_box=None, max_views: int = 16) -> List[Dict[str, torch.Tensor]]:
+        """get_outputs_for_camera for every camera of a batch, with the argument conventions of
+        SplatfactoModel.get_outputs_for_cameras: camera_to_worlds [B,3,4]; fx, fy, cx, cy, distortion_params (and
+        camera_type) one value or one per camera; one image size, anything else raises ValueError.  Element v equals
+        get_outputs_for_camera(camera v, obb_box) bit for bit, and the model is left as after B such calls.  Up to
+        max_views (<= lib.NERF_MAX_VIEWS) small frames share one launch group (render.render_cameras, which also says when
+        the batch is rendered camera by camera instead, with the same results)."""
+        if not 1 <= max_views <= _lib.NERF_MAX_VIEWS:
+            raise ValueError(f"max_views={max_views}: a launch group holds 1 to {_lib.NERF_MAX_VIEWS} cameras")
+        c2w, H, W, singles = _camera_batch(cameras)
+        args = [_camera_args(cam)[1] for cam in singles]              # validates every camera as get_outputs_for_camera does
+        scene = self.device_scene()
+        batched, seeds = self._begin_render_views(scene, len(singles))
+        if not batched:
+            return [self.get_outputs_for_camera(cam, obb_box) for cam in singles]
+        obb = None if obb_box is None else (ops.world_to_box(obb_box.R, obb_box.T), torch.as_tensor(obb_box.S).detach().cpu())
+        return render.render_cameras(scene, c2w, [a["fx"] for a in args], [a["fy"] for a in args], [a["cx"] for a in args],
+                                     [a["cy"] for a in args], H, W, seeds=seeds, rays_per_launch=self.rays_per_launch, obb=obb,
+                                     distortion=[a.get("distortion") for a in args],
+                                     camera_type=[a.get("camera_type", _lib.CAMERA_PERSPECTIVE) for a in args],
+                                     max_views=max_views, **self._render_kwargs())
+
     @torch.no_grad()
     def get_outputs_for_camera_ray_bundle(self, camera_ray_bundle, directions: Optional[torch.Tensor] = None):
         """Model.get_outputs_for_camera_ray_bundle(camera_ray_bundle: RayBundle) (mcdropout_models.py:94-96): any object
@@ -612,6 +674,18 @@ class NerfactoMCDropoutModel(_NerfactoBase):
         scene.field.seed = frame_seed(self.seed, self.frame_counter if self.fresh_masks_per_render else 0)
         self.frame_counter += 1
 
+    def _begin_render_views(self, scene: NerfSceneDev, n_views: int) -> Tuple[bool, Optional[List[int]]]:
+        """view v of the batch is frame frame_counter + v: the seeds B successive _begin_render calls would set.
+        dropout_masks="torch": the frames' masks are drawn one frame at a time, so the cameras are too."""
+        if self.dropout_masks not in ("counter", "torch"):
+            raise ValueError(f"dropout_masks={self.dropout_masks!r}: expected 'counter' or 'torch'")
+        if self.dropout_masks == "torch" and scene.field.K > 0 and scene.field.p_drop > 0.0:
+            return False, None
+        self._frame_masks = None
+        seeds = [frame_seed(self.seed, (self.frame_counter + v) if self.fresh_masks_per_render else 0) for v in range(n_views)]
+        self.frame_counter += n_views
+        return True, seeds
+
     def _draw_frame_masks(self, scene: NerfSceneDev, total_rays: int, chunk_rays: int) -> ops.KeepMasks:
         f, S = scene.field, scene.num_nerf
         if f.any_width:
@@ -679,6 +753,9 @@ class NerfactoLaplaceModel(_NerfactoBase):
             self._ws, self._deterministic_density = None, False     # leave the previous camera's sampled heads behind
             self.invalidate()
         return super().get_outputs_for_camera(camera, obb_box)
+
+    def _begin_render_views(self, scene: NerfSceneDev, n_views: int) -> Tuple[bool, Optional[List[int]]]:
+        return False, None      # the Laplace kernels take one frame per call (per-chunk sample sets): camera by camera
 
     @torch.no_grad()
     def get_outputs_for_camera_unc(self, camera, obb_box=None, is_inference: bool = True,

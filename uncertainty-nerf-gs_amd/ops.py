@@ -815,6 +815,59 @@ def pack_laplace_sets(ws_density: torch.Tensor, ws_rgb: torch.Tensor, device, ex
     return blob, torch.cat([head, B[:, :, brow].reshape(T, -1)], dim=1).contiguous()
 
 
+# ------------------------------------------------------- several views per launch -------
+
+@dataclass
+class RayViews:
+    """Several whole views of one image size in one launch (include/unerf.h: unerf_ray_views): the R = n_views *
+    rays_per_view rays of a call are view 0's H*W rays, then view 1's, ...  weights_pdf_resample / field_fwd /
+    composite_var / composite_moments (views=...) then number the clip rows, and the MC-dropout mask counter, inside each
+    view's own frame; `seeds`: the mask seed of each view (MCDROPOUT; None = the field's seed for every view)."""
+    n_views: int
+    rays_per_view: int
+    seeds: Optional[Tuple[int, ...]] = None
+
+    def cstruct(self, default_seed: int = 0) -> _l.RayViews:
+        cs = _l.RayViews()
+        cs.n_views, cs.rays_per_view = int(self.n_views), int(self.rays_per_view)
+        seeds = self.seeds if self.seeds is not None else (default_seed,) * max(int(self.n_views), 0)
+        if len(seeds) > _l.NERF_MAX_VIEWS or (self.seeds is not None and len(seeds) != self.n_views):
+            raise _l.UnerfError(f"RayViews: {len(seeds)} seeds for {self.n_views} views (at most {_l.NERF_MAX_VIEWS})")
+        for i, sd in enumerate(seeds):
+            cs.seed[i] = int(sd) & 0xFFFFFFFF
+        return cs
+
+
+def clip_rows_per_view(rays_per_view: int, chunk_rays: int) -> int:
+    """rows of the clip buffer each view owns: view v's chunk c is row v * clip_rows_per_view + c"""
+    return (int(rays_per_view) + int(chunk_rays) - 1) // int(chunk_rays)
+
+
+def generate_rays_views(c2ws: torch.Tensor, fx, fy, cx, cy, H: int, W: int, device, distortions=None,
+                        camera_type: int = _l.CAMERA_PERSPECTIVE):
+    """The rays of B whole frames of one size and camera type in one launch: c2ws [B,3|4,4]; fx, fy, cx, cy: B values
+    each; distortions: None or B entries (None | 6 lens parameters).  -> origins [B*H*W,3], directions [B*H*W,3]; view
+    v's rows are generate_rays(c2ws[v], ...) bit for bit."""
+    lib = _l.load()
+    B = int(c2ws.shape[0])
+    if not 1 <= B <= _l.NERF_MAX_VIEWS:
+        raise _l.UnerfError(f"generate_rays_views: {B} views (1 to {_l.NERF_MAX_VIEWS})")
+    cams = (_l.RayCamera * B)()
+    host = c2ws.detach().cpu().to(torch.float32)
+    for v in range(B):
+        cams[v].c2w[:] = [float(x) for x in host[v].reshape(-1)[:12]]
+        cams[v].fx, cams[v].fy, cams[v].cx, cams[v].cy = float(fx[v]), float(fy[v]), float(cx[v]), float(cy[v])
+        dist = None if distortions is None else _host_distortion(distortions[v])
+        cams[v].distortion[:] = [0.0] * 6 if dist is None else list(dist)
+    n = B * H * W
+    o = torch.empty(n, 3, device=device, dtype=torch.float32)
+    d = torch.empty(n, 3, device=device, dtype=torch.float32)
+    with _ctx(o.device):
+        _run("generate_rays_views", lambda: lib.unerf_generate_rays_views(cams, B, int(camera_type), H, W, _p(o), _p(d), None,
+                                                                          _stream()))
+    return o, d
+
+
 # ------------------------------------------------------- frame-path scratch -------------
 
 class Workspace:
@@ -894,8 +947,10 @@ def proposal_density(origins, directions, sbins, net: DensityNetDev, near: float
 def weights_pdf_resample(density, sbins, u, near: float, far: float, histogram_padding: float = 0.01,
                          eps: float = 1e-5, want_prop_depth: bool = True, want_weights: bool = False,
                          clip_minmax: Optional[torch.Tensor] = None, ray_offset: int = 0, chunk_rays: int = 1 << 15,
-                         spacing: int = 0, workspace: Optional[Workspace] = None):
-    """-> (new sbins [R,m+1], prop_depth [R,1] | None, weights [R,n] | None); workspace: the new bins are a view of it"""
+                         spacing: int = 0, workspace: Optional[Workspace] = None, views: Optional[RayViews] = None):
+    """-> (new sbins [R,m+1], prop_depth [R,1] | None, weights [R,n] | None); workspace: the new bins are a view of it
+    views: the rays are several whole views (RayViews); clip_minmax then holds clip_rows_per_view rows per view and
+    ray_offset is not read"""
     lib = _l.load()
     R, n = density.shape
     m = u.numel() - 1
@@ -903,6 +958,13 @@ def weights_pdf_resample(density, sbins, u, near: float, far: float, histogram_p
     out = _scratch(workspace, f"pdf_bins_{m}", (R, m + 1), density.device)
     pd = torch.empty(R, 1, device=density.device, dtype=torch.float32) if want_prop_depth else None
     w = torch.empty(R, n, device=density.device, dtype=torch.float32) if want_weights else None
+    if views is not None:
+        vs = views.cstruct()
+        with _ctx(density.device):
+            _run(f"weights_pdf_resample_{n}", lambda: lib.unerf_weights_pdf_resample_views(
+                _p(density), _p(sbins), stride, R, n, near, far, spacing, _p(u), m, histogram_padding, eps, _p(out), _p(pd), _p(w),
+                _p(clip_minmax), C.byref(vs), chunk_rays, _stream()))
+        return out, pd, w
     with _ctx(density.device):
         _run(f"weights_pdf_resample_{n}", lambda: lib.unerf_weights_pdf_resample(_p(density), _p(sbins), stride, R, n, near, far, spacing, _p(u), m,
                                                 histogram_padding, eps, _p(out), _p(pd), _p(w), _p(clip_minmax),
@@ -1027,7 +1089,8 @@ def mc_keep_bits(field: FieldDev, first_sample: int, n_samples: int, pass_stride
 def field_fwd(origins, directions, sbins, field: FieldDev, near: float, far: float, ray_offset: int = 0,
               features: Optional[torch.Tensor] = None, image_width: int = 0, euclidean_bins: bool = False,
               sample_major: bool = False, spacing: int = 0, nonfinite_flag: Optional[torch.Tensor] = None,
-              packed: bool = False, workspace: Optional[Workspace] = None, keep_masks: Optional[KeepMasks] = None):
+              packed: bool = False, workspace: Optional[Workspace] = None, keep_masks: Optional[KeepMasks] = None,
+              views: Optional[RayViews] = None):
     """-> density [B,R,S], rgb [B,R,S,3], aux, aux2 (see include/unerf.h).  image_width > 0 tells the kernel that
     rays [ray_offset, ray_offset+R) are consecutive pixels of a row-major image (8x4-pixel tiles: same results).
     euclidean_bins: `sbins` holds Euclidean bin edges (a caller-made RaySamples) instead of spacing-domain bins.
@@ -1036,7 +1099,9 @@ def field_fwd(origins, directions, sbins, field: FieldDev, near: float, far: flo
     per sample; composite_var / composite_moments take the rows as `rgb` with density=None.
     workspace: the four outputs are views of that scratch arena (valid until the next call with it).
     keep_masks (MCDROPOUT): explicit keep masks instead of the counter generator's (unerf_field_fwd_masked); the call
-    reads rows keep_masks.sample_offset + r * S + s, and ray_offset is then only the tile hint of image_width."""
+    reads rows keep_masks.sample_offset + r * S + s, and ray_offset is then only the tile hint of image_width.
+    views: the rays are several whole views (RayViews, unerf_field_fwd_views): the mask counter runs inside each view's
+    frame under views.seeds[v]; ray_offset is not read.  The f16 matrix kernels only -- anything else is refused."""
     if euclidean_bins:
         near = -1.0
     lib = _l.load()
@@ -1059,6 +1124,14 @@ def field_fwd(origins, directions, sbins, field: FieldDev, near: float, far: flo
     cs.sample_major = 1 if sample_major else 0
     cs.packed_out = 1 if packed else 0
     cs.overflow_flag = _p(nonfinite_flag, torch.int32)      # set by the f16 matrix kernels (either form) on operand overflow
+    if views is not None:
+        vs = views.cstruct(field.seed)
+        km = None if keep_masks is None else keep_masks.cstruct(B)     # (refused by the entry point, by name)
+        with _ctx(dev):
+            _run("field_fwd", lambda: lib.unerf_field_fwd_views(
+                _p(origins), _p(directions), _p(sbins), R, S, near, far, spacing, C.byref(vs), C.byref(cs), _p(features),
+                _p(density), _p(rgb), _p(aux), _p(aux2), None if km is None else C.byref(km), _stream()))
+        return density, rgb, aux, aux2
     if keep_masks is not None:
         km = keep_masks.cstruct(B)
         with _ctx(dev):
@@ -1148,7 +1221,7 @@ def _packed_shape(density, rgb):
 
 def composite_var(density, rgb, sbins, near: float, far: float, beta=None, weights_alt=None, clip_minmax=None,
                   ray_offset: int = 0, chunk_rays: int = 1 << 15, spacing: int = 0, background=None,
-                  nonfinite_flag: Optional[torch.Tensor] = None) -> torch.Tensor:
+                  nonfinite_flag: Optional[torch.Tensor] = None, views: Optional[RayViews] = None) -> torch.Tensor:
     """density [B,R,S] -> out [B,R,8] = rgb3, accumulation, depth, expected_depth, rgb_var, depth_var.
     density=None: `rgb` holds the packed rows [B,R,S,4] = (sigma, r, g, b) of field_fwd(packed=True).
     nonfinite_flag: int32 device tensor (1 element) that receives |= 1 when a NaN density / colour is read"""
@@ -1156,6 +1229,13 @@ def composite_var(density, rgb, sbins, near: float, far: float, beta=None, weigh
     B, R, S = _packed_shape(density, rgb)
     out = torch.empty(B, R, 8, device=rgb.device, dtype=torch.float32)
     bg_mode, bg_rgb = _background(background)
+    if views is not None:     # clip rows numbered per view, as weights_pdf_resample(views=...) filled them
+        vs = views.cstruct()
+        with _ctx(out.device):
+            _run("composite_var", lambda: lib.unerf_composite_var_views(
+                _p(density), _p(rgb), _p(beta), _p(weights_alt), _p(sbins), B, R, S, near, far, spacing, _p(clip_minmax),
+                C.byref(vs), chunk_rays, bg_mode, bg_rgb, _p(nonfinite_flag, torch.int32), _p(out), _stream()))
+        return out
     with _ctx(out.device):
         _run("composite_var", lambda: lib.unerf_composite_var(_p(density), _p(rgb), _p(beta), _p(weights_alt), _p(sbins), B, R, S, near,
                                          far, spacing, _p(clip_minmax), ray_offset, chunk_rays, bg_mode, bg_rgb,
@@ -1164,7 +1244,8 @@ def composite_var(density, rgb, sbins, near: float, far: float, beta=None, weigh
 
 
 def composite_moments(density, rgb, sbins, near: float, far: float, clip_minmax=None, ray_offset: int = 0,
-                      chunk_rays: int = 1 << 15, spacing: int = 0, background=None, nonfinite_flag=None):
+                      chunk_rays: int = 1 << 15, spacing: int = 0, background=None, nonfinite_flag=None,
+                      views: Optional[RayViews] = None):
     """density [B<=16,R,S], rgb [B,R,S,3] -> (mean [R,8], var [R,8]) over the B passes (fused composite + moments);
     density=None: `rgb` holds the packed rows [B,R,S,4] of field_fwd(packed=True)"""
     lib = _l.load()
@@ -1172,6 +1253,13 @@ def composite_moments(density, rgb, sbins, near: float, far: float, clip_minmax=
     mean = torch.empty(R, 8, device=rgb.device, dtype=torch.float32)
     var = torch.empty(R, 8, device=rgb.device, dtype=torch.float32)
     bg_mode, bg_rgb = _background(background)
+    if views is not None:
+        vs = views.cstruct()
+        with _ctx(mean.device):
+            _run("composite_moments", lambda: lib.unerf_composite_moments_views(
+                _p(density), _p(rgb), _p(sbins), B, R, S, near, far, spacing, _p(clip_minmax), C.byref(vs), chunk_rays, bg_mode,
+                bg_rgb, _p(nonfinite_flag, torch.int32), _p(mean), _p(var), _stream()))
+        return mean, var
     with _ctx(mean.device):
         _run("composite_moments", lambda: lib.unerf_composite_moments(_p(density), _p(rgb), _p(sbins), B, R, S, near, far,
                                                                       spacing, _p(clip_minmax), ray_offset, chunk_rays,

@@ -18,6 +18,7 @@ forward to the HIP-kernel mirrors of `models.py`:
     get_outputs(ray_bundle: RayBundle)                      one chunk of rays
     get_outputs_for_camera_ray_bundle(camera_ray_bundle)    [H,W] bundle (mcdropout_models.py:94-96)
     get_outputs_for_camera(camera, obb_box=None)            (eval_uncertainty.py:1097)
+    get_outputs_for_cameras(cameras, obb_box=None)          a batch of cameras of one size, several views per launch
     NerfactoLaplaceModel.get_outputs_for_camera_unc(...)    (laplace_model.py:403-415), compute_hessian_naive (:343)
     load_state_dict / get_param_groups / get_training_callbacks / get_metrics_dict / get_image_metrics_and_images
 
@@ -28,7 +29,7 @@ uses them).  The scope is inference: `get_loss_dict` raises -- training losses a
 """
 from __future__ import annotations
 
-from typing import Any, Dict, List, Tuple
+from typing import Any, Dict, List, Optional, Tuple
 
 import torch
 
@@ -165,6 +166,12 @@ def _build() -> Dict[str, Any]:
         @torch.no_grad()
         def get_outputs_for_camera(self, camera, obb_box=None):
             return self._mirror.get_outputs_for_camera(camera, obb_box=obb_box)
+
+        @torch.no_grad()
+        def get_outputs_for_cameras(self, cameras, obb_box=None, max_views: Optional[int] = None):
+            """a batch of cameras of one image size, several views per launch; element v = get_outputs_for_camera(camera v)"""
+            kw = {} if max_views is None else {"max_views": max_views}
+            return self._mirror.get_outputs_for_cameras(cameras, obb_box=obb_box, **kw)
 
         def load_state_dict(self, state_dict, strict: bool = False, **kw):  # type: ignore[override]
             return self._mirror.load_state_dict(state_dict, strict=strict, **kw)

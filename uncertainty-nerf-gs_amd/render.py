@@ -129,8 +129,10 @@ class OverflowGuard:
 
 def sample_rays(scene: NerfSceneDev, origins: torch.Tensor, directions: torch.Tensor, clip: Optional[torch.Tensor],
                 ray_offset: int = 0, want_prop_depth: bool = True, image_width: int = 0,
-                init_bins: Optional[torch.Tensor] = None, workspace: Optional[ops.Workspace] = None):
+                init_bins: Optional[torch.Tensor] = None, workspace: Optional[ops.Workspace] = None,
+                views: Optional[ops.RayViews] = None):
     """ProposalNetworkSampler at eval.  -> (final spacing bins [R,S+1], [prop_depth_0, prop_depth_1])
+    views: the rays are several whole views (render_cameras): `clip` holds each view's own chunk rows
     workspace (the frame path only): the bins are a view of that scratch arena, not a tensor of their own
     init_bins [R, num_prop[0]+1]: per-ray first-level bins (a bundle with its own nears / fars: `crop_bins`), else
     the shared uniform row"""
@@ -146,7 +148,8 @@ def sample_rays(scene: NerfSceneDev, origins: torch.Tensor, directions: torch.Te
         sb, pd, _ = ops.weights_pdf_resample(dens, sb, scene.const("u", m), scene.near, scene.far,
                                              want_prop_depth=want_prop_depth,
                                              clip_minmax=clip if last else None, ray_offset=ray_offset,
-                                             chunk_rays=scene.chunk_rays, spacing=scene.spacing, workspace=workspace)
+                                             chunk_rays=scene.chunk_rays, spacing=scene.spacing, workspace=workspace,
+                                             views=views if last else None)
         prop_depths.append(pd)
     return sb, prop_depths
 
@@ -177,12 +180,12 @@ def crop_bins(scene: NerfSceneDev, origins, directions, obb=None, nears=None, fa
 
 
 def sampling_stage(scene: NerfSceneDev, origins, directions, clip, ray_offset: int, image_width: int = 0,
-                   init_bins: Optional[torch.Tensor] = None, scratch: bool = True):
+                   init_bins: Optional[torch.Tensor] = None, scratch: bool = True, views: Optional[ops.RayViews] = None):
     """-> (final spacing bins, prop depths, feature planes | None); the frame path's stage: its temporaries live in
     scene.workspace.  scratch=False (render_camera(overlap=True)): tensors of their own -- there the bins of group g are
     still being read by the shading stream while this stage runs for group g + 1"""
     sb, prop_depths = sample_rays(scene, origins, directions, clip, ray_offset, image_width=image_width,
-                                  init_bins=init_bins, workspace=scene.workspace if scratch else None)
+                                  init_bins=init_bins, workspace=scene.workspace if scratch else None, views=views)
     feats = (ops.field_gather(origins, directions, sb, scene.field, scene.near, scene.far, spacing=scene.spacing)
              if _uses_split(scene) else None)
     return sb, prop_depths, feats
@@ -192,8 +195,10 @@ def shading_stage(scene: NerfSceneDev, origins, directions, sb, prop_depths, fea
                   depth_noise: Optional[torch.Tensor] = None, depth_draws: int = 100, depth_seed: int = 0,
                   keep_density: bool = False, image_width: int = 0,
                   nonfinite_flag: Optional[torch.Tensor] = None,
-                  keep_masks: Optional[ops.KeepMasks] = None) -> Dict[str, torch.Tensor]:
-    """keep_masks (MCDROPOUT): the FRAME's explicit keep masks (ops.KeepMasks over all its rays, row = ray * S + sample);
+                  keep_masks: Optional[ops.KeepMasks] = None, views: Optional[ops.RayViews] = None) -> Dict[str, torch.Tensor]:
+    """views: the rays are several whole views (render_cameras): the mask counter and the clip rows are numbered inside
+    each view's own frame (ops.RayViews); ray_offset is then 0, the row of the tall image the launch starts at.
+    keep_masks (MCDROPOUT): the FRAME's explicit keep masks (ops.KeepMasks over all its rays, row = ray * S + sample);
     this launch group reads them from row ray_offset * S.  The fp32 re-render of the overflow guard and the two-stream
     path come through here with the same masks."""
     f = scene.field
@@ -205,10 +210,14 @@ def shading_stage(scene: NerfSceneDev, origins, directions, sb, prop_depths, fea
     packed = scene.packed_out and not planes and ops.supports_packed(f)
     density, rgb, aux, aux2 = ops.field_fwd(origins, directions, sb, f, scene.near, scene.far, ray_offset, features=feats,
                                             image_width=image_width, sample_major=planes, spacing=scene.spacing,
-                                            nonfinite_flag=nonfinite_flag, packed=packed, workspace=scene.workspace,
+                                            nonfinite_flag=nonfinite_flag, packed=packed, workspace=scene.workspace, views=views,
                                             keep_masks=None if keep_masks is None else keep_masks.at(ray_offset * (sb.shape[1] - 1)))
     kw = dict(clip_minmax=clip, ray_offset=ray_offset, chunk_rays=scene.chunk_rays, spacing=scene.spacing,
               background=scene.background, nonfinite_flag=nonfinite_flag)
+    if views is not None:
+        if planes or f.mode == _l.FIELD_LAPLACE:
+            raise _l.UnerfError("shading_stage: several views per launch are built for the ray-major ACTIVE / MCDROPOUT path")
+        kw["views"] = views
     res: Dict[str, torch.Tensor] = {}
     if f.mode == _l.FIELD_ACTIVE:
         if planes:
@@ -261,21 +270,25 @@ def shading_stage(scene: NerfSceneDev, origins, directions, sb, prop_depths, fea
 
 def render_rays(scene: NerfSceneDev, origins: torch.Tensor, directions: torch.Tensor, ray_offset: int = 0,
                 total_rays: Optional[int] = None, clip: Optional[torch.Tensor] = None,
-                init_bins: Optional[torch.Tensor] = None, **shade_kw) -> Dict[str, torch.Tensor]:
+                init_bins: Optional[torch.Tensor] = None, views: Optional[ops.RayViews] = None,
+                **shade_kw) -> Dict[str, torch.Tensor]:
     """Render rays [R,3] with the scene's method (field.mode).  Output keys follow the reference:
       ACTIVE     activenerfacto_model.py:117-127   rgb accumulation depth expected_depth rgb_var rgb_std
                                                    depth_var depth_std prop_depth_i (+density)
       MCDROPOUT  mcdropout_models.py:121-126       means of every key + rgb_std depth_std expected_depth_std
       LAPLACE    laplace_model.py:523-530          rgb rgb_std accumulation depth depth_std expected_depth
     keep_masks= (MCDROPOUT, with the other shading arguments): explicit keep masks of the frame, see shading_stage.
+    views= (render_cameras): the rays are several whole views of one size; `clip` must then be given, with each view's rows.
     """
     _l.require_gpu()
     R = origins.shape[0]
     if clip is None:
+        if views is not None:
+            raise _l.UnerfError("render_rays(views=...): pass the clip buffer (clip_rows_per_view rows per view)")
         clip = ops.new_clip_buffer((total_rays or (ray_offset + R)), scene.chunk_rays, origins.device)
     sb, prop_depths, feats = sampling_stage(scene, origins, directions, clip, ray_offset,
-                                            image_width=shade_kw.get("image_width", 0), init_bins=init_bins)
-    return shading_stage(scene, origins, directions, sb, prop_depths, feats, clip, ray_offset, **shade_kw)
+                                            image_width=shade_kw.get("image_width", 0), init_bins=init_bins, views=views)
+    return shading_stage(scene, origins, directions, sb, prop_depths, feats, clip, ray_offset, views=views, **shade_kw)
 
 
 def render_camera(scene: NerfSceneDev, c2w: torch.Tensor, fx: float, fy: float, cx: float, cy: float, H: int, W: int,
@@ -347,6 +360,142 @@ def render_camera(scene: NerfSceneDev, c2w: torch.Tensor, fx: float, fy: float, 
                 for k, v in guard.redo(gi, lambda: group(gi)).items():
                     lists[k][gi] = v
         return {k: torch.cat(v).view(H, W, -1) for k, v in lists.items()}
+
+
+def plan_view_groups(n_views: int, rays_per_view: int, rays_per_launch: int = 1 << 20, chunk_rays: int = 1 << 15,
+                     max_views: int = _l.NERF_MAX_VIEWS) -> Optional[List[Tuple[int, int]]]:
+    """How render_cameras fills its launch groups with WHOLE views: [(first view, number of views), ...], or None when a
+    view is larger than half a launch group (nothing to share: the per-camera loop).  A group holds
+    max(1, rpl // rays_per_view) views, at most max_views (<= lib.NERF_MAX_VIEWS); rpl = rays_per_launch rounded to whole
+    chunks as in render_camera.  Pure function of its arguments."""
+    rpl = max(chunk_rays, (rays_per_launch // chunk_rays) * chunk_rays)
+    if n_views < 1 or rays_per_view < 1:
+        raise ValueError(f"plan_view_groups: {n_views} views of {rays_per_view} rays")
+    if 2 * rays_per_view > rpl:
+        return None
+    per = max(1, min(rpl // rays_per_view, max_views, _l.NERF_MAX_VIEWS))
+    return [(v0, min(per, n_views - v0)) for v0 in range(0, n_views, per)]
+
+
+def _per_view(x, B: int, name: str) -> list:
+    """one value, or one per camera -> B host values"""
+    if torch.is_tensor(x):
+        x = x.detach().cpu().reshape(-1).tolist()
+    if isinstance(x, (list, tuple)):
+        if len(x) == 1:
+            return [x[0]] * B
+        if len(x) != B:
+            raise ValueError(f"render_cameras: {name} has {len(x)} entries for {B} cameras")
+        return list(x)
+    return [x] * B
+
+
+def _per_view_distortion(distortion, B: int) -> Optional[list]:
+    """None | one 6-vector | B entries (None or 6-vector) -> None (no lens anywhere) | B entries"""
+    if distortion is None:
+        return None
+    if torch.is_tensor(distortion):
+        distortion = [distortion] if distortion.dim() == 1 else list(distortion)
+    elif len(distortion) == 6 and not any(d is None or hasattr(d, "__len__") for d in distortion):
+        distortion = [distortion]
+    out = _per_view(list(distortion), B, "distortion")
+    return None if all(d is None for d in out) else out
+
+
+def view_batch_loop_reason(scene: NerfSceneDev, overlap: bool = False, keep_masks=None) -> Optional[str]:
+    """Why render_cameras renders this scene camera by camera (None: it shares launches).  The several-views kernels are
+    built for the frame path's default form: ACTIVE / MCDROPOUT on the f16 matrix kernels, fused lookup, ray-major rows."""
+    f = scene.field
+    if f.mode == _l.FIELD_LAPLACE:
+        return "a Laplace field (its sample sets are per chunk of one frame)"
+    if keep_masks is not None:
+        return "explicit keep masks span one frame"
+    if overlap:
+        return "overlap=True (two streams)"
+    if scene.sample_major:
+        return "sample_major planes"
+    if scene.split_gather:
+        return "split_gather"
+    if f.any_width:
+        return "an any-width field"
+    if not (f.use_mfma and f.precision in ("f16x2", "f16") and f.mfma16_blob is not None):
+        return "an fp32 field (no f16 matrix operands)"
+    if f.mode == _l.FIELD_MCDROPOUT and f.K > 0 and ops.FieldDev._sites(f.drop_sites) != (_l.DROP_TRUNK | _l.DROP_HEAD1):
+        return "non-default dropout sites"
+    return None
+
+
+def render_cameras(scene: NerfSceneDev, c2ws: torch.Tensor, fx, fy, cx, cy, H: int, W: int, seeds=None,
+                   rays_per_launch: int = 1 << 20, overlap: bool = False, obb=None, distortion=None, camera_type=1,
+                   max_views: int = _l.NERF_MAX_VIEWS, **shade_kw) -> List[Dict[str, torch.Tensor]]:
+    """get_outputs_for_camera for B cameras of ONE image size: c2ws [B,3|4,4]; fx, fy, cx, cy, camera_type: one value or one
+    per camera; distortion: None, one 6-vector or one entry per camera.  -> B dicts of images [H,W,C]; element v is
+    bit-identical to render_camera(scene, c2ws[v], ...) -- for MC-dropout with scene.field.seed = seeds[v] (seeds=None:
+    every view under the field's own seed).
+
+    Small frames leave most of a launch group empty (a 200 x 200 frame is 40,000 rays of 2^20), so the rays of several
+    WHOLE views share one launch group: max(1, rpl // (H W)) views per group (plan_view_groups; a view is never split),
+    laid out as one tall row-major image.  The kernels number the clip chunks of the expected depth and the MC-dropout
+    mask counter inside each view's own frame (ops.RayViews), which is what keeps a view's bits.  One OverflowGuard word
+    per group; the views of a group whose word is set are rendered again one by one with render_camera (which re-renders
+    its own offending groups on the fp32 kernels), so they too equal the loop.  scene.workspace, obb and keep_density work
+    as in render_camera.
+
+    Rendered as a plain loop over render_camera -- the SAME results, without shared launches -- when H W exceeds half a
+    launch group, for a Laplace field, with keep_masks= (dropout_masks="torch"), with overlap=True, scene.sample_major or
+    scene.split_gather, for an any-width or fp32 field, non-default dropout sites, and when the camera types of the batch
+    differ (view_batch_loop_reason)."""
+    _l.require_gpu()
+    B = int(c2ws.shape[0])
+    if B < 1:
+        return []
+    fxs, fys, cxs, cys = (_per_view(v, B, n) for v, n in ((fx, "fx"), (fy, "fy"), (cx, "cx"), (cy, "cy")))
+    types = [int(t) for t in _per_view(camera_type, B, "camera_type")]
+    dists = _per_view_distortion(distortion, B)
+    if seeds is not None and len(seeds) != B:
+        raise ValueError(f"render_cameras: {len(seeds)} seeds for {B} cameras")
+    total = H * W
+    f = scene.field
+    c2ws = c2ws.detach().cpu()       # one device -> host copy for the batch (the ray kernels take host camera records)
+
+    def single(v: int) -> Dict[str, torch.Tensor]:
+        saved = f.seed
+        if seeds is not None:
+            f.seed = int(seeds[v])
+        try:
+            return render_camera(scene, c2ws[v], fxs[v], fys[v], cxs[v], cys[v], H, W, rays_per_launch=rays_per_launch,
+                                 overlap=overlap, obb=obb, distortion=None if dists is None else dists[v],
+                                 camera_type=types[v], **shade_kw)
+        finally:
+            f.seed = saved
+
+    groups = plan_view_groups(B, total, rays_per_launch, scene.chunk_rays, max_views)
+    if (groups is None or len(set(types)) != 1
+            or view_batch_loop_reason(scene, overlap, shade_kw.get("keep_masks")) is not None):
+        return [single(v) for v in range(B)]
+    dev = scene.device
+    cpv = ops.clip_rows_per_view(total, scene.chunk_rays)
+    clip = ops.new_clip_buffer(B * cpv * scene.chunk_rays, scene.chunk_rays, dev)     # [B * cpv, 2]: every view its own rows
+    outs: List[Optional[Dict[str, torch.Tensor]]] = [None] * B
+    with torch.cuda.device(dev):
+        guard = OverflowGuard(scene, len(groups))
+        for gi, (v0, nv) in enumerate(groups):
+            o, d = ops.generate_rays_views(c2ws[v0:v0 + nv], fxs[v0:v0 + nv], fys[v0:v0 + nv], cxs[v0:v0 + nv], cys[v0:v0 + nv],
+                                           H, W, dev, distortions=None if dists is None else dists[v0:v0 + nv],
+                                           camera_type=types[0])
+            views = ops.RayViews(nv, total, None if seeds is None else tuple(int(x) for x in seeds[v0:v0 + nv]))
+            res = render_rays(scene, o, d, ray_offset=0, clip=clip[v0 * cpv:(v0 + nv) * cpv], image_width=W,
+                              init_bins=crop_bins(scene, o, d, obb), nonfinite_flag=guard.flag(gi), views=views, **shade_kw)
+            # one contiguous [nv,H,W,C] image stack per key (render_camera's torch.cat), handed out view by view
+            stacks = {k: t.reshape(nv, H, W, -1).contiguous() for k, t in res.items()}
+            for i in range(nv):
+                outs[v0 + i] = {k: t[i] for k, t in stacks.items()}
+        for gi in guard.offenders():
+            v0, nv = groups[gi]
+            for v in range(v0, v0 + nv):
+                outs[v] = single(v)
+            guard.rerendered.append(gi)
+    return outs
 
 
 _STREAMS: Dict[int, Tuple["torch.cuda.Stream", "torch.cuda.Stream"]] = {}
