@@ -624,6 +624,24 @@ int unerf_image_metrics(const float* pred, const float* target, const float* sig
                         const double* z_host, int n_z, int flags, void* workspace, size_t workspace_bytes, double* out,
                         void* stream);
 
+/* The same for a batch of B images of ONE size in one call: the metric stage behind a view batch of the eval loop
+ * (scripts/eval_uncertainty.py:306-412, 647-813 once per image there; eval.py: get_average_uncertainty_metrics with
+ * view_batch > 1).  pred / target [B, n, C], sigma [B, n], mask [B, n] or NULL: contiguous stacks, image b at b n C
+ * (b n) elements; n, C, H, W, the clip, the tables and the flags are shared by the images, 1 <= B <=
+ * UNERF_METRICS_MAX_IMAGES, n C < 2^31 per image (the offsets that carry the image index are 64-bit).
+ * out [B, UNERF_METRICS_ROW]: row b is the row unerf_image_metrics writes for image b alone, EQUAL BIT FOR BIT in all
+ * 656 slots (the zero slots of unset flags and the +-inf minima of an image with nothing valid included) -- the image is
+ * an outer grid coordinate of every kernel, each image keeps the workgroup decomposition and the fixed reduction order
+ * it has alone, and has its own region of the workspace.  The number of memsets and kernel launches does not depend on B.
+ * workspace: unerf_image_metrics_batch_workspace_bytes(n, B) bytes, 8-byte aligned (B times the single-image size).
+ * n = 0 is a successful no-op that leaves `out` alone. */
+#define UNERF_METRICS_MAX_IMAGES 64
+size_t unerf_image_metrics_batch_workspace_bytes(int64_t n, int B);
+int unerf_image_metrics_batch(const float* pred, const float* target, const float* sigma, const uint8_t* mask, int64_t n, int B,
+                              int C, int H, int W, float pred_clip_max, float nll_min_sigma, const double* ratios_host,
+                              int n_ratios, const double* z_host, int n_z, int flags, void* workspace, size_t workspace_bytes,
+                              double* out, void* stream);
+
 /* ================================================================ splats ==
  * gsplat 0.1.11 call sites in models/activesplatfacto/activesplatfacto_model.py. */
 

@@ -16,6 +16,12 @@
 // Every float64 sum goes wave butterfly -> LDS -> slab -> one reducer in a fixed order: two calls on the same inputs
 // give the same bits.  Built with -ffp-contract=off like the rest: the float32 error definitions and the cut ranks
 // (int64)((1 - r) n) are the host's IEEE operations, and the float64 products below fuse only where fma() says so.
+//
+// A batch (unerf_image_metrics_batch) is B images of one size in ONE grid of each kernel: the image is blockIdx.y, and
+// everything an image reads or writes -- its slice of the input stacks, its region of the workspace, its row of `out` --
+// is the single-image pointer moved by a 64-bit per-image stride (mt_img).  blockIdx.x, and with it every fixed-order
+// reduction, is what it is for that image alone: row b of a batch is the row of image b scored alone, bit for bit.
+// unerf_image_metrics is the B = 1 case.
 #include "unerf_common.hpp"
 
 #include <algorithm>
@@ -52,17 +58,24 @@ struct MtLayout {
     size_t zeroed, auce_cnt, seg_part, stat_slab, ssim_slab, seg_block, dtot, table, ksq, kab, kvar, tmp0, tmp1, idx0, idx1, total;
     size_t zero_bytes;
     uint32_t nblocks;
+    // a batch keeps the accumulated regions of its B images next to each other in front (one memset clears them all) and
+    // the B remainders behind them; the offsets above are image 0's, an image's own are these strides further on
+    size_t zstride, rstride;
 };
 inline size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
-MtLayout mt_layout(int64_t n) {
+MtLayout mt_layout(int64_t n, int B) {
     MtLayout L;
+    const size_t nb = B > 1 ? (size_t)B : 1;
     const size_t nn = n > 0 ? (size_t)n : 0;
     L.nblocks = (uint32_t)((nn + MS_TILE - 1) / MS_TILE);
     size_t o = 0;
     L.zeroed = o;                                   // one hipMemsetAsync covers the two regions that are accumulated into
     L.auce_cnt = o; o = al256(o + (MT_MAXK + 1) * sizeof(unsigned long long));
     L.seg_part = o; o = al256(o + MT_FAM * MT_MAXK * sizeof(double));
-    L.zero_bytes = o;
+    L.zstride = o;
+    L.zero_bytes = o * nb;
+    o = L.zero_bytes;
+    const size_t rest0 = o;
     L.stat_slab = o; o = al256(o + (size_t)MT_MAX_WG * MT_NSTAT * sizeof(double));
     L.ssim_slab = o; o = al256(o + (size_t)MT_SSIM_WG * sizeof(double));
     L.seg_block = o; o = al256(o + (size_t)MT_FAM * MT_MAX_WG * sizeof(double));
@@ -70,9 +83,24 @@ MtLayout mt_layout(int64_t n) {
     L.table = o; o = al256(o + (size_t)256 * L.nblocks * sizeof(uint32_t));
     size_t* arr[7] = {&L.ksq, &L.kab, &L.kvar, &L.tmp0, &L.tmp1, &L.idx0, &L.idx1};
     for (size_t* a : arr) { *a = o; o = al256(o + nn * sizeof(uint32_t)); }
-    L.total = o;
+    L.rstride = o - rest0;
+    L.total = rest0 + L.rstride * nb;
     return L;
 }
+
+// image blockIdx.y's copy of a per-image array, given image 0's and the distance between two images in BYTES; a pointer
+// that is not there (no mask, no keys wanted, no payload) stays null
+template <class T>
+__device__ __forceinline__ T* mt_img(T* p, size_t stride_bytes) {
+    return p ? (T*)((char*)p + (size_t)blockIdx.y * stride_bytes) : nullptr;
+}
+template <class T>
+__device__ __forceinline__ const T* mt_img(const T* p, size_t stride_bytes) {
+    return p ? (const T*)((const char*)p + (size_t)blockIdx.y * stride_bytes) : nullptr;
+}
+struct MtStrides {      // bytes from one image to the next
+    size_t z, r;        // workspace: accumulated regions, the rest
+};
 
 // ---- fixed-order reductions ----------------------------------------------------------
 __device__ __forceinline__ double wave_sum(double v) {
@@ -115,12 +143,21 @@ __device__ __forceinline__ bool mt_finite(float x) { return fabsf(x) <= FLT_MAX;
 
 // ---- pass 1: error vectors, plain sums, NLL, AUCE histogram ----------------------------
 template <int C>
-__global__ __launch_bounds__(MT_THREADS) void mt_stats_kernel(const float* __restrict__ pred, const float* __restrict__ target,
-                                                              const float* __restrict__ sigma, const uint8_t* __restrict__ mask,
+__global__ __launch_bounds__(MT_THREADS) void mt_stats_kernel(const float* __restrict__ pred0, const float* __restrict__ target0,
+                                                              const float* __restrict__ sigma0, const uint8_t* __restrict__ mask0,
                                                               uint32_t n, float clip, float min_sigma, int flags, MtZTable zt,
-                                                              uint32_t* __restrict__ ksq, uint32_t* __restrict__ kab,
-                                                              uint32_t* __restrict__ kvar, double* __restrict__ slab,
-                                                              unsigned long long* __restrict__ auce_cnt) {
+                                                              uint32_t* __restrict__ ksq0, uint32_t* __restrict__ kab0,
+                                                              uint32_t* __restrict__ kvar0, double* __restrict__ slab0,
+                                                              unsigned long long* __restrict__ auce_cnt0, MtStrides sd) {
+    const float* __restrict__ pred = mt_img(pred0, (size_t)n * C * sizeof(float));
+    const float* __restrict__ target = mt_img(target0, (size_t)n * C * sizeof(float));
+    const float* __restrict__ sigma = mt_img(sigma0, (size_t)n * sizeof(float));
+    const uint8_t* __restrict__ mask = mt_img(mask0, (size_t)n);
+    uint32_t* __restrict__ ksq = mt_img(ksq0, sd.r);
+    uint32_t* __restrict__ kab = mt_img(kab0, sd.r);
+    uint32_t* __restrict__ kvar = mt_img(kvar0, sd.r);
+    double* __restrict__ slab = mt_img(slab0, sd.r);
+    unsigned long long* __restrict__ auce_cnt = mt_img(auce_cnt0, sd.z);
     __shared__ double zs[MT_MAXK];
     __shared__ uint32_t hist[MT_MAXK + 1];
     __shared__ double red[MT_WAVES];
@@ -206,9 +243,11 @@ __global__ __launch_bounds__(MT_THREADS) void mt_stats_kernel(const float* __res
     }
 }
 
-// slab [nwg, 12] -> out[0..11]; one workgroup of 1024, row t on thread t
-__global__ __launch_bounds__(1024) void mt_reduce_kernel(const double* __restrict__ slab, int nwg, double* __restrict__ out) {
+// slab [nwg, 12] -> out[0..11]; one workgroup of 1024 per image, row t on thread t
+__global__ __launch_bounds__(1024) void mt_reduce_kernel(const double* __restrict__ slab0, int nwg, double* __restrict__ out0, MtStrides sd) {
     __shared__ double red[16];
+    const double* __restrict__ slab = mt_img(slab0, sd.r);
+    double* __restrict__ out = mt_img(out0, UNERF_METRICS_ROW * sizeof(double));
     const int t = threadIdx.x;
     for (int j = 0; j < MT_NSTAT; ++j) {
         if (j < 8) {
@@ -233,9 +272,11 @@ __global__ __launch_bounds__(1024) void mt_reduce_kernel(const double* __restric
 // ---- stable LSD radix sort, 8-bit digits -------------------------------------------------
 // A tile is 4096 consecutive slots; wave w owns slots [1024 w, 1024 (w + 1)) of it and visits them 64 at a time, so
 // "tile, wave, step, lane" is slot order and every rank below is taken in that order: equal digits keep their order.
-__global__ __launch_bounds__(MT_THREADS) void ms_hist_kernel(const uint32_t* __restrict__ keys, uint32_t n, int shift,
-                                                             uint32_t* __restrict__ table, uint32_t nblocks) {
+__global__ __launch_bounds__(MT_THREADS) void ms_hist_kernel(const uint32_t* __restrict__ keys0, uint32_t n, int shift,
+                                                             uint32_t* __restrict__ table0, uint32_t nblocks, MtStrides sd) {
     __shared__ uint32_t h[256];
+    const uint32_t* __restrict__ keys = mt_img(keys0, sd.r);
+    uint32_t* __restrict__ table = mt_img(table0, sd.r);
     h[threadIdx.x] = 0u;
     __syncthreads();
     const uint32_t base = blockIdx.x * MS_TILE;
@@ -249,9 +290,12 @@ __global__ __launch_bounds__(MT_THREADS) void ms_hist_kernel(const uint32_t* __r
 }
 
 // workgroup d: exclusive scan of digit d's row of the table in place, the row's total -> dtot[d]
-__global__ __launch_bounds__(1024) void ms_rowscan_kernel(uint32_t* __restrict__ table, uint32_t nblocks, uint32_t* __restrict__ dtot) {
+__global__ __launch_bounds__(1024) void ms_rowscan_kernel(uint32_t* __restrict__ table0, uint32_t nblocks, uint32_t* __restrict__ dtot0,
+                                                          MtStrides sd) {
     __shared__ uint32_t wsum[16];
     __shared__ uint32_t carry_sh;
+    uint32_t* __restrict__ table = mt_img(table0, sd.r);
+    uint32_t* __restrict__ dtot = mt_img(dtot0, sd.r);
     uint32_t* row = table + (size_t)blockIdx.x * nblocks;
     const int t = threadIdx.x, lane = t & 63, w = t >> 6;
     if (t == 0) carry_sh = 0u;
@@ -273,12 +317,18 @@ __global__ __launch_bounds__(1024) void ms_rowscan_kernel(uint32_t* __restrict__
 }
 
 template <bool IDX_IN, bool IDX_OUT>
-__global__ __launch_bounds__(MT_THREADS) void ms_scatter_kernel(const uint32_t* __restrict__ kin, const uint32_t* __restrict__ iin,
-                                                                uint32_t* __restrict__ kout, uint32_t* __restrict__ iout, uint32_t n,
-                                                                int shift, const uint32_t* __restrict__ table,
-                                                                const uint32_t* __restrict__ dtot, uint32_t nblocks) {
+__global__ __launch_bounds__(MT_THREADS) void ms_scatter_kernel(const uint32_t* __restrict__ kin0, const uint32_t* __restrict__ iin0,
+                                                                uint32_t* __restrict__ kout0, uint32_t* __restrict__ iout0, uint32_t n,
+                                                                int shift, const uint32_t* __restrict__ table0,
+                                                                const uint32_t* __restrict__ dtot0, uint32_t nblocks, MtStrides sd) {
     __shared__ uint32_t cnt[MT_WAVES][256];
     __shared__ uint32_t wsum[MT_WAVES];
+    const uint32_t* __restrict__ kin = mt_img(kin0, sd.r);
+    const uint32_t* __restrict__ iin = mt_img(iin0, sd.r);
+    uint32_t* __restrict__ kout = mt_img(kout0, sd.r);
+    uint32_t* __restrict__ iout = mt_img(iout0, sd.r);
+    const uint32_t* __restrict__ table = mt_img(table0, sd.r);
+    const uint32_t* __restrict__ dtot = mt_img(dtot0, sd.r);
     const int t = threadIdx.x, lane = t & 63, w = t >> 6;
     volatile uint32_t* mycnt = cnt[w];
 #pragma unroll
@@ -350,12 +400,18 @@ __device__ __forceinline__ long long mt_keep(double ratio, double n_valid) {
     return k < 0 ? 0 : (k > nv ? nv : k);
 }
 template <bool BY_VAR>
-__global__ __launch_bounds__(MT_THREADS) void mt_segsum_kernel(const uint32_t* __restrict__ sorted, const uint32_t* __restrict__ ksq,
-                                                               const uint32_t* __restrict__ kab, uint32_t n, uint32_t per,
-                                                               const double* __restrict__ row, MtRatios rt, int fam0,
-                                                               double* __restrict__ seg_block, double* __restrict__ seg_part) {
+__global__ __launch_bounds__(MT_THREADS) void mt_segsum_kernel(const uint32_t* __restrict__ sorted0, const uint32_t* __restrict__ ksq0,
+                                                               const uint32_t* __restrict__ kab0, uint32_t n, uint32_t per,
+                                                               const double* __restrict__ row0, MtRatios rt, int fam0,
+                                                               double* __restrict__ seg_block0, double* __restrict__ seg_part0, MtStrides sd) {
     __shared__ double red[MT_WAVES];
     __shared__ long long keep[MT_MAXK];
+    const uint32_t* __restrict__ sorted = mt_img(sorted0, sd.r);
+    const uint32_t* __restrict__ ksq = mt_img(ksq0, sd.r);
+    const uint32_t* __restrict__ kab = mt_img(kab0, sd.r);
+    const double* __restrict__ row = mt_img(row0, UNERF_METRICS_ROW * sizeof(double));     // the image's own n_valid
+    double* __restrict__ seg_block = mt_img(seg_block0, sd.r);
+    double* __restrict__ seg_part = mt_img(seg_part0, sd.z);
     const double n_valid = row[0];
     for (int k = threadIdx.x; k < rt.n; k += MT_THREADS) keep[k] = mt_keep(rt.r[k], n_valid);
     __syncthreads();
@@ -398,9 +454,14 @@ __global__ __launch_bounds__(MT_THREADS) void mt_segsum_kernel(const uint32_t* _
 // One work item = a 32 x 16 tile of interior pixels of one channel: its 42 x 26 input pixels go to LDS, the rows are
 // filtered into five float64 maps, the columns of those give the window sums.  Work items are dealt to the workgroups
 // round-robin, each workgroup leaves one partial sum.
-__global__ __launch_bounds__(MT_THREADS) void mt_ssim_kernel(const float* __restrict__ pred, const float* __restrict__ target, int H,
-                                                             int W, int C, float clip, MtGauss gw, const double* __restrict__ row,
-                                                             double* __restrict__ slab) {
+__global__ __launch_bounds__(MT_THREADS) void mt_ssim_kernel(const float* __restrict__ pred0, const float* __restrict__ target0, int H,
+                                                             int W, int C, float clip, MtGauss gw, const double* __restrict__ row0,
+                                                             double* __restrict__ slab0, MtStrides sd) {
+    const size_t image_bytes = (size_t)H * W * C * sizeof(float);
+    const float* __restrict__ pred = mt_img(pred0, image_bytes);
+    const float* __restrict__ target = mt_img(target0, image_bytes);
+    const double* __restrict__ row = mt_img(row0, UNERF_METRICS_ROW * sizeof(double));     // the image's own minima / maxima
+    double* __restrict__ slab = mt_img(slab0, sd.r);
     __shared__ float sp[SS_IH][SS_IW], st[SS_IH][SS_IW];
     __shared__ double hor[5][SS_IH][SS_TW];
     __shared__ double red[MT_WAVES];
@@ -465,13 +526,18 @@ __global__ __launch_bounds__(MT_THREADS) void mt_ssim_kernel(const float* __rest
     if (threadIdx.x == 0) slab[blockIdx.x] = r;
 }
 
-// ---- the last kernel: workgroups 0..3 the AUSE families, 4 the AUCE counts, 5 the SSIM sum -----
-__global__ __launch_bounds__(1024) void mt_finish_kernel(const double* __restrict__ seg_block, const double* __restrict__ seg_part,
-                                                         int seg_blocks, uint32_t per, MtRatios rt, const unsigned long long* __restrict__ auce_cnt,
-                                                         MtZTable zt, const double* __restrict__ ssim_slab, int ssim_wg, double ssim_count,
-                                                         int flags, double* __restrict__ out) {
+// ---- the last kernel: per image, workgroups 0..3 the AUSE families, 4 the AUCE counts, 5 the SSIM sum -----
+__global__ __launch_bounds__(1024) void mt_finish_kernel(const double* __restrict__ seg_block0, const double* __restrict__ seg_part0,
+                                                         int seg_blocks, uint32_t per, MtRatios rt, const unsigned long long* __restrict__ auce_cnt0,
+                                                         MtZTable zt, const double* __restrict__ ssim_slab0, int ssim_wg, double ssim_count,
+                                                         int flags, double* __restrict__ out0, MtStrides sd) {
     __shared__ double sc[1025];
     __shared__ double red[16];
+    const double* __restrict__ seg_block = mt_img(seg_block0, sd.r);
+    const double* __restrict__ seg_part = mt_img(seg_part0, sd.z);
+    const unsigned long long* __restrict__ auce_cnt = mt_img(auce_cnt0, sd.z);
+    const double* __restrict__ ssim_slab = mt_img(ssim_slab0, sd.r);
+    double* __restrict__ out = mt_img(out0, UNERF_METRICS_ROW * sizeof(double));
     const int t = threadIdx.x;
     if (blockIdx.x < MT_FAM) {
         if (!(flags & UNERF_METRICS_AUSE)) return;
@@ -518,7 +584,8 @@ __global__ __launch_bounds__(1024) void mt_finish_kernel(const double* __restric
     }
 }
 
-void ms_sort(hipStream_t st, const MtLayout& L, char* ws, uint32_t n, const uint32_t* keys, bool with_idx) {
+void ms_sort(hipStream_t st, const MtLayout& L, char* ws, uint32_t n, int B, const uint32_t* keys, bool with_idx) {
+    const MtStrides sd{L.zstride, L.rstride};
     uint32_t* table = (uint32_t*)(ws + L.table);
     uint32_t* dtot = (uint32_t*)(ws + L.dtot);
     uint32_t* kbuf[2] = {(uint32_t*)(ws + L.tmp0), (uint32_t*)(ws + L.tmp1)};
@@ -529,48 +596,51 @@ void ms_sort(hipStream_t st, const MtLayout& L, char* ws, uint32_t n, const uint
         uint32_t* kout = kbuf[pass & 1];
         uint32_t* iout = ibuf[pass & 1];
         const int shift = 8 * pass;
-        hipLaunchKernelGGL(ms_hist_kernel, dim3(L.nblocks), dim3(MT_THREADS), 0, st, kin, n, shift, table, L.nblocks);
-        hipLaunchKernelGGL(ms_rowscan_kernel, dim3(256), dim3(1024), 0, st, table, L.nblocks, dtot);
+        hipLaunchKernelGGL(ms_hist_kernel, dim3(L.nblocks, B), dim3(MT_THREADS), 0, st, kin, n, shift, table, L.nblocks, sd);
+        hipLaunchKernelGGL(ms_rowscan_kernel, dim3(256, B), dim3(1024), 0, st, table, L.nblocks, dtot, sd);
         if (!with_idx)
-            hipLaunchKernelGGL((ms_scatter_kernel<false, false>), dim3(L.nblocks), dim3(MT_THREADS), 0, st, kin, iin, kout, iout, n, shift, table, dtot, L.nblocks);
+            hipLaunchKernelGGL((ms_scatter_kernel<false, false>), dim3(L.nblocks, B), dim3(MT_THREADS), 0, st, kin, iin, kout, iout, n, shift, table, dtot, L.nblocks, sd);
         else if (pass == 0)
-            hipLaunchKernelGGL((ms_scatter_kernel<false, true>), dim3(L.nblocks), dim3(MT_THREADS), 0, st, kin, iin, kout, iout, n, shift, table, dtot, L.nblocks);
+            hipLaunchKernelGGL((ms_scatter_kernel<false, true>), dim3(L.nblocks, B), dim3(MT_THREADS), 0, st, kin, iin, kout, iout, n, shift, table, dtot, L.nblocks, sd);
         else
-            hipLaunchKernelGGL((ms_scatter_kernel<true, true>), dim3(L.nblocks), dim3(MT_THREADS), 0, st, kin, iin, kout, iout, n, shift, table, dtot, L.nblocks);
+            hipLaunchKernelGGL((ms_scatter_kernel<true, true>), dim3(L.nblocks, B), dim3(MT_THREADS), 0, st, kin, iin, kout, iout, n, shift, table, dtot, L.nblocks, sd);
         kin = kout;
         iin = iout;
     }
 }
 
-}  // namespace
-
-extern "C" size_t unerf_image_metrics_workspace_bytes(int64_t n) { return mt_layout(n).total; }
-
-extern "C" int unerf_image_metrics(const float* pred, const float* target, const float* sigma, const uint8_t* mask, int64_t n, int C,
-                                   int H, int W, float pred_clip_max, float nll_min_sigma, const double* ratios_host, int n_ratios,
-                                   const double* z_host, int n_z, int flags, void* workspace, size_t workspace_bytes, double* out,
-                                   void* stream) {
-    UNERF_REQUIRE(n >= 0, "image_metrics: n = %lld", (long long)n);
+// Both entry points.  `who` names the entry in messages, `batch` selects the wording of the workspace refusal; B = 1 is the
+// single image.  Every launch below is one grid over all B images: nothing here loops over them.
+int mt_run(const char* who, bool batch, const float* pred, const float* target, const float* sigma, const uint8_t* mask, int64_t n, int B,
+           int C, int H, int W, float pred_clip_max, float nll_min_sigma, const double* ratios_host, int n_ratios, const double* z_host,
+           int n_z, int flags, void* workspace, size_t workspace_bytes, double* out, void* stream) {
+    UNERF_REQUIRE(n >= 0, "%s: n = %lld", who, (long long)n);
+    UNERF_REQUIRE(B >= 1 && B <= UNERF_METRICS_MAX_IMAGES, "%s: B = %d (expected 1..%d images)", who, B, UNERF_METRICS_MAX_IMAGES);
     if (n == 0) return UNERF_OK;
-    UNERF_REQUIRE(pred && target && sigma && out && workspace, "image_metrics: null pointer (pred / target / sigma / workspace / out) with n > 0");
-    UNERF_REQUIRE(C >= 1 && C <= 4, "image_metrics: C = %d (expected 1..4)", C);
-    UNERF_REQUIRE(n * (int64_t)C < ((int64_t)1 << 31), "image_metrics: n * C = %lld (must stay below 2^31)", (long long)(n * C));
-    UNERF_REQUIRE(n_ratios >= 1 && n_ratios <= MT_MAXK && ratios_host, "image_metrics: n_ratios = %d (expected 1..128 host values)", n_ratios);
-    UNERF_REQUIRE(n_z >= 1 && n_z <= MT_MAXK && z_host, "image_metrics: n_z = %d (expected 1..128 host values)", n_z);
+    UNERF_REQUIRE(pred && target && sigma && out && workspace, "%s: null pointer (pred / target / sigma / workspace / out) with n > 0", who);
+    UNERF_REQUIRE(C >= 1 && C <= 4, "%s: C = %d (expected 1..4)", who, C);
+    UNERF_REQUIRE(n * (int64_t)C < ((int64_t)1 << 31), "%s: n * C = %lld (must stay below 2^31)", who, (long long)(n * C));
+    UNERF_REQUIRE(n_ratios >= 1 && n_ratios <= MT_MAXK && ratios_host, "%s: n_ratios = %d (expected 1..128 host values)", who, n_ratios);
+    UNERF_REQUIRE(n_z >= 1 && n_z <= MT_MAXK && z_host, "%s: n_z = %d (expected 1..128 host values)", who, n_z);
     if (flags & UNERF_METRICS_SSIM) {
-        UNERF_REQUIRE(mask == nullptr, "image_metrics: UNERF_METRICS_SSIM takes no mask");
-        UNERF_REQUIRE((int64_t)H * (int64_t)W == n && H > 0 && W > 0, "image_metrics: UNERF_METRICS_SSIM needs H * W == n (H = %d, W = %d, n = %lld)", H,
+        UNERF_REQUIRE(mask == nullptr, "%s: UNERF_METRICS_SSIM takes no mask", who);
+        UNERF_REQUIRE((int64_t)H * (int64_t)W == n && H > 0 && W > 0, "%s: UNERF_METRICS_SSIM needs H * W == n (H = %d, W = %d, n = %lld)", who, H,
                       W, (long long)n);
-        UNERF_REQUIRE(std::min(H, W) >= SS_K, "image_metrics: UNERF_METRICS_SSIM needs min(H, W) >= 11 (H = %d, W = %d)", H, W);
+        UNERF_REQUIRE(std::min(H, W) >= SS_K, "%s: UNERF_METRICS_SSIM needs min(H, W) >= 11 (H = %d, W = %d)", who, H, W);
     }
-    const MtLayout L = mt_layout(n);
-    UNERF_REQUIRE(workspace_bytes >= L.total, "image_metrics: workspace of %zu bytes, unerf_image_metrics_workspace_bytes(%lld) = %zu",
-                  workspace_bytes, (long long)n, L.total);
-    UNERF_REQUIRE(((uintptr_t)workspace & 7) == 0 && ((uintptr_t)out & 7) == 0, "image_metrics: workspace / out must be 8-byte aligned");
+    const MtLayout L = mt_layout(n, B);
+    if (batch)
+        UNERF_REQUIRE(workspace_bytes >= L.total, "%s: workspace of %zu bytes, unerf_image_metrics_batch_workspace_bytes(%lld, %d) = %zu", who,
+                      workspace_bytes, (long long)n, B, L.total);
+    else
+        UNERF_REQUIRE(workspace_bytes >= L.total, "%s: workspace of %zu bytes, unerf_image_metrics_workspace_bytes(%lld) = %zu", who,
+                      workspace_bytes, (long long)n, L.total);
+    UNERF_REQUIRE(((uintptr_t)workspace & 7) == 0 && ((uintptr_t)out & 7) == 0, "%s: workspace / out must be 8-byte aligned", who);
 
     hipStream_t st = (hipStream_t)stream;
     char* ws = (char*)workspace;
     const uint32_t un = (uint32_t)n;
+    const MtStrides sd{L.zstride, L.rstride};
     MtZTable zt;
     {   // thresholds ascending (ties in the caller's order) and the way back
         int order[MT_MAXK];
@@ -583,8 +653,9 @@ extern "C" int unerf_image_metrics(const float* pred, const float* target, const
     for (int i = 0; i < MT_MAXK; ++i) rt.r[i] = i < n_ratios ? ratios_host[i] : 0.0;
     rt.n = n_ratios;
 
-    if (hipMemsetAsync(ws + L.zeroed, 0, L.zero_bytes, st) != hipSuccess) return unerf_check_launch("image_metrics (memset)");
-    if (hipMemsetAsync(out, 0, UNERF_METRICS_ROW * sizeof(double), st) != hipSuccess) return unerf_check_launch("image_metrics (memset)");
+    // the accumulated regions of all B images lie next to each other, and so do the B rows
+    if (hipMemsetAsync(ws + L.zeroed, 0, L.zero_bytes, st) != hipSuccess) return unerf_check_launch(who);
+    if (hipMemsetAsync(out, 0, (size_t)B * UNERF_METRICS_ROW * sizeof(double), st) != hipSuccess) return unerf_check_launch(who);
     const bool want_ause = flags & UNERF_METRICS_AUSE;
     uint32_t* ksq = want_ause ? (uint32_t*)(ws + L.ksq) : nullptr;
     uint32_t* kab = (uint32_t*)(ws + L.kab);
@@ -593,8 +664,8 @@ extern "C" int unerf_image_metrics(const float* pred, const float* target, const
     unsigned long long* auce_cnt = (unsigned long long*)(ws + L.auce_cnt);
     const int nwg = (int)std::min<int64_t>((n + MT_THREADS - 1) / MT_THREADS, MT_MAX_WG);
 #define MT_STATS(CC)                                                                                                              \
-    hipLaunchKernelGGL(mt_stats_kernel<CC>, dim3(nwg), dim3(MT_THREADS), 0, st, pred, target, sigma, mask, un, pred_clip_max, \
-                       nll_min_sigma, flags, zt, ksq, kab, kvar, stat_slab, auce_cnt)
+    hipLaunchKernelGGL(mt_stats_kernel<CC>, dim3(nwg, B), dim3(MT_THREADS), 0, st, pred, target, sigma, mask, un, pred_clip_max, \
+                       nll_min_sigma, flags, zt, ksq, kab, kvar, stat_slab, auce_cnt, sd)
     switch (C) {
         case 1: MT_STATS(1); break;
         case 2: MT_STATS(2); break;
@@ -602,9 +673,9 @@ extern "C" int unerf_image_metrics(const float* pred, const float* target, const
         default: MT_STATS(4); break;
     }
 #undef MT_STATS
-    hipLaunchKernelGGL(mt_reduce_kernel, dim3(1), dim3(1024), 0, st, stat_slab, nwg, out);
+    hipLaunchKernelGGL(mt_reduce_kernel, dim3(1, B), dim3(1024), 0, st, stat_slab, nwg, out, sd);
 
-    // segsum blocks: at most 1024 of them, each a whole number of 256-slot strides
+    // segsum blocks: at most 1024 of them per image, each a whole number of 256-slot strides
     const uint32_t per = (uint32_t)(((n + MT_MAX_WG - 1) / MT_MAX_WG + MT_THREADS - 1) / MT_THREADS) * MT_THREADS;
     const int seg_blocks = (int)((n + per - 1) / per);
     double* seg_block = (double*)(ws + L.seg_block);
@@ -612,12 +683,12 @@ extern "C" int unerf_image_metrics(const float* pred, const float* target, const
     if (want_ause) {
         const uint32_t* sorted_k = (const uint32_t*)(ws + L.tmp1);
         const uint32_t* sorted_i = (const uint32_t*)(ws + L.idx1);
-        ms_sort(st, L, ws, un, ksq, false);
-        hipLaunchKernelGGL(mt_segsum_kernel<false>, dim3(seg_blocks), dim3(MT_THREADS), 0, st, sorted_k, ksq, kab, un, per, out, rt, 0, seg_block, seg_part);
-        ms_sort(st, L, ws, un, kab, false);
-        hipLaunchKernelGGL(mt_segsum_kernel<false>, dim3(seg_blocks), dim3(MT_THREADS), 0, st, sorted_k, ksq, kab, un, per, out, rt, 1, seg_block, seg_part);
-        ms_sort(st, L, ws, un, kvar, true);
-        hipLaunchKernelGGL(mt_segsum_kernel<true>, dim3(seg_blocks), dim3(MT_THREADS), 0, st, sorted_i, ksq, kab, un, per, out, rt, 2, seg_block, seg_part);
+        ms_sort(st, L, ws, un, B, ksq, false);
+        hipLaunchKernelGGL(mt_segsum_kernel<false>, dim3(seg_blocks, B), dim3(MT_THREADS), 0, st, sorted_k, ksq, kab, un, per, out, rt, 0, seg_block, seg_part, sd);
+        ms_sort(st, L, ws, un, B, kab, false);
+        hipLaunchKernelGGL(mt_segsum_kernel<false>, dim3(seg_blocks, B), dim3(MT_THREADS), 0, st, sorted_k, ksq, kab, un, per, out, rt, 1, seg_block, seg_part, sd);
+        ms_sort(st, L, ws, un, B, kvar, true);
+        hipLaunchKernelGGL(mt_segsum_kernel<true>, dim3(seg_blocks, B), dim3(MT_THREADS), 0, st, sorted_i, ksq, kab, un, per, out, rt, 2, seg_block, seg_part, sd);
     }
     int ssim_wg = 0;
     double ssim_count = 0.0;
@@ -630,10 +701,32 @@ extern "C" int unerf_image_metrics(const float* pred, const float* target, const
         const int64_t items = (int64_t)((OW + SS_TW - 1) / SS_TW) * ((OH + SS_TH - 1) / SS_TH) * C;
         ssim_wg = (int)std::min<int64_t>(items, MT_SSIM_WG);
         ssim_count = (double)OW * (double)OH * (double)C;
-        hipLaunchKernelGGL(mt_ssim_kernel, dim3(ssim_wg), dim3(MT_THREADS), 0, st, pred, target, H, W, C, pred_clip_max, gw, out,
-                           (double*)(ws + L.ssim_slab));
+        hipLaunchKernelGGL(mt_ssim_kernel, dim3(ssim_wg, B), dim3(MT_THREADS), 0, st, pred, target, H, W, C, pred_clip_max, gw, out,
+                           (double*)(ws + L.ssim_slab), sd);
     }
-    hipLaunchKernelGGL(mt_finish_kernel, dim3(MT_FAM + 2), dim3(1024), 0, st, seg_block, seg_part, seg_blocks, per, rt, auce_cnt, zt,
-                       (const double*)(ws + L.ssim_slab), ssim_wg, ssim_count, flags, out);
-    return unerf_check_launch("image_metrics");
+    hipLaunchKernelGGL(mt_finish_kernel, dim3(MT_FAM + 2, B), dim3(1024), 0, st, seg_block, seg_part, seg_blocks, per, rt, auce_cnt, zt,
+                       (const double*)(ws + L.ssim_slab), ssim_wg, ssim_count, flags, out, sd);
+    return unerf_check_launch(who);
+}
+
+}  // namespace
+
+extern "C" size_t unerf_image_metrics_workspace_bytes(int64_t n) { return mt_layout(n, 1).total; }
+
+extern "C" int unerf_image_metrics(const float* pred, const float* target, const float* sigma, const uint8_t* mask, int64_t n, int C,
+                                   int H, int W, float pred_clip_max, float nll_min_sigma, const double* ratios_host, int n_ratios,
+                                   const double* z_host, int n_z, int flags, void* workspace, size_t workspace_bytes, double* out,
+                                   void* stream) {
+    return mt_run("image_metrics", false, pred, target, sigma, mask, n, 1, C, H, W, pred_clip_max, nll_min_sigma, ratios_host, n_ratios,
+                  z_host, n_z, flags, workspace, workspace_bytes, out, stream);
+}
+
+extern "C" size_t unerf_image_metrics_batch_workspace_bytes(int64_t n, int B) { return mt_layout(n, B).total; }
+
+extern "C" int unerf_image_metrics_batch(const float* pred, const float* target, const float* sigma, const uint8_t* mask, int64_t n, int B,
+                                         int C, int H, int W, float pred_clip_max, float nll_min_sigma, const double* ratios_host,
+                                         int n_ratios, const double* z_host, int n_z, int flags, void* workspace, size_t workspace_bytes,
+                                         double* out, void* stream) {
+    return mt_run("image_metrics_batch", true, pred, target, sigma, mask, n, B, C, H, W, pred_clip_max, nll_min_sigma, ratios_host, n_ratios,
+                  z_host, n_z, flags, workspace, workspace_bytes, out, stream);
 }

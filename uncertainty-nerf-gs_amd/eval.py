@@ -22,7 +22,7 @@ import time
 from dataclasses import dataclass
 from functools import partial
 from pathlib import Path
-from typing import Callable, Dict, Iterable, List, Optional, Tuple, Union
+from typing import Callable, Dict, Iterable, List, Optional, Sequence, Tuple, Union
 
 import numpy as np
 import torch
@@ -74,22 +74,65 @@ def image_metrics_unc(outputs: Dict[str, torch.Tensor], gt_image: torch.Tensor, 
 def _image_metrics_unc_fused(outputs, gt_image, eval_rgb_unc, min_rgb_std_for_nll, composite_gt):
     """image_metrics_unc through the kernels.  The ground-truth composition stays in torch in front of the call
     (elementwise, no sync); the clip of the prediction to <= 1 happens inside the kernels."""
-    from . import lib as _l, ops
-    rgb = outputs["rgb"].to(torch.float32).contiguous()
-    image = gt_image.to(rgb.device)
-    if "background" in outputs and composite_gt is not None:
-        image = composite_gt(image, outputs["background"])
-    image = image[..., :rgb.shape[-1]].to(torch.float32).contiguous()
+    from . import ops
+    rgb, image, std, flags = _rgb_operands(outputs, gt_image, eval_rgb_unc, composite_gt)
     H, W, Cc = rgb.shape
-    if eval_rgb_unc:
-        flags, std = _l.METRICS_ALL, outputs["rgb_std"].to(torch.float32).reshape(H, W).contiguous()
-    else:
-        flags, std = _l.METRICS_SSIM, torch.zeros(H, W, device=rgb.device)
     row = ops.image_metrics(rgb, image, std, None, image_hw=(H, W), clip_max=1.0, nll_min_sigma=min_rgb_std_for_nll, flags=flags)
     md, curves = M.finish_metrics(row.cpu().numpy(), Cc, "rgb", flags)
     if not eval_rgb_unc:
         md = {"psnr": md["psnr"], "ssim": md["ssim"]}
     return md, curves
+
+
+def _rgb_operands(outputs, gt_image, eval_rgb_unc, composite_gt):
+    """one image's operands of the fused rgb metrics: (rgb [H,W,C], composed GT [H,W,C], std [H,W], flags), float32"""
+    from . import lib as _l
+    rgb = outputs["rgb"].to(torch.float32).contiguous()
+    image = gt_image.to(rgb.device)
+    if "background" in outputs and composite_gt is not None:
+        image = composite_gt(image, outputs["background"])
+    image = image[..., :rgb.shape[-1]].to(torch.float32).contiguous()
+    H, W, _ = rgb.shape
+    if eval_rgb_unc:
+        return rgb, image, outputs["rgb_std"].to(torch.float32).reshape(H, W).contiguous(), _l.METRICS_ALL
+    return rgb, image, torch.zeros(H, W, device=rgb.device), _l.METRICS_SSIM
+
+
+def _finish_rows(rows_host, image_ids, finish):
+    """finish(row) per row of a batch; a row that cannot be finished (non-finite input, nothing valid) raises as
+    finish_metrics does, with the image named in front"""
+    done = []
+    for b, row in enumerate(rows_host):
+        try:
+            done.append(finish(row))
+        except ValueError as e:
+            raise ValueError(f"image {b if image_ids is None else image_ids[b]}: {e}") from None
+    return done
+
+
+def image_metrics_unc_batch(outputs_list: Sequence[Dict[str, torch.Tensor]], gt_images: Sequence[torch.Tensor], eval_rgb_unc: bool = True,
+                            min_rgb_std_for_nll: float = 3e-2, composite_gt: Optional[Callable] = None, *,
+                            image_ids: Optional[Sequence[int]] = None):
+    """image_metrics_unc(fused=True) for B renders of one size (at most lib.METRICS_MAX_IMAGES) -> [(metrics_dict, curves)] * B.
+    The ground-truth composition and the float32 casts stay per image; then one torch.stack per operand, ONE
+    ops.image_metrics_batch, one copy of its [B, row] result to the host and finish_metrics per row.  Row b of the batch is
+    the row of image b alone bit for bit, so every entry equals the per-image call's.  An image with a non-finite input
+    raises as finish_metrics does, named by image_ids[b] (default: its position in the batch)."""
+    from . import ops
+    if len(outputs_list) != len(gt_images) or not outputs_list:
+        raise ValueError(f"{len(outputs_list)} renders for {len(gt_images)} ground-truth images")
+    parts = [_rgb_operands(o, gt, eval_rgb_unc, composite_gt) for o, gt in zip(outputs_list, gt_images)]
+    flags = parts[0][3]
+    if any(p[0].shape != parts[0][0].shape for p in parts):
+        raise ValueError(f"a batch holds renders of one size, got {sorted({tuple(p[0].shape) for p in parts})}")
+    rgb, image, std = (torch.stack([p[j] for p in parts]) for j in range(3))
+    _, H, W, Cc = rgb.shape
+    rows = ops.image_metrics_batch(rgb, image, std, None, image_hw=(H, W), clip_max=1.0, nll_min_sigma=min_rgb_std_for_nll,
+                                   flags=flags).cpu().numpy()
+    done = _finish_rows(rows, image_ids, lambda row: M.finish_metrics(row, Cc, "rgb", flags))
+    if not eval_rgb_unc:
+        done = [({"psnr": md["psnr"], "ssim": md["ssim"]}, curves) for md, curves in done]
+    return done
 
 
 def load_depth_gt(dataset_path: str, img_num: int) -> Tuple[np.ndarray, float]:
@@ -108,21 +151,7 @@ def depth_metrics_unc(outputs: Dict[str, torch.Tensor], depth_gt, scale: float, 
     fused=True: resize / scale / clip stay in torch (elementwise, `gt.max()` stays a tensor: no sync); everything behind
     them is one ops.image_metrics call with mask = GT > 0 (the NLL-then-mask above is the masked NLL, element by
     element).  The ground truth is taken as float32 there."""
-    depth = outputs["depth"].squeeze(-1).to(torch.float32)
-    depth_std = outputs["depth_std"].squeeze(-1).to(torch.float32)
-    gt = torch.as_tensor(depth_gt, device=depth.device)
-
-    def _fit(x):
-        if gt.shape[-2:] == x.shape[-2:]:
-            return x
-        return torch.nn.functional.interpolate(x[None, None], size=tuple(gt.shape[-2:]), mode="bilinear",
-                                               align_corners=False, antialias=False)[0, 0]
-
-    depth, depth_std = _fit(depth), _fit(depth_std)
-    lo, hi = 1e-3, gt.max().float()
-    depth = scale * depth
-    depth_std = scale * depth_std
-    clipped = torch.minimum(torch.clamp_min(depth, lo), hi)
+    clipped, gt, depth_std = _depth_operands(outputs, depth_gt, scale)
     if fused:
         from . import lib as _l, ops
         flags = _l.METRICS_ALL & ~_l.METRICS_SSIM
@@ -151,6 +180,47 @@ def depth_metrics_unc(outputs: Dict[str, torch.Tensor], depth_gt, scale: float, 
               "neg_coverage_error_values"):
         curves[f"depth_all_auce_{k}"] = a[k]
     return md, curves
+
+
+def _depth_operands(outputs, depth_gt, scale):
+    """one image's depth operands in torch: resize to the GT map, scale, clip to [1e-3, max GT] (a tensor: no sync)
+    -> (clipped depth [H,W], gt [H,W] on the render's device, scaled depth_std [H,W])"""
+    depth = outputs["depth"].squeeze(-1).to(torch.float32)
+    depth_std = outputs["depth_std"].squeeze(-1).to(torch.float32)
+    gt = torch.as_tensor(depth_gt, device=depth.device)
+
+    def _fit(x):
+        if gt.shape[-2:] == x.shape[-2:]:
+            return x
+        return torch.nn.functional.interpolate(x[None, None], size=tuple(gt.shape[-2:]), mode="bilinear",
+                                               align_corners=False, antialias=False)[0, 0]
+
+    depth, depth_std = _fit(depth), _fit(depth_std)
+    lo, hi = 1e-3, gt.max().float()
+    depth = scale * depth
+    depth_std = scale * depth_std
+    return torch.minimum(torch.clamp_min(depth, lo), hi), gt, depth_std
+
+
+def depth_metrics_unc_batch(outputs_list: Sequence[Dict[str, torch.Tensor]], depth_gts: Sequence, scales: Sequence[float],
+                            min_depth_std_for_nll: float = 1.0, *, image_ids: Optional[Sequence[int]] = None):
+    """depth_metrics_unc(fused=True) for B renders whose depth GT maps share ONE shape (at most lib.METRICS_MAX_IMAGES)
+    -> [(metrics_dict, curves)] * B.  Resize, scale and clip stay in torch per image (each image's `gt.max()` stays a
+    tensor); the masks `gt > 0` go in as the [B, n] mask of one ops.image_metrics_batch without SSIM; one copy to the host,
+    finish_metrics per row.  Entries equal the per-image call's; errors name the image as in image_metrics_unc_batch."""
+    from . import lib as _l, ops
+    if not (len(outputs_list) == len(depth_gts) == len(scales)) or not outputs_list:
+        raise ValueError(f"{len(outputs_list)} renders for {len(depth_gts)} depth maps and {len(scales)} scales")
+    parts = [_depth_operands(o, gt, a) for o, gt, a in zip(outputs_list, depth_gts, scales)]
+    if any(p[1].shape != parts[0][1].shape for p in parts):
+        raise ValueError(f"a batch holds depth maps of one shape, got {sorted({tuple(p[1].shape) for p in parts})}")
+    flags = _l.METRICS_ALL & ~_l.METRICS_SSIM
+    pred = torch.stack([p[0].unsqueeze(-1) for p in parts])
+    target = torch.stack([p[1].to(torch.float32).unsqueeze(-1) for p in parts])
+    std = torch.stack([p[2] for p in parts])
+    mask = torch.stack([p[1] > 0 for p in parts])
+    rows = ops.image_metrics_batch(pred, target, std, mask, nll_min_sigma=min_depth_std_for_nll, flags=flags).cpu().numpy()
+    return _finish_rows(rows, image_ids, lambda row: M.finish_metrics(row, 1, "depth", flags, with_psnr=False))
 
 
 def _camera_size(camera) -> Tuple[int, int]:
@@ -189,7 +259,7 @@ def get_average_uncertainty_metrics(get_outputs_for_camera: Callable, eval_set: 
                                     eval_rgb_unc: bool = True, min_rgb_std_for_nll: float = 3e-2,
                                     composite_gt: Optional[Callable] = None, depth_gt_fn: Optional[Callable] = None,
                                     min_depth_std_for_nll: float = 1.0, fused: bool = False, view_batch: int = 1,
-                                    get_outputs_for_cameras: Optional[Callable] = None):
+                                    get_outputs_for_cameras: Optional[Callable] = None, metric_batch: bool = True):
     """eval_uncertainty.py:816-1079.  -> (averaged metrics dict, averaged curves dict).
     depth_gt_fn(image_index) -> (depth_gt [H,W], scale) switches the depth metrics on (eval_depth_unc).
     fused: the per-image metric stage through the HIP kernels (image_metrics_unc / depth_metrics_unc, fused=True).
@@ -197,7 +267,14 @@ def get_average_uncertainty_metrics(get_outputs_for_camera: Callable, eval_set: 
     get_outputs_for_cameras (`get_outputs_for_cameras=`, else the method of that name on the object
     get_outputs_for_camera is bound to) -- NeRF and splat models alike; a change of image size starts a new batch.  Same
     metric keys; a batch's render time is shared equally between its images for the three timing keys.  The default (1) is
-    the reference's per-camera loop."""
+    the reference's per-camera loop.
+    metric_batch (with fused and view_batch > 1): the images of a view batch are also SCORED together, by
+    image_metrics_unc_batch / depth_metrics_unc_batch in chunks of at most lib.METRICS_MAX_IMAGES -- the kernel launches
+    and the one host copy of a single image per chunk; where the depth GT maps of a chunk differ in shape its depth
+    metrics are scored image by image.  Every metric key and every curve is bit-equal to metric_batch=False (today's
+    per-image fused scoring, kept for comparison in one process); the three timing keys then share the batch's render
+    time AND its metric time equally between its images.  An image with a non-finite input raises as finish_metrics does,
+    named by its index in the eval set."""
     if view_batch < 1:
         raise ValueError(f"view_batch={view_batch}: at least 1")
     if view_batch > 1 and get_outputs_for_cameras is None:
@@ -211,21 +288,47 @@ def get_average_uncertainty_metrics(get_outputs_for_camera: Callable, eval_set: 
         if torch.cuda.is_available():
             torch.cuda.synchronize()
 
+    def record(md, curves, hw, render_s, metric_s):
+        H, W = hw
+        md["num_rays_per_sec"] = H * W / (render_s + metric_s)
+        md["fps"] = md["num_rays_per_sec"] / (H * W)
+        md["render_rays_per_sec"] = H * W / render_s
+        rows.append(md)
+        for k, v in curves.items():
+            sums[k] = sums.get(k, 0) + np.asarray(v, dtype=np.float64)
+
     def score(img_num, outputs, gt, render_s):
         start = time.time()
-        H, W = outputs["rgb"].shape[:2]
         md, curves = image_metrics_unc(outputs, gt, eval_rgb_unc, min_rgb_std_for_nll, composite_gt, fused=fused)
         if depth_gt_fn is not None:
             dgt, scale = depth_gt_fn(img_num)
             dmd, dcurves = depth_metrics_unc(outputs, dgt, scale, min_depth_std_for_nll, fused=fused)
             md.update(dmd)
             curves.update(dcurves)
-        md["num_rays_per_sec"] = H * W / (render_s + time.time() - start)
-        md["fps"] = md["num_rays_per_sec"] / (H * W)
-        md["render_rays_per_sec"] = H * W / render_s
-        rows.append(md)
-        for k, v in curves.items():
-            sums[k] = sums.get(k, 0) + np.asarray(v, dtype=np.float64)
+        record(md, curves, outputs["rgb"].shape[:2], render_s, time.time() - start)
+
+    def score_batch(pending, outs, render_share):
+        from . import lib as _l
+        start = time.time()
+        scored = []
+        for c0 in range(0, len(pending), _l.METRICS_MAX_IMAGES):
+            ids = [img_num for img_num, _, _ in pending[c0:c0 + _l.METRICS_MAX_IMAGES]]
+            chunk = outs[c0:c0 + len(ids)]
+            done = image_metrics_unc_batch(chunk, [gt for _, _, gt in pending[c0:c0 + len(ids)]], eval_rgb_unc, min_rgb_std_for_nll,
+                                           composite_gt, image_ids=ids)
+            if depth_gt_fn is not None:
+                dgts, scales = zip(*(depth_gt_fn(i) for i in ids))
+                if len({tuple(np.shape(d)) for d in dgts}) == 1:
+                    ddone = depth_metrics_unc_batch(chunk, dgts, scales, min_depth_std_for_nll, image_ids=ids)
+                else:       # maps of several shapes do not stack: this chunk's depth metrics image by image
+                    ddone = [depth_metrics_unc(o, d, a, min_depth_std_for_nll, fused=True) for o, d, a in zip(chunk, dgts, scales)]
+                for (md, curves), (dmd, dcurves) in zip(done, ddone):
+                    md.update(dmd)
+                    curves.update(dcurves)
+            scored += done
+        metric_share = (time.time() - start) / len(pending)
+        for (md, curves), outputs in zip(scored, outs):
+            record(md, curves, outputs["rgb"].shape[:2], render_share, metric_share)
 
     def flush(pending):     # [(image index, camera, gt)] of one image size
         if not pending:
@@ -234,6 +337,9 @@ def get_average_uncertainty_metrics(get_outputs_for_camera: Callable, eval_set: 
         outs = get_outputs_for_cameras(stack_cameras([cam for _, cam, _ in pending]))
         sync()
         share = (time.time() - start) / len(pending)
+        if fused and metric_batch:
+            score_batch(pending, list(outs), share)
+            return
         for (img_num, _, gt), outputs in zip(pending, outs):
             score(img_num, outputs, gt, share)
 
@@ -351,13 +457,15 @@ def outputs_fn_for(eval_config: EvalConfigs, model, ggn_batches=None, pipeline=N
 
 def run_eval(eval_config: EvalConfigs, model, eval_set, experiment_name: str = "", method_name: str = "",
              checkpoint: str = "", depth_gt_fn: Optional[Callable] = None, composite_gt: Optional[Callable] = None,
-             fused: bool = False, view_batch: int = 1, **fn_kw) -> Dict[str, float]:
+             fused: bool = False, view_batch: int = 1, metric_batch: bool = True, **fn_kw) -> Dict[str, float]:
     """main() of scripts/eval_uncertainty.py:1082-1169 without nerfstudio's pipeline loading: pick the method's
     callable, average the per-image metrics, write the metrics.json envelope to eval_config.output_path.
     fused=True computes the per-image metrics with the HIP kernels behind ops.image_metrics (same keys; opt-in).
     view_batch > 1 (MCDropoutConfig, ActiveNerfactoConfig, ActiveSplatfactoConfig): that many consecutive eval cameras of
     one size per model.get_outputs_for_cameras call (get_average_uncertainty_metrics); the Laplace and ensemble callables
-    render one camera per call whatever it is."""
+    render one camera per call whatever it is.
+    metric_batch (with fused=True and view_batch > 1): a view batch is also scored by one batched metric call
+    (get_average_uncertainty_metrics); False keeps the per-image fused scoring.  Same numbers either way."""
     fn = outputs_fn_for(eval_config, model, **fn_kw)
     batch_fn = None
     if view_batch > 1 and not isinstance(eval_config, (LaplaceConfig, EnsembleConfig)):
@@ -370,6 +478,6 @@ def run_eval(eval_config: EvalConfigs, model, eval_set, experiment_name: str = "
         fn, eval_set, eval_rgb_unc=eval_config.eval_rgb, min_rgb_std_for_nll=eval_config.min_rgb_std_for_nll,
         composite_gt=composite_gt, depth_gt_fn=depth_gt_fn if eval_config.eval_depth else None,
         min_depth_std_for_nll=eval_config.min_depth_std_for_nll, fused=fused,
-        view_batch=view_batch if batch_fn is not None else 1, get_outputs_for_cameras=batch_fn)
+        view_batch=view_batch if batch_fn is not None else 1, get_outputs_for_cameras=batch_fn, metric_batch=metric_batch)
     write_metrics_json(str(eval_config.output_path), experiment_name, method_name, checkpoint, metrics)
     return metrics

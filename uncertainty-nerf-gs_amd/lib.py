@@ -218,6 +218,9 @@ SIGNATURES = {
     "unerf_image_metrics_workspace_bytes": (C.c_size_t, [_i64]),
     "unerf_image_metrics": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i, _i, _f, _f, C.POINTER(C.c_double), _i, C.POINTER(C.c_double), _i,
                                  _i, _vp, C.c_size_t, _vp, _vp]),
+    "unerf_image_metrics_batch_workspace_bytes": (C.c_size_t, [_i64, _i]),
+    "unerf_image_metrics_batch": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i, _i, _i, _f, _f, C.POINTER(C.c_double), _i, C.POINTER(C.c_double),
+                                       _i, _i, _vp, C.c_size_t, _vp, _vp]),
     "unerf_splat_project": (_i, [_vp, _vp, _f, _vp, _fp, _f, _f, _f, _f, _i, _i, _i, _f, _i64, _vp, _vp, _vp, _vp,
                                  _vp, _vp, _vp, _vp]),
     "unerf_splat_project_raw": (_i, [_vp, _vp, _f, _vp, _fp, _f, _f, _f, _f, _i, _i, _i, _f, _i64, _vp, _i, _vp, _vp, _vp,
@@ -249,6 +252,7 @@ SIGNATURES = {
 METRICS_AUSE, METRICS_AUCE, METRICS_NLL, METRICS_SSIM = 1, 2, 4, 8
 METRICS_ALL = METRICS_AUSE | METRICS_AUCE | METRICS_NLL | METRICS_SSIM
 METRICS_AUCE_OFF, METRICS_AUSE_OFF, METRICS_ROW, METRICS_MAX_CUTS = 16, 144, 656, 128
+METRICS_MAX_IMAGES = 64                           # include/unerf.h: UNERF_METRICS_MAX_IMAGES (unerf_image_metrics_batch)
 SPLAT_MAX_VIEWS = 16                              # include/unerf.h: UNERF_SPLAT_MAX_VIEWS
 SPLAT_VIEW_FLOATS = 19                            # include/unerf.h: UNERF_SPLAT_VIEW_FLOATS
 SPLAT_BATCH_MAX_TILES = 11999                     # include/unerf.h: UNERF_SPLAT_BATCH_MAX_TILES

@@ -1364,6 +1364,48 @@ def image_metrics(pred: torch.Tensor, target: torch.Tensor, sigma: torch.Tensor,
     return out
 
 
+def image_metrics_batch(pred: torch.Tensor, target: torch.Tensor, sigma: torch.Tensor, mask: Optional[torch.Tensor] = None, *,
+                        image_hw: Optional[Tuple[int, int]] = None, clip_max: float = float("inf"), nll_min_sigma: float,
+                        flags: int, workspace: Optional[Workspace] = None, ratios=None, z=None) -> torch.Tensor:
+    """unerf_image_metrics_batch: B images of one size in one call.  pred / target [B, ..., C], sigma [B, ...], mask
+    [B, ...] (bool / uint8) or None, contiguous stacks -> the device tensor [B, lib.METRICS_ROW] float64 whose row b is,
+    bit for bit, the row image_metrics leaves for image b alone.  The launches of one image, whatever B is; asynchronous on
+    the current stream, no host synchronisation.  B <= lib.METRICS_MAX_IMAGES: a longer list is the caller's to chunk.
+    The other arguments are image_metrics's; workspace: scratch from that arena under its own name."""
+    import numpy as np
+    lib = _l.load()
+    if pred.dim() < 2 or sigma.dim() < 1:
+        raise _l.UnerfError(f"image_metrics_batch: pred {tuple(pred.shape)}, sigma {tuple(sigma.shape)}: expected [B, ..., C] and [B, ...]")
+    B, Cc = int(pred.shape[0]), int(pred.shape[-1])
+    if B < 1 or B > _l.METRICS_MAX_IMAGES:
+        raise _l.UnerfError(f"image_metrics_batch: B = {B} images (1..{_l.METRICS_MAX_IMAGES} per call)")
+    n = sigma.numel() // B
+    if sigma.shape[0] != B or pred.numel() != B * n * Cc or target.shape != pred.shape:
+        raise _l.UnerfError(f"image_metrics_batch: pred {tuple(pred.shape)}, target {tuple(target.shape)}, sigma {tuple(sigma.shape)}")
+    if mask is not None:
+        if mask.numel() != B * n or mask.shape[0] != B:
+            raise _l.UnerfError(f"image_metrics_batch: mask {tuple(mask.shape)} for {B} images of {n} pixels")
+        if mask.dtype == torch.bool:
+            mask = mask.view(torch.uint8)
+    H, W = (int(image_hw[0]), int(image_hw[1])) if image_hw is not None else (0, 0)
+    tr, tz = metric_tables()
+    ratios = tr if ratios is None else np.ascontiguousarray(ratios, dtype=np.float64)
+    z = tz if z is None else np.ascontiguousarray(z, dtype=np.float64)
+    dp = C.POINTER(C.c_double)
+    dev = pred.device
+    with _ctx(dev):
+        nbytes = lib.unerf_image_metrics_batch_workspace_bytes(n, B)
+        words = (nbytes + 7) // 8
+        ws = (workspace.get("image_metrics_batch", (words,), dev, dtype=torch.float64) if workspace is not None
+              else torch.empty(words, device=dev, dtype=torch.float64))
+        out = torch.zeros(B, _l.METRICS_ROW, device=dev, dtype=torch.float64)
+        _run("image_metrics_batch", lambda: lib.unerf_image_metrics_batch(
+            _p(pred, name="pred"), _p(target, name="target"), _p(sigma, name="sigma"), _p(mask, torch.uint8, "mask"), n, B, Cc, H, W,
+            float(clip_max), float(nll_min_sigma), ratios.ctypes.data_as(dp), int(ratios.size), z.ctypes.data_as(dp), int(z.size),
+            int(flags), _p(ws, torch.float64, "workspace"), nbytes, _p(out, torch.float64, "out"), _stream()))
+    return out
+
+
 # ---------------------------------------------------------------- splats ---------------
 
 def splat_project(means3d, scales, glob_scale: float, quats, viewmat: torch.Tensor, fx, fy, cx, cy, H: int, W: int,
