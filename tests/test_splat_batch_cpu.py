@@ -72,6 +72,12 @@ def test_count_and_sort_batch_argument_checks(lib):
     assert rc == -1 and b"view 1" in h.unerf_last_error()
     rc = h.unerf_splat_bin_sort_batch(*args(3, ok, H=2160, W=3840))
     assert rc == -1 and b"tiles" in h.unerf_last_error()
+    # UNERF_SPLAT_BATCH_MAX_TILES = 11,999: one tile more is refused by name, the limit itself gets past this check
+    rc = h.unerf_splat_bin_sort_batch(*args(3, ok, H=16, W=16 * 12000))
+    assert rc == -1 and b"12000 tiles" in h.unerf_last_error() and b"up to 11999" in h.unerf_last_error()
+    rc = h.unerf_splat_bin_sort_batch(1, 1, 1, 1, 3, 100, ok, 16, 16 * 11999, 16, None, None, 1, 1, 1, 0, None)
+    msg = h.unerf_last_error()      # (the size refusal itself, not the "tile tables ... workspace layout" one in front of it)
+    assert rc == -1 and b"workspace 0 <" in msg and b"unerf_splat_sort_workspace_bytes_batch" in msg, msg
     rc = h.unerf_splat_bin_sort_batch(1, 1, 1, 1, 3, 100, ok, 64, 64, 16, 1, None, 1, 1, 1, 1 << 30, None)
     assert rc == -1 and b"tight lists" in h.unerf_last_error()
 
