@@ -1,7 +1,8 @@
 """Several camera views per NeRF render call against a loop of single-view calls, on small frames.
 
-For active-nerfacto and nerfacto-mcdropout (K = 8, precision "f16", the bench headline's arithmetic) with full-size tables,
-and 16 cameras at each of --sizes: the 16 views rendered as a loop of render.render_camera and as ONE render.render_cameras
+For active-nerfacto and nerfacto-mcdropout (K = 8, precision "f16", the bench headline's arithmetic) -- and, with
+--methods laplace, nerfacto-laplace (100 + 100 sampled last-layer rows, a set per 32,768-ray eval chunk, precision "f16x2") --
+with full-size tables, and 16 cameras at each of --sizes: the 16 views rendered as a loop of render.render_camera and as ONE render.render_cameras
 call, both in this process, each form warmed up, the forms alternated pass by pass in the order loop, batch, loop -- the
 loop is measured TWICE so that its own run-to-run spread is on record next to the gain.  Wall time around each 16-view pass
 with the device synchronised in front and behind (host launch work counts: it is part of what a frame costs); as many
@@ -25,7 +26,18 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from uncertainty_nerf_gs_amd import lib, render, synthetic  # noqa: E402
 
-METHODS = {"active": ("active", {}), "mcdropout": ("mcdropout", dict(K=8, seed=1, p_drop=0.2))}
+METHODS = {"active": ("active", {}), "mcdropout": ("mcdropout", dict(K=8, seed=1, p_drop=0.2)), "laplace": ("laplace", {})}
+
+
+def laplace_scene(tensors, dev, rays_per_view, chunk_rays=1 << 15):
+    """per-chunk sample sets as the reference draws them: one set of 100 + 100 rows per eval chunk of a frame (both forms
+    render every view with these sets: the loop over this scene is what the batch is compared against)"""
+    n_sets = -(-rays_per_view // chunk_rays)
+    ws = [synthetic.laplace_weight_samples(tensors, seed=40 + i, n_samples=100) for i in range(n_sets)]
+    scene = synthetic.scene_to_device(tensors, dev, ws_density=torch.stack([w[0] for w in ws]).to(dev),
+                                      ws_rgb=torch.stack([w[1] for w in ws]).to(dev), lap_chunk_rays=chunk_rays)
+    scene.chunk_rays, scene.field.precision = chunk_rays, "f16x2"
+    return scene
 
 
 def main():
@@ -48,11 +60,15 @@ def main():
     rows = []
     for name in args.methods.split(","):
         kind, kw = METHODS[name]
-        scene = synthetic.scene_to_device(synthetic.make_scene_tensors(seed=0, kind=kind), dev, **kw)
+        tensors = synthetic.make_scene_tensors(seed=0, kind=kind)
+        scene = None if name == "laplace" else synthetic.scene_to_device(tensors, dev, **kw)
         if name == "mcdropout":
             scene.field.precision = "f16"
         for size in (int(s) for s in args.sizes.split(",")):
             H = W = size
+            if name == "laplace":       # the number of sets follows the frame size
+                scene = laplace_scene(tensors, dev, H * W)
+                assert render.view_batch_loop_reason(scene) is None
             f = 1111.0 * W / 1920
             cam = dict(fx=f, fy=f, cx=W / 2, cy=H / 2, H=H, W=W)
             use_seeds = seeds if name == "mcdropout" else None

@@ -562,7 +562,7 @@ int unerf_composite_moments_views(const float* density, const float* rgb, const 
  * Built for the frame kernels: ACTIVE and MCDROPOUT on the split-f16 / single-f16 matrix kernels (mfma16_blob; "f16x2" and
  * "f16"), nerfacto's widths, the default Dropout sites, ray-major outputs (packed_out or not).  ACTIVE, and MCDROPOUT
  * with K = 0 or p_drop = 0, have no per-view value and run the kernels of unerf_field_fwd.  Refused before any launch,
- * with a message that says so: LAPLACE, no mfma16_blob (the exact-fp32 and VALU kernels), the any-width kernel,
+ * with a message that says so: LAPLACE (its views form is unerf_field_fwd_laplace_views, below), no mfma16_blob (the exact-fp32 and VALU kernels), the any-width kernel,
  * sample_major planes, pre-gathered features, other drop_sites than TRUNK | HEAD1, and explicit keep masks (`masks`
  * is there to be refused by name: unerf_field_fwd_masked takes one frame, and nothing falls back to another kernel). */
 int unerf_field_fwd_views(const float* origins, const float* directions, const float* sbins, int64_t R, int S,
@@ -570,6 +570,40 @@ int unerf_field_fwd_views(const float* origins, const float* directions, const f
                           const unerf_field_params* p /* host struct */, const float* features /* must be NULL */,
                           float* density, float* rgb, float* aux, float* aux2,
                           const unerf_keep_masks* masks /* must be NULL */, void* stream);
+
+/* LAPLACE over several views.  The Laplace kernels number two more things by the ray's index inside its frame: the sample
+ * set of a ray (p->lap_chunk_rays rays per set) and the stream of its depth draws.  Next to unerf_ray_views (n_views,
+ * rays_per_view) the two entry points below take the per-view values of both: */
+typedef struct {            /* host struct */
+    int32_t set_base[UNERF_NERF_MAX_VIEWS];     /* first sample set of view v in the stacks of unerf_field_params */
+    uint32_t depth_seed[UNERF_NERF_MAX_VIEWS];  /* seed of view v's depth draws (unerf_laplace_depth_weights_views) */
+} unerf_laplace_views;
+
+/* unerf_field_fwd (LAPLACE, f16 matrix kernel) for several views: view v is rendered with the sets set_base[v] +
+ * local_ray / lap_chunk_rays (set_base[v] alone when lap_chunk_rays == 0: one set per view) of the stacks lap16_blob /
+ * ws_* [lap_sets, ...], i.e. what unerf_field_fwd(ray_offset = 0) computes for that view's rays with the stacks narrowed
+ * to its own sets, bit for bit.  The kernel lays its blocks of 32 rays out per view (ceil(rays_per_view / 32) blocks each),
+ * so a tile never straddles two views or two sets whatever rays_per_view is.  Outputs as unerf_field_fwd: dense, ray-major,
+ * row = launch row; aux = density variance, aux2 = colour variance; p->overflow_flag as there.
+ * Refused before any launch, with a message that says why: a bad view table, lap_views == NULL, a mode other than LAPLACE,
+ * no mfma16_blob or lap16_blob (the exact-fp32 and VALU kernels render one frame per call), the any-width kernel,
+ * sample_major, lap_chunk_rays < 0 or not a multiple of 32, set_base[v] < 0, set_base[v] + ceil(rays_per_view /
+ * lap_chunk_rays) > lap_sets (lap_chunk_rays == 0: set_base[v] >= max(lap_sets, 1)), rays_per_view * S >= 2^32.  There is no
+ * `features` argument: pre-gathered features have no LAPLACE form. */
+int unerf_field_fwd_laplace_views(const float* origins, const float* directions, const float* sbins, int64_t R, int S,
+                                  float near_plane, float far_plane, int spacing, const unerf_ray_views* views /* host struct */,
+                                  const unerf_laplace_views* lap_views /* host struct */,
+                                  const unerf_field_params* p /* host struct */, float* density, float* rgb, float* aux,
+                                  float* aux2, void* stream);
+
+/* unerf_laplace_depth_weights for several views: the draws of launch row r (view r / rays_per_view, frame-local ray r mod
+ * rays_per_view) are those of unerf_laplace_depth_weights(seed = depth_seed[view], ray_offset = 0) on that view's rows.
+ * noise != NULL: [D,R,S] explicit draws indexed by launch row -- no per-view value, the single call on the tall ray list.
+ * Same S range (1 to 256, ragged S included) as the single call. */
+int unerf_laplace_depth_weights_views(const float* density_mu, const float* density_var, const float* sbins, int64_t R, int S,
+                                      float near_plane, float far_plane, int spacing, const float* noise, int D,
+                                      const unerf_ray_views* views /* host struct */,
+                                      const unerf_laplace_views* lap_views /* host struct */, float* weights_out, void* stream);
 
 /* ------------------------------------------------------ moments over K --
  * Replaces torch.stack(...).mean(0) / .std(0) / .var(0) over MC passes

@@ -1348,13 +1348,10 @@ struct TileSample {
     float dx, dy, dz;
     float px, py, pz;
 };
-__device__ __forceinline__ TileSample tile_sample(const FieldArgs& a, uint32_t tile, const FastDiv& div_s, int j) {
+// (r: already clamped to a ray of the launch when !valid)
+__device__ __forceinline__ TileSample tile_sample_at(const FieldArgs& a, int64_t r, int s, bool valid) {
     TileSample t;
-    const uint32_t rb = fastdiv(tile, div_s);
-    const int s = (int)(tile - rb * (uint32_t)a.S);
-    int64_t r;
-    tile_ray(a, rb, j, r, t.valid);
-    if (!t.valid) r = a.R - 1;
+    t.valid = valid;
     t.n = r * a.S + s;
     t.r = r;
     t.s = s;
@@ -1368,6 +1365,15 @@ __device__ __forceinline__ TileSample tile_sample(const FieldArgs& a, uint32_t t
     t.py = a.origins[r * 3 + 1] + t.dy * t01 / 2.f;
     t.pz = a.origins[r * 3 + 2] + t.dz * t01 / 2.f;
     return t;
+}
+__device__ __forceinline__ TileSample tile_sample(const FieldArgs& a, uint32_t tile, const FastDiv& div_s, int j) {
+    const uint32_t rb = fastdiv(tile, div_s);
+    const int s = (int)(tile - rb * (uint32_t)a.S);
+    int64_t r;
+    bool valid;
+    tile_ray(a, rb, j, r, valid);
+    if (!valid) r = a.R - 1;
+    return tile_sample_at(a, r, s, valid);
 }
 
 // Where one (pass k, ray r, sample s) lands in the outputs.  Default (sample_major = 0): density [B,R,S], rgb [B,R,S,3],
@@ -1409,6 +1415,40 @@ __device__ __forceinline__ void store_packed(const FieldArgs& a, int k, int64_t 
 __device__ __forceinline__ const float* lap_set_blob(const FieldArgs& a, const float* blob, uint32_t tile, const FastDiv& div_s) {
     if (a.p.lap_chunk_rays == 0) return blob;
     const uint32_t set = fastdiv(a.chunk0 + fastdiv(tile, div_s) * 32u, a.div_chunk);
+    return blob + (size_t)set * UNERF_LAP_BLOB_FLOATS;
+}
+
+// SEVERAL VIEWS in one LAPLACE launch (unerf_field_fwd_laplace_views): a kernel argument of views_laplace_kernel_mfma16 only.
+// The ray blocks are laid out PER VIEW -- bpv = ceil(hw / 32) blocks each, block rb = view rb / bpv at frame-local rays
+// (rb % bpv) * 32 + [0, 32) -- so a tile never straddles two views, and inside its view it starts at a multiple of 32 as
+// the single-view tiles do: its sample set, set_base[view] + local / lap_chunk_rays, is uniform over the tile.  The columns
+// of a view's last block past hw are invalid (clamped, results dropped).
+struct LapViews {
+    FastDiv div_bpv;   // by ray blocks per view
+    uint32_t bpv;
+    uint32_t hw;       // rays per view
+    int32_t set_base[UNERF_NERF_MAX_VIEWS];   // first sample set of view v in the stacks (staged in LDS, read by view index)
+};
+__device__ __forceinline__ const LapViews& lv_of(const LapViews& x) { return x; }
+template <typename... XV> struct xv_is_lap_views : std::false_type {};
+template <> struct xv_is_lap_views<LapViews> : std::true_type {};
+__device__ __forceinline__ TileSample tile_sample_views(const FieldArgs& a, uint32_t tile, const FastDiv& div_s, int j, const LapViews& lv) {
+    const uint32_t rb = fastdiv(tile, div_s);
+    const int s = (int)(tile - rb * (uint32_t)a.S);
+    const uint32_t view = fastdiv(rb, lv.div_bpv);
+    uint32_t local = (rb - view * lv.bpv) * 32u + (uint32_t)j;
+    const bool valid = local < lv.hw;
+    if (!valid) local = lv.hw - 1u;
+    return tile_sample_at(a, (int64_t)view * lv.hw + local, s, valid);
+}
+// the blob of a tile's set; vsets = the LDS copy of lv.set_base.  `tile` is wave-uniform and so is everything here: the value
+// read from LDS is made a scalar again, so that the head operands keep their scalar base address
+__device__ __forceinline__ const float* lap_set_blob_views(const FieldArgs& a, const float* blob, uint32_t tile, const FastDiv& div_s,
+                                                           const LapViews& lv, const int32_t* vsets) {
+    const uint32_t rb = fastdiv(tile, div_s);
+    const uint32_t view = fastdiv(rb, lv.div_bpv);
+    uint32_t set = (uint32_t)__builtin_amdgcn_readfirstlane(vsets[view]);
+    if (a.p.lap_chunk_rays != 0) set += fastdiv((rb - view * lv.bpv) * 32u, a.div_chunk);
     return blob + (size_t)set * UNERF_LAP_BLOB_FLOATS;
 }
 
@@ -2994,160 +3034,17 @@ __device__ __forceinline__ void mf16_lap_stream(const float* __restrict__ lap, c
     }
 }
 
-template <int TCNN, bool F1 = false>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((F1 && !TCNN) ? 3 : 2))) void field_kernel_mfma16_laplace(FieldArgs a, uint32_t num_tiles, FastDiv div_s) {
-    extern __shared__ float lds[];
-    {
-        const float4* src = reinterpret_cast<const float4*>(a.p.mfma16_blob);
-        float4* dst = reinterpret_cast<float4*>(lds);
-        for (int i = threadIdx.x; i < UNERF_MFMA_BLOB_FLOATS / 4; i += 256) dst[i] = src[i];
-    }
-    __shared__ uint32_t s_tl[TCNN ? MF_TL_WORDS : 1];
-    // The bias rows of the sampled heads (16 per lane half and row block: the accumulators' initial values).  As global
-    // loads in front of every block's first MFMA they were the one load of the head loop whose latency nothing hid --
-    // 16 round trips to L2 per tile.  Each wave brings its tile's 512 words in with two 16-byte loads per lane while the
-    // hash grid is gathered, parks them in LDS, and the blocks read them back with ds_read_b128.
-    __shared__ float s_lbias[UNERF_LAP_BIAS_LDS && UNERF_LAP_PREFETCH >= 2 ? 4 : 1][UNERF_LAP_BIAS_LDS && UNERF_LAP_PREFETCH >= 2 ? 512 : 4];
-    if (TCNN) mf_stage_tcnn_levels<(TCNN == 2 ? 2 : 3)>(a, s_tl);
-    __syncthreads();
-    const int lane_c = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int j = lane_c & 31, h = lane_c >> 5;
-    const uint32_t mask = (1u << a.p.log2T) - 1u;
-    const float inv_n = 1.f / (float)a.p.n_lap, inv_nr = 1.f / (float)a.p.n_lap_rgb;
-    const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3, bpx = gridDim.x >> 3;
-    const uint32_t tpx = (num_tiles + 7u) / 8u;
-    const uint32_t tile_end = (xcd + 1) * tpx < num_tiles ? (xcd + 1) * tpx : num_tiles;
-    bool f1_bad = false;   // F1: a sampled-head mean of this lane came out inf / NaN
-    for (uint32_t tile = xcd * tpx + (uint32_t)slot * 4u + (uint32_t)wv; tile < tile_end; tile += (uint32_t)bpx * 4u) {
-        int lane = lane_c;
-        asm volatile("" : "+v"(lane));
-        const TileSample ts = tile_sample(a, tile, div_s, j);
-        const bool valid = ts.valid;
-        const int64_t n = ts.n;
-        const float dxr = ts.dx, dyr = ts.dy, dzr = ts.dz;
-        float px = ts.px, py = ts.py, pz = ts.pz;
-        // inference: the returned mu_d is NOT selector-masked (laplace_field.py:356-362) unless lap_mask_density
-        const float sel = unerf_normalize_position(px, py, pz, a.box);
-        constexpr bool BIAS_LDS = UNERF_LAP_BIAS_LDS && UNERF_LAP_PREFETCH >= 2 && !(F1 && !TCNN);
-        float4 lb0, lb1;
-        if (BIAS_LDS) {
-            const float4* lbsrc = reinterpret_cast<const float4*>(lap_set_blob(a, a.p.lap16_blob, tile, div_s) + LAP_BIAS_OFF) + lane_c * 2;
-            lb0 = lbsrc[0];
-            lb1 = lbsrc[1];
-        }
-        u32x8 feat_pk;
-        const f32x16 feat = mf_gather_feats<true, TCNN>(a, px, py, pz, h, mask, s_tl, &feat_pk);
-        if (BIAS_LDS) {   // (the previous tile's heads are done with the buffer: a wave's LDS operations execute in order)
-            float4* dst = reinterpret_cast<float4*>(s_lbias[wv]) + lane_c * 2;
-            dst[0] = lb0;
-            dst[1] = lb1;
-        }
-
-        const float* lap16 = lap_set_blob(a, a.p.lap16_blob, tile, div_s);
-        // (the single-product kernel at three waves per SIMD has no registers for a third operand buffer: it keeps the
-        // one-block-ahead heads)
-        constexpr bool STREAM = UNERF_LAP_PREFETCH >= 2 && !(F1 && !TCNN);
-        // base_mlp: bare Linear 32 -> 64 (no ReLU, utils.py:22-23)
-        f32x16 hb0 = mf16_bias(lds, 0, h), hb1 = mf16_bias(lds, 1, h);
-#pragma unroll
-        for (int st = 0; st < 2; ++st) {
-            f16x8 bhi, blo;
-            mf16_feat_operand<TCNN, F1>(feat, feat_pk, st, bhi, blo);
-            mf16_mac2<F1, TCNN == 2>(lds, 2 * st, 2 * st + 1, lane, bhi, blo, hb0, hb1);
-        }
-        // the 64 base outputs feed both mlp_hidden (geo) and the sampled density rows: split them once
-        f16x8 xhi[4], xlo[4];
-#pragma unroll
-        for (int st = 0; st < 4; ++st) mf16_split<F1>(st < 2 ? hb0 : hb1, st & 1, xhi[st], xlo[st]);
-        f32x16 t = mf16_bias(lds, 2, h);
-#pragma unroll
-        for (int st = 0; st < 4; ++st) t = mf16_mac<F1>(lds, 4 + st, lane, xhi[st], xlo[st], t);
-        float d1, d2;
-        if constexpr (STREAM) {
-            float ds1[1], ds2[1];
-            if (a.p.lap_softplus) mf16_lap_stream<2, F1, 1>(lap16, s_lbias[wv], 0, a.p.n_lap, lane, xhi, xlo, h, ds1, ds2);   // uniform
-            else mf16_lap_stream<0, F1, 1>(lap16, s_lbias[wv], 0, a.p.n_lap, lane, xhi, xlo, h, ds1, ds2);
-            d1 = ds1[0];
-            d2 = ds2[0];
-        } else {
-            if (a.p.lap_softplus) mf16_lap_head<2, F1>(lap16, 0, a.p.n_lap, lane, xhi, xlo, h, d1, d2);   // uniform
-            else mf16_lap_head<0, F1>(lap16, 0, a.p.n_lap, lane, xhi, xlo, h, d1, d2);
-        }
-        float mu_d = d1 * inv_n, mu2_d = d2 * inv_n;
-        if (a.p.lap_mask_density) {  // use_deterministic_density: selector-masked mean, no variance
-            mu_d *= sel;
-            mu2_d = mu_d * mu_d;
-        }
-
-        // colour trunk: [geo15 | SH16] -> 64 -> 64
-        f32x16 c0 = mf16_bias(lds, 3, h), c1 = mf16_bias(lds, 4, h);
-        {
-            f16x8 bhi, blo;
-            mf16_split<F1>(t, 0, bhi, blo);
-            mf16_mac2<F1>(lds, 8, 9, lane, bhi, blo, c0, c1);
-            float sh[16];
-            float ux = (dxr + 1.f) / 2.f, uy = (dyr + 1.f) / 2.f, uz = (dzr + 1.f) / 2.f;
-            if (a.p.sh_remap) {
-                ux = ux * 2.f - 1.f;
-                uy = uy * 2.f - 1.f;
-                uz = uz * 2.f - 1.f;
-            }
-            unerf_sh16(ux, uy, uz, sh);
-            const uint32_t hm = 0u - (uint32_t)h;
-            float mine[8];
-#pragma unroll
-            for (int q = 0; q < 8; ++q)
-                mine[q] = __uint_as_float((__float_as_uint(sh[8 + q]) & hm) | (__float_as_uint(sh[q]) & ~hm));
-            mf16_split8<F1>(mine, bhi, blo);
-            mf16_mac2<F1>(lds, 10, 11, lane, bhi, blo, c0, c1);
-        }
-        // (an overflowed operand of the split form makes every unit of the next layer NaN, which the integer-maximum ReLU
-        // may turn into 0: one accumulator per colour layer is tested first -- see field_kernel_mfma16)
-        if (!F1) f1_bad |= c0[0] != c0[0];
-        c0 = mf_relu(c0);
-        c1 = mf_relu(c1);
-        f32x16 x0 = mf16_bias(lds, 5, h), x1 = mf16_bias(lds, 6, h);
-        mf16_layer64<2, F1>(lds, 12, lane, c0, c1, x0, x1);
-        if (!F1) f1_bad |= x0[0] != x0[0];
-        x0 = mf_relu(x0);
-        x1 = mf_relu(x1);
-#pragma unroll
-        for (int st = 0; st < 4; ++st) mf16_split<F1>(st < 2 ? x0 : x1, st & 1, xhi[st], xlo[st]);
-        float mu_c[3], vsum = 0.f;
-        if constexpr (STREAM) {
-            float cs1[3], cs2[3];
-            mf16_lap_stream<1, F1, 3>(lap16, s_lbias[wv], 1, a.p.n_lap_rgb, lane, xhi, xlo, h, cs1, cs2);
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                mu_c[c] = cs1[c] * inv_nr;
-                vsum += fmaxf(cs2[c] * inv_nr - mu_c[c] * mu_c[c], 0.f);
-            }
-        } else {
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                float c1s, c2s;
-                mf16_lap_head<1, F1>(lap16, 1 + c, a.p.n_lap_rgb, lane, xhi, xlo, h, c1s, c2s);
-                mu_c[c] = c1s * inv_nr;
-                vsum += fmaxf(c2s * inv_nr - mu_c[c] * mu_c[c], 0.f);
-            }
-        }
-        // F1: an f16 operand beyond 65504 turns the sampled rows into +-inf / NaN; a density mean of +inf from a FINITE
-        // logit is not possible below e^88, so non-finite means are treated as operand overflow (see field_kernel_mfma16)
-        if (F1 && valid) f1_bad |= !(fabsf(mu_d) < INFINITY) | !(fabsf(mu_c[0] + mu_c[1] + mu_c[2]) < INFINITY);
-        if (valid && h == 0) {
-            a.density[n] = mu_d;
-            a.aux[n] = mu2_d - mu_d * mu_d;
-            a.aux2[n] = vsum / 3.f;
-            a.rgb[n * 3 + 0] = mu_c[0];
-            a.rgb[n * 3 + 1] = mu_c[1];
-            a.rgb[n * 3 + 2] = mu_c[2];
-        }
-    }
-    if (a.p.overflow_flag) {
-        const uint64_t m = __builtin_amdgcn_ballot_w64(f1_bad);
-        if (m != 0 && lane_c == (int)__builtin_ctzll(m)) atomicOr(a.p.overflow_flag, 1);
-    }
-}
+#define UNERF_LAP16_KERNEL field_kernel_mfma16_laplace
+#define UNERF_LAP16_VIEWS false
+#include "unerf_field_lap16.inc"
+#undef UNERF_LAP16_KERNEL
+#undef UNERF_LAP16_VIEWS
+// the same kernel under the name its several-views instantiations carry (unerf_field_fwd_laplace_views)
+#define UNERF_LAP16_KERNEL views_laplace_kernel_mfma16
+#define UNERF_LAP16_VIEWS true
+#include "unerf_field_lap16.inc"
+#undef UNERF_LAP16_KERNEL
+#undef UNERF_LAP16_VIEWS
 
 // --------------------------------------------------------------------------------------
 // 5c. level-major hash-grid gather.  One level of the main grid is 2^19 x 8 B = 4 MiB -- exactly
@@ -3557,7 +3454,7 @@ extern "C" int unerf_field_fwd_views(const float* origins, const float* directio
     UNERF_REQUIRE(p, "field_fwd_views: null params");
     if (int rc = check_views(views, R, "field_fwd_views")) return rc;
     UNERF_REQUIRE(p->mode == UNERF_FIELD_ACTIVE || p->mode == UNERF_FIELD_MCDROPOUT,
-                  "field_fwd_views: mode %d is not built for several views (ACTIVE / MCDROPOUT only; LAPLACE renders one frame per call)", p->mode);
+                  "field_fwd_views: mode %d is not built for several views (ACTIVE / MCDROPOUT only; LAPLACE renders one frame per call here: unerf_field_fwd_laplace_views)", p->mode);
     UNERF_REQUIRE(p->mfma16_blob, "field_fwd_views: built for the f16 matrix kernels (mfma16_blob, precision f16x2 / f16); the exact-fp32 "
                                   "and VALU kernels render one frame per call");
     UNERF_REQUIRE(!features, "field_fwd_views: pre-gathered features are not built for several views");
@@ -3589,6 +3486,64 @@ extern "C" int unerf_field_fwd_views(const float* origins, const float* directio
         field_launch(a, generic, nullptr, (hipStream_t)stream);
     }
     return unerf_check_launch("field_fwd_views");
+}
+
+// LAPLACE over several views: views_laplace_kernel_mfma16 with the ray blocks laid out per view (LapViews) and every view's
+// own run of sample sets.  Everything is refused before any launch; nothing falls back to another kernel.
+extern "C" int unerf_field_fwd_laplace_views(const float* origins, const float* directions, const float* sbins, int64_t R, int S,
+                                             float near_plane, float far_plane, int spacing, const unerf_ray_views* views,
+                                             const unerf_laplace_views* lap_views, const unerf_field_params* p, float* density,
+                                             float* rgb, float* aux, float* aux2, void* stream) {
+    UNERF_REQUIRE(p, "field_fwd_laplace_views: null params");
+    if (int rc = check_views(views, R, "field_fwd_laplace_views")) return rc;
+    UNERF_REQUIRE(lap_views, "field_fwd_laplace_views: null lap_views (the sample-set base of every view)");
+    UNERF_REQUIRE(p->mode == UNERF_FIELD_LAPLACE, "field_fwd_laplace_views: mode %d is not LAPLACE (ACTIVE / MCDROPOUT: unerf_field_fwd_views)", p->mode);
+    UNERF_REQUIRE(p->mfma16_blob && p->lap16_blob, "field_fwd_laplace_views: built for the f16 matrix kernel (mfma16_blob and lap16_blob, precision "
+                                                   "f16x2 / f16); the exact-fp32 and VALU kernels render one frame per call");
+    FieldArgs a;
+    a.origins = origins; a.dirs = directions; a.sbins = sbins; a.R = R; a.S = S; a.ray_offset = 0;
+    a.p = *p; a.density = density; a.rgb = rgb; a.aux = aux; a.aux2 = aux2; a.features = nullptr;
+    const bool generic = field_set_widths(a.p);
+    UNERF_REQUIRE(!generic, "field_fwd_laplace_views: the any-width kernel is not built for several views (nerfacto widths 64 / 64 / 15 / 2, L = 16)");
+    UNERF_REQUIRE(!p->sample_major, "field_fwd_laplace_views: sample_major planes are not built for several views");
+    const int64_t hw = views->rays_per_view, cr = p->lap_chunk_rays;
+    UNERF_REQUIRE(cr >= 0 && cr % 32 == 0, "field_fwd_laplace_views: lap_chunk_rays=%d must be 0 or a positive multiple of 32 (a tile of 32 rays has one sample set)",
+                  p->lap_chunk_rays);
+    const int64_t spv = cr ? (hw + cr - 1) / cr : 1, sets = p->lap_sets > 1 ? p->lap_sets : 1;   // sets per view, sets in the stacks
+    for (int v = 0; v < views->n_views; ++v) {
+        const int64_t b = lap_views->set_base[v];
+        UNERF_REQUIRE(b >= 0, "field_fwd_laplace_views: set_base[%d]=%lld is negative", v, (long long)b);
+        UNERF_REQUIRE(b + spv <= sets, "field_fwd_laplace_views: view %d reads sample sets [%lld, %lld) of %lld (set_base[%d] + sets per view > lap_sets)", v,
+                      (long long)b, (long long)(b + spv), (long long)sets, v);
+    }
+    UNERF_REQUIRE((uint64_t)hw * (uint64_t)S < (1ull << 32), "field_fwd_laplace_views: sample index of a view exceeds 32 bits (rays_per_view x S)");
+    UNERF_REQUIRE(p->n_lap >= 1 && p->n_lap <= 32 * LAP_BLOCKS, "field_fwd_laplace_views: n_lap=%d rows do not fit the head blobs (1 to %d)", p->n_lap,
+                  32 * LAP_BLOCKS);
+    const int64_t bpv = (hw + 31) / 32, tiles = (int64_t)views->n_views * bpv * (int64_t)S;
+    UNERF_REQUIRE(S >= 1 && tiles < (1ll << 31), "field_fwd_laplace_views: %lld tiles in one launch (32-bit tile index)", (long long)tiles);
+    UNERF_REQUIRE(origins && directions && sbins && density && rgb, "field_fwd_laplace_views: null pointer");
+    // the single-view checks see one view: the sample counter bound and the reach into the sets are per view here (above)
+    FieldArgs one = a;
+    one.R = hw;
+    one.p.lap_chunk_rays = 0;
+    if (int rc = field_check_args(one, near_plane, generic, nullptr)) return rc;
+    field_fill_args(a, near_plane, far_plane, spacing, nullptr);
+    one = a;
+    one.R = hw;
+    one.p.lap_chunk_rays = 0;
+    if (int rc = field_check_nonempty(one, spacing, generic)) return rc;
+    (void)make_tiles(a, 0);   // 1-D tiles: a.tm says "no image width"
+    LapViews lv;
+    lv.div_bpv = make_fastdiv((uint32_t)bpv); lv.bpv = (uint32_t)bpv; lv.hw = (uint32_t)hw;
+    for (int v = 0; v < UNERF_NERF_MAX_VIEWS; ++v) lv.set_base[v] = lap_views->set_base[v < views->n_views ? v : 0];
+    with_int3(tcnn_arg(a.p), [&](auto tc) {
+        with_bool(a.p.f16_single != 0, [&](auto f1) {
+            const auto kernel = views_laplace_kernel_mfma16<decltype(tc)::value, decltype(f1)::value, LapViews>;
+            hipLaunchKernelGGL(kernel, dim3(mfma_grid_for(kernel, tiles, MF_LDS_BYTES)), dim3(256), MF_LDS_BYTES, (hipStream_t)stream, a,
+                               (uint32_t)tiles, make_fastdiv((uint32_t)a.S), lv);
+        });
+    });
+    return unerf_check_launch("field_fwd_laplace_views");
 }
 
 // --------------------------------------------------------------------------------------
@@ -4528,13 +4483,31 @@ __device__ __forceinline__ void group_weights_accumulate(const float (&z)[SPL], 
     for (int e = 0; e < SPL; ++e) wsum[e] = fmaf(carry, dl[e], wsum[e]);
 }
 
-template <int SPL, bool RAGGED = false>
-__global__ __launch_bounds__(256) void lap_depth_kernel(LapDepthArgs a) {
+// SEVERAL VIEWS (unerf_laplace_depth_weights_views): a kernel argument of lap_depth_kernel_views only.  Launch row r is
+// frame-local ray r mod hw of view r / hw; its streams are seeded inside its own frame under its view's seed.
+struct LapDepthViews {
+    FastDiv div_hw;   // by rays per view
+    uint32_t hw;
+    uint32_t seed[UNERF_NERF_MAX_VIEWS];   // staged in LDS, read by view index (a block of 16 rays straddles views)
+};
+__device__ __forceinline__ const LapDepthViews& lap_depth_views_of(const LapDepthViews& x) { return x; }
+template <int SPL, bool RAGGED = false, typename... VW>   // VW = LapDepthViews (unerf_laplace_depth_weights_views), else none
+__global__ __launch_bounds__(256) void lap_depth_kernel(LapDepthArgs a, VW... vw) {
     const int l16 = threadIdx.x & 15;
     int64_t r = (int64_t)blockIdx.x * 16 + (threadIdx.x >> 4);
     const bool ok = r < a.R;
     if (!ok) r = a.R - 1;
     const int S = a.S, k0 = l16 * SPL;
+    uint32_t vseed = 0u, vlocal = 0u;   // VW: the seed of this group's view and its ray inside the view's frame
+    if constexpr (sizeof...(VW) != 0) {
+        __shared__ uint32_t s_seed[UNERF_NERF_MAX_VIEWS];
+        const LapDepthViews& dv = lap_depth_views_of(vw...);
+        if (threadIdx.x < UNERF_NERF_MAX_VIEWS) s_seed[threadIdx.x] = dv.seed[threadIdx.x];
+        __syncthreads();
+        const uint32_t view = fastdiv((uint32_t)r, dv.div_hw);
+        vseed = s_seed[view];
+        vlocal = (uint32_t)r - view * dv.hw;
+    }
     const float* sb = a.sbins + r * (S + 1);
     float eu[SPL + 1], ca[SPL], cb[SPL], wsum[SPL];
     uint32_t st[SPL];
@@ -4550,7 +4523,8 @@ __global__ __launch_bounds__(256) void lap_depth_kernel(LapDepthArgs a) {
         ca[e] = nd2 * sd;
         cb[e] = nd2 * mu;
         wsum[e] = 0.f;
-        st[e] = a.noise ? 0u : unerf_depth_stream_seed(a.seed, (uint32_t)((a.ray_offset + r) * S + k0 + e));
+        if constexpr (sizeof...(VW) != 0) st[e] = a.noise ? 0u : unerf_depth_stream_seed(vseed, (uint32_t)((int64_t)vlocal * S + k0 + e));
+        else st[e] = a.noise ? 0u : unerf_depth_stream_seed(a.seed, (uint32_t)((a.ray_offset + r) * S + k0 + e));
     }
     for (int d0 = 0; d0 < a.D; d0 += 2) {
         float z[2][SPL];
@@ -4579,6 +4553,9 @@ __global__ __launch_bounds__(256) void lap_depth_kernel(LapDepthArgs a) {
         }
     }
 }
+// the several-views instantiations under a name of two template arguments (UNERF_DISPATCH_SPL)
+template <int SPL, bool RAGGED = false>
+constexpr auto lap_depth_kernel_views = lap_depth_kernel<SPL, RAGGED, LapDepthViews>;
 
 extern "C" int unerf_laplace_depth_weights(const float* density_mu, const float* density_var, const float* sbins,
                                            int64_t R, int S, float near_plane, float far_plane, int spacing, const float* noise,
@@ -4594,6 +4571,30 @@ extern "C" int unerf_laplace_depth_weights(const float* density_mu, const float*
     hipStream_t st = (hipStream_t)stream;
     UNERF_DISPATCH_SPL(S, lap_depth_kernel, grid, block, 0, st, a);
     return unerf_check_launch("laplace_depth_weights");
+}
+
+// Several views in one launch: the stream of launch row r, sample k is seeded by (depth_seed[view], local * S + k), i.e. what
+// unerf_laplace_depth_weights(seed = depth_seed[view], ray_offset = 0) draws for that view alone.  With explicit `noise` there
+// is no per-view value: rows are launch rows, as in the single call on the tall ray list.
+extern "C" int unerf_laplace_depth_weights_views(const float* density_mu, const float* density_var, const float* sbins,
+                                                 int64_t R, int S, float near_plane, float far_plane, int spacing, const float* noise,
+                                                 int D, const unerf_ray_views* views, const unerf_laplace_views* lap_views,
+                                                 float* weights_out, void* stream) {
+    if (int rc = check_views(views, R, "laplace_depth_weights_views")) return rc;
+    UNERF_REQUIRE(lap_views, "laplace_depth_weights_views: null lap_views (the depth seed of every view)");
+    UNERF_REQUIRE(density_mu && density_var && sbins && weights_out, "laplace_depth_weights_views: null pointer");
+    UNERF_REQUIRE(D >= 1 && S >= 1 && S <= 256, "laplace_depth_weights_views: bad D/S");
+    LapDepthArgs a;
+    a.mu = density_mu; a.var = density_var; a.sbins = sbins; a.R = R; a.S = S;
+    UNERF_REQUIRE_SPACING(spacing); a.lin = spacing; a.s_near = unerf_spacing_of(near_plane, spacing); a.s_far = unerf_spacing_of(far_plane, spacing);
+    a.noise = noise; a.D = D; a.seed = 0u; a.ray_offset = 0; a.out = weights_out;
+    LapDepthViews dv;
+    dv.div_hw = make_fastdiv((uint32_t)views->rays_per_view); dv.hw = (uint32_t)views->rays_per_view;
+    for (int v = 0; v < UNERF_NERF_MAX_VIEWS; ++v) dv.seed[v] = lap_views->depth_seed[v < views->n_views ? v : 0];
+    dim3 grid(blocks_for(R, 16)), block(256);
+    hipStream_t st = (hipStream_t)stream;
+    UNERF_DISPATCH_SPL(S, lap_depth_kernel_views, grid, block, 0, st, a, dv);
+    return unerf_check_launch("laplace_depth_weights_views");
 }
 
 // ======================================================================================

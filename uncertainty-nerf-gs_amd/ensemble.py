@@ -215,6 +215,25 @@ class EnsemblePipeline:
         return aggregate(outs, moments_fn=self.moments_fn)
 
 
+    @torch.no_grad()
+    def get_ensemble_outputs_for_cameras(self, cameras, obb_box=None, max_views: int = 16) -> List[Dict[str, torch.Tensor]]:
+        """get_ensemble_outputs_for_camera_ray_bundle for every camera of a batch of one image size (the argument
+        conventions of the members' get_outputs_for_cameras): each member renders the whole batch through its own
+        get_outputs_for_cameras -- up to max_views small frames per launch group --, then the moments run per view.
+        Element v equals the per-camera call for camera v."""
+        kw = {} if obb_box is None else {"obb_box": obb_box}
+        per_member = [m.get_outputs_for_cameras(cameras, max_views=max_views, **kw) for m in self.models]
+        res = []
+        for v in range(len(per_member[0])):
+            outs = [pm[v] for pm in per_member]
+            if self._distributed():
+                res.append(aggregate_distributed(outs, group=self.group, moments_fn=self.moments_fn))
+            else:
+                assert len(outs) > 1, "Ensemble requires at least two models."
+                res.append(aggregate(outs, moments_fn=self.moments_fn))
+        return res
+
+
 def views_for_rank(num_views: int, rank: int, world: int) -> List[int]:
     """View-batch data parallelism for splats / single models: replicas of the scene,
     disjoint cameras per rank, no data-path collective."""

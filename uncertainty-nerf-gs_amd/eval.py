@@ -461,14 +461,22 @@ def run_eval(eval_config: EvalConfigs, model, eval_set, experiment_name: str = "
     """main() of scripts/eval_uncertainty.py:1082-1169 without nerfstudio's pipeline loading: pick the method's
     callable, average the per-image metrics, write the metrics.json envelope to eval_config.output_path.
     fused=True computes the per-image metrics with the HIP kernels behind ops.image_metrics (same keys; opt-in).
-    view_batch > 1 (MCDropoutConfig, ActiveNerfactoConfig, ActiveSplatfactoConfig): that many consecutive eval cameras of
-    one size per model.get_outputs_for_cameras call (get_average_uncertainty_metrics); the Laplace and ensemble callables
-    render one camera per call whatever it is.
+    view_batch > 1: that many consecutive eval cameras of one size per call of the method's batch callable
+    (get_average_uncertainty_metrics) -- model.get_outputs_for_cameras; for LaplaceConfig
+    model.get_outputs_for_cameras_unc with the keyword arguments of the per-camera callable (the last-layer samples are
+    drawn in the per-camera order, so the metrics are those of view_batch = 1 under the same generator state); for
+    EnsembleConfig EnsemblePipeline.get_ensemble_outputs_for_cameras (every member renders the batch, the moments run
+    per view).
     metric_batch (with fused=True and view_batch > 1): a view batch is also scored by one batched metric call
     (get_average_uncertainty_metrics); False keeps the per-image fused scoring.  Same numbers either way."""
     fn = outputs_fn_for(eval_config, model, **fn_kw)
     batch_fn = None
-    if view_batch > 1 and not isinstance(eval_config, (LaplaceConfig, EnsembleConfig)):
+    if view_batch > 1 and isinstance(eval_config, LaplaceConfig):
+        if hasattr(model, "get_outputs_for_cameras_unc"):
+            batch_fn = partial(model.get_outputs_for_cameras_unc, **fn.keywords)
+    elif view_batch > 1 and isinstance(eval_config, EnsembleConfig):
+        batch_fn = getattr(getattr(fn, "__self__", None), "get_ensemble_outputs_for_cameras", None)
+    elif view_batch > 1:
         batch_fn = getattr(model, "get_outputs_for_cameras", None)
     if composite_gt is None and hasattr(model, "composite_gt"):   # splat models: GT alpha over the background
         composite_gt = model.composite_gt

@@ -17,8 +17,8 @@ INCLUDE = os.path.join(os.path.dirname(_HERE), "include")
 # UNERF_LIB: another build of the same ABI, for A/B timing on one box (benchmarks/ab_bench.sh); unset in normal use
 LIB_PATH = os.environ.get("UNERF_LIB") or os.path.join(CSRC, "libunerf.so")
 SOURCES = ["unerf_nerf.hip", "unerf_splat.hip", "unerf_metrics.hip"]
-# text included by the sources (unerf_nerf.hip compiles the f16 matrix field kernel from unerf_field_mfma16.inc under two names)
-INCLUDED = ["unerf_common.hpp", "unerf_field_mfma16.inc"]
+# text included by the sources (unerf_nerf.hip compiles the f16 matrix field kernels from the two .inc files under two names each)
+INCLUDED = ["unerf_common.hpp", "unerf_field_mfma16.inc", "unerf_field_lap16.inc"]
 # -amdgpu-mfma-vgpr-form: gfx950 has one unified register file; let the MFMAs write their accumulators to
 # ordinary VGPRs so ReLU / dropout / the next layer's B operand read them without v_accvgpr_read copies
 # (97 copies per tile in the K-pass kernel, which is VALU-issue-bound; rocprof r1_04).
@@ -154,6 +154,11 @@ class RayViews(C.Structure):
     _fields_ = [("n_views", C.c_int32), ("rays_per_view", C.c_int64), ("seed", C.c_uint32 * NERF_MAX_VIEWS)]
 
 
+class LaplaceViews(C.Structure):
+    """include/unerf.h: unerf_laplace_views (per-view sample-set base and depth seed of the LAPLACE *_views entry points)"""
+    _fields_ = [("set_base", C.c_int32 * NERF_MAX_VIEWS), ("depth_seed", C.c_uint32 * NERF_MAX_VIEWS)]
+
+
 class RayCamera(C.Structure):
     """include/unerf.h: unerf_ray_camera (one camera of unerf_generate_rays_views)"""
     _fields_ = [("c2w", C.c_float * 12), ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float),
@@ -214,6 +219,10 @@ SIGNATURES = {
                                            _vp, _vp, _vp]),
     "unerf_field_fwd_views": (_i, [_vp, _vp, _vp, _i64, _i, _f, _f, _i, C.POINTER(RayViews), C.POINTER(FieldParams), _vp, _vp, _vp,
                                    _vp, _vp, C.POINTER(KeepMasks), _vp]),
+    "unerf_field_fwd_laplace_views": (_i, [_vp, _vp, _vp, _i64, _i, _f, _f, _i, C.POINTER(RayViews), C.POINTER(LaplaceViews),
+                                           C.POINTER(FieldParams), _vp, _vp, _vp, _vp, _vp]),
+    "unerf_laplace_depth_weights_views": (_i, [_vp, _vp, _vp, _i64, _i, _f, _f, _i, _vp, _i, C.POINTER(RayViews),
+                                               C.POINTER(LaplaceViews), _vp, _vp]),
     "unerf_moments": (_i, [_vp, _i, _i64, _i, _vp, _vp, _vp]),
     "unerf_image_metrics_workspace_bytes": (C.c_size_t, [_i64]),
     "unerf_image_metrics": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i, _i, _f, _f, C.POINTER(C.c_double), _i, C.POINTER(C.c_double), _i,

@@ -731,6 +731,8 @@ class NerfactoLaplaceModel(_NerfactoBase):
         return "f16x2"
 
     _ws = None                       # sampled last layers of the current *_unc call; None: the mean heads
+    _ws_per_chunk = True             # a stack [sets, n, P] in _ws holds one set per eval chunk (False: one per camera)
+    _view_sets: Optional[List[int]] = None     # get_outputs_for_cameras_unc: first sample set of every camera of the batch
     _deterministic_density = False
 
     def _field_to_device(self, device):
@@ -743,8 +745,11 @@ class NerfactoLaplaceModel(_NerfactoBase):
             ws_r = parameters_to_vector(self.field.mlp_rgb_ll.parameters()).detach().reshape(1, -1)
             return self.field.to_device(device, ws_density=ws_d, ws_rgb=ws_r, lap_mask_density=1)
         ws_d, ws_r = self._ws
-        return self.field.to_device(device, ws_density=ws_d, ws_rgb=ws_r, lap_mask_density=int(self._deterministic_density),
-                                    lap_chunk_rays=int(self.config.eval_num_rays_per_chunk) if ws_d.dim() == 3 else 0)
+        fd = self.field.to_device(device, ws_density=ws_d, ws_rgb=ws_r, lap_mask_density=int(self._deterministic_density),
+                                  lap_chunk_rays=int(self.config.eval_num_rays_per_chunk) if ws_d.dim() == 3 else 0)
+        if ws_d.dim() == 3 and not self._ws_per_chunk:
+            fd.lap_chunk_rays = 0      # get_outputs_for_cameras_unc, one set per camera: the stack is indexed by view alone
+        return fd
 
     @torch.no_grad()
     def get_outputs_for_camera(self, camera, obb_box=None):
@@ -755,7 +760,65 @@ class NerfactoLaplaceModel(_NerfactoBase):
         return super().get_outputs_for_camera(camera, obb_box)
 
     def _begin_render_views(self, scene: NerfSceneDev, n_views: int) -> Tuple[bool, Optional[List[int]]]:
-        return False, None      # the Laplace kernels take one frame per call (per-chunk sample sets): camera by camera
+        return True, None       # no mask seeds; the per-view sample sets travel in _render_kwargs
+
+    @torch.no_grad()
+    def get_outputs_for_cameras(self, cameras, obb_box=None, max_views: int = 16):
+        """the plain (deterministic, mean-head) render of every camera unless called through get_outputs_for_cameras_unc"""
+        if not getattr(self, "_in_unc_call", False) and self._ws is not None:
+            self._ws, self._deterministic_density = None, False
+            self.invalidate()
+        return super().get_outputs_for_cameras(cameras, obb_box, max_views)
+
+    @torch.no_grad()
+    def get_outputs_for_cameras_unc(self, cameras, obb_box=None, is_inference: bool = True,
+                                    use_deterministic_density: bool = False, prior_prec: float = 1.0,
+                                    n_samples: int = 100, eps: float = 1e-9, generator=None, max_views: int = 16):
+        """get_outputs_for_camera_unc for every camera of a batch (argument conventions of get_outputs_for_cameras).  Element
+        v equals the v-th of B successive get_outputs_for_camera_unc calls bit for bit, and the generator is left as after
+        those calls: for every max_views cameras the sets of those cameras are drawn in the loop's order (camera by camera,
+        chunk by chunk, density then colour: field.sample_last_layers(n_sets=...)), stacked into one device field, and the
+        cameras rendered with set_base[v] = v * sets per camera (render.render_cameras: lap_view_sets)."""
+        if not is_inference:
+            raise NotImplementedError("is_inference=False is the training forward (used by compute_hessian_naive only)")
+        if self.resample not in ("chunk", "camera"):
+            raise ValueError(f"NerfactoLaplaceModel.resample={self.resample!r}: expected 'chunk' or 'camera'")
+        if not 1 <= max_views <= _lib.NERF_MAX_VIEWS:
+            raise ValueError(f"max_views={max_views}: a launch group holds 1 to {_lib.NERF_MAX_VIEWS} cameras")
+        _, H, W, singles = _camera_batch(cameras)
+        for cam in singles:
+            _camera_args(cam)
+        per_chunk = self.resample == "chunk"
+        chunk = int(self.config.eval_num_rays_per_chunk)
+        from .eval import stack_cameras
+        outs: List[Dict[str, torch.Tensor]] = []
+        for v0 in range(0, len(singles), max_views):
+            part = singles[v0:v0 + max_views]
+            spv = 1
+            if per_chunk:
+                if chunk <= 0 or chunk % 32:
+                    import warnings
+                    for _ in part:      # (one warning per camera, as the loop gives)
+                        warnings.warn(f"eval_num_rays_per_chunk={chunk} is not a multiple of 32: per-chunk Laplace sample sets need "
+                                      "that; rendering this frame with one set (model.resample = 'camera')")
+                    per_chunk = False
+                else:
+                    spv = -(-(H * W) // chunk)
+            self._ws = self.field.sample_last_layers(n_samples=n_samples, prior_prec=prior_prec, eps=eps, generator=generator,
+                                                     deterministic_density=use_deterministic_density, n_sets=len(part) * spv)
+            self._ws_per_chunk = per_chunk
+            self._view_sets = [i * spv for i in range(len(part))]
+            self._deterministic_density = bool(use_deterministic_density)
+            self.invalidate()
+            self._in_unc_call = True
+            try:
+                outs.extend(self.get_outputs_for_cameras(stack_cameras(part), obb_box, max_views))
+            finally:
+                self._in_unc_call = False
+                self._ws, self._deterministic_density, self._view_sets = None, False, None
+                self._ws_per_chunk = True
+                self.invalidate()
+        return outs
 
     @torch.no_grad()
     def get_outputs_for_camera_unc(self, camera, obb_box=None, is_inference: bool = True,
@@ -796,7 +859,10 @@ class NerfactoLaplaceModel(_NerfactoBase):
             self.invalidate()
 
     def _render_kwargs(self):
-        return {"depth_draws": 100, "depth_seed": self.depth_seed}  # num_samples = 100 (laplace_model.py:487)
+        kw = {"depth_draws": 100, "depth_seed": self.depth_seed}  # num_samples = 100 (laplace_model.py:487)
+        if self._view_sets is not None:     # inside get_outputs_for_cameras_unc (render.render_cameras)
+            kw["lap_view_sets"] = list(self._view_sets)
+        return kw
 
     @torch.no_grad()
     def compute_hessian_naive(self, pipeline=None, n_iters: int = 1000, ray_batches=None, device=None):

@@ -838,6 +838,49 @@ class RayViews:
         return cs
 
 
+@dataclass
+class LaplaceViews:
+    """The per-view values of a LAPLACE launch over several views (include/unerf.h: unerf_laplace_views), next to RayViews:
+    set_base[v] = the first sample set of view v in the field's stacks (ws_* / lap16_blob [sets, ...]; None = 0 for every
+    view: the field's own sets, what a loop over the same field renders), depth_seeds[v] = the seed of its depth draws
+    (None = `default_seed` of cstruct for every view)."""
+    set_base: Optional[Tuple[int, ...]] = None
+    depth_seeds: Optional[Tuple[int, ...]] = None
+
+    def cstruct(self, n_views: int, default_seed: int = 0) -> _l.LaplaceViews:
+        cs = _l.LaplaceViews()
+        for name, vals in (("set_base", self.set_base), ("depth_seeds", self.depth_seeds)):
+            if vals is not None and (len(vals) != n_views or len(vals) > _l.NERF_MAX_VIEWS):
+                raise _l.UnerfError(f"LaplaceViews: {len(vals)} {name} for {n_views} views (at most {_l.NERF_MAX_VIEWS})")
+        for i in range(min(max(int(n_views), 0), _l.NERF_MAX_VIEWS)):
+            cs.set_base[i] = 0 if self.set_base is None else int(self.set_base[i])
+            cs.depth_seed[i] = (default_seed if self.depth_seeds is None else int(self.depth_seeds[i])) & 0xFFFFFFFF
+        return cs
+
+
+def laplace_sets_per_view(field: "FieldDev", rays_per_view: int) -> int:
+    """sample sets a view of rays_per_view rays reads: ceil(rays / lap_chunk_rays) with per-chunk sets, else 1"""
+    stacked = field.ws_density is not None and field.ws_density.dim() == 3
+    cr = int(field.lap_chunk_rays) if stacked else 0
+    return (int(rays_per_view) + cr - 1) // cr if cr > 0 else 1
+
+
+def laplace_sets_view(field: "FieldDev", base: int, count: int) -> "FieldDev":
+    """The LAPLACE field with its stacks of sample sets narrowed to sets [base, base + count): what view v of a
+    several-views call with set_base[v] = base is rendered with (no copy: slices of the stacks).  A field with one set
+    ([n, P] rows) has nothing to narrow and takes base = 0 only."""
+    import dataclasses
+    if field.ws_density is None or field.ws_density.dim() != 3:
+        if base != 0:
+            raise _l.UnerfError(f"laplace_sets_view: set {base} of a field with one sample set")
+        return field
+    if base < 0 or count < 1 or base + count > field.ws_density.shape[0]:
+        raise _l.UnerfError(f"laplace_sets_view: sets [{base}, {base + count}) of {field.ws_density.shape[0]}")
+    cut = lambda t: None if t is None else t[base:base + count]
+    return dataclasses.replace(field, ws_density=cut(field.ws_density), ws_rgb=cut(field.ws_rgb), lap_blob=cut(field.lap_blob),
+                               lap16_blob=cut(field.lap16_blob))
+
+
 def clip_rows_per_view(rays_per_view: int, chunk_rays: int) -> int:
     """rows of the clip buffer each view owns: view v's chunk c is row v * clip_rows_per_view + c"""
     return (int(rays_per_view) + int(chunk_rays) - 1) // int(chunk_rays)
@@ -1090,7 +1133,7 @@ def field_fwd(origins, directions, sbins, field: FieldDev, near: float, far: flo
               features: Optional[torch.Tensor] = None, image_width: int = 0, euclidean_bins: bool = False,
               sample_major: bool = False, spacing: int = 0, nonfinite_flag: Optional[torch.Tensor] = None,
               packed: bool = False, workspace: Optional[Workspace] = None, keep_masks: Optional[KeepMasks] = None,
-              views: Optional[RayViews] = None):
+              views: Optional[RayViews] = None, lap_views: Optional[LaplaceViews] = None):
     """-> density [B,R,S], rgb [B,R,S,3], aux, aux2 (see include/unerf.h).  image_width > 0 tells the kernel that
     rays [ray_offset, ray_offset+R) are consecutive pixels of a row-major image (8x4-pixel tiles: same results).
     euclidean_bins: `sbins` holds Euclidean bin edges (a caller-made RaySamples) instead of spacing-domain bins.
@@ -1101,9 +1144,18 @@ def field_fwd(origins, directions, sbins, field: FieldDev, near: float, far: flo
     keep_masks (MCDROPOUT): explicit keep masks instead of the counter generator's (unerf_field_fwd_masked); the call
     reads rows keep_masks.sample_offset + r * S + s, and ray_offset is then only the tile hint of image_width.
     views: the rays are several whole views (RayViews, unerf_field_fwd_views): the mask counter runs inside each view's
-    frame under views.seeds[v]; ray_offset is not read.  The f16 matrix kernels only -- anything else is refused."""
+    frame under views.seeds[v]; ray_offset is not read.  The f16 matrix kernels only -- anything else is refused.
+    lap_views (LAPLACE with views=; None = LaplaceViews()): the sample-set base of every view
+    (unerf_field_fwd_laplace_views)."""
     if euclidean_bins:
         near = -1.0
+    if views is not None and field.mode == _l.FIELD_LAPLACE:   # (unerf_field_fwd_laplace_views takes neither)
+        if features is not None:
+            raise _l.UnerfError("field_fwd: pre-gathered features are not built for several views (and have no LAPLACE form)")
+        if keep_masks is not None:
+            raise _l.UnerfError("field_fwd: explicit keep masks are an MCDROPOUT mode")
+    elif lap_views is not None:
+        raise _l.UnerfError("field_fwd: lap_views goes with views= and a LAPLACE field")
     lib = _l.load()
     R, S = sbins.shape[0], sbins.shape[1] - 1
     B = max(field.K, 1) if field.mode == _l.FIELD_MCDROPOUT else 1
@@ -1124,6 +1176,14 @@ def field_fwd(origins, directions, sbins, field: FieldDev, near: float, far: flo
     cs.sample_major = 1 if sample_major else 0
     cs.packed_out = 1 if packed else 0
     cs.overflow_flag = _p(nonfinite_flag, torch.int32)      # set by the f16 matrix kernels (either form) on operand overflow
+    if views is not None and field.mode == _l.FIELD_LAPLACE:
+        vs = views.cstruct()
+        ls = (lap_views or LaplaceViews()).cstruct(views.n_views)
+        with _ctx(dev):
+            _run("field_fwd", lambda: lib.unerf_field_fwd_laplace_views(
+                _p(origins), _p(directions), _p(sbins), R, S, near, far, spacing, C.byref(vs), C.byref(ls), C.byref(cs),
+                _p(density), _p(rgb), _p(aux), _p(aux2), _stream()))
+        return density, rgb, aux, aux2
     if views is not None:
         vs = views.cstruct(field.seed)
         km = None if keep_masks is None else keep_masks.cstruct(B)     # (refused by the entry point, by name)
@@ -1146,10 +1206,23 @@ def field_fwd(origins, directions, sbins, field: FieldDev, near: float, far: flo
 
 
 def laplace_depth_weights(density_mu, density_var, sbins, near: float, far: float, noise: Optional[torch.Tensor],
-                          D: int = 100, seed: int = 0, ray_offset: int = 0, spacing: int = 0) -> torch.Tensor:
+                          D: int = 100, seed: int = 0, ray_offset: int = 0, spacing: int = 0,
+                          views: Optional[RayViews] = None, lap_views: Optional[LaplaceViews] = None) -> torch.Tensor:
+    """views: the rows are several whole views (unerf_laplace_depth_weights_views): view v's draws are those of a call of
+    its own with seed = lap_views.depth_seeds[v] (None: `seed` for every view) and ray_offset = 0; ray_offset is not read."""
     lib = _l.load()
     R, S = density_mu.shape
     out = torch.empty(R, S, device=density_mu.device, dtype=torch.float32)
+    if views is not None:
+        vs = views.cstruct()
+        ls = (lap_views or LaplaceViews()).cstruct(views.n_views, seed)
+        with _ctx(out.device):
+            _run("laplace_depth_weights", lambda: lib.unerf_laplace_depth_weights_views(
+                _p(density_mu), _p(density_var), _p(sbins), R, S, near, far, spacing, _p(noise), D, C.byref(vs), C.byref(ls),
+                _p(out), _stream()))
+        return out
+    if lap_views is not None:
+        raise _l.UnerfError("laplace_depth_weights: lap_views goes with views=")
     with _ctx(out.device):
         _run("laplace_depth_weights", lambda: lib.unerf_laplace_depth_weights(_p(density_mu), _p(density_var), _p(sbins), R, S, near, far,
                                                  spacing, _p(noise), D, seed & 0xFFFFFFFF, ray_offset, _p(out), _stream()))

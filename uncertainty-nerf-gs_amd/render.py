@@ -195,9 +195,12 @@ def shading_stage(scene: NerfSceneDev, origins, directions, sb, prop_depths, fea
                   depth_noise: Optional[torch.Tensor] = None, depth_draws: int = 100, depth_seed: int = 0,
                   keep_density: bool = False, image_width: int = 0,
                   nonfinite_flag: Optional[torch.Tensor] = None,
-                  keep_masks: Optional[ops.KeepMasks] = None, views: Optional[ops.RayViews] = None) -> Dict[str, torch.Tensor]:
+                  keep_masks: Optional[ops.KeepMasks] = None, views: Optional[ops.RayViews] = None,
+                  lap_views: Optional[ops.LaplaceViews] = None) -> Dict[str, torch.Tensor]:
     """views: the rays are several whole views (render_cameras): the mask counter and the clip rows are numbered inside
     each view's own frame (ops.RayViews); ray_offset is then 0, the row of the tall image the launch starts at.
+    lap_views (LAPLACE with views): every view's first sample set in the field's stacks and the seed of its depth draws
+    (ops.LaplaceViews; None: set 0 and depth_seed for every view).
     keep_masks (MCDROPOUT): the FRAME's explicit keep masks (ops.KeepMasks over all its rays, row = ray * S + sample);
     this launch group reads them from row ray_offset * S.  The fp32 re-render of the overflow guard and the two-stream
     path come through here with the same masks."""
@@ -211,12 +214,13 @@ def shading_stage(scene: NerfSceneDev, origins, directions, sb, prop_depths, fea
     density, rgb, aux, aux2 = ops.field_fwd(origins, directions, sb, f, scene.near, scene.far, ray_offset, features=feats,
                                             image_width=image_width, sample_major=planes, spacing=scene.spacing,
                                             nonfinite_flag=nonfinite_flag, packed=packed, workspace=scene.workspace, views=views,
+                                            lap_views=lap_views if f.mode == _l.FIELD_LAPLACE else None,
                                             keep_masks=None if keep_masks is None else keep_masks.at(ray_offset * (sb.shape[1] - 1)))
     kw = dict(clip_minmax=clip, ray_offset=ray_offset, chunk_rays=scene.chunk_rays, spacing=scene.spacing,
               background=scene.background, nonfinite_flag=nonfinite_flag)
     if views is not None:
-        if planes or f.mode == _l.FIELD_LAPLACE:
-            raise _l.UnerfError("shading_stage: several views per launch are built for the ray-major ACTIVE / MCDROPOUT path")
+        if planes:
+            raise _l.UnerfError("shading_stage: several views per launch are built for the ray-major path")
         kw["views"] = views
     res: Dict[str, torch.Tensor] = {}
     if f.mode == _l.FIELD_ACTIVE:
@@ -257,7 +261,7 @@ def shading_stage(scene: NerfSceneDev, origins, directions, sb, prop_depths, fea
         # use_deterministic_density (laplace_model.py:486-507 is skipped): depth from the ordinary weights
         walt = None if f.lap_mask_density else ops.laplace_depth_weights(
             density[0], aux, sb, scene.near, scene.far, depth_noise, depth_draws, depth_seed, ray_offset,
-            spacing=scene.spacing)
+            spacing=scene.spacing, views=views, lap_views=lap_views if views is not None else None)
         out = ops.composite_var(density, rgb, sb, scene.near, scene.far, beta=aux2, weights_alt=walt, **kw)[0]
         u = _unpack(out)
         res = {"rgb": u["rgb"], "rgb_std": u["rgb_var"].sqrt(), "accumulation": u["accumulation"],
@@ -404,10 +408,9 @@ def _per_view_distortion(distortion, B: int) -> Optional[list]:
 
 def view_batch_loop_reason(scene: NerfSceneDev, overlap: bool = False, keep_masks=None) -> Optional[str]:
     """Why render_cameras renders this scene camera by camera (None: it shares launches).  The several-views kernels are
-    built for the frame path's default form: ACTIVE / MCDROPOUT on the f16 matrix kernels, fused lookup, ray-major rows."""
+    built for the frame path's default form: ACTIVE / MCDROPOUT / LAPLACE on the f16 matrix kernels, fused lookup,
+    ray-major rows."""
     f = scene.field
-    if f.mode == _l.FIELD_LAPLACE:
-        return "a Laplace field (its sample sets are per chunk of one frame)"
     if keep_masks is not None:
         return "explicit keep masks span one frame"
     if overlap:
@@ -422,12 +425,15 @@ def view_batch_loop_reason(scene: NerfSceneDev, overlap: bool = False, keep_mask
         return "an fp32 field (no f16 matrix operands)"
     if f.mode == _l.FIELD_MCDROPOUT and f.K > 0 and ops.FieldDev._sites(f.drop_sites) != (_l.DROP_TRUNK | _l.DROP_HEAD1):
         return "non-default dropout sites"
+    if f.mode == _l.FIELD_LAPLACE and f.lap16_blob is None:
+        return "a Laplace field without f16 head operands (more than 128 sampled rows)"
     return None
 
 
 def render_cameras(scene: NerfSceneDev, c2ws: torch.Tensor, fx, fy, cx, cy, H: int, W: int, seeds=None,
                    rays_per_launch: int = 1 << 20, overlap: bool = False, obb=None, distortion=None, camera_type=1,
-                   max_views: int = _l.NERF_MAX_VIEWS, **shade_kw) -> List[Dict[str, torch.Tensor]]:
+                   max_views: int = _l.NERF_MAX_VIEWS, lap_view_sets=None, depth_seeds=None,
+                   **shade_kw) -> List[Dict[str, torch.Tensor]]:
     """get_outputs_for_camera for B cameras of ONE image size: c2ws [B,3|4,4]; fx, fy, cx, cy, camera_type: one value or one
     per camera; distortion: None, one 6-vector or one entry per camera.  -> B dicts of images [H,W,C]; element v is
     bit-identical to render_camera(scene, c2ws[v], ...) -- for MC-dropout with scene.field.seed = seeds[v] (seeds=None:
@@ -441,10 +447,17 @@ def render_cameras(scene: NerfSceneDev, c2ws: torch.Tensor, fx, fy, cx, cy, H: i
     its own offending groups on the fp32 kernels), so they too equal the loop.  scene.workspace, obb and keep_density work
     as in render_camera.
 
+    A Laplace scene (f16 matrix kernels) shares launches too.  lap_view_sets[v] = the first sample set of view v in the
+    field's stacks (ws_* / lap16_blob [sets, ...]); view v is rendered with the sets lap_view_sets[v] + [0, sets per view)
+    -- sets per view = ceil(H W / field.lap_chunk_rays), 1 without per-chunk sets -- and equals render_camera on the field
+    narrowed to those sets (ops.laplace_sets_view).  Default: 0 for every view, the field's own sets, which is what a loop of
+    render_camera over the same scene renders.  depth_seeds[v] = the seed of view v's depth draws (default: the depth_seed
+    keyword for every view).  The views of a flagged launch group are re-rendered with their own sets and depth seed.
+
     Rendered as a plain loop over render_camera -- the SAME results, without shared launches -- when H W exceeds half a
-    launch group, for a Laplace field, with keep_masks= (dropout_masks="torch"), with overlap=True, scene.sample_major or
-    scene.split_gather, for an any-width or fp32 field, non-default dropout sites, and when the camera types of the batch
-    differ (view_batch_loop_reason)."""
+    launch group, with keep_masks= (dropout_masks="torch"), with overlap=True, scene.sample_major or scene.split_gather, for
+    an any-width or fp32 field, non-default dropout sites, a Laplace field with more than 128 sampled rows, and when the
+    camera types of the batch differ (view_batch_loop_reason)."""
     _l.require_gpu()
     B = int(c2ws.shape[0])
     if B < 1:
@@ -457,17 +470,30 @@ def render_cameras(scene: NerfSceneDev, c2ws: torch.Tensor, fx, fy, cx, cy, H: i
     total = H * W
     f = scene.field
     c2ws = c2ws.detach().cpu()       # one device -> host copy for the batch (the ray kernels take host camera records)
+    laplace = f.mode == _l.FIELD_LAPLACE
+    if not laplace and (lap_view_sets is not None or depth_seeds is not None):
+        raise ValueError("render_cameras: lap_view_sets / depth_seeds belong to a Laplace scene")
+    for name, vals in (("lap_view_sets", lap_view_sets), ("depth_seeds", depth_seeds)):
+        if vals is not None and len(vals) != B:
+            raise ValueError(f"render_cameras: {len(vals)} {name} for {B} cameras")
+    lap_spv = ops.laplace_sets_per_view(f, total) if laplace else 0
 
     def single(v: int) -> Dict[str, torch.Tensor]:
         saved = f.seed
         if seeds is not None:
             f.seed = int(seeds[v])
+        kw = shade_kw
+        if depth_seeds is not None:
+            kw = dict(shade_kw, depth_seed=int(depth_seeds[v]))
+        if lap_view_sets is not None:      # this view's own sets: the stacks narrowed to them
+            scene.field = ops.laplace_sets_view(f, int(lap_view_sets[v]), lap_spv)
         try:
             return render_camera(scene, c2ws[v], fxs[v], fys[v], cxs[v], cys[v], H, W, rays_per_launch=rays_per_launch,
                                  overlap=overlap, obb=obb, distortion=None if dists is None else dists[v],
-                                 camera_type=types[v], **shade_kw)
+                                 camera_type=types[v], **kw)
         finally:
             f.seed = saved
+            scene.field = f
 
     groups = plan_view_groups(B, total, rays_per_launch, scene.chunk_rays, max_views)
     if (groups is None or len(set(types)) != 1
@@ -484,8 +510,13 @@ def render_cameras(scene: NerfSceneDev, c2ws: torch.Tensor, fx, fy, cx, cy, H: i
                                            H, W, dev, distortions=None if dists is None else dists[v0:v0 + nv],
                                            camera_type=types[0])
             views = ops.RayViews(nv, total, None if seeds is None else tuple(int(x) for x in seeds[v0:v0 + nv]))
+            kw = shade_kw
+            if laplace:
+                kw = dict(shade_kw, lap_views=ops.LaplaceViews(
+                    None if lap_view_sets is None else tuple(int(x) for x in lap_view_sets[v0:v0 + nv]),
+                    None if depth_seeds is None else tuple(int(x) for x in depth_seeds[v0:v0 + nv])))
             res = render_rays(scene, o, d, ray_offset=0, clip=clip[v0 * cpv:(v0 + nv) * cpv], image_width=W,
-                              init_bins=crop_bins(scene, o, d, obb), nonfinite_flag=guard.flag(gi), views=views, **shade_kw)
+                              init_bins=crop_bins(scene, o, d, obb), nonfinite_flag=guard.flag(gi), views=views, **kw)
             # one contiguous [nv,H,W,C] image stack per key (render_camera's torch.cat), handed out view by view
             stacks = {k: t.reshape(nv, H, W, -1).contiguous() for k, t in res.items()}
             for i in range(nv):
