@@ -230,11 +230,9 @@ def _pick(counts, P, rng):
     return keep
 
 
-@pytest.mark.parametrize("pairs", [(2048, 0, 2049), (32769, 5, 2048)], ids=_name)
-def test_tight_lists_at_chunk_and_segment_edges(dev, pairs):
+def _tight_case(dev, pairs):
     """Tight lists (map_intersects_kernel<uint16_t, 8>: the rows project_kernel counted) of a projected scene, cut down per view
-    to splats whose tight counts sum to the wanted pairs.  The numpy oracle has no tight rows, so reference (b) alone applies:
-    the single-view tight sort of every view's slice."""
+    to splats whose tight counts sum to the wanted pairs -> (case, device tensors, (conics, opacities), kept splats)"""
     import test_gpu_splat_batch as TB
     from uncertainty_nerf_gs_amd import ops, splat
     B, H, W, N = len(pairs), 256, 256, 20000
@@ -249,7 +247,14 @@ def test_tight_lists_at_chunk_and_segment_edges(dev, pairs):
     keep = torch.from_numpy(np.stack([_pick(nth[v].cpu().numpy(), P, rng) for v, P in enumerate(pairs)])).to(dev)
     radii, nth = torch.where(keep, radii, 0).contiguous(), torch.where(keep, nth, 0).contiguous()
     c = dict(pairs=pairs, H=H, W=W, N=N, B=B, tiles=256)
-    t = dict(xys=xys, depths=depths, radii=radii, nth=nth)
+    return c, dict(xys=xys, depths=depths, radii=radii, nth=nth), (conics, opac), keep
+
+
+@pytest.mark.parametrize("pairs", [(2048, 0, 2049), (32769, 5, 2048)], ids=_name)
+def test_tight_lists_at_chunk_and_segment_edges(dev, pairs):
+    """The numpy oracle has no tight rows, so reference (b) alone applies: the single-view tight sort of every view's slice."""
+    c, t, (conics, opac), keep = _tight_case(dev, pairs)
+    B, N = c["B"], c["N"]
     totals, visible, ids, bins, _ = _run(dev, c, tight=(conics, opac), t=t)
     assert totals == list(pairs) and visible == [p > 0 for p in pairs]
     _check_properties(pairs, N, ids, bins)
@@ -258,6 +263,45 @@ def test_tight_lists_at_chunk_and_segment_edges(dev, pairs):
     assert np.array_equal(ids, ids1) and np.array_equal(bins, bins1)
     owner = np.repeat(np.arange(B), pairs)
     assert bool(keep.cpu().numpy()[owner, ids - owner * N].all())          # only kept splats are listed
+
+
+# (pairs, tiles, N): pair counts below, at and above one 2,048-pair chunk of the tile passes and above one 16-chunk histogram
+# workgroup, at the last two one-pass tile counts and the first two-pass one; one splat, a full and a ragged second 1,024-splat
+# chunk of the depth passes (every splat live); no pairs at all
+ONE_VIEW = ([(I, tiles, None) for tiles in (63, 127, 128) for I in (1, 2047, 2048, 2049, 32769)] +
+            [(N, 63, N) for N in (1, 1024, 1025)] + [(0, 63, None)])
+
+
+def _batch_of_one_vs_single(dev, c, t=None, tight=None):
+    """unerf_splat_bin_sort_batch with B = 1 and unerf_splat_bin_sort on the same inputs: one body, the batch's chunks padded
+    to whole histogram workgroups and sorted by the segment kernels, the single view's not -- the same ids and tile ranges"""
+    from uncertainty_nerf_gs_amd import ops
+    assert c["B"] == 1
+    t = t or {k: torch.from_numpy(c[k]).to(dev) for k in ("xys", "depths", "radii", "nth")}
+    count = ops.SplatCountBatch(t["nth"], t["radii"] if tight else None)
+    totals, _, gids, bins = ops.splat_bin_sort_batch(t["xys"], t["depths"], t["radii"], count, c["H"], c["W"], tight=tight)
+    I, _, _, gids1, bins1 = ops.splat_bin_sort(t["xys"][0], t["depths"][0], t["radii"][0], t["nth"][0], c["H"], c["W"],
+                                               want_isect_ids=False, tight=(tight[0][0], tight[1][0]) if tight else None)
+    assert list(totals) == [I] == list(c["pairs"])
+    assert gids1.shape == (I,) and bins.shape == (1, c["tiles"], 2)
+    assert torch.equal(gids[:I], gids1), "gaussian_ids_sorted"
+    assert torch.equal(bins[0], bins1), "tile_bins"
+    if I == 0:
+        assert not bool(bins.any()) and not bool(bins1.any())
+    else:
+        assert int(bins1.max()) == I
+
+
+@pytest.mark.parametrize("pairs,tiles,N", ONE_VIEW, ids=lambda x: str(x))
+def test_a_batch_of_one_view_equals_the_single_view_sort(dev, pairs, tiles, N):
+    """box lists"""
+    _batch_of_one_vs_single(dev, _case((pairs,), tiles, N=N, multis=N is None))
+
+
+def test_a_batch_of_one_view_equals_the_single_view_sort_on_tight_lists(dev):
+    """2,049 tight pairs at 256 tiles: a ragged second chunk, two passes"""
+    c, t, tight, _ = _tight_case(dev, (2049,))
+    _batch_of_one_vs_single(dev, c, t=t, tight=tight)
 
 
 @pytest.mark.parametrize("N", [1, 1023, 1024, 1025, 4097])

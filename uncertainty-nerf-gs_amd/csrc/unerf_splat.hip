@@ -8,6 +8,7 @@
 
 #include <hipcub/hipcub.hpp>
 
+#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 
@@ -631,7 +632,7 @@ static TileSortPlan tile_sort_plan(int64_t I, int tiles) {
 // stages in LDS in digit order and writes out as runs of consecutive slots (see rs_scatter_kernel for why).
 #define RS_M_TILE 2048      // pairs per wave, tile sort (u16 / u32 keys, <= 128 digits: runs of >= 16 slots per digit)
 #define RS_M_DEPTH 1024     // pairs per wave, depth sort (u32 keys, 256 digits: runs of 4)
-#define RS_CPW 1            // chunks per wave in the histogram kernels; the whole-key histogram's workgroup = 16 waves = 16 chunks
+#define RS_CPW 1            // chunks per wave in the histogram kernels (rs_pass); the whole-key histogram's workgroup = 16 waves = 16 chunks
 struct RsTilePlan {
     int nchunk, b0, B0, B1, nhw;      // digit 0 = key & (B0 - 1), digit 1 = key >> b0 (< B1; B0, B1 powers of two <= 128)
 };
@@ -652,7 +653,9 @@ static RsTilePlan rs_tile_plan(int64_t I, int T1) {
 // is sorted on its own (its digit prefixes, totals and output slots stay inside it).  One segment: a single view; a batch of
 // views: one segment per view, so every view's pairs leave in the order a single-view sort gives them.
 // S: segments the launch can carry -- 1 for the single-view sort (kernel arguments of the old size), UNERF_SPLAT_MAX_VIEWS for
-// unerf_splat_bin_sort_batch
+// unerf_splat_bin_sort_batch.  The host code (rs_pass, staged_depth_sort, staged_tile_sort, bin_sort_body) is written once over
+// SEG = "more than one segment can come": it takes its chunk count, pair count and segment count from the RsSegs it is given,
+// and the two entry points differ in how they build theirs.
 template <int S>
 struct RsSegs {
     int n;
@@ -711,6 +714,8 @@ static hipError_t depth_sort_pairs(void* tmp, size_t& tmp_bytes, const uint32_t*
 struct SortWs {
     int64_t tmp, dkey_in, dkey_out, id_in, order, counts, cum, tkey_in, tkey_out, val_in, val_mid, ts_table, ts_segsum, ts_start, ds_table, ds_total, total;
 };
+// One layout serves both entry points, and bin_sort_body reads it the same way for both (sort_ws_ptrs; the tables of the tile
+// passes are carved out of ts_table / ts_segsum by staged_tile_sort from the chunk and segment counts of its RsSegs).
 // batch (unerf_splat_*_batch, any B >= 1): N splats in each of B views, I pairs over all views.  Each view's chunks of the tile
 // passes are padded to a multiple of 16 (a whole-key histogram workgroup never straddles two views): at most 16 B chunks more
 // than the single-view plan, and as many whole-key rows more (rs_tile_tables_fit checks a batch's actual plan against this).
@@ -748,6 +753,35 @@ static SortWs sort_ws_layout(int64_t N, int64_t I, int B = 1, bool batch = false
     w.ds_total = take((int64_t)256 * B * 4);
     w.total = off + 1024;
     return w;
+}
+// the tile passes' tables of a chunk plan -- 2 x [128][nchunk] digit counters + [nchunk / 16][T1] whole-key rows -- against what
+// the layout reserved for them
+static bool rs_tile_tables_fit(const SortWs& L, int64_t nchunk, int T1, int64_t& need, int64_t& have) {
+    need = ((int64_t)256 * nchunk + (nchunk + 15) / 16 * T1) * 4;
+    have = L.ts_segsum - L.ts_table;
+    return need <= have;
+}
+
+// the workspace as typed pointers (the tile keys are uint16_t up to 16 key bits, uint32_t beyond: cast where they are used)
+struct SortPtrs {
+    void* tmp;              // rocprim's scratch; own_inclusive_scan's block sums
+    size_t tmp_bytes;
+    uint32_t *dk_in, *dk_out, *ts_table, *ts_segsum, *ts_start, *ds_table, *ds_total;
+    int32_t *id_in, *order, *counts, *cum_sorted, *v_in, *v_mid;
+    void *tk_in, *tk_out;
+};
+static SortPtrs sort_ws_ptrs(void* workspace, const SortWs& L) {
+    char* ws = (char*)workspace;
+    auto u32 = [&](int64_t off) { return reinterpret_cast<uint32_t*>(ws + off); };
+    auto i32 = [&](int64_t off) { return reinterpret_cast<int32_t*>(ws + off); };
+    SortPtrs p;
+    p.tmp = ws + L.tmp; p.tmp_bytes = (size_t)(L.dkey_in - L.tmp);
+    p.dk_in = u32(L.dkey_in); p.dk_out = u32(L.dkey_out); p.id_in = i32(L.id_in); p.order = i32(L.order);
+    p.counts = i32(L.counts); p.cum_sorted = i32(L.cum);
+    p.tk_in = ws + L.tkey_in; p.tk_out = ws + L.tkey_out; p.v_in = i32(L.val_in); p.v_mid = i32(L.val_mid);
+    p.ts_table = u32(L.ts_table); p.ts_segsum = u32(L.ts_segsum); p.ts_start = u32(L.ts_start);
+    p.ds_table = u32(L.ds_table); p.ds_total = u32(L.ds_total);
+    return p;
 }
 
 extern "C" int64_t unerf_splat_sort_workspace_bytes(int64_t N, int64_t I) {
@@ -1554,96 +1588,192 @@ __global__ __launch_bounds__(256) void tile_isect_ids_kernel(const uint32_t* __r
     isect_ids[i] = ((int64_t)lo << 32) | (int64_t)(uint32_t)__float_as_int(depths[gids[i]]);
 }
 
+// ---- the staged passes on the host: one description for the depth sort, the tile sort, one view and a batch ---------------------
+// One staged pass: histogram -> row scan -> scatter, over the chunks and segments of `segs` (SEG: the batch's kernels).
+//   TKey, M, DMAX, shift, digits: the keys, the pairs per chunk, the digit values the LDS tables are sized for and the digit
+//   FULL: the histogram also counts whole keys (<= kmax) into `full`, one row per 16-chunk workgroup; else `full` is unused
+//   KEYS_OUT / COUNTS: as in rs_scatter_kernel (kout; radii, cum, counts)
+//   SWPB: waves (= chunks) per scatter workgroup -- 4 in the depth sort, 1 in the tile sort (1, 2 or 4 measured alike: 4.5.77);
+//   the histogram has 16 waves per workgroup when FULL, else 4
+template <bool SEG, typename TKey, int M, int DMAX, int SWPB, bool FULL, bool KEYS_OUT, bool COUNTS = false>
+static void rs_pass(const RsSegs<SEG ? UNERF_SPLAT_MAX_VIEWS : 1>& segs, uint32_t kmax, int shift, int digits, const TKey* kin,
+                    const int32_t* vin, TKey* kout, int32_t* vout, uint32_t* table, uint32_t* full, uint32_t* dtotal,
+                    hipStream_t st, const int32_t* radii = nullptr, const int32_t* cum = nullptr, int32_t* counts = nullptr) {
+    constexpr int S = SEG ? UNERF_SPLAT_MAX_VIEWS : 1, HWPB = FULL ? 16 : 4;
+    const int nchunk = segs.cb[segs.n];
+    const size_t lds_hist = (HWPB * 256 + (FULL ? (size_t)kmax + 1 : 0)) * sizeof(uint32_t);
+    const size_t lds_sc = SWPB * (size_t)RsLds<M, DMAX, TKey>::WAVE_WORDS * sizeof(uint32_t);
+    hipLaunchKernelGGL((rs_hist_kernel<TKey, FULL, SEG>), dim3(blocks_for(nchunk, HWPB * RS_CPW)), dim3(64 * HWPB), lds_hist, st,
+                       kin, segs, M, nchunk, kmax, shift, digits, RS_CPW, table, full);
+    hipLaunchKernelGGL(rs_rowscan_kernel<S>, dim3(digits, segs.n), dim3(1024), 0, st, table, nchunk, segs, dtotal);
+    hipLaunchKernelGGL((rs_scatter_kernel<TKey, M, DMAX, KEYS_OUT, COUNTS, SEG>), dim3(blocks_for(nchunk, SWPB)), dim3(64 * SWPB),
+                       lds_sc, st, kin, vin, segs, nchunk, kmax, shift, digits, table, dtotal, kout, vout, radii, cum, counts);
+}
+
+// every segment's splats in depth order (stable: equal depths keep their index order), segment after segment: four staged 8-bit
+// LSD passes; the last one writes `order` and, in that order, the tile counts
+template <bool SEG>
+static void staged_depth_sort(const SortPtrs& P, const RsSegs<SEG ? UNERF_SPLAT_MAX_VIEWS : 1>& segs, const float* depths,
+                              const int32_t* radii, const int32_t* cum_tiles_hit, hipStream_t st) {
+    const int64_t NB = segs.pb[segs.n];
+    hipLaunchKernelGGL(depth_keys_kernel, dim3(blocks_for(NB, 256)), dim3(256), 0, st, depths, radii, NB, P.dk_out, P.order);
+    uint32_t* const k[2] = {P.dk_out, P.dk_in};
+    int32_t* const v[2] = {P.order, P.id_in};
+    for (int p = 0; p < 4; ++p) {      // (dk_out, order) -> (dk_in, id_in) -> (dk_out, order) -> (dk_in, id_in) -> order
+        const int i = p & 1, o = i ^ 1;
+        if (p < 3)
+            rs_pass<SEG, uint32_t, RS_M_DEPTH, 256, 4, false, true>(segs, 0xFFFFFFFFu, 8 * p, 256, k[i], v[i], k[o], v[o], P.ds_table,
+                                                                    nullptr, P.ds_total, st);
+        else
+            rs_pass<SEG, uint32_t, RS_M_DEPTH, 256, 4, false, false, true>(segs, 0xFFFFFFFFu, 8 * p, 256, k[i], v[i], nullptr, P.order,
+                                                                           P.ds_table, nullptr, P.ds_total, st, radii, cum_tiles_hit,
+                                                                           P.counts);
+    }
+}
+
+// the (tile, splat) pairs in depth order.  Tight lists: 8 lanes per splat; gsplat's boxes (37 tiles per splat on the bench frame): 16
 template <typename TKey>
-static int bin_sort_impl(const float* xys, const float* depths, const int32_t* radii, const int32_t* order,
-                         const int32_t* cum_sorted, const float* conics, const float* opac, int64_t N, int64_t I, int bw,
-                         int tbx, int tby, int bits, int own_sort,
-                         int64_t* isect_ids_sorted, int32_t* gaussian_ids_sorted, int32_t* tile_bins, char* ws,
-                         const SortWs& L, size_t tmp_bytes, hipStream_t st) {
-    TKey* tk_in = reinterpret_cast<TKey*>(ws + L.tkey_in);
-    TKey* tk_out = reinterpret_cast<TKey*>(ws + L.tkey_out);
-    int32_t* v_in = reinterpret_cast<int32_t*>(ws + L.val_in);
-    // tight lists: 8 lanes per splat; gsplat's boxes (37 tiles per splat on the bench frame): 16
+static void emit_pairs(const SortPtrs& P, const float* xys, const int32_t* radii, const float* conics, const float* opac, int64_t NB,
+                       int bw, int tbx, int tby, hipStream_t st) {
+    TKey* tk_in = static_cast<TKey*>(P.tk_in);
     if (conics)
-        hipLaunchKernelGGL((map_intersects_kernel<TKey, 8>), dim3(blocks_for(N, 32)), dim3(256), 0, st, xys, radii, order,
-                           cum_sorted, N, bw, tbx, tby, conics, opac, tk_in, v_in);
+        hipLaunchKernelGGL((map_intersects_kernel<TKey, 8>), dim3(blocks_for(NB, 32)), dim3(256), 0, st, xys, radii, P.order,
+                           P.cum_sorted, NB, bw, tbx, tby, conics, opac, tk_in, P.v_in);
     else
-    hipLaunchKernelGGL((map_intersects_kernel<TKey, 16>), dim3(blocks_for(N, 16)), dim3(256), 0, st, xys, radii, order,
-                       cum_sorted, N, bw, tbx, tby, conics, opac, tk_in, v_in);
+        hipLaunchKernelGGL((map_intersects_kernel<TKey, 16>), dim3(blocks_for(NB, 16)), dim3(256), 0, st, xys, radii, P.order,
+                           P.cum_sorted, NB, bw, tbx, tby, conics, opac, tk_in, P.v_in);
+}
+
+// stable sort of the pairs by tile, segment by segment -- one staged pass on the whole key up to 128 keys, else low digit, then
+// high digit -- and per segment: tile totals (column sums of the whole-key histograms, 16 row segments summed in parallel;
+// tile_scan_kernel adds them up per tile) -> tile starts from the segment's first slot and its tile_bins.
+// ts_table: [128][nchunk] x 2 digit counters + [nchunk / 16][T1] whole-key rows; ts_segsum: dtotal [2][B][256] + total [B][16][T1]
+template <bool SEG, typename TKey>
+static void staged_tile_sort(const SortPtrs& P, const RsSegs<SEG ? UNERF_SPLAT_MAX_VIEWS : 1>& segs, int tiles, const float* depths,
+                             int64_t* isect_ids_sorted, int32_t* gaussian_ids_sorted, int32_t* tile_bins, hipStream_t st) {
+    constexpr int S = SEG ? UNERF_SPLAT_MAX_VIEWS : 1;
+    const int B = segs.n, nchunk = segs.cb[B], T1 = tiles + 1;
+    const int64_t I = segs.pb[B];
+    const RsTilePlan rp = rs_tile_plan(I, T1);      // (the digit split only: the chunks are the caller's)
+    uint32_t *table0 = P.ts_table, *table1 = table0 + (size_t)128 * nchunk, *full = table1 + (size_t)128 * nchunk;
+    uint32_t *dtotal0 = P.ts_segsum, *dtotal1 = dtotal0 + (size_t)256 * B, *total = dtotal1 + (size_t)256 * B;
+    uint32_t* start = P.ts_start;                   // [B][T1 + 1]
+    TKey *tk_in = static_cast<TKey*>(P.tk_in), *tk_mid = static_cast<TKey*>(P.tk_out);
+    const uint32_t kmax = (uint32_t)tiles;
+    if (rp.b0 == 0) {      // <= 128 keys: one pass
+        rs_pass<SEG, TKey, RS_M_TILE, 128, 1, true, false>(segs, kmax, 0, rp.B1, tk_in, P.v_in, nullptr, gaussian_ids_sorted, table1,
+                                                           full, dtotal1, st);
+    } else {
+        rs_pass<SEG, TKey, RS_M_TILE, 128, 1, true, true>(segs, kmax, 0, rp.B0, tk_in, P.v_in, tk_mid, P.v_mid, table0, full, dtotal0,
+                                                          st);
+        rs_pass<SEG, TKey, RS_M_TILE, 128, 1, false, false>(segs, kmax, rp.b0, rp.B1, tk_mid, P.v_mid, nullptr, gaussian_ids_sorted,
+                                                            table1, nullptr, dtotal1, st);
+    }
+    hipLaunchKernelGGL(rs_colsum_kernel<S>, dim3(blocks_for(T1, 256), 16, B), dim3(256), 0, st, full, segs, T1, total);
+    hipLaunchKernelGGL((tile_scan_kernel<16, S>), dim3(B), dim3(1024), ((size_t)T1 + 16) * sizeof(uint32_t), st, total, T1, tiles,
+                       start, tile_bins, segs);
+    if (isect_ids_sorted)      // (one segment only)
+        hipLaunchKernelGGL(tile_isect_ids_kernel, dim3(blocks_for(I, 256)), dim3(256), 0, st, start, T1, gaussian_ids_sorted, depths,
+                           I, isect_ids_sorted);
+}
+
+static int sort_check(const char* what, const char* step) {
+    char label[96];
+    snprintf(label, sizeof(label), "%s %s", what, step);
+    return unerf_check_launch(label);
+}
+
+// The default bin-and-sort of both entry points: dsegs / tsegs are the segments (views) of the depth passes and of the tile
+// passes.  All views' splats are one stream (view-major: id v N + i) and every staged pass runs segment by segment, so each
+// view's order is exactly its single-view order -- depth, then splat index on ties; tile, then depth order -- and its pairs leave
+// contiguous, view after view.  The keys stay the per-view tile ids (13 bits at 1080p): a combined (view, tile) key would outgrow
+// the LDS tables from two 1080p views on.  The caller checks the launches of step 3.
+template <bool SEG>
+static int bin_sort_body(const char* what, const SortPtrs& P, const RsSegs<SEG ? UNERF_SPLAT_MAX_VIEWS : 1>& dsegs,
+                         const RsSegs<SEG ? UNERF_SPLAT_MAX_VIEWS : 1>& tsegs, const float* xys, const float* depths,
+                         const int32_t* radii, const int32_t* cum_tiles_hit, const float* conics, const float* opac, int bw, int tbx,
+                         int tby, int64_t* isect_ids_sorted, int32_t* gaussian_ids_sorted, int32_t* tile_bins, hipStream_t st) {
+    const int64_t NB = dsegs.pb[dsegs.n];
+    // 1. splats in depth order
+    staged_depth_sort<SEG>(P, dsegs, depths, radii, cum_tiles_hit, st);
+    int rc = sort_check(what, "depth sort");
+    if (rc) return rc;
+    // 2. where each depth-ordered splat's intersections start: one scan over all counts (views stay contiguous)
+    own_inclusive_scan(P.counts, P.cum_sorted, NB, static_cast<int32_t*>(P.tmp), st);
+    // 3. emission in that order, the stable sort by tile, tile ranges (+ ids)
+    emit_pairs<uint16_t>(P, xys, radii, conics, opac, NB, bw, tbx, tby, st);
+    if ((rc = sort_check(what, "map"))) return rc;
+    staged_tile_sort<SEG, uint16_t>(P, tsegs, tbx * tby, depths, isect_ids_sorted, gaussian_ids_sorted, tile_bins, st);
+    return UNERF_OK;
+}
+
+// ---- single view: the alternates kept for A/B timing and the identity tests (tests/test_gpu_splat.py), and the sort of images
+// the staged tile passes do not serve.  Same steps as bin_sort_body, each with its substitute:
+//   rocprim_depth (UNERF_SPLAT_DEPTH_SORT=rocprim): rocprim's stable sort + sorted_counts_kernel
+//   rocprim_scan (UNERF_SPLAT_SCAN=rocprim): hipcub's scan
+//   tile_sort 0: rocprim's radix sort (UNERF_SPLAT_TILE_SORT=radix, more than TS_MAX_T1 - 1 tiles, 32-bit keys) + tile_edges_kernel,
+//             1: the round-4 one-pass LDS-digit sort (=onepass), 2: the staged passes
+template <typename TKey>
+static int bin_sort_alternates(bool rocprim_depth, bool rocprim_scan, int tile_sort, const SortPtrs& P, const RsSegs<1>& dsegs,
+                               const RsSegs<1>& tsegs, const float* xys, const float* depths, const int32_t* radii,
+                               const int32_t* cum_tiles_hit, const float* conics, const float* opac, int bw, int tbx, int tby,
+                               int bits, int64_t* isect_ids_sorted, int32_t* gaussian_ids_sorted, int32_t* tile_bins,
+                               hipStream_t st) {
+    const int64_t N = dsegs.pb[1], I = tsegs.pb[1];
+    const int tiles = tbx * tby;
+    size_t tmp_bytes = P.tmp_bytes;      // (hipcub takes it by reference and leaves it alone)
+    hipError_t e = hipSuccess;
+    if (rocprim_depth) {
+        hipLaunchKernelGGL(depth_keys_kernel, dim3(blocks_for(N, 256)), dim3(256), 0, st, depths, radii, N, P.dk_in, P.id_in);
+        e = depth_sort_pairs(P.tmp, tmp_bytes, P.dk_in, P.dk_out, P.id_in, P.order, N, st);
+        if (e != hipSuccess) {
+            unerf_set_error("splat_bin_sort: depth sort: %s", hipGetErrorString(e));
+            return UNERF_ERR_HIP;
+        }
+        hipLaunchKernelGGL(sorted_counts_kernel, dim3(blocks_for(N, 256)), dim3(256), 0, st, P.order, radii, cum_tiles_hit, N,
+                           P.counts);
+    } else {
+        staged_depth_sort<false>(P, dsegs, depths, radii, cum_tiles_hit, st);
+        int rc = unerf_check_launch("splat_bin_sort depth sort");
+        if (rc) return rc;
+    }
+    if (!rocprim_scan) {
+        own_inclusive_scan(P.counts, P.cum_sorted, N, static_cast<int32_t*>(P.tmp), st);
+    } else {
+        e = hipcub::DeviceScan::InclusiveSum(P.tmp, tmp_bytes, P.counts, P.cum_sorted, (int)N, st);
+        if (e != hipSuccess) {
+            unerf_set_error("splat_bin_sort: scan: %s", hipGetErrorString(e));
+            return UNERF_ERR_HIP;
+        }
+    }
+    emit_pairs<TKey>(P, xys, radii, conics, opac, N, bw, tbx, tby, st);
     int rc = unerf_check_launch("splat_bin_sort map");
     if (rc) return rc;
-    const int tiles = tbx * tby;
-    if (sizeof(TKey) != 2) own_sort = 0;      // (the own sorts serve <= TS_MAX_T1 tiles: always 16-bit keys; their LDS images are sized for them)
-    if (own_sort == 2) {   // two staged LSD passes (rs_* kernels above)
-        const int T1 = tiles + 1;
-        const RsTilePlan rp = rs_tile_plan(I, T1);
-        uint32_t* base = reinterpret_cast<uint32_t*>(ws + L.ts_table);
-        uint32_t* table0 = base;                                        // [B0][nchunk]
-        uint32_t* table1 = table0 + (size_t)128 * rp.nchunk;            // [B1][nchunk]
-        uint32_t* full = table1 + (size_t)128 * rp.nchunk;              // [nhw][T1]
-        uint32_t* dtotal = reinterpret_cast<uint32_t*>(ws + L.ts_segsum);      // [256] + [256] (one segment)
-        uint32_t* total = dtotal + 512;                                 // [16][T1]
-        const RsSegs<1> one = rs_one_seg(rp.nchunk, I);
-        uint32_t* start = reinterpret_cast<uint32_t*>(ws + L.ts_start);
-        TKey* tk_mid = tk_out;
-        int32_t* v_mid = reinterpret_cast<int32_t*>(ws + L.val_mid);
-        const int swpb = 1, sgrid = (rp.nchunk + swpb - 1) / swpb;      // single-wave workgroups (1, 2 or 4 waves measured alike: 4.5.77)
-        const uint32_t kmax = (uint32_t)tiles;
-        const size_t lds_full = (16 * 256 + (size_t)T1) * sizeof(uint32_t), lds_dig = 1024 * sizeof(uint32_t);
-        const int hgrid = (rp.nchunk + 3) / 4;      // digit-only histogram: one chunk per wave, four waves per workgroup
-        const size_t lds_sc = swpb * (size_t)RsLds<RS_M_TILE, 128, TKey>::WAVE_WORDS * sizeof(uint32_t);
-        if (rp.b0 == 0) {      // <= 128 keys: one pass
-            hipLaunchKernelGGL((rs_hist_kernel<TKey, true>), dim3(rp.nhw), dim3(1024), lds_full, st, tk_in, one, RS_M_TILE, rp.nchunk, kmax, 0,
-                               rp.B1, 1, table1, full);
-            hipLaunchKernelGGL(rs_rowscan_kernel<1>, dim3(rp.B1), dim3(1024), 0, st, table1, rp.nchunk, one, dtotal + 256);
-            hipLaunchKernelGGL((rs_scatter_kernel<TKey, RS_M_TILE, 128, false>), dim3(sgrid), dim3(64 * swpb), lds_sc, st, tk_in, v_in, one, rp.nchunk, kmax,
-                               0, rp.B1, table1, dtotal + 256, (TKey*)nullptr, gaussian_ids_sorted);
-        } else {
-            hipLaunchKernelGGL((rs_hist_kernel<TKey, true>), dim3(rp.nhw), dim3(1024), lds_full, st, tk_in, one, RS_M_TILE, rp.nchunk, kmax, 0,
-                               rp.B0, 1, table0, full);
-            hipLaunchKernelGGL(rs_rowscan_kernel<1>, dim3(rp.B0), dim3(1024), 0, st, table0, rp.nchunk, one, dtotal);
-            hipLaunchKernelGGL((rs_scatter_kernel<TKey, RS_M_TILE, 128, true>), dim3(sgrid), dim3(64 * swpb), lds_sc, st, tk_in, v_in, one, rp.nchunk, kmax,
-                               0, rp.B0, table0, dtotal, tk_mid, v_mid);
-            hipLaunchKernelGGL((rs_hist_kernel<TKey, false>), dim3(hgrid), dim3(256), lds_dig, st, tk_mid, one, RS_M_TILE, rp.nchunk, kmax,
-                               rp.b0, rp.B1, 1, table1, (uint32_t*)nullptr);
-            hipLaunchKernelGGL(rs_rowscan_kernel<1>, dim3(rp.B1), dim3(1024), 0, st, table1, rp.nchunk, one, dtotal + 256);
-            hipLaunchKernelGGL((rs_scatter_kernel<TKey, RS_M_TILE, 128, false>), dim3(sgrid), dim3(64 * swpb), lds_sc, st, tk_mid, v_mid, one, rp.nchunk,
-                               kmax, rp.b0, rp.B1, table1, dtotal + 256, (TKey*)nullptr, gaussian_ids_sorted);
-        }
-        // tile totals (column sums of the whole-key histograms) -> tile starts and the tile_bins
-        // (16 row segments summed in parallel; tile_scan_kernel adds them up per tile)
-        hipLaunchKernelGGL(rs_colsum_kernel<1>, dim3(blocks_for(T1, 256), 16, 1), dim3(256), 0, st, full, one, T1, total);
-        hipLaunchKernelGGL(tile_scan_kernel<16>, dim3(1), dim3(1024), ((size_t)T1 + 16) * sizeof(uint32_t), st, total, T1, tiles, start, tile_bins,
-                           one);
-        if (isect_ids_sorted)
-            hipLaunchKernelGGL(tile_isect_ids_kernel, dim3(blocks_for(I, 256)), dim3(256), 0, st, start, T1,
-                               gaussian_ids_sorted, depths, I, isect_ids_sorted);
+    TKey *tk_in = static_cast<TKey*>(P.tk_in), *tk_out = static_cast<TKey*>(P.tk_out);
+    if (tile_sort == 2) {
+        staged_tile_sort<false, TKey>(P, tsegs, tiles, depths, isect_ids_sorted, gaussian_ids_sorted, tile_bins, st);
         return unerf_check_launch("splat_bin_sort two-pass tile sort");
     }
-    if (own_sort == 1) {   // the one-pass LDS-digit sort (above)
+    if (tile_sort == 1) {
         const TileSortPlan tp = tile_sort_plan(I, tiles);
-        uint32_t* table = reinterpret_cast<uint32_t*>(ws + L.ts_table);
-        uint32_t* segsum = reinterpret_cast<uint32_t*>(ws + L.ts_segsum);
-        uint32_t* start = reinterpret_cast<uint32_t*>(ws + L.ts_start);
+        uint32_t *table = P.ts_table, *segsum = P.ts_segsum, *start = P.ts_start, *total = start + tp.T1 + 1;
         const size_t lds = (size_t)tp.T1 * sizeof(uint32_t);
         const int rps = tp.rows / TS_SEG;
         hipLaunchKernelGGL((tile_hist_kernel<TKey>), dim3(tp.rows), dim3(256), lds, st, tk_in, I, tp.chunk, tp.T1, table);
         hipLaunchKernelGGL(tile_colsum_kernel, dim3(blocks_for(tp.T1, 256), TS_SEG), dim3(256), 0, st, table, rps, tp.T1, segsum);
-        uint32_t* total = start + tp.T1 + 1;
         hipLaunchKernelGGL(tile_segscan_kernel, dim3(blocks_for(tp.T1, 256)), dim3(256), 0, st, segsum, tp.T1, total);
-        hipLaunchKernelGGL(tile_scan_kernel<1>, dim3(1), dim3(1024), ((size_t)tp.T1 + 16) * sizeof(uint32_t), st, total, tp.T1, tiles, start, tile_bins,
-                           rs_one_seg(tp.nblk, I));
+        hipLaunchKernelGGL(tile_scan_kernel<1>, dim3(1), dim3(1024), ((size_t)tp.T1 + 16) * sizeof(uint32_t), st, total, tp.T1, tiles,
+                           start, tile_bins, rs_one_seg(tp.nblk, I));
         hipLaunchKernelGGL(tile_apply_kernel, dim3(blocks_for(tp.T1, 256), TS_SEG), dim3(256), 0, st, table, rps, tp.T1, segsum,
                            start);
         hipLaunchKernelGGL((tile_scatter_kernel<TKey>), dim3(UNERF_SPLAT_XCD ? ((tp.nblk + 7) / 8) * 8 : tp.nblk), dim3(64), lds, st,
-                           tk_in, v_in, I, tp.chunk, tp.T1, table, gaussian_ids_sorted);
+                           tk_in, P.v_in, I, tp.chunk, tp.T1, table, gaussian_ids_sorted);
         if (isect_ids_sorted)
             hipLaunchKernelGGL(tile_isect_ids_kernel, dim3(blocks_for(I, 256)), dim3(256), 0, st, start, tp.T1,
                                gaussian_ids_sorted, depths, I, isect_ids_sorted);
         return unerf_check_launch("splat_bin_sort tile sort");
     }
-    hipError_t e = hipcub::DeviceRadixSort::SortPairs(ws + L.tmp, tmp_bytes, tk_in, tk_out, v_in, gaussian_ids_sorted,
-                                                      (int)I, 0, bits, st);
+    e = hipcub::DeviceRadixSort::SortPairs(P.tmp, tmp_bytes, tk_in, tk_out, P.v_in, gaussian_ids_sorted, (int)I, 0, bits, st);
     if (e != hipSuccess) {
         unerf_set_error("splat_bin_sort: tile sort: %s", hipGetErrorString(e));
         return UNERF_ERR_HIP;
@@ -1671,83 +1801,30 @@ extern "C" int unerf_splat_bin_sort(const float* xys, const float* depths, const
     const SortWs L = sort_ws_layout(N, I);
     UNERF_REQUIRE(workspace_bytes >= L.total, "splat_bin_sort: workspace %lld < %lld bytes (unerf_splat_sort_workspace_bytes)",
                   (long long)workspace_bytes, (long long)L.total);
-    char* ws = (char*)workspace;
-    size_t tmp_bytes = (size_t)(L.dkey_in - L.tmp);
-    uint32_t* dk_in = reinterpret_cast<uint32_t*>(ws + L.dkey_in);
-    uint32_t* dk_out = reinterpret_cast<uint32_t*>(ws + L.dkey_out);
-    int32_t* id_in = reinterpret_cast<int32_t*>(ws + L.id_in);
-    int32_t* order = reinterpret_cast<int32_t*>(ws + L.order);
-    int32_t* counts = reinterpret_cast<int32_t*>(ws + L.counts);
-    int32_t* cum_sorted = reinterpret_cast<int32_t*>(ws + L.cum);
-    // 1. splats in depth order (stable: equal depths keep their index order)
-    hipError_t e = hipSuccess;
+    const SortPtrs P = sort_ws_ptrs(workspace, L);
+    // one segment each: the depth passes' chunks, and the tile passes' -- not padded
+    const RsSegs<1> dsegs = rs_one_seg((int)((N + RS_M_DEPTH - 1) / RS_M_DEPTH), N);
+    const RsSegs<1> tsegs = rs_one_seg(rs_tile_plan(I, tbx * tby + 1).nchunk, I);
+    // the alternates: asked for by the environment, or an image beyond the staged tile passes (more than TS_MAX_T1 - 1 tiles;
+    // up to there the keys have 16 bits: the staged passes' LDS images are sized for them)
     const char* denv = getenv("UNERF_SPLAT_DEPTH_SORT");
-    if (denv && strcmp(denv, "rocprim") == 0) {      // rocprim's stable sort (kept for A/B runs and the identity test)
-        hipLaunchKernelGGL(depth_keys_kernel, dim3(blocks_for(N, 256)), dim3(256), 0, st, depths, radii, N, dk_in, id_in);
-        e = depth_sort_pairs(ws + L.tmp, tmp_bytes, dk_in, dk_out, id_in, order, N, st);
-        if (e != hipSuccess) {
-            unerf_set_error("splat_bin_sort: depth sort: %s", hipGetErrorString(e));
-            return UNERF_ERR_HIP;
-        }
-    } else {      // four staged 8-bit LSD passes (rs_* kernels); the last one writes `order`
-        const int nchunk = (int)((N + RS_M_DEPTH - 1) / RS_M_DEPTH), grid = (nchunk + 3) / 4, hgrid = grid;
-        uint32_t* table = reinterpret_cast<uint32_t*>(ws + L.ds_table);
-        uint32_t* dtotal = reinterpret_cast<uint32_t*>(ws + L.ds_total);
-        const size_t lds_sc = 4 * (size_t)RsLds<RS_M_DEPTH, 256, uint32_t>::WAVE_WORDS * sizeof(uint32_t), lds_dig = 1024 * sizeof(uint32_t);
-        hipLaunchKernelGGL(depth_keys_kernel, dim3(blocks_for(N, 256)), dim3(256), 0, st, depths, radii, N, dk_out, order);
-        const RsSegs<1> one = rs_one_seg(nchunk, N);
-        uint32_t* kin = dk_out; uint32_t* kout = dk_in;
-        int32_t* vin = order; int32_t* vout = id_in;
-        for (int p = 0; p < 4; ++p) {      // (dk_out, order) -> (dk_in, id_in) -> (dk_out, order) -> (dk_in, id_in) -> order
-            hipLaunchKernelGGL((rs_hist_kernel<uint32_t, false>), dim3(hgrid), dim3(256), lds_dig, st, kin, one, RS_M_DEPTH, nchunk, 0xFFFFFFFFu,
-                               8 * p, 256, 1, table, (uint32_t*)nullptr);
-            hipLaunchKernelGGL(rs_rowscan_kernel<1>, dim3(256), dim3(1024), 0, st, table, nchunk, one, dtotal);
-            if (p < 3)
-                hipLaunchKernelGGL((rs_scatter_kernel<uint32_t, RS_M_DEPTH, 256, true>), dim3(grid), dim3(256), lds_sc, st, kin, vin, one, nchunk,
-                                   0xFFFFFFFFu, 8 * p, 256, table, dtotal, kout, vout);
-            else
-                hipLaunchKernelGGL((rs_scatter_kernel<uint32_t, RS_M_DEPTH, 256, false, true>), dim3(grid), dim3(256), lds_sc, st, kin, vin, one, nchunk,
-                                   0xFFFFFFFFu, 8 * p, 256, table, dtotal, (uint32_t*)nullptr, order, radii, cum_tiles_hit, counts);
-            uint32_t* tk = kin; kin = kout; kout = tk;
-            int32_t* tv = vin; vin = vout; vout = tv;
-        }
-        int rc = unerf_check_launch("splat_bin_sort depth sort");
-        if (rc) return rc;
+    const char* tenv = getenv("UNERF_SPLAT_TILE_SORT");
+    const bool rocprim_depth = denv && strcmp(denv, "rocprim") == 0, rocprim_scan = use_rocprim_scan();
+    int tile_sort = 0;
+    if (tbx * tby + 1 <= TS_MAX_T1 && !(tenv && strcmp(tenv, "radix") == 0)) tile_sort = (tenv && strcmp(tenv, "onepass") == 0) ? 1 : 2;
+    if (rocprim_depth || rocprim_scan || tile_sort != 2) {
+        const int bits = tile_bits(H, W, block_width);      // (the sentinel tile `tbx * tby` included)
+        auto alt = bits <= 16 ? bin_sort_alternates<uint16_t> : bin_sort_alternates<uint32_t>;
+        return alt(rocprim_depth, rocprim_scan, tile_sort, P, dsegs, tsegs, xys, depths, radii, cum_tiles_hit, tight_conics,
+                   tight_opacities, block_width, tbx, tby, bits, isect_ids_sorted, gaussian_ids_sorted, tile_bins, st);
     }
-    // 2. where each depth-ordered splat's intersections start
-    if (denv && strcmp(denv, "rocprim") == 0)      // (the staged depth sort's last pass has written them)
-        hipLaunchKernelGGL(sorted_counts_kernel, dim3(blocks_for(N, 256)), dim3(256), 0, st, order, radii, cum_tiles_hit, N,
-                           counts);
-    tmp_bytes = (size_t)(L.dkey_in - L.tmp);
-    if (!use_rocprim_scan()) {
-        own_inclusive_scan(counts, cum_sorted, N, reinterpret_cast<int32_t*>(ws + L.tmp), st);
-    } else {
-        e = hipcub::DeviceScan::InclusiveSum(ws + L.tmp, tmp_bytes, counts, cum_sorted, (int)N, st);
-        if (e != hipSuccess) {
-            unerf_set_error("splat_bin_sort: scan: %s", hipGetErrorString(e));
-            return UNERF_ERR_HIP;
-        }
-    }
-    // 3. emit in depth order, stable sort by tile (two staged LSD passes when the image has <= TS_MAX_T1 - 1 tiles; rocprim's
-    // radix sort beyond that or when UNERF_SPLAT_TILE_SORT=radix asks for it, the round-4 one-pass sort with =onepass: A/B
-    // timing and the identity tests), tile ranges + ids
-    const int bits = tile_bits(H, W, block_width);      // (the sentinel tile `tbx * tby` included)
-    const char* env = getenv("UNERF_SPLAT_TILE_SORT");
-    int own_sort = 0;      // 0: rocprim radix sort, 1: one-pass LDS-digit sort, 2: two-pass LSD sort (default)
-    if (tbx * tby + 1 <= TS_MAX_T1 && !(env && strcmp(env, "radix") == 0)) own_sort = (env && strcmp(env, "onepass") == 0) ? 1 : 2;
-    tmp_bytes = (size_t)(L.dkey_in - L.tmp);
-    if (bits <= 16)
-        return bin_sort_impl<uint16_t>(xys, depths, radii, order, cum_sorted, tight_conics, tight_opacities, N, I, block_width, tbx, tby, bits,
-                                       own_sort, isect_ids_sorted, gaussian_ids_sorted, tile_bins, ws, L, tmp_bytes, st);
-    return bin_sort_impl<uint32_t>(xys, depths, radii, order, cum_sorted, tight_conics, tight_opacities, N, I, block_width, tbx, tby, bits,
-                                   own_sort, isect_ids_sorted, gaussian_ids_sorted, tile_bins, ws, L, tmp_bytes, st);
+    const int rc = bin_sort_body<false>("splat_bin_sort", P, dsegs, tsegs, xys, depths, radii, cum_tiles_hit, tight_conics,
+                                        tight_opacities, block_width, tbx, tby, isect_ids_sorted, gaussian_ids_sorted, tile_bins, st);
+    return rc ? rc : unerf_check_launch("splat_bin_sort two-pass tile sort");
 }
 
-// B views of one splat set in the same launches (unerf_splat_bin_sort_batch).  The splats of all views are one stream of B N
-// (view-major: id v N + i); every staged pass runs segment by segment (RsSegs: one segment per view), so each view's order is
-// exactly its single-view order -- depth, then splat index on ties; tile, then depth order -- and its pairs leave contiguous,
-// view after view.  The keys stay the per-view tile ids (13 bits at 1080p): a combined (view, tile) key would outgrow the LDS
-// tables from two 1080p views on.
+// B views of one splat set in the same launches: bin_sort_body over one segment per view.  Its own: the checks, each view's
+// chunks of the tile passes padded to whole 16-chunk histogram workgroups, and the table-fit check that padding calls for.
 extern "C" int unerf_splat_bin_sort_batch(const float* xys, const float* depths, const int32_t* radii,
                                           const int32_t* cum_tiles_hit, int B, int64_t N, const int64_t* isects_host, int H,
                                           int W, int block_width, const float* tight_conics, const float* tight_opacities,
@@ -1773,15 +1850,20 @@ extern "C" int unerf_splat_bin_sort_batch(const float* xys, const float* depths,
     UNERF_REQUIRE(tiles <= UNERF_SPLAT_BATCH_MAX_TILES, "splat_bin_sort_batch: %d tiles, the batched tile sort serves up to %d",
                   tiles, UNERF_SPLAT_BATCH_MAX_TILES);
     UNERF_REQUIRE(I == 0 || gaussian_ids_sorted, "splat_bin_sort_batch: null output");
-    const SortWs L = sort_ws_layout(N, I, B, true);
-    {   // the tile passes' tables for this batch's own chunk plan must fit what the layout reserved for them
-        int64_t nchunk = 0;
-        for (int v = 0; v < B; ++v) nchunk += ((isects_host[v] + RS_M_TILE - 1) / RS_M_TILE + 15) / 16 * 16;
-        const int64_t need = ((int64_t)256 * nchunk + (nchunk / 16) * (tiles + 1)) * 4;
-        UNERF_REQUIRE(need <= L.ts_segsum - L.ts_table,
-                      "splat_bin_sort_batch: tile tables of %lld bytes exceed the %lld the workspace layout reserves (internal)",
-                      (long long)need, (long long)(L.ts_segsum - L.ts_table));
+    // one segment per view: cpv depth chunks each; the view's own tile chunks, in whole histogram workgroups
+    const int cpv = (int)((N + RS_M_DEPTH - 1) / RS_M_DEPTH);
+    RsSegs<UNERF_SPLAT_MAX_VIEWS> dsegs, tsegs;
+    dsegs.n = tsegs.n = B; dsegs.cb[0] = tsegs.cb[0] = 0; dsegs.pb[0] = tsegs.pb[0] = 0;
+    for (int v = 0; v < B; ++v) {
+        const int64_t c = (isects_host[v] + RS_M_TILE - 1) / RS_M_TILE;
+        dsegs.cb[v + 1] = (v + 1) * cpv; dsegs.pb[v + 1] = (int64_t)(v + 1) * N;
+        tsegs.cb[v + 1] = tsegs.cb[v] + (int)(((c + 15) / 16) * 16); tsegs.pb[v + 1] = tsegs.pb[v] + isects_host[v];
     }
+    const SortWs L = sort_ws_layout(N, I, B, true);
+    int64_t need, have;
+    UNERF_REQUIRE(rs_tile_tables_fit(L, tsegs.cb[B], tiles + 1, need, have),
+                  "splat_bin_sort_batch: tile tables of %lld bytes exceed the %lld the workspace layout reserves (internal)",
+                  (long long)need, (long long)have);
     UNERF_REQUIRE(workspace_bytes >= L.total,
                   "splat_bin_sort_batch: workspace %lld < %lld bytes (unerf_splat_sort_workspace_bytes_batch)",
                   (long long)workspace_bytes, (long long)L.total);
@@ -1789,99 +1871,10 @@ extern "C" int unerf_splat_bin_sort_batch(const float* xys, const float* depths,
     if (hipMemsetAsync(tile_bins, 0, (size_t)B * tiles * 2 * sizeof(int32_t), st) != hipSuccess)
         return unerf_check_launch("splat_bin_sort_batch memset");
     if (I == 0) return UNERF_OK;
-    const int64_t NB = (int64_t)B * N;
-    char* ws = (char*)workspace;
-    uint32_t* dk_in = reinterpret_cast<uint32_t*>(ws + L.dkey_in);
-    uint32_t* dk_out = reinterpret_cast<uint32_t*>(ws + L.dkey_out);
-    int32_t* id_in = reinterpret_cast<int32_t*>(ws + L.id_in);
-    int32_t* order = reinterpret_cast<int32_t*>(ws + L.order);
-    int32_t* counts = reinterpret_cast<int32_t*>(ws + L.counts);
-    int32_t* cum_sorted = reinterpret_cast<int32_t*>(ws + L.cum);
-    // 1. each view's splats in depth order, view after view: four staged 8-bit LSD passes, segment by segment
-    {
-        const int cpv = (int)((N + RS_M_DEPTH - 1) / RS_M_DEPTH), nchunk = B * cpv, grid = (nchunk + 3) / 4;
-        RsSegs<UNERF_SPLAT_MAX_VIEWS> sg;
-        sg.n = B;
-        for (int v = 0; v <= B; ++v) { sg.cb[v] = v * cpv; sg.pb[v] = (int64_t)v * N; }
-        uint32_t* table = reinterpret_cast<uint32_t*>(ws + L.ds_table);
-        uint32_t* dtotal = reinterpret_cast<uint32_t*>(ws + L.ds_total);
-        const size_t lds_sc = 4 * (size_t)RsLds<RS_M_DEPTH, 256, uint32_t>::WAVE_WORDS * sizeof(uint32_t), lds_dig = 1024 * sizeof(uint32_t);
-        hipLaunchKernelGGL(depth_keys_kernel, dim3(blocks_for(NB, 256)), dim3(256), 0, st, depths, radii, NB, dk_out, order);
-        uint32_t* kin = dk_out; uint32_t* kout = dk_in;
-        int32_t* vin = order; int32_t* vout = id_in;
-        for (int p = 0; p < 4; ++p) {
-            hipLaunchKernelGGL((rs_hist_kernel<uint32_t, false, true>), dim3(grid), dim3(256), lds_dig, st, kin, sg, RS_M_DEPTH, nchunk, 0xFFFFFFFFu,
-                               8 * p, 256, 1, table, (uint32_t*)nullptr);
-            hipLaunchKernelGGL(rs_rowscan_kernel<UNERF_SPLAT_MAX_VIEWS>, dim3(256, B), dim3(1024), 0, st, table, nchunk, sg, dtotal);
-            if (p < 3)
-                hipLaunchKernelGGL((rs_scatter_kernel<uint32_t, RS_M_DEPTH, 256, true, false, true>), dim3(grid), dim3(256), lds_sc, st, kin, vin, sg, nchunk,
-                                   0xFFFFFFFFu, 8 * p, 256, table, dtotal, kout, vout);
-            else
-                hipLaunchKernelGGL((rs_scatter_kernel<uint32_t, RS_M_DEPTH, 256, false, true, true>), dim3(grid), dim3(256), lds_sc, st, kin, vin, sg, nchunk,
-                                   0xFFFFFFFFu, 8 * p, 256, table, dtotal, (uint32_t*)nullptr, order, radii, cum_tiles_hit, counts);
-            uint32_t* tk = kin; kin = kout; kout = tk;
-            int32_t* tv = vin; vin = vout; vout = tv;
-        }
-        int rc = unerf_check_launch("splat_bin_sort_batch depth sort");
-        if (rc) return rc;
-    }
-    // 2. where each splat's intersections start: one scan over the B N depth-ordered counts (views stay contiguous)
-    own_inclusive_scan(counts, cum_sorted, NB, reinterpret_cast<int32_t*>(ws + L.tmp), st);
-    // 3. emission in that order, then the two staged tile passes segment by segment (view v's pairs: [pb[v], pb[v + 1]))
-    uint16_t* tk_in = reinterpret_cast<uint16_t*>(ws + L.tkey_in);
-    uint16_t* tk_mid = reinterpret_cast<uint16_t*>(ws + L.tkey_out);
-    int32_t* v_in = reinterpret_cast<int32_t*>(ws + L.val_in);
-    int32_t* v_mid = reinterpret_cast<int32_t*>(ws + L.val_mid);
-    if (tight_conics)
-        hipLaunchKernelGGL((map_intersects_kernel<uint16_t, 8>), dim3(blocks_for(NB, 32)), dim3(256), 0, st, xys, radii, order,
-                           cum_sorted, NB, block_width, tbx, tby, tight_conics, tight_opacities, tk_in, v_in);
-    else
-        hipLaunchKernelGGL((map_intersects_kernel<uint16_t, 16>), dim3(blocks_for(NB, 16)), dim3(256), 0, st, xys, radii, order,
-                           cum_sorted, NB, block_width, tbx, tby, tight_conics, tight_opacities, tk_in, v_in);
-    const int T1 = tiles + 1;
-    const RsTilePlan rp = rs_tile_plan(I, T1);      // (digit split only: the chunks are laid out per view below)
-    RsSegs<UNERF_SPLAT_MAX_VIEWS> sg;
-    sg.n = B; sg.cb[0] = 0; sg.pb[0] = 0;
-    for (int v = 0; v < B; ++v) {
-        const int64_t c = (isects_host[v] + RS_M_TILE - 1) / RS_M_TILE;
-        sg.cb[v + 1] = sg.cb[v] + (int)(((c + 15) / 16) * 16);      // whole histogram workgroups per view
-        sg.pb[v + 1] = sg.pb[v] + isects_host[v];
-    }
-    const int nchunk = sg.cb[B], nhw = nchunk / 16;
-    uint32_t* table0 = reinterpret_cast<uint32_t*>(ws + L.ts_table);     // [B0][nchunk]
-    uint32_t* table1 = table0 + (size_t)128 * nchunk;                      // [B1][nchunk]
-    uint32_t* full = table1 + (size_t)128 * nchunk;                        // [nhw][T1]
-    uint32_t* dtotal0 = reinterpret_cast<uint32_t*>(ws + L.ts_segsum);    // [B][256] per pass
-    uint32_t* dtotal1 = dtotal0 + (size_t)256 * B;
-    uint32_t* total = dtotal1 + (size_t)256 * B;                           // [B][16][T1]
-    uint32_t* start = reinterpret_cast<uint32_t*>(ws + L.ts_start);       // [B][T1 + 1]
-    const uint32_t kmax = (uint32_t)tiles;
-    const size_t lds_full = (16 * 256 + (size_t)T1) * sizeof(uint32_t), lds_dig = 1024 * sizeof(uint32_t);
-    const size_t lds_sc = (size_t)RsLds<RS_M_TILE, 128, uint16_t>::WAVE_WORDS * sizeof(uint32_t);
-    const int hgrid = (nchunk + 3) / 4;
-    if (rp.b0 == 0) {      // <= 128 keys: one pass
-        hipLaunchKernelGGL((rs_hist_kernel<uint16_t, true, true>), dim3(nhw), dim3(1024), lds_full, st, tk_in, sg, RS_M_TILE, nchunk, kmax, 0,
-                           rp.B1, 1, table1, full);
-        hipLaunchKernelGGL(rs_rowscan_kernel<UNERF_SPLAT_MAX_VIEWS>, dim3(rp.B1, B), dim3(1024), 0, st, table1, nchunk, sg, dtotal1);
-        hipLaunchKernelGGL((rs_scatter_kernel<uint16_t, RS_M_TILE, 128, false, false, true>), dim3(nchunk), dim3(64), lds_sc, st, tk_in, v_in, sg, nchunk, kmax,
-                           0, rp.B1, table1, dtotal1, (uint16_t*)nullptr, gaussian_ids_sorted);
-    } else {
-        hipLaunchKernelGGL((rs_hist_kernel<uint16_t, true, true>), dim3(nhw), dim3(1024), lds_full, st, tk_in, sg, RS_M_TILE, nchunk, kmax, 0,
-                           rp.B0, 1, table0, full);
-        hipLaunchKernelGGL(rs_rowscan_kernel<UNERF_SPLAT_MAX_VIEWS>, dim3(rp.B0, B), dim3(1024), 0, st, table0, nchunk, sg, dtotal0);
-        hipLaunchKernelGGL((rs_scatter_kernel<uint16_t, RS_M_TILE, 128, true, false, true>), dim3(nchunk), dim3(64), lds_sc, st, tk_in, v_in, sg, nchunk, kmax,
-                           0, rp.B0, table0, dtotal0, tk_mid, v_mid);
-        hipLaunchKernelGGL((rs_hist_kernel<uint16_t, false, true>), dim3(hgrid), dim3(256), lds_dig, st, tk_mid, sg, RS_M_TILE, nchunk, kmax,
-                           rp.b0, rp.B1, 1, table1, (uint32_t*)nullptr);
-        hipLaunchKernelGGL(rs_rowscan_kernel<UNERF_SPLAT_MAX_VIEWS>, dim3(rp.B1, B), dim3(1024), 0, st, table1, nchunk, sg, dtotal1);
-        hipLaunchKernelGGL((rs_scatter_kernel<uint16_t, RS_M_TILE, 128, false, false, true>), dim3(nchunk), dim3(64), lds_sc, st, tk_mid, v_mid, sg, nchunk,
-                           kmax, rp.b0, rp.B1, table1, dtotal1, (uint16_t*)nullptr, gaussian_ids_sorted);
-    }
-    // 4. per view: tile totals -> tile starts (from the view's first slot) and its tile_bins
-    hipLaunchKernelGGL(rs_colsum_kernel<UNERF_SPLAT_MAX_VIEWS>, dim3(blocks_for(T1, 256), 16, B), dim3(256), 0, st, full, sg, T1, total);
-    hipLaunchKernelGGL((tile_scan_kernel<16, UNERF_SPLAT_MAX_VIEWS>), dim3(B), dim3(1024), ((size_t)T1 + 16) * sizeof(uint32_t), st, total, T1, tiles, start,
-                       tile_bins, sg);
-    return unerf_check_launch("splat_bin_sort_batch");
+    const int rc = bin_sort_body<true>("splat_bin_sort_batch", sort_ws_ptrs(workspace, L), dsegs, tsegs, xys, depths, radii,
+                                       cum_tiles_hit, tight_conics, tight_opacities, block_width, tbx, tby, nullptr,
+                                       gaussian_ids_sorted, tile_bins, st);
+    return rc ? rc : unerf_check_launch("splat_bin_sort_batch");
 }
 
 // ======================================================================================
