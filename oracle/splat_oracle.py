@@ -170,9 +170,10 @@ def bin_and_sort(xys, depths, radii, num_tiles_hit, H, W, bw=16):
     return I, cum, keys, vals, bins
 
 
-def rasterize(gids, bins, xys, conics, colors, opacities, H, W, background=None, bw=16):
+def rasterize(gids, bins, xys, conics, colors, opacities, H, W, background=None, bw=16, stop_idx=None):
     """rasterize_forward / nd_rasterize_forward for C channels.  colors [N,C], opacities [N].
-    -> out [H,W,C], final_T [H,W], final_idx [H,W]"""
+    -> out [H,W,C], final_T [H,W], final_idx [H,W].  stop_idx [H,W]: the bounded second pass of csrc/unerf_splat.hip (a pixel
+    visits the indices <= its stop and never applies the 1e-4 stop)"""
     colors, xys, conics, opacities = _f(colors), _f(xys), _f(conics), _f(opacities).reshape(-1)
     C = colors.shape[1]
     bg = np.zeros(C, f32) if background is None else _f(background)
@@ -190,7 +191,10 @@ def rasterize(gids, bins, xys, conics, colors, opacities, H, W, background=None,
             pix = np.zeros(py.shape + (C,), f32)
             done = np.zeros(py.shape, bool)
             cur = np.zeros(py.shape, np.int32)
+            stop_at = None if stop_idx is None else np.asarray(stop_idx)[ys[0]:ys[-1] + 1, xs[0]:xs[-1] + 1]
             for idx in range(r0, r1):
+                if stop_at is not None:
+                    done |= idx > stop_at
                 if done.all():
                     break
                 g = gids[idx]
@@ -201,7 +205,7 @@ def rasterize(gids, bins, xys, conics, colors, opacities, H, W, background=None,
                     alpha = np.minimum(f32(0.999), opacities[g] * np.exp(-sigma))
                 act = ~done & ~((sigma < 0) | (alpha < f32(1.0) / f32(255.0)))
                 nT = T * (f32(1) - alpha)
-                stop = act & (nT <= f32(1e-4))
+                stop = act & (nT <= f32(1e-4)) & (stop_at is None)
                 done |= stop
                 act &= ~stop
                 vis = alpha * T
@@ -212,6 +216,79 @@ def rasterize(gids, bins, xys, conics, colors, opacities, H, W, background=None,
             fT[ys[0]:ys[-1] + 1, xs[0]:xs[-1] + 1] = T
             fidx[ys[0]:ys[-1] + 1, xs[0]:xs[-1] + 1] = cur
     return out, fT, fidx
+
+
+def rasterize_f64(gids, bins, xys, conics, colors, opacities, H, W, background=None, bw=16, stop_idx=None):
+    """The schedule of `rasterize` with every quantity in float64 on the fp32 inputs (the thresholds are the kernel's fp32
+    constants).  stop_idx [H,W]: the bounded pass (a pixel visits the indices <= its stop, blends every pair with sigma >= 0
+    and alpha >= 1/255 and never applies the 1e-4 stop).
+    -> out [H,W,C] f64, final_T [H,W] f64, final_idx [H,W] i32, n_blended [H,W] i32, grazing_ids (sorted, unique).
+
+    grazing_ids: the splats with a (pixel, splat) pair, visited while the pixel was live, on which an fp32 evaluation and this
+    one could decide differently.  With S = |a dx^2 / 2| + |c dy^2 / 2| + |b dx dy| (the magnitude sigma is summed from) and
+    r = 255 o e^-sigma:
+      * |r - 1| < 1e-3 + 1e-5 S r: alpha on 1/255.  1e-3 is ~2,000 x the relative error of an fp32 exp at sigma <= ln 255; the S
+        term covers a sigma that is a small difference of large terms (needles), whose fp32 rounding is ~3e-7 S;
+      * |sigma| < 1e-5 S while r > 0.5: cancellation that could turn the sign of sigma in fp32;
+      * the pair is blended or stopping and |T (1 - alpha) / 1e-4 - 1| < 1e-2: transmittance on the stop (unbounded pass)."""
+    f64 = np.float64
+    colors, xys, conics = _f(colors).astype(f64), _f(xys).astype(f64), _f(conics).astype(f64)
+    opacities = _f(opacities).reshape(-1).astype(f64)
+    C = colors.shape[1]
+    bg = np.zeros(C, f64) if background is None else _f(background).astype(f64)
+    a_max, a_min, t_min = f64(f32(0.999)), f64(f32(1.0) / f32(255.0)), f64(f32(1e-4))
+    tbx, tby = (W + bw - 1) // bw, (H + bw - 1) // bw
+    out = np.zeros((H, W, C), f64)
+    fT = np.ones((H, W), f64)
+    fidx = np.zeros((H, W), np.int32)
+    nbl = np.zeros((H, W), np.int32)
+    grazing = set()
+    for ty in range(tby):
+        for tx in range(tbx):
+            r0, r1 = bins[ty * tbx + tx]
+            ys = np.arange(ty * bw, min((ty + 1) * bw, H))
+            xs = np.arange(tx * bw, min((tx + 1) * bw, W))
+            win = (slice(ys[0], ys[-1] + 1), slice(xs[0], xs[-1] + 1))
+            py, px = np.meshgrid(ys.astype(f64) + 0.5, xs.astype(f64) + 0.5, indexing="ij")
+            T = np.ones(py.shape, f64)
+            pix = np.zeros(py.shape + (C,), f64)
+            done = np.zeros(py.shape, bool)
+            cur = np.zeros(py.shape, np.int32)
+            cnt = np.zeros(py.shape, np.int32)
+            stop_at = None if stop_idx is None else np.asarray(stop_idx)[win]
+            for idx in range(r0, r1):
+                if stop_at is not None:
+                    done |= idx > stop_at
+                if done.all():
+                    break
+                g = gids[idx]
+                dx, dy = xys[g, 0] - px, xys[g, 1] - py
+                ca, cb, cc = conics[g]
+                t1, t2, t3 = 0.5 * ca * dx * dx, 0.5 * cc * dy * dy, cb * dx * dy
+                sigma = t1 + t2 + t3
+                S = np.abs(t1) + np.abs(t2) + np.abs(t3)
+                with np.errstate(over="ignore", invalid="ignore"):
+                    raw = opacities[g] * np.exp(-sigma)
+                    alpha = np.minimum(a_max, raw)
+                    r = 255.0 * raw
+                    act = ~done & ~((sigma < 0) | (alpha < a_min))
+                    nT = T * (1.0 - alpha)
+                    graze = (np.abs(r - 1.0) < 1e-3 + 1e-5 * S * r) | ((np.abs(sigma) < 1e-5 * S) & (r > 0.5))
+                    if stop_at is None:
+                        graze |= act & (np.abs(nT / t_min - 1.0) < 1e-2)
+                if (graze & ~done).any():
+                    grazing.add(int(g))
+                stop = act & (nT <= t_min) & (stop_at is None)
+                done |= stop
+                act &= ~stop
+                vis = alpha * T
+                pix[act] += colors[g][None, :] * vis[act][:, None]
+                T[act] = nT[act]
+                cur[act] = idx
+                cnt[act] += 1
+            out[win] = pix + T[..., None] * bg
+            fT[win], fidx[win], nbl[win] = T, cur, cnt
+    return out, fT, fidx, nbl, np.array(sorted(grazing), np.int64)
 
 
 def viewmat_from_c2w(c2w):
