@@ -612,6 +612,61 @@ int unerf_laplace_depth_weights_views(const float* density_mu, const float* dens
  * var [N,C] (unbiased, K-1; NULL ok).  Two-pass in fp32 like torch. */
 int unerf_moments(const float* x, int K, int64_t N, int C, float* mean, float* var, void* stream);
 
+/* ------------------------------------- fused ensemble reduce over B views --
+ * The stack -> unerf_moments -> key loop chain of models/ensemble/ensemble_pipeline.py:159-189 for B views x every member
+ * key x M members in ONE launch, whatever B, M and the key count are; no host-device synchronisation.
+ *
+ * Sources are read in place through `table`, a DEVICE array [B][n_keys][M] of pointers: entry (v, k, j) is member j's
+ * tensor of input key k in view v, element p channel c at ptr[p * keys[k].stride + c] (no stacked copy; a channel slice
+ * of wider rows, such as columns 4..6 of the composite's [R,8] rows, is stride 8 with the pointer moved to column 4).
+ * keys[k] (host) describes input key k: `channels` C, `n` elements (the pixels of an image key, 1 for a non-image key
+ * such as a splat member's background [3]) and the element stride in floats (>= C).
+ *
+ * Per (view, key, element, channel) the mean and unbiased variance over the members are unerf_moments's, bit for bit
+ * (the same device function: s += x_j in member order, m = s / M, q += (x_j - m)^2, q / (M - 1); M = 1: NaN variance).
+ * plan[o] (host) asks for one output block [keys[key].n, C_out], written contiguously at
+ * arena[v * view_stride + plan[o].offset] for every view v:
+ *   UNERF_ENS_MEAN          C_out = C   mean
+ *   UNERF_ENS_VAR           C_out = C   variance
+ *   UNERF_ENS_VAR_CMEAN     C_out = 1   epi  = ((var_0 + var_1) + ...) / C            (channel order, IEEE divide)
+ *   UNERF_ENS_ALEA_CMEAN    C_out = 1   alea = ((a_0 + a_1) + ...) / C_aux,  a = the member mean of key `aux`
+ *   UNERF_ENS_EPI_ALEA      C_out = 1   epi + alea
+ *   UNERF_ENS_EPI_ALEA_SQRT C_out = 1   sqrtf(epi + alea)                              (IEEE square root)
+ *   UNERF_ENS_STD_CMEAN     C_out = 1   ((sqrtf(var_0) + sqrtf(var_1)) + ...) / C
+ * `aux` is read by the three alea statistics only (keys[aux].n must equal keys[key].n), else ignored.  A (key, statistic)
+ * pair may appear once.  Blocks must lie inside [0, view_stride) without overlapping, B * view_stride <= arena_floats.
+ *
+ * UNERF_ERR_ARG before any launch or device call: B > UNERF_NERF_MAX_VIEWS, n_keys outside [1, UNERF_ENS_MAX_KEYS],
+ * M outside [1, UNERF_ENS_MAX_MEMBERS], channels outside [1, UNERF_ENS_MAX_CHANNELS], stride < channels, negative n, a
+ * bad plan entry, a null table / arena while there is something to reduce.  B = 0, n_out = 0 or every n = 0: success,
+ * nothing launched. */
+#define UNERF_ENS_MAX_KEYS 32
+#define UNERF_ENS_MAX_MEMBERS 64
+#define UNERF_ENS_MAX_CHANNELS 64
+#define UNERF_ENS_MEAN 0
+#define UNERF_ENS_VAR 1
+#define UNERF_ENS_VAR_CMEAN 2
+#define UNERF_ENS_ALEA_CMEAN 3
+#define UNERF_ENS_EPI_ALEA 4
+#define UNERF_ENS_EPI_ALEA_SQRT 5
+#define UNERF_ENS_STD_CMEAN 6
+#define UNERF_ENS_STATS 7
+typedef struct {            /* host struct: one input key */
+    int32_t channels;       /* C */
+    int32_t stride;         /* floats between consecutive elements of one source (>= C) */
+    int64_t n;              /* elements: pixels of an image key, 1 for a non-image key */
+} unerf_ens_key;
+typedef struct {            /* host struct: one output block per view */
+    int32_t stat;           /* UNERF_ENS_* */
+    int32_t key;            /* input key whose moments it is made of */
+    int32_t aux;            /* input key whose member mean is the aleatoric term (alea statistics only) */
+    int32_t reserved;       /* 0 */
+    int64_t offset;         /* floats from the start of the view's part of the arena */
+} unerf_ens_out;
+int unerf_ensemble_reduce(const float* const* table /* device */, int B, int n_keys, int M, const unerf_ens_key* keys /* host */,
+                          const unerf_ens_out* plan /* host */, int n_out, int64_t view_stride, float* arena,
+                          int64_t arena_floats, void* stream);
+
 /* ------------------------------------------------- per-image eval metrics --
  * Replaces the torch / numpy chain behind one image's entry of metrics.json: get_image_metrics_and_images_unc and
  * get_unc_metrics_depth (scripts/eval_uncertainty.py:306-412, 647-813: error definitions, psnr, mse / rmse, Gaussian

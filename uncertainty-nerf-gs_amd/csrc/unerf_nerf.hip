@@ -4600,22 +4600,74 @@ extern "C" int unerf_laplace_depth_weights_views(const float* density_mu, const 
 // ======================================================================================
 // 7. moments over the leading (pass / member) dimension
 // ======================================================================================
+// The two-pass fp32 moments of NC neighbouring channels of one element over its K sources, x(k, c) = source k's value of
+// channel c: what torch.stack(...).mean(0) / .var(0) compute.  ONE statement of the order of operations for moments_kernel
+// and ensemble_reduce_kernel, so that the two agree bit for bit: per channel s += x_k for k = 0 .. K-1, m = s / K,
+// q += (x_k - m)^2 in the same order, q / (K - 1).
+// The loads of MOMENTS_UNROLL sources are issued together and then added in source order -- the additions are the ones of the
+// plain loop, the memory latencies overlap instead of following one another.
+// The second pass reads the sources again: K is a run-time count (up to 64 members of up to 4 channels), so the values cannot
+// stay in registers without spilling, and the re-read comes from lines the same wave has just fetched (TCP, else L2).
+#define MOMENTS_UNROLL 8
+template <int NC, class Load>
+__device__ __forceinline__ void moments_of(Load x, int K, bool want_var, float (&mean)[NC], float (&var)[NC]) {
+    constexpr int U = NC == 1 ? MOMENTS_UNROLL : MOMENTS_UNROLL / 2;
+    float s[NC];
+#pragma unroll
+    for (int c = 0; c < NC; ++c) s[c] = 0.f;
+    int k = 0;
+    for (; k + U <= K; k += U) {
+        float t[U][NC];
+#pragma unroll
+        for (int u = 0; u < U; ++u)
+#pragma unroll
+            for (int c = 0; c < NC; ++c) t[u][c] = x(k + u, c);
+#pragma unroll
+        for (int u = 0; u < U; ++u)
+#pragma unroll
+            for (int c = 0; c < NC; ++c) s[c] += t[u][c];
+    }
+    for (; k < K; ++k)
+#pragma unroll
+        for (int c = 0; c < NC; ++c) s[c] += x(k, c);
+#pragma unroll
+    for (int c = 0; c < NC; ++c) mean[c] = s[c] / (float)K;
+    if (!want_var) return;
+    float q[NC];
+#pragma unroll
+    for (int c = 0; c < NC; ++c) q[c] = 0.f;
+    for (k = 0; k + U <= K; k += U) {
+        float t[U][NC];
+#pragma unroll
+        for (int u = 0; u < U; ++u)
+#pragma unroll
+            for (int c = 0; c < NC; ++c) t[u][c] = x(k + u, c);
+#pragma unroll
+        for (int u = 0; u < U; ++u)
+#pragma unroll
+            for (int c = 0; c < NC; ++c) {
+                float d = t[u][c] - mean[c];
+                q[c] += d * d;
+            }
+    }
+    for (; k < K; ++k)
+#pragma unroll
+        for (int c = 0; c < NC; ++c) {
+            float d = x(k, c) - mean[c];
+            q[c] += d * d;
+        }
+#pragma unroll
+    for (int c = 0; c < NC; ++c) var[c] = q[c] / (float)(K - 1);  // K==1 -> NaN, as torch.var(unbiased) does
+}
+
 __global__ __launch_bounds__(256) void moments_kernel(const float* __restrict__ x, int K, int64_t NC,
                                                       float* __restrict__ mean, float* __restrict__ var) {
     int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= NC) return;
-    float s = 0.f;
-    for (int k = 0; k < K; ++k) s += x[(int64_t)k * NC + i];
-    float m = s / (float)K;
-    mean[i] = m;
-    if (var) {
-        float q = 0.f;
-        for (int k = 0; k < K; ++k) {
-            float d = x[(int64_t)k * NC + i] - m;
-            q += d * d;
-        }
-        var[i] = q / (float)(K - 1);  // K==1 -> NaN, as torch.var(unbiased) does
-    }
+    float m[1], v[1];
+    moments_of<1>([&](int k, int) { return x[(int64_t)k * NC + i]; }, K, var != nullptr, m, v);
+    mean[i] = m[0];
+    if (var) var[i] = v[0];
 }
 
 extern "C" int unerf_moments(const float* x, int K, int64_t N, int C, float* mean, float* var, void* stream) {
@@ -4625,4 +4677,173 @@ extern "C" int unerf_moments(const float* x, int K, int64_t N, int C, float* mea
     hipLaunchKernelGGL(moments_kernel, dim3(blocks_for(N * C, 256)), dim3(256), 0, (hipStream_t)stream, x, K, N * C,
                        mean, var);
     return unerf_check_launch("moments");
+}
+
+// ======================================================================================
+// 8. fused ensemble reduce: B views x every member key x M members in one launch
+// ======================================================================================
+// One thread per (view, input key, element): it walks the key's channels, takes their moments over the members with
+// moments_of, stores the blocks the plan asks for and keeps the running channel sums of the derived keys, so a derived
+// value never leaves the thread.  The aleatoric term is the member mean of ANOTHER key (rgb -> rgb_var): the thread forms it
+// again from that key's sources -- the same additions in the same order as the thread that owns the key, hence the same
+// bits -- instead of waiting for a second launch.
+// Memory: the kernel is bandwidth-bound.  Lanes are consecutive elements, so a [n,1] key is one 256-byte run per wave and
+// load.  [n,3] rows (12-byte stride) spread a wave's load over six 128-byte lines; the three channels of a row are loaded
+// back to back (moments_of<3>), so the lines are fetched once and the other two loads hit them.  A 3-channel slice of [n,8]
+// rows (32-byte stride) touches sixteen lines of which 12 bytes in 32 are used, whatever the mapping is.  Channels go in
+// groups of 4, then 3, then 1, each group with 12 to 16 loads in flight per lane.  The variance pass re-reads (see
+// moments_of).
+// Block order: the keys of a member are often slices of the SAME rows (rgb, accumulation, depth ... of the composite's
+// [R,8] rows), so the blocks that work on one pixel range for different keys should meet in one L2.  Blocks are dealt
+// round-robin over the 8 XCDs, each with its own L2; blockIdx.x = ((g * keys + k) * 8 + x) puts pixel block 8 g + x of
+// every key k on XCD x, one key after the other: the first key's block brings the rows in, the others hit them.  (Key-major
+// order -- all blocks of key 0, then key 1 ... -- fetched every row once per key: measured 0.84 x the per-view loop on
+// active-nerfacto keys at 800 x 800.)  A key with fewer blocks than the largest leaves its surplus blocks idle.
+struct EnsKeyDev {
+    int64_t n;                       // elements
+    int64_t out[UNERF_ENS_STATS];    // offset of the statistic's block inside a view's part of the arena, -1: not asked for
+    int32_t C, stride;
+    int32_t aux, aux_C, aux_stride;  // aux < 0: no aleatoric term
+    int32_t pad;
+};
+struct EnsArgs {
+    EnsKeyDev key[UNERF_ENS_MAX_KEYS];
+    const float* const* table;       // [B][n_keys][M]
+    float* arena;
+    int64_t view_stride;
+    int32_t n_keys, M;
+    int32_t n_used;                  // keys something is asked of: used[0 .. n_used)
+    uint8_t used[UNERF_ENS_MAX_KEYS];
+};
+#define ENS_XCDS 8
+typedef const float __attribute__((address_space(1)))* ens_src_t;   // the sources are device memory: global, not flat, loads
+
+// channels c0 .. c0 + NC - 1 of element p (e = its first float): moments, the MEAN / VAR blocks, the running channel sums
+template <int NC>
+__device__ __forceinline__ void ens_channels(const float* const* __restrict__ src, int M, int64_t e, int c0, bool want_var,
+                                             float* __restrict__ out, int64_t o_mean, int64_t o_var, int64_t row, float& sum_m,
+                                             float& sum_v, float& sum_sd) {
+    float m[NC], v[NC];
+#pragma unroll
+    for (int c = 0; c < NC; ++c) v[c] = 0.f;
+    moments_of<NC>([&](int j, int c) { return ((ens_src_t)src[j])[e + c0 + c]; }, M, want_var, m, v);
+#pragma unroll
+    for (int c = 0; c < NC; ++c) {
+        if (o_mean >= 0) out[o_mean + row + c0 + c] = m[c];
+        if (o_var >= 0) out[o_var + row + c0 + c] = v[c];
+        const float sd = sqrtf(v[c]);
+        const bool first = c0 + c == 0;
+        sum_m = first ? m[c] : sum_m + m[c];
+        sum_v = first ? v[c] : sum_v + v[c];
+        sum_sd = first ? sd : sum_sd + sd;
+    }
+}
+
+// every channel of one element of one key, in channel order: groups of 4, a last group of 3, else single channels
+__device__ __forceinline__ void ens_element(const float* const* __restrict__ src, int M, int C, int64_t e, bool want_var,
+                                            float* __restrict__ out, int64_t o_mean, int64_t o_var, int64_t row, float& sum_m,
+                                            float& sum_v, float& sum_sd) {
+    int c = 0;
+    for (; C - c >= 4; c += 4) ens_channels<4>(src, M, e, c, want_var, out, o_mean, o_var, row, sum_m, sum_v, sum_sd);
+    if (C - c == 3) {
+        ens_channels<3>(src, M, e, c, want_var, out, o_mean, o_var, row, sum_m, sum_v, sum_sd);
+        return;
+    }
+    for (; c < C; ++c) ens_channels<1>(src, M, e, c, want_var, out, o_mean, o_var, row, sum_m, sum_v, sum_sd);
+}
+
+__global__ __launch_bounds__(256) void ensemble_reduce_kernel(EnsArgs a) {
+    const int v = blockIdx.y;
+    const uint32_t x = blockIdx.x % ENS_XCDS, t = blockIdx.x / ENS_XCDS;
+    const int k = a.used[t % (uint32_t)a.n_used];
+    const EnsKeyDev& d = a.key[k];
+    const int64_t p = ((int64_t)(t / (uint32_t)a.n_used) * ENS_XCDS + x) * 256 + threadIdx.x;
+    if (p >= d.n) return;
+    const int M = a.M, C = d.C;
+    float* __restrict__ out = a.arena + (int64_t)v * a.view_stride;
+    const int64_t o_mean = d.out[UNERF_ENS_MEAN], o_var = d.out[UNERF_ENS_VAR], o_epi = d.out[UNERF_ENS_VAR_CMEAN],
+                  o_alea = d.out[UNERF_ENS_ALEA_CMEAN], o_sum = d.out[UNERF_ENS_EPI_ALEA],
+                  o_sqrt = d.out[UNERF_ENS_EPI_ALEA_SQRT], o_std = d.out[UNERF_ENS_STD_CMEAN];
+    const bool want_var = (o_var & o_epi & o_sum & o_sqrt & o_std) >= 0;   // one of them is asked for (offsets are >= 0 or -1)
+    float sum_m = 0.f, sum_v = 0.f, sum_sd = 0.f;
+    ens_element(a.table + ((int64_t)v * a.n_keys + k) * M, M, C, p * d.stride, want_var, out, o_mean, o_var, p * C, sum_m, sum_v,
+                sum_sd);
+    const float epi = sum_v / (float)C;
+    if (o_epi >= 0) out[o_epi + p] = epi;
+    if (o_std >= 0) out[o_std + p] = sum_sd / (float)C;
+    if ((o_alea & o_sum & o_sqrt) >= 0 && d.aux >= 0) {
+        float alea = 0.f, unused_v = 0.f, unused_sd = 0.f;
+        ens_element(a.table + ((int64_t)v * a.n_keys + d.aux) * M, M, d.aux_C, p * d.aux_stride, false, out, -1, -1, 0, alea,
+                    unused_v, unused_sd);
+        alea = alea / (float)d.aux_C;
+        if (o_alea >= 0) out[o_alea + p] = alea;
+        const float sum = epi + alea;
+        if (o_sum >= 0) out[o_sum + p] = sum;
+        if (o_sqrt >= 0) out[o_sqrt + p] = sqrtf(sum);
+    }
+}
+
+extern "C" int unerf_ensemble_reduce(const float* const* table, int B, int n_keys, int M, const unerf_ens_key* keys,
+                                     const unerf_ens_out* plan, int n_out, int64_t view_stride, float* arena,
+                                     int64_t arena_floats, void* stream) {
+    UNERF_REQUIRE(B >= 0 && B <= UNERF_NERF_MAX_VIEWS, "ensemble_reduce: B=%d outside [0,%d]", B, UNERF_NERF_MAX_VIEWS);
+    UNERF_REQUIRE(n_keys >= 1 && n_keys <= UNERF_ENS_MAX_KEYS, "ensemble_reduce: n_keys=%d outside [1,%d]", n_keys,
+                  UNERF_ENS_MAX_KEYS);
+    UNERF_REQUIRE(M >= 1 && M <= UNERF_ENS_MAX_MEMBERS, "ensemble_reduce: M=%d outside [1,%d]", M, UNERF_ENS_MAX_MEMBERS);
+    UNERF_REQUIRE(keys && n_out >= 0 && (plan || n_out == 0), "ensemble_reduce: null key / plan descriptor");
+    UNERF_REQUIRE(view_stride >= 0 && arena_floats >= 0, "ensemble_reduce: negative arena size");
+    EnsArgs a;
+    a.table = table; a.arena = arena; a.view_stride = view_stride; a.n_keys = n_keys; a.M = M;
+    for (int k = 0; k < UNERF_ENS_MAX_KEYS; ++k) {
+        EnsKeyDev& d = a.key[k];
+        d.n = 0; d.C = 1; d.stride = 1; d.aux = -1; d.aux_C = 1; d.aux_stride = 1; d.pad = 0;
+        a.used[k] = 0;
+        for (int s = 0; s < UNERF_ENS_STATS; ++s) d.out[s] = -1;
+    }
+    int64_t most = 0, work = 0;   // most: blocks of the key with the most elements
+    a.n_used = 0;
+    for (int k = 0; k < n_keys; ++k) {
+        UNERF_REQUIRE(keys[k].channels >= 1 && keys[k].channels <= UNERF_ENS_MAX_CHANNELS,
+                      "ensemble_reduce: key %d has %d channels, outside [1,%d]", k, keys[k].channels, UNERF_ENS_MAX_CHANNELS);
+        UNERF_REQUIRE(keys[k].stride >= keys[k].channels && keys[k].n >= 0,
+                      "ensemble_reduce: key %d: stride %d < channels %d, or n < 0", k, keys[k].stride, keys[k].channels);
+        a.key[k].n = keys[k].n; a.key[k].C = keys[k].channels; a.key[k].stride = keys[k].stride;
+    }
+    for (int o = 0; o < n_out; ++o) {
+        const unerf_ens_out& e = plan[o];
+        UNERF_REQUIRE(e.stat >= 0 && e.stat < UNERF_ENS_STATS && e.key >= 0 && e.key < n_keys,
+                      "ensemble_reduce: output %d: statistic %d / key %d", o, e.stat, e.key);
+        EnsKeyDev& d = a.key[e.key];
+        UNERF_REQUIRE(d.out[e.stat] < 0, "ensemble_reduce: output %d repeats statistic %d of key %d", o, e.stat, e.key);
+        const int64_t len = d.n * (e.stat <= UNERF_ENS_VAR ? d.C : 1);
+        UNERF_REQUIRE(e.offset >= 0 && e.offset + len <= view_stride, "ensemble_reduce: output %d leaves the view's part of the arena", o);
+        for (int q = 0; q < o; ++q) {
+            const int64_t lq = a.key[plan[q].key].n * (plan[q].stat <= UNERF_ENS_VAR ? a.key[plan[q].key].C : 1);
+            UNERF_REQUIRE(e.offset + len <= plan[q].offset || plan[q].offset + lq <= e.offset,
+                          "ensemble_reduce: outputs %d and %d overlap", q, o);
+        }
+        if (e.stat == UNERF_ENS_ALEA_CMEAN || e.stat == UNERF_ENS_EPI_ALEA || e.stat == UNERF_ENS_EPI_ALEA_SQRT) {
+            UNERF_REQUIRE(e.aux >= 0 && e.aux < n_keys && a.key[e.aux].n == d.n && (d.aux < 0 || d.aux == e.aux),
+                          "ensemble_reduce: output %d: aux key %d", o, e.aux);
+            d.aux = e.aux; d.aux_C = a.key[e.aux].C; d.aux_stride = a.key[e.aux].stride;
+        }
+        d.out[e.stat] = e.offset;
+    }
+    for (int k = 0; k < n_keys; ++k) {
+        bool used = false;
+        for (int s = 0; s < UNERF_ENS_STATS; ++s) used = used || a.key[k].out[s] >= 0;
+        if (!used || a.key[k].n == 0) continue;      // nothing asked of this key, or nothing in it: no blocks
+        a.used[a.n_used++] = (uint8_t)k;
+        const int64_t nb = (a.key[k].n + 255) / 256;
+        if (nb > most) most = nb;
+        work += a.key[k].n;
+    }
+    const int64_t blocks = (most + ENS_XCDS - 1) / ENS_XCDS * ENS_XCDS * a.n_used;
+    UNERF_REQUIRE(blocks < (int64_t)1 << 31, "ensemble_reduce: too many elements for one launch");
+    UNERF_REQUIRE((int64_t)B * view_stride <= arena_floats, "ensemble_reduce: arena of %lld floats for %d views of %lld",
+                  (long long)arena_floats, B, (long long)view_stride);
+    UNERF_REQUIRE(B == 0 || work == 0 || (table && arena), "ensemble_reduce: null table / arena");
+    if (B == 0 || work == 0) return UNERF_OK;
+    hipLaunchKernelGGL(ensemble_reduce_kernel, dim3((unsigned)blocks, (unsigned)B), dim3(256), 0, (hipStream_t)stream, a);
+    return unerf_check_launch("ensemble_reduce");
 }

@@ -165,6 +165,16 @@ class RayCamera(C.Structure):
                 ("distortion", C.c_float * 6)]
 
 
+class EnsKey(C.Structure):
+    """include/unerf.h: unerf_ens_key (one input key of unerf_ensemble_reduce)"""
+    _fields_ = [("channels", C.c_int32), ("stride", C.c_int32), ("n", C.c_int64)]
+
+
+class EnsOut(C.Structure):
+    """include/unerf.h: unerf_ens_out (one output block per view of unerf_ensemble_reduce)"""
+    _fields_ = [("stat", C.c_int32), ("key", C.c_int32), ("aux", C.c_int32), ("reserved", C.c_int32), ("offset", C.c_int64)]
+
+
 ABI_VERSION = 1420                                # include/unerf.h: UNERF_ABI_VERSION (struct layouts / argument lists)
 FIELD_ACTIVE, FIELD_MCDROPOUT, FIELD_LAPLACE = 0, 1, 2
 SPACING_PIECEWISE, SPACING_UNIFORM = 0, 1         # include/unerf.h: UNERF_SPACING_*
@@ -224,6 +234,7 @@ SIGNATURES = {
     "unerf_laplace_depth_weights_views": (_i, [_vp, _vp, _vp, _i64, _i, _f, _f, _i, _vp, _i, C.POINTER(RayViews),
                                                C.POINTER(LaplaceViews), _vp, _vp]),
     "unerf_moments": (_i, [_vp, _i, _i64, _i, _vp, _vp, _vp]),
+    "unerf_ensemble_reduce": (_i, [_vp, _i, _i, _i, C.POINTER(EnsKey), C.POINTER(EnsOut), _i, _i64, _vp, _i64, _vp]),
     "unerf_image_metrics_workspace_bytes": (C.c_size_t, [_i64]),
     "unerf_image_metrics": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i, _i, _f, _f, C.POINTER(C.c_double), _i, C.POINTER(C.c_double), _i,
                                  _i, _vp, C.c_size_t, _vp, _vp]),
@@ -262,6 +273,10 @@ METRICS_AUSE, METRICS_AUCE, METRICS_NLL, METRICS_SSIM = 1, 2, 4, 8
 METRICS_ALL = METRICS_AUSE | METRICS_AUCE | METRICS_NLL | METRICS_SSIM
 METRICS_AUCE_OFF, METRICS_AUSE_OFF, METRICS_ROW, METRICS_MAX_CUTS = 16, 144, 656, 128
 METRICS_MAX_IMAGES = 64                           # include/unerf.h: UNERF_METRICS_MAX_IMAGES (unerf_image_metrics_batch)
+# include/unerf.h: UNERF_ENS_* (bounds and statistics of unerf_ensemble_reduce)
+ENS_MAX_KEYS, ENS_MAX_MEMBERS, ENS_MAX_CHANNELS = 32, 64, 64
+ENS_MEAN, ENS_VAR, ENS_VAR_CMEAN, ENS_ALEA_CMEAN, ENS_EPI_ALEA, ENS_EPI_ALEA_SQRT, ENS_STD_CMEAN = range(7)
+ENS_ALEA_STATS = (ENS_ALEA_CMEAN, ENS_EPI_ALEA, ENS_EPI_ALEA_SQRT)
 SPLAT_MAX_VIEWS = 16                              # include/unerf.h: UNERF_SPLAT_MAX_VIEWS
 SPLAT_VIEW_FLOATS = 19                            # include/unerf.h: UNERF_SPLAT_VIEW_FLOATS
 SPLAT_BATCH_MAX_TILES = 11999                     # include/unerf.h: UNERF_SPLAT_BATCH_MAX_TILES

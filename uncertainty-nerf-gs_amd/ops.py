@@ -1383,6 +1383,64 @@ def moments(x: torch.Tensor, want_var: bool = True):
     return mean, var
 
 
+ENS_STATS = {"mean": _l.ENS_MEAN, "var": _l.ENS_VAR, "var_cmean": _l.ENS_VAR_CMEAN, "alea_cmean": _l.ENS_ALEA_CMEAN,
+             "epi_plus_alea": _l.ENS_EPI_ALEA, "sqrt_epi_plus_alea": _l.ENS_EPI_ALEA_SQRT, "std_cmean": _l.ENS_STD_CMEAN}
+
+
+def ensemble_reduce(views, plan, arena: Optional[torch.Tensor] = None) -> List[Dict[str, torch.Tensor]]:
+    """unerf_ensemble_reduce: the member moments and the derived keys of B views in ONE launch.
+    views[v][key] is the list over the M members of that key's [n, C] tensor in view v -- read where it lies: rows may be
+    slices of wider rows (any row stride, unit channel stride), only the row stride of a key must be one value.
+    plan is ensemble.reduce_plan's list of (output key, statistic, input key); "var" (the raw variance) is accepted too,
+    and the alea statistics read the member mean of input key + "_var".
+    Returns, per view, {output key: [n, C_out]}: contiguous views into one arena (allocated here unless given; blocks in
+    plan order, view after view).  One upload of the pointer table, no host synchronisation.  B <= lib.NERF_MAX_VIEWS."""
+    lib = _l.load()
+    B = len(views)
+    if B == 0:
+        return []
+    names = list(views[0])
+    index = {k: i for i, k in enumerate(names)}
+    first = {k: views[0][k][0] for k in names}
+    M, dev = len(views[0][names[0]]), first[names[0]].device
+    keys = (_l.EnsKey * len(names))()
+    for i, k in enumerate(names):
+        t = first[k]
+        if t.dim() != 2:
+            raise _l.UnerfError(f"ensemble_reduce: {k}: expected [n, C] sources, got {tuple(t.shape)}")
+        keys[i].n, keys[i].channels = int(t.shape[0]), int(t.shape[1])
+        keys[i].stride = int(t.stride(0)) if t.shape[0] > 1 else int(t.shape[1])
+    ptrs = []
+    for vw in views:
+        if list(vw) != names:
+            raise _l.UnerfError("ensemble_reduce: the views differ in their keys")
+        for i, k in enumerate(names):
+            if len(vw[k]) != M:
+                raise _l.UnerfError(f"ensemble_reduce: {k}: {len(vw[k])} members, expected {M}")
+            for t in vw[k]:
+                if (not t.is_cuda or t.device != dev or t.dtype != torch.float32 or tuple(t.shape) != (keys[i].n, keys[i].channels)
+                        or (keys[i].channels > 1 and t.stride(1) != 1) or (keys[i].n > 1 and t.stride(0) != keys[i].stride)):
+                    raise _l.UnerfError(f"ensemble_reduce: {k}: every source must be a float32 HIP tensor {(keys[i].n, keys[i].channels)} "
+                                        f"with row stride {keys[i].stride} and unit channel stride (libunerf has no CPU path)")
+                ptrs.append(t.data_ptr())
+    outs = (_l.EnsOut * max(len(plan), 1))()
+    blocks, off = [], 0
+    for o, (name, stat, src) in enumerate(plan):
+        e, code = outs[o], ENS_STATS[stat]
+        e.stat, e.key, e.aux, e.offset = code, index[src], (index[src + "_var"] if code in _l.ENS_ALEA_STATS else -1), off
+        cout = keys[e.key].channels if code in (_l.ENS_MEAN, _l.ENS_VAR) else 1
+        blocks.append((name, off, int(keys[e.key].n), cout))
+        off += int(keys[e.key].n) * cout
+    if arena is None:
+        arena = torch.empty(B * off, device=dev, dtype=torch.float32)
+    with _ctx(dev):
+        table = torch.tensor(ptrs, dtype=torch.int64).pin_memory().to(dev, non_blocking=True)
+        _run("ensemble_reduce", lambda: lib.unerf_ensemble_reduce(
+            _p(table, torch.int64, "table"), B, len(names), M, keys, outs, len(plan), off, _p(arena, name="arena"), arena.numel(),
+            _stream()))
+    return [{name: arena[v * off + o:v * off + o + n * c].view(n, c) for name, o, n, c in blocks} for v in range(B)]
+
+
 # ------------------------------------------------------- per-image eval metrics --------
 
 _METRIC_TABLES = None
