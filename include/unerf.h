@@ -731,6 +731,27 @@ int unerf_image_metrics_batch(const float* pred, const float* target, const floa
                               int n_ratios, const double* z_host, int n_z, int flags, void* workspace, size_t workspace_bytes,
                               double* out, void* stream);
 
+/* The rendered images of the eval stage: what save_imgs_rgb (scripts/eval_uncertainty.py:209-303) hands to
+ * media.write_image per eval image, as final 8-bit planes for a batch of B images of ONE size (eval.py: save_imgs_rgb,
+ * host definition eval.pack_eval_images).  pred / target [B, n, 3], sigma [B, n]: contiguous float32 stacks; 1 <= B <=
+ * UNERF_METRICS_MAX_IMAGES, 3 n < 2^31 per image (the offsets that carry the image index are 64-bit).
+ * With q(x) = (uint8)(clip(x, 0, 1) * 255 + 0.5) in float64, truncating, NaN -> 0:
+ *   gt8   [B, n, 3] = q(target)          pred8 [B, n, 3] = q(pred), not clipped first
+ *   err8  [B, n]    = q(|d0| + |d1| + |d2|), d = pred - target in float32, channels added left to right
+ *   std8  [B, n, 3] = lut[min((int)(a * 256), 255)], a = ((double)s - vmin) / ((vmax - vmin) + DBL_EPSILON) in float64,
+ *                     s = clip((sigma - unc_lo) / unc_span, 0, 1) in float32 (a NaN stays one), vmin / vmax the minimum /
+ *                     maximum of s over the image's own non-NaN pixels; a NaN pixel is (0, 0, 0)
+ * lut: DEVICE [256, 3] bytes (colormaps.JET_U8).  unc_lo = min(unc_min, unc_max), unc_span = |unc_max - unc_min| > 0.
+ * Any plane may be NULL and is then skipped; the others do not change.  Two kernels (the per-image range of s, run only
+ * when std8 is wanted; the pack) and two memsets of the workspace, whatever B is: the image is an outer grid coordinate.
+ * The range is an integer min / max of bit patterns (s >= 0): two calls on the same inputs give equal bytes.
+ * workspace: unerf_eval_images_workspace_bytes(B) bytes, 4-byte aligned, initialised inside the call.
+ * n = 0 is a successful no-op.  Argument errors are reported before any device call. */
+size_t unerf_eval_images_workspace_bytes(int B);
+int unerf_eval_images_batch(const float* pred, const float* target, const float* sigma, int64_t n, int B, float unc_lo,
+                            float unc_span, const uint8_t* lut, uint8_t* gt8, uint8_t* pred8, uint8_t* err8, uint8_t* std8,
+                            void* workspace, size_t workspace_bytes, void* stream);
+
 /* ================================================================ splats ==
  * gsplat 0.1.11 call sites in models/activesplatfacto/activesplatfacto_model.py. */
 

@@ -22,6 +22,9 @@
 // is the single-image pointer moved by a 64-bit per-image stride (mt_img).  blockIdx.x, and with it every fixed-order
 // reduction, is what it is for that image alone: row b of a batch is the row of image b scored alone, bit for bit.
 // unerf_image_metrics is the B = 1 case.
+//
+// The rendered images of the same stage (unerf_eval_images_batch: ground truth, prediction, absolute error and the
+// jet-coloured std as final 8-bit planes) are at the end of the file: ei_range / ei_pack.
 #include "unerf_common.hpp"
 
 #include <algorithm>
@@ -729,4 +732,152 @@ extern "C" int unerf_image_metrics_batch(const float* pred, const float* target,
                                          double* out, void* stream) {
     return mt_run("image_metrics_batch", true, pred, target, sigma, mask, n, B, C, H, W, pred_clip_max, nll_min_sigma, ratios_host, n_ratios,
                   z_host, n_z, flags, workspace, workspace_bytes, out, stream);
+}
+
+// ---- rendered eval images: the four 8-bit planes of eval.save_imgs_rgb ------------------------------------------------
+// unerf_eval_images_batch (include/unerf.h): what scripts/eval_uncertainty.py:209-303 hands to media.write_image, as final
+// bytes.  Two kernels, the image is blockIdx.y of both (mt_img): ei_range leaves each image's min / max of the
+// normalised std s over its non-NaN pixels, ei_pack writes every plane that was asked for, one pixel per thread.
+// s is in [0, 1] or NaN, so its float32 order is the order of its bit patterns: the range goes wave butterfly -> LDS ->
+// one integer atomicMin / atomicMax per workgroup on the image's two words, order-free and so repeatable.  The words are
+// set inside the call (min 0xFFFFFFFF, max 0).  Arithmetic is the host definition's (eval.pack_eval_images): float32 for
+// the differences, their sum and s, float64 for the colour index and the quantisation, every division IEEE (this file
+// is built without fast-math and with hipcc's correctly rounded float32 division).
+namespace {
+
+constexpr int EI_THREADS = 256;          // pixels per workgroup and step
+constexpr int EI_MAX_WG = 1024;          // workgroups per image; an image of more than EI_THREADS * EI_MAX_WG pixels strides
+
+size_t ei_workspace(int B) { return al256(2 * sizeof(uint32_t) * (size_t)(B > 1 ? B : 1)); }
+
+// clip((sigma - lo) / span, 0, 1) in float32; NaN stays NaN (fminf / fmaxf would drop it), -0 becomes +0
+__device__ __forceinline__ float ei_norm(float sigma, float lo, float span) {
+    const float x = (sigma - lo) / span;
+    if (x != x) return x;
+    return fminf(fmaxf(x, 0.f), 1.f) + 0.f;
+}
+// mediapy's float -> uint8: (uint8)(clip(x, 0, 1) * 255 + 0.5) in float64, truncating; NaN -> 0
+__device__ __forceinline__ uint8_t ei_q(float x) {
+    if (x != x) return 0;
+    const double c = fmin(fmax((double)x, 0.0), 1.0);
+    return (uint8_t)(int)(c * 255.0 + 0.5);
+}
+
+__global__ __launch_bounds__(EI_THREADS) void ei_range_kernel(const float* __restrict__ sigma0, uint32_t n, float lo, float span,
+                                                              uint32_t* __restrict__ range /* [2, B]: min bits, max bits */) {
+    __shared__ uint32_t red[2][EI_THREADS / 64];
+    const float* __restrict__ sigma = mt_img(sigma0, (size_t)n * sizeof(float));
+    uint32_t kmin = 0xFFFFFFFFu, kmax = 0u;
+    for (uint32_t i = blockIdx.x * EI_THREADS + threadIdx.x; i < n; i += gridDim.x * EI_THREADS) {
+        const float s = ei_norm(sigma[i], lo, span);
+        if (s == s) {
+            const uint32_t k = __float_as_uint(s);
+            kmin = min(kmin, k);
+            kmax = max(kmax, k);
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        kmin = min(kmin, (uint32_t)__shfl_xor((int)kmin, o));
+        kmax = max(kmax, (uint32_t)__shfl_xor((int)kmax, o));
+    }
+    if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = kmin; red[1][threadIdx.x >> 6] = kmax; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int w = 1; w < EI_THREADS / 64; ++w) { kmin = min(kmin, red[0][w]); kmax = max(kmax, red[1][w]); }
+        if (kmin != 0xFFFFFFFFu) {      // a workgroup without a finite pixel has nothing to say
+            atomicMin(&range[blockIdx.y], kmin);
+            atomicMax(&range[gridDim.y + blockIdx.y], kmax);
+        }
+    }
+}
+
+__global__ __launch_bounds__(EI_THREADS) void ei_pack_kernel(const float* __restrict__ pred0, const float* __restrict__ target0,
+                                                             const float* __restrict__ sigma0, uint32_t n, float lo, float span,
+                                                             const uint8_t* __restrict__ lut, const uint32_t* __restrict__ range,
+                                                             uint8_t* __restrict__ gt0, uint8_t* __restrict__ pr0,
+                                                             uint8_t* __restrict__ er0, uint8_t* __restrict__ sd0) {
+    __shared__ uint8_t jet[256 * 3];
+    const float* __restrict__ pred = mt_img(pred0, (size_t)n * 3 * sizeof(float));
+    const float* __restrict__ target = mt_img(target0, (size_t)n * 3 * sizeof(float));
+    const float* __restrict__ sigma = mt_img(sigma0, (size_t)n * sizeof(float));
+    uint8_t* __restrict__ gt8 = mt_img(gt0, (size_t)n * 3);
+    uint8_t* __restrict__ pred8 = mt_img(pr0, (size_t)n * 3);
+    uint8_t* __restrict__ err8 = mt_img(er0, (size_t)n);
+    uint8_t* __restrict__ std8 = mt_img(sd0, (size_t)n * 3);
+    double vmin = 0.0, denom = 1.0;
+    if (std8) {
+        for (int i = threadIdx.x; i < 256 * 3; i += EI_THREADS) jet[i] = lut[i];
+        // an image without a finite pixel keeps min = 0xFFFFFFFF (a NaN): every pixel of it is NaN and takes the branch below
+        vmin = (double)__uint_as_float(range[blockIdx.y]);
+        denom = ((double)__uint_as_float(range[gridDim.y + blockIdx.y]) - vmin) + DBL_EPSILON;
+        __syncthreads();
+    }
+    for (uint32_t i = blockIdx.x * EI_THREADS + threadIdx.x; i < n; i += gridDim.x * EI_THREADS) {
+        const size_t i3 = (size_t)i * 3;
+        if (gt8 || pred8 || err8) {
+            float p[3], t[3];
+#pragma unroll
+            for (int c = 0; c < 3; ++c) { p[c] = pred[i3 + c]; t[c] = target[i3 + c]; }
+            if (gt8) {
+#pragma unroll
+                for (int c = 0; c < 3; ++c) gt8[i3 + c] = ei_q(t[c]);
+            }
+            if (pred8) {
+#pragma unroll
+                for (int c = 0; c < 3; ++c) pred8[i3 + c] = ei_q(p[c]);
+            }
+            if (err8) {
+                float ab = 0.f;
+#pragma unroll
+                for (int c = 0; c < 3; ++c) ab = ab + fabsf(p[c] - t[c]);
+                err8[i] = ei_q(ab);
+            }
+        }
+        if (std8) {
+            const float s = ei_norm(sigma[i], lo, span);
+            uint8_t r = 0, g = 0, b = 0;
+            if (s == s) {
+                const double a = ((double)s - vmin) / denom;
+                const int idx = min((int)(a * 256.0), 255);
+                r = jet[3 * idx]; g = jet[3 * idx + 1]; b = jet[3 * idx + 2];
+            }
+            std8[i3] = r; std8[i3 + 1] = g; std8[i3 + 2] = b;
+        }
+    }
+}
+
+}  // namespace
+
+extern "C" size_t unerf_eval_images_workspace_bytes(int B) { return ei_workspace(B); }
+
+extern "C" int unerf_eval_images_batch(const float* pred, const float* target, const float* sigma, int64_t n, int B, float unc_lo,
+                                       float unc_span, const uint8_t* lut, uint8_t* gt8, uint8_t* pred8, uint8_t* err8, uint8_t* std8,
+                                       void* workspace, size_t workspace_bytes, void* stream) {
+    const char* who = "eval_images_batch";
+    UNERF_REQUIRE(n >= 0, "%s: n = %lld", who, (long long)n);
+    UNERF_REQUIRE(B >= 1 && B <= UNERF_METRICS_MAX_IMAGES, "%s: B = %d (expected 1..%d images)", who, B, UNERF_METRICS_MAX_IMAGES);
+    UNERF_REQUIRE(unc_span > 0.f && unc_span <= FLT_MAX && fabsf(unc_lo) <= FLT_MAX,
+                  "%s: unc_lo = %g, unc_span = %g (expected finite values and unc_span > 0)", who, (double)unc_lo, (double)unc_span);
+    if (n == 0) return UNERF_OK;
+    UNERF_REQUIRE(3 * n < ((int64_t)1 << 31), "%s: 3 n = %lld (must stay below 2^31)", who, (long long)(3 * n));
+    UNERF_REQUIRE(pred && target && sigma && lut && workspace, "%s: null pointer (pred / target / sigma / lut / workspace) with n > 0", who);
+    UNERF_REQUIRE(workspace_bytes >= ei_workspace(B), "%s: workspace of %zu bytes, unerf_eval_images_workspace_bytes(%d) = %zu", who,
+                  workspace_bytes, B, ei_workspace(B));
+    UNERF_REQUIRE(((uintptr_t)workspace & 3) == 0, "%s: workspace must be 4-byte aligned", who);
+    if (!gt8 && !pred8 && !err8 && !std8) return UNERF_OK;
+
+    hipStream_t st = (hipStream_t)stream;
+    uint32_t* range = (uint32_t*)workspace;
+    const uint32_t un = (uint32_t)n;
+    const dim3 grid((uint32_t)std::min<int64_t>((n + EI_THREADS - 1) / EI_THREADS, EI_MAX_WG), B);
+    if (std8) {
+        if (hipMemsetAsync(range, 0xFF, (size_t)B * sizeof(uint32_t), st) != hipSuccess) return unerf_check_launch(who);
+        if (hipMemsetAsync(range + B, 0, (size_t)B * sizeof(uint32_t), st) != hipSuccess) return unerf_check_launch(who);
+        hipLaunchKernelGGL(ei_range_kernel, grid, dim3(EI_THREADS), 0, st, sigma, un, unc_lo, unc_span, range);
+    }
+    hipLaunchKernelGGL(ei_pack_kernel, grid, dim3(EI_THREADS), 0, st, pred, target, sigma, un, unc_lo, unc_span, lut, range, gt8, pred8,
+                       err8, std8);
+    return unerf_check_launch(who);
 }

@@ -8,8 +8,10 @@ rgb_auc_{abs_error,length,neg_error}) plus `num_rays_per_sec` / `fps` (:948-952)
 the images (:1069-1077) and writes the same `metrics.json` envelope (:1156-1169).
 
 Differences, on purpose: SSIM / LPIPS (torchmetrics / torchvision networks, absent here) are not
-computed; no plots; and `num_rays_per_sec` is reported twice -- `num_rays_per_sec` covers render +
-metrics like the reference's counter (so numbers stay comparable with its metrics.json), while
+computed; of the plots, the four rendered images per eval image (`save_imgs_rgb`, :209-303) and the test-set
+sparsification-error plots (:85-98) are written with `save_rendered_images`, the AUCE curve plot and the depth images
+(`save_imgs_depth` returns without writing, :182) are not; and `num_rays_per_sec` is reported twice --
+`num_rays_per_sec` covers render + metrics like the reference's counter (so numbers stay comparable with its metrics.json), while
 `render_rays_per_sec` times the render alone (HIP-synchronised).  Depth metrics (`depth_metrics_unc`,
 eval_uncertainty.py:415-644) take the dataset's `depth_gt_XX.npy` map and `scale_parameters.txt` factor,
 read by `load_depth_gt`; pass `depth_gt_fn` to `get_average_uncertainty_metrics` to include them.
@@ -18,7 +20,9 @@ from __future__ import annotations
 
 import json
 import os
+import struct
 import time
+import zlib
 from dataclasses import dataclass
 from functools import partial
 from pathlib import Path
@@ -133,6 +137,139 @@ def image_metrics_unc_batch(outputs_list: Sequence[Dict[str, torch.Tensor]], gt_
     if not eval_rgb_unc:
         done = [({"psnr": md["psnr"], "ssim": md["ssim"]}, curves) for md, curves in done]
     return done
+
+
+# ---- rendered images (save_imgs_rgb, scripts/eval_uncertainty.py:209-303) ------------------------------------------------
+
+def _q8(x: np.ndarray) -> np.ndarray:
+    """float -> uint8 as media.write_image does it: (uint8)(clip(x, 0, 1) * 255 + 0.5) in float64, truncating; NaN -> 0"""
+    with np.errstate(invalid="ignore"):
+        v = np.clip(np.asarray(x).astype(np.float64), 0.0, 1.0) * 255.0 + 0.5
+    return np.where(np.isnan(v), 0.0, v).astype(np.uint8)
+
+
+def _unc_range(unc_min: float, unc_max: float) -> Tuple[np.float32, np.float32]:
+    if float(unc_max) == float(unc_min):
+        raise ValueError(f"unc_max == unc_min == {unc_min}: the uncertainty range must not be empty (the reference divides by zero)")
+    return np.float32(min(unc_min, unc_max)), np.float32(abs(unc_max - unc_min))
+
+
+def pack_eval_images(rgb, gt, rgb_std, unc_min: float = 0.0, unc_max: float = 1.0) -> Dict[str, np.ndarray]:
+    """The four arrays save_imgs_rgb (eval_uncertainty.py:209-303) hands to media.write_image, as the bytes that reach the
+    files, in plain numpy: the CPU path, and the definition ops.eval_images (unerf_eval_images_batch) is held to byte for
+    byte.  rgb / gt [H, W, 3] (gt already composed as the metrics see it), rgb_std [H, W] or [H, W, 1], float32 ->
+      "gt"   [H, W, 3]  q(gt)
+      "pred" [H, W, 3]  q(rgb), not clipped first (:316, :395)
+      "err"  [H, W]     q(clip(|d0| + |d1| + |d2|, 0, 1)), d = rgb - gt in float32, channels added left to right (:328, :379)
+      "std"  [H, W, 3]  colormaps.JET_U8[min((int)(a * 256), 255)] with s = clip((std - min(unc_min, unc_max)) /
+                        |unc_max - unc_min|, 0, 1) in float32 (:265; a NaN stays one) and, in float64 and per image,
+                        a = (s - vmin) / (vmax - vmin + DBL_EPSILON), vmin / vmax over the non-NaN pixels of s (:280-281:
+                        media.to_rgb without vmin / vmax; a constant image gives a = 0); a NaN pixel is (0, 0, 0)
+    with q(x) = (uint8)(clip(x, 0, 1) * 255 + 0.5) in float64, truncating, NaN -> 0.
+    [UPSTREAM-RECALL] mediapy is not installed here: q (its float -> uint8 conversion) and the to_rgb normalisation are
+    restated from its published source and are not pinned by a test against it; the colour table is matplotlib's `jet`,
+    which is pinned (tests/test_eval_images_cpu.py).  unc_max == unc_min raises ValueError."""
+    from .colormaps import JET_U8
+    lo, span = _unc_range(unc_min, unc_max)
+    rgb, gt = np.asarray(rgb, dtype=np.float32), np.asarray(gt, dtype=np.float32)
+    std = np.asarray(rgb_std, dtype=np.float32).reshape(rgb.shape[:-1])
+    with np.errstate(invalid="ignore", over="ignore"):
+        d = np.abs(rgb - gt)
+        err = np.clip((d[..., 0] + d[..., 1]) + d[..., 2], 0.0, 1.0)
+        s = np.clip((std - lo) / span, np.float32(0), np.float32(1))
+    ok = ~np.isnan(s)
+    std8 = np.zeros(s.shape + (3,), dtype=np.uint8)
+    if ok.any():
+        vmin, vmax = np.float64(s[ok].min()), np.float64(s[ok].max())
+        a = (np.where(ok, s, vmin).astype(np.float64) - vmin) / ((vmax - vmin) + np.finfo(np.float64).eps)
+        std8 = JET_U8[np.minimum((a * 256.0).astype(np.int64), 255)]
+        std8[~ok] = 0
+    return {"gt": _q8(gt), "pred": _q8(rgb), "err": _q8(err), "std": std8}
+
+
+def _write_png(path, array_u8: np.ndarray, compress_level: int = 6) -> None:
+    """array_u8 [H, W] (8-bit grey) or [H, W, 3] (8-bit RGB) -> a PNG file: IHDR, one IDAT (zlib over the rows, each
+    behind filter type 0), IEND.  zlib and struct only."""
+    a = np.ascontiguousarray(array_u8)
+    if a.dtype != np.uint8 or a.size == 0 or not (a.ndim == 2 or (a.ndim == 3 and a.shape[2] == 3)):
+        raise ValueError(f"_write_png: expected a non-empty uint8 [H, W] or [H, W, 3] array, got {a.dtype} {a.shape}")
+    H, W = a.shape[:2]
+    rows = np.empty((H, 1 + a.size // H), dtype=np.uint8)
+    rows[:, 0] = 0
+    rows[:, 1:] = a.reshape(H, -1)
+
+    def chunk(tag: bytes, data: bytes) -> bytes:
+        return struct.pack(">I", len(data)) + tag + data + struct.pack(">I", zlib.crc32(tag + data) & 0xFFFFFFFF)
+
+    with open(path, "wb") as f:
+        f.write(b"\x89PNG\r\n\x1a\n" + chunk(b"IHDR", struct.pack(">IIBBBBB", W, H, 8, 0 if a.ndim == 2 else 2, 0, 0, 0))
+                + chunk(b"IDAT", zlib.compress(rows.tobytes(), compress_level)) + chunk(b"IEND", b""))
+
+
+RENDERED_IMAGE_FILES = (("gt", "rgb_gt"), ("pred", "rgb_pred"), ("err", "rgb_abs_err"), ("std", "rgb_std"))   # plane, file stem
+
+
+def save_imgs_rgb(img_nums: Sequence[int], outputs_list: Sequence[Dict[str, torch.Tensor]], gt_images: Sequence[torch.Tensor],
+                  plots_path, unc_min: float = 0.0, unc_max: float = 1.0, composite_gt: Optional[Callable] = None,
+                  fused: bool = False, encode: bool = True) -> Dict[int, Dict[str, np.ndarray]]:
+    """save_imgs_rgb (eval_uncertainty.py:209-303) for a list of eval images: `{i}_rgb_gt.png`, `{i}_rgb_pred.png`,
+    `{i}_rgb_abs_err.png`, `{i}_rgb_std.png` under plots_path (created), i = img_nums[b]; the ground truth is composed as
+    for the metrics.  -> {i: the four uint8 arrays of pack_eval_images}.
+    fused=False: four float32 images per eval image go to the host and through pack_eval_images.
+    fused=True: the images (of ONE size) are stacked, ops.eval_images packs them on the device in chunks of at most
+    lib.METRICS_MAX_IMAGES, and one copy per chunk brings the final bytes (10 per pixel) to the host; same files, byte for byte.
+    encode=False returns the arrays without writing files (benchmarks/eval_images.py times the two halves apart)."""
+    _unc_range(unc_min, unc_max)
+    if not (len(img_nums) == len(outputs_list) == len(gt_images)):
+        raise ValueError(f"{len(img_nums)} image numbers for {len(outputs_list)} renders and {len(gt_images)} ground-truth images")
+    plots_path = Path(plots_path)
+    if encode:
+        plots_path.mkdir(parents=True, exist_ok=True)
+    parts = [_rgb_operands(o, gt, True, composite_gt)[:3] for o, gt in zip(outputs_list, gt_images)]
+    packed: Dict[int, Dict[str, np.ndarray]] = {}
+    if not fused:
+        for i, (rgb, image, std) in zip(img_nums, parts):
+            packed[int(i)] = pack_eval_images(rgb.cpu().numpy(), image.cpu().numpy(), std.cpu().numpy(), unc_min, unc_max)
+    elif parts:
+        from . import lib as _l, ops
+        if any(p[0].shape != parts[0][0].shape for p in parts):
+            raise ValueError(f"a batch holds renders of one size, got {sorted({tuple(p[0].shape) for p in parts})}")
+        H, W, _ = parts[0][0].shape
+        for c0 in range(0, len(parts), _l.METRICS_MAX_IMAGES):
+            chunk = parts[c0:c0 + _l.METRICS_MAX_IMAGES]
+            rgb, image, std = (torch.stack([p[j] for p in chunk]) for j in range(3))
+            host = ops.eval_images(rgb, image, std, unc_min, unc_max)["buffer"].cpu()
+            planes = {name: plane.numpy() for name, plane in ops.eval_image_planes(host, len(chunk), (H, W)).items()}
+            for b, i in enumerate(img_nums[c0:c0 + len(chunk)]):
+                packed[int(i)] = {name: plane[b] for name, plane in planes.items()}
+    if encode:
+        for i, planes in packed.items():
+            for name, stem in RENDERED_IMAGE_FILES:
+                _write_png(plots_path / f"{i}_{stem}.png", planes[name])
+    return packed
+
+
+def save_sparsification_plots(plots_path, curves: Dict[str, np.ndarray], output: str = "rgb") -> List[Path]:
+    """plot_errors (eval_uncertainty.py:85-98) as the pipeline calls it for the whole test set (:967-994, :1023-1050):
+    `plot_{output}_{mse,rmse,mae}_all.png`, the averaged curve err_by_var - err over the fractions removed.  matplotlib is
+    imported here (Agg canvas, no global backend change); without it the plots are skipped with one printed line."""
+    try:
+        from matplotlib.backends.backend_agg import FigureCanvasAgg
+        from matplotlib.figure import Figure
+    except ImportError:
+        print(f"matplotlib is not installed: the {output} sparsification plots are skipped")
+        return []
+    plots_path = Path(plots_path)
+    plots_path.mkdir(parents=True, exist_ok=True)
+    ratio = np.linspace(0, 1, 100, endpoint=False)
+    written = []
+    for et in ("mse", "rmse", "mae"):
+        fig = Figure()
+        FigureCanvasAgg(fig)
+        fig.add_subplot().plot(ratio, np.asarray(curves[f"{output}_all_var_ause_{et}"]) - np.asarray(curves[f"{output}_all_ause_{et}"]), "-g")
+        written.append(plots_path / f"plot_{output}_{et}_all.png")
+        fig.savefig(written[-1])
+    return written
 
 
 def load_depth_gt(dataset_path: str, img_num: int) -> Tuple[np.ndarray, float]:
@@ -259,7 +396,9 @@ def get_average_uncertainty_metrics(get_outputs_for_camera: Callable, eval_set: 
                                     eval_rgb_unc: bool = True, min_rgb_std_for_nll: float = 3e-2,
                                     composite_gt: Optional[Callable] = None, depth_gt_fn: Optional[Callable] = None,
                                     min_depth_std_for_nll: float = 1.0, fused: bool = False, view_batch: int = 1,
-                                    get_outputs_for_cameras: Optional[Callable] = None, metric_batch: bool = True):
+                                    get_outputs_for_cameras: Optional[Callable] = None, metric_batch: bool = True,
+                                    save_rendered_images: bool = False, plots_path=None, unc_min: float = 0.0,
+                                    unc_max: float = 1.0):
     """eval_uncertainty.py:816-1079.  -> (averaged metrics dict, averaged curves dict).
     depth_gt_fn(image_index) -> (depth_gt [H,W], scale) switches the depth metrics on (eval_depth_unc).
     fused: the per-image metric stage through the HIP kernels (image_metrics_unc / depth_metrics_unc, fused=True).
@@ -274,7 +413,17 @@ def get_average_uncertainty_metrics(get_outputs_for_camera: Callable, eval_set: 
     metrics are scored image by image.  Every metric key and every curve is bit-equal to metric_batch=False (today's
     per-image fused scoring, kept for comparison in one process); the three timing keys then share the batch's render
     time AND its metric time equally between its images.  An image with a non-finite input raises as finish_metrics does,
-    named by its index in the eval set."""
+    named by its index in the eval set.
+    save_rendered_images (with eval_rgb_unc, as at :754, :799): save_imgs_rgb writes the four PNGs of every eval image under
+    plots_path with the range unc_min / unc_max -- one image after its metrics, or the view batch after its batched
+    metrics (packed on the device when fused).  The saving counts into the metric time of `num_rays_per_sec` / `fps`, as
+    in the reference's counter (:898, :948-952), and not into `render_rays_per_sec`."""
+    if save_rendered_images and eval_rgb_unc:
+        if plots_path is None:
+            raise ValueError("save_rendered_images needs plots_path")
+        _unc_range(unc_min, unc_max)
+    save = partial(save_imgs_rgb, plots_path=plots_path, unc_min=unc_min, unc_max=unc_max, composite_gt=composite_gt,
+                   fused=fused) if save_rendered_images and eval_rgb_unc else None
     if view_batch < 1:
         raise ValueError(f"view_batch={view_batch}: at least 1")
     if view_batch > 1 and get_outputs_for_cameras is None:
@@ -305,6 +454,8 @@ def get_average_uncertainty_metrics(get_outputs_for_camera: Callable, eval_set: 
             dmd, dcurves = depth_metrics_unc(outputs, dgt, scale, min_depth_std_for_nll, fused=fused)
             md.update(dmd)
             curves.update(dcurves)
+        if save is not None:
+            save([img_num], [outputs], [gt])
         record(md, curves, outputs["rgb"].shape[:2], render_s, time.time() - start)
 
     def score_batch(pending, outs, render_share):
@@ -326,6 +477,8 @@ def get_average_uncertainty_metrics(get_outputs_for_camera: Callable, eval_set: 
                     md.update(dmd)
                     curves.update(dcurves)
             scored += done
+        if save is not None:
+            save([img_num for img_num, _, _ in pending], outs, [gt for _, _, gt in pending])
         metric_share = (time.time() - start) / len(pending)
         for (md, curves), outputs in zip(scored, outs):
             record(md, curves, outputs["rgb"].shape[:2], render_share, metric_share)
@@ -468,7 +621,10 @@ def run_eval(eval_config: EvalConfigs, model, eval_set, experiment_name: str = "
     EnsembleConfig EnsemblePipeline.get_ensemble_outputs_for_cameras (every member renders the batch, the moments run
     per view).
     metric_batch (with fused=True and view_batch > 1): a view batch is also scored by one batched metric call
-    (get_average_uncertainty_metrics); False keeps the per-image fused scoring.  Same numbers either way."""
+    (get_average_uncertainty_metrics); False keeps the per-image fused scoring.  Same numbers either way.
+    eval_config.save_rendered_images: the four rendered images per eval image (save_imgs_rgb, with eval_config.unc_min /
+    unc_max) and the test-set sparsification plots (save_sparsification_plots; depth ones when depth is evaluated) go to
+    `output_path.parent / "plots"` (:699-700).  Off (the default): no directory, the same keys."""
     fn = outputs_fn_for(eval_config, model, **fn_kw)
     batch_fn = None
     if view_batch > 1 and isinstance(eval_config, LaplaceConfig):
@@ -482,10 +638,17 @@ def run_eval(eval_config: EvalConfigs, model, eval_set, experiment_name: str = "
         composite_gt = model.composite_gt
     if eval_config.eval_depth and depth_gt_fn is None and eval_config.dataset_path is not None:
         depth_gt_fn = lambda i: load_depth_gt(str(eval_config.dataset_path), i)
-    metrics, _curves = get_average_uncertainty_metrics(
+    plots_path = Path(eval_config.output_path).parent / "plots" if eval_config.save_rendered_images else None
+    metrics, curves = get_average_uncertainty_metrics(
         fn, eval_set, eval_rgb_unc=eval_config.eval_rgb, min_rgb_std_for_nll=eval_config.min_rgb_std_for_nll,
         composite_gt=composite_gt, depth_gt_fn=depth_gt_fn if eval_config.eval_depth else None,
         min_depth_std_for_nll=eval_config.min_depth_std_for_nll, fused=fused,
-        view_batch=view_batch if batch_fn is not None else 1, get_outputs_for_cameras=batch_fn, metric_batch=metric_batch)
+        view_batch=view_batch if batch_fn is not None else 1, get_outputs_for_cameras=batch_fn, metric_batch=metric_batch,
+        save_rendered_images=eval_config.save_rendered_images, plots_path=plots_path, unc_min=eval_config.unc_min,
+        unc_max=eval_config.unc_max)
+    if plots_path is not None:
+        for output in ("depth", "rgb"):
+            if f"{output}_all_ause_mse" in curves:
+                save_sparsification_plots(plots_path, curves, output)
     write_metrics_json(str(eval_config.output_path), experiment_name, method_name, checkpoint, metrics)
     return metrics

@@ -241,6 +241,8 @@ SIGNATURES = {
     "unerf_image_metrics_batch_workspace_bytes": (C.c_size_t, [_i64, _i]),
     "unerf_image_metrics_batch": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i, _i, _i, _f, _f, C.POINTER(C.c_double), _i, C.POINTER(C.c_double),
                                        _i, _i, _vp, C.c_size_t, _vp, _vp]),
+    "unerf_eval_images_workspace_bytes": (C.c_size_t, [_i]),
+    "unerf_eval_images_batch": (_i, [_vp, _vp, _vp, _i64, _i, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
     "unerf_splat_project": (_i, [_vp, _vp, _f, _vp, _fp, _f, _f, _f, _f, _i, _i, _i, _f, _i64, _vp, _vp, _vp, _vp,
                                  _vp, _vp, _vp, _vp]),
     "unerf_splat_project_raw": (_i, [_vp, _vp, _f, _vp, _fp, _f, _f, _f, _f, _i, _i, _i, _f, _i64, _vp, _i, _vp, _vp, _vp,

@@ -1537,6 +1537,67 @@ def image_metrics_batch(pred: torch.Tensor, target: torch.Tensor, sigma: torch.T
     return out
 
 
+EVAL_IMAGE_PLANES = ("gt", "pred", "err", "std")     # bytes per pixel: 3, 3, 1, 3
+_JET_LUT: Dict[str, torch.Tensor] = {}               # colormaps.JET_U8 on each device it was asked for
+
+
+def eval_image_planes(buf: torch.Tensor, B: int, px) -> Dict[str, torch.Tensor]:
+    """the four planes of eval_images as views of its flat uint8 buffer (or of a host copy of it): one plane after the other,
+    each [B, *px, 3] ("err": [B, *px])"""
+    n = 1
+    for d in px:
+        n *= int(d)
+    planes, off = {}, 0
+    for name, ch in zip(EVAL_IMAGE_PLANES, (3, 3, 1, 3)):
+        planes[name] = buf[off:off + B * n * ch].view(B, *px, *((ch,) if ch == 3 else ()))
+        off += B * n * ch
+    return planes
+
+
+def eval_images(pred: torch.Tensor, target: torch.Tensor, sigma: torch.Tensor, unc_min: float, unc_max: float, *,
+                want=EVAL_IMAGE_PLANES, workspace: Optional[Workspace] = None) -> Dict[str, torch.Tensor]:
+    """unerf_eval_images_batch: the 8-bit planes eval.save_imgs_rgb writes for B renders of one size, in one call.
+    pred / target [B, ..., 3], sigma [B, ...]: contiguous float32 stacks, B <= lib.METRICS_MAX_IMAGES.  -> {"gt" [B, ..., 3],
+    "pred" [B, ..., 3], "err" [B, ...], "std" [B, ..., 3]} uint8 (the planes named in `want`), every byte the one
+    eval.pack_eval_images gives for that image alone.  The planes are views of ONE uint8 buffer of 10 B n bytes laid out
+    in that order (returned under "buffer": one copy brings all of them to the host), allocated here or taken from the
+    `workspace` arena.  Asynchronous on the current stream, no host synchronisation.  unc_max == unc_min raises ValueError."""
+    lib = _l.load()
+    if float(unc_max) == float(unc_min):
+        raise ValueError(f"eval_images: unc_max == unc_min == {unc_min} (the uncertainty range must not be empty)")
+    unknown = [w for w in want if w not in EVAL_IMAGE_PLANES]
+    if unknown:
+        raise _l.UnerfError(f"eval_images: want = {tuple(want)}: expected names out of {EVAL_IMAGE_PLANES}")
+    if pred.dim() < 2 or sigma.dim() < 1 or pred.shape[-1] != 3:
+        raise _l.UnerfError(f"eval_images: pred {tuple(pred.shape)}, sigma {tuple(sigma.shape)}: expected [B, ..., 3] and [B, ...]")
+    B = int(pred.shape[0])
+    if B < 1 or B > _l.METRICS_MAX_IMAGES:
+        raise _l.UnerfError(f"eval_images: B = {B} images (1..{_l.METRICS_MAX_IMAGES} per call)")
+    n = sigma.numel() // B
+    if sigma.shape[0] != B or pred.numel() != B * n * 3 or target.shape != pred.shape:
+        raise _l.UnerfError(f"eval_images: pred {tuple(pred.shape)}, target {tuple(target.shape)}, sigma {tuple(sigma.shape)}")
+    dev = pred.device
+    lo, span = float(min(unc_min, unc_max)), float(abs(unc_max - unc_min))
+    with _ctx(dev):
+        lut = _JET_LUT.get(str(dev))
+        if lut is None:
+            from . import colormaps
+            lut = _JET_LUT[str(dev)] = torch.from_numpy(colormaps.JET_U8.copy()).to(dev)
+        buf = (workspace.get("eval_images", (B * 10 * n,), dev, dtype=torch.uint8) if workspace is not None
+               else torch.empty(B * 10 * n, device=dev, dtype=torch.uint8))
+        planes = eval_image_planes(buf, B, tuple(pred.shape[1:-1]))
+        nbytes = lib.unerf_eval_images_workspace_bytes(B)
+        ws = (workspace.get("eval_images_range", ((nbytes + 3) // 4,), dev, dtype=torch.int32) if workspace is not None
+              else torch.empty((nbytes + 3) // 4, device=dev, dtype=torch.int32))
+        ptr = lambda name: _p(planes[name], torch.uint8, name) if name in want else None
+        _run("eval_images", lambda: lib.unerf_eval_images_batch(
+            _p(pred, name="pred"), _p(target, name="target"), _p(sigma, name="sigma"), n, B, lo, span, _p(lut, torch.uint8, "lut"),
+            ptr("gt"), ptr("pred"), ptr("err"), ptr("std"), _p(ws, torch.int32, "workspace"), nbytes, _stream()))
+    out = {name: planes[name] for name in EVAL_IMAGE_PLANES if name in want}
+    out["buffer"] = buf
+    return out
+
+
 # ---------------------------------------------------------------- splats ---------------
 
 def splat_project(means3d, scales, glob_scale: float, quats, viewmat: torch.Tensor, fx, fy, cx, cy, H: int, W: int,
