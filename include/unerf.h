@@ -752,6 +752,77 @@ int unerf_eval_images_batch(const float* pred, const float* target, const float*
                             float unc_span, const uint8_t* lut, uint8_t* gt8, uint8_t* pred8, uint8_t* err8, uint8_t* std8,
                             void* workspace, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------- LPIPS ------
+ * The `lpips` entry of metrics.json (scripts/eval_uncertainty.py:681-689: model.lpips = torchmetrics'
+ * LearnedPerceptualImagePatchSimilarity(net_type="alex", normalize=True)) for a batch of B image pairs of ONE size; host
+ * definition uncertainty-nerf-gs_amd/metrics.py: lpips.  Exact fp32 arithmetic in the trunk (fp32-input MFMA: each
+ * product rounded once, one fixed-order accumulation chain per output), float64 in the head.
+ *
+ * unerf_lpips_weights: DEVICE pointers to the network as the kernels read it.  conv_w[l]: [K_l, C_out_l] float32 with
+ * k = (ky * ks + kx) * C_in + c  (torch's [C_out, C_in, ks, ks] weight permuted to (ky, kx, c, C_out)); conv_b[l]
+ * [C_out_l]; lin_w[l] [C_out_l] (the 1x1 head); shift / scale: the ScalingLayer's 3 + 3 constants, by value.
+ * Layers: 11x11 / stride 4 / pad 2, 3 -> 64;  5x5 / pad 2, 64 -> 192;  3x3 / pad 1, 192 -> 384, 384 -> 256, 256 -> 256;
+ * a 3 / 2 max-pool in front of the second and the third. */
+#define UNERF_LPIPS_LAYERS 5
+typedef struct {
+    const float* conv_w[UNERF_LPIPS_LAYERS];
+    const float* conv_b[UNERF_LPIPS_LAYERS];
+    const float* lin_w[UNERF_LPIPS_LAYERS];
+    float shift[3];
+    float scale[3];
+} unerf_lpips_weights;
+
+/* Row of float64 results per image: [l] sum over the pixels of tap l of sum_c lin_w[c] (f0_c / n0 - f1_c / n1)^2 with
+ * n = sqrt(1e-8 + sum_c f_c^2), everything behind the fp32 features in float64; [5 + l] the pixel count of tap l;
+ * [10] the number of values of the (clipped) prediction and of the target outside [0, 1] or NaN.
+ * LPIPS = sum_l row[l] / row[5 + l], valid when row[10] == 0 (metrics.py: finish_lpips). */
+#define UNERF_LPIPS_ROW 11
+#define UNERF_LPIPS_BAD_OFF 10
+#define UNERF_LPIPS_MIN_SIDE 31      /* below it the second max-pool has no output */
+#define UNERF_LPIPS_CONV_TILE_M 64   /* output pixels per workgroup of the convolution kernel (its row tile) */
+#define UNERF_LPIPS_CONV_TILE_N 64   /* output channels per workgroup: C_out must be a multiple */
+#define UNERF_LPIPS_HEAD_PIXELS 64   /* pixels per workgroup of the head kernel */
+
+/* The input pack: pred / target [B, n, 3] float32 (HWC) -> act [2 B, n, 3]: prediction b at b, target b at B + b, each
+ * ((2 x - 1) - shift[c]) / scale[c] in float32, one rounding per operation, with x = the prediction clipped to <= 1 (a
+ * NaN stays one) or the target.  bad [B] uint32 (zeroed inside the call): values of image b outside [0, 1] or NaN,
+ * counted with integer atomics (order-free). */
+int unerf_lpips_pack(const float* pred, const float* target, int64_t n, int B, const unerf_lpips_weights* w, float* act,
+                     uint32_t* bad, void* stream);
+
+/* out[img, oy, ox, co] = relu?(bias[co] + sum_{ky, kx, c} in[img, oy stride - pad + ky, ox stride - pad + kx, c]
+ * w[(ky ks + kx) C_in + c, co]), NHWC float32, taps outside the image contributing zero (predicated loads, no padded
+ * copy); H_out = (H + 2 pad - ks) / stride + 1 (floor), W_out likewise.  An implicit GEMM on the fp32-input MFMA
+ * (32x32x2): rows = the N H_out W_out output pixels of all images in tiles of UNERF_LPIPS_CONV_TILE_M (a tile may
+ * straddle images), columns = C_out in tiles of UNERF_LPIPS_CONV_TILE_N (C_out must be a multiple), reduction over
+ * K = ks ks C_in in ascending k (any K >= 1).  Every output is ONE accumulation chain in that order, then + bias, then
+ * the ReLU: two calls give equal bits.  w: [K, C_out] as in unerf_lpips_weights. */
+int unerf_conv2d_bias_relu(const float* in, const float* w, const float* bias, float* out, int N, int H, int W, int C_in,
+                           int C_out, int ks, int stride, int pad, int relu, void* stream);
+
+/* max_pool2d(kernel 3, stride 2, no padding, floor mode) on NHWC float32: out [N, (H - 3) / 2 + 1, (W - 3) / 2 + 1, C];
+ * exact, a NaN in a window is its result (torch's rule).  H, W >= 3. */
+int unerf_maxpool3s2(const float* in, float* out, int N, int H, int W, int C, void* stream);
+
+/* The head for one tap: feats [2 B, P, C] float32 (image b at b, its partner at B + b), lin_w [C] -> out[b * out_stride]
+ * = the sum over the P pixels described at UNERF_LPIPS_ROW, float64.  One workgroup per UNERF_LPIPS_HEAD_PIXELS pixels
+ * and image (the image is grid.y) writes a partial into the workspace, a second kernel adds an image's partials in index
+ * order: no floating-point atomics, the value of image b does not depend on B.
+ * workspace: B * ceil(P / UNERF_LPIPS_HEAD_PIXELS) doubles, 8-byte aligned. */
+int unerf_lpips_head(const float* feats, const float* lin_w, int64_t P, int C, int B, void* workspace, size_t workspace_bytes,
+                     double* out, int64_t out_stride, void* stream);
+
+/* pred / target [B, H, W, 3] float32, 1 <= B <= UNERF_METRICS_MAX_IMAGES, H, W >= UNERF_LPIPS_MIN_SIDE and
+ * 6 B H W < 2^31 -> out [B, UNERF_LPIPS_ROW].  Row b equals the row of image b alone bit for bit; two calls give equal
+ * rows.  Launches (whatever B is): one memset, the pack, five convolutions, two max-pools, five head pairs, one kernel
+ * that fills the counts.  workspace: unerf_lpips_workspace_bytes(H, W, B) bytes (0 for an unsupported size), 256-byte
+ * aligned: every activation of the trunk (about 61 bytes per input pixel for each of the 2 B stacked images) and the
+ * head's partials; nothing in it is read before it is written.  Argument errors (NULL pointer, H or W < 31, short workspace)
+ * are reported before any device call. */
+size_t unerf_lpips_workspace_bytes(int H, int W, int B);
+int unerf_lpips_batch(const float* pred, const float* target, int H, int W, int B, const unerf_lpips_weights* w,
+                      void* workspace, size_t workspace_bytes, double* out, void* stream);
+
 /* ================================================================ splats ==
  * gsplat 0.1.11 call sites in models/activesplatfacto/activesplatfacto_model.py. */
 

@@ -12,12 +12,76 @@ from __future__ import annotations
 import os
 import re
 from pathlib import Path
+from dataclasses import dataclass, field
 from typing import Dict, Iterable, List, Optional, Sequence, Tuple, Union
 
 import torch
 
 PathLike = Union[str, os.PathLike]
 _STEP = re.compile(r"^step-(\d+)\.ckpt$")
+
+
+# ---- the LPIPS network a nerfstudio checkpoint carries --------------------------------------------------------------
+# nerfstudio models keep `self.lpips = LearnedPerceptualImagePatchSimilarity(normalize=True)` as a submodule, so every
+# pipeline state dict holds the AlexNet trunk and the five 1x1 heads under `_model.lpips.net.*` [UPSTREAM-RECALL
+# torchmetrics.functional.image.lpips: _LPIPS / Alexnet / NetLinLayer / ScalingLayer; the `lpips` package uses the same
+# names with `lins.{i}` next to `lin{i}`].
+LPIPS_CONVS = (("slice1.0", (64, 3, 11, 11)), ("slice2.3", (192, 64, 5, 5)), ("slice3.6", (384, 192, 3, 3)),
+               ("slice4.8", (256, 384, 3, 3)), ("slice5.10", (256, 256, 3, 3)))
+LPIPS_SHIFT = (-0.030, -0.088, -0.188)      # ScalingLayer: registered as non-persistent buffers upstream
+LPIPS_SCALE = (0.458, 0.448, 0.450)
+
+
+@dataclass
+class LpipsWeights:
+    """The tensors of the LPIPS AlexNet, float32 on the CPU, in torch's layouts: convs[l] = (weight [C_out, C_in, k, k],
+    bias [C_out]), lins[l] = the l-th head's weights [C_l] (non-negative in a trained network), shift / scale [3].
+    `_device` caches what the two routes read: the convolutions repacked to [K, C_out] per device (ops.lpips_batch) and the
+    tensors per device and dtype (metrics.lpips).  The tensors are taken as they are when first used: build a new object
+    (or clear `_device`) after changing one."""
+    convs: List[Tuple[torch.Tensor, torch.Tensor]]
+    lins: List[torch.Tensor]
+    shift: torch.Tensor
+    scale: torch.Tensor
+    _device: Dict[str, object] = field(default_factory=dict, repr=False, compare=False)
+
+
+def lpips_weights_from_state_dict(state_dict) -> Optional[LpipsWeights]:
+    """-> the LPIPS weights a checkpoint carries under `[_model.][module.]lpips.net.*`, or None when the set is not
+    complete (no warning: a checkpoint without the network is an ordinary one).  A complete set with a tensor of another
+    shape raises RuntimeError naming the key."""
+    sd = {}
+    for k, v in state_dict.items():
+        k = k[len("_model."):] if k.startswith("_model.") else k
+        k = k[len("module."):] if k.startswith("module.") else k
+        if k.startswith("lpips.net."):
+            sd[k[len("lpips.net."):]] = v
+    if not sd:
+        return None
+    found: Dict[str, Tuple[str, torch.Tensor, Tuple[int, ...]]] = {}
+    for l, (name, shape) in enumerate(LPIPS_CONVS):
+        for leaf, want in (("weight", shape), ("bias", shape[:1])):
+            key = f"net.{name}.{leaf}"
+            if key not in sd:
+                return None
+            found[f"conv{l}.{leaf}"] = (key, sd[key], want)
+        key = next((k for k in (f"lin{l}.model.1.weight", f"lins.{l}.model.1.weight") if k in sd), None)
+        if key is None:
+            return None
+        found[f"lin{l}"] = (key, sd[key], (1, shape[0], 1, 1))
+    for name in ("shift", "scale"):
+        key = f"scaling_layer.{name}"
+        if key in sd:
+            found[name] = (key, sd[key], None)
+    for key, v, want in found.values():
+        if not torch.is_tensor(v) or (want is not None and tuple(v.shape) != want) or (want is None and v.numel() != 3):
+            got = tuple(v.shape) if torch.is_tensor(v) else type(v).__name__
+            raise RuntimeError(f"lpips.net.{key}: shape {got} in the checkpoint, expected {want or '3 values'}")
+    f32 = lambda name: found[name][1].detach().to("cpu", torch.float32).contiguous().clone()
+    return LpipsWeights(convs=[(f32(f"conv{l}.weight"), f32(f"conv{l}.bias")) for l in range(5)],
+                        lins=[f32(f"lin{l}").reshape(-1) for l in range(5)],
+                        shift=f32("shift").reshape(3) if "shift" in found else torch.tensor(LPIPS_SHIFT, dtype=torch.float32),
+                        scale=f32("scale").reshape(3) if "scale" in found else torch.tensor(LPIPS_SCALE, dtype=torch.float32))
 
 
 def checkpoint_steps(load_dir: PathLike) -> List[int]:

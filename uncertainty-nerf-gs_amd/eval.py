@@ -7,8 +7,14 @@ closure ...), computes the reference's per-image RGB metrics under the reference
 rgb_auc_{abs_error,length,neg_error}) plus `num_rays_per_sec` / `fps` (:948-952), averages them over
 the images (:1069-1077) and writes the same `metrics.json` envelope (:1156-1169).
 
-Differences, on purpose: SSIM / LPIPS (torchmetrics / torchvision networks, absent here) are not
-computed; of the plots, the four rendered images per eval image (`save_imgs_rgb`, :209-303) and the test-set
+`lpips` (eval_uncertainty.py:681-689) is computed from the AlexNet weights the checkpoint itself carries under
+`lpips.net.*` (checkpoints.lpips_weights_from_state_dict -> model.lpips_weights; `lpips_weights=` overrides): the
+host definition metrics.lpips, or the HIP kernels behind ops.lpips_batch when fused.  A model without those weights
+leaves the key out, nothing is downloaded.  The formula is restated from torchmetrics' published source and no
+pretrained weights were available to this build, so agreement with torchmetrics on real weights is unverified
+(tests/test_lpips_cpu.py holds the comparison, skipped where torchmetrics or its cached weights are absent).
+
+Differences, on purpose: of the plots, the four rendered images per eval image (`save_imgs_rgb`, :209-303) and the test-set
 sparsification-error plots (:85-98) are written with `save_rendered_images`, the AUCE curve plot and the depth images
 (`save_imgs_depth` returns without writing, :182) are not; and `num_rays_per_sec` is reported twice --
 `num_rays_per_sec` covers render + metrics like the reference's counter (so numbers stay comparable with its metrics.json), while
@@ -35,21 +41,26 @@ from . import metrics as M
 
 
 def image_metrics_unc(outputs: Dict[str, torch.Tensor], gt_image: torch.Tensor, eval_rgb_unc: bool = True,
-                      min_rgb_std_for_nll: float = 3e-2, composite_gt: Optional[Callable] = None, fused: bool = False):
+                      min_rgb_std_for_nll: float = 3e-2, composite_gt: Optional[Callable] = None, fused: bool = False,
+                      lpips_weights=None):
     """get_image_metrics_and_images_unc (eval_uncertainty.py:647-813), RGB part.
     -> (metrics_dict, curves) where curves carries the per-image sparsification / calibration curves
     that the reference accumulates for its test-set plots.
     fused=True: the same keys and curves from one ops.image_metrics call (HIP kernels, one row of float64 sums, one copy to
-    the host) instead of the chain of torch ops below; needs the render on a HIP device."""
+    the host) instead of the chain of torch ops below; needs the render on a HIP device.
+    lpips_weights (a checkpoints.LpipsWeights): adds `lpips` behind `ssim` -- metrics.lpips on the render's device, or
+    ops.lpips_batch when fused (its row rides in the same host copy as the metric row).  None: the key is left out."""
     if fused:
-        return _image_metrics_unc_fused(outputs, gt_image, eval_rgb_unc, min_rgb_std_for_nll, composite_gt)
+        return _image_metrics_unc_fused(outputs, gt_image, eval_rgb_unc, min_rgb_std_for_nll, composite_gt, lpips_weights)
     rgb = torch.clip(outputs["rgb"], max=1.0)
     image = gt_image.to(rgb.device)
     if "background" in outputs and composite_gt is not None:  # splatfacto: blend GT alpha with the background
         image = composite_gt(image, outputs["background"])
-    # psnr / ssim as at eval_uncertainty.py:683-688; lpips needs the pretrained AlexNet weights (not available
-    # offline) and is left out of the dict rather than faked
+    # psnr / ssim / lpips as at eval_uncertainty.py:683-689; lpips with the weights the checkpoint brought, else left
+    # out of the dict rather than faked
     md: Dict[str, float] = {"psnr": M.psnr(rgb, image), "ssim": M.ssim(rgb, image[..., :3])}
+    if lpips_weights is not None:
+        md["lpips"] = M.lpips(rgb, image[..., :3], lpips_weights)
     curves: Dict[str, np.ndarray] = {}
     if eval_rgb_unc:
         rgb_std = outputs["rgb_std"]
@@ -75,17 +86,32 @@ def image_metrics_unc(outputs: Dict[str, torch.Tensor], gt_image: torch.Tensor, 
     return md, curves
 
 
-def _image_metrics_unc_fused(outputs, gt_image, eval_rgb_unc, min_rgb_std_for_nll, composite_gt):
+def _image_metrics_unc_fused(outputs, gt_image, eval_rgb_unc, min_rgb_std_for_nll, composite_gt, lpips_weights=None):
     """image_metrics_unc through the kernels.  The ground-truth composition stays in torch in front of the call
     (elementwise, no sync); the clip of the prediction to <= 1 happens inside the kernels."""
-    from . import ops
+    from . import lib as _l, ops
     rgb, image, std, flags = _rgb_operands(outputs, gt_image, eval_rgb_unc, composite_gt)
     H, W, Cc = rgb.shape
     row = ops.image_metrics(rgb, image, std, None, image_hw=(H, W), clip_max=1.0, nll_min_sigma=min_rgb_std_for_nll, flags=flags)
-    md, curves = M.finish_metrics(row.cpu().numpy(), Cc, "rgb", flags)
+    if lpips_weights is not None:       # both rows in ONE copy to the host
+        row = torch.cat((row, ops.lpips_batch(rgb[None], image[None], lpips_weights)[0]))
+    host = row.cpu().numpy()
+    md, curves = M.finish_metrics(host[:_l.METRICS_ROW], Cc, "rgb", flags)
     if not eval_rgb_unc:
         md = {"psnr": md["psnr"], "ssim": md["ssim"]}
+    if lpips_weights is not None:
+        md = _with_lpips(md, M.finish_lpips(host[_l.METRICS_ROW:]))
     return md, curves
+
+
+def _with_lpips(md: Dict[str, float], value: float) -> Dict[str, float]:
+    """md with `lpips` behind `ssim` (the key order of the torch path)"""
+    out: Dict[str, float] = {}
+    for k, v in md.items():
+        out[k] = v
+        if k == "ssim":
+            out["lpips"] = value
+    return out
 
 
 def _rgb_operands(outputs, gt_image, eval_rgb_unc, composite_gt):
@@ -116,13 +142,15 @@ def _finish_rows(rows_host, image_ids, finish):
 
 def image_metrics_unc_batch(outputs_list: Sequence[Dict[str, torch.Tensor]], gt_images: Sequence[torch.Tensor], eval_rgb_unc: bool = True,
                             min_rgb_std_for_nll: float = 3e-2, composite_gt: Optional[Callable] = None, *,
-                            image_ids: Optional[Sequence[int]] = None):
+                            image_ids: Optional[Sequence[int]] = None, lpips_weights=None):
     """image_metrics_unc(fused=True) for B renders of one size (at most lib.METRICS_MAX_IMAGES) -> [(metrics_dict, curves)] * B.
     The ground-truth composition and the float32 casts stay per image; then one torch.stack per operand, ONE
     ops.image_metrics_batch, one copy of its [B, row] result to the host and finish_metrics per row.  Row b of the batch is
     the row of image b alone bit for bit, so every entry equals the per-image call's.  An image with a non-finite input
-    raises as finish_metrics does, named by image_ids[b] (default: its position in the batch)."""
-    from . import ops
+    raises as finish_metrics does, named by image_ids[b] (default: its position in the batch).
+    lpips_weights: ONE ops.lpips_batch for the batch adds `lpips` to every entry; its [B, row] result is joined to the
+    metric rows on the device, so the batch still crosses to the host in one copy."""
+    from . import lib as _l, ops
     if len(outputs_list) != len(gt_images) or not outputs_list:
         raise ValueError(f"{len(outputs_list)} renders for {len(gt_images)} ground-truth images")
     parts = [_rgb_operands(o, gt, eval_rgb_unc, composite_gt) for o, gt in zip(outputs_list, gt_images)]
@@ -132,10 +160,16 @@ def image_metrics_unc_batch(outputs_list: Sequence[Dict[str, torch.Tensor]], gt_
     rgb, image, std = (torch.stack([p[j] for p in parts]) for j in range(3))
     _, H, W, Cc = rgb.shape
     rows = ops.image_metrics_batch(rgb, image, std, None, image_hw=(H, W), clip_max=1.0, nll_min_sigma=min_rgb_std_for_nll,
-                                   flags=flags).cpu().numpy()
-    done = _finish_rows(rows, image_ids, lambda row: M.finish_metrics(row, Cc, "rgb", flags))
+                                   flags=flags)
+    if lpips_weights is not None:
+        rows = torch.cat((rows, ops.lpips_batch(rgb, image, lpips_weights)), dim=1)
+    rows = rows.cpu().numpy()
+    done = _finish_rows(rows[:, :_l.METRICS_ROW], image_ids, lambda row: M.finish_metrics(row, Cc, "rgb", flags))
     if not eval_rgb_unc:
         done = [({"psnr": md["psnr"], "ssim": md["ssim"]}, curves) for md, curves in done]
+    if lpips_weights is not None:
+        values = _finish_rows(rows[:, _l.METRICS_ROW:], image_ids, M.finish_lpips)
+        done = [(_with_lpips(md, v), curves) for (md, curves), v in zip(done, values)]
     return done
 
 
@@ -398,7 +432,7 @@ def get_average_uncertainty_metrics(get_outputs_for_camera: Callable, eval_set: 
                                     min_depth_std_for_nll: float = 1.0, fused: bool = False, view_batch: int = 1,
                                     get_outputs_for_cameras: Optional[Callable] = None, metric_batch: bool = True,
                                     save_rendered_images: bool = False, plots_path=None, unc_min: float = 0.0,
-                                    unc_max: float = 1.0):
+                                    unc_max: float = 1.0, lpips_weights="model"):
     """eval_uncertainty.py:816-1079.  -> (averaged metrics dict, averaged curves dict).
     depth_gt_fn(image_index) -> (depth_gt [H,W], scale) switches the depth metrics on (eval_depth_unc).
     fused: the per-image metric stage through the HIP kernels (image_metrics_unc / depth_metrics_unc, fused=True).
@@ -417,7 +451,13 @@ def get_average_uncertainty_metrics(get_outputs_for_camera: Callable, eval_set: 
     save_rendered_images (with eval_rgb_unc, as at :754, :799): save_imgs_rgb writes the four PNGs of every eval image under
     plots_path with the range unc_min / unc_max -- one image after its metrics, or the view batch after its batched
     metrics (packed on the device when fused).  The saving counts into the metric time of `num_rays_per_sec` / `fps`, as
-    in the reference's counter (:898, :948-952), and not into `render_rays_per_sec`."""
+    in the reference's counter (:898, :948-952), and not into `render_rays_per_sec`.
+    lpips_weights: a checkpoints.LpipsWeights adds `lpips` per image (averaged like psnr and ssim); None leaves it out; the
+    default "model" takes `lpips_weights` of the object get_outputs_for_camera is bound to (an EnsemblePipeline: of its
+    first member) -- what load_state_dict found in the checkpoint -- or None."""
+    if isinstance(lpips_weights, str):
+        bound = getattr(get_outputs_for_camera, "func", get_outputs_for_camera)      # a functools.partial: its method
+        lpips_weights = default_lpips_weights(getattr(bound, "__self__", None))
     if save_rendered_images and eval_rgb_unc:
         if plots_path is None:
             raise ValueError("save_rendered_images needs plots_path")
@@ -448,7 +488,8 @@ def get_average_uncertainty_metrics(get_outputs_for_camera: Callable, eval_set: 
 
     def score(img_num, outputs, gt, render_s):
         start = time.time()
-        md, curves = image_metrics_unc(outputs, gt, eval_rgb_unc, min_rgb_std_for_nll, composite_gt, fused=fused)
+        md, curves = image_metrics_unc(outputs, gt, eval_rgb_unc, min_rgb_std_for_nll, composite_gt, fused=fused,
+                                       lpips_weights=lpips_weights)
         if depth_gt_fn is not None:
             dgt, scale = depth_gt_fn(img_num)
             dmd, dcurves = depth_metrics_unc(outputs, dgt, scale, min_depth_std_for_nll, fused=fused)
@@ -466,7 +507,7 @@ def get_average_uncertainty_metrics(get_outputs_for_camera: Callable, eval_set: 
             ids = [img_num for img_num, _, _ in pending[c0:c0 + _l.METRICS_MAX_IMAGES]]
             chunk = outs[c0:c0 + len(ids)]
             done = image_metrics_unc_batch(chunk, [gt for _, _, gt in pending[c0:c0 + len(ids)]], eval_rgb_unc, min_rgb_std_for_nll,
-                                           composite_gt, image_ids=ids)
+                                           composite_gt, image_ids=ids, lpips_weights=lpips_weights)
             if depth_gt_fn is not None:
                 dgts, scales = zip(*(depth_gt_fn(i) for i in ids))
                 if len({tuple(np.shape(d)) for d in dgts}) == 1:
@@ -511,6 +552,20 @@ def get_average_uncertainty_metrics(get_outputs_for_camera: Callable, eval_set: 
     flush(pending)
     avg = {k: float(torch.mean(torch.tensor([r[k] for r in rows], dtype=torch.float64))) for k in rows[0]}
     return avg, {k: v / len(rows) for k, v in sums.items()}
+
+
+def default_lpips_weights(model):
+    """`lpips_weights` of a model; of the first member for a list of members or an EnsemblePipeline; None without"""
+    if model is None:
+        return None
+    if isinstance(model, (list, tuple)):
+        return default_lpips_weights(model[0]) if model else None
+    if getattr(model, "lpips_weights", None) is not None:
+        return model.lpips_weights
+    members = getattr(model, "models", None)
+    if members is not None and len(members):
+        return getattr(members[0], "lpips_weights", None)
+    return None
 
 
 def write_metrics_json(path: str, experiment_name: str, method_name: str, checkpoint: str, results: Dict[str, float]):
@@ -610,7 +665,8 @@ def outputs_fn_for(eval_config: EvalConfigs, model, ggn_batches=None, pipeline=N
 
 def run_eval(eval_config: EvalConfigs, model, eval_set, experiment_name: str = "", method_name: str = "",
              checkpoint: str = "", depth_gt_fn: Optional[Callable] = None, composite_gt: Optional[Callable] = None,
-             fused: bool = False, view_batch: int = 1, metric_batch: bool = True, **fn_kw) -> Dict[str, float]:
+             fused: bool = False, view_batch: int = 1, metric_batch: bool = True, lpips_weights="model",
+             **fn_kw) -> Dict[str, float]:
     """main() of scripts/eval_uncertainty.py:1082-1169 without nerfstudio's pipeline loading: pick the method's
     callable, average the per-image metrics, write the metrics.json envelope to eval_config.output_path.
     fused=True computes the per-image metrics with the HIP kernels behind ops.image_metrics (same keys; opt-in).
@@ -624,7 +680,11 @@ def run_eval(eval_config: EvalConfigs, model, eval_set, experiment_name: str = "
     (get_average_uncertainty_metrics); False keeps the per-image fused scoring.  Same numbers either way.
     eval_config.save_rendered_images: the four rendered images per eval image (save_imgs_rgb, with eval_config.unc_min /
     unc_max) and the test-set sparsification plots (save_sparsification_plots; depth ones when depth is evaluated) go to
-    `output_path.parent / "plots"` (:699-700).  Off (the default): no directory, the same keys."""
+    `output_path.parent / "plots"` (:699-700).  Off (the default): no directory, the same keys.
+    lpips_weights: a checkpoints.LpipsWeights, None (no `lpips` key), or the default "model": the weights the model's
+    checkpoint brought (default_lpips_weights: model.lpips_weights, the first member's for an ensemble)."""
+    if isinstance(lpips_weights, str):
+        lpips_weights = default_lpips_weights(model)
     fn = outputs_fn_for(eval_config, model, **fn_kw)
     batch_fn = None
     if view_batch > 1 and isinstance(eval_config, LaplaceConfig):
@@ -645,7 +705,7 @@ def run_eval(eval_config: EvalConfigs, model, eval_set, experiment_name: str = "
         min_depth_std_for_nll=eval_config.min_depth_std_for_nll, fused=fused,
         view_batch=view_batch if batch_fn is not None else 1, get_outputs_for_cameras=batch_fn, metric_batch=metric_batch,
         save_rendered_images=eval_config.save_rendered_images, plots_path=plots_path, unc_min=eval_config.unc_min,
-        unc_max=eval_config.unc_max)
+        unc_max=eval_config.unc_max, lpips_weights=lpips_weights)
     if plots_path is not None:
         for output in ("depth", "rgb"):
             if f"{output}_all_ause_mse" in curves:

@@ -16,7 +16,7 @@ CSRC = os.path.join(_HERE, "csrc")
 INCLUDE = os.path.join(os.path.dirname(_HERE), "include")
 # UNERF_LIB: another build of the same ABI, for A/B timing on one box (benchmarks/ab_bench.sh); unset in normal use
 LIB_PATH = os.environ.get("UNERF_LIB") or os.path.join(CSRC, "libunerf.so")
-SOURCES = ["unerf_nerf.hip", "unerf_splat.hip", "unerf_metrics.hip"]
+SOURCES = ["unerf_nerf.hip", "unerf_splat.hip", "unerf_metrics.hip", "unerf_lpips.hip"]
 # text included by the sources (unerf_nerf.hip compiles the f16 matrix field kernels from the two .inc files under two names each)
 INCLUDED = ["unerf_common.hpp", "unerf_field_mfma16.inc", "unerf_field_lap16.inc"]
 # -amdgpu-mfma-vgpr-form: gfx950 has one unified register file; let the MFMAs write their accumulators to
@@ -175,6 +175,15 @@ class EnsOut(C.Structure):
     _fields_ = [("stat", C.c_int32), ("key", C.c_int32), ("aux", C.c_int32), ("reserved", C.c_int32), ("offset", C.c_int64)]
 
 
+LPIPS_LAYERS = 5                                  # include/unerf.h: UNERF_LPIPS_LAYERS
+
+
+class LpipsWeightsC(C.Structure):
+    """include/unerf.h: unerf_lpips_weights (device pointers to the repacked AlexNet, the scaling constants by value)"""
+    _fields_ = [("conv_w", C.c_void_p * LPIPS_LAYERS), ("conv_b", C.c_void_p * LPIPS_LAYERS), ("lin_w", C.c_void_p * LPIPS_LAYERS),
+                ("shift", C.c_float * 3), ("scale", C.c_float * 3)]
+
+
 ABI_VERSION = 1420                                # include/unerf.h: UNERF_ABI_VERSION (struct layouts / argument lists)
 FIELD_ACTIVE, FIELD_MCDROPOUT, FIELD_LAPLACE = 0, 1, 2
 SPACING_PIECEWISE, SPACING_UNIFORM = 0, 1         # include/unerf.h: UNERF_SPACING_*
@@ -243,6 +252,12 @@ SIGNATURES = {
                                        _i, _i, _vp, C.c_size_t, _vp, _vp]),
     "unerf_eval_images_workspace_bytes": (C.c_size_t, [_i]),
     "unerf_eval_images_batch": (_i, [_vp, _vp, _vp, _i64, _i, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
+    "unerf_lpips_pack": (_i, [_vp, _vp, _i64, _i, C.POINTER(LpipsWeightsC), _vp, _vp, _vp]),
+    "unerf_conv2d_bias_relu": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "unerf_maxpool3s2": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
+    "unerf_lpips_head": (_i, [_vp, _vp, _i64, _i, _i, _vp, C.c_size_t, _vp, _i64, _vp]),
+    "unerf_lpips_workspace_bytes": (C.c_size_t, [_i, _i, _i]),
+    "unerf_lpips_batch": (_i, [_vp, _vp, _i, _i, _i, C.POINTER(LpipsWeightsC), _vp, C.c_size_t, _vp, _vp]),
     "unerf_splat_project": (_i, [_vp, _vp, _f, _vp, _fp, _f, _f, _f, _f, _i, _i, _i, _f, _i64, _vp, _vp, _vp, _vp,
                                  _vp, _vp, _vp, _vp]),
     "unerf_splat_project_raw": (_i, [_vp, _vp, _f, _vp, _fp, _f, _f, _f, _f, _i, _i, _i, _f, _i64, _vp, _i, _vp, _vp, _vp,
@@ -275,6 +290,9 @@ METRICS_AUSE, METRICS_AUCE, METRICS_NLL, METRICS_SSIM = 1, 2, 4, 8
 METRICS_ALL = METRICS_AUSE | METRICS_AUCE | METRICS_NLL | METRICS_SSIM
 METRICS_AUCE_OFF, METRICS_AUSE_OFF, METRICS_ROW, METRICS_MAX_CUTS = 16, 144, 656, 128
 METRICS_MAX_IMAGES = 64                           # include/unerf.h: UNERF_METRICS_MAX_IMAGES (unerf_image_metrics_batch)
+# include/unerf.h: UNERF_LPIPS_* (row of unerf_lpips_batch, tiles of its kernels)
+LPIPS_ROW, LPIPS_BAD_OFF, LPIPS_MIN_SIDE = 11, 10, 31
+LPIPS_CONV_TILE_M, LPIPS_CONV_TILE_N, LPIPS_HEAD_PIXELS = 64, 64, 64
 # include/unerf.h: UNERF_ENS_* (bounds and statistics of unerf_ensemble_reduce)
 ENS_MAX_KEYS, ENS_MAX_MEMBERS, ENS_MAX_CHANNELS = 32, 64, 64
 ENS_MEAN, ENS_VAR, ENS_VAR_CMEAN, ENS_ALEA_CMEAN, ENS_EPI_ALEA, ENS_EPI_ALEA_SQRT, ENS_STD_CMEAN = range(7)

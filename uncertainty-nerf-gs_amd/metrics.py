@@ -8,7 +8,7 @@ tensors live on; results agree with the reference implementation to ~1e-7 (golde
 from __future__ import annotations
 
 import math
-from typing import Dict, Optional, Tuple
+from typing import Dict, List, Optional, Tuple
 
 import numpy as np
 import torch
@@ -159,6 +159,104 @@ def ssim(pred: torch.Tensor, gt: torch.Tensor, data_range=None) -> float:
     upper, lower = 2 * s_pt + c2, s_pp + s_tt + c2
     idx = ((2 * mu_p * mu_t + c1) * upper) / ((mu_p ** 2 + mu_t ** 2 + c1) * lower)
     return float(idx[..., pad:-pad, pad:-pad].mean().item())
+
+
+LPIPS_NORM_EPS = 1e-8      # inside the square root of the channel norm (torchmetrics' _normalize_tensor)
+LPIPS_MIN_SIDE = 31        # below it the second 3/2 max-pool of the AlexNet trunk has no output
+LPIPS_LAYERS = 5
+
+
+def lpips_map_sizes(H: int, W: int):
+    """(h, w) of the five taps of the AlexNet trunk for an H x W image: conv1 11x11 / 4 / pad 2, max-pool 3 / 2 (floor),
+    conv2 5x5 / pad 2, max-pool 3 / 2, conv3..5 3x3 / pad 1"""
+    c1 = ((H + 4 - 11) // 4 + 1, (W + 4 - 11) // 4 + 1)
+    p1 = ((c1[0] - 3) // 2 + 1, (c1[1] - 3) // 2 + 1)
+    p2 = ((p1[0] - 3) // 2 + 1, (p1[1] - 3) // 2 + 1)
+    return [c1, p1, p2, p2, p2]
+
+
+def _lpips_operands(pred: torch.Tensor, target: torch.Tensor):
+    """[H,W,3] / [B,H,W,3] pairs -> ([B,H,W,3] prediction clipped to <= 1, [B,H,W,3] target), checked as upstream's
+    input check under normalize=True does it: every value in [0, 1], no NaN"""
+    if pred.dim() == 3:
+        pred, target = pred[None], target[None]
+    if pred.dim() != 4 or pred.shape[-1] != 3 or target.shape != pred.shape:
+        raise ValueError(f"lpips: pred {tuple(pred.shape)}, target {tuple(target.shape)}: expected two [H,W,3] or [B,H,W,3] images")
+    H, W = int(pred.shape[1]), int(pred.shape[2])
+    if min(H, W) < LPIPS_MIN_SIDE:
+        raise ValueError(f"lpips: a {H} x {W} image; the AlexNet trunk needs min(H, W) >= {LPIPS_MIN_SIDE} "
+                         "(below it the second max-pool has no output)")
+    pred = torch.clip(pred, max=1.0)                        # eval_uncertainty.py:681
+    for name, x in (("prediction", pred), ("target", target)):
+        bad = int((~((x >= 0) & (x <= 1))).sum().item())    # a NaN fails both comparisons
+        if bad:
+            raise ValueError(f"lpips: {bad} values of the {name} are outside [0, 1] or NaN")
+    return pred, target
+
+
+def lpips_features(images: torch.Tensor, weights, dtype=torch.float32) -> List[torch.Tensor]:
+    """the five ReLU taps [N, C_l, h_l, w_l] of the AlexNet trunk for images [N,H,W,3] in [0, 1], in `dtype`"""
+    Fn = torch.nn.functional
+    shift, scale, convs, _ = _lpips_tensors(weights, images.device, dtype)
+    x = images.to(dtype).permute(0, 3, 1, 2)
+    x = 2 * x - 1
+    x = (x - shift) / scale
+    taps = []
+    for l, (stride, pad) in enumerate(((4, 2), (1, 2), (1, 1), (1, 1), (1, 1))):
+        if l in (1, 2):
+            x = Fn.max_pool2d(x, kernel_size=3, stride=2)
+        x = torch.relu(Fn.conv2d(x, convs[l][0], convs[l][1], stride=stride, padding=pad))
+        taps.append(x)
+    return taps
+
+
+def _lpips_tensors(weights, device, dtype):
+    """the weights as `dtype` tensors on `device`, converted once per LpipsWeights object (its `_device` cache):
+    (shift [1,3,1,1], scale [1,3,1,1], [(conv weight, bias)] * 5, [head weights [1,C,1,1]] * 5)"""
+    key = ("torch", str(torch.device(device)), str(dtype))
+    hit = weights._device.get(key)
+    if hit is None:
+        to = lambda t: t.to(device, dtype)
+        hit = weights._device[key] = (to(weights.shift).view(1, 3, 1, 1), to(weights.scale).view(1, 3, 1, 1),
+                                      [(to(w), to(b)) for w, b in weights.convs], [to(l).view(1, -1, 1, 1) for l in weights.lins])
+    return hit
+
+
+def lpips_per_image(pred: torch.Tensor, target: torch.Tensor, weights, dtype=torch.float32) -> torch.Tensor:
+    """`lpips` per image of a batch -> [B] tensor of `dtype` on the images' device"""
+    pred, target = _lpips_operands(pred, target)
+    B = pred.shape[0]
+    taps = lpips_features(torch.cat((pred, target)), weights, dtype)
+    total = torch.zeros(B, dtype=dtype, device=pred.device)
+    for f, lin in zip(taps, _lpips_tensors(weights, pred.device, dtype)[3]):
+        f = f / torch.sqrt(LPIPS_NORM_EPS + torch.sum(f ** 2, dim=1, keepdim=True))
+        d = (f[:B] - f[B:]) ** 2
+        total = total + (d * lin).sum(dim=1).mean(dim=(1, 2))
+    return total
+
+
+def lpips(pred: torch.Tensor, target: torch.Tensor, weights, dtype=torch.float32) -> float:
+    """torchmetrics LearnedPerceptualImagePatchSimilarity(net_type="alex", normalize=True) as reached through
+    model.lpips (scripts/eval_uncertainty.py:681-689) on [H,W,3] or [B,H,W,3] images (a batch gives the mean over its
+    images, the module's reduction), with `weights` a checkpoints.LpipsWeights.  [UPSTREAM-RECALL, torchmetrics is absent
+    here]: x = 2 img - 1, then (x - shift) / scale; AlexNet features: conv 11x11 / 4 / pad 2, ReLU (tap), max-pool 3 / 2,
+    conv 5x5 / pad 2, ReLU (tap), max-pool 3 / 2, three times conv 3x3 / pad 1 + ReLU (tap each); per tap
+    f / sqrt(LPIPS_NORM_EPS + sum_c f^2) for both images, the squared difference, the head's 1x1 weights over the
+    channels, the spatial mean; the five means are added.  The prediction is clipped to <= 1 first; a value outside
+    [0, 1] or a NaN in either image raises ValueError, as does min(H, W) < LPIPS_MIN_SIDE.  Plain torch on the images'
+    device: the CPU path, and with dtype=torch.float64 the yardstick the kernels behind ops.lpips_batch are held to."""
+    return float(lpips_per_image(pred, target, weights, dtype).to(torch.float64).mean().item())
+
+
+def finish_lpips(row_host) -> float:
+    """one host copy of a row of ops.lpips_batch (include/unerf.h: unerf_lpips_batch) -> LPIPS: the five layer sums over
+    their pixel counts, added.  Raises if the kernels counted a value outside [0, 1] or a NaN."""
+    from . import lib as _l
+    row = np.asarray(row_host, dtype=np.float64)
+    bad = int(row[_l.LPIPS_BAD_OFF])
+    if bad:
+        raise ValueError(f"lpips: {bad} values of the prediction or the target are outside [0, 1] or NaN")
+    return float(sum(row[l] / row[LPIPS_LAYERS + l] for l in range(LPIPS_LAYERS)))
 
 
 def negative_gaussian_loglikelihood(preds: torch.Tensor, targets: torch.Tensor, stds: torch.Tensor,

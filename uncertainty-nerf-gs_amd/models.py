@@ -305,9 +305,12 @@ def load_checked(model: nn.Module, state_dict, strict: bool = False) -> Incompat
 
 
 class _ImageMetrics:
-    """`model.psnr(image, rgb)` / `model.ssim(image, rgb)` on [1,3,H,W] images, as the eval script calls them
-    (scripts/eval_uncertainty.py:683-684; nerfstudio sets them to torchmetrics' PSNR(data_range=1.0) and SSIM).
-    `lpips` needs the pretrained AlexNet weights and raises."""
+    """`model.psnr(image, rgb)` / `model.ssim(image, rgb)` / `model.lpips(image, rgb)` on [1,3,H,W] images, as the eval
+    script calls them (scripts/eval_uncertainty.py:683-689; nerfstudio sets them to torchmetrics' PSNR(data_range=1.0),
+    SSIM and LearnedPerceptualImagePatchSimilarity(normalize=True)).  `lpips` needs the network's weights: a checkpoint
+    that carries `lpips.net.*` supplies them at load_state_dict (checkpoints.lpips_weights_from_state_dict), or
+    set_lpips_weights by hand; `lpips_weights` is a plain attribute, neither parameter nor buffer."""
+    lpips_weights = None
 
     @staticmethod
     def psnr(image: torch.Tensor, rgb: torch.Tensor) -> torch.Tensor:
@@ -319,9 +322,22 @@ class _ImageMetrics:
         from . import metrics
         return torch.tensor(metrics.ssim(rgb, image), dtype=torch.float64)
 
-    @staticmethod
-    def lpips(image: torch.Tensor, rgb: torch.Tensor):
-        raise NotImplementedError("LPIPS needs pretrained network weights, which this offline build does not ship")
+    def set_lpips_weights(self, weights) -> None:
+        """weights: a checkpoints.LpipsWeights (or None to drop them)"""
+        object.__setattr__(self, "lpips_weights", weights)
+
+    def _adopt_lpips_weights(self, state_dict) -> None:
+        from .checkpoints import lpips_weights_from_state_dict
+        self.set_lpips_weights(lpips_weights_from_state_dict(state_dict))
+
+    def lpips(self, image: torch.Tensor, rgb: torch.Tensor) -> torch.Tensor:
+        """[1,3,H,W] (or [B,3,H,W]) images in [0, 1] -> the 0-d float64 LPIPS (metrics.lpips, the host definition)"""
+        if self.lpips_weights is None:
+            raise NotImplementedError("LPIPS needs the AlexNet weights: load a checkpoint that carries `lpips.net.*` keys "
+                                      "(every nerfstudio checkpoint does) or call set_lpips_weights")
+        from . import metrics
+        return torch.tensor(metrics.lpips(rgb.permute(0, 2, 3, 1), image.permute(0, 2, 3, 1), self.lpips_weights),
+                            dtype=torch.float64)
 
 
 class _NerfactoBase(nn.Module, _ImageMetrics):
@@ -371,7 +387,9 @@ class _NerfactoBase(nn.Module, _ImageMetrics):
         for m in self.modules():
             if hasattr(m, "invalidate") and m is not self:
                 m.invalidate()
-        return load_checked(self, state_dict, strict=strict)
+        report = load_checked(self, state_dict, strict=strict)
+        self._adopt_lpips_weights(state_dict)
+        return report
 
     # -- lowering to the device ---------------------------------------------------------------
     def _field_to_device(self, device):
@@ -943,6 +961,7 @@ class SplatfactoModel(nn.Module, _ImageMetrics):
         of this model's gaussian parameters (a plain splatfacto run loaded as active-splatfacto has no
         `log_uncertainties`) raises instead of leaving it at its random initial value (load_checked)."""
         self.step = 30000
+        lpips_source = dict
         dict = strip_pipeline_prefixes(dict)
         if "means" in dict:
             for p in self.GAUSS:
@@ -954,7 +973,9 @@ class SplatfactoModel(nn.Module, _ImageMetrics):
         newp = dict["gauss_params.means"].shape[0]
         for name, param in self.gauss_params.items():
             self.gauss_params[name] = nn.Parameter(torch.zeros((newp,) + param.shape[1:], device=param.device))
-        return load_checked(self, dict, strict=strict)
+        report = load_checked(self, dict, strict=strict)
+        self._adopt_lpips_weights(lpips_source)
+        return report
 
     def set_crop(self, crop_box) -> None:
         """[UPSTREAM SplatfactoModel.set_crop] crop_box: None or an object with `.within(points [N,3]) -> bool [N(,1)]`

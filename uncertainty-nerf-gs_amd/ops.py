@@ -1598,6 +1598,133 @@ def eval_images(pred: torch.Tensor, target: torch.Tensor, sigma: torch.Tensor, u
     return out
 
 
+# ------------------------------------------------------- LPIPS ---------------------------
+
+_LPIPS_ARENA = Workspace()      # the trunk's activations (about 120 bytes per input pixel and image pair), kept between calls
+
+
+def lpips_device_weights(weights, device):
+    """a checkpoints.LpipsWeights as the kernels read it on `device`, made once per object and device: the convolutions
+    repacked from [C_out, C_in, ks, ks] to [K, C_out] with k = (ky ks + kx) C_in + c, biases, head weights, and the ctypes
+    struct that points at them.  -> (lib.LpipsWeightsC, the tensors it points at)"""
+    key = str(torch.device(device))
+    hit = weights._device.get(key)
+    if hit is not None:
+        return hit
+    convs = [(w.to(torch.float32).permute(2, 3, 1, 0).reshape(-1, w.shape[0]).contiguous().to(device),
+              b.to(torch.float32).contiguous().to(device)) for w, b in weights.convs]
+    lins = [l.to(torch.float32).reshape(-1).contiguous().to(device) for l in weights.lins]
+    st = _l.LpipsWeightsC()
+    for l in range(_l.LPIPS_LAYERS):
+        st.conv_w[l], st.conv_b[l], st.lin_w[l] = convs[l][0].data_ptr(), convs[l][1].data_ptr(), lins[l].data_ptr()
+    for c in range(3):
+        st.shift[c], st.scale[c] = float(weights.shift[c]), float(weights.scale[c])
+    weights._device[key] = (st, (convs, lins))
+    return weights._device[key]
+
+
+def lpips_pack(pred: torch.Tensor, target: torch.Tensor, weights) -> Tuple[torch.Tensor, torch.Tensor]:
+    """unerf_lpips_pack: pred / target [B, ..., 3] float32 -> (the scaled activation stack [2 B, ..., 3]: predictions
+    clipped to <= 1 first, then targets; int32 [B] counts of values outside [0, 1] or NaN per image)"""
+    lib = _l.load()
+    B = int(pred.shape[0])
+    n = pred.numel() // (3 * max(B, 1))
+    if pred.dim() < 2 or pred.shape[-1] != 3 or target.shape != pred.shape:
+        raise _l.UnerfError(f"lpips_pack: pred {tuple(pred.shape)}, target {tuple(target.shape)}: expected two [B, ..., 3] stacks")
+    dev = pred.device
+    with _ctx(dev):
+        st, _keep = lpips_device_weights(weights, dev)
+        act = torch.empty((2 * B,) + tuple(pred.shape[1:]), device=dev, dtype=torch.float32)
+        bad = torch.empty(B, device=dev, dtype=torch.int32)
+        _run("lpips_pack", lambda: lib.unerf_lpips_pack(_p(pred, name="pred"), _p(target, name="target"), n, B, C.byref(st),
+                                                        _p(act, name="act"), _p(bad, torch.int32, "bad"), _stream()))
+    return act, bad
+
+
+def conv2d_bias_relu(x: torch.Tensor, w_packed: torch.Tensor, bias: torch.Tensor, ks: int, stride: int = 1, pad: int = 0,
+                     relu: bool = True, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """unerf_conv2d_bias_relu: x [N, H, W, C_in] (NHWC), w_packed [ks ks C_in, C_out] (k = (ky ks + kx) C_in + c), bias
+    [C_out] -> [N, H_out, W_out, C_out].  C_out must be a multiple of lib.LPIPS_CONV_TILE_N.  out: write there instead
+    of a fresh tensor."""
+    lib = _l.load()
+    if x.dim() != 4 or w_packed.dim() != 2 or w_packed.shape[0] != ks * ks * x.shape[3] or bias.shape != (w_packed.shape[1],):
+        raise _l.UnerfError(f"conv2d_bias_relu: x {tuple(x.shape)}, w_packed {tuple(w_packed.shape)}, bias {tuple(bias.shape)}, ks = {ks}")
+    N, H, W, Ci = (int(v) for v in x.shape)
+    Co = int(w_packed.shape[1])
+    Ho, Wo = (H + 2 * pad - ks) // stride + 1, (W + 2 * pad - ks) // stride + 1
+    dev = x.device
+    with _ctx(dev):
+        if out is None:
+            out = torch.empty(N, max(Ho, 0), max(Wo, 0), Co, device=dev, dtype=torch.float32)
+        elif tuple(out.shape) != (N, Ho, Wo, Co):
+            raise _l.UnerfError(f"conv2d_bias_relu: out {tuple(out.shape)}, expected {(N, Ho, Wo, Co)}")
+        _run("conv2d_bias_relu", lambda: lib.unerf_conv2d_bias_relu(
+            _p(x, name="x"), _p(w_packed, name="w_packed"), _p(bias, name="bias"), _p(out, name="out"), N, H, W, Ci, Co, int(ks),
+            int(stride), int(pad), int(bool(relu)), _stream()))
+    return out
+
+
+def maxpool3s2(x: torch.Tensor) -> torch.Tensor:
+    """unerf_maxpool3s2: x [N, H, W, C] (NHWC) -> max_pool2d(3, stride 2, floor mode) [N, (H - 3) // 2 + 1, (W - 3) // 2 + 1, C]"""
+    lib = _l.load()
+    if x.dim() != 4:
+        raise _l.UnerfError(f"maxpool3s2: x {tuple(x.shape)}: expected [N, H, W, C]")
+    N, H, W, Cc = (int(v) for v in x.shape)
+    dev = x.device
+    with _ctx(dev):
+        out = torch.empty(N, max((H - 3) // 2 + 1, 0), max((W - 3) // 2 + 1, 0), Cc, device=dev, dtype=torch.float32)
+        _run("maxpool3s2", lambda: lib.unerf_maxpool3s2(_p(x, name="x"), _p(out, name="out"), N, H, W, Cc, _stream()))
+    return out
+
+
+def lpips_head(feats: torch.Tensor, lin_w: torch.Tensor) -> torch.Tensor:
+    """unerf_lpips_head: feats [2 B, ..., C] float32 (image b at b, its partner at B + b), lin_w [C] -> float64 [B]: per
+    image the sum over the pixels of sum_c lin_w[c] (f0_c / n0 - f1_c / n1)^2, n = sqrt(1e-8 + sum_c f_c^2), in float64"""
+    lib = _l.load()
+    if feats.dim() < 2 or feats.shape[0] % 2 or lin_w.shape != (feats.shape[-1],):
+        raise _l.UnerfError(f"lpips_head: feats {tuple(feats.shape)}, lin_w {tuple(lin_w.shape)}: expected [2 B, ..., C] and [C]")
+    B, Cc = int(feats.shape[0]) // 2, int(feats.shape[-1])
+    P = feats.numel() // (2 * B * Cc)
+    dev = feats.device
+    with _ctx(dev):
+        words = B * ((P + _l.LPIPS_HEAD_PIXELS - 1) // _l.LPIPS_HEAD_PIXELS)
+        ws = torch.empty(max(words, 1), device=dev, dtype=torch.float64)
+        out = torch.empty(B, device=dev, dtype=torch.float64)
+        _run("lpips_head", lambda: lib.unerf_lpips_head(_p(feats, name="feats"), _p(lin_w, name="lin_w"), P, Cc, B,
+                                                        _p(ws, torch.float64, "workspace"), words * 8, _p(out, torch.float64, "out"),
+                                                        1, _stream()))
+    return out
+
+
+def lpips_batch(pred: torch.Tensor, target: torch.Tensor, weights, workspace: Optional[Workspace] = None) -> torch.Tensor:
+    """unerf_lpips_batch: pred / target [B, H, W, 3] contiguous float32 stacks in [0, 1] (the prediction is clipped to <= 1
+    inside), weights a checkpoints.LpipsWeights -> the device tensor [B, lib.LPIPS_ROW] float64 (layer sums, pixel counts,
+    the count of refused values: include/unerf.h; metrics.finish_lpips turns a host copy of a row into the number).  Row b
+    is the row of image b alone bit for bit.  The launches of one image, whatever B is; asynchronous on the current stream,
+    no host synchronisation.  Scratch comes from `workspace` (default: this module's persistent arena)."""
+    lib = _l.load()
+    if pred.dim() != 4 or pred.shape[-1] != 3 or target.shape != pred.shape:
+        raise _l.UnerfError(f"lpips_batch: pred {tuple(pred.shape)}, target {tuple(target.shape)}: expected two [B, H, W, 3] stacks")
+    B, H, W = int(pred.shape[0]), int(pred.shape[1]), int(pred.shape[2])
+    if B < 1 or B > _l.METRICS_MAX_IMAGES:
+        raise _l.UnerfError(f"lpips_batch: B = {B} images (1..{_l.METRICS_MAX_IMAGES} per call)")
+    if min(H, W) < _l.LPIPS_MIN_SIDE:
+        raise ValueError(f"lpips_batch: a {H} x {W} image; the AlexNet trunk needs min(H, W) >= {_l.LPIPS_MIN_SIDE}")
+    dev = pred.device
+    with _ctx(dev):
+        st, _keep = lpips_device_weights(weights, dev)
+        nbytes = lib.unerf_lpips_workspace_bytes(H, W, B)
+        if nbytes == 0:
+            raise _l.UnerfError(f"lpips_batch: {B} images of {H} x {W}: 6 B H W must stay below 2^31")
+        words = (nbytes + 7) // 8
+        ws = (_LPIPS_ARENA if workspace is None else workspace).get("lpips_batch", (words,), dev, dtype=torch.float64)
+        out = torch.zeros(B, _l.LPIPS_ROW, device=dev, dtype=torch.float64)
+        _run("lpips_batch", lambda: lib.unerf_lpips_batch(_p(pred, name="pred"), _p(target, name="target"), H, W, B, C.byref(st),
+                                                          _p(ws, torch.float64, "workspace"), nbytes, _p(out, torch.float64, "out"),
+                                                          _stream()))
+    return out
+
+
 # ---------------------------------------------------------------- splats ---------------
 
 def splat_project(means3d, scales, glob_scale: float, quats, viewmat: torch.Tensor, fx, fy, cx, cy, H: int, W: int,

@@ -222,3 +222,22 @@ def make_splat_tensors(seed: int = 7, N: int = 1_000_000) -> Dict[str, torch.Ten
         "features_rest": torch.randn(N, 15, 3, generator=g) * 0.05,
         "log_uncertainties": torch.rand(N, 1, generator=g),
     }
+
+
+def make_lpips_weights(seed: int = 0, heads: str = "lin") -> Dict[str, torch.Tensor]:
+    """A state dict of the LPIPS AlexNet under upstream's key names (`lpips.net.*`, checkpoints.LPIPS_CONVS) with seeded
+    random values -- no pretrained weights exist offline: He-scaled normal convolutions, small biases, non-negative head
+    weights (as the trained heads are).  heads = "lin" (`lin{l}.model.1.weight`, torchmetrics) or "lins"
+    (`lins.{l}.model.1.weight`, the other spelling the `lpips` package registers).  Feeds the tests and the benchmark."""
+    from .checkpoints import LPIPS_CONVS
+    if heads not in ("lin", "lins"):
+        raise ValueError(f"heads={heads!r}: expected 'lin' or 'lins'")
+    gen = torch.Generator().manual_seed(seed)
+    sd: Dict[str, torch.Tensor] = {}
+    for l, (name, shape) in enumerate(LPIPS_CONVS):
+        fan_in = shape[1] * shape[2] * shape[3]
+        sd[f"lpips.net.net.{name}.weight"] = torch.randn(shape, generator=gen) * math.sqrt(2.0 / fan_in)
+        sd[f"lpips.net.net.{name}.bias"] = (torch.rand(shape[0], generator=gen) * 2 - 1) * 0.05
+        head = f"lin{l}" if heads == "lin" else f"lins.{l}"
+        sd[f"lpips.net.{head}.model.1.weight"] = torch.rand(1, shape[0], 1, 1, generator=gen) / shape[0]
+    return sd
