@@ -439,7 +439,7 @@ def get_weights(density: torch.Tensor, deltas: torch.Tensor) -> torch.Tensor:
     dd = deltas * density
     alphas = 1 - torch.exp(-dd)
     trans = torch.cumsum(dd[..., :-1], dim=-1)
-    trans = torch.cat([torch.zeros_like(trans[..., :1]), trans], dim=-1)
+    trans = torch.cat([torch.zeros_like(dd[..., :1]), trans], dim=-1)   # (of dd: width 1 with one sample per ray too)
     trans = torch.exp(-trans)
     return torch.nan_to_num(alphas * trans)
 
