@@ -468,6 +468,26 @@ int unerf_laplace_ggn_diag(const float* origins, const float* directions, const 
                            void* workspace, size_t workspace_bytes, float* ggn_density, float* ggn_rgb,
                            void* stream);
 
+/* Per-ray camera-pose gradient: nerfuncertainty/scripts/estimate_gradient_pose_6dof.py:58-216 (one
+ * torch.autograd.grad(pred_rgb.mean(-1), c2w) per pixel of a frame) in one launch, without an autograd tape.
+ * s = channel mean of the eval-mode rgb of a ray (nan_to_num as in the forward; the clamp to [0, 1] passes the gradient
+ * where 0 <= pred <= 1; background as unerf_laplace_ggn_diag: for UNERF_BG_LAST_SAMPLE the transmittance left behind the
+ * last sample flows into that sample's colour).  The sample bins are held FIXED (upstream's PDFSampler detaches them): the
+ * pose reaches s through the sample positions o + d t_i and the SH encoding of d only.
+ *   rot_inv_host NULL : out_grad [R,6]  = (ds/do, ds/dd), d taken as a free vector
+ *   rot_inv_host [9]  : the inverse of c2w[:3,:3], row-major (host); out_grad [R,12] = ds/dc2w, row-major 3x4:
+ *                       ds/dc2w[:,3] = ds/do and ds/dc2w[a][b] = P[a] (R^-1 d)[b] with P = (I - d d^T) ds/dd -- autograd
+ *                       through d = normalize(R dir_cam) for any invertible R and any camera whose origin is c2w[:,3]
+ *   out_rgb           : NULL, or [R,3] <- the colour the kernel composited
+ * p: mode ACTIVE (trunk output 17) or MCDROPOUT (16; evaluated without dropout -- plain nerfacto), nerfacto's widths,
+ * torch-layout or tcnn-layout grid (grid_half: the half2 rows are widened on read); everything is computed in fp32,
+ * the blobs are not read.  sbins [R,S+1] spacing-domain bins, S <= 64.  Anything else (LAPLACE, other widths,
+ * near_plane < 0) is UNERF_ERR_ARG before any launch.  Two calls with the same inputs return the same bits. */
+int unerf_pose_grad(const float* origins, const float* directions, const float* sbins, int64_t R, int S,
+                    float near_plane, float far_plane, int spacing, const unerf_field_params* p /* host struct */,
+                    int background, const float* background_rgb_host, const float* rot_inv_host,
+                    float* out_grad, float* out_rgb, void* stream);
+
 /* ------------------------------------------------- composite + variance --
  * Replaces RaySamples.get_weights + RGB/Accumulation/Depth(median,expected)/Uncertainty
  * renderers + the depth-variance sum at models/activenerfacto/activenerfacto_model.py:94-112

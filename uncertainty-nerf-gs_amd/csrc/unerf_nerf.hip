@@ -3787,6 +3787,367 @@ extern "C" int unerf_laplace_ggn_diag(const float* origins, const float* directi
     return unerf_check_launch("laplace_ggn_diag");
 }
 
+// --------------------------------------------------------------------------------------
+// 5e. Per-ray camera-pose gradient of a nerfacto frame (nerfuncertainty/scripts/estimate_gradient_pose_6dof.py:58-216:
+// one torch.autograd.grad(pred_rgb.mean(-1), c2w) per pixel).  s = channel mean of the eval-mode rgb of one ray.  The
+// sample bins are held fixed (upstream's PDFSampler detaches them), so the pose reaches s only through the sample
+// positions x_i = o + d t_i and the SH encoding of d, and the backward pass needs no stored activations: the adjoint of
+// a Linear layer is its transposed weights, the adjoint of a ReLU its sign mask (one bit per unit).
+// One wave per ray (four rays per block), one lane per sample, everything in fp32:
+//   forward   grid lookup -> trunk -> colour head (activations in LDS as [unit][lane], weights through scalar loads;
+//             the arithmetic of field_kernel), compositing with wave scans
+//   adjoints  ds/dpred_c = live_c / 3 (live: the clamp passes 0 <= pred <= 1, as laplace_ggn_kernel);
+//             drgb_ic = ds/dpred_c (w_i + [i = S-1, last_sample] T_end);
+//             dsigma_i = sum_c ds/dpred_c delta_i [(1 - alpha_i) T_i (c_ic - bg_c) - sum_{j>i} w_j c_jc + bg_c sum_{j>i} w_j]
+//   backward  sigmoid, W3^T, mask, W2^T, mask, W1^T -> (dSH16 | dgeo15); trunk adjoint (dsigma sigma, dgeo, 0 for beta),
+//             Wt1^T, mask, Wt0^T -> dfeat[32]; the exact derivative of the trilinear blend at every level (the corner
+//             rows are fetched again) x level scale -> d(normalised position); / 4 and the SceneContraction(inf) Jacobian
+//             (or / box length) -> dx_i;  g_o = sum_i dx_i,  g_d = sum_i t_i dx_i + the SH term
+// The two sums over the ray are DPP reductions in a fixed order: two calls return the same bits.
+// --------------------------------------------------------------------------------------
+struct PoseGradArgs {
+    const float* origins;
+    const float* dirs;
+    const float* sbins;
+    int64_t R;
+    int S;
+    float s_near, s_far;
+    int lin;
+    unerf_field_params p;
+    unerf_norm_box box;
+    int bg_mode;
+    float bg[3];
+    int pose;          // 1: rinv holds R^-1 and out_grad is [R,12] = ds/dc2w; 0: out_grad is [R,6] = (ds/do, ds/dd)
+    float rinv[9];
+    float* out_grad;
+    float* out_rgb;    // may be NULL
+};
+
+// The weights are read through the CONSTANT address space: a uniform load from it is a scalar load (s_load_dwordx16 into
+// SGPRs, which the multiply-adds take as their scalar operand), whereas the same load through a global pointer becomes a
+// uniform-address VECTOR load in any kernel that also stores to global memory -- a VGPR per weight, 400 VGPRs here.  The
+// weights are written before the launch and never by it, which is all the scalar cache asks for.
+typedef const float __attribute__((address_space(4)))* pg_cfp;
+__device__ __forceinline__ pg_cfp pg_const(const float* p) { return (pg_cfp)(uintptr_t)p; }
+// acc[o] = b[o] + sum_i act[i] Wt[i][o], sequential over i (dense_lds's arithmetic)
+template <int IN, int OUT>
+__device__ __forceinline__ void pg_dense(pg_cfp Wt, pg_cfp b, const float* act, int lane, float (&acc)[OUT]) {
+#pragma unroll
+    for (int o = 0; o < OUT; ++o) acc[o] = b[o];
+#pragma unroll 2
+    for (int i = 0; i < IN; ++i) {
+        const float x = act[i * 64 + lane];
+#pragma unroll
+        for (int o = 0; o < OUT; ++o) acc[o] = fmaf(x, Wt[i * OUT + o], acc[o]);
+    }
+}
+// adjoint of that layer: row i of the LDS panel <- sum_o d[o] Wt[i][o], four partial sums combined in a fixed order
+template <int IN, int OUT>
+__device__ __forceinline__ void pg_dense_bwd(pg_cfp Wt, const float (&d)[OUT], float* act, int lane) {
+#pragma unroll 2
+    for (int i = 0; i < IN; ++i) {
+        float s[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int o = 0; o < OUT; ++o) s[o & 3] = fmaf(d[o], Wt[i * OUT + o], s[o & 3]);
+        act[i * 64 + lane] = (s[0] + s[1]) + (s[2] + s[3]);
+    }
+}
+__device__ __forceinline__ void relu_mask64(const float (&v)[64], uint32_t (&m)[2]) {
+    m[0] = m[1] = 0u;
+#pragma unroll
+    for (int o = 0; o < 64; ++o) m[o >> 5] |= (v[o] > 0.f) ? (1u << (o & 31)) : 0u;
+}
+__device__ __forceinline__ void load_masked64(const float* act, int lane, const uint32_t (&m)[2], float (&d)[64]) {
+#pragma unroll
+    for (int o = 0; o < 64; ++o) d[o] = ((m[o >> 5] >> (o & 31)) & 1u) ? act[o * 64 + lane] : 0.f;
+}
+
+// the 8 corner rows of one level as fp32 pairs.  GRID 0: torch layout (corner order and offsets of unerf_hash_corners);
+// 1 / 2: tcnn layout (unerf_tcnn_corners), fp32 rows / half2 rows widened on read.  -> interpolation weights (wx, wy, wz)
+template <int GRID>
+__device__ __forceinline__ void pg_level_corners(const PoseGradArgs& a, int l, uint32_t mask, float px, float py, float pz,
+                                                 float2 (&f)[8], float& wx, float& wy, float& wz, float& scale) {
+    if constexpr (GRID == 0) {
+        const float2* lvl = reinterpret_cast<const float2*>(a.p.table) + ((size_t)l << a.p.log2T);
+        scale = a.p.scalings[l];
+        uint32_t off[8];
+        unerf_hash_corners<false, false>(px, py, pz, scale, mask, off, wx, wy, wz);
+        unerf_fetch_corners(lvl, off, f);
+    } else {
+        const unerf_tcnn_level lv = a.p.tcnn_levels[l];
+        scale = lv.scale;
+        uint32_t rows[8];
+        unerf_tcnn_corners(lv, px, py, pz, rows, wx, wy, wz);
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            if constexpr (GRID == 1) f[k] = reinterpret_cast<const float2*>(a.p.table)[rows[k]];
+            else f[k] = unerf_h2_to_float2(reinterpret_cast<const uint32_t*>(a.p.table)[rows[k]]);
+        }
+    }
+}
+// d(blend of the scalar corner values v) / d(wx, wy, wz): the blend is linear in the rows, so the adjoint-weighted sum of the
+// two features is blended once
+template <int GRID>
+__device__ __forceinline__ void pg_blend_grad(const float (&v)[8], float wx, float wy, float wz, float& dx, float& dy, float& dz) {
+    const float mx = 1.f - wx, my = 1.f - wy, mz = 1.f - wz;
+    if constexpr (GRID == 0) {   // f03, f12, f56, f47 -> y -> z (unerf_blend8); the first of each pair takes the offset itself
+        const float v03 = v[0] * wx + v[3] * mx, v12 = v[1] * wx + v[2] * mx, v56 = v[5] * wx + v[6] * mx, v47 = v[4] * wx + v[7] * mx;
+        dx = wz * (wy * (v[0] - v[3]) + my * (v[1] - v[2])) + mz * (wy * (v[4] - v[7]) + my * (v[5] - v[6]));
+        dy = wz * (v03 - v12) + mz * (v47 - v56);
+        dz = (v03 * wy + v12 * my) - (v47 * wy + v56 * my);
+    } else {                     // corner k steps +1 along dim d where bit d of k is set (unerf_tcnn_blend)
+        const float x0 = v[0] * mx + v[1] * wx, x1 = v[2] * mx + v[3] * wx, x2 = v[4] * mx + v[5] * wx, x3 = v[6] * mx + v[7] * wx;
+        dx = mz * (my * (v[1] - v[0]) + wy * (v[3] - v[2])) + wz * (my * (v[5] - v[4]) + wy * (v[7] - v[6]));
+        dy = mz * (x1 - x0) + wz * (x3 - x2);
+        dz = (x2 * my + x3 * wy) - (x0 * my + x1 * wy);
+    }
+}
+
+template <int OUT1, int GRID>
+__global__ __launch_bounds__(256, 2) void pose_grad_kernel(PoseGradArgs a) {   // two waves per SIMD: two 64-KiB blocks per CU
+    extern __shared__ float lds[];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    float* A = lds + wv * (64 * 64);   // this wave's panel [64 units][64 lanes]; a lane reads only its own column
+    // one ray per wave, no loop over rays: a block's four panels fill its 64 KiB of LDS and two blocks share a CU
+    const int64_t r = (int64_t)blockIdx.x * 4 + wv;
+    if (r >= a.R) return;   // wave-uniform
+    const int S = a.S;
+    const bool in = lane < S;
+    const int i = in ? lane : S - 1;
+    const uint32_t mask = GRID == 0 ? (1u << a.p.log2T) - 1u : 0u;
+    {
+        // ---- sample position, normalisation ----
+        const float* sb = a.sbins + r * (S + 1);
+        const float e0 = unerf_s2e(sb[i], a.s_near, a.s_far, a.lin), e1 = unerf_s2e(sb[i + 1], a.s_near, a.s_far, a.lin);
+        const float delta = e1 - e0, t2 = e0 + e1;
+        const float ox = a.origins[r * 3 + 0], oy = a.origins[r * 3 + 1], oz = a.origins[r * 3 + 2];
+        const float dxr = a.dirs[r * 3 + 0], dyr = a.dirs[r * 3 + 1], dzr = a.dirs[r * 3 + 2];
+        const float x0 = ox + dxr * t2 / 2.f, y0 = oy + dyr * t2 / 2.f, z0 = oz + dzr * t2 / 2.f;
+        float px = x0, py = y0, pz = z0;
+        const float sel = unerf_normalize_position(px, py, pz, a.box);
+
+        // ---- forward: grid -> trunk -> head (field_kernel's arithmetic) ----
+#pragma unroll 2
+        for (int l = 0; l < 16; ++l) {
+            float2 f[8];
+            float wx, wy, wz, scale;
+            pg_level_corners<GRID>(a, l, mask, px, py, pz, f, wx, wy, wz, scale);
+            const float2 e = GRID == 0 ? unerf_blend8(f, wx, wy, wz) : unerf_tcnn_blend(f, wx, wy, wz);
+            A[(2 * l) * 64 + lane] = e.x;
+            A[(2 * l + 1) * 64 + lane] = e.y;
+        }
+        float acc[64];
+        uint32_t m0[2], m1[2], m2[2];
+        pg_dense<32, 64>(pg_const(a.p.w0t), pg_const(a.p.b0), A, lane, acc);
+        relu_mask64(acc, m0);
+        store_act<64>(A, lane, acc, 0, true);
+        float o1[OUT1];
+        pg_dense<64, OUT1>(pg_const(a.p.w1t), pg_const(a.p.b1), A, lane, o1);
+        const float sig = a.p.average_init_density * expf(o1[0]) * sel;
+        // SH inputs: (d + 1) / 2, mapped back to [-1, 1] by the tcnn encoding (sh_remap); du/dd = 1/2 or 1
+        float ux = (dxr + 1.f) / 2.f, uy = (dyr + 1.f) / 2.f, uz = (dzr + 1.f) / 2.f;
+        if (a.p.sh_remap) {
+            ux = ux * 2.f - 1.f;
+            uy = uy * 2.f - 1.f;
+            uz = uz * 2.f - 1.f;
+        }
+        {
+            float sh[16];
+            unerf_sh16(ux, uy, uz, sh);
+            store_act<16>(A, lane, sh, 0, false);
+        }
+#pragma unroll
+        for (int g = 0; g < 15; ++g) A[(16 + g) * 64 + lane] = o1[1 + g];
+        pg_dense<31, 64>(pg_const(a.p.h0t), pg_const(a.p.hb0), A, lane, acc);
+        relu_mask64(acc, m1);
+        store_act<64>(A, lane, acc, 0, true);
+        pg_dense<64, 64>(pg_const(a.p.h1t), pg_const(a.p.hb1), A, lane, acc);
+        relu_mask64(acc, m2);
+        store_act<64>(A, lane, acc, 0, true);
+        float c[3];
+        pg_dense<64, 3>(pg_const(a.p.h2t), pg_const(a.p.hb2), A, lane, c);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) c[k] = unerf_nan_to_num(unerf_sigmoid(c[k]));
+
+        // ---- compositing and its adjoints (laplace_ggn_kernel's scans) ----
+        const float dd = in ? delta * sig : 0.f;
+        const float em = expf(-dd);
+        const float T = expf(-group_excl_scan<64>(dd, lane));
+        const float w = in ? unerf_nan_to_num((1.f - em) * T) : 0.f;
+        const float Tf = 1.f - group_sum<64>(w);
+        const bool last_bg = a.bg_mode == UNERF_BG_LAST_SAMPLE;
+        // sum_{j>i} x_j as a scan over the reversed wave, NOT total - prefix: behind an opaque sample every term of dsigma is
+        // of the size of the transmittance there, and the rounding of a difference of O(1) sums (2^-24), multiplied by
+        // delta sigma of a dense sample (1e3 and more), would be the whole error of the gradient
+        const int rl = 63 - lane;
+        const float sw = __shfl(group_excl_scan<64>(__shfl(w, rl, 64), lane), rl, 64);
+        float dsig = 0.f, dc[3], pred[3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const float bg = last_bg ? __shfl(c[k], S - 1, 64) : a.bg[k];
+            const float wc = w * c[k];
+            const float swc = __shfl(group_excl_scan<64>(__shfl(wc, rl, 64), lane), rl, 64);
+            pred[k] = group_sum<64>(wc) + Tf * bg;
+            const float live = (pred[k] >= 0.f && pred[k] <= 1.f && in) ? 1.f / 3.f : 0.f;
+            // d pred / d(delta_i sigma_i) of pred = sum_j w_j c_j + bg (1 - sum_j w_j), w_i = (1 - em_i) T_i
+            dsig += live * delta * (em * T * (c[k] - bg) - swc + bg * sw);
+            const float wt = w + ((last_bg && lane == S - 1) ? Tf : 0.f);
+            dc[k] = live * wt * c[k] * (1.f - c[k]);   // through the sigmoid
+        }
+
+        // ---- backward: colour head ----
+        float d[64];
+        const pg_cfp h2t = pg_const(a.p.h2t);
+#pragma unroll
+        for (int o = 0; o < 64; ++o) {
+            const float v = fmaf(dc[2], h2t[o * 3 + 2], fmaf(dc[1], h2t[o * 3 + 1], dc[0] * h2t[o * 3 + 0]));
+            d[o] = ((m2[o >> 5] >> (o & 31)) & 1u) ? v : 0.f;
+        }
+        pg_dense_bwd<64, 64>(pg_const(a.p.h1t), d, A, lane);
+        load_masked64(A, lane, m1, d);
+        pg_dense_bwd<31, 64>(pg_const(a.p.h0t), d, A, lane);   // rows 0..15: dSH, 16..30: dgeo
+        float gdx, gdy, gdz;   // the SH term of ds/dd
+        {
+            float q[16];
+#pragma unroll
+            for (int j = 0; j < 16; ++j) q[j] = A[j * 64 + lane];
+            const float x = ux, y = uy, z = uz, xx = x * x, yy = y * y, zz = z * z;
+            const float c1 = 0.4886025119029199f, c2 = 1.0925484305920792f, c6 = 0.9461746957575601f, c8 = 0.5462742152960396f,
+                        c9 = 0.5900435899266435f, c10 = 2.890611442640554f, c11 = 0.4570457994644658f, c12 = 0.3731763325901154f,
+                        c14 = 1.445305721320277f;
+            const float z5 = 5.f * zz - 1.f, d3 = 3.f * (xx - yy);
+            gdx = q[3] * c1 + q[4] * (c2 * y) + q[7] * (c2 * z) + q[8] * (2.f * c8 * x) + q[9] * (6.f * c9 * x * y) + q[10] * (c10 * y * z) +
+                  q[13] * (c11 * z5) + q[14] * (2.f * c14 * x * z) + q[15] * (c9 * d3);
+            gdy = q[1] * c1 + q[4] * (c2 * x) + q[5] * (c2 * z) - q[8] * (2.f * c8 * y) + q[9] * (c9 * d3) + q[10] * (c10 * x * z) +
+                  q[11] * (c11 * z5) - q[14] * (2.f * c14 * y * z) - q[15] * (6.f * c9 * x * y);
+            gdz = q[2] * c1 + q[5] * (c2 * y) + q[6] * (2.f * c6 * z) + q[7] * (c2 * x) + q[10] * (c10 * x * y) + q[11] * (10.f * c11 * y * z) +
+                  q[12] * (c12 * (15.f * zz - 3.f)) + q[13] * (10.f * c11 * x * z) + q[14] * (c14 * (xx - yy));
+            const float du = a.p.sh_remap ? 1.f : 0.5f;
+            gdx *= du;
+            gdy *= du;
+            gdz *= du;
+        }
+        // ---- backward: trunk ----
+        float d1[OUT1];
+        d1[0] = dsig * sig;   // sigma = aid exp(pre) selector: dsigma/dpre = sigma (zero where the selector is)
+#pragma unroll
+        for (int g = 0; g < 15; ++g) d1[1 + g] = A[(16 + g) * 64 + lane];
+        if constexpr (OUT1 == 17) d1[16] = 0.f;   // the learned-variance logit does not reach the colour
+        pg_dense_bwd<64, OUT1>(pg_const(a.p.w1t), d1, A, lane);
+        load_masked64(A, lane, m0, d);
+        pg_dense_bwd<32, 64>(pg_const(a.p.w0t), d, A, lane);   // rows 2l, 2l+1: adjoint of level l's features
+
+        // ---- backward: grid -> normalised position ----
+        float gpx = 0.f, gpy = 0.f, gpz = 0.f;
+#pragma unroll 2
+        for (int l = 0; l < 16; ++l) {
+            float2 f[8];
+            float wx, wy, wz, scale;
+            pg_level_corners<GRID>(a, l, mask, px, py, pz, f, wx, wy, wz, scale);
+            const float g0 = A[(2 * l) * 64 + lane], g1 = A[(2 * l + 1) * 64 + lane];
+            float v[8];
+#pragma unroll
+            for (int k = 0; k < 8; ++k) v[k] = fmaf(g1, f[k].y, g0 * f[k].x);
+            float bx, by, bz;
+            pg_blend_grad<GRID>(v, wx, wy, wz, bx, by, bz);
+            gpx = fmaf(scale, bx, gpx);
+            gpy = fmaf(scale, by, gpy);
+            gpz = fmaf(scale, bz, gpz);
+        }
+        // ---- normalised position -> world position ----
+        float gx = gpx * sel, gy = gpy * sel, gz = gpz * sel;
+        if (a.box.use_aabb) {   // uniform
+            gx /= a.box.len[0];
+            gy /= a.box.len[1];
+            gz /= a.box.len[2];
+        } else {
+            gx *= 0.25f;
+            gy *= 0.25f;
+            gz *= 0.25f;
+            const float ax = fabsf(x0), ay = fabsf(y0), az = fabsf(z0);
+            const float m = fmaxf(fmaxf(ax, ay), az);
+            if (!(m < 1.f)) {
+                // y = (2 - 1/m) x / m, m = |x_k|: dy_j/dx_j = (2 - 1/m)/m (j != k), dy_k/dx_k = 1/m^2,
+                // dy_j/dx_k = x_j sign(x_k) 2 (1 - m) / m^3
+                const float inv = 1.f / m, diag = (2.f - inv) * inv, cross = 2.f * (1.f - m) * inv * inv * inv;
+                const int k = (ax >= ay && ax >= az) ? 0 : (ay >= az ? 1 : 2);
+                const float dot = (k == 0 ? 0.f : gx * x0) + (k == 1 ? 0.f : gy * y0) + (k == 2 ? 0.f : gz * z0);
+                const float xk = k == 0 ? x0 : (k == 1 ? y0 : z0), gk = k == 0 ? gx : (k == 1 ? gy : gz);
+                const float along = gk * inv * inv + cross * (xk < 0.f ? -dot : dot);
+                gx = k == 0 ? along : gx * diag;
+                gy = k == 1 ? along : gy * diag;
+                gz = k == 2 ? along : gz * diag;
+            }
+        }
+        if (!in) gx = gy = gz = gdx = gdy = gdz = 0.f;
+        const float th = t2 / 2.f;
+        const float go0 = group_sum<64>(gx), go1 = group_sum<64>(gy), go2 = group_sum<64>(gz);
+        const float gd0 = group_sum<64>(fmaf(th, gx, gdx)), gd1 = group_sum<64>(fmaf(th, gy, gdy)), gd2 = group_sum<64>(fmaf(th, gz, gdz));
+
+        // ---- epilogue: every store is a vector store of a lane-selected value ----
+        if (a.pose) {
+            // d = normalize(R dir_cam): ds/dc2w[a][b] = P[a] (R^-1 d)[b] with P = (I - d d^T) g_d; ds/dc2w[:, 3] = g_o
+            const float gdd = gd0 * dxr + gd1 * dyr + gd2 * dzr;
+            const float P[3] = {gd0 - dxr * gdd, gd1 - dyr * gdd, gd2 - dzr * gdd};
+            const float go[3] = {go0, go1, go2};
+            const int row = lane >> 2, col = lane & 3;
+            const float Pa = row == 0 ? P[0] : (row == 1 ? P[1] : P[2]);
+            const float ga = row == 0 ? go[0] : (row == 1 ? go[1] : go[2]);
+            const int cb = col < 3 ? col : 0;
+            const float q = a.rinv[cb * 3 + 0] * dxr + a.rinv[cb * 3 + 1] * dyr + a.rinv[cb * 3 + 2] * dzr;
+            if (lane < 12) a.out_grad[r * 12 + lane] = col == 3 ? ga : Pa * q;
+        } else {
+            const float v6 = lane == 0 ? go0 : lane == 1 ? go1 : lane == 2 ? go2 : lane == 3 ? gd0 : lane == 4 ? gd1 : gd2;
+            if (lane < 6) a.out_grad[r * 6 + lane] = v6;
+        }
+        if (a.out_rgb && lane < 3) {
+            const float pv = lane == 0 ? pred[0] : (lane == 1 ? pred[1] : pred[2]);
+            a.out_rgb[r * 3 + lane] = fminf(fmaxf(pv, 0.f), 1.f);
+        }
+    }
+}
+
+extern "C" int unerf_pose_grad(const float* origins, const float* directions, const float* sbins, int64_t R, int S,
+                               float near_plane, float far_plane, int spacing, const unerf_field_params* p, int background,
+                               const float* background_rgb, const float* rot_inv, float* out_grad, float* out_rgb,
+                               void* stream) {
+    UNERF_REQUIRE(R >= 0 && S >= 1 && S <= 64, "pose_grad: S=%d outside [1,64]", S);
+    if (R == 0) return UNERF_OK;
+    UNERF_REQUIRE(origins && directions && sbins && p && out_grad, "pose_grad: null pointer");
+    UNERF_REQUIRE(p->mode == UNERF_FIELD_ACTIVE || p->mode == UNERF_FIELD_MCDROPOUT,
+                  "pose_grad: mode %d (a nerfacto / active-nerfacto field is needed: the Laplace field's sampled heads are "
+                  "not differentiated)", p->mode);
+    UNERF_REQUIRE(p->hidden == 0 && p->hidden_color == 0 && p->geo_dim == 0 && p->feat_per_level == 0 && p->L == 16,
+                  "pose_grad: nerfacto's widths only (hidden 64 / 64, geo 15, 2 features x 16 levels)");
+    UNERF_REQUIRE(p->out1 == (p->mode == UNERF_FIELD_ACTIVE ? 17 : 16), "pose_grad: trunk output %d does not fit mode %d", p->out1,
+                  p->mode);
+    UNERF_REQUIRE(p->table && p->w0t && p->b0 && p->w1t && p->b1 && p->h0t && p->hb0 && p->h1t && p->hb1 && p->h2t && p->hb2 &&
+                      (p->scalings || p->tcnn_levels),
+                  "pose_grad: null field pointer");
+    UNERF_REQUIRE(p->tcnn_levels || (p->log2T >= 1 && p->log2T <= 24), "pose_grad: bad log2T=%d", p->log2T);
+    UNERF_REQUIRE(p->tcnn_levels || !p->grid_half, "pose_grad: grid_half needs a tcnn-layout grid");
+    UNERF_REQUIRE(near_plane >= 0.f, "pose_grad: near_plane=%g (spacing-domain bins only)", (double)near_plane);
+    PoseGradArgs g;
+    g.origins = origins; g.dirs = directions; g.sbins = sbins; g.R = R; g.S = S;
+    UNERF_REQUIRE_SPACING(spacing); g.lin = spacing; g.s_near = unerf_spacing_of(near_plane, spacing); g.s_far = unerf_spacing_of(far_plane, spacing);
+    g.p = *p;
+    g.box = make_norm_box(p->use_aabb, p->aabb);
+    if (int rc = unerf_set_background(g, background, background_rgb, "pose_grad")) return rc;
+    g.pose = rot_inv ? 1 : 0;
+    for (int k = 0; k < 9; ++k) g.rinv[k] = rot_inv ? rot_inv[k] : 0.f;
+    g.out_grad = out_grad; g.out_rgb = out_rgb;
+    UNERF_REQUIRE(R < (1ll << 32), "pose_grad: R=%lld rays in one launch, split the batch", (long long)R);
+    const int64_t blocks = (R + 3) / 4;   // a wave per ray; 64 KiB of LDS per block: two blocks per CU
+    constexpr size_t lds_bytes = 4 * 64 * 64 * sizeof(float);
+    with_int3(tcnn_arg(g.p), [&](auto tc) {
+        with_bool(g.p.out1 == 17, [&](auto wide) {
+            hipLaunchKernelGGL((pose_grad_kernel<decltype(wide)::value ? 17 : 16, decltype(tc)::value>), dim3((unsigned)blocks), dim3(256),
+                               lds_bytes, (hipStream_t)stream, g);
+        });
+    });
+    return unerf_check_launch("pose_grad");
+}
+
 // ======================================================================================
 // 6. per-ray groups of 16 lanes x SPL samples: get_weights, composite, laplace depth draws
 // ======================================================================================

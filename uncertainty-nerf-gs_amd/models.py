@@ -480,6 +480,22 @@ class _NerfactoBase(nn.Module, _ImageMetrics):
         return render.render_camera(scene, c2w, rays_per_launch=self.rays_per_launch, obb=obb,
                                     **cam, **self._render_kwargs())
 
+    # one sentence saying why this model has no pose gradient (None: it has one)
+    _no_pose_gradient: Optional[str] = "this model does not define the rendered colour as one deterministic field evaluation."
+
+    @torch.no_grad()
+    def get_pose_gradients_for_camera(self, camera, rays_per_launch: Optional[int] = None, want_rgb: bool = False):
+        """d mean_c(rgb[y, x]) / d camera_to_worlds for every pixel of one camera -> [H,W,3,4] float32 on the device (with
+        want_rgb also the colour the gradient kernel composited, [H,W,3]): what the reference's
+        estimate_gradient_pose_6dof.py:128-139 collects with one autograd backward per pixel, from
+        render.pose_gradient_camera (sample bins held fixed, fp32 arithmetic whatever precision the frames render in)."""
+        if self._no_pose_gradient is not None:
+            raise NotImplementedError(f"{type(self).__name__}.get_pose_gradients_for_camera: {self._no_pose_gradient}")
+        c2w, cam = _camera_args(camera)
+        scene = self.device_scene()
+        return render.pose_gradient_camera(scene, c2w, rays_per_launch=rays_per_launch or self.rays_per_launch,
+                                           want_rgb=want_rgb, **cam)
+
     def _begin_render_views(self, scene: NerfSceneDev, n_views: int) -> Tuple[bool, Optional[List[int]]]:
         """once per get_outputs_for_cameras call -> (render the batch through render.render_cameras, mask seed per view |
         None); False: the model renders its cameras one by one through get_outputs_for_camera"""
@@ -595,6 +611,7 @@ class NerfactoModel(_NerfactoBase):
     """[UPSTREAM nerfstudio 1.1.0 NerfactoModel] plain nerfacto: rgb, accumulation, depth, expected_depth, prop_depth_i.
     The member model of the reference's NeRF ensembles (ensemble_utils.py:149-150)."""
     config: PlainNerfactoModelConfig
+    _no_pose_gradient = None
 
     def _make_field(self):
         return F.NerfactoField(average_init_density=self.config.average_init_density, **self._field_kwargs())
@@ -602,6 +619,7 @@ class NerfactoModel(_NerfactoBase):
 
 class ActiveNerfactoModel(_NerfactoBase):
     config: ActiveNerfactoModelConfig
+    _no_pose_gradient = None
 
     def _make_field(self):
         return F.ActiveNerfactoField(beta_min=self.config.beta_min, **self._field_kwargs())
@@ -682,6 +700,8 @@ class NerfactoMCDropoutModel(_NerfactoBase):
     mask_generator: Optional[torch.Generator] = None     # "torch": None = torch's global CPU generator
     mask_budget_bytes: int = 1 << 34                     # "torch": a frame whose packed masks need more raises (1080p, K = 8: 12.7 GB)
     _frame_masks: Optional[ops.KeepMasks] = None
+    _no_pose_gradient = ("its colour is the mean of K passes under fresh dropout masks, and the gradient kernel "
+                         "differentiates one deterministic pass.")
 
     def _begin_render(self, scene: NerfSceneDev, total_rays: int = 0, chunk_rays: int = 0) -> None:
         if self.dropout_masks not in ("counter", "torch"):
@@ -740,6 +760,8 @@ class NerfactoLaplaceModel(_NerfactoBase):
     # independent sets of n_samples draws, so its Monte-Carlo error is independent from chunk to chunk.  "camera": one
     # set for the whole frame (no visible seams between chunks; the field kernel keeps its 8x4 pixel-patch tiles).
     resample: str = "chunk"
+    _no_pose_gradient = ("its colour is the mean over sampled last layers, which the gradient kernel (one deterministic "
+                         "nerfacto head) does not evaluate.")
 
     def _make_field(self):
         return F.NerfactoLaplaceField(density_activation=self.config.density_activation, **self._field_kwargs())

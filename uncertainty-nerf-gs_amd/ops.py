@@ -1256,6 +1256,33 @@ def laplace_ggn_diag(origins, directions, sbins, field: FieldDev, density_mean: 
                                                                    _p(ggn_rgb), _stream()))
 
 
+def pose_grad(origins, directions, sbins, field: FieldDev, near: float, far: float, rot_inv: Optional[torch.Tensor] = None,
+              spacing: int = 0, background=None, want_rgb: bool = False):
+    """Per-ray gradient of s = mean over channels of the eval-mode rgb, with the sample bins held fixed
+    (unerf_pose_grad; the reference's estimate_gradient_pose_6dof.py:128-139 is one autograd backward per pixel).
+    rot_inv None -> [R,6] = (ds/do, ds/dd); rot_inv [3,3] = inverse of c2w[:3,:3] -> [R,12] = ds/dc2w, row-major 3x4.
+    want_rgb: also the colour the kernel composited, [R,3].  -> grad | (grad, rgb)"""
+    lib = _l.load()
+    if field.mode not in (_l.FIELD_ACTIVE, _l.FIELD_MCDROPOUT):
+        raise _l.UnerfError("pose_grad needs a nerfacto / active-nerfacto field (the Laplace field's sampled heads are not differentiated)")
+    R, S = sbins.shape[0], sbins.shape[1] - 1
+    dev = origins.device
+    cs = field.cstruct()
+    ri = None
+    if rot_inv is not None:
+        vals = [float(v) for v in torch.as_tensor(rot_inv).detach().cpu().to(torch.float32).reshape(-1)]
+        if len(vals) != 9:
+            raise _l.UnerfError(f"pose_grad: rot_inv must have 9 entries, got {len(vals)}")
+        ri = (C.c_float * 9)(*vals)
+    grad = torch.empty(R, 6 if ri is None else 12, device=dev, dtype=torch.float32)
+    rgb = torch.empty(R, 3, device=dev, dtype=torch.float32) if want_rgb else None
+    bg_mode, bg_rgb = _background(background)
+    with _ctx(dev):
+        _run("pose_grad", lambda: lib.unerf_pose_grad(_p(origins), _p(directions), _p(sbins), R, S, near, far, spacing, C.byref(cs),
+                                                      bg_mode, bg_rgb, ri, _p(grad), _p(rgb), _stream()))
+    return (grad, rgb) if want_rgb else grad
+
+
 def background_of(name) -> Tuple[int, Optional[Tuple[float, float, float]]]:
     """config.background_color -> (UNERF_BG_* mode, constant colour | None).  [UPSTREAM nerfstudio 1.1.0 RGBRenderer:
     "last_sample" blends the last sample's colour, "random" returns the composited colour unblended at eval, "white" /

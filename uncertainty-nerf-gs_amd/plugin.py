@@ -173,6 +173,15 @@ def _build() -> Dict[str, Any]:
             kw = {} if max_views is None else {"max_views": max_views}
             return self._mirror.get_outputs_for_cameras(cameras, obb_box=obb_box, **kw)
 
+        @torch.no_grad()
+        def get_pose_gradients_for_camera(self, camera, **kw):
+            """d mean_c(rgb) / d camera_to_worlds per pixel, [H,W,3,4] (estimate_gradient_pose_6dof.py:128-139); the
+            mc-dropout, Laplace and splat mirrors raise NotImplementedError"""
+            fn = getattr(self._mirror, "get_pose_gradients_for_camera", None)
+            if fn is None:
+                raise NotImplementedError(f"{type(self._mirror).__name__} has no pose gradient: it is not a nerfacto ray model.")
+            return fn(camera, **kw)
+
         def load_state_dict(self, state_dict, strict: bool = False, **kw):  # type: ignore[override]
             return self._mirror.load_state_dict(state_dict, strict=strict, **kw)
 

@@ -1,0 +1,112 @@
+"""Pose-sensitivity export: the counterpart of the reference's nerfuncertainty/scripts/estimate_gradient_pose_6dof.py.
+
+The script perturbs one training camera along one of six pose parameters, renders it in 256-ray chunks and calls
+torch.autograd.grad(pred_rgb_j.mean(-1), c2w) once per pixel (:153-190).  Here the per-pixel gradients of a frame come from
+one kernel launch per group of rays (models.*.get_pose_gradients_for_camera -> render.pose_gradient_camera ->
+unerf_pose_grad), and the files the script leaves behind are written with its names, shapes and dtypes.
+
+What differs from the reference: it differentiates whatever arithmetic its checkpoint runs in (half precision for a tcnn
+field); this build differentiates the fp32 field.  Its ground-truth and rendered images are JPEG (mediapy); no JPEG encoder
+is assumed here, the rendered image is a PNG."""
+from __future__ import annotations
+
+import copy
+from pathlib import Path
+from typing import Dict
+
+import numpy as np
+import torch
+
+POSE_PARAMS = ("tx", "ty", "tz", "angx", "angy", "angz")
+
+
+def exp_map_se3(tangent: torch.Tensor) -> torch.Tensor:
+    """[UPSTREAM-RECALL nerfstudio 1.1.0 cameras.lie_groups.exp_map_SE3, restated from memory] tangent [B,6] =
+    (v, w) -> [B,3,4] = (exp([w]x) | V v): the SE(3) exponential of the twist, with upstream's series for |w| < 1e-2
+    (cos ~ 8 / (4 + t^2) - 1, sin t / t ~ (cos + 1) / 2 in the rotation; Taylor terms in the translation)."""
+    lin = tangent[:, :3].reshape(-1, 3, 1)
+    ang = tangent[:, 3:].reshape(-1, 3, 1)
+    theta = torch.linalg.norm(ang, dim=1).unsqueeze(1)
+    theta2, theta3 = theta ** 2, theta ** 3
+    near_zero = theta < 1e-2
+    one = torch.ones(1, dtype=tangent.dtype, device=tangent.device)
+    theta_nz, theta2_nz, theta3_nz = (torch.where(near_zero, one, t) for t in (theta, theta2, theta3))
+    sine = theta.sin()
+    cosine = torch.where(near_zero, 8 / (4 + theta2) - 1, theta.cos())
+    sine_by_theta = torch.where(near_zero, 0.5 * cosine + 0.5, sine / theta_nz)
+    omc_by_theta2 = torch.where(near_zero, 0.5 * sine_by_theta, (1 - cosine) / theta2_nz)
+    ret = torch.zeros(tangent.shape[0], 3, 4, dtype=tangent.dtype, device=tangent.device)
+    ret[:, :3, :3] = omc_by_theta2 * ang @ ang.transpose(1, 2)
+    for a in range(3):
+        ret[:, a, a] += cosine.view(-1)
+    temp = sine_by_theta.view(-1, 1) * ang.view(-1, 3)
+    ret[:, 0, 1] -= temp[:, 2]
+    ret[:, 1, 0] += temp[:, 2]
+    ret[:, 0, 2] += temp[:, 1]
+    ret[:, 2, 0] -= temp[:, 1]
+    ret[:, 1, 2] -= temp[:, 0]
+    ret[:, 2, 1] += temp[:, 0]
+    sine_by_theta = torch.where(near_zero, 1 - theta2 / 6, sine_by_theta)
+    omc_by_theta2 = torch.where(near_zero, 0.5 - theta2 / 24, omc_by_theta2)
+    tms_by_theta3 = torch.where(near_zero, 1.0 / 6 - theta2 / 120, (theta - sine) / theta3_nz)
+    ret[:, :, 3:] = sine_by_theta * lin
+    ret[:, :, 3:] += omc_by_theta2 * torch.cross(ang, lin, dim=1)
+    ret[:, :, 3:] += tms_by_theta3 * (ang @ (ang.transpose(1, 2) @ lin))
+    return ret
+
+
+def pose_multiply(pose_a: torch.Tensor, pose_b: torch.Tensor) -> torch.Tensor:
+    """[UPSTREAM-RECALL nerfstudio 1.1.0 utils.poses.multiply] [...,3,4] x [...,3,4]: (R1 R2 | t1 + R1 t2)"""
+    R1, t1 = pose_a[..., :3, :3], pose_a[..., :3, 3:]
+    R2, t2 = pose_b[..., :3, :3], pose_b[..., :3, 3:]
+    return torch.cat([R1.matmul(R2), t1 + R1.matmul(t2)], dim=-1)
+
+
+def perturbed_pose(c2w: torch.Tensor, param: str, magnitude: float) -> torch.Tensor:
+    """estimate_gradient_pose_6dof.py:22-39, 118-124: c2w [3,4] times the SE(3) exponential of a twist that is
+    `magnitude` in one of tx | ty | tz | angx | angy | angz and zero elsewhere (the camera's own frame) -> [3,4] float32"""
+    if param not in POSE_PARAMS:
+        raise ValueError(f"shift_param={param!r}: expected one of {', '.join(POSE_PARAMS)}")
+    p = torch.zeros(1, 6)
+    p[0, POSE_PARAMS.index(param)] = float(magnitude)
+    c2w = torch.as_tensor(c2w).detach().cpu().to(torch.float32)
+    c2w = c2w[0] if c2w.dim() == 3 else c2w
+    return pose_multiply(c2w[:3, :4], exp_map_se3(p)[0])
+
+
+def export_pose_gradients(model, camera, image_idx: int, output_dir, shift_param: str = "tz", shift_magnitude: float = 0.0,
+                          seed: int = 42) -> Dict[str, Path]:
+    """One image of estimate_gradient_pose_6dof.py:109-216 -> the files it writes under output_dir / f"image_{image_idx}":
+      c2w_img{idx}.npy          [3,4] float32    the camera's own pose
+      c2w_perturbed.npy         [3,4] float32    perturbed_pose(c2w, shift_param, shift_magnitude)
+      camera_intrinsics.npy     [3,3] float32    K
+      pred_rgb_perturbed.npy    [H,W,3] float32  the perturbed camera's render (the colour the gradient kernel composited)
+      c2w_grads_perturbed.npy   [H,W,3,4] float64  d mean_c(rgb[y,x]) / d c2w_perturbed
+      image{idx:05d}_perturbed.png               the render as an 8-bit image (the reference writes a JPEG)
+    model: anything with get_pose_gradients_for_camera(camera, want_rgb=True) (models.NerfactoModel / ActiveNerfactoModel,
+    the plugin's models).  camera: one camera (camera_to_worlds, fx, fy, cx, cy, height, width, ...); it is not modified.
+    seed: as the script, torch.manual_seed(seed) before the perturbation (which draws nothing).  -> {file stem: path}"""
+    from .eval import _write_png
+    from .models import _scalar
+    torch.manual_seed(seed)
+    out = Path(output_dir) / f"image_{int(image_idx)}"
+    out.mkdir(parents=True, exist_ok=True)
+    c2w = torch.as_tensor(camera.camera_to_worlds).detach().cpu().to(torch.float32)
+    c2w = (c2w[0] if c2w.dim() == 3 else c2w)[:3, :4]
+    c2w_p = perturbed_pose(c2w, shift_param, shift_magnitude)
+    cam = copy.copy(camera)
+    cam.camera_to_worlds = c2w_p
+    grads, rgb = model.get_pose_gradients_for_camera(cam, want_rgb=True)
+    rgb = rgb.detach().cpu().to(torch.float32).numpy()
+    K = np.array([[_scalar(camera.fx), 0.0, _scalar(camera.cx)], [0.0, _scalar(camera.fy), _scalar(camera.cy)], [0.0, 0.0, 1.0]],
+                 np.float32)
+    files = {"c2w": out / f"c2w_img{int(image_idx):d}.npy", "c2w_perturbed": out / "c2w_perturbed.npy",
+             "camera_intrinsics": out / "camera_intrinsics.npy", "pred_rgb_perturbed": out / "pred_rgb_perturbed.npy",
+             "c2w_grads_perturbed": out / "c2w_grads_perturbed.npy", "image": out / f"image{int(image_idx):05d}_perturbed.png"}
+    np.save(files["c2w"], c2w.numpy())
+    np.save(files["c2w_perturbed"], c2w_p.numpy())
+    np.save(files["camera_intrinsics"], K)
+    np.save(files["pred_rgb_perturbed"], rgb)
+    np.save(files["c2w_grads_perturbed"], grads.detach().cpu().numpy().astype(np.float64))
+    _write_png(files["image"], np.clip(np.rint(rgb * 255.0), 0, 255).astype(np.uint8))
+    return files

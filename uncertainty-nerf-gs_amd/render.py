@@ -366,6 +366,40 @@ def render_camera(scene: NerfSceneDev, c2w: torch.Tensor, fx: float, fy: float, 
         return {k: torch.cat(v).view(H, W, -1) for k, v in lists.items()}
 
 
+def pose_gradient_camera(scene: NerfSceneDev, c2w: torch.Tensor, fx: float, fy: float, cx: float, cy: float, H: int, W: int,
+                         rays_per_launch: int = 1 << 20, obb=None, distortion=None, camera_type: int = 1,
+                         want_rgb: bool = False):
+    """d mean_c(rgb[y, x]) / d c2w for every pixel of one camera -> [H,W,3,4] float32 on the device (with want_rgb:
+    also the colour unerf_pose_grad composited, [H,W,3]) -- the per-pixel autograd loop of the reference's
+    estimate_gradient_pose_6dof.py:128-139 as ray kernel -> proposal sampler -> one gradient launch per group of
+    rays_per_launch rays.  The sample bins are held fixed, as upstream's PDFSampler detaches them: the pose acts through
+    the ray origins (c2w[:, 3]) and the directions normalize(c2w[:3, :3] dir_cam) only.  ORTHOPHOTO cameras and `obb`
+    crops are refused: their origins / sampling planes depend on the pose themselves."""
+    _l.require_gpu()
+    if int(camera_type) == _l.CAMERA_ORTHOPHOTO:
+        raise _l.UnerfError("pose_gradient_camera: an ORTHOPHOTO camera's ray origins depend on the rotation; not differentiated")
+    if obb is not None:
+        raise _l.UnerfError("pose_gradient_camera: obb crops make the sampling planes depend on the pose; not differentiated")
+    total = H * W
+    dev = scene.device
+    c2w = c2w.detach().cpu().to(torch.float32)
+    rot_inv = torch.linalg.inv(c2w[:3, :3].double()).to(torch.float32)
+    rpl = max(1, int(rays_per_launch))
+    grads, rgbs = [], []
+    with torch.cuda.device(dev):
+        for start in range(0, total, rpl):
+            o, d, _ = ops.generate_rays(c2w, fx, fy, cx, cy, H, W, dev, start, min(rpl, total - start), distortion=distortion,
+                                        camera_type=camera_type)
+            sb, _ = sample_rays(scene, o, d, None, start, want_prop_depth=False, image_width=W, workspace=scene.workspace)
+            res = ops.pose_grad(o, d, sb, scene.field, scene.near, scene.far, rot_inv=rot_inv, spacing=scene.spacing,
+                                background=scene.background, want_rgb=want_rgb)
+            grads.append(res[0] if want_rgb else res)
+            if want_rgb:
+                rgbs.append(res[1])
+    g = torch.cat(grads).view(H, W, 3, 4)
+    return (g, torch.cat(rgbs).view(H, W, 3)) if want_rgb else g
+
+
 def plan_view_groups(n_views: int, rays_per_view: int, rays_per_launch: int = 1 << 20, chunk_rays: int = 1 << 15,
                      max_views: int = _l.NERF_MAX_VIEWS) -> Optional[List[Tuple[int, int]]]:
     """How render_cameras fills its launch groups with WHOLE views: [(first view, number of views), ...], or None when a
