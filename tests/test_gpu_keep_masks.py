@@ -44,7 +44,7 @@ def _unpack(bits: torch.Tensor, n: int) -> np.ndarray:
 def _close(got, ref, rtol, atol, what, max_bad_frac=0.0):
     got, ref = got.detach().cpu().double(), ref.detach().cpu().double()
     assert got.shape == ref.shape, f"{what}: shape {tuple(got.shape)} vs {tuple(ref.shape)}"
-    bad = (got - ref).abs() > (atol + rtol * ref.abs())
+    bad = ((got - ref).abs() > (atol + rtol * ref.abs())) | (torch.isnan(got) != torch.isnan(ref))      # a NaN on one side only is off (NaN > tol is False)
     frac = bad.double().mean().item()
     assert frac <= max_bad_frac, f"{what}: {frac:.3e} of elements off (worst |diff|={(got - ref).abs().max().item():.3e})"
 
@@ -295,7 +295,7 @@ def test_model_in_torch_mask_mode_matches_the_oracle_under_the_same_draws(dev):
 
     def img_close(key, atol, rtol, max_bad_frac=0.0):
         got, want = out[key].cpu().double(), ref[key].double()
-        frac = ((got - want).abs() > atol + rtol * want.abs()).double().mean().item()
+        frac = (((got - want).abs() > atol + rtol * want.abs()) | (torch.isnan(got) != torch.isnan(want))).double().mean().item()
         assert frac <= max_bad_frac, f"{key}: {frac:.3e} of pixels off, worst {(got - want).abs().max().item():.3e}"
 
     img_close("rgb", 5e-5, 0)

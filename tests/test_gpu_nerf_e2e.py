@@ -151,7 +151,7 @@ def _gates(name, out_rgb, out_std, ref_rgb, ref_std, out=None, ref=None, diag=No
 def _img_close(got, ref, atol, rtol, what, max_bad_frac=0.0):
     got, ref = got.cpu().double(), ref.double()
     assert got.shape == ref.shape, (what, got.shape, ref.shape)
-    bad = (got - ref).abs() > atol + rtol * ref.abs()
+    bad = ((got - ref).abs() > atol + rtol * ref.abs()) | (torch.isnan(got) != torch.isnan(ref))      # a NaN on one side only is off (NaN > tol is False)
     frac = bad.double().mean().item()
     assert frac <= max_bad_frac, f"{what}: {frac:.3e} of pixels off, worst {(got - ref).abs().max().item():.3e}"
 

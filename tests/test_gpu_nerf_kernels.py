@@ -27,7 +27,7 @@ def _rays(H=24, W=32, theta=0.3):
 def _close(got, ref, rtol, atol, what, max_bad_frac=0.0):
     got, ref = got.detach().cpu().double(), ref.detach().cpu().double()
     assert got.shape == ref.shape, f"{what}: shape {tuple(got.shape)} vs {tuple(ref.shape)}"
-    bad = (got - ref).abs() > (atol + rtol * ref.abs())
+    bad = ((got - ref).abs() > (atol + rtol * ref.abs())) | (torch.isnan(got) != torch.isnan(ref))      # a NaN on one side only is off (NaN > tol is False)
     frac = bad.double().mean().item()
     worst = (got - ref).abs().max().item()
     assert frac <= max_bad_frac, f"{what}: {frac:.3e} of elements off (worst |diff|={worst:.3e})"

@@ -29,7 +29,7 @@ def _rays(H=16, W=24, theta=0.8):
 
 def _close(got, ref, rtol, atol, what, max_bad_frac=0.0):
     got, ref = got.detach().cpu().double(), ref.detach().cpu().double()
-    bad = (got - ref).abs() > (atol + rtol * ref.abs())
+    bad = ((got - ref).abs() > (atol + rtol * ref.abs())) | (torch.isnan(got) != torch.isnan(ref))      # a NaN on one side only is off (NaN > tol is False)
     assert bad.double().mean().item() <= max_bad_frac, f"{what}: {bad.double().mean().item():.3e} off, worst {(got - ref).abs().max().item():.3e}"
 
 

@@ -4370,7 +4370,9 @@ __global__ __launch_bounds__(256) void composite_kernel_packed_views(CompArgs a,
 // K-pass form: one 16-lane group walks the B <= 16 passes of a ray, lane b keeps pass b's eight
 // outputs, and the per-pixel mean and unbiased variance over the passes (two-pass, like
 // torch.stack(...).mean(0) / .var(0), mcdropout_models.py:121-126) come out of two group reductions:
-// the [B,R,8] per-pass images never touch HBM.
+// the [B,R,8] per-pass images never touch HBM.  Both passes run on x_b - x_0 (pass 0's value, as the planes
+// kernel's shifted sums do): the mean of B equal values is then that value and their variance 0 exactly, where
+// sum(x) * (1 / B) rounds the mean off x and left a variance of a few ulp(x)^2.
 template <int SPL, bool RAGGED, bool PACKED, typename... VW>
 __device__ __forceinline__ void composite_moments_body(const CompArgs& a, float* __restrict__ mean_out,
                                                        float* __restrict__ var_out, const VW&... vw) {
@@ -4394,9 +4396,12 @@ __device__ __forceinline__ void composite_moments_body(const CompArgs& a, float*
     float m8[8], v8[8];
 #pragma unroll
     for (int c = 0; c < 8; ++c) {
-        m8[c] = group_sum<16>(mine[c]) * invB;
-        float d = (l16 < a.B) ? mine[c] - m8[c] : 0.f;
-        v8[c] = group_sum<16>(d * d) * invB1;
+        const float x0 = __shfl(mine[c], 0, 16);
+        const float d = (l16 < a.B) ? mine[c] - x0 : 0.f;
+        const float dm = group_sum<16>(d) * invB;
+        m8[c] = x0 + dm;
+        const float dev = (l16 < a.B) ? d - dm : 0.f;
+        v8[c] = group_sum<16>(dev * dev) * invB1;
     }
     if (ok && l16 == 0) {
         float4* mo = reinterpret_cast<float4*>(mean_out + r * 8);
@@ -4620,15 +4625,17 @@ __global__ __launch_bounds__(256) void composite_sm_kernel(CompSmArgs a) {
     for (int c = 0; c < 8; ++c) x0[c] = sd[c] = sd2[c] = 0.f;
     for (int b0 = 0; b0 < a.B; b0 += CSM_G) {
         const int nb = min(CSM_G, a.B - b0);
-        float cum[CSM_G], cr[CSM_G], cg[CSM_G], cb[CSM_G], accw[CSM_G], wt[CSM_G], uvar[CSM_G], depth[CSM_G];
+        float cr[CSM_G], cg[CSM_G], cb[CSM_G], accw[CSM_G], wt[CSM_G], uvar[CSM_G], depth[CSM_G];
         float lr[CSM_G], lg[CSM_G], lb[CSM_G];
-        double m0[CSM_G], m1[CSM_G], m2[CSM_G];
+        // the optical-depth prefix in fp64: S fp32 additions in a row lose up to S / 2 ulp of the prefix (2.8e-6 of a weight
+        // behind 255 thin samples, three times what the scanned prefix of the group kernels is allowed)
+        double cum[CSM_G], m0[CSM_G], m1[CSM_G], m2[CSM_G];
         bool found[CSM_G];
 #pragma unroll
         for (int j = 0; j < CSM_G; ++j) {
-            cum[j] = cr[j] = cg[j] = cb[j] = accw[j] = wt[j] = uvar[j] = depth[j] = 0.f;
+            cr[j] = cg[j] = cb[j] = accw[j] = wt[j] = uvar[j] = depth[j] = 0.f;
             lr[j] = lg[j] = lb[j] = 0.f;
-            m0[j] = m1[j] = m2[j] = 0.0;
+            cum[j] = m0[j] = m1[j] = m2[j] = 0.0;
             found[j] = false;
         }
         float e0 = unerf_s2e(sb[0], a.s_near, a.s_far, a.lin);
@@ -4650,8 +4657,8 @@ __global__ __launch_bounds__(256) void composite_sm_kernel(CompSmArgs a) {
                     saw_nan |= (dens != dens) | (cp[0] != cp[0]) | (cp[R] != cp[R]) | (cp[2 * R] != cp[2 * R]);
                     const float dd = delta * dens;
                     const float alpha = 1.f - unerf_exp(-dd);
-                    const float T = unerf_exp(-cum[j]);
-                    cum[j] += dd;
+                    const float T = unerf_exp(-(float)cum[j]);
+                    cum[j] += (double)dd;
                     const float w = unerf_nan_to_num(alpha * T);
                     cr[j] += w * r0;
                     cg[j] += w * g0;
@@ -4819,8 +4826,10 @@ __device__ __forceinline__ void unerf_normal_pair_from_state(uint32_t x, float& 
 // b_i = -delta_i log2(e) mu_i formed once per sample (= -delta log2(e) relu(mu + sd z): -delta <= 0 turns the relu into a
 // min), one v_exp_f32, one multiply for the running product, one subtract, and one fma that adds carry * (P_i - P_{i+1})
 // to the sample's sum over the draws -- 7 issue slots + 5 DPP multiplies per lane and draw (round 2: 12 + 5).
-// NaN (a NaN mean or variance reaches every draw alike) poisons the sums it would zero in get_weights' nan_to_num: this
-// sample, the later ones of the lane and, through the carry, of the ray; the caller maps the final NaN to 0.
+// NaN: fminf drops a NaN exponent (the factor becomes 1: weight 0 at that sample, the later ones untouched), where
+// get_weights' cumsum carries it into every later sample of the ray and nan_to_num zeroes them all.  A NaN exponent comes from
+// b_i (a NaN mean or bin edge; a NaN or negative variance becomes sd = 1e-10) and is the same in every draw, so the caller finds
+// the first such sample of the ray once and writes 0 from there on; a NaN that still reaches a sum is mapped to 0 there too.
 template <int SPL>
 __device__ __forceinline__ void group_weights_accumulate(const float (&z)[SPL], const float (&a)[SPL], const float (&b)[SPL],
                                                          float (&wsum)[SPL]) {
@@ -4887,6 +4896,14 @@ __global__ __launch_bounds__(256) void lap_depth_kernel(LapDepthArgs a, VW... vw
         if constexpr (sizeof...(VW) != 0) st[e] = a.noise ? 0u : unerf_depth_stream_seed(vseed, (uint32_t)((int64_t)vlocal * S + k0 + e));
         else st[e] = a.noise ? 0u : unerf_depth_stream_seed(a.seed, (uint32_t)((a.ray_offset + r) * S + k0 + e));
     }
+    int first_nan = S;   // the first sample of the ray whose exponent is NaN in every draw (see group_weights_accumulate)
+#pragma unroll
+    for (int e = 0; e < SPL; ++e)
+        if ((!RAGGED || k0 + e < S) && cb[e] != cb[e]) first_nan = min(first_nan, k0 + e);
+    first_nan = min(first_nan, dpp_i<0xB1>(first_nan));
+    first_nan = min(first_nan, dpp_i<0x4E>(first_nan));
+    first_nan = min(first_nan, dpp_i<0x141>(first_nan));
+    first_nan = min(first_nan, dpp_i<0x140>(first_nan));
     for (int d0 = 0; d0 < a.D; d0 += 2) {
         float z[2][SPL];
         if (a.noise) {
@@ -4910,7 +4927,7 @@ __global__ __launch_bounds__(256) void lap_depth_kernel(LapDepthArgs a, VW... vw
 #pragma unroll
         for (int e = 0; e < SPL; ++e) {
             const float w = wsum[e] / (float)a.D;
-            if (!RAGGED || k0 + e < S) a.out[r * S + k0 + e] = (w != w) ? 0.f : w;
+            if (!RAGGED || k0 + e < S) a.out[r * S + k0 + e] = (w != w || k0 + e >= first_nan) ? 0.f : w;
         }
     }
 }
