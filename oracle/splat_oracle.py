@@ -85,7 +85,9 @@ def project_gaussians(means3d, scales, glob_scale, quats, viewmat, fx, fy, cx, c
     out["conics"][ok_det] = conics[ok_det]
     out["num_tiles_hit"][ok] = area[ok]
     out["depths"][ok] = tz[ok]
-    out["radii"][ok] = radius[ok].astype(np.int32)
+    # (int)radius saturates, as the CUDA / HIP conversion does (a plain astype wraps beyond 2^31)
+    with np.errstate(all="ignore"):
+        out["radii"][ok] = np.where(radius[ok] >= f32(2.0 ** 31), 2 ** 31 - 1, radius[ok].astype(np.int64)).astype(np.int32)
     out["xys"][ok, 0] = u[ok]
     out["xys"][ok, 1] = v[ok]
     out["compensation"][ok] = comp[ok]
