@@ -1267,9 +1267,9 @@ struct FieldArgs {
     float* rgb;
     float* aux;
     float* aux2;
-    int32_t keep_hi;     // MC-dropout keep threshold thr_s << 16 (unerf_keep_lo / unerf_keep_hi)
+    int32_t keep_hi;     // MC-dropout keep threshold thr_s << 16 (unerf_keep_lo / unerf_keep_hi); bit 0: keep every unit (field_keep_all)
     uint32_t keep_pk;    // thr_s in both 16-bit halves (packed-f16 masks of the split-f16 kernels)
-    int drop_on;         // K > 0 and p_drop > 0: masks are generated (p_drop == 0 keeps every unit)
+    int drop_on;         // the mask path runs: K > 0 and the threshold drops units, or explicit masks, or (fp32 kernels) a scale without drops
     int drop_sites;      // UNERF_DROP_* bits actually in use (0 when !drop_on)
     float drop_scale;
     const float* features;  // optional [16][N][2] level-major planes from unerf_field_gather (MFMA kernel)
@@ -1483,6 +1483,12 @@ __device__ __forceinline__ void dense_lds(const float* __restrict__ Wt, const fl
     }
 }
 
+// FieldArgs.keep_hi = thr_s << 16 has a zero low half; bit 0 set says KEEP EVERY UNIT.  The host sets it where p_drop > 0 is
+// so small that round((1 - p) 65536) = 65536: no signed 16-bit threshold keeps every half, and the scale 1 / (1 - p) still
+// applies (field_fill_args).  Read by the generator paths of the fp32 kernels; the f16 kernels carry the scale in their operand
+// blob and run without masks there.
+__device__ __forceinline__ bool field_keep_all(int32_t thr_hi) { return (thr_hi & 1) != 0; }
+
 // same, with an inverted-dropout mask on the IN inputs (mask words: unerf_mask_word0 / unerf_mask_step; unit 2j is the
 // low half of word j, unit 2j + 1 the high half)
 template <int OUT, int IN = 64>
@@ -1492,16 +1498,17 @@ __device__ __forceinline__ void dense_lds_dropout(const float* __restrict__ Wt, 
 #pragma unroll
     for (int o = 0; o < OUT; ++o) acc[o] = b[o];
     const uint32_t bh[2] = {unerf_mc_base_h(pre, 0u), unerf_mc_base_h(pre, 1u)};
+    const bool all = field_keep_all(thr_hi);
     for (int j = 0; j < (IN + 1) / 2; ++j) {
         uint32_t rnd = unerf_mask_word0(bh[(j >> 1) & 1], stream_id, (uint32_t)j);
         for (int q = 0; q < pass; ++q) rnd = unerf_mask_step(rnd);
         float x0 = act[(2 * j) * 64 + lane];
-        x0 = unerf_keep_lo(rnd, thr_hi) ? x0 * scale : 0.f;
+        x0 = (all || unerf_keep_lo(rnd, thr_hi)) ? x0 * scale : 0.f;
 #pragma unroll
         for (int o = 0; o < OUT; ++o) acc[o] = fmaf(x0, Wt[(2 * j) * OUT + o], acc[o]);
         if (2 * j + 1 < IN) {
             float x1 = act[(2 * j + 1) * 64 + lane];
-            x1 = unerf_keep_hi(rnd, thr_hi) ? x1 * scale : 0.f;
+            x1 = (all || unerf_keep_hi(rnd, thr_hi)) ? x1 * scale : 0.f;
 #pragma unroll
             for (int o = 0; o < OUT; ++o) acc[o] = fmaf(x1, Wt[(2 * j + 1) * OUT + o], acc[o]);
         }
@@ -1756,11 +1763,12 @@ __device__ __forceinline__ void dense_any(const float* __restrict__ Wt, const fl
 __device__ __forceinline__ void mask_any(const float* src, float* dst, int n, int lane, uint32_t pre, int pass,
                                          uint32_t stream_id, int32_t thr_hi, float scale) {
     const uint32_t bh[2] = {unerf_mc_base_h(pre, 0u), unerf_mc_base_h(pre, 1u)};
+    const bool all = field_keep_all(thr_hi);
     for (int j = 0; 2 * j < n; ++j) {
         uint32_t rnd = unerf_mask_word0(bh[(j >> 1) & 1], stream_id, (uint32_t)j);
         for (int q = 0; q < pass; ++q) rnd = unerf_mask_step(rnd);
-        dst[(2 * j) * 64 + lane] = unerf_keep_lo(rnd, thr_hi) ? src[(2 * j) * 64 + lane] * scale : 0.f;
-        if (2 * j + 1 < n) dst[(2 * j + 1) * 64 + lane] = unerf_keep_hi(rnd, thr_hi) ? src[(2 * j + 1) * 64 + lane] * scale : 0.f;
+        dst[(2 * j) * 64 + lane] = (all || unerf_keep_lo(rnd, thr_hi)) ? src[(2 * j) * 64 + lane] * scale : 0.f;
+        if (2 * j + 1 < n) dst[(2 * j + 1) * 64 + lane] = (all || unerf_keep_hi(rnd, thr_hi)) ? src[(2 * j + 1) * 64 + lane] * scale : 0.f;
     }
 }
 // one level of the torch-layout grid with FOUR features per row (16-byte rows): the same corners and lerp order
@@ -1991,10 +1999,11 @@ __device__ __forceinline__ void mf_xm_words(uint32_t (&st)[8], const uint32_t* r
     for (int q = 0; q < 8; ++q) st[q] = xm_word(bits, 2 * (q & 1) + 8 * (q >> 1));
 }
 __device__ __forceinline__ f32x16 mf_dropout(f32x16 v, const uint32_t (&st)[8], int32_t thr_hi, float scale) {
+    const bool all = field_keep_all(thr_hi);
 #pragma unroll
     for (int q = 0; q < 8; ++q) {
-        v[2 * q] = unerf_keep_lo(st[q], thr_hi) ? v[2 * q] * scale : 0.f;
-        v[2 * q + 1] = unerf_keep_hi(st[q], thr_hi) ? v[2 * q + 1] * scale : 0.f;
+        v[2 * q] = (all || unerf_keep_lo(st[q], thr_hi)) ? v[2 * q] * scale : 0.f;
+        v[2 * q + 1] = (all || unerf_keep_hi(st[q], thr_hi)) ? v[2 * q + 1] * scale : 0.f;
     }
     return v;
 }
@@ -3303,10 +3312,20 @@ static void field_fill_args(FieldArgs& a, float near_plane, float far_plane, int
         a.keep_pk = 0u;
     } else {   // keep iff (signed 16-bit half) < thr_s = round((1-p) 65536) - 32768; p = 0 keeps everything (no masks)
         const long thr = lrint((1.0 - (double)a.p.p_drop) * 65536.0);
-        a.drop_on = (a.p.mode == UNERF_FIELD_MCDROPOUT && a.p.K > 0 && thr < 65536) ? 1 : 0;
+        const bool passes = a.p.mode == UNERF_FIELD_MCDROPOUT && a.p.K > 0;
+        a.drop_on = (passes && thr < 65536) ? 1 : 0;
         const int32_t thr_s = (int32_t)(thr < 65536 ? thr : 65535) - 32768;
         a.keep_hi = (int32_t)((uint32_t)thr_s << 16);
         a.keep_pk = ((uint32_t)thr_s & 0xFFFFu) * 0x10001u;
+        // 0 < p <= 2^-17: the threshold keeps every unit, and the Dropout modules still scale by 1 / (1 - p) -- the ONE rule for
+        // the scale is "K > 0", on both sides: ops.pack_field_mfma16 folds it into the f16 operand blob whenever K > 0, so the f16
+        // kernels run without masks here; the kernels that scale at run time (fp32 matrix, VALU, any-width) take the mask path
+        // with the keep-every-unit bit (field_keep_all).  UNERF_DROP_HEADIN is served by the VALU kernel whatever the blobs.
+        const bool f16_blob = a.p.mfma16_blob && !a.features && !(requested_drop_sites(a.p) & UNERF_DROP_HEADIN);
+        if (passes && thr >= 65536 && a.p.p_drop > 0.f && !f16_blob) {
+            a.drop_on = 1;
+            a.keep_hi |= 1;
+        }
     }
     a.drop_sites = a.drop_on ? requested_drop_sites(a.p) : 0;
     a.drop_scale = 1.f / (1.f - a.p.p_drop);
