@@ -434,7 +434,8 @@ for _S in (33, 64):
     COMPOSITE[f"uniform-S{_S}"] = functools.partial(toleranced, _S, 3, "last_sample", "uniform")
     COMPOSITE[f"nobeta-S{_S}"] = functools.partial(toleranced, _S, 1, "white", "nobeta")
 ALT = {f"alt-S{S}": functools.partial(toleranced, S, 1, "last_sample", "alt") for S in S_ALT}
-VIEWS = {f"views-S{S}": functools.partial(toleranced, S, 3, "last_sample", "views") for S in (17, 48)}
+# several views: the first and last rows of the samples-per-lane table (SPL 1 ragged, SPL 16 aligned) and two between them
+VIEWS = {f"views-S{S}": functools.partial(toleranced, S, 3, "last_sample", "views") for S in (1, 17, 48, 256)}
 EXACT = {f"exact-S{S}-{bg if isinstance(bg, str) else 'colour'}": functools.partial(exact, S, bg) for S in S_EXACT for bg in BACKGROUNDS}
 MOMENTS = {f"mom-S{S}-B{B}": functools.partial(toleranced, S, B, BACKGROUNDS[(i + j) % 5])
            for i, S in enumerate(S_MOMENTS) for j, B in enumerate(B_MOMENTS)}

@@ -65,6 +65,19 @@ def test_bad_shapes_are_rejected(lib):
     rc = h.unerf_weights_pdf_resample(1, 1, 0, 4, 300, 0.05, 1000.0, 0, 1, 96, 0.01, 1e-5, 1, None, None, None, 0, 32768,
                                       None)
     assert rc == -1 and b"outside" in h.unerf_last_error()
+    # one past the largest sample count of the ray stages, refused by each entry point under its own name (no kernel is
+    # selected for it: unerf_nerf.hip with_spl / with_int)
+    rc = h.unerf_weights_pdf_resample(1, 1, 0, 4, 257, 0.05, 1000.0, 0, 1, 96, 0.01, 1e-5, 1, None, None, None, 0, 32768,
+                                      None)
+    assert rc == -1 and b"weights_pdf_resample: n=257 outside [1,256]" in h.unerf_last_error()
+    rc = h.unerf_composite_moments(1, 1, 1, 8, 4, 257, 0.05, 1000.0, 0, None, 0, 32768, 0, None, None, 1, 1, None)
+    assert rc == -1 and b"composite_moments: S=257 outside [1,256]" in h.unerf_last_error()
+    rc = h.unerf_laplace_depth_weights(1, 1, 1, 4, 257, 0.05, 1000.0, 0, None, 100, 0, 0, 1, None)
+    assert rc == -1 and b"laplace_depth_weights: bad D/R/S" in h.unerf_last_error()
+    views = lib.RayViews()
+    views.n_views, views.rays_per_view = 2, 2
+    rc = h.unerf_laplace_depth_weights_views(1, 1, 1, 4, 48, 0.05, 1000.0, 0, None, 100, C.byref(views), None, 1, None)
+    assert rc == -1 and b"laplace_depth_weights_views: null lap_views" in h.unerf_last_error()
     rc = h.unerf_splat_rasterize(None, 1, 1, 1, 1, 1, None, 9, 16, 16, 16, None, 0, -1, None, 1, 1, None, None)
     assert rc == -1 and b"C=9" in h.unerf_last_error()
     rc = h.unerf_splat_rasterize(None, 1, 1, 1, 1, 1, None, 5, 16, 16, 16, None, 0, 5, 1, 1, 1, None, None)

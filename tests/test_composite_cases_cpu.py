@@ -161,7 +161,7 @@ MUTATIONS = {
     "clamp_S": ["S16-B3", "S17-B3", "S129-B1", "S256-B3", "alt-S48"],
     "le": ["alt-S17", "alt-S48", "alt-S129"],
     "no_offset": ["S16-B3", "S129-B3", "S255-B1"],
-    "global_row": ["views-S17", "views-S48"],
+    "global_row": ["views-S1", "views-S17", "views-S48", "views-S256"],
 }
 
 

@@ -69,12 +69,13 @@ def test_every_weight_bin_and_depth_within_its_bound(dev, key):
     _check_clip(c, new, clip, lambda r: r // CHUNK)
 
 
-def test_views_entry_point_at_three_samples_per_lane(dev):
-    """pdf_kernel<3, ViewMap>: three views of 12 rays (RayViews holds views of one size): same bits as the plain call, the clip
-    rows numbered inside each view (3 rows per view at 5 rays per chunk)"""
+@pytest.mark.parametrize("key,epl", [("plain-63-64", 1), ("plain-127-128", 2), ("plain-191-65", 3), ("plain-256-255", 4)])
+def test_views_entry_point_at_every_samples_per_lane(dev, key, epl):
+    """pdf_kernel<EPL, ViewMap>, EPL 1 .. 4: three views of 12 rays (RayViews holds views of one size): same bits as the plain
+    call, the clip rows numbered inside each view (3 rows per view at 5 rays per chunk)"""
     from uncertainty_nerf_gs_amd import ops
-    c, rows = PC.ALL["plain-191-65"](), slice(0, 36)
-    assert c.epl == 3 and ops.clip_rows_per_view(12, CHUNK) == 3
+    c, rows = PC.ALL[key](), slice(0, 36)
+    assert c.epl == epl and c.dens.shape[0] >= 36 and ops.clip_rows_per_view(12, CHUNK) == 3
     plain = _call(dev, c, rows)
     new, pd, w, clip = _call(dev, c, rows, views=ops.RayViews(3, 12), clip_rows=9)
     for a, b in zip((new, pd, w), plain):

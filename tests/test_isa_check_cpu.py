@@ -47,3 +47,14 @@ def test_the_built_library_passes_and_its_matrix_kernels_are_found(lib):
     import re
     fk = [k for k in stats if re.match(r"_Z\d+field_kernel", k)]
     assert len(fk) == 61 and sum("8KeepArgs" in k for k in fk) == 11, (len(fk), sorted(fk))
+    # ... and so for the ray stages around the field (with_spl / with_int / with_bool / with_pack in the same file):
+    # pdf_kernel 4 EPL x {none, ViewMap}; composite_kernel and composite_moments_kernel 7 SPL x {aligned, RAGGED} x
+    # {plain, PACKED} x {none, ViewMap}; lap_depth_kernel 7 SPL x {aligned, RAGGED} x {none, LapDepthViews}; both proposal
+    # kernels for the six (L, hidden) networks; the planes composite with and without MOMENTS
+    count = lambda name: sum(bool(re.match(rf"_Z\d+{name}I", k)) for k in stats)
+    views = lambda name, pack: sum(bool(re.match(rf"_Z\d+{name}I", k)) and pack in k for k in stats)
+    assert (count("pdf_kernel"), views("pdf_kernel", "7ViewMap")) == (8, 4)
+    assert (count("composite_kernel"), views("composite_kernel", "7ViewMap")) == (56, 28)
+    assert (count("composite_moments_kernel"), views("composite_moments_kernel", "7ViewMap")) == (56, 28)
+    assert (count("lap_depth_kernel"), views("lap_depth_kernel", "13LapDepthViews")) == (28, 14)
+    assert (count("prop_density_kernel"), count("prop_patch_kernel"), count("composite_sm_kernel")) == (6, 6, 2)

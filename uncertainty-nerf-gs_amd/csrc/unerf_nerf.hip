@@ -7,6 +7,7 @@
 #include <type_traits>
 #include <unordered_map>
 
+#include <cassert>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -115,6 +116,52 @@ static inline int unerf_set_background(Args& a, int background, const float* rgb
 
 #define UNERF_REQUIRE_SPACING(sp) \
     UNERF_REQUIRE((sp) == UNERF_SPACING_PIECEWISE || (sp) == UNERF_SPACING_UNIFORM, "spacing=%d (expected UNERF_SPACING_*)", (int)(sp))
+// the spacing fields of a kernel's argument struct: the checked UNERF_SPACING_* and the near / far planes in its domain
+template <typename Args>
+static inline int set_spacing(Args& a, float near_plane, float far_plane, int spacing) {
+    UNERF_REQUIRE_SPACING(spacing);
+    a.lin = spacing; a.s_near = unerf_spacing_of(near_plane, spacing); a.s_far = unerf_spacing_of(far_plane, spacing);
+    return UNERF_OK;
+}
+
+// ---- kernel selection: a run-time value as a compile-time constant handed to f, once.  Every host function that picks a
+// template instantiation does it through these (one launch expression per kernel family), and nothing else does.
+// v in Vs... -> f(std::integral_constant<int, v>{}); false when v is none of them (f is not called)
+template <int... Vs, typename F>
+static bool with_int(int v, F&& f) {
+    return ((v == Vs && (f(std::integral_constant<int, Vs>{}), true)) || ...);
+}
+// {0, 1, 2}: the TCNN argument of the matrix kernels and the UNERF_FIELD_* mode (checked before: no other value gets here)
+template <typename F>
+static void with_int3(int v, F&& f) { with_int<0, 1, 2>(v, f); }
+template <typename F>
+static void with_bool(bool b, F&& f) {
+    if (b) f(std::true_type{});
+    else f(std::false_type{});
+}
+// the trailing argument pack of the *_views kernels: f(make()) when the launch has one, f() for the single-view kernels
+template <typename Make, typename F>
+static void with_pack(bool on, Make&& make, F&& f) {
+    if (on) f(make());
+    else f();
+}
+// Samples per lane of the 16-lane ray groups (composite, depth draws): S = 16 * SPL for SPL in {1,2,3,4,6,8,16} (every
+// nerfacto sample count) takes the aligned kernels; any other 1 <= S <= 256 takes the RAGGED instantiation of the next SPL
+// up, whose slots k >= S are masked.
+static inline int unerf_spl_for(int S) {
+    const int want = (S + 15) / 16;
+    for (int spl : {1, 2, 3, 4, 6, 8, 16})
+        if (spl >= want) return spl;
+    return 0;
+}
+// f(integral_constant<int, SPL>, bool_constant<RAGGED>); the callers have refused S outside [1,256] by name
+template <typename F>
+static void with_spl(int S, F&& f) {
+    const int spl = unerf_spl_for(S);
+    const bool built = with_int<1, 2, 3, 4, 6, 8, 16>(spl, [&](auto n) { with_bool(spl * 16 != S, [&](auto ragged) { f(n, ragged); }); });
+    assert(built);
+    (void)built;
+}
 static inline unsigned blocks_for(int64_t n, int per_block) { return (unsigned)((n + per_block - 1) / per_block); }
 
 // Division of an index < 2^31 by a launch-invariant divisor (samples per ray): one multiply-high and a
@@ -921,7 +968,7 @@ extern "C" int unerf_proposal_density(const float* origins, const float* directi
     if (R == 0) return UNERF_OK;
     PropArgs a;
     a.origins = origins; a.dirs = directions; a.sbins = sbins; a.sstride = sbins_stride; a.R = R; a.n = n;
-    UNERF_REQUIRE_SPACING(spacing); a.lin = spacing; a.s_near = unerf_spacing_of(near_plane, spacing); a.s_far = unerf_spacing_of(far_plane, spacing);
+    if (int rc = set_spacing(a, near_plane, far_plane, spacing)) return rc;
     a.net = *net; a.avg = average_init_density; a.out = density_out;
     a.box = make_norm_box(net->use_aabb, net->aabb);
     a.fd = make_fastdiv((uint32_t)n); a.small = (R * (int64_t)n < (1ll << 31)) ? 1 : 0;
@@ -943,21 +990,17 @@ extern "C" int unerf_proposal_density(const float* origins, const float* directi
     hipStream_t st = (hipStream_t)stream;
     // image-ordered rays: the LDS-staged patch kernel; anything else: one thread per sample
     const bool patch = a.img_w != 0 && !getenv("UNERF_NO_PATCH_KERNEL");
-#define UNERF_PROP_LAUNCH(LL, HH)                                                                          \
-    if (patch) hipLaunchKernelGGL((prop_patch_kernel<LL, HH>), grid, block, 0, st, a);                    \
-    else hipLaunchKernelGGL((prop_density_kernel<LL, HH>), grid, block, 0, st, a)
-    if (net->L == 5 && net->hidden == 16) { UNERF_PROP_LAUNCH(5, 16); }
-    else if (net->L == 5 && net->hidden == 64) { UNERF_PROP_LAUNCH(5, 64); }
-    else if (net->L == 8 && net->hidden == 64) { UNERF_PROP_LAUNCH(8, 64); }
-    else if (net->L == 8 && net->hidden == 16) { UNERF_PROP_LAUNCH(8, 16); }
-    else if (net->L == 5 && net->hidden == 0) { UNERF_PROP_LAUNCH(5, 0); }   // use_linear=True
-    else if (net->L == 8 && net->hidden == 0) { UNERF_PROP_LAUNCH(8, 0); }
-    else {
-        unerf_set_error("proposal_density: unsupported (L=%d, hidden=%d); built: (5,16) (5,64) (8,16) (8,64) (5,0) (8,0)", net->L,
-                        net->hidden);
-        return UNERF_ERR_ARG;
-    }
-#undef UNERF_PROP_LAUNCH
+    // both kernels are built for L in {5, 8} levels x a hidden width in {16, 64, 0}; 0: use_linear=True
+    bool built = false;
+    with_int<5, 8>(net->L, [&](auto L) {
+        built = with_int<16, 64, 0>(net->hidden, [&](auto hidden) {
+            const auto kernel = patch ? prop_patch_kernel<decltype(L)::value, decltype(hidden)::value>
+                                      : prop_density_kernel<decltype(L)::value, decltype(hidden)::value>;
+            hipLaunchKernelGGL(kernel, grid, block, 0, st, a);
+        });
+    });
+    UNERF_REQUIRE(built, "proposal_density: unsupported (L=%d, hidden=%d); built: (5,16) (5,64) (8,16) (8,64) (5,0) (8,0)", net->L,
+                  net->hidden);
     return unerf_check_launch("proposal_density");
 }
 
@@ -1191,29 +1234,20 @@ static int pdf_resample_impl(const float* density, const float* sbins, int64_t s
     if (R <= 0) return UNERF_OK;
     PdfArgs a;
     a.density = density; a.sbins = sbins; a.sstride = sbins_stride; a.R = R; a.n = n;
-    UNERF_REQUIRE_SPACING(spacing); a.lin = spacing; a.s_near = unerf_spacing_of(near_plane, spacing); a.s_far = unerf_spacing_of(far_plane, spacing);
+    if (int rc = set_spacing(a, near_plane, far_plane, spacing)) return rc;
     a.u = u; a.m = m; a.pad = histogram_padding; a.eps = eps; a.sbins_out = sbins_out; a.prop_depth = prop_depth_out;
     a.weights_out = weights_out; a.clip = clip_minmax; a.ray_offset = ray_offset; a.chunk_rays = chunk_rays;
     dim3 grid(blocks_for(R, PDF_RAYS_PER_BLOCK)), block(256);
     hipStream_t st = (hipStream_t)stream;
-    int epl = (n + 63) / 64;
-    if (views && clip_minmax) {   // (without a clip buffer nothing in the kernel is numbered by the frame)
-        const ViewMap vm = make_view_map(views, chunk_rays);
-        switch (epl) {
-            case 1: hipLaunchKernelGGL((pdf_kernel<1, ViewMap>), grid, block, 0, st, a, vm); break;
-            case 2: hipLaunchKernelGGL((pdf_kernel<2, ViewMap>), grid, block, 0, st, a, vm); break;
-            case 3: hipLaunchKernelGGL((pdf_kernel<3, ViewMap>), grid, block, 0, st, a, vm); break;
-            default: hipLaunchKernelGGL((pdf_kernel<4, ViewMap>), grid, block, 0, st, a, vm); break;
-        }
-        return unerf_check_launch("weights_pdf_resample_views");
-    }
-    switch (epl) {
-        case 1: hipLaunchKernelGGL((pdf_kernel<1>), grid, block, 0, st, a); break;
-        case 2: hipLaunchKernelGGL((pdf_kernel<2>), grid, block, 0, st, a); break;
-        case 3: hipLaunchKernelGGL((pdf_kernel<3>), grid, block, 0, st, a); break;
-        default: hipLaunchKernelGGL((pdf_kernel<4>), grid, block, 0, st, a); break;
-    }
-    return unerf_check_launch("weights_pdf_resample");
+    // pdf_kernel<EPL, VW...>: EPL = ceil(n / 64) samples per lane (n <= PDF_MAXN: 1 .. 4); the clip rows are numbered per
+    // view only where there is a clip buffer (without one nothing in the kernel is numbered by the frame)
+    const bool per_view = views && clip_minmax;
+    with_pack(per_view, [&] { return make_view_map(views, chunk_rays); }, [&](auto... vm) {
+        with_int<1, 2, 3, 4>((n + 63) / 64, [&](auto epl) {
+            hipLaunchKernelGGL((pdf_kernel<decltype(epl)::value, decltype(vm)...>), grid, block, 0, st, a, vm...);
+        });
+    });
+    return unerf_check_launch(per_view ? "weights_pdf_resample_views" : "weights_pdf_resample");
 }
 
 extern "C" int unerf_weights_pdf_resample(const float* density, const float* sbins, int64_t sbins_stride, int64_t R,
@@ -3107,7 +3141,7 @@ extern "C" int unerf_field_gather(const float* origins, const float* directions,
     if (R == 0) return UNERF_OK;
     GatherArgs a;
     a.origins = origins; a.dirs = directions; a.sbins = sbins; a.R = R; a.S = S;
-    UNERF_REQUIRE_SPACING(spacing); a.lin = spacing; a.s_near = unerf_spacing_of(near_plane, spacing); a.s_far = unerf_spacing_of(far_plane, spacing);
+    if (int rc = set_spacing(a, near_plane, far_plane, spacing)) return rc;
     a.table = table; a.scalings = scalings; a.L = L; a.log2T = log2T; a.planes = feature_planes;
     a.box = make_norm_box(0, nullptr);
     // blockIdx.x runs fastest in dispatch order, so all workgroups of level l are issued before
@@ -3163,21 +3197,7 @@ constexpr size_t mf16_lds_bytes(bool F1, bool DROP) { return (F1 || DROP) ? (siz
 // The kernel selection is field_launch() with the launch_* helpers above it, and nothing else (as a table: DESIGN.md 6,
 // "Which field kernel a call runs").
 // --------------------------------------------------------------------------------------
-// a run-time value in {0, 1, 2} as a compile-time constant handed to f: the TCNN argument of the matrix kernels and the
-// UNERF_FIELD_* mode (checked before: no other value gets here)
-template <typename F>
-static void with_int3(int v, F&& f) {
-    switch (v) {
-        case 0: f(std::integral_constant<int, 0>{}); break;
-        case 1: f(std::integral_constant<int, 1>{}); break;
-        case 2: f(std::integral_constant<int, 2>{}); break;
-    }
-}
-template <typename F>
-static void with_bool(bool b, F&& f) {
-    if (b) f(std::true_type{});
-    else f(std::false_type{});
-}
+// (with_int3 / with_bool: "kernel selection" in the host plumbing at the top of the file)
 // the TCNN template argument: 0 = torch-layout grid, 1 = tcnn layout, 2 = tcnn layout with half2 rows (grid_half)
 static int tcnn_arg(const unerf_field_params& p) { return p.tcnn_levels ? (p.grid_half ? 2 : 1) : 0; }
 
@@ -3790,7 +3810,8 @@ extern "C" int unerf_laplace_ggn_diag(const float* origins, const float* directi
     hipStream_t st = (hipStream_t)stream;
     FieldArgs a;
     a.origins = origins; a.dirs = directions; a.sbins = sbins; a.R = R; a.S = S;
-    UNERF_REQUIRE_SPACING(spacing); a.lin = spacing; a.s_near = unerf_spacing_of(near_plane, spacing); a.s_far = unerf_spacing_of(far_plane, spacing); a.ray_offset = 0;
+    if (int rc = set_spacing(a, near_plane, far_plane, spacing)) return rc;
+    a.ray_offset = 0;
     a.p = *p; a.density = sigma; a.rgb = col; a.aux = X; a.aux2 = Hc; a.features = nullptr;
     a.keep_hi = 0; a.keep_pk = 0; a.drop_on = 0; a.drop_sites = 0; a.drop_scale = 1.f;
     a.box = make_norm_box(p->use_aabb, p->aabb);
@@ -4148,7 +4169,7 @@ extern "C" int unerf_pose_grad(const float* origins, const float* directions, co
     UNERF_REQUIRE(near_plane >= 0.f, "pose_grad: near_plane=%g (spacing-domain bins only)", (double)near_plane);
     PoseGradArgs g;
     g.origins = origins; g.dirs = directions; g.sbins = sbins; g.R = R; g.S = S;
-    UNERF_REQUIRE_SPACING(spacing); g.lin = spacing; g.s_near = unerf_spacing_of(near_plane, spacing); g.s_far = unerf_spacing_of(far_plane, spacing);
+    if (int rc = set_spacing(g, near_plane, far_plane, spacing)) return rc;
     g.p = *p;
     g.box = make_norm_box(p->use_aabb, p->aabb);
     if (int rc = unerf_set_background(g, background, background_rgb, "pose_grad")) return rc;
@@ -4368,22 +4389,10 @@ __device__ __forceinline__ void composite_kernel_body(const CompArgs& a, const V
         o[1] = make_float4(o8[4], o8[5], o8[6], o8[7]);
     }
 }
-template <int SPL, bool RAGGED = false>
-__global__ __launch_bounds__(256) void composite_kernel(CompArgs a) {
-    composite_kernel_body<SPL, RAGGED, false>(a);
-}
-template <int SPL, bool RAGGED = false>
-__global__ __launch_bounds__(256) void composite_kernel_packed(CompArgs a) {
-    composite_kernel_body<SPL, RAGGED, true>(a);
-}
-// unerf_composite_var_views
-template <int SPL, bool RAGGED = false>
-__global__ __launch_bounds__(256) void composite_kernel_views(CompArgs a, ViewMap vm) {
-    composite_kernel_body<SPL, RAGGED, false>(a, vm);
-}
-template <int SPL, bool RAGGED = false>
-__global__ __launch_bounds__(256) void composite_kernel_packed_views(CompArgs a, ViewMap vm) {
-    composite_kernel_body<SPL, RAGGED, true>(a, vm);
+// (a wrapper: with the body itself as the kernel some instantiations compile to other code, docs/experiments.md 8.3)
+template <int SPL, bool RAGGED, bool PACKED, typename... VW>   // VW = ViewMap: unerf_composite_var_views with a clip buffer
+__global__ __launch_bounds__(256) void composite_kernel(CompArgs a, VW... vw) {
+    composite_kernel_body<SPL, RAGGED, PACKED>(a, vw...);
 }
 
 // K-pass form: one 16-lane group walks the B <= 16 passes of a ray, lane b keeps pass b's eight
@@ -4431,58 +4440,11 @@ __device__ __forceinline__ void composite_moments_body(const CompArgs& a, float*
         vo[1] = make_float4(v8[4], v8[5], v8[6], v8[7]);
     }
 }
-template <int SPL, bool RAGGED = false>
+template <int SPL, bool RAGGED, bool PACKED, typename... VW>   // VW = ViewMap: unerf_composite_moments_views with a clip buffer
 __global__ __launch_bounds__(256) void composite_moments_kernel(CompArgs a, float* __restrict__ mean_out,
-                                                                float* __restrict__ var_out) {
-    composite_moments_body<SPL, RAGGED, false>(a, mean_out, var_out);
+                                                                float* __restrict__ var_out, VW... vw) {
+    composite_moments_body<SPL, RAGGED, PACKED>(a, mean_out, var_out, vw...);
 }
-template <int SPL, bool RAGGED = false>
-__global__ __launch_bounds__(256) void composite_moments_kernel_packed(CompArgs a, float* __restrict__ mean_out,
-                                                                       float* __restrict__ var_out) {
-    composite_moments_body<SPL, RAGGED, true>(a, mean_out, var_out);
-}
-// unerf_composite_moments_views
-template <int SPL, bool RAGGED = false>
-__global__ __launch_bounds__(256) void composite_moments_kernel_views(CompArgs a, float* __restrict__ mean_out,
-                                                                      float* __restrict__ var_out, ViewMap vm) {
-    composite_moments_body<SPL, RAGGED, false>(a, mean_out, var_out, vm);
-}
-template <int SPL, bool RAGGED = false>
-__global__ __launch_bounds__(256) void composite_moments_kernel_packed_views(CompArgs a, float* __restrict__ mean_out,
-                                                                             float* __restrict__ var_out, ViewMap vm) {
-    composite_moments_body<SPL, RAGGED, true>(a, mean_out, var_out, vm);
-}
-
-// Samples per lane: S = 16 * SPL for SPL in {1,2,3,4,6,8,16} (every nerfacto sample count) takes the aligned
-// kernels; any other 1 <= S <= 256 takes the RAGGED instantiation of the next SPL up, whose slots k >= S are masked.
-static inline int unerf_spl_for(int S) {
-    const int want = (S + 15) / 16;
-    for (int spl : {1, 2, 3, 4, 6, 8, 16})
-        if (spl >= want) return spl;
-    return 0;
-}
-#define UNERF_SPL_CASE(N, KERNEL, ...)                                                                              \
-    case N:                                                                                                         \
-        if (ragged_) hipLaunchKernelGGL((KERNEL<N, true>), __VA_ARGS__);                                            \
-        else hipLaunchKernelGGL((KERNEL<N, false>), __VA_ARGS__);                                                   \
-        break;
-#define UNERF_DISPATCH_SPL(S, KERNEL, ...)                                                                          \
-    {                                                                                                               \
-        const int spl_ = unerf_spl_for(S);                                                                          \
-        const bool ragged_ = spl_ * 16 != (S);                                                                      \
-        switch (spl_) {                                                                                             \
-            UNERF_SPL_CASE(1, KERNEL, __VA_ARGS__)                                                                  \
-            UNERF_SPL_CASE(2, KERNEL, __VA_ARGS__)                                                                  \
-            UNERF_SPL_CASE(3, KERNEL, __VA_ARGS__)                                                                  \
-            UNERF_SPL_CASE(4, KERNEL, __VA_ARGS__)                                                                  \
-            UNERF_SPL_CASE(6, KERNEL, __VA_ARGS__)                                                                  \
-            UNERF_SPL_CASE(8, KERNEL, __VA_ARGS__)                                                                  \
-            UNERF_SPL_CASE(16, KERNEL, __VA_ARGS__)                                                                 \
-            default:                                                                                                \
-                unerf_set_error("samples per ray S=%d outside [1,256]", (S));                                       \
-                return UNERF_ERR_ARG;                                                                               \
-        }                                                                                                           \
-    }
 
 // views = NULL: unerf_composite_var
 static int composite_var_impl(const float* density, const float* rgb, const float* beta, const float* weights_alt,
@@ -4497,27 +4459,24 @@ static int composite_var_impl(const float* density, const float* rgb, const floa
     if (R == 0) return UNERF_OK;
     CompArgs a;
     a.density = density; a.rgb = rgb; a.beta = beta; a.walt = weights_alt; a.sbins = sbins; a.B = B; a.R = R; a.S = S;
-    UNERF_REQUIRE_SPACING(spacing); a.lin = spacing; a.s_near = unerf_spacing_of(near_plane, spacing); a.s_far = unerf_spacing_of(far_plane, spacing);
+    if (int rc = set_spacing(a, near_plane, far_plane, spacing)) return rc;
     a.clip = clip_minmax; a.ray_offset = ray_offset; a.chunk_rays = chunk_rays; a.out = out;
     if (int rc = unerf_set_background(a, background, background_rgb, "composite_var")) return rc;
     a.flag = nonfinite_flag;
     dim3 grid(blocks_for((int64_t)B * R, 16)), block(256);
     hipStream_t st = (hipStream_t)stream;
-    if (views && clip_minmax) {   // (without a clip buffer nothing in the kernel is numbered by the frame)
-        const ViewMap vm = make_view_map(views, chunk_rays);
-        if (density) {
-            UNERF_DISPATCH_SPL(S, composite_kernel_views, grid, block, 0, st, a, vm);
-        } else {
-            UNERF_DISPATCH_SPL(S, composite_kernel_packed_views, grid, block, 0, st, a, vm);
-        }
-        return unerf_check_launch("composite_var_views");
-    }
-    if (density) {
-        UNERF_DISPATCH_SPL(S, composite_kernel, grid, block, 0, st, a);
-    } else {
-        UNERF_DISPATCH_SPL(S, composite_kernel_packed, grid, block, 0, st, a);
-    }
-    return unerf_check_launch("composite_var");
+    // composite_kernel<SPL, RAGGED, PACKED, VW...>; per-view clip rows only where there is a clip buffer (without one
+    // nothing in the kernel is numbered by the frame)
+    const bool per_view = views && clip_minmax;
+    with_pack(per_view, [&] { return make_view_map(views, chunk_rays); }, [&](auto... vm) {
+        with_spl(S, [&](auto spl, auto ragged) {
+            with_bool(density == nullptr, [&](auto packed) {
+                hipLaunchKernelGGL((composite_kernel<decltype(spl)::value, decltype(ragged)::value, decltype(packed)::value, decltype(vm)...>),
+                                   grid, block, 0, st, a, vm...);
+            });
+        });
+    });
+    return unerf_check_launch(per_view ? "composite_var_views" : "composite_var");
 }
 
 extern "C" int unerf_composite_var(const float* density, const float* rgb, const float* beta, const float* weights_alt,
@@ -4551,27 +4510,22 @@ static int composite_moments_impl(const float* density, const float* rgb, const 
     if (R == 0) return UNERF_OK;
     CompArgs a;
     a.density = density; a.rgb = rgb; a.beta = nullptr; a.walt = nullptr; a.sbins = sbins; a.B = B; a.R = R; a.S = S;
-    UNERF_REQUIRE_SPACING(spacing); a.lin = spacing; a.s_near = unerf_spacing_of(near_plane, spacing); a.s_far = unerf_spacing_of(far_plane, spacing);
+    if (int rc = set_spacing(a, near_plane, far_plane, spacing)) return rc;
     a.clip = clip_minmax; a.ray_offset = ray_offset; a.chunk_rays = chunk_rays; a.out = nullptr;
     if (int rc = unerf_set_background(a, background, background_rgb, "composite_moments")) return rc;
     a.flag = nonfinite_flag;
     dim3 grid(blocks_for(R, 16)), block(256);
     hipStream_t st = (hipStream_t)stream;
-    if (views && clip_minmax) {
-        const ViewMap vm = make_view_map(views, chunk_rays);
-        if (density) {
-            UNERF_DISPATCH_SPL(S, composite_moments_kernel_views, grid, block, 0, st, a, mean_out, var_out, vm);
-        } else {
-            UNERF_DISPATCH_SPL(S, composite_moments_kernel_packed_views, grid, block, 0, st, a, mean_out, var_out, vm);
-        }
-        return unerf_check_launch("composite_moments_views");
-    }
-    if (density) {
-        UNERF_DISPATCH_SPL(S, composite_moments_kernel, grid, block, 0, st, a, mean_out, var_out);
-    } else {
-        UNERF_DISPATCH_SPL(S, composite_moments_kernel_packed, grid, block, 0, st, a, mean_out, var_out);
-    }
-    return unerf_check_launch("composite_moments");
+    const bool per_view = views && clip_minmax;   // composite_moments_kernel<SPL, RAGGED, PACKED, VW...>, as composite_var_impl
+    with_pack(per_view, [&] { return make_view_map(views, chunk_rays); }, [&](auto... vm) {
+        with_spl(S, [&](auto spl, auto ragged) {
+            with_bool(density == nullptr, [&](auto packed) {
+                hipLaunchKernelGGL((composite_moments_kernel<decltype(spl)::value, decltype(ragged)::value, decltype(packed)::value, decltype(vm)...>),
+                                   grid, block, 0, st, a, mean_out, var_out, vm...);
+            });
+        });
+    });
+    return unerf_check_launch(per_view ? "composite_moments_views" : "composite_moments");
 }
 
 extern "C" int unerf_composite_moments(const float* density, const float* rgb, const float* sbins, int B, int64_t R, int S,
@@ -4763,14 +4717,15 @@ static int composite_planes_launch(const float* density, const float* rgb, const
     if (R == 0) return UNERF_OK;
     CompSmArgs a;
     a.density = density; a.rgb = rgb; a.beta = beta; a.sbins = sbins; a.B = B; a.R = R; a.S = S;
-    UNERF_REQUIRE_SPACING(spacing); a.lin = spacing; a.s_near = unerf_spacing_of(near_plane, spacing); a.s_far = unerf_spacing_of(far_plane, spacing);
+    if (int rc = set_spacing(a, near_plane, far_plane, spacing)) return rc;
     a.clip = clip_minmax; a.ray_offset = ray_offset; a.chunk_rays = chunk_rays;
     a.out = out; a.mean_out = mean_out; a.var_out = var_out;
     if (int rc = unerf_set_background(a, background, background_rgb, what)) return rc;
     a.flag = nonfinite_flag;
     dim3 grid(blocks_for(R, 256)), block(256);
-    if (out) hipLaunchKernelGGL(composite_sm_kernel<false>, grid, block, 0, (hipStream_t)stream, a);
-    else hipLaunchKernelGGL(composite_sm_kernel<true>, grid, block, 0, (hipStream_t)stream, a);
+    with_bool(out == nullptr, [&](auto moments) {
+        hipLaunchKernelGGL(composite_sm_kernel<decltype(moments)::value>, grid, block, 0, (hipStream_t)stream, a);
+    });
     return unerf_check_launch(what);
 }
 
@@ -4872,7 +4827,7 @@ __device__ __forceinline__ void group_weights_accumulate(const float (&z)[SPL], 
     for (int e = 0; e < SPL; ++e) wsum[e] = fmaf(carry, dl[e], wsum[e]);
 }
 
-// SEVERAL VIEWS (unerf_laplace_depth_weights_views): a kernel argument of lap_depth_kernel_views only.  Launch row r is
+// SEVERAL VIEWS (unerf_laplace_depth_weights_views): a kernel argument of lap_depth_kernel<.., LapDepthViews> only.  Launch row r is
 // frame-local ray r mod hw of view r / hw; its streams are seeded inside its own frame under its view's seed.
 struct LapDepthViews {
     FastDiv div_hw;   // by rays per view
@@ -4950,9 +4905,30 @@ __global__ __launch_bounds__(256) void lap_depth_kernel(LapDepthArgs a, VW... vw
         }
     }
 }
-// the several-views instantiations under a name of two template arguments (UNERF_DISPATCH_SPL)
-template <int SPL, bool RAGGED = false>
-constexpr auto lap_depth_kernel_views = lap_depth_kernel<SPL, RAGGED, LapDepthViews>;
+// One body behind both entry points (each keeps its own checks): views = lap_views = NULL is unerf_laplace_depth_weights.
+static int lap_depth_impl(const float* density_mu, const float* density_var, const float* sbins, int64_t R, int S,
+                          float near_plane, float far_plane, int spacing, const float* noise, int D, uint32_t seed,
+                          int64_t ray_offset, const unerf_ray_views* views, const unerf_laplace_views* lap_views,
+                          float* weights_out, void* stream, const char* what) {
+    LapDepthArgs a;
+    a.mu = density_mu; a.var = density_var; a.sbins = sbins; a.R = R; a.S = S;
+    if (int rc = set_spacing(a, near_plane, far_plane, spacing)) return rc;
+    a.noise = noise; a.D = D; a.seed = seed; a.ray_offset = ray_offset; a.out = weights_out;
+    auto make_views = [&] {
+        LapDepthViews dv;
+        dv.div_hw = make_fastdiv((uint32_t)views->rays_per_view); dv.hw = (uint32_t)views->rays_per_view;
+        for (int v = 0; v < UNERF_NERF_MAX_VIEWS; ++v) dv.seed[v] = lap_views->depth_seed[v < views->n_views ? v : 0];
+        return dv;
+    };
+    dim3 grid(blocks_for(R, 16)), block(256);
+    with_pack(views != nullptr, make_views, [&](auto... dv) {   // lap_depth_kernel<SPL, RAGGED, VW...>
+        with_spl(S, [&](auto spl, auto ragged) {
+            hipLaunchKernelGGL((lap_depth_kernel<decltype(spl)::value, decltype(ragged)::value, decltype(dv)...>), grid, block, 0,
+                               (hipStream_t)stream, a, dv...);
+        });
+    });
+    return unerf_check_launch(what);
+}
 
 extern "C" int unerf_laplace_depth_weights(const float* density_mu, const float* density_var, const float* sbins,
                                            int64_t R, int S, float near_plane, float far_plane, int spacing, const float* noise,
@@ -4960,14 +4936,8 @@ extern "C" int unerf_laplace_depth_weights(const float* density_mu, const float*
     UNERF_REQUIRE(R == 0 || (density_mu && density_var && sbins && weights_out), "laplace_depth_weights: null pointer");
     UNERF_REQUIRE(D >= 1 && R >= 0 && S >= 1 && S <= 256, "laplace_depth_weights: bad D/R/S");
     if (R == 0) return UNERF_OK;
-    LapDepthArgs a;
-    a.mu = density_mu; a.var = density_var; a.sbins = sbins; a.R = R; a.S = S;
-    UNERF_REQUIRE_SPACING(spacing); a.lin = spacing; a.s_near = unerf_spacing_of(near_plane, spacing); a.s_far = unerf_spacing_of(far_plane, spacing);
-    a.noise = noise; a.D = D; a.seed = seed; a.ray_offset = ray_offset; a.out = weights_out;
-    dim3 grid(blocks_for(R, 16)), block(256);
-    hipStream_t st = (hipStream_t)stream;
-    UNERF_DISPATCH_SPL(S, lap_depth_kernel, grid, block, 0, st, a);
-    return unerf_check_launch("laplace_depth_weights");
+    return lap_depth_impl(density_mu, density_var, sbins, R, S, near_plane, far_plane, spacing, noise, D, seed, ray_offset, nullptr,
+                          nullptr, weights_out, stream, "laplace_depth_weights");
 }
 
 // Several views in one launch: the stream of launch row r, sample k is seeded by (depth_seed[view], local * S + k), i.e. what
@@ -4981,17 +4951,8 @@ extern "C" int unerf_laplace_depth_weights_views(const float* density_mu, const 
     UNERF_REQUIRE(lap_views, "laplace_depth_weights_views: null lap_views (the depth seed of every view)");
     UNERF_REQUIRE(density_mu && density_var && sbins && weights_out, "laplace_depth_weights_views: null pointer");
     UNERF_REQUIRE(D >= 1 && S >= 1 && S <= 256, "laplace_depth_weights_views: bad D/S");
-    LapDepthArgs a;
-    a.mu = density_mu; a.var = density_var; a.sbins = sbins; a.R = R; a.S = S;
-    UNERF_REQUIRE_SPACING(spacing); a.lin = spacing; a.s_near = unerf_spacing_of(near_plane, spacing); a.s_far = unerf_spacing_of(far_plane, spacing);
-    a.noise = noise; a.D = D; a.seed = 0u; a.ray_offset = 0; a.out = weights_out;
-    LapDepthViews dv;
-    dv.div_hw = make_fastdiv((uint32_t)views->rays_per_view); dv.hw = (uint32_t)views->rays_per_view;
-    for (int v = 0; v < UNERF_NERF_MAX_VIEWS; ++v) dv.seed[v] = lap_views->depth_seed[v < views->n_views ? v : 0];
-    dim3 grid(blocks_for(R, 16)), block(256);
-    hipStream_t st = (hipStream_t)stream;
-    UNERF_DISPATCH_SPL(S, lap_depth_kernel_views, grid, block, 0, st, a, dv);
-    return unerf_check_launch("laplace_depth_weights_views");
+    return lap_depth_impl(density_mu, density_var, sbins, R, S, near_plane, far_plane, spacing, noise, D, 0u, 0, views, lap_views,
+                          weights_out, stream, "laplace_depth_weights_views");
 }
 
 // ======================================================================================

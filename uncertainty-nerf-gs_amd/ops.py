@@ -1001,17 +1001,13 @@ def weights_pdf_resample(density, sbins, u, near: float, far: float, histogram_p
     out = _scratch(workspace, f"pdf_bins_{m}", (R, m + 1), density.device)
     pd = torch.empty(R, 1, device=density.device, dtype=torch.float32) if want_prop_depth else None
     w = torch.empty(R, n, device=density.device, dtype=torch.float32) if want_weights else None
-    if views is not None:
-        vs = views.cstruct()
-        with _ctx(density.device):
-            _run(f"weights_pdf_resample_{n}", lambda: lib.unerf_weights_pdf_resample_views(
-                _p(density), _p(sbins), stride, R, n, near, far, spacing, _p(u), m, histogram_padding, eps, _p(out), _p(pd), _p(w),
-                _p(clip_minmax), C.byref(vs), chunk_rays, _stream()))
-        return out, pd, w
+    # how the clip rows are numbered: per view (*_views), else by the frame ray ray_offset + r
+    vs = None if views is None else views.cstruct()
+    fn, numbering = (lib.unerf_weights_pdf_resample, ray_offset) if views is None else (lib.unerf_weights_pdf_resample_views, C.byref(vs))
     with _ctx(density.device):
-        _run(f"weights_pdf_resample_{n}", lambda: lib.unerf_weights_pdf_resample(_p(density), _p(sbins), stride, R, n, near, far, spacing, _p(u), m,
-                                                histogram_padding, eps, _p(out), _p(pd), _p(w), _p(clip_minmax),
-                                                ray_offset, chunk_rays, _stream()))
+        _run(f"weights_pdf_resample_{n}", lambda: fn(
+            _p(density), _p(sbins), stride, R, n, near, far, spacing, _p(u), m, histogram_padding, eps, _p(out), _p(pd), _p(w),
+            _p(clip_minmax), numbering, chunk_rays, _stream()))
     return out, pd, w
 
 
@@ -1176,32 +1172,24 @@ def field_fwd(origins, directions, sbins, field: FieldDev, near: float, far: flo
     cs.sample_major = 1 if sample_major else 0
     cs.packed_out = 1 if packed else 0
     cs.overflow_flag = _p(nonfinite_flag, torch.int32)      # set by the f16 matrix kernels (either form) on operand overflow
+    # The entry point, and what its signature has where the others differ: the ray numbering in front of the parameters,
+    # the pre-gathered features behind them (the LAPLACE views form takes none), the keep masks behind the outputs.
+    km = None if keep_masks is None else keep_masks.cstruct(B)
+    name, feats, masks = "field_fwd", (features,), ()
     if views is not None and field.mode == _l.FIELD_LAPLACE:
-        vs = views.cstruct()
-        ls = (lap_views or LaplaceViews()).cstruct(views.n_views)
-        with _ctx(dev):
-            _run("field_fwd", lambda: lib.unerf_field_fwd_laplace_views(
-                _p(origins), _p(directions), _p(sbins), R, S, near, far, spacing, C.byref(vs), C.byref(ls), C.byref(cs),
-                _p(density), _p(rgb), _p(aux), _p(aux2), _stream()))
-        return density, rgb, aux, aux2
-    if views is not None:
+        vs, ls = views.cstruct(), (lap_views or LaplaceViews()).cstruct(views.n_views)
+        fn, numbering, feats = lib.unerf_field_fwd_laplace_views, (C.byref(vs), C.byref(ls)), ()
+    elif views is not None:
         vs = views.cstruct(field.seed)
-        km = None if keep_masks is None else keep_masks.cstruct(B)     # (refused by the entry point, by name)
-        with _ctx(dev):
-            _run("field_fwd", lambda: lib.unerf_field_fwd_views(
-                _p(origins), _p(directions), _p(sbins), R, S, near, far, spacing, C.byref(vs), C.byref(cs), _p(features),
-                _p(density), _p(rgb), _p(aux), _p(aux2), None if km is None else C.byref(km), _stream()))
-        return density, rgb, aux, aux2
-    if keep_masks is not None:
-        km = keep_masks.cstruct(B)
-        with _ctx(dev):
-            _run("field_fwd_masked", lambda: lib.unerf_field_fwd_masked(
-                _p(origins), _p(directions), _p(sbins), R, S, near, far, spacing, ray_offset, C.byref(cs), _p(features),
-                _p(density), _p(rgb), _p(aux), _p(aux2), C.byref(km), _stream()))
-        return density, rgb, aux, aux2
+        fn, numbering = lib.unerf_field_fwd_views, (C.byref(vs),)
+        masks = (None if km is None else C.byref(km),)     # (refused by the entry point, by name)
+    elif keep_masks is not None:
+        name, fn, numbering, masks = "field_fwd_masked", lib.unerf_field_fwd_masked, (ray_offset,), (C.byref(km),)
+    else:
+        fn, numbering = lib.unerf_field_fwd, (ray_offset,)
     with _ctx(dev):
-        _run("field_fwd", lambda: lib.unerf_field_fwd(_p(origins), _p(directions), _p(sbins), R, S, near, far, spacing, ray_offset,
-                                     C.byref(cs), _p(features), _p(density), _p(rgb), _p(aux), _p(aux2), _stream()))
+        _run(name, lambda: fn(_p(origins), _p(directions), _p(sbins), R, S, near, far, spacing, *numbering, C.byref(cs), *map(_p, feats),
+                              _p(density), _p(rgb), _p(aux), _p(aux2), *masks, _stream()))
     return density, rgb, aux, aux2
 
 
@@ -1213,19 +1201,17 @@ def laplace_depth_weights(density_mu, density_var, sbins, near: float, far: floa
     lib = _l.load()
     R, S = density_mu.shape
     out = torch.empty(R, S, device=density_mu.device, dtype=torch.float32)
-    if views is not None:
+    if views is not None:     # the streams are seeded per view and numbered inside each view's frame
         vs = views.cstruct()
         ls = (lap_views or LaplaceViews()).cstruct(views.n_views, seed)
-        with _ctx(out.device):
-            _run("laplace_depth_weights", lambda: lib.unerf_laplace_depth_weights_views(
-                _p(density_mu), _p(density_var), _p(sbins), R, S, near, far, spacing, _p(noise), D, C.byref(vs), C.byref(ls),
-                _p(out), _stream()))
-        return out
-    if lap_views is not None:
+        fn, numbering = lib.unerf_laplace_depth_weights_views, (C.byref(vs), C.byref(ls))
+    elif lap_views is not None:
         raise _l.UnerfError("laplace_depth_weights: lap_views goes with views=")
+    else:
+        fn, numbering = lib.unerf_laplace_depth_weights, (seed & 0xFFFFFFFF, ray_offset)
     with _ctx(out.device):
-        _run("laplace_depth_weights", lambda: lib.unerf_laplace_depth_weights(_p(density_mu), _p(density_var), _p(sbins), R, S, near, far,
-                                                 spacing, _p(noise), D, seed & 0xFFFFFFFF, ray_offset, _p(out), _stream()))
+        _run("laplace_depth_weights", lambda: fn(
+            _p(density_mu), _p(density_var), _p(sbins), R, S, near, far, spacing, _p(noise), D, *numbering, _p(out), _stream()))
     return out
 
 
@@ -1329,17 +1315,13 @@ def composite_var(density, rgb, sbins, near: float, far: float, beta=None, weigh
     B, R, S = _packed_shape(density, rgb)
     out = torch.empty(B, R, 8, device=rgb.device, dtype=torch.float32)
     bg_mode, bg_rgb = _background(background)
-    if views is not None:     # clip rows numbered per view, as weights_pdf_resample(views=...) filled them
-        vs = views.cstruct()
-        with _ctx(out.device):
-            _run("composite_var", lambda: lib.unerf_composite_var_views(
-                _p(density), _p(rgb), _p(beta), _p(weights_alt), _p(sbins), B, R, S, near, far, spacing, _p(clip_minmax),
-                C.byref(vs), chunk_rays, bg_mode, bg_rgb, _p(nonfinite_flag, torch.int32), _p(out), _stream()))
-        return out
+    # clip rows numbered per view, as weights_pdf_resample(views=...) filled them, else by the frame ray ray_offset + r
+    vs = None if views is None else views.cstruct()
+    fn, numbering = (lib.unerf_composite_var, ray_offset) if views is None else (lib.unerf_composite_var_views, C.byref(vs))
     with _ctx(out.device):
-        _run("composite_var", lambda: lib.unerf_composite_var(_p(density), _p(rgb), _p(beta), _p(weights_alt), _p(sbins), B, R, S, near,
-                                         far, spacing, _p(clip_minmax), ray_offset, chunk_rays, bg_mode, bg_rgb,
-                                         _p(nonfinite_flag, torch.int32), _p(out), _stream()))
+        _run("composite_var", lambda: fn(
+            _p(density), _p(rgb), _p(beta), _p(weights_alt), _p(sbins), B, R, S, near, far, spacing, _p(clip_minmax),
+            numbering, chunk_rays, bg_mode, bg_rgb, _p(nonfinite_flag, torch.int32), _p(out), _stream()))
     return out
 
 
@@ -1353,18 +1335,12 @@ def composite_moments(density, rgb, sbins, near: float, far: float, clip_minmax=
     mean = torch.empty(R, 8, device=rgb.device, dtype=torch.float32)
     var = torch.empty(R, 8, device=rgb.device, dtype=torch.float32)
     bg_mode, bg_rgb = _background(background)
-    if views is not None:
-        vs = views.cstruct()
-        with _ctx(mean.device):
-            _run("composite_moments", lambda: lib.unerf_composite_moments_views(
-                _p(density), _p(rgb), _p(sbins), B, R, S, near, far, spacing, _p(clip_minmax), C.byref(vs), chunk_rays, bg_mode,
-                bg_rgb, _p(nonfinite_flag, torch.int32), _p(mean), _p(var), _stream()))
-        return mean, var
+    vs = None if views is None else views.cstruct()     # clip rows: as composite_var
+    fn, numbering = (lib.unerf_composite_moments, ray_offset) if views is None else (lib.unerf_composite_moments_views, C.byref(vs))
     with _ctx(mean.device):
-        _run("composite_moments", lambda: lib.unerf_composite_moments(_p(density), _p(rgb), _p(sbins), B, R, S, near, far,
-                                                                      spacing, _p(clip_minmax), ray_offset, chunk_rays,
-                                                                      bg_mode, bg_rgb, _p(nonfinite_flag, torch.int32),
-                                                                      _p(mean), _p(var), _stream()))
+        _run("composite_moments", lambda: fn(
+            _p(density), _p(rgb), _p(sbins), B, R, S, near, far, spacing, _p(clip_minmax), numbering, chunk_rays, bg_mode,
+            bg_rgb, _p(nonfinite_flag, torch.int32), _p(mean), _p(var), _stream()))
     return mean, var
 
 
