@@ -4,8 +4,8 @@ In scope, all reached through unerf_field_fwd / unerf_field_fwd_masked (csrc/une
 field_kernel<ACTIVE | MCDROPOUT> (VALU, one wave per 64 samples), field_kernel_mfma<ACTIVE | MCDROPOUT> (exact fp32 matrix
 kernel; fused lookup and pre-gathered features, all three grid layouts), field_kernel_mfma16 in its split form ("f16x2":
 hi*hi + hi*lo + lo*hi) and its single-product form ("f16"), the three (SITES, DROP) forms, and the explicit-mask (KeepArgs)
-instantiations of each.  OUT of scope: the LAPLACE kernels (their E[x^2] - E[x]^2 outputs need a bound of their own),
-field_kernel_generic, the several-views kernels (tests/test_gpu_nerf_view_batch.py compares them bit for bit with single
+instantiations of each.  The LAPLACE kernels and the GGN fit have a module of their own, tests/laplace_cases.py (their
+E[x^2] - E[x]^2 outputs carry a bound that scales with the sample's own second moment).  OUT of scope: field_kernel_generic, the several-views kernels (tests/test_gpu_nerf_view_batch.py compares them bit for bit with single
 launches) and the R * S >= 2^31 addressing, which is out of reach at test size.
 
 Nets (L = 16, 64 / 64 / 15 / 2, log2T 8 .. 12, a non-zero appearance embedding): the torch hash table, the tcnn layout with
