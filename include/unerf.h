@@ -1029,6 +1029,36 @@ int unerf_splat_normalize_outputs_batch(float* img, int stride, int ch, const fl
 int unerf_splat_depth_sqdiff_batch(const float* xys, const float* depths, const float* depth_img, int stride, int ch, int B,
                                    int H, int W, int64_t N, float* sq_diff_out, void* stream);
 
+/* ------------------------------------------------- splat pose gradient --
+ * d mean_c(rgb[y,x]) / d camera_to_worlds of a splat frame per pixel (the quantity of the reference's
+ * scripts/estimate_gradient_pose_6dof.py:128-139, which itself serves nerfacto models only), in forward mode: the pose reaches
+ * a pixel only through each splat's projected q = (u, v, conic a, conic b, conic c, compensation) -- the SH view directions
+ * are detached (activesplatfacto_model.py:243); near-plane cull, radii, tile lists, skipped pairs and stops are held fixed.
+ *
+ * unerf_splat_pose_tangents: tangents [N, UNERF_SPLAT_POSE_Q, 12] <- d q / d V[r][c] (k = 4 r + c over the 3 x 4 world-to-camera
+ * rows `viewmat_host`), through the arithmetic of unerf_splat_project* behind its `cov3d` [N,6] output.  Splats with
+ * radii == 0 get zeros.  The fov clamp passes no x (y) sensitivity where it is active, compensation has derivative 0 where
+ * det_orig <= 0.  288 bytes per splat; 16-byte aligned. */
+#define UNERF_SPLAT_POSE_Q 6
+int unerf_splat_pose_tangents(const float* means3d, const float* cov3d, const int32_t* radii, int64_t N,
+                              const float* viewmat_host, float fx, float fy, float cx, float cy, int H, int W,
+                              float clip_thresh, float* tangents, void* stream);
+
+/* The walk of unerf_splat_rasterize (same lists, same skip and stop decisions, C = 3, flags as there) carrying the 12 tangents
+ * of T and of the three colour sums; a tile's list is staged UNERF_SPLAT_POSE_GRAD_BATCH splats at a time.
+ * compensation [N] or NULL: given ("antialiased": opacities = sigmoid(.) * compensation) alpha also moves with the
+ * compensation's tangent; NULL ("classic") the tangents' last 12 floats per splat are not read.
+ * background [3] DEVICE or NULL (zeros).  c2w_host: the 3 x 4 camera-to-world rows V was made from
+ * (V = [R'^T | -R'^T t], R' = R diag(1,-1,-1), the reference's transposition :184-195) -> out_grad [H W, 3, 4] = ds / d c2w;
+ * NULL -> out_grad [H W, 12] = ds / dV.  s = mean_c min(pix_c + T bg_c, 1): a channel at or above 1 contributes 0; alpha on its
+ * 0.999 clamp has derivative 0.  out_rgb [H W,3] (the clamped colour) and final_T [H W] may be NULL.
+ * No atomics, no division by 1 - alpha: two calls return the same bits. */
+#define UNERF_SPLAT_POSE_GRAD_BATCH 128
+int unerf_splat_pose_grad(const int32_t* gaussian_ids_sorted, const int32_t* tile_bins, const float* xys,
+                          const float* conics, const float* colors, const float* opacities, const float* compensation,
+                          const float* tangents, const float* background, const float* c2w_host, int H, int W,
+                          int block_width, int flags, float* out_grad, float* out_rgb, float* final_T, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

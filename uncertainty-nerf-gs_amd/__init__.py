@@ -8,6 +8,8 @@ Layout
   fields.py / models.py / ensemble.py
               host-side mirrors of the reference's Field / Model / EnsemblePipeline surface
   metrics.py  ause / auce / psnr / nll (parity metrics)
-  posegrad.py per-pixel camera-pose gradients of a frame, exported as the reference's pose-sensitivity script writes them
+  splat.py    frame-level splat pipelines: active_splatfacto_outputs(_batch), pose_gradient_camera (the splat pose gradient)
+  posegrad.py per-pixel camera-pose gradients of a frame (nerfacto and splat models), exported as the reference's
+              pose-sensitivity script writes them
 """
 __version__ = "0.1.0"

@@ -2325,3 +2325,336 @@ extern "C" int unerf_splat_depth_sqdiff_batch(const float* xys, const float* dep
                        depth_img, stride, ch, H, W, N, sq_diff_out);
     return unerf_check_launch("splat_depth_sqdiff_batch");
 }
+
+// ======================================================================================
+// per-pixel camera-pose gradient of a frame, forward mode
+// ======================================================================================
+// s = mean_c clamp(pix_c + T_end bg_c, max = 1) of a pixel depends on the pose only through each splat's projected
+// q = (u, v, conic a, b, c, compensation): the SH view directions are detached (activesplatfacto_model.py:243) and radii,
+// lists, skips and stops are locally constant.  splat_pose_tangents_kernel writes dq / dV for the 12 entries of V[:3,:4];
+// splat_pose_grad_kernel walks the tile lists as raster_kernel does and carries dT[12], dpix[3][12] next to T, pix[3].
+struct PoseTanArgs {
+    const float* means;
+    const float* cov3d;
+    const int32_t* radii;
+    int64_t N;
+    float V[12];
+    float fx, fy, cx, cy;
+    int H, W;
+    float clip;
+    float* tan;
+};
+
+// the arithmetic of project_kernel behind `cov3d`, with the tangent of every intermediate for a unit change of V[r][c]
+__global__ __launch_bounds__(256) void splat_pose_tangents_kernel(PoseTanArgs a) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= a.N) return;
+    float out[UNERF_SPLAT_POSE_Q][12];
+#pragma unroll
+    for (int q = 0; q < UNERF_SPLAT_POSE_Q; ++q)
+#pragma unroll
+        for (int k = 0; k < 12; ++k) out[q][k] = 0.f;
+    float4* row = reinterpret_cast<float4*>(a.tan + i * (int64_t)(UNERF_SPLAT_POSE_Q * 12));
+    const float* V = a.V;
+    const float m[4] = {a.means[i * 3], a.means[i * 3 + 1], a.means[i * 3 + 2], 1.f};
+    const float tx = ((V[0] * m[0] + V[1] * m[1]) + V[2] * m[2]) + V[3];
+    const float ty = ((V[4] * m[0] + V[5] * m[1]) + V[6] * m[2]) + V[7];
+    const float tz = ((V[8] * m[0] + V[9] * m[1]) + V[10] * m[2]) + V[11];
+    if (a.radii[i] != 0 && !(tz <= a.clip)) {
+        const float* cv = a.cov3d + i * 6;
+        const float C3[9] = {cv[0], cv[1], cv[2], cv[1], cv[3], cv[4], cv[2], cv[4], cv[5]};
+        const float lim_x = 1.3f * (0.5f * (float)a.W / a.fx), lim_y = 1.3f * (0.5f * (float)a.H / a.fy);
+        const float rx = tx / tz, ry = ty / tz;
+        // torch.clamp's derivative: 1 on [-lim, lim] (the ends included), 0 outside
+        const bool clamp_x = rx > lim_x || rx < -lim_x, clamp_y = ry > lim_y || ry < -lim_y;
+        const float cxr = fminf(lim_x, fmaxf(-lim_x, rx)), cyr = fminf(lim_y, fmaxf(-lim_y, ry));
+        const float ex = tz * cxr, ey = tz * cyr;
+        const float rz = 1.f / tz, rz2 = rz * rz;
+        const float J00 = a.fx * rz, J02 = (-a.fx * ex) * rz2, J11 = a.fy * rz, J12 = (-a.fy * ey) * rz2;
+        float T0[3], T1[3], TV0[3], TV1[3];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            T0[c] = J00 * V[c] + J02 * V[8 + c];
+            T1[c] = J11 * V[4 + c] + J12 * V[8 + c];
+        }
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            TV0[c] = (T0[0] * C3[c] + T0[1] * C3[3 + c]) + T0[2] * C3[6 + c];
+            TV1[c] = (T1[0] * C3[c] + T1[1] * C3[3 + c]) + T1[2] * C3[6 + c];
+        }
+        const float c00 = (TV0[0] * T0[0] + TV0[1] * T0[1]) + TV0[2] * T0[2];
+        const float c01 = (TV0[0] * T1[0] + TV0[1] * T1[1]) + TV0[2] * T1[2];
+        const float c11 = (TV1[0] * T1[0] + TV1[1] * T1[1]) + TV1[2] * T1[2];
+        const float det_orig = c00 * c11 - c01 * c01;
+        const float ca = c00 + 0.3f, cb = c01, cc = c11 + 0.3f;
+        const float det = ca * cc - cb * cb;
+        const float inv_det = 1.f / det, inv_det2 = inv_det * inv_det;
+        const float ratio = det_orig / det;
+        const float comp = sqrtf(fmaxf(0.f, ratio));
+        const bool comp_live = det_orig > 0.f && ratio > 0.f;
+        const float rw = 1.f / (tz + 1e-6f), rw2 = rw * rw;
+#pragma unroll
+        for (int k = 0; k < 12; ++k) {
+            const int r = k >> 2, c = k & 3;           // the entry V[r][c] moves
+            const float dtx = r == 0 ? m[c] : 0.f, dty = r == 1 ? m[c] : 0.f, dtz = r == 2 ? m[c] : 0.f;
+            const float dex = clamp_x ? dtz * cxr : dtx, dey = clamp_y ? dtz * cyr : dty;
+            const float drz = -rz2 * dtz, drz2 = 2.f * rz * drz;
+            const float dJ00 = a.fx * drz, dJ11 = a.fy * drz;
+            const float dJ02 = -a.fx * (dex * rz2 + ex * drz2), dJ12 = -a.fy * (dey * rz2 + ey * drz2);
+            float dT0[3], dT1[3];
+#pragma unroll
+            for (int j = 0; j < 3; ++j) {
+                dT0[j] = dJ00 * V[j] + dJ02 * V[8 + j];
+                dT1[j] = dJ11 * V[4 + j] + dJ12 * V[8 + j];
+                if (c == j) {                          // (c == 3: the translation column enters through t only)
+                    if (r == 0) dT0[j] += J00;
+                    if (r == 1) dT1[j] += J11;
+                    if (r == 2) { dT0[j] += J02; dT1[j] += J12; }
+                }
+            }
+            const float dc00 = 2.f * ((TV0[0] * dT0[0] + TV0[1] * dT0[1]) + TV0[2] * dT0[2]);
+            const float dc11 = 2.f * ((TV1[0] * dT1[0] + TV1[1] * dT1[1]) + TV1[2] * dT1[2]);
+            const float dc01 = ((TV1[0] * dT0[0] + TV1[1] * dT0[1]) + TV1[2] * dT0[2])
+                             + ((TV0[0] * dT1[0] + TV0[1] * dT1[1]) + TV0[2] * dT1[2]);
+            const float ddet_orig = (dc00 * c11 + c00 * dc11) - 2.f * c01 * dc01;
+            const float ddet = (dc00 * cc + ca * dc11) - 2.f * cb * dc01;
+            out[0][k] = a.fx * (dtx * rw - tx * rw2 * dtz);
+            out[1][k] = a.fy * (dty * rw - ty * rw2 * dtz);
+            out[2][k] = dc11 * inv_det - cc * ddet * inv_det2;
+            out[3][k] = cb * ddet * inv_det2 - dc01 * inv_det;
+            out[4][k] = dc00 * inv_det - ca * ddet * inv_det2;
+            out[5][k] = comp_live ? (0.5f / comp) * (ddet_orig * inv_det - det_orig * ddet * inv_det2) : 0.f;
+        }
+    }
+#pragma unroll
+    for (int q = 0; q < UNERF_SPLAT_POSE_Q; ++q)
+#pragma unroll
+        for (int w = 0; w < 3; ++w) row[q * 3 + w] = make_float4(out[q][4 * w], out[q][4 * w + 1], out[q][4 * w + 2], out[q][4 * w + 3]);
+}
+
+extern "C" int unerf_splat_pose_tangents(const float* means3d, const float* cov3d, const int32_t* radii, int64_t N,
+                                         const float* viewmat_host, float fx, float fy, float cx, float cy, int H, int W,
+                                         float clip_thresh, float* tangents, void* stream) {
+    UNERF_REQUIRE(viewmat_host && (N <= 0 || (means3d && cov3d && radii && tangents)), "splat_pose_tangents: null pointer");
+    UNERF_REQUIRE(H > 0 && W > 0 && N >= 0, "splat_pose_tangents: bad H/W/N");
+    UNERF_REQUIRE((reinterpret_cast<uintptr_t>(tangents) & 15) == 0, "splat_pose_tangents: tangents must be 16-byte aligned");
+    if (N == 0) return UNERF_OK;
+    PoseTanArgs a;
+    a.means = means3d; a.cov3d = cov3d; a.radii = radii; a.N = N;
+    for (int k = 0; k < 12; ++k) a.V[k] = viewmat_host[k];
+    a.fx = fx; a.fy = fy; a.cx = cx; a.cy = cy; a.H = H; a.W = W; a.clip = clip_thresh; a.tan = tangents;
+    hipLaunchKernelGGL(splat_pose_tangents_kernel, dim3(blocks_for(N, 256)), dim3(256), 0, (hipStream_t)stream, a);
+    return unerf_check_launch("splat_pose_tangents");
+}
+
+struct PoseGradArgs {
+    const int32_t* ids;
+    const int32_t* bins;
+    const float* xys;
+    const float* conics;
+    const float* colors;
+    const float* opac;
+    const float* comp;
+    const float* tan;
+    const float* bg;
+    int has_c2w;
+    float c2w[12];
+    int H, W, bw;
+    int cull;
+    float* grad;
+    float* rgb;
+    float* finalT;
+};
+
+// AA ("antialiased"): the staged opacity is sigmoid(.) comp, so alpha carries comp's tangent as well.
+// A staged record is PG_REC4 16-byte words: [x, y, o, a | b, c, r, g | b, 1 / comp, -, - | the tangents of x, y, a, b, c (, comp),
+// 12 floats each]; PG_BATCH records of the antialiased kind are 42 KiB, with the lists 43.6 KiB: two (and three) workgroups of a
+// CU's 160 KiB.
+template <bool AA>
+__global__ __launch_bounds__(256) void splat_pose_grad_kernel(PoseGradArgs a) {
+    constexpr int PG = UNERF_SPLAT_POSE_GRAD_BATCH;
+    constexpr int NT = AA ? 6 : 5;               // tangent 12-vectors per splat
+    constexpr int TQ = 3 * NT;                   // ... in 16-byte words
+    constexpr int REC4 = 3 + TQ;
+    __shared__ float4 s_rec[PG * REC4];
+    __shared__ int32_t s_gid[PG];
+    __shared__ uint8_t s_mask[PG];
+    __shared__ uint16_t s_list[4][PG];
+    const int bw = a.bw;
+    const int tbx = (a.W + bw - 1) / bw;
+    const int bx = blockIdx.x, by = blockIdx.y;
+    const int tile = by * tbx + bx;
+    const int tr = threadIdx.x;
+    // raster_kernel's thread-to-pixel mapping: a wave is one 8 x 8 quadrant of a 16-wide tile
+    const int ly = bw == 16 ? 8 * (tr >> 7) + ((tr & 63) >> 3) : tr / bw;
+    const int lx = bw == 16 ? 8 * ((tr >> 6) & 1) + (tr & 7) : tr - (tr / bw) * bw;
+    const int i = by * bw + ly, j = bx * bw + lx;
+    const float px = (float)j + 0.5f, py = (float)i + 0.5f;
+    const bool inside = (ly < bw) && (i < a.H) && (j < a.W);
+    const int64_t p = (int64_t)i * a.W + j;
+    bool done = !inside;
+    const int r0 = a.bins[tile * 2], r1 = a.bins[tile * 2 + 1];
+    const int nbatch = (r1 - r0 + PG - 1) / PG;
+    const bool cull = a.cull && bw == 16;
+    const int wv = __builtin_amdgcn_readfirstlane(tr >> 6), lane = tr & 63;
+    const float tile_x0 = (float)(bx * bw), tile_y0 = (float)(by * bw);
+    float T = 1.f, pix[3] = {0.f, 0.f, 0.f};
+    float dT[12], dpix[3][12];
+#pragma unroll
+    for (int k = 0; k < 12; ++k) { dT[k] = 0.f; dpix[0][k] = 0.f; dpix[1][k] = 0.f; dpix[2][k] = 0.f; }
+    for (int b = 0; b < nbatch; ++b) {
+        const int start = r0 + PG * b;
+        if (__syncthreads_count(done ? 1 : 0) >= 256) break;
+        const int bsz = min(PG, r1 - start);
+        if (tr < bsz) {
+            const int g = a.ids[start + tr];
+            const float x = a.xys[g * 2], y = a.xys[g * 2 + 1], op = a.opac[g];
+            const float ca = a.conics[g * 3], cb = a.conics[g * 3 + 1], cc = a.conics[g * 3 + 2];
+            const float* crow = a.colors + (int64_t)g * 3;
+            s_rec[tr * REC4] = make_float4(x, y, op, ca);
+            s_rec[tr * REC4 + 1] = make_float4(cb, cc, crow[0], crow[1]);
+            s_rec[tr * REC4 + 2] = make_float4(crow[2], AA ? 1.f / a.comp[g] : 1.f, 0.f, 0.f);
+            s_gid[tr] = g;
+            if (cull) s_mask[tr] = (uint8_t)raster_quad_mask(x, y, op, ca, cb, cc, tile_x0, tile_y0);
+        }
+        __syncthreads();
+        // the tangent rows, 16 bytes per thread and trip (a row is UNERF_SPLAT_POSE_Q * 12 floats; comp's 12 are its last)
+        for (int w = tr; w < bsz * TQ; w += 256) {
+            const int rec = w / TQ, q = w - rec * TQ;
+            s_rec[rec * REC4 + 3 + q] = reinterpret_cast<const float4*>(a.tan + (int64_t)s_gid[rec] * (UNERF_SPLAT_POSE_Q * 12))[q];
+        }
+        __syncthreads();
+        int n_mine = bsz;
+        if (cull) {   // this wave's (order-preserving) list of the staged splats its quadrant can see
+            n_mine = 0;
+#pragma unroll
+            for (int ch = 0; ch < PG / 64; ++ch) {
+                const int t = ch * 64 + lane;
+                const bool need = t < bsz && ((s_mask[t] >> wv) & 1u);
+                const uint64_t mm = __builtin_amdgcn_ballot_w64(need);
+                if (need) s_list[wv][n_mine + __builtin_popcountll(mm & ((1ull << lane) - 1ull))] = (uint16_t)t;
+                n_mine += __builtin_popcountll(mm);
+            }
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+        }
+        for (int k0 = 0; k0 < n_mine; ++k0) {
+            if (__builtin_amdgcn_ballot_w64(!done) == 0ull) break;     // uniform: every pixel of this wave has finished
+            const int t = cull ? (int)s_list[wv][k0] : k0;
+            const float4 h0 = s_rec[t * REC4], h1 = s_rec[t * REC4 + 1], h2 = s_rec[t * REC4 + 2];
+            bool blend = false;
+            float alpha = 0.f, nT = T, dx = 0.f, dy = 0.f;
+            bool clamped = false;
+            if (!done) {
+                // raster_kernel's decisions, on its expressions
+                dx = h0.x - px; dy = h0.y - py;
+                const float op = h0.z, ca = h0.w, cb = h1.x, cc = h1.y;
+                const float sigma = 0.5f * (ca * dx * dx + cc * dy * dy) + cb * dx * dy;
+                const float raw = op * __expf(-sigma);
+                alpha = fminf(0.999f, raw);
+                clamped = raw > 0.999f;
+                if (!(sigma < 0.f || alpha < 1.f / 255.f)) {
+                    nT = T * (1.f - alpha);
+                    if (nT <= 1e-4f) done = true;
+                    else blend = true;
+                }
+            }
+            if (__builtin_amdgcn_ballot_w64(blend) == 0ull) continue;  // uniform: nobody needs this splat's tangents
+            const float ca = h0.w, cb = h1.x, cc = h1.y;
+            const float wx = ca * dx + cb * dy, wy = cc * dy + cb * dx;
+            const float wa = 0.5f * dx * dx, wb = dx * dy, wc = 0.5f * dy * dy;
+            const float col[3] = {h1.z, h1.w, h2.x};
+            const float om = 1.f - alpha;
+            const float4* tq = &s_rec[t * REC4 + 3];
+#pragma unroll
+            for (int w = 0; w < 3; ++w) {
+                const float4 vx = tq[w], vy = tq[3 + w], va = tq[6 + w], vb = tq[9 + w], vc = tq[12 + w];
+                const float ex[4] = {vx.x, vx.y, vx.z, vx.w}, ey[4] = {vy.x, vy.y, vy.z, vy.w};
+                const float ea[4] = {va.x, va.y, va.z, va.w}, eb[4] = {vb.x, vb.y, vb.z, vb.w}, ec[4] = {vc.x, vc.y, vc.z, vc.w};
+                float eo[4] = {0.f, 0.f, 0.f, 0.f};
+                if (AA) { const float4 vo = tq[15 + w]; eo[0] = vo.x; eo[1] = vo.y; eo[2] = vo.z; eo[3] = vo.w; }
+                if (blend) {
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        const int k = 4 * w + e;
+                        const float sd = (((wx * ex[e] + wy * ey[e]) + wa * ea[e]) + wb * eb[e]) + wc * ec[e];
+                        const float ad = clamped ? 0.f : alpha * (h2.y * eo[e] - sd);
+                        const float wk = ad * T + alpha * dT[k];
+                        dpix[0][k] += col[0] * wk;
+                        dpix[1][k] += col[1] * wk;
+                        dpix[2][k] += col[2] * wk;
+                        dT[k] = dT[k] * om - T * ad;
+                    }
+                }
+            }
+            if (blend) {
+                const float vis = alpha * T;
+                pix[0] += col[0] * vis; pix[1] += col[1] * vis; pix[2] += col[2] * vis;
+                T = nT;
+            }
+        }
+    }
+    if (!inside) return;
+    float live[3], gV[12];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const float bgc = a.bg ? a.bg[c] : 0.f;
+        const float v = pix[c] + T * bgc;
+        live[c] = v < 1.f ? 1.f : 0.f;           // clamp(max = 1): a saturated channel contributes nothing
+        if (a.rgb) a.rgb[p * 3 + c] = fminf(v, 1.f);
+    }
+    if (a.finalT) a.finalT[p] = T;
+#pragma unroll
+    for (int k = 0; k < 12; ++k) {
+        float s = 0.f;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) s += live[c] * (dpix[c][k] + (a.bg ? a.bg[c] : 0.f) * dT[k]);
+        gV[k] = s * (1.f / 3.f);
+    }
+    float o[12];
+    if (a.has_c2w) {
+        // V = [R'^T | -R'^T t], R' = R diag(1, -1, -1):  ds/dt = -R' g_t,  ds/dR[r][c] = F_cc (G[c][r] - g_t[c] t[r])
+#pragma unroll
+        for (int r = 0; r < 3; ++r) {
+            const float tr_ = a.c2w[r * 4 + 3];
+            float st = 0.f;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                const float F = c == 0 ? 1.f : -1.f;
+                o[r * 4 + c] = F * (gV[c * 4 + r] - gV[c * 4 + 3] * tr_);
+                st += (F * a.c2w[r * 4 + c]) * gV[c * 4 + 3];
+            }
+            o[r * 4 + 3] = -st;
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < 12; ++k) o[k] = gV[k];
+    }
+    float4* orow = reinterpret_cast<float4*>(a.grad + p * 12);
+#pragma unroll
+    for (int w = 0; w < 3; ++w) orow[w] = make_float4(o[4 * w], o[4 * w + 1], o[4 * w + 2], o[4 * w + 3]);
+}
+
+extern "C" int unerf_splat_pose_grad(const int32_t* gaussian_ids_sorted, const int32_t* tile_bins, const float* xys,
+                                     const float* conics, const float* colors, const float* opacities,
+                                     const float* compensation, const float* tangents, const float* background,
+                                     const float* c2w_host, int H, int W, int block_width, int flags, float* out_grad,
+                                     float* out_rgb, float* final_T, void* stream) {
+    UNERF_REQUIRE(gaussian_ids_sorted && tile_bins && xys && conics && colors && opacities && tangents && out_grad,
+                  "splat_pose_grad: null pointer");
+    UNERF_REQUIRE(block_width >= 1 && block_width <= 16 && H > 0 && W > 0, "splat_pose_grad: bad block_width/H/W");
+    UNERF_REQUIRE((flags & ~UNERF_RASTER_NO_CULL) == 0, "splat_pose_grad: unknown flags %d", flags);
+    UNERF_REQUIRE((reinterpret_cast<uintptr_t>(tangents) & 15) == 0 && (reinterpret_cast<uintptr_t>(out_grad) & 15) == 0,
+                  "splat_pose_grad: tangents and out_grad must be 16-byte aligned");
+    PoseGradArgs a;
+    a.ids = gaussian_ids_sorted; a.bins = tile_bins; a.xys = xys; a.conics = conics; a.colors = colors; a.opac = opacities;
+    a.comp = compensation; a.tan = tangents; a.bg = background;
+    a.has_c2w = c2w_host ? 1 : 0;
+    for (int k = 0; k < 12; ++k) a.c2w[k] = c2w_host ? c2w_host[k] : 0.f;
+    a.H = H; a.W = W; a.bw = block_width; a.cull = (flags & UNERF_RASTER_NO_CULL) ? 0 : 1;
+    a.grad = out_grad; a.rgb = out_rgb; a.finalT = final_T;
+    const dim3 grid((W + block_width - 1) / block_width, (H + block_width - 1) / block_width), block(256);
+    if (compensation) hipLaunchKernelGGL(splat_pose_grad_kernel<true>, grid, block, 0, (hipStream_t)stream, a);
+    else hipLaunchKernelGGL(splat_pose_grad_kernel<false>, grid, block, 0, (hipStream_t)stream, a);
+    return unerf_check_launch("splat_pose_grad");
+}

@@ -285,6 +285,8 @@ SIGNATURES = {
                                          _vp, _vp]),
     "unerf_splat_normalize_outputs_batch": (_i, [_vp, _i, _i, _vp, _i, _i64, _vp, _vp, _vp, _i, _vp, _vp, _vp]),
     "unerf_splat_depth_sqdiff_batch": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i64, _vp, _vp]),
+    "unerf_splat_pose_tangents": (_i, [_vp, _vp, _vp, _i64, _fp, _f, _f, _f, _f, _i, _i, _f, _vp, _vp]),
+    "unerf_splat_pose_grad": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _fp, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
 }
 # include/unerf.h: UNERF_METRICS_* (flags of unerf_image_metrics, layout of its row of float64 results)
 METRICS_AUSE, METRICS_AUCE, METRICS_NLL, METRICS_SSIM = 1, 2, 4, 8
@@ -301,6 +303,8 @@ ENS_ALEA_STATS = (ENS_ALEA_CMEAN, ENS_EPI_ALEA, ENS_EPI_ALEA_SQRT)
 SPLAT_MAX_VIEWS = 16                              # include/unerf.h: UNERF_SPLAT_MAX_VIEWS
 SPLAT_VIEW_FLOATS = 19                            # include/unerf.h: UNERF_SPLAT_VIEW_FLOATS
 SPLAT_BATCH_MAX_TILES = 11999                     # include/unerf.h: UNERF_SPLAT_BATCH_MAX_TILES
+SPLAT_POSE_Q = 6                                  # include/unerf.h: UNERF_SPLAT_POSE_Q
+SPLAT_POSE_GRAD_BATCH = 128                       # include/unerf.h: UNERF_SPLAT_POSE_GRAD_BATCH
 
 _lib: Optional[C.CDLL] = None
 

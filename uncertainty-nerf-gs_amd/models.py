@@ -1028,6 +1028,22 @@ class SplatfactoModel(nn.Module, _ImageMetrics):
         return self.get_outputs(camera)
 
     @torch.no_grad()
+    def get_pose_gradients_for_camera(self, camera, want_rgb: bool = False):
+        """d mean_c(rgb[y, x]) / d camera_to_worlds for every pixel of one camera -> [H,W,3,4] float32 on the device (with
+        want_rgb also the colour the gradient kernel blended, [H,W,3]): the per-pixel quantity of the reference's
+        estimate_gradient_pose_6dof.py:128-139, from splat.pose_gradient_camera (tile lists, skips and stops held fixed; the
+        crop box set by set_crop / get_outputs_for_camera is honoured).  One PERSPECTIVE camera, as get_outputs."""
+        c2w, cam = _camera_args(camera, lens=False)
+        n = min(self.step // self.config.sh_degree_interval, self.config.sh_degree) if self.config.sh_degree > 0 else 0
+        gp = {k: v.detach() for k, v in self.gauss_params.items()}
+        crop_ids = None
+        if self.crop_box is not None and not self.training:
+            crop_ids = self.crop_box.within(gp["means"]).squeeze()
+        return splat.pose_gradient_camera(gp, c2w, background=self.background_color.to(gp["means"].device), sh_degree=n,
+                                          rasterize_mode=self.config.rasterize_mode, crop_ids=crop_ids,
+                                          config_sh_degree=self.config.sh_degree, want_rgb=want_rgb, **cam)
+
+    @torch.no_grad()
     def get_outputs_for_cameras(self, cameras, obb_box=None, max_views: int = 8) -> List[Dict[str, Optional[torch.Tensor]]]:
         """get_outputs_for_camera for every camera of a batch (camera_to_worlds [B,3,4]; fx, fy, cx, cy scalar or one per
         camera; one image size), rendered max_views cameras per call (splat.active_splatfacto_outputs_batch): element i

@@ -1959,6 +1959,42 @@ def splat_rasterize(gaussian_ids_sorted, tile_bins, xys, conics, colors, opaciti
     return out, fT, fidx
 
 
+def splat_pose_tangents(means3d, cov3d, radii, viewmat: torch.Tensor, fx, fy, cx, cy, H: int, W: int,
+                        clip_thresh: float = 0.01, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """-> tangents [N, 6, 12]: d (u, v, conic a, b, c, compensation) / d viewmat[:3,:4] (k = 4 row + column) of every splat the
+    projection left alive (radii > 0; zeros otherwise), through the arithmetic of splat_project behind its cov3d [N,6]."""
+    lib = _l.load()
+    N, dev = means3d.shape[0], means3d.device
+    tan = torch.empty(N, _l.SPLAT_POSE_Q, 12, device=dev) if out is None else out
+    with _ctx(dev):
+        _run("splat_pose_tangents", lambda: lib.unerf_splat_pose_tangents(
+            _p(means3d), _p(cov3d), _p(radii, torch.int32), N, _host12(viewmat), fx, fy, cx, cy, H, W, clip_thresh, _p(tan),
+            _stream()))
+    return tan
+
+
+def splat_pose_grad(gaussian_ids_sorted, tile_bins, xys, conics, colors, opacities, tangents, H: int, W: int,
+                    background: Optional[torch.Tensor] = None, compensation: Optional[torch.Tensor] = None,
+                    c2w: Optional[torch.Tensor] = None, block_width: int = 16, cull: bool = True, want_rgb: bool = False,
+                    want_final_T: bool = False, out: Optional[torch.Tensor] = None):
+    """The rasteriser's walk in forward mode: colors [N,3], tangents [N,6,12] (splat_pose_tangents) -> (grad, rgb | None,
+    final_T | None).  c2w [3,4] given: grad [H,W,3,4] = d mean_c(rgb) / d c2w; None: grad [H,W,12] = d mean_c(rgb) / d viewmat.
+    compensation [N] given: "antialiased" (opacities already hold the factor); None: "classic".  rgb is clamped at 1."""
+    lib = _l.load()
+    dev = xys.device
+    grad = (torch.empty(H, W, 3, 4, device=dev) if c2w is not None else torch.empty(H, W, 12, device=dev)) if out is None else out
+    rgb = torch.empty(H, W, 3, device=dev) if want_rgb else None
+    fT = torch.empty(H, W, device=dev) if want_final_T else None
+    if gaussian_ids_sorted.numel() == 0:
+        gaussian_ids_sorted = torch.zeros(1, device=dev, dtype=torch.int32)
+    with _ctx(dev):
+        _run("splat_pose_grad", lambda: lib.unerf_splat_pose_grad(
+            _p(gaussian_ids_sorted, torch.int32), _p(tile_bins, torch.int32), _p(xys), _p(conics), _p(colors), _p(opacities),
+            _p(compensation), _p(tangents), _p(background), None if c2w is None else _host12(c2w), H, W, block_width,
+            0 if cull else _l.RASTER_NO_CULL, _p(grad), _p(rgb), _p(fT), _stream()))
+    return grad, rgb, fT
+
+
 def splat_alpha_normalize(img: torch.Tensor, ch: int, final_T: torch.Tensor, max_ready: Optional[torch.Tensor] = None) -> None:
     """in place on channel `ch` of img [H,W,C].  max_ready: the device float a splat_rasterize(chan_max=(ch, float)) call
     that produced img left the channel's maximum in; None: the maximum is computed here."""

@@ -176,10 +176,10 @@ def _build() -> Dict[str, Any]:
         @torch.no_grad()
         def get_pose_gradients_for_camera(self, camera, **kw):
             """d mean_c(rgb) / d camera_to_worlds per pixel, [H,W,3,4] (estimate_gradient_pose_6dof.py:128-139); the
-            mc-dropout, Laplace and splat mirrors raise NotImplementedError"""
+            mc-dropout and Laplace mirrors raise NotImplementedError"""
             fn = getattr(self._mirror, "get_pose_gradients_for_camera", None)
             if fn is None:
-                raise NotImplementedError(f"{type(self._mirror).__name__} has no pose gradient: it is not a nerfacto ray model.")
+                raise NotImplementedError(f"{type(self._mirror).__name__} has no pose gradient.")
             return fn(camera, **kw)
 
         def load_state_dict(self, state_dict, strict: bool = False, **kw):  # type: ignore[override]

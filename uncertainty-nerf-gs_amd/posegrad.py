@@ -3,7 +3,8 @@
 The script perturbs one training camera along one of six pose parameters, renders it in 256-ray chunks and calls
 torch.autograd.grad(pred_rgb_j.mean(-1), c2w) once per pixel (:153-190).  Here the per-pixel gradients of a frame come from
 one kernel launch per group of rays (models.*.get_pose_gradients_for_camera -> render.pose_gradient_camera ->
-unerf_pose_grad), and the files the script leaves behind are written with its names, shapes and dtypes.
+unerf_pose_grad; for the splat models -> splat.pose_gradient_camera -> unerf_splat_pose_tangents + unerf_splat_pose_grad),
+and the files the script leaves behind are written with its names, shapes and dtypes.
 
 What differs from the reference: it differentiates whatever arithmetic its checkpoint runs in (half precision for a tcnn
 field); this build differentiates the fp32 field.  Its ground-truth and rendered images are JPEG (mediapy); no JPEG encoder
@@ -84,7 +85,8 @@ def export_pose_gradients(model, camera, image_idx: int, output_dir, shift_param
       c2w_grads_perturbed.npy   [H,W,3,4] float64  d mean_c(rgb[y,x]) / d c2w_perturbed
       image{idx:05d}_perturbed.png               the render as an 8-bit image (the reference writes a JPEG)
     model: anything with get_pose_gradients_for_camera(camera, want_rgb=True) (models.NerfactoModel / ActiveNerfactoModel,
-    the plugin's models).  camera: one camera (camera_to_worlds, fx, fy, cx, cy, height, width, ...); it is not modified.
+    models.SplatfactoModel / ActiveSplatfactoModel -- for which the reference's script has no counterpart: it asserts a
+    NerfactoModel -- and the plugin's models).  camera: one camera (camera_to_worlds, fx, fy, cx, cy, height, width, ...); it is not modified.
     seed: as the script, torch.manual_seed(seed) before the perturbation (which draws nothing).  -> {file stem: path}"""
     from .eval import _write_png
     from .models import _scalar

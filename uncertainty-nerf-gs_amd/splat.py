@@ -144,6 +144,62 @@ def active_splatfacto_outputs(gp: Dict[str, torch.Tensor], c2w: torch.Tensor, fx
             "depth_var": dv, "depth_std": dstd}
 
 
+def pose_gradient_camera(gp: Dict[str, torch.Tensor], c2w: torch.Tensor, fx: float, fy: float, cx: float, cy: float,
+                         H: int, W: int, background: torch.Tensor, sh_degree: int = 3, rasterize_mode: str = "classic",
+                         block_width: int = 16, crop_ids: Optional[torch.Tensor] = None,
+                         config_sh_degree: Optional[int] = None, tight: bool = True, want_rgb: bool = False):
+    """d mean_c(rgb[y, x]) / d camera_to_worlds of the frame active_splatfacto_outputs renders -> [H,W,3,4] float32 (with
+    want_rgb also the frame's rgb [H,W,3] as the gradient kernel blended it): the per-pixel quantity of the reference's
+    scripts/estimate_gradient_pose_6dof.py:128-139, for splats.  The projection, shading, count and
+    bin-sort calls are the frame's own, so the tile lists are; then one per-splat tangent kernel and one forward-mode walk.
+    Held fixed: near-plane cull, radii, lists, skipped pairs, stops, the crop and the (detached, :243) SH colours.  A frame
+    answered with empty_outputs has a zero gradient and the background image.  Works with and without
+    `log_uncertainties`; only rgb is differentiated."""
+    _l.require_gpu()
+    dev = gp["means"].device
+    background = background.to(dev, torch.float32)
+
+    def empty():
+        g = torch.zeros(H, W, 3, 4, device=dev)
+        return (g, background.repeat(H, W, 1)) if want_rgb else g
+
+    if gp["means"].shape[0] == 0:
+        return empty()
+    if crop_ids is not None:
+        crop_ids = crop_ids.reshape(-1).to(dev)
+        if int(crop_ids.sum().item()) == 0:
+            return empty()
+        gp = {k: v[crop_ids].contiguous() for k, v in gp.items()}
+    means = gp["means"].contiguous()
+    c2w = c2w.detach().to("cpu", torch.float32)
+    V = viewmat_from_c2w(c2w)
+    if rasterize_mode not in ("classic", "antialiased"):
+        raise ValueError(f"Unknown rasterize_mode: {rasterize_mode}")
+    aa = rasterize_mode == "antialiased"
+    logits = gp["opacities"].reshape(-1).contiguous()
+    proj = ops.splat_project(means, gp["scales"].contiguous(), 1.0, gp["quats"].contiguous(), V[:3], fx, fy, cx, cy, H, W,
+                             block_width, raw=True, opacity_logits=logits if tight else None, antialiased=aa)
+    xys, depths, radii, conics, comp, tiles, cov3d = proj[:7]
+    opac = proj[7] if tight else None
+    count = ops.SplatCount(tiles, defer_copy=True)
+    if config_sh_degree is not None and config_sh_degree <= 0:
+        sh_degree = -1
+    cols, opac2 = ops.splat_shade_inputs(sh_degree, means, c2w[:3, 3], gp["features_dc"].contiguous(),
+                                         gp["features_rest"].contiguous(), None, 0.0, None if tight else logits,
+                                         comp if aa else None, depths)
+    count.start_copy()
+    opac = opac if tight else opac2
+    I, _cum, _keys, gids, bins = ops.splat_bin_sort(xys, depths, radii, tiles, H, W, block_width, want_isect_ids=False,
+                                                    count=count, tight=(conics, opac) if tight else None)
+    if I == 0 and not (tight and bool((radii > 0).any())):
+        return empty()
+    tan = ops.splat_pose_tangents(means, cov3d, radii, V[:3], fx, fy, cx, cy, H, W)
+    grad, rgb, _ = ops.splat_pose_grad(gids, bins, xys, conics, cols[:, :3].contiguous(), opac, tan, H, W, background,
+                                       compensation=comp if aa else None, c2w=c2w[:3, :4], block_width=block_width,
+                                       want_rgb=want_rgb)
+    return (grad, rgb) if want_rgb else grad
+
+
 def _per_view(x, B: int, name: str) -> List[float]:
     """a scalar (or one-element tensor) for every view, or B values"""
     t = torch.as_tensor(x).detach().to("cpu", torch.float64).reshape(-1)
