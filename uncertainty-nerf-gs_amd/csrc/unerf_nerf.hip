@@ -1005,7 +1005,7 @@ extern "C" int unerf_proposal_density(const float* origins, const float* directi
 }
 
 // ======================================================================================
-// 4. weights + PDF resampling: one wave per ray, lane owns EPL consecutive samples
+// 4. weights + PDF resampling: a wave (n > 128) or a 16-lane group (n <= 128) per ray, lane owns EPL consecutive samples
 // ======================================================================================
 struct PdfArgs {
     const float* density;
@@ -1219,6 +1219,201 @@ __global__ __launch_bounds__(256) void pdf_kernel(PdfArgs a, VW... vw) {
     }
 }
 
+// The grouped form (n <= 128): a ray belongs to a group of PDF_GROUP = 16 lanes -- one DPP row, as in composite_kernel --
+// so a wave holds four rays and a block trip sixteen; lane l of a group owns the samples [l EPL, (l + 1) EPL),
+// EPL = ceil(n / 16).  What a ray costs once -- two sums, the median, the padding division, the clip -- is then paid once
+// per wave for four rays.  Every value comes from the formulas of pdf_kernel in the same order inside a lane; only the
+// cross-lane sums associate differently (group_*<16>).
+// LDS is sized by the launch (pdf_group_lds_bytes): one CDF row per group, and one row of bin edges per group or -- the
+// shared row, sstride == 0 -- that row and its Euclidean copy once per block.  The new bins are not staged: the clip
+// takes the first two and the last two from the lanes that made them.
+__host__ __device__ inline int pdf_row_stride(int n) { return (n + 1) | 1; }   // odd: the groups' rows start on different banks
+#define PDF_GROUP 16
+static inline size_t pdf_group_lds_bytes(int n, bool shared_row) {
+    const int groups = 256 / PDF_GROUP;
+    return (size_t)(shared_row ? groups + 2 : 2 * groups) * pdf_row_stride(n) * sizeof(float);
+}
+
+template <int EPL, typename... VW>
+__global__ __launch_bounds__(256) void pdf_group_kernel(PdfArgs a, VW... vw) {
+    constexpr int G = PDF_GROUP;
+    constexpr int NG = 256 / G;   // groups of a block = rays of a block trip
+    static_assert(PDF_RAYS_PER_BLOCK % NG == 0, "whole trips");
+    extern __shared__ float s_rows[];
+    __shared__ unsigned int s_clip[NG][2];
+    const int lane = threadIdx.x & 63, gl = lane & (G - 1), grp = threadIdx.x / G;
+    const int n = a.n, nb = a.m + 1, rs = pdf_row_stride(n);
+    const int top_step = 1 << (31 - __builtin_clz((unsigned)n));   // largest power of two <= n
+    const bool shared_row = a.sstride == 0;
+    float* const s_cdf = s_rows + grp * rs;
+    float* const s_sb = s_rows + (shared_row ? NG : NG + grp) * rs;
+    float* const s_eu = s_rows + (NG + 1) * rs;   // shared row only
+    if (shared_row) {
+        for (int k = threadIdx.x; k <= n; k += 256) {
+            const float b = a.sbins[k];
+            s_sb[k] = b;
+            s_eu[k] = unerf_s2e(b, a.s_near, a.s_far, a.lin);
+        }
+        __syncthreads();
+    }
+    // the running clip bounds of this GROUP's rays (its lane 0 keeps them), merged per block at the end as in pdf_kernel
+    int64_t cur_chunk = -1;
+    unsigned int cmin = 0x7F800000u, cmax = 0u;
+    for (int it = 0; it < PDF_RAYS_PER_BLOCK / NG; ++it) {
+    int64_t r = (int64_t)blockIdx.x * PDF_RAYS_PER_BLOCK + it * NG + grp;
+    const bool ray_ok = r < a.R;
+    if (!ray_ok) r = a.R - 1;  // a group past the last ray re-runs ray R - 1 with its stores switched off
+    wave_lds_sync();           // the rows of a wave's groups are read by that wave alone
+    if (!shared_row) {
+        const float* sb = a.sbins + r * a.sstride;
+        for (int k = gl; k <= n; k += G) s_sb[k] = sb[k];
+        wave_lds_sync();
+    }
+
+    float eu[EPL + 1], w[EPL], dd[EPL];
+    const int k0 = gl * EPL;
+    if (shared_row) {
+#pragma unroll
+        for (int e = 0; e <= EPL; ++e) eu[e] = s_eu[min(k0 + e, n)];
+    } else {
+#pragma unroll
+        for (int e = 0; e <= EPL; ++e) eu[e] = unerf_s2e(s_sb[min(k0 + e, n)], a.s_near, a.s_far, a.lin);
+    }
+    float lsum = 0.f, lexcl[EPL];
+#pragma unroll
+    for (int e = 0; e < EPL; ++e) {
+        const int k = k0 + e;
+        float dens = (k < n) ? a.density[r * n + k] : 0.f;
+        dd[e] = (k < n) ? (eu[e + 1] - eu[e]) * dens : 0.f;
+        lexcl[e] = lsum;
+        lsum += dd[e];
+    }
+    float carry = group_excl_scan<G>(lsum, gl);
+#pragma unroll
+    for (int e = 0; e < EPL; ++e) {
+        float alpha = 1.f - unerf_exp(-dd[e]);
+        float T = unerf_exp(-(carry + lexcl[e]));
+        w[e] = (k0 + e < n) ? unerf_nan_to_num(alpha * T) : 0.f;
+        if (a.weights_out && ray_ok && k0 + e < n) a.weights_out[r * n + k0 + e] = w[e];
+    }
+    // median depth of this level (prop_depth_i): the lane that owns the median sample writes its mid-point
+    if (a.prop_depth) {
+        float ls = 0.f, lc[EPL];
+#pragma unroll
+        for (int e = 0; e < EPL; ++e) {
+            ls += w[e];
+            lc[e] = ls;
+        }
+        float cbase = group_excl_scan<G>(ls, gl);
+        int cnt = 0;
+#pragma unroll
+        for (int e = 0; e < EPL; ++e) cnt += (k0 + e < n && (cbase + lc[e]) < 0.5f) ? 1 : 0;
+        cnt = group_sum_i<G>(cnt);
+        const int idx = min(cnt, n - 1);
+        const int owner = idx / EPL, slot = idx - owner * EPL;
+        float e0 = eu[0], e1 = eu[1];
+#pragma unroll
+        for (int e = 1; e < EPL; ++e) {
+            e0 = (e == slot) ? eu[e] : e0;
+            e1 = (e == slot) ? eu[e + 1] : e1;
+        }
+        if (gl == owner && ray_ok) a.prop_depth[r] = (e0 + e1) / 2.f;
+    }
+    // histogram -> pdf -> cdf
+    float wp[EPL], lw = 0.f;
+#pragma unroll
+    for (int e = 0; e < EPL; ++e) {
+        wp[e] = (k0 + e < n) ? w[e] + a.pad : 0.f;
+        lw += wp[e];
+    }
+    float wsum = group_sum<G>(lw);
+    float padding = fmaxf(a.eps - wsum, 0.f);
+    float padn = padding / (float)n;
+    wsum += padding;
+    float lp = 0.f, lcdf[EPL];
+#pragma unroll
+    for (int e = 0; e < EPL; ++e) {
+        float pdf = (k0 + e < n) ? (wp[e] + padn) / wsum : 0.f;
+        lp += pdf;
+        lcdf[e] = lp;
+    }
+    float cb = group_excl_scan<G>(lp, gl);
+    if (gl == 0) s_cdf[0] = 0.f;
+#pragma unroll
+    for (int e = 0; e < EPL; ++e)
+        if (k0 + e < n) s_cdf[k0 + e + 1] = fminf(1.f, cb + lcdf[e]);
+    wave_lds_sync();
+
+    float vfirst = 0.f, vlast = 0.f;   // this lane's first and last output: outputs 0, 1 and nb - 2, nb - 1 are among them
+    for (int j = gl; j < nb; j += G) {
+        float u = a.u[j];
+        // searchsorted(cdf[0..n], u, side="right") by the power-of-two descent of pdf_kernel
+        int pos = 0;
+        for (int step = top_step; step > 0; step >>= 1) {   // uniform trip count
+            const int probe = min(pos + step, n);
+            pos = (s_cdf[probe] <= u) ? probe : pos;
+        }
+        const int lo = pos + 1;
+        int below = min(max(lo - 1, 0), n), above = min(max(lo, 0), n);
+        float g0 = s_cdf[below], g1 = s_cdf[above];
+        float b0 = s_sb[below], b1 = s_sb[above];
+        float t = (u - g0) / (g1 - g0);
+        t = unerf_nan_to_num(t);
+        t = fminf(fmaxf(t, 0.f), 1.f);
+        float v = b0 + t * (b1 - b0);
+        vfirst = (j == gl) ? v : vfirst;
+        vlast = v;
+        if (ray_ok) a.sbins_out[r * nb + j] = v;
+    }
+    if (a.clip) {
+        // lanes 0..3 of a group convert the four edges (first two, last two) at once; outputs 0 and 1 are the first of
+        // lanes 0 and 1, outputs nb - 2 and nb - 1 the last of the lanes they fell to
+        const int src = (lane - gl) + ((gl & 2) ? ((nb - 2 + (gl & 1)) & (G - 1)) : (gl & 1));
+        const float xf = __shfl(vfirst, src, 64), xl = __shfl(vlast, src, 64);
+        const float ev = unerf_s2e((gl & 2) ? xl : xf, a.s_near, a.s_far, a.lin);
+        const float mid = (ev + dpp_f<0xB1>(ev)) / 2.f;   // lane 0: (f0 + f1) / 2, lane 2: (l0 + l1) / 2
+        const float last = dpp_f<0xAA>(mid);              // quad_perm [2,2,2,2]
+        if (ray_ok && gl == 0) {
+            const int64_t chunk = clip_chunk(a, r, vw...);
+            if (chunk != cur_chunk) {
+                if (cur_chunk >= 0) pdf_clip_commit(a.clip, cur_chunk, cmin, cmax);
+                cur_chunk = chunk;
+                cmin = 0x7F800000u;
+                cmax = 0u;
+            }
+            // positive floats order like their bit patterns
+            cmin = min(cmin, __float_as_uint(mid));
+            cmax = max(cmax, __float_as_uint(last));
+        }
+    }
+    }  // rays of this block
+    if (a.clip) {
+        // the groups of a block normally sit in one chunk: merge them through LDS and send one update
+        const int64_t blk_chunk = clip_chunk(a, (int64_t)blockIdx.x * PDF_RAYS_PER_BLOCK, vw...);
+        const bool mergeable = cur_chunk == blk_chunk;  // this group never left the block's first chunk
+        if (gl == 0) {
+            s_clip[grp][0] = mergeable ? cmin : 0x7F800000u;
+            s_clip[grp][1] = mergeable ? cmax : 0u;
+            if (!mergeable && cur_chunk >= 0) pdf_clip_commit(a.clip, cur_chunk, cmin, cmax);
+        }
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            unsigned int lo = 0x7F800000u, hi = 0u;
+            for (int g = 0; g < NG; ++g) {
+                lo = min(lo, s_clip[g][0]);
+                hi = max(hi, s_clip[g][1]);
+            }
+            if (lo != 0x7F800000u || hi != 0u) pdf_clip_commit(a.clip, blk_chunk, lo, hi);
+        }
+    }
+}
+
+// Lanes per ray, from n alone: 16 = pdf_group_kernel (EPL = ceil(n / 16) <= 8), 64 = pdf_kernel (a wave per ray,
+// EPL = ceil(n / 64) <= 4).  Above n = 128 a group's lane would sum nine and more samples in sequence; a 32-lane group
+// (EPL <= 8 up to n = 256) was built and measured, and put one weight of tests/pdf_group_cases.py's plain-256-96 at 1.03 of
+// its float64 bound (docs/experiments.md 8.4), so those n stay on the wave.
+static inline int pdf_lanes_per_ray(int n) { return n <= 128 ? PDF_GROUP : 64; }
+
 // views = NULL: unerf_weights_pdf_resample
 static int pdf_resample_impl(const float* density, const float* sbins, int64_t sbins_stride, int64_t R,
                              int n, float near_plane, float far_plane, int spacing, const float* u, int m,
@@ -1239,13 +1434,21 @@ static int pdf_resample_impl(const float* density, const float* sbins, int64_t s
     a.weights_out = weights_out; a.clip = clip_minmax; a.ray_offset = ray_offset; a.chunk_rays = chunk_rays;
     dim3 grid(blocks_for(R, PDF_RAYS_PER_BLOCK)), block(256);
     hipStream_t st = (hipStream_t)stream;
-    // pdf_kernel<EPL, VW...>: EPL = ceil(n / 64) samples per lane (n <= PDF_MAXN: 1 .. 4); the clip rows are numbered per
-    // view only where there is a clip buffer (without one nothing in the kernel is numbered by the frame)
+    // G lanes per ray and EPL = ceil(n / G) samples per lane: pdf_group_kernel<EPL, VW...> at G = 16 (EPL 1 .. 8),
+    // pdf_kernel<EPL, VW...> at G = 64 (EPL 3, 4 reached: n > 128); the clip rows are numbered per view only where there is a
+    // clip buffer (without one nothing in the kernel is numbered by the frame)
     const bool per_view = views && clip_minmax;
+    const int lanes = pdf_lanes_per_ray(n);
     with_pack(per_view, [&] { return make_view_map(views, chunk_rays); }, [&](auto... vm) {
-        with_int<1, 2, 3, 4>((n + 63) / 64, [&](auto epl) {
-            hipLaunchKernelGGL((pdf_kernel<decltype(epl)::value, decltype(vm)...>), grid, block, 0, st, a, vm...);
-        });
+        if (lanes == PDF_GROUP)
+            with_int<1, 2, 3, 4, 5, 6, 7, 8>((n + PDF_GROUP - 1) / PDF_GROUP, [&](auto epl) {
+                hipLaunchKernelGGL((pdf_group_kernel<decltype(epl)::value, decltype(vm)...>), grid, block,
+                                   pdf_group_lds_bytes(n, sbins_stride == 0), st, a, vm...);
+            });
+        else
+            with_int<1, 2, 3, 4>((n + 63) / 64, [&](auto epl) {
+                hipLaunchKernelGGL((pdf_kernel<decltype(epl)::value, decltype(vm)...>), grid, block, 0, st, a, vm...);
+            });
     });
     return unerf_check_launch(per_view ? "weights_pdf_resample_views" : "weights_pdf_resample");
 }
