@@ -7,22 +7,15 @@
 #                launch of the field kernel for each variant: do the cycles grow while the time stays?)
 cd "$(dirname "$0")/.."
 B=benchmarks/build_probe
-FLAGS="--offload-arch=gfx950 -O3 -ffp-contract=off -std=c++17 -fPIC -shared -mllvm -amdgpu-mfma-vgpr-form -I include"
-SRC="uncertainty-nerf-gs_amd/csrc/unerf_nerf.hip uncertainty-nerf-gs_amd/csrc/unerf_splat.hip"
 if [ "$1" = build ]; then
     mkdir -p $B
-    # the probe code lives in benchmarks/probe_source.py, which writes patched COPIES of the product source
-    SPLAT=uncertainty-nerf-gs_amd/csrc/unerf_splat.hip
-    /opt/rocm/bin/hipcc $FLAGS -o $B/libunerf_v0.so $SRC &
+    # the probe code lives in benchmarks/probe_source.py, which writes patched COPIES of the product source; every
+    # library is built by the product recipe (benchmarks/build_variant.py)
+    python benchmarks/build_variant.py v0 || exit 1
     for v in valu32:--extra-valu=32 valu64:--extra-valu=64 mfma4:--extra-mfma=4 mfma8:--extra-mfma=8; do
-        python benchmarks/probe_source.py ${v#*:} -o $B/unerf_nerf_${v%%:*}.hip
+        python benchmarks/probe_source.py ${v#*:} -o $B/unerf_nerf_${v%%:*}.hip &&
+            python benchmarks/build_variant.py ${v%%:*} --nerf-source $B/unerf_nerf_${v%%:*}.hip || exit 1
     done
-    /opt/rocm/bin/hipcc $FLAGS -o $B/libunerf_valu32.so $B/unerf_nerf_valu32.hip $SPLAT &
-    /opt/rocm/bin/hipcc $FLAGS -o $B/libunerf_valu64.so $B/unerf_nerf_valu64.hip $SPLAT &
-    wait
-    /opt/rocm/bin/hipcc $FLAGS -o $B/libunerf_mfma4.so $B/unerf_nerf_mfma4.hip $SPLAT &
-    /opt/rocm/bin/hipcc $FLAGS -o $B/libunerf_mfma8.so $B/unerf_nerf_mfma8.hip $SPLAT &
-    wait
     exit 0
 fi
 export OUT=${OUT:-$PWD/benchmarks/out}   # scratch: the per-run lines and the summary

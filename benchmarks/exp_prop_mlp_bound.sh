@@ -6,14 +6,11 @@
 #   on the box:  bash benchmarks/exp_prop_mlp_bound.sh run     -> gpurun_out/multi_ab.json
 cd "$(dirname "$0")/.."
 B=benchmarks/build_probe
-FLAGS="--offload-arch=gfx950 -O3 -ffp-contract=off -std=c++17 -fPIC -shared -mllvm -amdgpu-mfma-vgpr-form -I include"
-SRC="uncertainty-nerf-gs_amd/csrc/unerf_nerf.hip uncertainty-nerf-gs_amd/csrc/unerf_splat.hip"
 if [ "$1" = build ]; then
     mkdir -p $B
-    /opt/rocm/bin/hipcc $FLAGS -o $B/libunerf_base.so $SRC &
-    python benchmarks/probe_source.py --no-prop-mlp -o $B/unerf_nerf_nomlp.hip   # a patched COPY of the product source
-    /opt/rocm/bin/hipcc $FLAGS -o $B/libunerf_nomlp.so $B/unerf_nerf_nomlp.hip uncertainty-nerf-gs_amd/csrc/unerf_splat.hip &
-    wait
+    python benchmarks/build_variant.py base || exit 1
+    python benchmarks/probe_source.py --no-prop-mlp -o $B/unerf_nerf_nomlp.hip || exit 1   # a patched COPY of the product source
+    python benchmarks/build_variant.py nomlp --nerf-source $B/unerf_nerf_nomlp.hip || exit 1
     exit 0
 fi
 bash benchmarks/multi_ab.sh active base nomlp

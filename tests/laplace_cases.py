@@ -54,7 +54,7 @@ LOG2E = 1.4426950408889634
 LAP_PAD_BIAS = -1e30
 LAP_ROWS = 128                 # rows of a head in the blobs (LAP_BLOCKS x 32)
 F16_LIMIT = 65504.0
-EXP2_ROWS = True               # the build the bounds are stated for (UNERF_LAP_EXP2); the GPU test asserts the library's flag
+EXP2_ROWS = True               # the build the bounds are stated for (bare exp2 in the heads: unerf_build_flags); the GPU test asserts the library's flag
 NF_LONG, NF_SHORT = PC.NF_LONG, PC.NF_SHORT
 FAMILIES, BOUND_OF, SENTINEL = FC.FAMILIES, FC.BOUND_OF, FC.SENTINEL
 SOFTPLUS_JUMP, SERIES = FC.SOFTPLUS_JUMP, 2.5e-10

@@ -237,40 +237,21 @@ __device__ __forceinline__ void unerf_hash_corners(float px, float py, float pz,
 // row ride one packed fp32 pair (v_pk_mul_f32 / v_pk_add_f32 round each half exactly like the scalar
 // op): 21 packed instructions per level.  Left as scalar code the SLP vectoriser paired (f0*ox, f3*mx)
 // instead and spent a half-wasted horizontal v_pk_add plus ~25 register moves per level.
-// FUSED (the proposal kernels, UNERF_PROP_BLEND_FMA): each lerp as fma(a, o, b * (1 - o)) -- one rounding fewer than torch's
+// FUSED (the proposal kernels): each lerp as fma(a, o, b * (1 - o)) -- one rounding fewer than torch's
 // mul, mul, add, two instructions instead of three: 14 per level.  The proposal kernels are VALU-issue bound and the blend
 // was 37 % of their instructions: first proposal pass 6.78 -> 6.49 ms per frame, second 3.12 -> 3.08
 // (profiles/r4_exp_blend_fma_*.json).  unerf_hashgrid_fwd (whose outputs are the reference's bits) and the field kernels
-// keep torch's order.  UNERF_FIELD_BLEND_FMA=1 builds the field kernels with the fused form too (-1.1 % K-pass, -1.7 %
-// ACTIVE) -- NOT shippable: the split-f16 kernels of that build return different values from run to run in the columns
-// 16..31 of a few tiles per launch (every other build and kernel is bit-reproducible, tests/test_gpu_repeatability.py);
-// the cause was not found (not the inline assembly, not the MFMA register form, not the scheduler strategy: DESIGN.md 4.5).
-#ifndef UNERF_PROP_BLEND_FMA
-#define UNERF_PROP_BLEND_FMA 1
-#endif
-#ifndef UNERF_FIELD_BLEND_FMA
-#define UNERF_FIELD_BLEND_FMA 0
-#endif
+// keep torch's order: field kernels built with the fused form (-1.1 % K-pass, -1.7 % ACTIVE) were NOT shippable -- the
+// split-f16 kernels of that build returned different values from run to run in the columns 16..31 of a few tiles per
+// launch (every shipped kernel is bit-reproducible, tests/test_gpu_repeatability.py); the cause was not found (not the
+// inline assembly, not the MFMA register form, not the scheduler strategy: DESIGN.md 4.5, docs/experiments.md).
 typedef float unerf_v2f __attribute__((ext_vector_type(2)));
 template <bool FUSED = false>
 __device__ __forceinline__ unerf_v2f unerf_lerp2(unerf_v2f a, unerf_v2f b, float o, float m) {
-#if UNERF_FIELD_BLEND_FMA == 7
-    // experiment: the scalar weights as REAL register pairs, both halves written -- no packed operand
-    // whose upper half is an undefined register the allocator may hand to another live value
-    unerf_v2f oo = {o, o}, mm = {m, m};
-    asm volatile("" : "+v"(oo), "+v"(mm));
-    if (FUSED) return __builtin_elementwise_fma(a, oo, b * mm);
-    return a * oo + b * mm;
-#else
     if (FUSED) return __builtin_elementwise_fma(a, unerf_v2f{o, o}, b * m);
     return a * o + b * m;
-#endif
 }
-template <bool FUSED = false>
-__device__ __forceinline__ float unerf_lerp1(float a, float b, float o, float m) {
-    if (FUSED) return __builtin_fmaf(a, o, b * m);
-    return a * o + b * m;
-}
+__device__ __forceinline__ float unerf_lerp1(float a, float b, float o, float m) { return a * o + b * m; }
 template <bool FUSED = false>
 __device__ __forceinline__ float2 unerf_blend8(const float2 (&f)[8], float ox, float oy, float oz) {
     const float mx = 1.f - ox, my = 1.f - oy, mz = 1.f - oz;
@@ -290,27 +271,26 @@ __device__ __forceinline__ float2 unerf_blend8(const float2 (&f)[8], float ox, f
 // Scalar statement of the same blend (identical roundings) for the MFMA field kernels, which are bound
 // by the gather rather than by VALU issue: the packed form's aligned register pairs cost them ~18 VGPRs
 // and with that the third wave per SIMD.
-template <bool FUSED = false>
 __device__ __forceinline__ float2 unerf_blend8_scalar(const float2 (&f)[8], float ox, float oy, float oz) {
     float mx = 1.f - ox, my = 1.f - oy, mz = 1.f - oz;
     float2 r;
     {
-        float f03 = unerf_lerp1<FUSED>(f[0].x, f[3].x, ox, mx);
-        float f12 = unerf_lerp1<FUSED>(f[1].x, f[2].x, ox, mx);
-        float f56 = unerf_lerp1<FUSED>(f[5].x, f[6].x, ox, mx);
-        float f47 = unerf_lerp1<FUSED>(f[4].x, f[7].x, ox, mx);
-        float f0312 = unerf_lerp1<FUSED>(f03, f12, oy, my);
-        float f4756 = unerf_lerp1<FUSED>(f47, f56, oy, my);
-        r.x = unerf_lerp1<FUSED>(f0312, f4756, oz, mz);
+        float f03 = unerf_lerp1(f[0].x, f[3].x, ox, mx);
+        float f12 = unerf_lerp1(f[1].x, f[2].x, ox, mx);
+        float f56 = unerf_lerp1(f[5].x, f[6].x, ox, mx);
+        float f47 = unerf_lerp1(f[4].x, f[7].x, ox, mx);
+        float f0312 = unerf_lerp1(f03, f12, oy, my);
+        float f4756 = unerf_lerp1(f47, f56, oy, my);
+        r.x = unerf_lerp1(f0312, f4756, oz, mz);
     }
     {
-        float f03 = unerf_lerp1<FUSED>(f[0].y, f[3].y, ox, mx);
-        float f12 = unerf_lerp1<FUSED>(f[1].y, f[2].y, ox, mx);
-        float f56 = unerf_lerp1<FUSED>(f[5].y, f[6].y, ox, mx);
-        float f47 = unerf_lerp1<FUSED>(f[4].y, f[7].y, ox, mx);
-        float f0312 = unerf_lerp1<FUSED>(f03, f12, oy, my);
-        float f4756 = unerf_lerp1<FUSED>(f47, f56, oy, my);
-        r.y = unerf_lerp1<FUSED>(f0312, f4756, oz, mz);
+        float f03 = unerf_lerp1(f[0].y, f[3].y, ox, mx);
+        float f12 = unerf_lerp1(f[1].y, f[2].y, ox, mx);
+        float f56 = unerf_lerp1(f[5].y, f[6].y, ox, mx);
+        float f47 = unerf_lerp1(f[4].y, f[7].y, ox, mx);
+        float f0312 = unerf_lerp1(f03, f12, oy, my);
+        float f4756 = unerf_lerp1(f47, f56, oy, my);
+        r.y = unerf_lerp1(f0312, f4756, oz, mz);
     }
     return r;
 }

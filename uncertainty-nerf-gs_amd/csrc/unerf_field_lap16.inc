@@ -25,7 +25,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((F1 && !TCN
     // loads in front of every block's first MFMA they were the one load of the head loop whose latency nothing hid --
     // 16 round trips to L2 per tile.  Each wave brings its tile's 512 words in with two 16-byte loads per lane while the
     // hash grid is gathered, parks them in LDS, and the blocks read them back with ds_read_b128.
-    __shared__ float s_lbias[UNERF_LAP_BIAS_LDS && UNERF_LAP_PREFETCH >= 2 ? 4 : 1][UNERF_LAP_BIAS_LDS && UNERF_LAP_PREFETCH >= 2 ? 512 : 4];
+    __shared__ float s_lbias[4][512];
     if (TCNN) mf_stage_tcnn_levels<(TCNN == 2 ? 2 : 3)>(a, s_tl);
     __syncthreads();
     const int lane_c = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -53,7 +53,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((F1 && !TCN
         float px = ts.px, py = ts.py, pz = ts.pz;
         // inference: the returned mu_d is NOT selector-masked (laplace_field.py:356-362) unless lap_mask_density
         const float sel = unerf_normalize_position(px, py, pz, a.box);
-        constexpr bool BIAS_LDS = UNERF_LAP_BIAS_LDS && UNERF_LAP_PREFETCH >= 2 && !(F1 && !TCNN);
+        constexpr bool BIAS_LDS = !(F1 && !TCNN);
         float4 lb0, lb1;
         if (BIAS_LDS) {
             const float4* lbsrc = reinterpret_cast<const float4*>(set_blob(a.p.lap16_blob) + LAP_BIAS_OFF) + lane_c * 2;
@@ -71,7 +71,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((F1 && !TCN
         const float* lap16 = set_blob(a.p.lap16_blob);
         // (the single-product kernel at three waves per SIMD has no registers for a third operand buffer: it keeps the
         // one-block-ahead heads)
-        constexpr bool STREAM = UNERF_LAP_PREFETCH >= 2 && !(F1 && !TCNN);
+        constexpr bool STREAM = !(F1 && !TCNN);
         // base_mlp: bare Linear 32 -> 64 (no ReLU, utils.py:22-23)
         f32x16 hb0 = mf16_bias(lds, 0, h), hb1 = mf16_bias(lds, 1, h);
 #pragma unroll

@@ -49,8 +49,8 @@ void UNERF_MFMA16_KERNEL(FieldArgs a, uint32_t num_tiles, FastDiv div_s, XA... x
         float px = ts.px, py = ts.py, pz = ts.pz;
         const float sel = unerf_normalize_position(px, py, pz, a.box);
         // packed fp32x2 blend: this kernel has the registers for it (123 VGPRs without) in every mode
-        // colour layer 0, SH half (pass-invariant): components 8h..8h+7 of this lane half, one k-step -- as a closure, so
-        // that the torch-layout kernels can run it behind the first grid loads of the tile (mf_gather_feats_pipe)
+        // colour layer 0, SH half (pass-invariant): components 8h..8h+7 of this lane half, one k-step.  (A closure called
+        // behind the gather: stated in line there, the same statements compile to other code in 36 of the kernels.)
         f32x16 csh0 = mf16_bias(lds, 3, h), csh1 = mf16_bias(lds, 4, h);
         auto sh_layer = [&]() {
             float sh[16];
@@ -71,13 +71,8 @@ void UNERF_MFMA16_KERNEL(FieldArgs a, uint32_t num_tiles, FastDiv div_s, XA... x
             mf16_mac2<F1>(lds, 10, 11, lane, bhi, blo, csh0, csh1);
         };
         u32x8 feat_pk;
-        f32x16 feat;
-        if constexpr (TCNN == 0 && UNERF_GATHER_PIPE != 0) {
-            feat = mf_gather_feats_pipe(a, px, py, pz, h, mask, sh_layer);
-        } else {
-            feat = mf_gather_feats<true, TCNN>(a, px, py, pz, h, mask, s_tl, &feat_pk);
-            sh_layer();
-        }
+        const f32x16 feat = mf_gather_feats<true, TCNN>(a, px, py, pz, h, mask, s_tl, &feat_pk);
+        sh_layer();
 
         // layer 0: 32 -> 64 (this half's 16 features = two k-steps), ReLU; the 64 hidden units are the trunk
         // layer's four k-steps and do not depend on the MC pass: they are split into f16 operand quads ONCE
@@ -105,11 +100,11 @@ void UNERF_MFMA16_KERNEL(FieldArgs a, uint32_t num_tiles, FastDiv div_s, XA... x
         }
 
         const int passes = (MODE == UNERF_FIELD_MCDROPOUT && a.p.K > 0) ? a.p.K : 1;
-        // variants: the trunk-out operands (4 k-steps x 2 quads = 32 VGPRs) kept in registers across the passes; the
-        // 16-row trunk-out layer of MCDROPOUT folded into two MFMAs per k-step
-        constexpr bool TRUNK_RESIDENT = UNERF_TRUNK_RESIDENT && MODE == UNERF_FIELD_MCDROPOUT && DROP && !SITES;
+        // the trunk-out operands (4 k-steps x 2 quads = 32 VGPRs) kept in registers across the passes (-3.5 %); the
+        // 16-row trunk-out layer of MCDROPOUT folded into two MFMAs per k-step (-1 % kernel time)
+        constexpr bool TRUNK_RESIDENT = MODE == UNERF_FIELD_MCDROPOUT && DROP && !SITES;
         // F1: the first operand of a (folded or plain) trunk slab is W_hi, which is all the single-product form reads
-        constexpr bool FOLD = UNERF_TRUNK_FOLD && MODE == UNERF_FIELD_MCDROPOUT && !F1;
+        constexpr bool FOLD = MODE == UNERF_FIELD_MCDROPOUT && !F1;
         f16x8 ta0[4], ta1[4];   // first / second operand of trunk slab 4 + st
         if (TRUNK_RESIDENT) {
 #pragma unroll
@@ -140,19 +135,6 @@ void UNERF_MFMA16_KERNEL(FieldArgs a, uint32_t num_tiles, FastDiv div_s, XA... x
             mf_mask_init(mk2, 0, h, base0, 1u);
             mf_mask_init(mk3, 1, h, base0, 1u);
         }
-        // UNERF_KPASS_FILL (F1, default sites): AND masks of the trunk for the pass about to run (am_t*), of the head for the
-        // running pass (am_h*).  The words are stepped and tested BEHIND the matrix instructions of a pass instead of in front
-        // of them: an MFMA holds the SIMD's issue for ~10 of its 32 cycles, five or six independent VALU instructions ride in
-        // its shadow for nothing (benchmarks/issue_sweep_probe.hip), and the mask arithmetic -- 96 of a pass' 216 VALU
-        // instructions -- depends on nothing the pass computes.  Same words, same tests, same bits.
-        constexpr bool FILL = UNERF_KPASS_FILL && F1 && DROP && !SITES && MODE == UNERF_FIELD_MCDROPOUT;
-        uint32_t am_t0[8], am_t1[8], am_h0[8], am_h1[8];
-        if (FILL) {
-            mf16_keep_sub(mk0, a.keep_pk, am_t0);
-            mf16_keep_sub(mk1, a.keep_pk, am_t1);
-            mf16_keep_sign(am_t0);
-            mf16_keep_sign(am_t1);
-        }
         for (int k = 0; k < passes; ++k) {
             asm volatile("" : "+v"(lane));
             if constexpr (XM) {   // this pass' words from the keep bits instead of a generator step
@@ -164,7 +146,7 @@ void UNERF_MFMA16_KERNEL(FieldArgs a, uint32_t num_tiles, FastDiv div_s, XA... x
                     mf_xm_words(mk2, xm_row(xm_of(xa...), 2, k, n), 0, h);
                     mf_xm_words(mk3, xm_row(xm_of(xa...), 2, k, n), 1, h);
                 }
-            } else if (!FILL && drop && k > 0) {
+            } else if (drop && k > 0) {
                 mf_mask_step(mk0);
                 mf_mask_step(mk1);
                 mf_mask_step(mk2);
@@ -183,11 +165,7 @@ void UNERF_MFMA16_KERNEL(FieldArgs a, uint32_t num_tiles, FastDiv div_s, XA... x
 #pragma unroll
             for (int st = 0; st < 4; ++st) {
                 f16x8 bhi = hhi[st], blo = hlo[st];
-                if (FILL) {
-                    const uint32_t (&am)[8] = st < 2 ? am_t0 : am_t1;
-                    const u32x4 m = {am[4 * (st & 1)], am[4 * (st & 1) + 1], am[4 * (st & 1) + 2], am[4 * (st & 1) + 3]};
-                    bhi = __builtin_bit_cast(f16x8, __builtin_bit_cast(u32x4, bhi) & m);
-                } else if (drop_trunk) mf16_apply_masks<F1>(bhi, blo, st < 2 ? mk0 : mk1, st & 1, a.keep_pk);
+                if (drop_trunk) mf16_apply_masks<F1>(bhi, blo, st < 2 ? mk0 : mk1, st & 1, a.keep_pk);
                 f16x8 a0, a1;
                 if (TRUNK_RESIDENT) {
                     a0 = ta0[st];
@@ -207,15 +185,6 @@ void UNERF_MFMA16_KERNEL(FieldArgs a, uint32_t num_tiles, FastDiv div_s, XA... x
                 }
             }
             if (FOLD) t = mf16_fold_rows(t);
-            if (FILL) {   // behind the trunk's four MFMAs: this pass' head words tested (mf16_split_relu_drop), then stepped for the next pass
-                MF_FENCE();
-                mf16_keep_sub(mk2, a.keep_pk, am_h0);
-                mf16_keep_sub(mk3, a.keep_pk, am_h1);
-                mf_mask_step(mk2);
-                mf_mask_step(mk3);
-                mf_pin8(am_h0); mf_pin8(am_h1); mf_pin8(mk2); mf_pin8(mk3);
-                MF_FENCE();
-            }
             // colour 0: geo rows of t (registers 0..7 = one k-step) on top of the SH partial sum, ReLU
             f32x16 c0 = csh0, c1 = csh1;
             {
@@ -264,13 +233,6 @@ void UNERF_MFMA16_KERNEL(FieldArgs a, uint32_t num_tiles, FastDiv div_s, XA... x
                 // select 1 on the fp32 accumulators, and 4 MFMAs (128 issue cycles) instead of 48 packed FMAs + the half
                 // exchange.  (Round 3 measured this form at -5 % and dropped it over ONE AUSE figure at 1.04e-3 -- a gate
                 // that the reference's own two arithmetics miss by more on that target, DESIGN.md 6.)
-                if (FILL) {   // behind colour 1's last MFMAs: the trunk words stepped for the next pass
-                    MF_FENCE();
-                    mf_mask_step(mk0);
-                    mf_mask_step(mk1);
-                    mf_pin8(mk0); mf_pin8(mk1);
-                    MF_FENCE();
-                }
                 __builtin_amdgcn_s_setprio(1);
                 f32x16 o4;
 #pragma unroll
@@ -278,26 +240,17 @@ void UNERF_MFMA16_KERNEL(FieldArgs a, uint32_t num_tiles, FastDiv div_s, XA... x
 #pragma unroll
                 for (int st = 0; st < 4; ++st) {
                     f16x8 bhi;
-                    if (FILL || drop_head1) {
-                        const uint32_t (&w)[8] = FILL ? (st < 2 ? am_h0 : am_h1) : (st < 2 ? mk2 : mk3);
+                    if (drop_head1) {
+                        const uint32_t (&w)[8] = st < 2 ? mk2 : mk3;
                         u32x4 dd;
 #pragma unroll
-                        for (int p = 0; p < 4; ++p) dd[p] = FILL ? w[4 * (st & 1) + p] : mf16_keep_diff(w[4 * (st & 1) + p], a.keep_pk);
+                        for (int p = 0; p < 4; ++p) dd[p] = mf16_keep_diff(w[4 * (st & 1) + p], a.keep_pk);
                         mf16_split_relu_drop(st < 2 ? d0 : d1, st & 1, dd, bhi);
                     } else {
                         mf16_split_relu(st < 2 ? d0 : d1, st & 1, bhi);
                     }
                     const f16x8 aw = mf16_lds_op(lds + UNERF_MFMA_BLOB_FLOATS + st * 256 + lane * 4);
                     o4 = __builtin_amdgcn_mfma_f32_32x32x16_f16(aw, bhi, o4, 0, 0, 0);
-                }
-                if (FILL) {   // behind colour 2's four MFMAs: the next pass' trunk masks
-                    MF_FENCE();
-                    mf16_keep_sub(mk0, a.keep_pk, am_t0);
-                    mf16_keep_sub(mk1, a.keep_pk, am_t1);
-                    mf16_keep_sign(am_t0);
-                    mf16_keep_sign(am_t1);
-                    mf_pin8(am_t0); mf_pin8(am_t1);
-                    MF_FENCE();
                 }
                 // rows 0..2 = registers 0..2 of the h = 0 half: one v_permlane32_swap each hands them to both halves
 #pragma unroll
@@ -347,9 +300,9 @@ void UNERF_MFMA16_KERNEL(FieldArgs a, uint32_t num_tiles, FastDiv div_s, XA... x
                         for (int c = 0; c < CG; ++c) {
 #pragma unroll
                             for (int q4 = 0; q4 < 4; ++q4) {
-                                // (round 6) UNERF_RGB_SCALAR: the same four fused multiply-adds on scalar registers (1: every
-                                // mode, 2: ACTIVE only -- measured -1.8 % there and +0.7 % in the K-pass kernel, same box)
-                                if constexpr (UNERF_RGB_SCALAR == 1 || (UNERF_RGB_SCALAR == 2 && MODE == UNERF_FIELD_ACTIVE)) {
+                                // ACTIVE: the same four fused multiply-adds on scalar registers (measured -1.8 % there and
+                                // +0.7 % in the K-pass kernel, same box)
+                                if constexpr (MODE == UNERF_FIELD_ACTIVE) {
                                     acc2[c0g + c].x = __builtin_fmaf(dv[4 * q4], wv[c][q4].x, acc2[c0g + c].x);
                                     acc2[c0g + c].y = __builtin_fmaf(dv[4 * q4 + 1], wv[c][q4].y, acc2[c0g + c].y);
                                     acc2[c0g + c].x = __builtin_fmaf(dv[4 * q4 + 2], wv[c][q4].z, acc2[c0g + c].x);

@@ -33,43 +33,12 @@ int unerf_check_launch(const char* what) {
     }
     return UNERF_OK;
 }
-// ---- build switches measured against each other on one box (benchmarks/exp_kpass_variants.sh,
-// profiles/r2_exp_kpass_variants.json); the defaults are what ships.  unerf_build_flags() reports them, and the host
-// packs the operands to match (ops.pack_field_mfma16: fold_trunk).
-#ifndef UNERF_TRUNK_FOLD
-#define UNERF_TRUNK_FOLD 1       // K-pass kernel, 16-row trunk-out layer: two MFMAs per k-step (-1 % kernel time)
-#endif
-#ifndef UNERF_LAP_EXP2
-#define UNERF_LAP_EXP2 1         // LAPLACE: lap16_blob rows pre-scaled by +-log2(e), bare exp2 in the epilogue
-#endif
-#ifndef UNERF_RGB_SCALAR
-#define UNERF_RGB_SCALAR 2   // the split-f16 kernels' fp32 colour layer as scalar fmas instead of v_pk_fma_f32: 1 every mode, 2 ACTIVE only
-#endif
-#ifndef UNERF_LAP_SCALAR_MOMENTS
-#define UNERF_LAP_SCALAR_MOMENTS 1   // 1: no packed-fp32 fma in the Laplace heads' moment sums (-1.4 % Laplace field kernel, same box)
-#endif
-#ifndef UNERF_LAP_NO_FENCE
-#define UNERF_LAP_NO_FENCE 0         // 1 (with scalar moments only: no inline assembly left in the heads): no scheduling fences
-#endif
-#if UNERF_LAP_NO_FENCE && UNERF_LAP_SCALAR_MOMENTS
-#define LAP_FENCE() ((void)0)
-#else
-#define LAP_FENCE() __builtin_amdgcn_sched_barrier(0)
-#endif
-#ifndef UNERF_KPASS_FILL
-#define UNERF_KPASS_FILL 0   // 1: "f16" K-pass kernel with the mask arithmetic placed behind the MFMAs of a pass (round 6)
-#endif
-#ifndef UNERF_FIELD_BLEND_SCALAR
-#define UNERF_FIELD_BLEND_SCALAR 0   // 1: no packed-fp32 instruction in the matrix kernels' grid blend (same roundings)
-#endif
-#ifndef UNERF_TRUNK_RESIDENT
-#define UNERF_TRUNK_RESIDENT 1   // ... and its operands kept in registers across the passes (-3.5 %)
-#endif
 
 extern "C" const char* unerf_last_error(void) { return g_err; }
-extern "C" int unerf_build_flags(void) {
-    return (UNERF_TRUNK_FOLD ? UNERF_BUILD_TRUNK_FOLD : 0) | (UNERF_LAP_EXP2 ? UNERF_BUILD_LAP_EXP2 : 0);
-}
+// The operand layouts the kernels read, for the host to pack to (ops.pack_field_mfma16: fold_trunk; ops.pack_laplace_heads16:
+// exp2_rows): the K-pass kernel's 16-row trunk-out layer folded into two MFMAs per k-step, and lap16_blob rows pre-scaled
+// by +-log2(e) for a bare exp2 in the Laplace heads' epilogue.
+extern "C" int unerf_build_flags(void) { return UNERF_BUILD_TRUNK_FOLD | UNERF_BUILD_LAP_EXP2; }
 // 11xx: round-2 ABI (drop_sites, sample_major planes, aabb, ...); 1101: ray_box_bins / ray_planes_bins; 1102: build flags,
 // folded trunk-out slabs; 12xx: round-3 ABI -- `spacing` (UNERF_SPACING_*) behind every near / far pair, `background`
 // (UNERF_BG_*) on the composite / GGN entry points
@@ -780,11 +749,11 @@ __global__ __launch_bounds__(256) void prop_density_kernel(PropArgs a) {
         } else if (a.net.tcnn_levels) {  // uniform: tcnn-layout grid
             f = unerf_tcnn_level_feat(reinterpret_cast<const float2*>(a.net.table), a.net.tcnn_levels[l], px, py, pz);
         } else if (l < a.net.n_dense) {  // wave-uniform: coarse level with a dense, x-paired copy
-            f = unerf_dense_level<(UNERF_PROP_BLEND_FMA != 0)>(reinterpret_cast<const float4*>(a.net.dense) + a.net.dense_off[l], a.net.dense_dim[l],
-                                  px, py, pz, a.net.scalings[l]);
+            f = unerf_dense_level<true>(reinterpret_cast<const float4*>(a.net.dense) + a.net.dense_off[l], a.net.dense_dim[l],
+                                        px, py, pz, a.net.scalings[l]);
         } else {
             const float2* lvl = reinterpret_cast<const float2*>(a.net.table) + ((size_t)l << a.net.log2T);
-            f = unerf_hash_level<false, (UNERF_PROP_BLEND_FMA != 0)>(lvl, px, py, pz, a.net.scalings[l], mask);
+            f = unerf_hash_level<false, true>(lvl, px, py, pz, a.net.scalings[l], mask);
         }
         feat[2 * l] = f.x;
         feat[2 * l + 1] = f.y;
@@ -829,23 +798,16 @@ __global__ __launch_bounds__(256) void prop_density_kernel(PropArgs a) {
 // workgroup and storing one 16-byte vector per ray removes about half of the cache-line accesses of the 96-sample
 // pass (own sbins row per ray) and a quarter of the 256-sample pass (shared sbins).  Same arithmetic on
 // the same values: bit-identical to prop_density_kernel.
-#ifndef UNERF_PROP_XCD
-#define UNERF_PROP_XCD 1
-#endif
 template <int L, int HID>
 __global__ __launch_bounds__(256) void prop_patch_kernel(PropArgs a) {
     __shared__ float s_od[6][64];
     __shared__ float s_e[5][64];
     __shared__ float s_out[64][4];
-    // XCD-aware order (UNERF_PROP_XCD): workgroups go to the 8 XCDs round-robin; every XCD takes a CONTIGUOUS
+    // XCD-aware order: workgroups go to the 8 XCDs round-robin; every XCD takes a CONTIGUOUS
     // eighth of the (patch, sample group) list -- a band of the image -- instead of every eighth workgroup, so the grid lines
     // neighbouring patches share are fetched into one L2 instead of all eight.  Pure scheduling: same values per sample.
-#if UNERF_PROP_XCD
     const uint32_t per = (gridDim.x + 7u) >> 3, bid = (blockIdx.x & 7u) * per + (blockIdx.x >> 3);
     if (bid >= a.nblocks) return;
-#else
-    const uint32_t bid = blockIdx.x;
-#endif
     const uint32_t patch = fastdiv(bid, a.div_nsg), sg = bid - patch * a.nsg;
     const uint32_t band = fastdiv(patch, a.div_pcols), pc = patch - band * a.pcols;
     const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
@@ -902,11 +864,11 @@ __global__ __launch_bounds__(256) void prop_patch_kernel(PropArgs a) {
             } else if (a.net.tcnn_levels) {  // uniform: tcnn-layout grid
                 f = unerf_tcnn_level_feat(reinterpret_cast<const float2*>(a.net.table), a.net.tcnn_levels[l], px, py, pz);
             } else if (l < a.net.n_dense) {  // wave-uniform: coarse level with a dense, x-paired copy
-                f = unerf_dense_level<(UNERF_PROP_BLEND_FMA != 0)>(reinterpret_cast<const float4*>(a.net.dense) + a.net.dense_off[l], a.net.dense_dim[l],
-                                      px, py, pz, a.net.scalings[l]);
+                f = unerf_dense_level<true>(reinterpret_cast<const float4*>(a.net.dense) + a.net.dense_off[l], a.net.dense_dim[l],
+                                            px, py, pz, a.net.scalings[l]);
             } else {
                 const float2* lvl = reinterpret_cast<const float2*>(a.net.table) + ((size_t)l << a.net.log2T);
-                f = unerf_hash_level<false, (UNERF_PROP_BLEND_FMA != 0)>(lvl, px, py, pz, a.net.scalings[l], mask);
+                f = unerf_hash_level<false, true>(lvl, px, py, pz, a.net.scalings[l], mask);
             }
             feat[2 * l] = f.x;
             feat[2 * l + 1] = f.y;
@@ -984,7 +946,7 @@ extern "C" int unerf_proposal_density(const float* origins, const float* directi
             a.div_nsg = make_fastdiv((uint32_t)nsg); a.div_pcols = make_fastdiv((uint32_t)pcols);
             a.g0 = ray_offset; a.first_row = band0 * 8;
             a.nblocks = (uint32_t)blocks;
-            grid = dim3((unsigned)(UNERF_PROP_XCD ? ((blocks + 7) / 8) * 8 : blocks));
+            grid = dim3((unsigned)(((blocks + 7) / 8) * 8));
         }
     }
     hipStream_t st = (hipStream_t)stream;
@@ -2361,79 +2323,13 @@ __device__ __forceinline__ f32x16 mf_gather_feats(const FieldArgs& a, float px, 
             float2 c8[8];
 #pragma unroll
             for (int k = 0; k < 8; ++k) c8[k] = cd[8 * q + k];
-            // UNERF_FIELD_BLEND_FMA (experiments; 0 ships): 1 = fused lerps, 2 = fused lerps in the SCALAR form
-            // in every kernel (no v_pk_fma_f32 in the blend), 3 = as 1 with two wait states behind every level's blend
-            float2 f = (PACKED && UNERF_FIELD_BLEND_FMA != 2 && !UNERF_FIELD_BLEND_SCALAR) ? unerf_blend8<(UNERF_FIELD_BLEND_FMA != 0)>(c8, of[3 * q], of[3 * q + 1], of[3 * q + 2])
-                              : unerf_blend8_scalar<(UNERF_FIELD_BLEND_FMA != 0)>(c8, of[3 * q], of[3 * q + 1], of[3 * q + 2]);
-#if UNERF_FIELD_BLEND_FMA == 3
-            asm volatile("s_nop 1" : "+v"(f.x), "+v"(f.y));
-#elif UNERF_FIELD_BLEND_FMA == 4
-            asm volatile("s_nop 0" : "+v"(f.x), "+v"(f.y));
-#elif UNERF_FIELD_BLEND_FMA == 5
-            asm volatile("" : "+v"(f.x), "+v"(f.y));
-#endif
+            float2 f = PACKED ? unerf_blend8(c8, of[3 * q], of[3 * q + 1], of[3 * q + 2])
+                              : unerf_blend8_scalar(c8, of[3 * q], of[3 * q + 1], of[3 * q + 2]);
             feat[2 * (4 * hb + q)] = f.x;
             feat[2 * (4 * hb + q) + 1] = f.y;
         }
         __builtin_amdgcn_sched_barrier(0);
     }
-    return feat;
-}
-
-// The same lookup as a ROLLING stream (torch layout, packed blend): four batches of two levels (16 corner rows each); the
-// loads of batch b + 1 are issued BEFORE batch b is blended, and `filler` -- work that does not depend on the grid (the
-// direction encoding and its two MFMAs) -- runs behind the first two batches' loads.  mf_gather_feats asks for 32 rows,
-// blends them all, and only then asks for the next 32: between the two bursts the wave has nothing in flight, and at
-// the start of a tile it sits through a full memory round trip with the SH arithmetic already behind it.  Same 64
-// data registers (two 16-row buffers), same values: every level is blended exactly as before.
-// MEASURED AND NOT ADOPTED (profiles/r5_exp_gather_pipe_ab.txt): K-pass "f16" field 24.9 -> 25.5 ms per frame,
-// ACTIVE "f16" 9.82 -> 10.0, ACTIVE split 12.2 -> 12.9 (its 168-register budget spills 40 B) -- the K-pass kernel issues on
-// 0.93 of its cycles (nothing to hide latency under), and the ACTIVE kernels pay for the second address set with their third
-// wave's registers.  UNERF_GATHER_PIPE=1 builds it.
-#ifndef UNERF_GATHER_PIPE
-#define UNERF_GATHER_PIPE 0
-#endif
-template <typename Filler>
-__device__ __forceinline__ f32x16 mf_gather_feats_pipe(const FieldArgs& a, float px, float py, float pz, int h, uint32_t mask,
-                                                       Filler&& filler) {
-    f32x16 feat;
-    const char* tbase = reinterpret_cast<const char*>(a.p.table);
-    float2 cd[2][16];
-    float of[2][6];
-    auto issue = [&](int b, int buf) {
-#pragma unroll
-        for (int q = 0; q < 2; ++q) {
-            const int lev = 8 * h + 2 * b + q;
-            uint32_t off[8];
-            unerf_hash_corners<true>(px, py, pz, a.p.scalings[lev], mask, off, of[buf][3 * q], of[buf][3 * q + 1], of[buf][3 * q + 2],
-                                     (uint32_t)lev << (a.p.log2T + 3));
-#pragma unroll
-            for (int k = 0; k < 8; ++k) cd[buf][8 * q + k] = *reinterpret_cast<const float2*>(tbase + off[k]);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-    };
-    auto blend = [&](int b, int buf) {
-#pragma unroll
-        for (int q = 0; q < 2; ++q) {
-            float2 c8[8];
-#pragma unroll
-            for (int k = 0; k < 8; ++k) c8[k] = cd[buf][8 * q + k];
-            const float2 f = unerf_blend8<(UNERF_FIELD_BLEND_FMA != 0)>(c8, of[buf][3 * q], of[buf][3 * q + 1], of[buf][3 * q + 2]);
-            feat[2 * (2 * b + q)] = f.x;
-            feat[2 * (2 * b + q) + 1] = f.y;
-        }
-        __builtin_amdgcn_sched_barrier(0);
-    };
-    issue(0, 0);
-    issue(1, 1);
-    filler();
-    __builtin_amdgcn_sched_barrier(0);
-    blend(0, 0);
-    issue(2, 0);
-    blend(1, 1);
-    issue(3, 1);
-    blend(2, 0);
-    blend(3, 1);
     return feat;
 }
 
@@ -2864,23 +2760,6 @@ __device__ __forceinline__ void mf16_apply_masks(f16x8& hi, f16x8& lo, const uin
     if (!F1) lo = __builtin_bit_cast(f16x8, __builtin_bit_cast(u32x4, lo) & m);
 }
 
-// UNERF_KPASS_FILL: the keep test of eight words in its two halves, so that the halves can sit in different MFMA shadows
-__device__ __forceinline__ void mf16_keep_sub(const uint32_t (&w)[8], uint32_t thr_pk, uint32_t (&d)[8]) {
-#pragma unroll
-    for (int q = 0; q < 8; ++q) d[q] = mf16_keep_diff(w[q], thr_pk);
-}
-__device__ __forceinline__ void mf16_keep_sign(uint32_t (&d)[8]) {
-#pragma unroll
-    for (int q = 0; q < 8; ++q) d[q] = __builtin_bit_cast(uint32_t, __builtin_bit_cast(i16x2, d[q]) >> (short)15);
-}
-// the eight values exist HERE: an empty volatile statement the optimiser can neither sink into the loop latch (where it put the
-// mask steps, whose results only the next pass reads) nor hoist
-__device__ __forceinline__ void mf_pin8(uint32_t (&x)[8]) {
-    asm volatile("" : "+v"(x[0]), "+v"(x[1]), "+v"(x[2]), "+v"(x[3]), "+v"(x[4]), "+v"(x[5]), "+v"(x[6]), "+v"(x[7]));
-}
-// scheduling fence that LDS reads and scalar instructions may cross (the next layer's operand reads go up, nothing else moves)
-#define MF_FENCE() __builtin_amdgcn_sched_barrier(0x0104)
-
 // SITES = false: the reference's default Dropout placement (trunk + last head layer), every site test a compile-time
 // constant.  SITES = true: any other unerf_field_params.drop_sites (run-time site tests, and the words of the
 // UNERF_DROP_HEAD0 site recomputed per pass).  A separate instantiation: as run-time branches of the default kernel
@@ -3117,15 +2996,17 @@ __global__ __launch_bounds__(256) void field_kernel_mfma_laplace(FieldArgs a, ui
 // matrix work cut 5x the exp / rcp epilogues (quarter-rate transcendentals) are the larger half, so register
 // quads that only hold padding rows (rows >= n_lap) are skipped.
 // --------------------------------------------------------------------------------------
-// ACT: 0 exp, 1 sigmoid, 2 softplus.  With UNERF_LAP_EXP2 the rows of lap16_blob carry the base change
-// (ops.pack_laplace_heads16: density rows x log2 e, colour rows x -log2 e), so exp / sigmoid are the bare v_exp_f32
-// (+ v_rcp_f32); softplus rows are unscaled.  The running sums of p and p^2 are one packed fma per activation,
-// (s1, s2) += (p, p) * (1, p), instead of a multiply and a packed add.
+// ACT: 0 exp, 1 sigmoid, 2 softplus.  The rows of lap16_blob carry the base change (ops.pack_laplace_heads16: density
+// rows x log2 e, colour rows x -log2 e; unerf_build_flags() tells the host), so exp / sigmoid are the bare v_exp_f32
+// (+ v_rcp_f32); softplus rows are unscaled.
+// The fences keep each row block's MFMAs in front of its activations, as separate scheduling regions (they cost nothing:
+// docs/experiments.md 6.4).
+#define LAP_FENCE() __builtin_amdgcn_sched_barrier(0)
 template <int ACT, bool F1 = false>
 __device__ __forceinline__ void mf16_lap_head(const float* __restrict__ lap, int q, int n_lap, int lane,
                                               const f16x8 (&bhi)[4], const f16x8 (&blo)[4], int h, float& sum1,
                                               float& sum2) {
-    unerf_v2f s12 = {0.f, 0.f}, pr = {1.f, 0.f};
+    unerf_v2f s12 = {0.f, 0.f};
     f16x8 cur[8], nxt[8];
     {
         const float* f = lap + (size_t)((q * LAP_BLOCKS + 0) * 8) * 256 + lane * 4;
@@ -3142,8 +3023,6 @@ __device__ __forceinline__ void mf16_lap_head(const float* __restrict__ lap, int
         const float4* bp = reinterpret_cast<const float4*>(lap + LAP_BIAS_OFF + ((q * LAP_BLOCKS + b) * 2 + h) * 16);
         float4 b0 = bp[0], b1 = bp[1], b2 = bp[2], b3 = bp[3];
         f32x16 acc = {b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, b1.z, b1.w, b2.x, b2.y, b2.z, b2.w, b3.x, b3.y, b3.z, b3.w};
-        // the fences keep each row block's MFMAs and its activations (with the inline-asm packed fma, whose hazards
-        // the compiler does not model) as separate scheduling regions: without them the kernel is 1.3 % faster and wrong
         LAP_FENCE();
 #pragma unroll
         for (int st = 0; st < 4; ++st) {  // cur[2 st] = hi, cur[2 st + 1] = lo of k-step st
@@ -3164,25 +3043,16 @@ __device__ __forceinline__ void mf16_lap_head(const float* __restrict__ lap, int
                     if (ACT == 2) {
                         p = mf_softplus_fast(acc[r]);
                     } else {
-                        const float e = UNERF_LAP_EXP2 ? __builtin_amdgcn_exp2f(acc[r]) : __expf(ACT == 1 ? -acc[r] : acc[r]);
+                        const float e = __builtin_amdgcn_exp2f(acc[r]);
                         p = ACT == 1 ? __builtin_amdgcn_rcpf(1.f + e) : e;
                     }
-                    // (s1, s2) += (p, p) * (1, p): both factors read from the pair P = (1, p) through op_sel (src0 takes
-                    // the high dword for both lanes, src1 low / high).  Spelled with vector types the compiler builds the
-                    // two factor pairs with a v_mov each.  s_nop: a transcendental's result (p comes from v_exp / v_rcp)
-                    // needs one wait state before a VALU instruction the compiler cannot see may read it.
-#if UNERF_LAP_SCALAR_MOMENTS
-                    // round 6: the same two sums as one add and one fma on their own registers (the same roundings as the
-                    // packed fma's two halves).  A packed-fp32 instruction cannot run beside an MFMA -- one behind an MFMA
+                    // the sums of p and p^2 as one add and one fma on their own registers, not one packed fma (the same
+                    // roundings as its two halves).  A packed-fp32 instruction cannot run beside an MFMA -- one behind an MFMA
                     // waits for it and costs 18 cycles, the next MFMA waits for the packed instruction in turn
                     // (benchmarks/issue_sweep_probe.hip) -- and at two or three waves per SIMD the other wave's head MFMAs
                     // are always in flight; v_add_f32 / v_fmac_f32 issue in their shadow.
                     s12.x += p;
                     s12.y = __builtin_fmaf(p, p, s12.y);
-#else
-                    pr.y = p;
-                    asm("s_nop 0\n\tv_pk_fma_f32 %0, %1, %1, %0 op_sel:[1,0,0] op_sel_hi:[1,1,1]" : "+v"(s12) : "v"(pr));
-#endif
                 }
             }
         }
@@ -3196,17 +3066,12 @@ __device__ __forceinline__ void mf16_lap_head(const float* __restrict__ lap, int
     sum2 = s12.y + __shfl_xor(s12.y, 32, 64);
 }
 
-// UNERF_LAP_PREFETCH >= 2: the same head evaluation as ONE operand stream over NHEADS consecutive heads with the loads
+// The same head evaluation as ONE operand stream over NHEADS consecutive heads with the loads
 // running TWO row blocks ahead of the matrix work (three rotating register buffers instead of two).  The kernel was
 // latency-bound on exactly this stream -- 8 KB per wave and block from L2, one block (~0.9 us of two waves' work) of
 // lead against ~1.4 us of loaded L2 latency: issue-busy 0.575, SQ_WAIT_ANY 0.34 (profiles/issue_laplace.json, round
 // 3) -- and every head started cold; the three colour heads now run as one 12-block stream.
-#ifndef UNERF_LAP_PREFETCH
-#define UNERF_LAP_PREFETCH 2
-#endif
-#ifndef UNERF_LAP_BIAS_LDS
-#define UNERF_LAP_BIAS_LDS 1     // the 512 bias words of a sample set staged in LDS per wave and tile (see the kernel)
-#endif
+// lds_bias: the 512 bias words of the sample set, staged in LDS per wave and tile (see the kernel).
 template <int ACT, bool F1, int NHEADS>
 __device__ __forceinline__ void mf16_lap_stream(const float* __restrict__ lap, const float* __restrict__ lds_bias, int q0,
                                                 int n_lap, int lane, const f16x8 (&bhi)[4], const f16x8 (&blo)[4], int h,
@@ -3220,7 +3085,7 @@ __device__ __forceinline__ void mf16_lap_stream(const float* __restrict__ lap, c
 #pragma unroll
         for (int i = 0; i < 8; i += (F1 ? 2 : 1)) buf[1][i] = *reinterpret_cast<const f16x8*>(base + (8 + i) * 256);
     }
-    unerf_v2f s12 = {0.f, 0.f}, pr = {1.f, 0.f};
+    unerf_v2f s12 = {0.f, 0.f};
 #pragma unroll
     for (int blk = 0; blk < NB; ++blk) {
         const int b = blk % LAP_BLOCKS, hd = blk / LAP_BLOCKS;
@@ -3230,12 +3095,11 @@ __device__ __forceinline__ void mf16_lap_stream(const float* __restrict__ lap, c
                 buf[(blk + 2) % 3][i] = *reinterpret_cast<const f16x8*>(base + ((blk + 2) * 8 + i) * 256);
         }
         const f16x8 (&cur)[8] = buf[blk % 3];
-        const float4* bp = reinterpret_cast<const float4*>((UNERF_LAP_BIAS_LDS ? lds_bias : lap + LAP_BIAS_OFF) +
-                                                           (((q0 + hd) * LAP_BLOCKS + b) * 2 + h) * 16);
+        const float4* bp = reinterpret_cast<const float4*>(lds_bias + (((q0 + hd) * LAP_BLOCKS + b) * 2 + h) * 16);
         float4 b0 = bp[0], b1 = bp[1], b2 = bp[2], b3 = bp[3];
         f32x16 acc = {b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, b1.z, b1.w, b2.x, b2.y, b2.z, b2.w, b3.x, b3.y, b3.z, b3.w};
         if (b == 0) s12 = unerf_v2f{0.f, 0.f};
-        LAP_FENCE();   // (see mf16_lap_head: the inline-asm packed fma and its operands stay in one region)
+        LAP_FENCE();
 #pragma unroll
         for (int st = 0; st < 4; ++st) {
             if (!F1) {
@@ -3254,21 +3118,12 @@ __device__ __forceinline__ void mf16_lap_stream(const float* __restrict__ lap, c
                     if (ACT == 2) {
                         p = mf_softplus_fast(acc[r]);
                     } else {
-                        const float e = UNERF_LAP_EXP2 ? __builtin_amdgcn_exp2f(acc[r]) : __expf(ACT == 1 ? -acc[r] : acc[r]);
+                        const float e = __builtin_amdgcn_exp2f(acc[r]);
                         p = ACT == 1 ? __builtin_amdgcn_rcpf(1.f + e) : e;
                     }
-#if UNERF_LAP_SCALAR_MOMENTS
-                    // round 6: the same two sums as one add and one fma on their own registers (the same roundings as the
-                    // packed fma's two halves).  A packed-fp32 instruction cannot run beside an MFMA -- one behind an MFMA
-                    // waits for it and costs 18 cycles, the next MFMA waits for the packed instruction in turn
-                    // (benchmarks/issue_sweep_probe.hip) -- and at two or three waves per SIMD the other wave's head MFMAs
-                    // are always in flight; v_add_f32 / v_fmac_f32 issue in their shadow.
+                    // (scalar moment sums: see mf16_lap_head)
                     s12.x += p;
                     s12.y = __builtin_fmaf(p, p, s12.y);
-#else
-                    pr.y = p;
-                    asm("s_nop 0\n\tv_pk_fma_f32 %0, %1, %1, %0 op_sel:[1,0,0] op_sel_hi:[1,1,1]" : "+v"(s12) : "v"(pr));
-#endif
                 }
             }
         }

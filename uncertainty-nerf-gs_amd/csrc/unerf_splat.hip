@@ -1233,28 +1233,15 @@ __global__ __launch_bounds__(256) void tile_apply_kernel(uint32_t* __restrict__ 
 // memory latency (four waves per CU: the 32-KB tables), so it works on four vectors per round and asks for the next
 // round's pairs before it ranks this round's.
 #define TS_VEC 4
-#ifndef UNERF_SPLAT_XCD
-#define UNERF_SPLAT_XCD 0
-#endif
 template <typename TKey>
 __global__ __launch_bounds__(64) void tile_scatter_kernel(const TKey* __restrict__ keys, const int32_t* __restrict__ vals,
                                                           int64_t I, int chunk, int T1, const uint32_t* __restrict__ table,
                                                           int32_t* __restrict__ out) {
     extern __shared__ uint32_t s_off[];
     const int lane = threadIdx.x;
-    // XCD-aware chunk order (UNERF_SPLAT_XCD): workgroups go to the 8 XCDs round-robin, and chunk c writes, for every tile,
-    // the slots right behind chunk c - 1's.  With chunk = blockIdx the eight chunks that fill one 64-byte line of a tile's
-    // list run on eight different XCDs, each of which holds the line partially written in its own L2 (WRITE_SIZE 7.6 x the
-    // payload, rocprofv3 r4_09).  Giving every XCD a CONTIGUOUS eighth of the chunks makes it the only writer of (almost)
-    // every line it touches, and its ~128 co-resident waves are exactly consecutive chunks: the line fills while it is
-    // still in that L2.  Same slots, same lists.
-#if UNERF_SPLAT_XCD
-    const int cpx = (int)(gridDim.x >> 3);      // the launcher rounds the grid up to 8 x ceil(nblk / 8) workgroups
-    const int cid = (int)(blockIdx.x & 7u) * cpx + (int)(blockIdx.x >> 3);
-    if ((int64_t)cid * chunk >= I) return;      // (the whole single-wave workgroup: a slot past the last chunk)
-#else
+    // (chunk = blockIdx: an XCD-contiguous chunk order gained nothing, the scatter is bound by the number of store
+    // requests, not by where the partially written lines live -- docs/experiments.md 4.5.75)
     const int cid = (int)blockIdx.x;
-#endif
     {
         const uint32_t* row = table + (size_t)cid * T1;
 #pragma unroll 8
@@ -1766,7 +1753,7 @@ static int bin_sort_alternates(bool rocprim_depth, bool rocprim_scan, int tile_s
                            start, tile_bins, rs_one_seg(tp.nblk, I));
         hipLaunchKernelGGL(tile_apply_kernel, dim3(blocks_for(tp.T1, 256), TS_SEG), dim3(256), 0, st, table, rps, tp.T1, segsum,
                            start);
-        hipLaunchKernelGGL((tile_scatter_kernel<TKey>), dim3(UNERF_SPLAT_XCD ? ((tp.nblk + 7) / 8) * 8 : tp.nblk), dim3(64), lds, st,
+        hipLaunchKernelGGL((tile_scatter_kernel<TKey>), dim3(tp.nblk), dim3(64), lds, st,
                            tk_in, P.v_in, I, tp.chunk, tp.T1, table, gaussian_ids_sorted);
         if (isect_ids_sorted)
             hipLaunchKernelGGL(tile_isect_ids_kernel, dim3(blocks_for(I, 256)), dim3(256), 0, st, start, tp.T1,
@@ -1954,19 +1941,8 @@ __global__ __launch_bounds__(256) void raster_kernel(RasterArgs a) {
         if (BOUNDED) a.stop_idx += vw * hw;
         if (a.chan_max) a.chan_max += vw;
     }
-    // XCD-aware tile order (UNERF_SPLAT_XCD): every XCD rasterises a contiguous eighth of the row-major tile list -- a band of
-    // the image -- so the splats its tiles gather (neighbouring tiles share most of theirs) are looked up in ONE L2 instead
-    // of all eight.  Pure scheduling: a tile is computed exactly as before.
-#if UNERF_SPLAT_XCD
-    const int ntile = tbx * (int)gridDim.y;
-    const int lin = (int)(blockIdx.y * gridDim.x + blockIdx.x), tpx = (ntile + 7) >> 3;
-    const int tile = (lin & 7) * tpx + (lin >> 3);
-    if ((lin >> 3) >= tpx || tile >= ntile) return;      // the launcher pads the grid to at least 8 x ceil(ntile / 8) workgroups
-    const int bx = tile % tbx, by = tile / tbx;
-#else
     const int bx = blockIdx.x, by = blockIdx.y;
     const int tile = by * tbx + bx;
-#endif
     const int tr = threadIdx.x;
     // 16-wide tiles: a wave owns one 8 x 8 quadrant (wave w: quadrant column w & 1, row w >> 1; lane l: pixel (l & 7,
     // l >> 3) of it); narrower tiles keep the row-major mapping (no culling there)
@@ -2123,12 +2099,6 @@ static int splat_rasterize_impl(const char* what, int B, const int32_t* gaussian
     a.final_idx = final_idx; a.stop_idx = stop_idx; a.cull = (flags & UNERF_RASTER_NO_CULL) ? 0 : 1;
     a.chan_max = reinterpret_cast<unsigned int*>(chan_max); a.max_ch = chan_max ? max_channel : -1;
     dim3 grid((W + block_width - 1) / block_width, (H + block_width - 1) / block_width, B), block(256);
-#if UNERF_SPLAT_XCD
-    {   // linear ids 0 .. 8 ceil(ntile / 8) - 1 must exist: one more grid column covers the padding (tby >= 1 workgroups more)
-        const unsigned ntile = grid.x * grid.y, need = ((ntile + 7u) / 8u) * 8u;
-        if (grid.x * grid.y < need) grid.x += 1;
-    }
-#endif
     hipStream_t st = (hipStream_t)stream;
 #define UNERF_RASTER_CASE(N)                                                                       \
     case N:                                                                                        \

@@ -1,7 +1,7 @@
 """Build-time scan of the gfx950 code objects inside libunerf.so (lib.build_library runs it after every fresh compile).
 
 Why: the matrix kernels carry hand-placed instructions the compiler cannot see into -- the split-f16 residuals
-(v_fma_mixlo / mixhi_f16 in one inline-assembly statement), the Laplace heads' packed moment update -- and the hazard
+(v_fma_mixlo / mixhi_f16 in one inline-assembly statement) -- and the hazard
 recogniser does not look inside inline assembly.  Round 4 found MFMAs ONE instruction behind the v_fma_mixhi_f16 that
 completes their B operand (benchmarks/hazard_probe.hip: with no instruction between a VALU write of a VGPR and the MFMA
 that reads it, 97 % of the accumulators are wrong; with one wait state or more, none; the compiler keeps two for its own
@@ -120,8 +120,9 @@ def scan_listing(text: str) -> Tuple[List[str], Dict[str, Dict[str, int]]]:
     return hazards, stats
 
 
-def disassemble(path: str) -> List[str]:
-    """listings of the gfx950 code objects bundled in a HIP shared library"""
+def disassemble(path: str, tool: str = "llvm-objdump", args: Tuple[str, ...] = ("-d",)) -> List[str]:
+    """listings of the gfx950 code objects bundled in a HIP shared library (or what another llvm tool prints for each:
+    benchmarks/isa_diff.py reads their notes)"""
     objdump = os.path.join(LLVM_BIN, "llvm-objdump")
     if not os.path.exists(objdump):
         raise FileNotFoundError(objdump)
@@ -133,7 +134,7 @@ def disassemble(path: str) -> List[str]:
         outs = []
         for f in sorted(os.listdir(tmp)):
             if "amdgcn" in f:
-                res = subprocess.run([objdump, "-d", os.path.join(tmp, f)], capture_output=True, text=True, check=True)
+                res = subprocess.run([os.path.join(LLVM_BIN, tool), *args, os.path.join(tmp, f)], capture_output=True, text=True, check=True)
                 outs.append(res.stdout)
         return outs
     finally:

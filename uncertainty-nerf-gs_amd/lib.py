@@ -17,15 +17,13 @@ INCLUDE = os.path.join(os.path.dirname(_HERE), "include")
 # UNERF_LIB: another build of the same ABI, for A/B timing on one box (benchmarks/ab_bench.sh); unset in normal use
 LIB_PATH = os.environ.get("UNERF_LIB") or os.path.join(CSRC, "libunerf.so")
 SOURCES = ["unerf_nerf.hip", "unerf_splat.hip", "unerf_metrics.hip", "unerf_lpips.hip"]
-# text included by the sources (unerf_nerf.hip compiles the f16 matrix field kernels from the two .inc files under two names each)
-INCLUDED = ["unerf_common.hpp", "unerf_field_mfma16.inc", "unerf_field_lap16.inc"]
 # -amdgpu-mfma-vgpr-form: gfx950 has one unified register file; let the MFMAs write their accumulators to
 # ordinary VGPRs so ReLU / dropout / the next layer's B operand read them without v_accvgpr_read copies
 # (97 copies per tile in the K-pass kernel, which is VALU-issue-bound; rocprof r1_04).
 # -fno-slp-vectorize: the one KNOWN trigger of run-to-run differences in the split-f16 field kernels is code the SLP
-# vectoriser makes (packed v_pk_mul_f32 forms of the position x scale products in front of the hash): the fused-blend
-# experiment build (UNERF_FIELD_BLEND_FMA=1) differs from launch to launch with it and repeats bit for bit without it
-# (profiles/r5_exp_blend_defect.jsonl).  The shipped sources never showed the defect, but the flag costs
+# vectoriser makes (packed v_pk_mul_f32 forms of the position x scale products in front of the hash): an experiment
+# build with fused lerps in the field kernels' grid blend differed from launch to launch with it and repeated bit for bit
+# without it (docs/experiments.md, profiles/r5_exp_blend_defect.jsonl).  The shipped sources never showed the defect, but the flag costs
 # nothing (same frame times, same bits: every hot loop is written on explicit 2-vectors) and removes the trigger class.
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-std=c++17", "-fPIC", "-shared",
                "-fno-slp-vectorize", "-mllvm", "-amdgpu-mfma-vgpr-form"]
@@ -39,13 +37,62 @@ class UnerfError(RuntimeError):
     pass
 
 
-def _source_digest() -> str:
+def _source_digest(csrc: str = CSRC) -> str:
+    """Content hash of everything a build reads: the flags, every .hip / .hpp / .inc of `csrc` (by name, sorted -- a new
+    header counts without being listed anywhere) and include/unerf.h."""
     import hashlib
     h = hashlib.sha256(" ".join(HIPCC_FLAGS).encode())
-    for f in [os.path.join(CSRC, s) for s in SOURCES + INCLUDED] + [os.path.join(INCLUDE, "unerf.h")]:
+    names = sorted(n for n in os.listdir(csrc) if n.endswith((".hip", ".hpp", ".inc")))
+    for f in [os.path.join(csrc, n) for n in names] + [os.path.join(INCLUDE, "unerf.h")]:
+        h.update(os.path.basename(f).encode())
         with open(f, "rb") as fh:
             h.update(fh.read())
     return h.hexdigest()
+
+
+def compile_command(out: str, extra_args=(), replace: Optional[tuple] = None) -> list:
+    """The one hipcc command line of a libunerf build: HIPCC_FLAGS, `extra_args` (-D...), every entry of SOURCES.
+    replace = (name, path): `path` is compiled in place of csrc/<name> (a patched copy: benchmarks/probe_source.py), with
+    csrc/ on the include path so that the copy finds the texts it includes."""
+    paths = {s: os.path.join(CSRC, s) for s in SOURCES}
+    cmd = [os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")] + HIPCC_FLAGS + list(extra_args) + ["-I", INCLUDE]
+    if replace is not None:
+        name, path = replace
+        if name not in paths:
+            raise UnerfError(f"{name} is not one of {SOURCES}")
+        paths[name] = path
+        cmd += ["-I", CSRC]
+    return cmd + ["-o", out] + [paths[s] for s in SOURCES]
+
+
+def compile_library(out: str, extra_args=(), replace: Optional[tuple] = None, verbose: bool = False) -> str:
+    """Compile all of SOURCES for gfx950 into `out` (compile_command) and run the ISA hazard check on the result, which
+    is removed if the check refuses it.  The product build and every A/B variant (benchmarks/build_variant.py) come
+    through here."""
+    cmd = compile_command(out, extra_args, replace)
+    ver = subprocess.run([cmd[0], "--version"], capture_output=True, text=True).stdout
+    if VALIDATED_HIPCC not in ver:
+        import warnings
+        warnings.warn(f"libunerf: building with {ver.splitlines()[0] if ver else cmd[0]!r}; the kernels were validated with "
+                      f"'{VALIDATED_HIPCC}*' (run tests/test_gpu_repeatability.py on the GPU before trusting this build)")
+    if verbose:
+        print(" ".join(cmd))
+    res = subprocess.run(cmd, capture_output=True, text=True)
+    if res.returncode != 0:
+        raise UnerfError("hipcc failed:\n" + res.stdout + res.stderr)
+    # the listing of what was just built: no MFMA may read a VGPR within two wait states of the VALU instruction that
+    # writes it (the compiler guarantees that for its own instructions, nobody does for inline assembly: isa_check.py)
+    if not os.environ.get("UNERF_SKIP_ISA_CHECK"):
+        from . import isa_check
+        try:
+            isa_check.check_library(out, verbose=verbose)
+        except isa_check.IsaHazard as e:
+            os.remove(out)
+            raise UnerfError(f"libunerf: refused by the ISA check -- {e}")
+        except (FileNotFoundError, subprocess.CalledProcessError) as e:
+            import warnings
+            warnings.warn(f"libunerf: ISA check skipped ({e})")
+    return out
 
 
 def build_library(force: bool = False, verbose: bool = False) -> str:
@@ -71,31 +118,8 @@ def build_library(force: bool = False, verbose: bool = False) -> str:
         try:
             if not force and fresh():   # another rank built it while we waited
                 return LIB_PATH
-            hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-            ver = subprocess.run([hipcc, "--version"], capture_output=True, text=True).stdout
-            if VALIDATED_HIPCC not in ver:
-                import warnings
-                warnings.warn(f"libunerf: building with {ver.splitlines()[0] if ver else hipcc!r}; the kernels were validated with "
-                              f"'{VALIDATED_HIPCC}*' (run tests/test_gpu_repeatability.py on the GPU before trusting this build)")
             tmp = f"{LIB_PATH}.tmp.{os.getpid()}"
-            cmd = [hipcc] + HIPCC_FLAGS + ["-I", INCLUDE, "-o", tmp] + [os.path.join(CSRC, s) for s in SOURCES]
-            if verbose:
-                print(" ".join(cmd))
-            res = subprocess.run(cmd, capture_output=True, text=True)
-            if res.returncode != 0:
-                raise UnerfError("hipcc failed:\n" + res.stdout + res.stderr)
-            # the listing of what was just built: no MFMA may read a VGPR within two wait states of the VALU instruction that
-            # writes it (the compiler guarantees that for its own instructions, nobody does for inline assembly: isa_check.py)
-            if not os.environ.get("UNERF_SKIP_ISA_CHECK"):
-                from . import isa_check
-                try:
-                    isa_check.check_library(tmp, verbose=verbose)
-                except isa_check.IsaHazard as e:
-                    os.remove(tmp)
-                    raise UnerfError(f"libunerf: refused by the ISA check -- {e}")
-                except (FileNotFoundError, subprocess.CalledProcessError) as e:
-                    import warnings
-                    warnings.warn(f"libunerf: ISA check skipped ({e})")
+            compile_library(tmp, verbose=verbose)
             os.replace(tmp, LIB_PATH)
             with open(stamp, "w") as f:
                 f.write(digest)
