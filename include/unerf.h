@@ -488,6 +488,28 @@ int unerf_pose_grad(const float* origins, const float* directions, const float* 
                     int background, const float* background_rgb_host, const float* rot_inv_host,
                     float* out_grad, float* out_rgb, void* stream);
 
+/* The same gradient of an MC-DROPOUT frame under a NAMED mask draw: rgb = (1/K) sum_k clamp(pred_k), pass k evaluated with
+ * the keep masks of that pass, and out_grad = (1/K) sum_k of unerf_pose_grad's quantity of pass k (each pass with its own
+ * clamp gate, nan_to_num, background rule and last-sample term).  One launch whatever K is: the grid lookup and trunk
+ * layer 0 lie in front of every Dropout site and are evaluated once, the adjoints of all passes are summed in front of them.
+ *   p     : mode MCDROPOUT, K = p->K >= 1, nerfacto's widths, either grid layout (grid_half widened on read); fp32, the
+ *           blobs are not read.  Active sites: p->drop_sites (0 = TRUNK | HEAD1), any combination of TRUNK, HEAD0, HEAD1.
+ *   masks : NULL = the counter generator (csrc/unerf_common.hpp) for sample index (ray_offset + r) S + s, seed p->seed and
+ *           the site's stream id -- the masks unerf_field_fwd draws for these rays; else the bit arrays of
+ *           unerf_field_fwd_masked (row sample_offset + r S + s, pass_stride), and ray_offset / p->seed are not read.
+ *           A kept unit is multiplied by 1/(1 - p_drop); a dropped one is exactly 0, and so is its adjoint.
+ *   out_grad [R,6] / [R,12] as unerf_pose_grad (same rot_inv_host epilogue); out_rgb NULL or [R,3] = the mean colour.
+ * With K = 1, p_drop = 0 and all-ones explicit masks both outputs equal unerf_pose_grad's bit for bit.  Two calls with the
+ * same inputs return the same bits.  UNERF_ERR_ARG before any launch: another mode, K < 1, UNERF_DROP_HEADIN, other
+ * widths, near_plane < 0, S outside [1, 64]; with masks: an active site without its array, an array for an inactive
+ * site, pass_stride < sample_offset + R S. */
+int unerf_pose_grad_mc(const float* origins, const float* directions, const float* sbins, int64_t R, int S,
+                       float near_plane, float far_plane, int spacing, int64_t ray_offset,
+                       const unerf_field_params* p /* host struct */,
+                       const unerf_keep_masks* masks /* host struct; NULL = the counter generator */,
+                       int background, const float* background_rgb_host, const float* rot_inv_host,
+                       float* out_grad, float* out_rgb, void* stream);
+
 /* ------------------------------------------------- composite + variance --
  * Replaces RaySamples.get_weights + RGB/Accumulation/Depth(median,expected)/Uncertainty
  * renderers + the depth-variance sum at models/activenerfacto/activenerfacto_model.py:94-112

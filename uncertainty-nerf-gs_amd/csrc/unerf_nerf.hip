@@ -4246,6 +4246,377 @@ extern "C" int unerf_pose_grad(const float* origins, const float* directions, co
     return unerf_check_launch("pose_grad");
 }
 
+// --------------------------------------------------------------------------------------
+// 5e'. The same gradient of an MC-DROPOUT frame under a named mask draw: rgb = (1/K) sum_k clamp(pred_k), pass k with the
+// keep masks of (seed, pass, sample, unit) -- the counter generator's, or explicit bit arrays (unerf_keep_masks).  Under a
+// fixed draw every pass is the deterministic piecewise-smooth function pose_grad_kernel differentiates, with h -> h keep /
+// (1 - p) behind the ReLU of each active site; the adjoint of that is the same factor.  Dropout sits BEHIND trunk layer 0, so
+// the grid lookup and layer 0 do not depend on the pass, and the adjoints of all passes are summed in front of them:
+//   once      grid lookup -> F[32] -> layer 0 -> ReLU bits m0, activations H0 (a second LDS panel, kept for all passes)
+//   per pass  A <- H0 keep_T scale; layer 1 -> sigma_k, geo; colour head with keep_0 / keep_1; compositing and its adjoints;
+//             head and trunk backward down to the layer-0 pre-activation: G[64] += (m0 & keep_T) scale A   (registers)
+//   once      W0^T G -> dfeat[32]; grid backward (the corner rows fetched the second and last time); contraction; ray sums
+// One wave = one ray = one block (two 16-KiB panels, 256 VGPRs + 188 AGPRs, no scratch: one wave per SIMD -- DESIGN.md 4.6a);
+// the sums over passes run k = 0 .. K-1: two calls return the same bits.
+// With K = 1 and every unit kept at scale 1.0 each statement of a pass is pose_grad_kernel's, in its order.
+// --------------------------------------------------------------------------------------
+struct PoseGradMcArgs {
+    KeepArgs xm;          // explicit masks: site[] = TRUNK, HEAD0, HEAD1 (counter mode: all NULL)
+    int explicit_masks;
+    int K;
+    int keep_all;         // counter mode: the threshold keeps every unit (p <= 2^-17)
+    int32_t keep_hi;      // counter mode: thr_s << 16
+    uint32_t key;         // counter mode: unerf_mc_key(seed, 0)
+    uint32_t sample0;     // counter mode: ray_offset * S
+    float scale[3];       // 1 / (1 - p) at an active site, 1 at an inactive one (TRUNK, HEAD0, HEAD1)
+    int active[3];
+    float inv_k;
+};
+
+struct PoseGradWeights {   // the layers behind trunk layer 0 (the pass loop of pose_grad_mc_kernel)
+    const float *w1t, *b1, *h0t, *hb0, *h1t, *hb1, *h2t, *hb2;
+};
+// keep bits (bit u = unit u kept) of one 64-unit site of this lane's sample at pass k.  Counter mode: the words of
+// mc_keep_bits_kernel, made and stepped by the same functions.
+template <uint32_t STREAM>
+__device__ __forceinline__ void pgmc_keep_bits(const PoseGradMcArgs& m, int site, const uint32_t (&bh)[2], int k, int64_t n,
+                                               uint32_t (&bits)[2]) {
+    bits[0] = bits[1] = 0xFFFFFFFFu;
+    if (!m.active[site]) return;   // uniform
+    if (m.explicit_masks) {
+        const uint32_t* row = xm_row(m.xm, site, k, n);
+        bits[0] = row[0];
+        bits[1] = row[1];
+        return;
+    }
+    if (m.keep_all) return;
+    uint32_t word[32];
+#pragma unroll
+    for (int j = 0; j < 32; ++j) word[j] = unerf_mask_word0(bh[(j >> 1) & 1], STREAM, (uint32_t)j);
+    for (int q = 0; q < k; ++q) {
+#pragma unroll
+        for (int j = 0; j < 32; ++j) word[j] = unerf_mask_step(word[j]);
+    }
+    bits[0] = bits[1] = 0u;
+#pragma unroll
+    for (int j = 0; j < 32; ++j) {
+        bits[j >> 4] |= (unerf_keep_lo(word[j], m.keep_hi) ? 1u : 0u) << ((2 * j) & 31);
+        bits[j >> 4] |= (unerf_keep_hi(word[j], m.keep_hi) ? 1u : 0u) << ((2 * j + 1) & 31);
+    }
+}
+// ReLU, then the site's dropout: row o <- keep ? max(v, 0) scale : 0
+__device__ __forceinline__ void pgmc_store_relu_keep(float* act, int lane, const float (&v)[64], const uint32_t (&keep)[2], float scale) {
+#pragma unroll
+    for (int o = 0; o < 64; ++o) act[o * 64 + lane] = ((keep[o >> 5] >> (o & 31)) & 1u) ? fmaxf(v[o], 0.f) * scale : 0.f;
+}
+
+template <int GRID>
+__global__ __launch_bounds__(64) void pose_grad_mc_kernel(PoseGradArgs a, PoseGradMcArgs m) {
+    extern __shared__ float lds[];
+    const int lane = threadIdx.x;
+    float* A = lds;               // the working panel [64 units][64 lanes] of pose_grad_kernel
+    float* H0 = lds + 64 * 64;    // relu(layer 0), kept for every pass
+    const int64_t r = blockIdx.x;
+    if (r >= a.R) return;
+    const int S = a.S;
+    const bool in = lane < S;
+    const int i = in ? lane : S - 1;
+    const uint32_t mask = GRID == 0 ? (1u << a.p.log2T) - 1u : 0u;
+    const int64_t n = r * S + i;   // this lane's sample in the launch
+    // ---- sample position, normalisation ----
+    const float* sb = a.sbins + r * (S + 1);
+    const float e0 = unerf_s2e(sb[i], a.s_near, a.s_far, a.lin), e1 = unerf_s2e(sb[i + 1], a.s_near, a.s_far, a.lin);
+    const float delta = e1 - e0, t2 = e0 + e1;
+    const float ox = a.origins[r * 3 + 0], oy = a.origins[r * 3 + 1], oz = a.origins[r * 3 + 2];
+    const float dxr = a.dirs[r * 3 + 0], dyr = a.dirs[r * 3 + 1], dzr = a.dirs[r * 3 + 2];
+    const float x0 = ox + dxr * t2 / 2.f, y0 = oy + dyr * t2 / 2.f, z0 = oz + dzr * t2 / 2.f;
+    float px = x0, py = y0, pz = z0;
+    const float sel = unerf_normalize_position(px, py, pz, a.box);
+
+    // ---- once: grid -> layer 0 ----
+#pragma unroll 4   // (one wave per SIMD: the gathers of four levels in flight; the registers are there)
+    for (int l = 0; l < 16; ++l) {
+        float2 f[8];
+        float wx, wy, wz, scale;
+        pg_level_corners<GRID>(a, l, mask, px, py, pz, f, wx, wy, wz, scale);
+        const float2 e = GRID == 0 ? unerf_blend8(f, wx, wy, wz) : unerf_tcnn_blend(f, wx, wy, wz);
+        A[(2 * l) * 64 + lane] = e.x;
+        A[(2 * l + 1) * 64 + lane] = e.y;
+    }
+    uint32_t m0[2];
+    {
+        float acc[64];
+        pg_dense<32, 64>(pg_const(a.p.w0t), pg_const(a.p.b0), A, lane, acc);
+        relu_mask64(acc, m0);
+        store_act<64>(H0, lane, acc, 0, true);
+    }
+    float ux = (dxr + 1.f) / 2.f, uy = (dyr + 1.f) / 2.f, uz = (dzr + 1.f) / 2.f;
+    if (a.p.sh_remap) {
+        ux = ux * 2.f - 1.f;
+        uy = uy * 2.f - 1.f;
+        uz = uz * 2.f - 1.f;
+    }
+    uint32_t bh[2] = {0u, 0u};
+    if (!m.explicit_masks) {
+        const uint32_t pre = unerf_mc_pre(m.key, m.sample0 + (uint32_t)n);
+        bh[0] = unerf_mc_base_h(pre, 0u);
+        bh[1] = unerf_mc_base_h(pre, 1u);
+    }
+    const bool last_bg = a.bg_mode == UNERF_BG_LAST_SAMPLE;
+    const int rl = 63 - lane;
+    float G[64];   // running adjoint of the layer-0 pre-activation, summed over the passes
+#pragma unroll
+    for (int o = 0; o < 64; ++o) G[o] = 0.f;
+    float gdx = 0.f, gdy = 0.f, gdz = 0.f;   // the SH term of ds/dd, summed over the passes
+    float rgb_sum[3] = {0.f, 0.f, 0.f};
+
+#pragma unroll 1
+    for (int k = 0; k < m.K; ++k) {
+        uint32_t kt[2], k0[2], k1[2];
+        pgmc_keep_bits<0u>(m, 0, bh, k, n, kt);
+        pgmc_keep_bits<2u>(m, 1, bh, k, n, k0);
+        pgmc_keep_bits<1u>(m, 2, bh, k, n, k1);
+        // The weight pointers pass an empty asm once per pass: as loop invariants the compiler hoists scalar weight loads
+        // out of the pass loop and spills them into VGPR lanes (365 spilled SGPRs without this, 249 with it; the rest are
+        // the hoisted multiplier constants of the mask words).  Worth 2 % at K = 1 together with the level unrolling.
+        PoseGradWeights wp = {a.p.w1t, a.p.b1, a.p.h0t, a.p.hb0, a.p.h1t, a.p.hb1, a.p.h2t, a.p.hb2};
+        asm volatile("" : "+s"(wp.w1t), "+s"(wp.b1), "+s"(wp.h0t), "+s"(wp.hb0), "+s"(wp.h1t), "+s"(wp.hb1), "+s"(wp.h2t), "+s"(wp.hb2));
+        // ---- forward: dropout on layer 0's activations -> trunk layer 1 -> colour head ----
+#pragma unroll 8
+        for (int o = 0; o < 64; ++o) A[o * 64 + lane] = ((kt[o >> 5] >> (o & 31)) & 1u) ? H0[o * 64 + lane] * m.scale[0] : 0.f;
+        float o1[16];
+        pg_dense<64, 16>(pg_const(wp.w1t), pg_const(wp.b1), A, lane, o1);
+        const float sig = a.p.average_init_density * expf(o1[0]) * sel;
+        {
+            float sh[16];
+            unerf_sh16(ux, uy, uz, sh);
+            store_act<16>(A, lane, sh, 0, false);
+        }
+#pragma unroll
+        for (int g = 0; g < 15; ++g) A[(16 + g) * 64 + lane] = o1[1 + g];
+        float acc[64];
+        uint32_t m1[2], m2[2];
+        pg_dense<31, 64>(pg_const(wp.h0t), pg_const(wp.hb0), A, lane, acc);
+        relu_mask64(acc, m1);
+        pgmc_store_relu_keep(A, lane, acc, k0, m.scale[1]);
+        pg_dense<64, 64>(pg_const(wp.h1t), pg_const(wp.hb1), A, lane, acc);
+        relu_mask64(acc, m2);
+        pgmc_store_relu_keep(A, lane, acc, k1, m.scale[2]);
+        float c[3];
+        pg_dense<64, 3>(pg_const(wp.h2t), pg_const(wp.hb2), A, lane, c);
+#pragma unroll
+        for (int q = 0; q < 3; ++q) c[q] = unerf_nan_to_num(unerf_sigmoid(c[q]));
+
+        // ---- compositing and its adjoints, per pass (pose_grad_kernel's scans) ----
+        const float dd = in ? delta * sig : 0.f;
+        const float em = expf(-dd);
+        const float T = expf(-group_excl_scan<64>(dd, lane));
+        const float w = in ? unerf_nan_to_num((1.f - em) * T) : 0.f;
+        const float Tf = 1.f - group_sum<64>(w);
+        const float sw = __shfl(group_excl_scan<64>(__shfl(w, rl, 64), lane), rl, 64);
+        float dsig = 0.f, dc[3];
+#pragma unroll
+        for (int q = 0; q < 3; ++q) {
+            const float bg = last_bg ? __shfl(c[q], S - 1, 64) : a.bg[q];
+            const float wc = w * c[q];
+            const float swc = __shfl(group_excl_scan<64>(__shfl(wc, rl, 64), lane), rl, 64);
+            const float pred = group_sum<64>(wc) + Tf * bg;
+            const float live = (pred >= 0.f && pred <= 1.f && in) ? 1.f / 3.f : 0.f;
+            dsig += live * delta * (em * T * (c[q] - bg) - swc + bg * sw);
+            const float wt = w + ((last_bg && lane == S - 1) ? Tf : 0.f);
+            dc[q] = live * wt * c[q] * (1.f - c[q]);
+            rgb_sum[q] += fminf(fmaxf(pred, 0.f), 1.f);
+        }
+
+        // ---- backward: colour head (the adjoint of a dropout site is its own factor) ----
+        m2[0] &= k1[0]; m2[1] &= k1[1];
+        m1[0] &= k0[0]; m1[1] &= k0[1];
+        float d[64];
+        const pg_cfp h2t = pg_const(wp.h2t);
+#pragma unroll
+        for (int o = 0; o < 64; ++o) {
+            const float v = fmaf(dc[2], h2t[o * 3 + 2], fmaf(dc[1], h2t[o * 3 + 1], dc[0] * h2t[o * 3 + 0]));
+            d[o] = ((m2[o >> 5] >> (o & 31)) & 1u) ? v * m.scale[2] : 0.f;
+        }
+        pg_dense_bwd<64, 64>(pg_const(wp.h1t), d, A, lane);
+        load_masked64(A, lane, m1, d);
+#pragma unroll
+        for (int o = 0; o < 64; ++o) d[o] *= m.scale[1];
+        pg_dense_bwd<31, 64>(pg_const(wp.h0t), d, A, lane);   // rows 0..15: dSH, 16..30: dgeo
+        {
+            float q[16];
+#pragma unroll
+            for (int j = 0; j < 16; ++j) q[j] = A[j * 64 + lane];
+            const float x = ux, y = uy, z = uz, xx = x * x, yy = y * y, zz = z * z;
+            const float c1 = 0.4886025119029199f, c2 = 1.0925484305920792f, c6 = 0.9461746957575601f, c8 = 0.5462742152960396f,
+                        c9 = 0.5900435899266435f, c10 = 2.890611442640554f, c11 = 0.4570457994644658f, c12 = 0.3731763325901154f,
+                        c14 = 1.445305721320277f;
+            const float z5 = 5.f * zz - 1.f, d3 = 3.f * (xx - yy);
+            float sx = q[3] * c1 + q[4] * (c2 * y) + q[7] * (c2 * z) + q[8] * (2.f * c8 * x) + q[9] * (6.f * c9 * x * y) + q[10] * (c10 * y * z) +
+                       q[13] * (c11 * z5) + q[14] * (2.f * c14 * x * z) + q[15] * (c9 * d3);
+            float sy = q[1] * c1 + q[4] * (c2 * x) + q[5] * (c2 * z) - q[8] * (2.f * c8 * y) + q[9] * (c9 * d3) + q[10] * (c10 * x * z) +
+                       q[11] * (c11 * z5) - q[14] * (2.f * c14 * y * z) - q[15] * (6.f * c9 * x * y);
+            float sz = q[2] * c1 + q[5] * (c2 * y) + q[6] * (2.f * c6 * z) + q[7] * (c2 * x) + q[10] * (c10 * x * y) + q[11] * (10.f * c11 * y * z) +
+                       q[12] * (c12 * (15.f * zz - 3.f)) + q[13] * (10.f * c11 * x * z) + q[14] * (c14 * (xx - yy));
+            const float du = a.p.sh_remap ? 1.f : 0.5f;
+            gdx += sx * du;
+            gdy += sy * du;
+            gdz += sz * du;
+        }
+        // ---- backward: trunk layer 1, down to the layer-0 pre-activation ----
+        float d1[16];
+        d1[0] = dsig * sig;
+#pragma unroll
+        for (int g = 0; g < 15; ++g) d1[1 + g] = A[(16 + g) * 64 + lane];
+        pg_dense_bwd<64, 16>(pg_const(wp.w1t), d1, A, lane);
+        const uint32_t e0m[2] = {m0[0] & kt[0], m0[1] & kt[1]};
+#pragma unroll
+        for (int o = 0; o < 64; ++o) G[o] += ((e0m[o >> 5] >> (o & 31)) & 1u) ? A[o * 64 + lane] * m.scale[0] : 0.f;
+    }
+
+    // ---- once: layer 0 backward, grid -> normalised position ----
+    pg_dense_bwd<32, 64>(pg_const(a.p.w0t), G, A, lane);   // rows 2l, 2l+1: adjoint of level l's features
+    float gpx = 0.f, gpy = 0.f, gpz = 0.f;
+#pragma unroll 4   // (one wave per SIMD: the gathers of four levels in flight; the registers are there)
+    for (int l = 0; l < 16; ++l) {
+        float2 f[8];
+        float wx, wy, wz, scale;
+        pg_level_corners<GRID>(a, l, mask, px, py, pz, f, wx, wy, wz, scale);
+        const float g0 = A[(2 * l) * 64 + lane], g1 = A[(2 * l + 1) * 64 + lane];
+        float v[8];
+#pragma unroll
+        for (int q = 0; q < 8; ++q) v[q] = fmaf(g1, f[q].y, g0 * f[q].x);
+        float bx, by, bz;
+        pg_blend_grad<GRID>(v, wx, wy, wz, bx, by, bz);
+        gpx = fmaf(scale, bx, gpx);
+        gpy = fmaf(scale, by, gpy);
+        gpz = fmaf(scale, bz, gpz);
+    }
+    // ---- normalised position -> world position (pose_grad_kernel's statements) ----
+    float gx = gpx * sel, gy = gpy * sel, gz = gpz * sel;
+    if (a.box.use_aabb) {   // uniform
+        gx /= a.box.len[0];
+        gy /= a.box.len[1];
+        gz /= a.box.len[2];
+    } else {
+        gx *= 0.25f;
+        gy *= 0.25f;
+        gz *= 0.25f;
+        const float ax = fabsf(x0), ay = fabsf(y0), az = fabsf(z0);
+        const float mm = fmaxf(fmaxf(ax, ay), az);
+        if (!(mm < 1.f)) {
+            const float inv = 1.f / mm, diag = (2.f - inv) * inv, cross = 2.f * (1.f - mm) * inv * inv * inv;
+            const int kk = (ax >= ay && ax >= az) ? 0 : (ay >= az ? 1 : 2);
+            const float dot = (kk == 0 ? 0.f : gx * x0) + (kk == 1 ? 0.f : gy * y0) + (kk == 2 ? 0.f : gz * z0);
+            const float xk = kk == 0 ? x0 : (kk == 1 ? y0 : z0), gk = kk == 0 ? gx : (kk == 1 ? gy : gz);
+            const float along = gk * inv * inv + cross * (xk < 0.f ? -dot : dot);
+            gx = kk == 0 ? along : gx * diag;
+            gy = kk == 1 ? along : gy * diag;
+            gz = kk == 2 ? along : gz * diag;
+        }
+    }
+    if (!in) gx = gy = gz = gdx = gdy = gdz = 0.f;
+    const float th = t2 / 2.f;
+    const float go0 = group_sum<64>(gx) * m.inv_k, go1 = group_sum<64>(gy) * m.inv_k, go2 = group_sum<64>(gz) * m.inv_k;
+    const float gd0 = group_sum<64>(fmaf(th, gx, gdx)) * m.inv_k, gd1 = group_sum<64>(fmaf(th, gy, gdy)) * m.inv_k,
+                gd2 = group_sum<64>(fmaf(th, gz, gdz)) * m.inv_k;
+
+    // ---- epilogue: every store is a vector store of a lane-selected value ----
+    if (a.pose) {
+        const float gdd = gd0 * dxr + gd1 * dyr + gd2 * dzr;
+        const float P[3] = {gd0 - dxr * gdd, gd1 - dyr * gdd, gd2 - dzr * gdd};
+        const float go[3] = {go0, go1, go2};
+        const int row = lane >> 2, col = lane & 3;
+        const float Pa = row == 0 ? P[0] : (row == 1 ? P[1] : P[2]);
+        const float ga = row == 0 ? go[0] : (row == 1 ? go[1] : go[2]);
+        const int cb = col < 3 ? col : 0;
+        const float q = a.rinv[cb * 3 + 0] * dxr + a.rinv[cb * 3 + 1] * dyr + a.rinv[cb * 3 + 2] * dzr;
+        if (lane < 12) a.out_grad[r * 12 + lane] = col == 3 ? ga : Pa * q;
+    } else {
+        const float v6 = lane == 0 ? go0 : lane == 1 ? go1 : lane == 2 ? go2 : lane == 3 ? gd0 : lane == 4 ? gd1 : gd2;
+        if (lane < 6) a.out_grad[r * 6 + lane] = v6;
+    }
+    if (a.out_rgb && lane < 3) {
+        const float pv = lane == 0 ? rgb_sum[0] : (lane == 1 ? rgb_sum[1] : rgb_sum[2]);
+        a.out_rgb[r * 3 + lane] = pv * m.inv_k;
+    }
+}
+
+extern "C" int unerf_pose_grad_mc(const float* origins, const float* directions, const float* sbins, int64_t R, int S,
+                                  float near_plane, float far_plane, int spacing, int64_t ray_offset, const unerf_field_params* p,
+                                  const unerf_keep_masks* masks, int background, const float* background_rgb,
+                                  const float* rot_inv, float* out_grad, float* out_rgb, void* stream) {
+    UNERF_REQUIRE(R >= 0 && S >= 1 && S <= 64, "pose_grad_mc: S=%d outside [1,64]", S);
+    if (R == 0) return UNERF_OK;
+    UNERF_REQUIRE(origins && directions && sbins && p && out_grad, "pose_grad_mc: null pointer");
+    UNERF_REQUIRE(p->mode == UNERF_FIELD_MCDROPOUT, "pose_grad_mc: mode %d (an MCDROPOUT field is needed; unerf_pose_grad differentiates "
+                  "the deterministic fields, the Laplace field's sampled heads are not differentiated)", p->mode);
+    UNERF_REQUIRE(p->K >= 1, "pose_grad_mc: K=%d, the mean over passes needs K >= 1", p->K);
+    UNERF_REQUIRE(p->p_drop >= 0.f && p->p_drop < 1.f, "pose_grad_mc: bad p_drop=%g", (double)p->p_drop);
+    UNERF_REQUIRE((p->drop_sites & ~DROP_SITES_KNOWN) == 0, "pose_grad_mc: unknown bits in drop_sites=%d", p->drop_sites);
+    UNERF_REQUIRE(!(p->drop_sites & UNERF_DROP_HEADIN), "pose_grad_mc: UNERF_DROP_HEADIN is out of scope (not built)");
+    UNERF_REQUIRE(p->hidden == 0 && p->hidden_color == 0 && p->geo_dim == 0 && p->feat_per_level == 0 && p->L == 16,
+                  "pose_grad_mc: nerfacto's widths only (hidden 64 / 64, geo 15, 2 features x 16 levels); the any-width kernel is out of scope");
+    UNERF_REQUIRE(p->out1 == 16, "pose_grad_mc: trunk output %d does not fit mode %d", p->out1, p->mode);
+    UNERF_REQUIRE(p->table && p->w0t && p->b0 && p->w1t && p->b1 && p->h0t && p->hb0 && p->h1t && p->hb1 && p->h2t && p->hb2 &&
+                      (p->scalings || p->tcnn_levels),
+                  "pose_grad_mc: null field pointer");
+    UNERF_REQUIRE(p->tcnn_levels || (p->log2T >= 1 && p->log2T <= 24), "pose_grad_mc: bad log2T=%d", p->log2T);
+    UNERF_REQUIRE(p->tcnn_levels || !p->grid_half, "pose_grad_mc: grid_half needs a tcnn-layout grid");
+    UNERF_REQUIRE(near_plane >= 0.f, "pose_grad_mc: near_plane=%g (spacing-domain bins only)", (double)near_plane);
+    const int sites = requested_drop_sites(*p);
+    PoseGradMcArgs m;
+    m.explicit_masks = masks ? 1 : 0;
+    m.K = p->K;
+    m.inv_k = 1.f / (float)p->K;
+    const float scale = 1.f / (1.f - p->p_drop);
+    for (int i = 0; i < 3; ++i) {
+        m.active[i] = (sites >> i) & 1;
+        m.scale[i] = m.active[i] ? scale : 1.f;
+        m.xm.site[i] = NULL;
+    }
+    m.xm.pass_stride = 0;
+    m.xm.sample_offset = 0;
+    m.keep_all = 0; m.keep_hi = 0; m.key = 0u; m.sample0 = 0u;
+    if (masks) {
+        static const char* const names[4] = {"TRUNK", "HEAD0", "HEAD1", "HEADIN"};
+        for (int i = 0; i < 4; ++i) {
+            UNERF_REQUIRE(!((sites >> i) & 1) || masks->site[i], "pose_grad_mc: site %s is active (drop_sites=%d) but its mask array is NULL", names[i], sites);
+            UNERF_REQUIRE(((sites >> i) & 1) || !masks->site[i], "pose_grad_mc: a mask array for site %s, which is not active (drop_sites=%d)", names[i], sites);
+        }
+        UNERF_REQUIRE(masks->sample_offset >= 0 && masks->pass_stride >= masks->sample_offset + R * (int64_t)S,
+                      "pose_grad_mc: pass_stride=%lld < sample_offset + R*S = %lld + %lld", (long long)masks->pass_stride,
+                      (long long)masks->sample_offset, (long long)(R * (int64_t)S));
+        for (int i = 0; i < 3; ++i) m.xm.site[i] = masks->site[i];
+        m.xm.pass_stride = masks->pass_stride;
+        m.xm.sample_offset = masks->sample_offset;
+    } else {   // the counter generator: threshold and key as unerf_field_fwd / unerf_mc_keep_bits make them
+        UNERF_REQUIRE(ray_offset >= 0 && (uint64_t)(ray_offset + R) * (uint64_t)S < (1ull << 32),
+                      "pose_grad_mc: sample index exceeds 32 bits (RNG counter)");
+        const long thr = lrint((1.0 - (double)p->p_drop) * 65536.0);
+        const int32_t thr_s = (int32_t)(thr < 65536 ? thr : 65535) - 32768;
+        m.keep_hi = (int32_t)((uint32_t)thr_s << 16);
+        m.keep_all = thr >= 65536 ? 1 : 0;
+        m.key = unerf_mc_key(p->seed, 0u);
+        m.sample0 = (uint32_t)((uint64_t)ray_offset * (uint64_t)S);
+    }
+    PoseGradArgs g;
+    g.origins = origins; g.dirs = directions; g.sbins = sbins; g.R = R; g.S = S;
+    if (int rc = set_spacing(g, near_plane, far_plane, spacing)) return rc;
+    g.p = *p;
+    g.box = make_norm_box(p->use_aabb, p->aabb);
+    if (int rc = unerf_set_background(g, background, background_rgb, "pose_grad_mc")) return rc;
+    g.pose = rot_inv ? 1 : 0;
+    for (int k = 0; k < 9; ++k) g.rinv[k] = rot_inv ? rot_inv[k] : 0.f;
+    g.out_grad = out_grad; g.out_rgb = out_rgb;
+    UNERF_REQUIRE(R < (1ll << 31), "pose_grad_mc: R=%lld rays in one launch, split the batch", (long long)R);
+    constexpr size_t lds_bytes = 2 * 64 * 64 * sizeof(float);   // the working panel and layer 0's activations
+    with_int3(tcnn_arg(g.p), [&](auto tc) {
+        hipLaunchKernelGGL((pose_grad_mc_kernel<decltype(tc)::value>), dim3((unsigned)R), dim3(64), lds_bytes, (hipStream_t)stream, g, m);
+    });
+    return unerf_check_launch("pose_grad_mc");
+}
+
 // ======================================================================================
 // 6. per-ray groups of 16 lanes x SPL samples: get_weights, composite, laplace depth draws
 // ======================================================================================

@@ -701,7 +701,37 @@ class NerfactoMCDropoutModel(_NerfactoBase):
     mask_budget_bytes: int = 1 << 34                     # "torch": a frame whose packed masks need more raises (1080p, K = 8: 12.7 GB)
     _frame_masks: Optional[ops.KeepMasks] = None
     _no_pose_gradient = ("its colour is the mean of K passes under fresh dropout masks, and the gradient kernel "
-                         "differentiates one deterministic pass.")
+                         "differentiates one deterministic pass; get_mc_pose_gradients_for_camera differentiates the frame "
+                         "of a named mask draw.")
+
+    @torch.no_grad()
+    def get_mc_pose_gradients_for_camera(self, camera, mask_seed: Optional[int] = None, rays_per_launch: Optional[int] = None,
+                                         want_rgb: bool = False):
+        """d mean_c(rgb[y, x]) / d camera_to_worlds of the MC-dropout frame of ONE mask draw -> [H,W,3,4] float32 on the device
+        (with want_rgb also the mean colour the gradient kernel composited, [H,W,3]): rgb is the mean of the K dropout passes,
+        and under a fixed draw it is a deterministic function of the pose (render.pose_gradient_camera_mc; sample bins held
+        fixed, fp32 arithmetic).  mask_seed None: the seed of this model's most recent render (the base seed before any
+        render), so get_outputs_for_camera(cam) followed by this call differentiates the frame just rendered; an int: that
+        seed of the counter generator.  frame_counter does not advance and scene.field.seed is left as found.
+        dropout_masks = "torch": the masks of the most recent frame are replayed while the model still holds them."""
+        c2w, cam = _camera_args(camera)
+        scene = self.device_scene()
+        kw = dict(rays_per_launch=rays_per_launch or self.rays_per_launch, want_rgb=want_rgb, **cam)
+        if self.dropout_masks == "torch" and scene.field.K > 0 and scene.field.p_drop > 0.0:
+            if mask_seed is not None:
+                raise ValueError("get_mc_pose_gradients_for_camera: mask_seed names a draw of the counter generator; "
+                                 "dropout_masks='torch' replays the masks of the most recent frame")
+            if self._frame_masks is None:
+                raise _lib.UnerfError("get_mc_pose_gradients_for_camera: the torch masks of that frame are gone (render the "
+                                      "camera with get_outputs_for_camera first; a batched or later render drops them)")
+            return render.pose_gradient_camera_mc(scene, c2w, keep_masks=self._frame_masks, **kw)
+        seed_was = scene.field.seed
+        try:
+            if mask_seed is not None:
+                scene.field.seed = int(mask_seed)
+            return render.pose_gradient_camera_mc(scene, c2w, **kw)
+        finally:
+            scene.field.seed = seed_was
 
     def _begin_render(self, scene: NerfSceneDev, total_rays: int = 0, chunk_rays: int = 0) -> None:
         if self.dropout_masks not in ("counter", "torch"):

@@ -1269,6 +1269,37 @@ def pose_grad(origins, directions, sbins, field: FieldDev, near: float, far: flo
     return (grad, rgb) if want_rgb else grad
 
 
+def pose_grad_mc(origins, directions, sbins, field: FieldDev, near: float, far: float, ray_offset: int = 0,
+                 keep_masks: Optional[KeepMasks] = None, rot_inv: Optional[torch.Tensor] = None, spacing: int = 0,
+                 background=None, want_rgb: bool = False):
+    """pose_grad of an MC-dropout frame under a named mask draw (unerf_pose_grad_mc): the gradient of
+    mean_c of rgb = (1/K) sum_k clamp(pred_k), pass k under the keep masks of that pass, in ONE launch whatever K is.
+    keep_masks None: the counter generator's masks for sample (ray_offset + r) * S + s and field.seed -- the masks
+    field_fwd(ray_offset=...) draws for these rays; else explicit bit arrays, read from row keep_masks.sample_offset + r * S + s
+    (ray_offset and field.seed are then not read).  Shapes as pose_grad.  -> grad | (grad, rgb)"""
+    lib = _l.load()
+    if field.mode != _l.FIELD_MCDROPOUT or field.K < 1:
+        raise _l.UnerfError("pose_grad_mc needs an MCDROPOUT field with K >= 1 (pose_grad differentiates the deterministic fields)")
+    R, S = sbins.shape[0], sbins.shape[1] - 1
+    dev = origins.device
+    cs = field.cstruct()
+    km = None if keep_masks is None else keep_masks.cstruct(field.K)
+    ri = None
+    if rot_inv is not None:
+        vals = [float(v) for v in torch.as_tensor(rot_inv).detach().cpu().to(torch.float32).reshape(-1)]
+        if len(vals) != 9:
+            raise _l.UnerfError(f"pose_grad_mc: rot_inv must have 9 entries, got {len(vals)}")
+        ri = (C.c_float * 9)(*vals)
+    grad = torch.empty(R, 6 if ri is None else 12, device=dev, dtype=torch.float32)
+    rgb = torch.empty(R, 3, device=dev, dtype=torch.float32) if want_rgb else None
+    bg_mode, bg_rgb = _background(background)
+    with _ctx(dev):
+        _run("pose_grad_mc", lambda: lib.unerf_pose_grad_mc(_p(origins), _p(directions), _p(sbins), R, S, near, far, spacing,
+                                                            int(ray_offset), C.byref(cs), None if km is None else C.byref(km),
+                                                            bg_mode, bg_rgb, ri, _p(grad), _p(rgb), _stream()))
+    return (grad, rgb) if want_rgb else grad
+
+
 def background_of(name) -> Tuple[int, Optional[Tuple[float, float, float]]]:
     """config.background_color -> (UNERF_BG_* mode, constant colour | None).  [UPSTREAM nerfstudio 1.1.0 RGBRenderer:
     "last_sample" blends the last sample's colour, "random" returns the composited colour unblended at eval, "white" /

@@ -182,6 +182,16 @@ def _build() -> Dict[str, Any]:
                 raise NotImplementedError(f"{type(self._mirror).__name__} has no pose gradient.")
             return fn(camera, **kw)
 
+        @torch.no_grad()
+        def get_mc_pose_gradients_for_camera(self, camera, **kw):
+            """the pose gradient of an MC-dropout frame under a named mask draw (mask_seed=, rays_per_launch=, want_rgb=:
+            models.NerfactoMCDropoutModel.get_mc_pose_gradients_for_camera); other mirrors raise NotImplementedError"""
+            fn = getattr(self._mirror, "get_mc_pose_gradients_for_camera", None)
+            if fn is None:
+                raise NotImplementedError(f"{type(self._mirror).__name__} has no MC-dropout pose gradient (its frames are not "
+                                          "means over dropout passes).")
+            return fn(camera, **kw)
+
         def load_state_dict(self, state_dict, strict: bool = False, **kw):  # type: ignore[override]
             return self._mirror.load_state_dict(state_dict, strict=strict, **kw)
 

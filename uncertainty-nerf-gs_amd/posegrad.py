@@ -76,7 +76,7 @@ def perturbed_pose(c2w: torch.Tensor, param: str, magnitude: float) -> torch.Ten
 
 
 def export_pose_gradients(model, camera, image_idx: int, output_dir, shift_param: str = "tz", shift_magnitude: float = 0.0,
-                          seed: int = 42) -> Dict[str, Path]:
+                          seed: int = 42, gradient_fn=None) -> Dict[str, Path]:
     """One image of estimate_gradient_pose_6dof.py:109-216 -> the files it writes under output_dir / f"image_{image_idx}":
       c2w_img{idx}.npy          [3,4] float32    the camera's own pose
       c2w_perturbed.npy         [3,4] float32    perturbed_pose(c2w, shift_param, shift_magnitude)
@@ -87,7 +87,9 @@ def export_pose_gradients(model, camera, image_idx: int, output_dir, shift_param
     model: anything with get_pose_gradients_for_camera(camera, want_rgb=True) (models.NerfactoModel / ActiveNerfactoModel,
     models.SplatfactoModel / ActiveSplatfactoModel -- for which the reference's script has no counterpart: it asserts a
     NerfactoModel -- and the plugin's models).  camera: one camera (camera_to_worlds, fx, fy, cx, cy, height, width, ...); it is not modified.
-    seed: as the script, torch.manual_seed(seed) before the perturbation (which draws nothing).  -> {file stem: path}"""
+    seed: as the script, torch.manual_seed(seed) before the perturbation (which draws nothing).
+    gradient_fn: None, or a callable (camera, want_rgb=True) -> (grads, rgb) used instead of the model's method, e.g.
+    model.get_mc_pose_gradients_for_camera or functools.partial of it with a mask_seed.  -> {file stem: path}"""
     from .eval import _write_png
     from .models import _scalar
     torch.manual_seed(seed)
@@ -98,7 +100,7 @@ def export_pose_gradients(model, camera, image_idx: int, output_dir, shift_param
     c2w_p = perturbed_pose(c2w, shift_param, shift_magnitude)
     cam = copy.copy(camera)
     cam.camera_to_worlds = c2w_p
-    grads, rgb = model.get_pose_gradients_for_camera(cam, want_rgb=True)
+    grads, rgb = (model.get_pose_gradients_for_camera if gradient_fn is None else gradient_fn)(cam, want_rgb=True)
     rgb = rgb.detach().cpu().to(torch.float32).numpy()
     K = np.array([[_scalar(camera.fx), 0.0, _scalar(camera.cx)], [0.0, _scalar(camera.fy), _scalar(camera.cy)], [0.0, 0.0, 1.0]],
                  np.float32)

@@ -375,11 +375,22 @@ def pose_gradient_camera(scene: NerfSceneDev, c2w: torch.Tensor, fx: float, fy: 
     rays_per_launch rays.  The sample bins are held fixed, as upstream's PDFSampler detaches them: the pose acts through
     the ray origins (c2w[:, 3]) and the directions normalize(c2w[:3, :3] dir_cam) only.  ORTHOPHOTO cameras and `obb`
     crops are refused: their origins / sampling planes depend on the pose themselves."""
+    return _pose_gradient_groups("pose_gradient_camera", scene, c2w, fx, fy, cx, cy, H, W, rays_per_launch, obb, distortion,
+                                 camera_type, want_rgb,
+                                 lambda o, d, sb, start, rot_inv: ops.pose_grad(o, d, sb, scene.field, scene.near, scene.far,
+                                                                                rot_inv=rot_inv, spacing=scene.spacing,
+                                                                                background=scene.background, want_rgb=want_rgb))
+
+
+def _pose_gradient_groups(what: str, scene: NerfSceneDev, c2w: torch.Tensor, fx, fy, cx, cy, H: int, W: int, rays_per_launch: int,
+                          obb, distortion, camera_type: int, want_rgb: bool, launch):
+    """the loop of pose_gradient_camera / pose_gradient_camera_mc: rays -> proposal sampler -> launch(o, d, sb, start, rot_inv)
+    per group of rays_per_launch rays"""
     _l.require_gpu()
     if int(camera_type) == _l.CAMERA_ORTHOPHOTO:
-        raise _l.UnerfError("pose_gradient_camera: an ORTHOPHOTO camera's ray origins depend on the rotation; not differentiated")
+        raise _l.UnerfError(f"{what}: an ORTHOPHOTO camera's ray origins depend on the rotation; not differentiated")
     if obb is not None:
-        raise _l.UnerfError("pose_gradient_camera: obb crops make the sampling planes depend on the pose; not differentiated")
+        raise _l.UnerfError(f"{what}: obb crops make the sampling planes depend on the pose; not differentiated")
     total = H * W
     dev = scene.device
     c2w = c2w.detach().cpu().to(torch.float32)
@@ -391,13 +402,30 @@ def pose_gradient_camera(scene: NerfSceneDev, c2w: torch.Tensor, fx: float, fy: 
             o, d, _ = ops.generate_rays(c2w, fx, fy, cx, cy, H, W, dev, start, min(rpl, total - start), distortion=distortion,
                                         camera_type=camera_type)
             sb, _ = sample_rays(scene, o, d, None, start, want_prop_depth=False, image_width=W, workspace=scene.workspace)
-            res = ops.pose_grad(o, d, sb, scene.field, scene.near, scene.far, rot_inv=rot_inv, spacing=scene.spacing,
-                                background=scene.background, want_rgb=want_rgb)
+            res = launch(o, d, sb, start, rot_inv)
             grads.append(res[0] if want_rgb else res)
             if want_rgb:
                 rgbs.append(res[1])
     g = torch.cat(grads).view(H, W, 3, 4)
     return (g, torch.cat(rgbs).view(H, W, 3)) if want_rgb else g
+
+
+def pose_gradient_camera_mc(scene: NerfSceneDev, c2w: torch.Tensor, fx: float, fy: float, cx: float, cy: float, H: int, W: int,
+                            rays_per_launch: int = 1 << 20, obb=None, distortion=None, camera_type: int = 1,
+                            want_rgb: bool = False, keep_masks: Optional[ops.KeepMasks] = None):
+    """pose_gradient_camera of an MC-dropout frame under a named mask draw (ops.pose_grad_mc): d mean_c(rgb) / d c2w of
+    rgb = the mean of the K dropout passes, one launch per group of rays whatever K is.  The masks are those of the frame
+    render_camera makes with the same scene.field.seed: every group is launched with ray_offset = its first ray, the
+    numbering render_camera gives the frame's own field launches, so the result does not depend on rays_per_launch.
+    keep_masks: an ops.KeepMasks over the H*W rays of the frame (row = ray * S + sample) instead of the counter generator's
+    masks; a group reads it from row start * S, as render_camera(keep_masks=) does.  Same refusals as pose_gradient_camera."""
+    def launch(o, d, sb, start, rot_inv):
+        km = None if keep_masks is None else keep_masks.at(start * (sb.shape[1] - 1))
+        return ops.pose_grad_mc(o, d, sb, scene.field, scene.near, scene.far, ray_offset=start, keep_masks=km, rot_inv=rot_inv,
+                                spacing=scene.spacing, background=scene.background, want_rgb=want_rgb)
+
+    return _pose_gradient_groups("pose_gradient_camera_mc", scene, c2w, fx, fy, cx, cy, H, W, rays_per_launch, obb, distortion,
+                                 camera_type, want_rgb, launch)
 
 
 def plan_view_groups(n_views: int, rays_per_view: int, rays_per_launch: int = 1 << 20, chunk_rays: int = 1 << 15,
