@@ -510,6 +510,30 @@ int unerf_pose_grad_mc(const float* origins, const float* directions, const floa
                        int background, const float* background_rgb_host, const float* rot_inv_host,
                        float* out_grad, float* out_rgb, void* stream);
 
+/* The same gradient of a LAPLACE frame under a NAMED draw of the last layers (laplace_field.py:279-362, 365-485, 528-568;
+ * laplace_model.py:456-480): per sample hb = W0 feat + b0 and geo = W1 hb + b1 (no ReLU), the density
+ * mu_d = (1/n_lap) sum_q act(w_q . hb + b_q) over the rows p->ws_density [set][q][65] (act = exp, softplus with lap_softplus;
+ * NOT multiplied by the selector unless lap_mask_density is set), the colour mu_c = (1/n_rgb) sum_q sigmoid(Wc_q h + bc_q) over
+ * p->ws_rgb [set][q][195] behind the two ReLU layers of the colour head (n_rgb = n_lap_rgb, or n_lap when that is <= 0),
+ * composited with get_weights(mu_d) under the background, nan_to_num and clamp rules of unerf_pose_grad.  The rows are
+ * ordinary tensors (field.sample_last_layers(generator=) reproduces them), so the frame is a deterministic function of the
+ * pose.  The set of ray r is (ray_offset + r) / lap_chunk_rays when lap_chunk_rays > 0, else set 0.
+ *   p : mode LAPLACE, out1 == 15, nerfacto's widths, L == 16, either grid layout (grid_half widened on read), use_aabb,
+ *       sh_remap; fp32 rows ws_density / ws_rgb with n_lap >= 1, n_lap_rgb >= 0, lap_sets, lap_chunk_rays >= 0 (ANY values:
+ *       the multiple-of-32 rule of unerf_field_fwd belongs to its 32-ray tiles; here a wave is one ray), lap_softplus,
+ *       lap_mask_density.  No blob is read.
+ *   out_grad [R,6] / [R,12] as unerf_pose_grad (same rot_inv_host epilogue); out_rgb NULL or [R,3] = the composited mean colour.
+ * fp32 throughout, ONE launch whatever n_lap is, no global scratch, no atomics, the heads summed in row order q = 0 .. n-1:
+ * two calls return the same bits, and a ray's bits do not depend on the other rays of its launch.  R == 0 is UNERF_OK.
+ * UNERF_ERR_ARG before any launch, each with its own message: another mode; other widths or L != 16; near_plane < 0; S
+ * outside [1, 64]; null ws_*, field or output pointers; n_lap < 1; lap_chunk_rays < 0; lap_chunk_rays > 0 and
+ * (ray_offset + R - 1) / lap_chunk_rays >= lap_sets; ray_offset < 0.  unerf_pose_grad keeps refusing LAPLACE. */
+int unerf_pose_grad_laplace(const float* origins, const float* directions, const float* sbins, int64_t R, int S,
+                            float near_plane, float far_plane, int spacing, int64_t ray_offset,
+                            const unerf_field_params* p /* host struct */,
+                            int background, const float* background_rgb_host, const float* rot_inv_host,
+                            float* out_grad, float* out_rgb, void* stream);
+
 /* ------------------------------------------------- composite + variance --
  * Replaces RaySamples.get_weights + RGB/Accumulation/Depth(median,expected)/Uncertainty
  * renderers + the depth-variance sum at models/activenerfacto/activenerfacto_model.py:94-112

@@ -4617,6 +4617,337 @@ extern "C" int unerf_pose_grad_mc(const float* origins, const float* directions,
     return unerf_check_launch("pose_grad_mc");
 }
 
+// --------------------------------------------------------------------------------------
+// 5e''. The same gradient of a LAPLACE frame under a named draw of the last layers (laplace_field.py:279-362, 365-485,
+// 528-568; laplace_model.py:456-480): the rows ws_density [set][q][65] / ws_rgb [set][q][195] are ordinary tensors, so the
+// colour is a deterministic piecewise-smooth function of the pose.  Per sample:
+//   hb = W0 feat + b0 (no ReLU), geo = W1 hb + b1 (no ReLU),
+//   mu_d = (1/n) sum_q act(w_q . hb + b_q)  (act = exp | softplus; x selector only with lap_mask_density),
+//   h = relu(H1 relu(H0 [SH16 | geo] + hb0) + hb1),  mu_c = (1/n_rgb) sum_q sigmoid(Wc_q h + bc_q),
+// composited with the weights of mu_d.  pose_grad_kernel's geometry is kept (a wave per ray, a lane per sample, one 16-KiB
+// panel per wave, two waves per SIMD); a wave has one ray, hence one sample set, so every head row is wave-uniform and is
+// read through the constant address space into scalar operands.
+//   forward   density rows: mu_d and, in the same pass, J = sum_q act'(pre_q) w_q (64 registers, carried to the trunk
+//             backward: d mu_d / d hb = J / n, which spares a second pass over the density rows and the recomputation of hb);
+//             colour rows: mu_c from h in registers and, in the same pass, D = sum_q sum_c s (1 - s) Wc_q[c,:] (64 registers)
+//   adjoints  pose_grad_kernel's scans give d mu_d and d mu_c
+//   backward  dh = d mu_c D / n_rgb when the three clamp gates of the ray are open (the channel adjoints are then equal; always,
+//             up to rounding, for a background in [0, 1]); else pass 2 over the colour rows: pre_qc recomputed from h,
+//             dh += d mu_c[c] s (1 - s) / n_rgb Wc_q[c,:].  ReLU, H1^T, ReLU, H0^T -> (dSH, dgeo); dhb = d mu_d J / n + W1^T dgeo;
+//             W0^T (no mask) -> dfeat; grid, contraction and ray sums as pose_grad_kernel.
+// The heads are summed in row order q = 0 .. n-1; no global scratch, no atomics.
+// --------------------------------------------------------------------------------------
+struct PoseGradLapArgs {
+    int64_t ray_offset;   // ray r of the launch is ray ray_offset + r of the frame: its set is that / lap_chunk_rays
+    int n_rgb;            // rows of ws_rgb per set (n_lap_rgb, or n_lap when that is <= 0)
+};
+
+template <int GRID>
+__global__ __launch_bounds__(256, 2) void pose_grad_laplace_kernel(PoseGradArgs a, PoseGradLapArgs la) {
+    extern __shared__ float lds[];
+    const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    float* A = lds + wv * (64 * 64);   // this wave's panel [64 units][64 lanes]; a lane reads only its own column
+    const int64_t r = (int64_t)blockIdx.x * 4 + wv;
+    if (r >= a.R) return;   // wave-uniform
+    const int S = a.S;
+    const bool in = lane < S;
+    const int i = in ? lane : S - 1;
+    const uint32_t mask = GRID == 0 ? (1u << a.p.log2T) - 1u : 0u;
+    const int nl = a.p.n_lap, nr = la.n_rgb;
+    const size_t set = a.p.lap_chunk_rays > 0 ? (size_t)((la.ray_offset + r) / a.p.lap_chunk_rays) : 0;   // wave-uniform
+    const pg_cfp wd = pg_const(a.p.ws_density) + set * (size_t)nl * 65;
+    const pg_cfp wc = pg_const(a.p.ws_rgb) + set * (size_t)nr * 195;
+
+    // ---- sample position, normalisation (pose_grad_kernel's statements) ----
+    const float* sb = a.sbins + r * (S + 1);
+    const float e0 = unerf_s2e(sb[i], a.s_near, a.s_far, a.lin), e1 = unerf_s2e(sb[i + 1], a.s_near, a.s_far, a.lin);
+    const float delta = e1 - e0, t2 = e0 + e1;
+    const float ox = a.origins[r * 3 + 0], oy = a.origins[r * 3 + 1], oz = a.origins[r * 3 + 2];
+    const float dxr = a.dirs[r * 3 + 0], dyr = a.dirs[r * 3 + 1], dzr = a.dirs[r * 3 + 2];
+    const float x0 = ox + dxr * t2 / 2.f, y0 = oy + dyr * t2 / 2.f, z0 = oz + dzr * t2 / 2.f;
+    float px = x0, py = y0, pz = z0;
+    const float sel = unerf_normalize_position(px, py, pz, a.box);
+
+    // ---- forward: grid -> bare-Linear trunk (field_kernel's LAPLACE arithmetic) ----
+#pragma unroll 2
+    for (int l = 0; l < 16; ++l) {
+        float2 f[8];
+        float wx, wy, wz, scale;
+        pg_level_corners<GRID>(a, l, mask, px, py, pz, f, wx, wy, wz, scale);
+        const float2 e = GRID == 0 ? unerf_blend8(f, wx, wy, wz) : unerf_tcnn_blend(f, wx, wy, wz);
+        A[(2 * l) * 64 + lane] = e.x;
+        A[(2 * l + 1) * 64 + lane] = e.y;
+    }
+    float acc[64];
+    pg_dense<32, 64>(pg_const(a.p.w0t), pg_const(a.p.b0), A, lane, acc);
+    store_act<64>(A, lane, acc, 0, false);
+    float geo[15];
+    pg_dense<64, 15>(pg_const(a.p.w1t), pg_const(a.p.b1), A, lane, geo);
+
+    // ---- density rows: the mean and its Jacobian with respect to hb in one pass ----
+    float J[64];
+#pragma unroll
+    for (int o = 0; o < 64; ++o) J[o] = 0.f;
+    float mu = 0.f;
+    for (int q = 0; q < nl; ++q) {
+        const pg_cfp w = wd + (size_t)q * 65;
+        float pre = 0.f;
+#pragma unroll
+        for (int o = 0; o < 64; ++o) pre = fmaf(acc[o], w[o], pre);
+        pre += w[64];
+        float pred, dact;
+        if (a.p.lap_softplus) {   // uniform
+            pred = unerf_softplus(pre);
+            dact = unerf_sigmoid(pre);   // = 1 - exp(-pred)
+        } else {
+            pred = expf(pre);
+            dact = pred;
+        }
+        mu += pred;
+#pragma unroll
+        for (int o = 0; o < 64; ++o) J[o] = fmaf(dact, w[o], J[o]);
+    }
+    mu /= (float)nl;
+    const float dsel = a.p.lap_mask_density ? sel : 1.f;   // inference: NOT selector-masked (laplace_field.py:356-362)
+    const float sig = mu * dsel;
+
+    // ---- colour head; rows, pass 1: the mean colour ----
+    float ux = (dxr + 1.f) / 2.f, uy = (dyr + 1.f) / 2.f, uz = (dzr + 1.f) / 2.f;
+    if (a.p.sh_remap) {
+        ux = ux * 2.f - 1.f;
+        uy = uy * 2.f - 1.f;
+        uz = uz * 2.f - 1.f;
+    }
+    {
+        float sh[16];
+        unerf_sh16(ux, uy, uz, sh);
+        store_act<16>(A, lane, sh, 0, false);
+    }
+    store_act<15>(A, lane, geo, 16, false);
+    uint32_t m1[2];
+    pg_dense<31, 64>(pg_const(a.p.h0t), pg_const(a.p.hb0), A, lane, acc);
+    relu_mask64(acc, m1);
+    store_act<64>(A, lane, acc, 0, true);
+    pg_dense<64, 64>(pg_const(a.p.h1t), pg_const(a.p.hb1), A, lane, acc);
+#pragma unroll
+    for (int o = 0; o < 64; ++o) acc[o] = fmaxf(acc[o], 0.f);   // h, kept in registers over both passes
+    // D = sum_q sum_c s_qc (1 - s_qc) Wc_q[c,:]: the adjoint of h for EQUAL channel adjoints, which is what the compositing
+    // hands back whenever all three clamp gates of the ray are open (pred = sum w c + T bg lies in [0, 1] for any colour mean
+    // and a background in [0, 1], up to rounding) -- then no second pass over the colour rows is needed
+    float c[3] = {0.f, 0.f, 0.f};
+    float d[64];
+#pragma unroll
+    for (int o = 0; o < 64; ++o) d[o] = 0.f;
+    for (int q = 0; q < nr; ++q) {
+        const pg_cfp w = wc + (size_t)q * 195;
+        float g[3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            float pre = 0.f;
+#pragma unroll
+            for (int o = 0; o < 64; ++o) pre = fmaf(acc[o], w[k * 64 + o], pre);
+            const float s = unerf_sigmoid(pre + w[192 + k]);
+            c[k] += s;
+            g[k] = s * (1.f - s);
+        }
+#pragma unroll
+        for (int o = 0; o < 64; ++o) d[o] = fmaf(g[2], w[128 + o], fmaf(g[1], w[64 + o], fmaf(g[0], w[o], d[o])));
+    }
+#pragma unroll
+    for (int k = 0; k < 3; ++k) c[k] = unerf_nan_to_num(c[k] / (float)nr);
+
+    // ---- compositing and its adjoints (pose_grad_kernel's scans) ----
+    const float dd = in ? delta * sig : 0.f;
+    const float em = expf(-dd);
+    const float T = expf(-group_excl_scan<64>(dd, lane));
+    const float wgt = in ? unerf_nan_to_num((1.f - em) * T) : 0.f;
+    const float Tf = 1.f - group_sum<64>(wgt);
+    const bool last_bg = a.bg_mode == UNERF_BG_LAST_SAMPLE;
+    const int rl = 63 - lane;
+    const float sw = __shfl(group_excl_scan<64>(__shfl(wgt, rl, 64), lane), rl, 64);
+    float dsig = 0.f, dc[3], pred[3];
+    bool gates_open = true;   // wave-uniform: pred is the ray's
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const float bg = last_bg ? __shfl(c[k], S - 1, 64) : a.bg[k];
+        const float wck = wgt * c[k];
+        const float swc = __shfl(group_excl_scan<64>(__shfl(wck, rl, 64), lane), rl, 64);
+        pred[k] = group_sum<64>(wck) + Tf * bg;
+        gates_open = gates_open && pred[k] >= 0.f && pred[k] <= 1.f;
+        const float live = (pred[k] >= 0.f && pred[k] <= 1.f && in) ? 1.f / 3.f : 0.f;
+        dsig += live * delta * (em * T * (c[k] - bg) - swc + bg * sw);
+        const float wt = wgt + ((last_bg && lane == S - 1) ? Tf : 0.f);
+        dc[k] = live * wt / (float)nr;   // adjoint of every row's sigmoid output
+    }
+
+    // ---- the adjoint of h: dc D with all gates open (dc[0] = dc[1] = dc[2]); else pass 2 over the colour rows, pre_qc
+    // recomputed from h and every channel with its own adjoint ----
+    if (gates_open) {
+#pragma unroll
+        for (int o = 0; o < 64; ++o) d[o] *= dc[0];
+    } else {
+#pragma unroll
+        for (int o = 0; o < 64; ++o) d[o] = 0.f;
+        for (int q = 0; q < nr; ++q) {
+            const pg_cfp w = wc + (size_t)q * 195;
+            float g[3];
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                float pre = 0.f;
+#pragma unroll
+                for (int o = 0; o < 64; ++o) pre = fmaf(acc[o], w[k * 64 + o], pre);
+                const float s = unerf_sigmoid(pre + w[192 + k]);
+                g[k] = dc[k] * s * (1.f - s);
+            }
+#pragma unroll
+            for (int o = 0; o < 64; ++o) d[o] = fmaf(g[2], w[128 + o], fmaf(g[1], w[64 + o], fmaf(g[0], w[o], d[o])));
+        }
+    }
+#pragma unroll
+    for (int o = 0; o < 64; ++o) d[o] = acc[o] > 0.f ? d[o] : 0.f;
+    pg_dense_bwd<64, 64>(pg_const(a.p.h1t), d, A, lane);
+    load_masked64(A, lane, m1, d);
+    pg_dense_bwd<31, 64>(pg_const(a.p.h0t), d, A, lane);   // rows 0..15: dSH, 16..30: dgeo
+    float gdx, gdy, gdz;   // the SH term of ds/dd
+    {
+        float q[16];
+#pragma unroll
+        for (int j = 0; j < 16; ++j) q[j] = A[j * 64 + lane];
+        const float x = ux, y = uy, z = uz, xx = x * x, yy = y * y, zz = z * z;
+        const float c1 = 0.4886025119029199f, c2 = 1.0925484305920792f, c6 = 0.9461746957575601f, c8 = 0.5462742152960396f,
+                    c9 = 0.5900435899266435f, c10 = 2.890611442640554f, c11 = 0.4570457994644658f, c12 = 0.3731763325901154f,
+                    c14 = 1.445305721320277f;
+        const float z5 = 5.f * zz - 1.f, d3 = 3.f * (xx - yy);
+        gdx = q[3] * c1 + q[4] * (c2 * y) + q[7] * (c2 * z) + q[8] * (2.f * c8 * x) + q[9] * (6.f * c9 * x * y) + q[10] * (c10 * y * z) +
+              q[13] * (c11 * z5) + q[14] * (2.f * c14 * x * z) + q[15] * (c9 * d3);
+        gdy = q[1] * c1 + q[4] * (c2 * x) + q[5] * (c2 * z) - q[8] * (2.f * c8 * y) + q[9] * (c9 * d3) + q[10] * (c10 * x * z) +
+              q[11] * (c11 * z5) - q[14] * (2.f * c14 * y * z) - q[15] * (6.f * c9 * x * y);
+        gdz = q[2] * c1 + q[5] * (c2 * y) + q[6] * (2.f * c6 * z) + q[7] * (c2 * x) + q[10] * (c10 * x * y) + q[11] * (10.f * c11 * y * z) +
+              q[12] * (c12 * (15.f * zz - 3.f)) + q[13] * (10.f * c11 * x * z) + q[14] * (c14 * (xx - yy));
+        const float du = a.p.sh_remap ? 1.f : 0.5f;
+        gdx *= du;
+        gdy *= du;
+        gdz *= du;
+    }
+    // ---- backward: trunk (no ReLU: no masks) ----
+    float d1[15];
+#pragma unroll
+    for (int g = 0; g < 15; ++g) d1[g] = A[(16 + g) * 64 + lane];
+    pg_dense_bwd<64, 15>(pg_const(a.p.w1t), d1, A, lane);
+    const float dmu = dsig * dsel / (float)nl;
+#pragma unroll
+    for (int o = 0; o < 64; ++o) d[o] = fmaf(dmu, J[o], A[o * 64 + lane]);
+    pg_dense_bwd<32, 64>(pg_const(a.p.w0t), d, A, lane);   // rows 2l, 2l+1: adjoint of level l's features
+
+    // ---- backward: grid -> normalised position -> world position, ray sums, epilogue (pose_grad_kernel's statements) ----
+    float gpx = 0.f, gpy = 0.f, gpz = 0.f;
+#pragma unroll 2
+    for (int l = 0; l < 16; ++l) {
+        float2 f[8];
+        float wx, wy, wz, scale;
+        pg_level_corners<GRID>(a, l, mask, px, py, pz, f, wx, wy, wz, scale);
+        const float g0 = A[(2 * l) * 64 + lane], g1 = A[(2 * l + 1) * 64 + lane];
+        float v[8];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) v[k] = fmaf(g1, f[k].y, g0 * f[k].x);
+        float bx, by, bz;
+        pg_blend_grad<GRID>(v, wx, wy, wz, bx, by, bz);
+        gpx = fmaf(scale, bx, gpx);
+        gpy = fmaf(scale, by, gpy);
+        gpz = fmaf(scale, bz, gpz);
+    }
+    float gx = gpx * sel, gy = gpy * sel, gz = gpz * sel;
+    if (a.box.use_aabb) {   // uniform
+        gx /= a.box.len[0];
+        gy /= a.box.len[1];
+        gz /= a.box.len[2];
+    } else {
+        gx *= 0.25f;
+        gy *= 0.25f;
+        gz *= 0.25f;
+        const float ax = fabsf(x0), ay = fabsf(y0), az = fabsf(z0);
+        const float m = fmaxf(fmaxf(ax, ay), az);
+        if (!(m < 1.f)) {
+            const float inv = 1.f / m, diag = (2.f - inv) * inv, cross = 2.f * (1.f - m) * inv * inv * inv;
+            const int k = (ax >= ay && ax >= az) ? 0 : (ay >= az ? 1 : 2);
+            const float dot = (k == 0 ? 0.f : gx * x0) + (k == 1 ? 0.f : gy * y0) + (k == 2 ? 0.f : gz * z0);
+            const float xk = k == 0 ? x0 : (k == 1 ? y0 : z0), gk = k == 0 ? gx : (k == 1 ? gy : gz);
+            const float along = gk * inv * inv + cross * (xk < 0.f ? -dot : dot);
+            gx = k == 0 ? along : gx * diag;
+            gy = k == 1 ? along : gy * diag;
+            gz = k == 2 ? along : gz * diag;
+        }
+    }
+    if (!in) gx = gy = gz = gdx = gdy = gdz = 0.f;
+    const float th = t2 / 2.f;
+    const float go0 = group_sum<64>(gx), go1 = group_sum<64>(gy), go2 = group_sum<64>(gz);
+    const float gd0 = group_sum<64>(fmaf(th, gx, gdx)), gd1 = group_sum<64>(fmaf(th, gy, gdy)), gd2 = group_sum<64>(fmaf(th, gz, gdz));
+    if (a.pose) {
+        const float gdd = gd0 * dxr + gd1 * dyr + gd2 * dzr;
+        const float P[3] = {gd0 - dxr * gdd, gd1 - dyr * gdd, gd2 - dzr * gdd};
+        const float go[3] = {go0, go1, go2};
+        const int row = lane >> 2, col = lane & 3;
+        const float Pa = row == 0 ? P[0] : (row == 1 ? P[1] : P[2]);
+        const float ga = row == 0 ? go[0] : (row == 1 ? go[1] : go[2]);
+        const int cb = col < 3 ? col : 0;
+        const float q = a.rinv[cb * 3 + 0] * dxr + a.rinv[cb * 3 + 1] * dyr + a.rinv[cb * 3 + 2] * dzr;
+        if (lane < 12) a.out_grad[r * 12 + lane] = col == 3 ? ga : Pa * q;
+    } else {
+        const float v6 = lane == 0 ? go0 : lane == 1 ? go1 : lane == 2 ? go2 : lane == 3 ? gd0 : lane == 4 ? gd1 : gd2;
+        if (lane < 6) a.out_grad[r * 6 + lane] = v6;
+    }
+    if (a.out_rgb && lane < 3) {
+        const float pv = lane == 0 ? pred[0] : (lane == 1 ? pred[1] : pred[2]);
+        a.out_rgb[r * 3 + lane] = fminf(fmaxf(pv, 0.f), 1.f);
+    }
+}
+
+extern "C" int unerf_pose_grad_laplace(const float* origins, const float* directions, const float* sbins, int64_t R, int S,
+                                       float near_plane, float far_plane, int spacing, int64_t ray_offset,
+                                       const unerf_field_params* p, int background, const float* background_rgb,
+                                       const float* rot_inv, float* out_grad, float* out_rgb, void* stream) {
+    UNERF_REQUIRE(R >= 0 && S >= 1 && S <= 64, "pose_grad_laplace: S=%d outside [1,64]", S);
+    if (R == 0) return UNERF_OK;
+    UNERF_REQUIRE(origins && directions && sbins && p && out_grad, "pose_grad_laplace: null pointer");
+    UNERF_REQUIRE(p->mode == UNERF_FIELD_LAPLACE, "pose_grad_laplace: mode %d (a LAPLACE field is needed; unerf_pose_grad and "
+                  "unerf_pose_grad_mc differentiate the other fields)", p->mode);
+    UNERF_REQUIRE(p->hidden == 0 && p->hidden_color == 0 && p->geo_dim == 0 && p->feat_per_level == 0 && p->L == 16 && p->out1 == 15,
+                  "pose_grad_laplace: nerfacto's widths only (hidden 64 / 64, geo 15 = trunk output 15, 2 features x 16 levels); the "
+                  "any-width kernel is out of scope");
+    UNERF_REQUIRE(p->table && p->w0t && p->b0 && p->w1t && p->b1 && p->h0t && p->hb0 && p->h1t && p->hb1 && (p->scalings || p->tcnn_levels),
+                  "pose_grad_laplace: null field pointer");
+    UNERF_REQUIRE(p->ws_density && p->ws_rgb, "pose_grad_laplace: null ws_density / ws_rgb (the sampled last layers of the named draw)");
+    UNERF_REQUIRE(p->tcnn_levels || (p->log2T >= 1 && p->log2T <= 24), "pose_grad_laplace: bad log2T=%d", p->log2T);
+    UNERF_REQUIRE(p->tcnn_levels || !p->grid_half, "pose_grad_laplace: grid_half needs a tcnn-layout grid");
+    UNERF_REQUIRE(near_plane >= 0.f, "pose_grad_laplace: near_plane=%g (spacing-domain bins only)", (double)near_plane);
+    UNERF_REQUIRE(p->n_lap >= 1, "pose_grad_laplace: n_lap=%d, the mean over sampled rows needs n_lap >= 1", p->n_lap);
+    UNERF_REQUIRE(ray_offset >= 0, "pose_grad_laplace: ray_offset=%lld < 0", (long long)ray_offset);
+    UNERF_REQUIRE(p->lap_chunk_rays >= 0, "pose_grad_laplace: lap_chunk_rays=%d < 0", p->lap_chunk_rays);
+    UNERF_REQUIRE(p->lap_chunk_rays == 0 || (ray_offset + R - 1) / p->lap_chunk_rays < p->lap_sets,
+                  "pose_grad_laplace: rays [%lld, %lld) reach past the last of lap_sets=%d sample sets of lap_chunk_rays=%d rays",
+                  (long long)ray_offset, (long long)(ray_offset + R), p->lap_sets, p->lap_chunk_rays);
+    PoseGradArgs g;
+    g.origins = origins; g.dirs = directions; g.sbins = sbins; g.R = R; g.S = S;
+    if (int rc = set_spacing(g, near_plane, far_plane, spacing)) return rc;
+    g.p = *p;
+    g.box = make_norm_box(p->use_aabb, p->aabb);
+    if (int rc = unerf_set_background(g, background, background_rgb, "pose_grad_laplace")) return rc;
+    g.pose = rot_inv ? 1 : 0;
+    for (int k = 0; k < 9; ++k) g.rinv[k] = rot_inv ? rot_inv[k] : 0.f;
+    g.out_grad = out_grad; g.out_rgb = out_rgb;
+    PoseGradLapArgs la;
+    la.ray_offset = ray_offset;
+    la.n_rgb = p->n_lap_rgb > 0 ? p->n_lap_rgb : p->n_lap;
+    UNERF_REQUIRE(R < (1ll << 32), "pose_grad_laplace: R=%lld rays in one launch, split the batch", (long long)R);
+    const int64_t blocks = (R + 3) / 4;   // a wave per ray; 64 KiB of LDS per block: two blocks per CU
+    constexpr size_t lds_bytes = 4 * 64 * 64 * sizeof(float);
+    with_int3(tcnn_arg(g.p), [&](auto tc) {
+        hipLaunchKernelGGL((pose_grad_laplace_kernel<decltype(tc)::value>), dim3((unsigned)blocks), dim3(256), lds_bytes,
+                           (hipStream_t)stream, g, la);
+    });
+    return unerf_check_launch("pose_grad_laplace");
+}
+
 // ======================================================================================
 // 6. per-ray groups of 16 lanes x SPL samples: get_weights, composite, laplace depth draws
 // ======================================================================================

@@ -251,6 +251,7 @@ SIGNATURES = {
     "unerf_pose_grad": (_i, [_vp, _vp, _vp, _i64, _i, _f, _f, _i, C.POINTER(FieldParams), _i, _fp, _fp, _vp, _vp, _vp]),
     "unerf_pose_grad_mc": (_i, [_vp, _vp, _vp, _i64, _i, _f, _f, _i, _i64, C.POINTER(FieldParams), C.POINTER(KeepMasks), _i, _fp,
                                 _fp, _vp, _vp, _vp]),
+    "unerf_pose_grad_laplace": (_i, [_vp, _vp, _vp, _i64, _i, _f, _f, _i, _i64, C.POINTER(FieldParams), _i, _fp, _fp, _vp, _vp, _vp]),
     "unerf_composite_var":(_i, [_vp, _vp, _vp, _vp, _vp, _i, _i64, _i, _f, _f, _i, _vp, _i64, _i64, _i, _fp, _vp, _vp, _vp]),
     "unerf_composite_moments": (_i, [_vp, _vp, _vp, _i, _i64, _i, _f, _f, _i, _vp, _i64, _i64, _i, _fp, _vp, _vp, _vp, _vp]),
     "unerf_composite_var_planes": (_i, [_vp, _vp, _vp, _vp, _i, _i64, _i, _f, _f, _i, _vp, _i64, _i64, _i, _fp, _vp, _vp, _vp]),

@@ -791,7 +791,49 @@ class NerfactoLaplaceModel(_NerfactoBase):
     # set for the whole frame (no visible seams between chunks; the field kernel keeps its 8x4 pixel-patch tiles).
     resample: str = "chunk"
     _no_pose_gradient = ("its colour is the mean over sampled last layers, which the gradient kernel (one deterministic "
-                         "nerfacto head) does not evaluate.")
+                         "nerfacto head) does not evaluate; get_laplace_pose_gradients_for_camera differentiates the frame of a "
+                         "named draw of the last layers.")
+
+    @torch.no_grad()
+    def get_laplace_pose_gradients_for_camera(self, camera, generator=None, weight_samples=None,
+                                              use_deterministic_density: bool = False, prior_prec: float = 1.0,
+                                              n_samples: int = 100, eps: float = 1e-9, rays_per_launch: Optional[int] = None,
+                                              want_rgb: bool = False):
+        """d mean_c(rgb[y, x]) / d camera_to_worlds of the Laplace frame of ONE draw of the last layers -> [H,W,3,4] float32
+        on the device (with want_rgb also the mean colour the gradient kernel composited, [H,W,3]): rgb is the mean over the
+        sampled heads, and under a fixed draw it is a deterministic function of the pose (render.pose_gradient_camera_laplace;
+        sample bins held fixed, fp32 arithmetic).  The sets are drawn exactly as get_outputs_for_camera_unc draws them (the
+        same field.sample_last_layers call: a set per eval chunk with resample = "chunk", one set -- with that method's
+        warning -- when eval_num_rays_per_chunk is no multiple of 32), so with a generator seeded like the one a
+        get_outputs_for_camera_unc call was given this differentiates that frame.  weight_samples = (ws_density, ws_rgb),
+        [n, 65] / [n, 195] or stacks [sets, n, ...] with a set per eval chunk: those rows are used and nothing is drawn.
+        The sampled heads belong to this call: afterwards the model renders with its mean heads again."""
+        if self.resample not in ("chunk", "camera"):
+            raise ValueError(f"NerfactoLaplaceModel.resample={self.resample!r}: expected 'chunk' or 'camera'")
+        c2w, cam = _camera_args(camera)
+        if weight_samples is not None:
+            ws = (weight_samples[0], weight_samples[1])
+        else:
+            n_sets = None
+            if self.resample == "chunk":
+                chunk = int(self.config.eval_num_rays_per_chunk)
+                if chunk <= 0 or chunk % 32:
+                    import warnings
+                    warnings.warn(f"eval_num_rays_per_chunk={chunk} is not a multiple of 32: per-chunk Laplace sample sets need "
+                                  "that; rendering this frame with one set (model.resample = 'camera')")
+                else:
+                    n_sets = -(-(cam["H"] * cam["W"]) // chunk)
+            ws = self.field.sample_last_layers(n_samples=n_samples, prior_prec=prior_prec, eps=eps, generator=generator,
+                                               deterministic_density=use_deterministic_density, n_sets=n_sets)
+        self._ws = ws
+        self._deterministic_density = bool(use_deterministic_density)
+        self.invalidate()
+        try:
+            return render.pose_gradient_camera_laplace(self.device_scene(), c2w, rays_per_launch=rays_per_launch or self.rays_per_launch,
+                                                       want_rgb=want_rgb, **cam)
+        finally:
+            self._ws, self._deterministic_density = None, False
+            self.invalidate()
 
     def _make_field(self):
         return F.NerfactoLaplaceField(density_activation=self.config.density_activation, **self._field_kwargs())

@@ -1300,6 +1300,35 @@ def pose_grad_mc(origins, directions, sbins, field: FieldDev, near: float, far: 
     return (grad, rgb) if want_rgb else grad
 
 
+def pose_grad_laplace(origins, directions, sbins, field: FieldDev, near: float, far: float, ray_offset: int = 0,
+                      rot_inv: Optional[torch.Tensor] = None, spacing: int = 0, background=None, want_rgb: bool = False):
+    """pose_grad of a Laplace frame under a named draw of the last layers (unerf_pose_grad_laplace): the gradient of mean_c of
+    the colour composited from the density and colour MEANS over the rows field.ws_density [n, 65] / field.ws_rgb [n_rgb, 195]
+    (or stacks [sets, n, ...]: ray ray_offset + r reads set (ray_offset + r) // field.lap_chunk_rays, any chunk size), in ONE
+    launch whatever the row counts are.  Shapes as pose_grad.  -> grad | (grad, rgb)"""
+    lib = _l.load()
+    if field.mode != _l.FIELD_LAPLACE or field.ws_density is None or field.ws_rgb is None:
+        raise _l.UnerfError("pose_grad_laplace needs a LAPLACE field with ws_density / ws_rgb (pose_grad and pose_grad_mc "
+                            "differentiate the other fields)")
+    R, S = sbins.shape[0], sbins.shape[1] - 1
+    dev = origins.device
+    cs = field.cstruct()
+    ri = None
+    if rot_inv is not None:
+        vals = [float(v) for v in torch.as_tensor(rot_inv).detach().cpu().to(torch.float32).reshape(-1)]
+        if len(vals) != 9:
+            raise _l.UnerfError(f"pose_grad_laplace: rot_inv must have 9 entries, got {len(vals)}")
+        ri = (C.c_float * 9)(*vals)
+    grad = torch.empty(R, 6 if ri is None else 12, device=dev, dtype=torch.float32)
+    rgb = torch.empty(R, 3, device=dev, dtype=torch.float32) if want_rgb else None
+    bg_mode, bg_rgb = _background(background)
+    with _ctx(dev):
+        _run("pose_grad_laplace", lambda: lib.unerf_pose_grad_laplace(_p(origins), _p(directions), _p(sbins), R, S, near, far, spacing,
+                                                                      int(ray_offset), C.byref(cs), bg_mode, bg_rgb, ri, _p(grad),
+                                                                      _p(rgb), _stream()))
+    return (grad, rgb) if want_rgb else grad
+
+
 def background_of(name) -> Tuple[int, Optional[Tuple[float, float, float]]]:
     """config.background_color -> (UNERF_BG_* mode, constant colour | None).  [UPSTREAM nerfstudio 1.1.0 RGBRenderer:
     "last_sample" blends the last sample's colour, "random" returns the composited colour unblended at eval, "white" /

@@ -192,6 +192,17 @@ def _build() -> Dict[str, Any]:
                                           "means over dropout passes).")
             return fn(camera, **kw)
 
+        @torch.no_grad()
+        def get_laplace_pose_gradients_for_camera(self, camera, **kw):
+            """the pose gradient of a Laplace frame under a named draw of the last layers (generator=, weight_samples=,
+            use_deterministic_density=, prior_prec=, n_samples=, eps=, rays_per_launch=, want_rgb=:
+            models.NerfactoLaplaceModel.get_laplace_pose_gradients_for_camera); other mirrors raise NotImplementedError"""
+            fn = getattr(self._mirror, "get_laplace_pose_gradients_for_camera", None)
+            if fn is None:
+                raise NotImplementedError(f"{type(self._mirror).__name__} has no Laplace pose gradient (its frames are not "
+                                          "means over sampled last layers).")
+            return fn(camera, **kw)
+
         def load_state_dict(self, state_dict, strict: bool = False, **kw):  # type: ignore[override]
             return self._mirror.load_state_dict(state_dict, strict=strict, **kw)
 

@@ -89,7 +89,9 @@ def export_pose_gradients(model, camera, image_idx: int, output_dir, shift_param
     NerfactoModel -- and the plugin's models).  camera: one camera (camera_to_worlds, fx, fy, cx, cy, height, width, ...); it is not modified.
     seed: as the script, torch.manual_seed(seed) before the perturbation (which draws nothing).
     gradient_fn: None, or a callable (camera, want_rgb=True) -> (grads, rgb) used instead of the model's method, e.g.
-    model.get_mc_pose_gradients_for_camera or functools.partial of it with a mask_seed.  -> {file stem: path}"""
+    model.get_mc_pose_gradients_for_camera or functools.partial of it with a mask_seed, or
+    functools.partial(model.get_laplace_pose_gradients_for_camera, generator=g) for the Laplace frame of that draw.
+    -> {file stem: path}"""
     from .eval import _write_png
     from .models import _scalar
     torch.manual_seed(seed)

@@ -384,8 +384,8 @@ def pose_gradient_camera(scene: NerfSceneDev, c2w: torch.Tensor, fx: float, fy: 
 
 def _pose_gradient_groups(what: str, scene: NerfSceneDev, c2w: torch.Tensor, fx, fy, cx, cy, H: int, W: int, rays_per_launch: int,
                           obb, distortion, camera_type: int, want_rgb: bool, launch):
-    """the loop of pose_gradient_camera / pose_gradient_camera_mc: rays -> proposal sampler -> launch(o, d, sb, start, rot_inv)
-    per group of rays_per_launch rays"""
+    """the loop of pose_gradient_camera / pose_gradient_camera_mc / pose_gradient_camera_laplace: rays -> proposal sampler ->
+    launch(o, d, sb, start, rot_inv) per group of rays_per_launch rays"""
     _l.require_gpu()
     if int(camera_type) == _l.CAMERA_ORTHOPHOTO:
         raise _l.UnerfError(f"{what}: an ORTHOPHOTO camera's ray origins depend on the rotation; not differentiated")
@@ -426,6 +426,24 @@ def pose_gradient_camera_mc(scene: NerfSceneDev, c2w: torch.Tensor, fx: float, f
 
     return _pose_gradient_groups("pose_gradient_camera_mc", scene, c2w, fx, fy, cx, cy, H, W, rays_per_launch, obb, distortion,
                                  camera_type, want_rgb, launch)
+
+
+def pose_gradient_camera_laplace(scene: NerfSceneDev, c2w: torch.Tensor, fx: float, fy: float, cx: float, cy: float, H: int, W: int,
+                                 rays_per_launch: int = 1 << 20, obb=None, distortion=None, camera_type: int = 1,
+                                 want_rgb: bool = False):
+    """pose_gradient_camera of a Laplace frame under a named draw of the last layers (ops.pose_grad_laplace): d mean_c(rgb) /
+    d c2w of rgb = the colour composited from the means over scene.field.ws_density / ws_rgb, one launch per group of rays
+    whatever the row counts are.  Every group is launched with ray_offset = its first ray, so with stacked sets a ray reads the
+    set render_camera gives it (ray // scene.field.lap_chunk_rays) and the result does not depend on rays_per_launch.  Same
+    refusals as pose_gradient_camera."""
+    if scene.field.mode != _l.FIELD_LAPLACE:
+        raise _l.UnerfError("pose_gradient_camera_laplace: the scene's field is not a LAPLACE field (pose_gradient_camera and "
+                            "pose_gradient_camera_mc differentiate the other fields)")
+    return _pose_gradient_groups("pose_gradient_camera_laplace", scene, c2w, fx, fy, cx, cy, H, W, rays_per_launch, obb, distortion,
+                                 camera_type, want_rgb,
+                                 lambda o, d, sb, start, rot_inv: ops.pose_grad_laplace(
+                                     o, d, sb, scene.field, scene.near, scene.far, ray_offset=start, rot_inv=rot_inv,
+                                     spacing=scene.spacing, background=scene.background, want_rgb=want_rgb))
 
 
 def plan_view_groups(n_views: int, rays_per_view: int, rays_per_launch: int = 1 << 20, chunk_rays: int = 1 << 15,
