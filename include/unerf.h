@@ -488,6 +488,37 @@ int unerf_pose_grad(const float* origins, const float* directions, const float* 
                     int background, const float* background_rgb_host, const float* rot_inv_host,
                     float* out_grad, float* out_rgb, void* stream);
 
+/* Per-ray pose JACOBIAN of the rendered channels: what the reference's user gets by changing outputs= of the
+ * torch.autograd.grad call in estimate_gradient_pose_6dof.py:183-190, one row per selected channel behind one forward pass.
+ *   UNERF_POSE_CH_R / _G / _B : d clamp(pred_c) / d. under exactly unerf_pose_grad's rules (nan_to_num, the clamp gate per
+ *                               channel -- a clamped channel's row is exactly 0 --, the background rule with the last-sample
+ *                               term, bins held fixed); out_val = the clamped colour, unerf_pose_grad's out_rgb bit for bit
+ *   UNERF_POSE_CH_ACC         : A = sum_i w_i (RaySamples.get_weights + AccumulationRenderer); out_val = A
+ *   UNERF_POSE_CH_EDEPTH      : e = sum_i w_i t_i / (A + 1e-10), t_i = the bin mid-point (DepthRenderer "expected"); out_val = e.
+ *                               The renderer's clip of e to the step range of the ray is NOT applied and NOT differentiated:
+ *                               it is the identity except where A is of the order of 1e-10.
+ * channels: a non-empty subset of the five bits, C = popcount; the rows stand in bit order (R, G, B, ACC, EDEPTH).
+ *   rot_inv_host NULL : D = 6, a row is (d./do, d./dd);  [9]: D = 12, a row is d./dc2w row-major 3x4 (unerf_pose_grad's epilogue)
+ *   proj_host         : NULL, or [D][P] row-major host floats, 1 <= P <= 12 (e.g. tangent basis x Cholesky factor of a pose
+ *                       covariance): out_proj [R,C,P] = row . proj summed over D in order, out_var [R,C] = sum_k out_proj_k^2
+ *                       summed over P in order -- the first-order variance of the channel under that covariance
+ *   out_jac [R,C,D], out_proj [R,C,P], out_var [R,C], out_val [R,C]: each may be NULL, not all four.
+ * p, sbins, background as unerf_pose_grad; fp32 throughout, ONE launch, no atomics, no global scratch.  Two calls return the
+ * same bits; a ray's bits do not depend on the other rays of its launch; a row's bits depend neither on the other channels
+ * selected nor on which outputs were requested.  R == 0 is UNERF_OK.  UNERF_ERR_ARG before any launch, each with its own
+ * message: everything unerf_pose_grad refuses; channels empty or with unknown bits; proj_host with P outside [1, 12];
+ * out_proj or out_var without proj_host; all four outputs NULL. */
+#define UNERF_POSE_CH_R 1
+#define UNERF_POSE_CH_G 2
+#define UNERF_POSE_CH_B 4
+#define UNERF_POSE_CH_ACC 8
+#define UNERF_POSE_CH_EDEPTH 16
+int unerf_pose_jacobian(const float* origins, const float* directions, const float* sbins, int64_t R, int S,
+                        float near_plane, float far_plane, int spacing, const unerf_field_params* p /* host struct */,
+                        int background, const float* background_rgb_host, const float* rot_inv_host,
+                        int channels, const float* proj_host, int P,
+                        float* out_jac, float* out_proj, float* out_var, float* out_val, void* stream);
+
 /* The same gradient of an MC-DROPOUT frame under a NAMED mask draw: rgb = (1/K) sum_k clamp(pred_k), pass k evaluated with
  * the keep masks of that pass, and out_grad = (1/K) sum_k of unerf_pose_grad's quantity of pass k (each pass with its own
  * clamp gate, nan_to_num, background rule and last-sample term).  One launch whatever K is: the grid lookup and trunk

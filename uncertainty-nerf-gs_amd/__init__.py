@@ -10,6 +10,7 @@ Layout
   metrics.py  ause / auce / psnr / nll (parity metrics)
   splat.py    frame-level splat pipelines: active_splatfacto_outputs(_batch), pose_gradient_camera (the splat pose gradient)
   posegrad.py per-pixel camera-pose gradients of a frame (nerfacto and splat models), exported as the reference's
-              pose-sensitivity script writes them
+              pose-sensitivity script writes them; tangent_basis / pose_projection: the six pose parameters and a pose
+              covariance for the per-channel pose Jacobian (ops.pose_jacobian, render.pose_jacobian_camera)
 """
 __version__ = "0.1.0"

@@ -4247,6 +4247,323 @@ extern "C" int unerf_pose_grad(const float* origins, const float* directions, co
 }
 
 // --------------------------------------------------------------------------------------
+// 5e-J. Per-ray pose JACOBIAN: one row per selected output channel (clamp(pred_r), clamp(pred_g), clamp(pred_b), the
+// accumulation A = sum_i w_i, the unclipped expected depth e = N / (A + 1e-10), N = sum_i w_i t_i) behind ONE forward.  The
+// backward of pose_grad_kernel keeps only three ReLU bit masks, the weights and the scans and is linear in its seed, so it is
+// run once per channel in a wave-uniform loop; the LDS panel holds adjoints only from then on.
+//   row R/G/B  the seed of pose_grad_kernel with live_c in place of live_c / 3 and the other two channels at 0
+//   row ACC    dA/d(delta_i sigma_i) = T_end = em_{S-1} T_{S-1} (read off the scan, not 1 - A: behind an opaque sample T_end
+//              is far below the rounding of A); no colour head, no SH term
+//   row EDEPTH de/d(delta_i sigma_i) = [(1 - alpha_i) T_i u_i - sum_{j>i} w_j u_j] / (A + eps), u = t - e: the quotient rule
+//              [(1-alpha_i) T_i t_i - sum_{j>i} w_j t_j] / (A+eps) - N/(A+eps)^2 [(1-alpha_i) T_i - sum_{j>i} w_j] with e taken
+//              into the sum first (the depths are centred before they are weighted, as autograd's backward does); the suffix
+//              sum is the reversed-wave scan.  The clip of the renderer to the step range is not differentiated.
+// Behind a row: out_proj = row . proj (sequential over D in lane k), out_var = sum_k out_proj_k^2 (sequential over P).
+// No atomics, no global scratch; every pass is a fixed sequence of the same statements: a row's bits depend neither on the
+// other rays, nor on the other channels, nor on which outputs were asked for.
+// --------------------------------------------------------------------------------------
+struct PoseJacArgs {
+    PoseGradArgs g;       // out_grad / out_rgb are not read; g.pose: D = 12, else 6
+    int channels;         // UNERF_POSE_CH_* bits; rows in bit order
+    int C;                // popcount(channels)
+    int P;                // 0: no projection
+    float proj[12 * 12];  // [D][P] row-major
+    float* out_jac;       // NULL or [R,C,D]
+    float* out_proj;      // NULL or [R,C,P]
+    float* out_var;       // NULL or [R,C]
+    float* out_val;       // NULL or [R,C]
+};
+
+template <int OUT1, int GRID>
+__global__ __launch_bounds__(256, 2) void pose_jac_kernel(PoseJacArgs ja) {
+    extern __shared__ float lds[];
+    const PoseGradArgs& a = ja.g;
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    float* A = lds + wv * (64 * 64);
+    const int64_t r = (int64_t)blockIdx.x * 4 + wv;
+    if (r >= a.R) return;   // wave-uniform
+    const int S = a.S;
+    const bool in = lane < S;
+    const int i = in ? lane : S - 1;
+    const uint32_t mask = GRID == 0 ? (1u << a.p.log2T) - 1u : 0u;
+    // ---- sample position, normalisation (pose_grad_kernel's statements down to the compositing) ----
+    const float* sb = a.sbins + r * (S + 1);
+    const float e0 = unerf_s2e(sb[i], a.s_near, a.s_far, a.lin), e1 = unerf_s2e(sb[i + 1], a.s_near, a.s_far, a.lin);
+    const float delta = e1 - e0, t2 = e0 + e1;
+    const float ox = a.origins[r * 3 + 0], oy = a.origins[r * 3 + 1], oz = a.origins[r * 3 + 2];
+    const float dxr = a.dirs[r * 3 + 0], dyr = a.dirs[r * 3 + 1], dzr = a.dirs[r * 3 + 2];
+    const float x0 = ox + dxr * t2 / 2.f, y0 = oy + dyr * t2 / 2.f, z0 = oz + dzr * t2 / 2.f;
+    float px = x0, py = y0, pz = z0;
+    const float sel = unerf_normalize_position(px, py, pz, a.box);
+
+    // ---- forward: grid -> trunk -> head ----
+#pragma unroll 2
+    for (int l = 0; l < 16; ++l) {
+        float2 f[8];
+        float wx, wy, wz, scale;
+        pg_level_corners<GRID>(a, l, mask, px, py, pz, f, wx, wy, wz, scale);
+        const float2 e = GRID == 0 ? unerf_blend8(f, wx, wy, wz) : unerf_tcnn_blend(f, wx, wy, wz);
+        A[(2 * l) * 64 + lane] = e.x;
+        A[(2 * l + 1) * 64 + lane] = e.y;
+    }
+    uint32_t m0[2], m1[2], m2[2];
+    float sig, c[3];
+    float ux = (dxr + 1.f) / 2.f, uy = (dyr + 1.f) / 2.f, uz = (dzr + 1.f) / 2.f;
+    if (a.p.sh_remap) {
+        ux = ux * 2.f - 1.f;
+        uy = uy * 2.f - 1.f;
+        uz = uz * 2.f - 1.f;
+    }
+    {
+        float acc[64];
+        pg_dense<32, 64>(pg_const(a.p.w0t), pg_const(a.p.b0), A, lane, acc);
+        relu_mask64(acc, m0);
+        store_act<64>(A, lane, acc, 0, true);
+        float o1[OUT1];
+        pg_dense<64, OUT1>(pg_const(a.p.w1t), pg_const(a.p.b1), A, lane, o1);
+        sig = a.p.average_init_density * expf(o1[0]) * sel;
+        {
+            float sh[16];
+            unerf_sh16(ux, uy, uz, sh);
+            store_act<16>(A, lane, sh, 0, false);
+        }
+#pragma unroll
+        for (int g = 0; g < 15; ++g) A[(16 + g) * 64 + lane] = o1[1 + g];
+        pg_dense<31, 64>(pg_const(a.p.h0t), pg_const(a.p.hb0), A, lane, acc);
+        relu_mask64(acc, m1);
+        store_act<64>(A, lane, acc, 0, true);
+        pg_dense<64, 64>(pg_const(a.p.h1t), pg_const(a.p.hb1), A, lane, acc);
+        relu_mask64(acc, m2);
+        store_act<64>(A, lane, acc, 0, true);
+        pg_dense<64, 3>(pg_const(a.p.h2t), pg_const(a.p.hb2), A, lane, c);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) c[k] = unerf_nan_to_num(unerf_sigmoid(c[k]));
+    }
+
+    // ---- compositing, once: the weights, the scans and every channel's value ----
+    const float dd = in ? delta * sig : 0.f;
+    const float em = expf(-dd);
+    const float T = expf(-group_excl_scan<64>(dd, lane));
+    const float w = in ? unerf_nan_to_num((1.f - em) * T) : 0.f;
+    const float Asum = group_sum<64>(w);
+    const float Tf = 1.f - Asum;
+    const bool last_bg = a.bg_mode == UNERF_BG_LAST_SAMPLE;
+    const int rl = 63 - lane;
+    const float sw = __shfl(group_excl_scan<64>(__shfl(w, rl, 64), lane), rl, 64);   // sum_{j>i} w_j (pose_grad_kernel: why a scan)
+    float bg[3], swc[3], pred[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        bg[k] = last_bg ? __shfl(c[k], S - 1, 64) : a.bg[k];
+        const float wc = w * c[k];
+        swc[k] = __shfl(group_excl_scan<64>(__shfl(wc, rl, 64), lane), rl, 64);
+        pred[k] = group_sum<64>(wc) + Tf * bg[k];
+    }
+    const float th = t2 / 2.f;
+    const float Tend = __shfl(em * T, S - 1, 64);              // the transmittance behind the last sample
+    const float inv_a = 1.f / (Asum + 1e-10f);
+    const float edep = group_sum<64>(w * th) * inv_a;          // unclipped expected depth
+    const float wu = w * (th - edep);
+    const float swu = __shfl(group_excl_scan<64>(__shfl(wu, rl, 64), lane), rl, 64);   // sum_{j>i} w_j (t_j - e)
+
+    const int D = a.pose ? 12 : 6;
+    int row = 0;
+#pragma unroll 1
+    for (int ch = 0; ch < 5; ++ch) {   // wave-uniform
+        if (!((ja.channels >> ch) & 1)) continue;
+        const int64_t rc = r * ja.C + row;
+        ++row;
+        float dsig, val;
+        float gdx = 0.f, gdy = 0.f, gdz = 0.f;   // the SH term of d row / dd
+        float d[64];
+        float d1[OUT1];
+#pragma unroll
+        for (int g = 0; g < OUT1; ++g) d1[g] = 0.f;
+        if (ch < 3) {
+            const float ck = ch == 0 ? c[0] : (ch == 1 ? c[1] : c[2]);
+            const float bk = ch == 0 ? bg[0] : (ch == 1 ? bg[1] : bg[2]);
+            const float sk = ch == 0 ? swc[0] : (ch == 1 ? swc[1] : swc[2]);
+            const float pk = ch == 0 ? pred[0] : (ch == 1 ? pred[1] : pred[2]);
+            val = fminf(fmaxf(pk, 0.f), 1.f);
+            const float live = (pk >= 0.f && pk <= 1.f && in) ? 1.f : 0.f;
+            dsig = live * delta * (em * T * (ck - bk) - sk + bk * sw);
+            const float wt = w + ((last_bg && lane == S - 1) ? Tf : 0.f);
+            const float dck = live * wt * ck * (1.f - ck);   // through the sigmoid
+            // ---- backward: colour head, this channel's column of the last layer ----
+            const pg_cfp h2t = pg_const(a.p.h2t);
+#pragma unroll
+            for (int o = 0; o < 64; ++o) d[o] = ((m2[o >> 5] >> (o & 31)) & 1u) ? dck * h2t[o * 3 + ch] : 0.f;
+            pg_dense_bwd<64, 64>(pg_const(a.p.h1t), d, A, lane);
+            load_masked64(A, lane, m1, d);
+            pg_dense_bwd<31, 64>(pg_const(a.p.h0t), d, A, lane);   // rows 0..15: dSH, 16..30: dgeo
+            {
+                float q[16];
+#pragma unroll
+                for (int j = 0; j < 16; ++j) q[j] = A[j * 64 + lane];
+                const float x = ux, y = uy, z = uz, xx = x * x, yy = y * y, zz = z * z;
+                const float c1 = 0.4886025119029199f, c2 = 1.0925484305920792f, c6 = 0.9461746957575601f, c8 = 0.5462742152960396f,
+                            c9 = 0.5900435899266435f, c10 = 2.890611442640554f, c11 = 0.4570457994644658f, c12 = 0.3731763325901154f,
+                            c14 = 1.445305721320277f;
+                const float z5 = 5.f * zz - 1.f, d3 = 3.f * (xx - yy);
+                gdx = q[3] * c1 + q[4] * (c2 * y) + q[7] * (c2 * z) + q[8] * (2.f * c8 * x) + q[9] * (6.f * c9 * x * y) + q[10] * (c10 * y * z) +
+                      q[13] * (c11 * z5) + q[14] * (2.f * c14 * x * z) + q[15] * (c9 * d3);
+                gdy = q[1] * c1 + q[4] * (c2 * x) + q[5] * (c2 * z) - q[8] * (2.f * c8 * y) + q[9] * (c9 * d3) + q[10] * (c10 * x * z) +
+                      q[11] * (c11 * z5) - q[14] * (2.f * c14 * y * z) - q[15] * (6.f * c9 * x * y);
+                gdz = q[2] * c1 + q[5] * (c2 * y) + q[6] * (2.f * c6 * z) + q[7] * (c2 * x) + q[10] * (c10 * x * y) + q[11] * (10.f * c11 * y * z) +
+                      q[12] * (c12 * (15.f * zz - 3.f)) + q[13] * (10.f * c11 * x * z) + q[14] * (c14 * (xx - yy));
+                const float du = a.p.sh_remap ? 1.f : 0.5f;
+                gdx *= du;
+                gdy *= du;
+                gdz *= du;
+            }
+#pragma unroll
+            for (int g = 0; g < 15; ++g) d1[1 + g] = A[(16 + g) * 64 + lane];
+        } else if (ch == 3) {
+            val = Asum;
+            dsig = in ? delta * Tend : 0.f;
+        } else {
+            val = edep;
+            dsig = in ? delta * inv_a * (em * T * (th - edep) - swu) : 0.f;
+        }
+        // ---- backward: trunk (the density logit; for a colour row also dgeo) ----
+        d1[0] = dsig * sig;
+        pg_dense_bwd<64, OUT1>(pg_const(a.p.w1t), d1, A, lane);
+        load_masked64(A, lane, m0, d);
+        pg_dense_bwd<32, 64>(pg_const(a.p.w0t), d, A, lane);
+
+        // ---- backward: grid -> normalised position (the corner rows are fetched again) ----
+        float gpx = 0.f, gpy = 0.f, gpz = 0.f;
+#pragma unroll 2
+        for (int l = 0; l < 16; ++l) {
+            float2 f[8];
+            float wx, wy, wz, scale;
+            pg_level_corners<GRID>(a, l, mask, px, py, pz, f, wx, wy, wz, scale);
+            const float g0 = A[(2 * l) * 64 + lane], g1 = A[(2 * l + 1) * 64 + lane];
+            float v[8];
+#pragma unroll
+            for (int k = 0; k < 8; ++k) v[k] = fmaf(g1, f[k].y, g0 * f[k].x);
+            float bx, by, bz;
+            pg_blend_grad<GRID>(v, wx, wy, wz, bx, by, bz);
+            gpx = fmaf(scale, bx, gpx);
+            gpy = fmaf(scale, by, gpy);
+            gpz = fmaf(scale, bz, gpz);
+        }
+        // ---- normalised position -> world position (pose_grad_kernel's statements) ----
+        float gx = gpx * sel, gy = gpy * sel, gz = gpz * sel;
+        if (a.box.use_aabb) {   // uniform
+            gx /= a.box.len[0];
+            gy /= a.box.len[1];
+            gz /= a.box.len[2];
+        } else {
+            gx *= 0.25f;
+            gy *= 0.25f;
+            gz *= 0.25f;
+            const float ax = fabsf(x0), ay = fabsf(y0), az = fabsf(z0);
+            const float m = fmaxf(fmaxf(ax, ay), az);
+            if (!(m < 1.f)) {
+                const float inv = 1.f / m, diag = (2.f - inv) * inv, cross = 2.f * (1.f - m) * inv * inv * inv;
+                const int k = (ax >= ay && ax >= az) ? 0 : (ay >= az ? 1 : 2);
+                const float dot = (k == 0 ? 0.f : gx * x0) + (k == 1 ? 0.f : gy * y0) + (k == 2 ? 0.f : gz * z0);
+                const float xk = k == 0 ? x0 : (k == 1 ? y0 : z0), gk = k == 0 ? gx : (k == 1 ? gy : gz);
+                const float along = gk * inv * inv + cross * (xk < 0.f ? -dot : dot);
+                gx = k == 0 ? along : gx * diag;
+                gy = k == 1 ? along : gy * diag;
+                gz = k == 2 ? along : gz * diag;
+            }
+        }
+        if (!in) gx = gy = gz = gdx = gdy = gdz = 0.f;
+        const float go0 = group_sum<64>(gx), go1 = group_sum<64>(gy), go2 = group_sum<64>(gz);
+        const float gd0 = group_sum<64>(fmaf(th, gx, gdx)), gd1 = group_sum<64>(fmaf(th, gy, gdy)), gd2 = group_sum<64>(fmaf(th, gz, gdz));
+
+        // ---- epilogue: lane j holds entry j of the row; every store is a vector store of a lane-selected value ----
+        float jv;
+        if (a.pose) {
+            const float gdd = gd0 * dxr + gd1 * dyr + gd2 * dzr;
+            const float P[3] = {gd0 - dxr * gdd, gd1 - dyr * gdd, gd2 - dzr * gdd};
+            const float go[3] = {go0, go1, go2};
+            const int rw = lane >> 2, col = lane & 3;
+            const float Pa = rw == 0 ? P[0] : (rw == 1 ? P[1] : P[2]);
+            const float ga = rw == 0 ? go[0] : (rw == 1 ? go[1] : go[2]);
+            const int cb = col < 3 ? col : 0;
+            const float q = a.rinv[cb * 3 + 0] * dxr + a.rinv[cb * 3 + 1] * dyr + a.rinv[cb * 3 + 2] * dzr;
+            jv = col == 3 ? ga : Pa * q;
+        } else {
+            jv = lane == 0 ? go0 : lane == 1 ? go1 : lane == 2 ? go2 : lane == 3 ? gd0 : lane == 4 ? gd1 : gd2;
+        }
+        if (ja.out_jac && lane < D) ja.out_jac[rc * D + lane] = jv;
+        if (ja.out_val && lane == 0) ja.out_val[rc] = val;
+        if (ja.P > 0 && (ja.out_proj || ja.out_var)) {   // uniform
+            const int P = ja.P;
+            const int k = lane < P ? lane : 0;
+            float pv = 0.f;
+            for (int j = 0; j < D; ++j) pv = fmaf(__shfl(jv, j, 64), ja.proj[j * P + k], pv);
+            if (ja.out_proj && lane < P) ja.out_proj[rc * P + lane] = pv;
+            if (ja.out_var) {
+                float var = 0.f;
+                for (int q = 0; q < P; ++q) {
+                    const float v = __shfl(pv, q, 64);
+                    var = fmaf(v, v, var);
+                }
+                if (lane == 0) ja.out_var[rc] = var;
+            }
+        }
+    }
+}
+
+extern "C" int unerf_pose_jacobian(const float* origins, const float* directions, const float* sbins, int64_t R, int S,
+                                   float near_plane, float far_plane, int spacing, const unerf_field_params* p, int background,
+                                   const float* background_rgb, const float* rot_inv, int channels, const float* proj, int P,
+                                   float* out_jac, float* out_proj, float* out_var, float* out_val, void* stream) {
+    constexpr int CH_KNOWN = UNERF_POSE_CH_R | UNERF_POSE_CH_G | UNERF_POSE_CH_B | UNERF_POSE_CH_ACC | UNERF_POSE_CH_EDEPTH;
+    UNERF_REQUIRE(R >= 0 && S >= 1 && S <= 64, "pose_jacobian: S=%d outside [1,64]", S);
+    UNERF_REQUIRE(channels != 0, "pose_jacobian: channels is empty (a non-empty subset of UNERF_POSE_CH_*)");
+    UNERF_REQUIRE((channels & ~CH_KNOWN) == 0, "pose_jacobian: unknown bits in channels=%d", channels);
+    UNERF_REQUIRE(!proj || (P >= 1 && P <= 12), "pose_jacobian: P=%d outside [1,12]", P);
+    UNERF_REQUIRE(proj || (!out_proj && !out_var), "pose_jacobian: out_proj / out_var need proj");
+    UNERF_REQUIRE(out_jac || out_proj || out_var || out_val, "pose_jacobian: no output requested (out_jac, out_proj, out_var and out_val are all NULL)");
+    if (R == 0) return UNERF_OK;
+    UNERF_REQUIRE(origins && directions && sbins && p, "pose_jacobian: null pointer");
+    UNERF_REQUIRE(p->mode == UNERF_FIELD_ACTIVE || p->mode == UNERF_FIELD_MCDROPOUT,
+                  "pose_jacobian: mode %d (a nerfacto / active-nerfacto field is needed: the Laplace field's sampled heads are "
+                  "not differentiated)", p->mode);
+    UNERF_REQUIRE(p->hidden == 0 && p->hidden_color == 0 && p->geo_dim == 0 && p->feat_per_level == 0 && p->L == 16,
+                  "pose_jacobian: nerfacto's widths only (hidden 64 / 64, geo 15, 2 features x 16 levels)");
+    UNERF_REQUIRE(p->out1 == (p->mode == UNERF_FIELD_ACTIVE ? 17 : 16), "pose_jacobian: trunk output %d does not fit mode %d", p->out1,
+                  p->mode);
+    UNERF_REQUIRE(p->table && p->w0t && p->b0 && p->w1t && p->b1 && p->h0t && p->hb0 && p->h1t && p->hb1 && p->h2t && p->hb2 &&
+                      (p->scalings || p->tcnn_levels),
+                  "pose_jacobian: null field pointer");
+    UNERF_REQUIRE(p->tcnn_levels || (p->log2T >= 1 && p->log2T <= 24), "pose_jacobian: bad log2T=%d", p->log2T);
+    UNERF_REQUIRE(p->tcnn_levels || !p->grid_half, "pose_jacobian: grid_half needs a tcnn-layout grid");
+    UNERF_REQUIRE(near_plane >= 0.f, "pose_jacobian: near_plane=%g (spacing-domain bins only)", (double)near_plane);
+    PoseJacArgs j;
+    PoseGradArgs& g = j.g;
+    g.origins = origins; g.dirs = directions; g.sbins = sbins; g.R = R; g.S = S;
+    if (int rc = set_spacing(g, near_plane, far_plane, spacing)) return rc;
+    g.p = *p;
+    g.box = make_norm_box(p->use_aabb, p->aabb);
+    if (int rc = unerf_set_background(g, background, background_rgb, "pose_jacobian")) return rc;
+    g.pose = rot_inv ? 1 : 0;
+    for (int k = 0; k < 9; ++k) g.rinv[k] = rot_inv ? rot_inv[k] : 0.f;
+    g.out_grad = nullptr; g.out_rgb = nullptr;
+    j.channels = channels;
+    j.C = __builtin_popcount((unsigned)channels);
+    j.P = proj ? P : 0;
+    const int D = rot_inv ? 12 : 6;
+    for (int k = 0; k < 144; ++k) j.proj[k] = (proj && k < D * P) ? proj[k] : 0.f;
+    j.out_jac = out_jac; j.out_proj = out_proj; j.out_var = out_var; j.out_val = out_val;
+    UNERF_REQUIRE(R < (1ll << 32), "pose_jacobian: R=%lld rays in one launch, split the batch", (long long)R);
+    const int64_t blocks = (R + 3) / 4;   // pose_grad_kernel's geometry
+    constexpr size_t lds_bytes = 4 * 64 * 64 * sizeof(float);
+    with_int3(tcnn_arg(g.p), [&](auto tc) {
+        with_bool(g.p.out1 == 17, [&](auto wide) {
+            hipLaunchKernelGGL((pose_jac_kernel<decltype(wide)::value ? 17 : 16, decltype(tc)::value>), dim3((unsigned)blocks), dim3(256),
+                               lds_bytes, (hipStream_t)stream, j);
+        });
+    });
+    return unerf_check_launch("pose_jacobian");
+}
+
+// --------------------------------------------------------------------------------------
 // 5e'. The same gradient of an MC-DROPOUT frame under a named mask draw: rgb = (1/K) sum_k clamp(pred_k), pass k with the
 // keep masks of (seed, pass, sample, unit) -- the counter generator's, or explicit bit arrays (unerf_keep_masks).  Under a
 // fixed draw every pass is the deterministic piecewise-smooth function pose_grad_kernel differentiates, with h -> h keep /

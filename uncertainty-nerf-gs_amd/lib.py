@@ -249,6 +249,8 @@ SIGNATURES = {
     "unerf_laplace_ggn_diag": (_i, [_vp, _vp, _vp, _i64, _i, _f, _f, _i, C.POINTER(FieldParams), _i, _fp, _vp, C.c_size_t,
                                     _vp, _vp, _vp]),
     "unerf_pose_grad": (_i, [_vp, _vp, _vp, _i64, _i, _f, _f, _i, C.POINTER(FieldParams), _i, _fp, _fp, _vp, _vp, _vp]),
+    "unerf_pose_jacobian": (_i, [_vp, _vp, _vp, _i64, _i, _f, _f, _i, C.POINTER(FieldParams), _i, _fp, _fp, _i, _fp, _i, _vp, _vp, _vp,
+                                 _vp, _vp]),
     "unerf_pose_grad_mc": (_i, [_vp, _vp, _vp, _i64, _i, _f, _f, _i, _i64, C.POINTER(FieldParams), C.POINTER(KeepMasks), _i, _fp,
                                 _fp, _vp, _vp, _vp]),
     "unerf_pose_grad_laplace": (_i, [_vp, _vp, _vp, _i64, _i, _f, _f, _i, _i64, C.POINTER(FieldParams), _i, _fp, _fp, _vp, _vp, _vp]),

@@ -496,6 +496,57 @@ class _NerfactoBase(nn.Module, _ImageMetrics):
         return render.pose_gradient_camera(scene, c2w, rays_per_launch=rays_per_launch or self.rays_per_launch,
                                            want_rgb=want_rgb, **cam)
 
+    def _require_pose_jacobian(self, what: str) -> None:
+        if self._no_pose_gradient is not None:
+            raise NotImplementedError(f"{type(self).__name__}.{what}: pose Jacobians are not built for this model (the "
+                                      "Jacobian kernel differentiates one deterministic nerfacto / active-nerfacto field).")
+
+    @torch.no_grad()
+    def get_pose_jacobians_for_camera(self, camera, channels=ops.POSE_CHANNELS, basis: str = "se3",
+                                      rays_per_launch: Optional[int] = None) -> Dict[str, torch.Tensor]:
+        """The per-pixel Jacobian of the rendered channels with respect to the camera pose ->
+        {"jacobian": [H,W,C,6 | 12], "values": [H,W,C]} float32 on the device; the C rows in ops.POSE_CHANNELS order
+        (r, g, b, accumulation, expected_depth).  basis "se3": the six parameters of posegrad.POSE_PARAMS (tx .. angz of
+        c2w . exp(xi), the camera's own frame; contracted in the kernel with posegrad.tangent_basis); "c2w": the twelve
+        entries of camera_to_worlds, row-major 3x4.  r / g / b follow get_pose_gradients_for_camera's rules (their mean over
+        the channels is its quantity).  expected_depth is the UNCLIPPED quotient sum w t / (sum w + 1e-10): the clip of the
+        rendered expected depth to the ray's step range is not applied and not differentiated (it is the identity except
+        where the accumulation is of the order of 1e-10).  Sample bins held fixed, fp32."""
+        self._require_pose_jacobian("get_pose_jacobians_for_camera")
+        if basis not in ("se3", "c2w"):
+            raise ValueError(f"get_pose_jacobians_for_camera: basis={basis!r} (expected 'se3' or 'c2w')")
+        from . import posegrad
+        c2w, cam = _camera_args(camera)
+        kw = dict(channels=channels, rays_per_launch=rays_per_launch or self.rays_per_launch, **cam)
+        if basis == "se3":
+            out = render.pose_jacobian_camera(self.device_scene(), c2w, proj=posegrad.pose_projection(c2w, None),
+                                              want=("proj", "val"), **kw)
+            return {"jacobian": out["proj"], "values": out["val"]}
+        out = render.pose_jacobian_camera(self.device_scene(), c2w, want=("jac", "val"), **kw)
+        return {"jacobian": out["jac"], "values": out["val"]}
+
+    @torch.no_grad()
+    def get_pose_uncertainty_for_camera(self, camera, pose_cov, rays_per_launch: Optional[int] = None) -> Dict[str, torch.Tensor]:
+        """First-order propagation of a pose covariance to every pixel: var_c = J_c Sigma J_c^T per channel, from one kernel
+        pass (posegrad.pose_projection(c2w, pose_cov) contracted and squared in the Jacobian kernel).  pose_cov: [6,6] in
+        posegrad.POSE_PARAMS order (the camera's own frame), or a 6-vector of standard deviations.  -> [H,W,1] each:
+          rgb_var_pose = mean_c var_c and rgb_std_pose = its root (the ensemble's convention, ensemble_pipeline.py:165-174),
+          expected_depth_std_pose, accumulation_std_pose,
+          and rgb [H,W,3], accumulation, expected_depth as the kernel composited them (expected_depth unclipped, see
+          get_pose_jacobians_for_camera)."""
+        self._require_pose_jacobian("get_pose_uncertainty_for_camera")
+        if pose_cov is None:
+            raise ValueError("get_pose_uncertainty_for_camera: pose_cov is needed ([6,6] or 6 standard deviations)")
+        from . import posegrad
+        c2w, cam = _camera_args(camera)
+        out = render.pose_jacobian_camera(self.device_scene(), c2w, proj=posegrad.pose_projection(c2w, pose_cov),
+                                          want=("var", "val"), rays_per_launch=rays_per_launch or self.rays_per_launch, **cam)
+        var, val = out["var"], out["val"]
+        rgb_var = var[..., :3].mean(dim=-1, keepdim=True)
+        return {"rgb_var_pose": rgb_var, "rgb_std_pose": rgb_var.sqrt(),
+                "accumulation_std_pose": var[..., 3:4].sqrt(), "expected_depth_std_pose": var[..., 4:5].sqrt(),
+                "rgb": val[..., :3], "accumulation": val[..., 3:4], "expected_depth": val[..., 4:5]}
+
     def _begin_render_views(self, scene: NerfSceneDev, n_views: int) -> Tuple[bool, Optional[List[int]]]:
         """once per get_outputs_for_cameras call -> (render the batch through render.render_cameras, mask seed per view |
         None); False: the model renders its cameras one by one through get_outputs_for_camera"""
@@ -1114,6 +1165,14 @@ class SplatfactoModel(nn.Module, _ImageMetrics):
         return splat.pose_gradient_camera(gp, c2w, background=self.background_color.to(gp["means"].device), sh_degree=n,
                                           rasterize_mode=self.config.rasterize_mode, crop_ids=crop_ids,
                                           config_sh_degree=self.config.sh_degree, want_rgb=want_rgb, **cam)
+
+    def get_pose_jacobians_for_camera(self, camera, **kw):
+        raise NotImplementedError(f"{type(self).__name__}.get_pose_jacobians_for_camera: pose Jacobians are not built for "
+                                  "splat models (get_pose_gradients_for_camera gives d mean_c(rgb) / d camera_to_worlds).")
+
+    def get_pose_uncertainty_for_camera(self, camera, pose_cov=None, **kw):
+        raise NotImplementedError(f"{type(self).__name__}.get_pose_uncertainty_for_camera: pose Jacobians are not built for "
+                                  "splat models.")
 
     @torch.no_grad()
     def get_outputs_for_cameras(self, cameras, obb_box=None, max_views: int = 8) -> List[Dict[str, Optional[torch.Tensor]]]:

@@ -1269,6 +1269,71 @@ def pose_grad(origins, directions, sbins, field: FieldDev, near: float, far: flo
     return (grad, rgb) if want_rgb else grad
 
 
+POSE_CHANNELS = ("r", "g", "b", "accumulation", "expected_depth")   # bit order of include/unerf.h: UNERF_POSE_CH_*
+
+
+def pose_channel_bits(channels) -> int:
+    """names of POSE_CHANNELS (any order, each once) -> the UNERF_POSE_CH_* bit set; the rows come back in POSE_CHANNELS order"""
+    names = [channels] if isinstance(channels, str) else list(channels)
+    bits = 0
+    for n in names:
+        if n not in POSE_CHANNELS:
+            raise _l.UnerfError(f"pose_jacobian: channel {n!r} (expected some of {', '.join(POSE_CHANNELS)})")
+        if bits & (1 << POSE_CHANNELS.index(n)):
+            raise _l.UnerfError(f"pose_jacobian: channel {n!r} is named twice")
+        bits |= 1 << POSE_CHANNELS.index(n)
+    if not bits:
+        raise _l.UnerfError("pose_jacobian: channels is empty")
+    return bits
+
+
+def pose_jacobian(origins, directions, sbins, field: FieldDev, near: float, far: float, rot_inv: Optional[torch.Tensor] = None,
+                  channels=POSE_CHANNELS, proj: Optional[torch.Tensor] = None, spacing: int = 0, background=None,
+                  want=("jac",)):
+    """Per-ray pose Jacobian of the selected rendered channels behind one forward pass (unerf_pose_jacobian): rows in
+    POSE_CHANNELS order, whatever order `channels` names them in; r / g / b under pose_grad's rules, accumulation, and the
+    UNCLIPPED expected depth sum w t / (sum w + 1e-10).  rot_inv None -> D = 6 (d/do, d/dd); [3,3] -> D = 12 (d/dc2w).
+    proj: None or [D,P] (1 <= P <= 12), e.g. posegrad.pose_projection.  want: some of
+      "jac" [R,C,D]   "proj" [R,C,P] = jac . proj   "var" [R,C] = sum_k proj_k^2   "val" [R,C] = the channels' values
+    -> dict of the requested entries"""
+    lib = _l.load()
+    if field.mode not in (_l.FIELD_ACTIVE, _l.FIELD_MCDROPOUT):
+        raise _l.UnerfError("pose_jacobian needs a nerfacto / active-nerfacto field: it is not built for the Laplace field "
+                            "(MC-dropout frames, ensembles and splats are out of its scope as well)")
+    bits = pose_channel_bits(channels)
+    want = (want,) if isinstance(want, str) else tuple(want)
+    if not want or any(w not in ("jac", "proj", "var", "val") for w in want):
+        raise _l.UnerfError(f"pose_jacobian: want={want!r} (expected a non-empty subset of 'jac', 'proj', 'var', 'val')")
+    if proj is None and ("proj" in want or "var" in want):
+        raise _l.UnerfError("pose_jacobian: 'proj' / 'var' need proj")
+    R, S = sbins.shape[0], sbins.shape[1] - 1
+    dev = origins.device
+    cs = field.cstruct()
+    ri = None
+    if rot_inv is not None:
+        vals = [float(v) for v in torch.as_tensor(rot_inv).detach().cpu().to(torch.float32).reshape(-1)]
+        if len(vals) != 9:
+            raise _l.UnerfError(f"pose_jacobian: rot_inv must have 9 entries, got {len(vals)}")
+        ri = (C.c_float * 9)(*vals)
+    D, Cn = (6 if ri is None else 12), bin(bits).count("1")
+    pj, P = None, 0
+    if proj is not None:
+        pt = torch.as_tensor(proj).detach().cpu().to(torch.float32)
+        if pt.dim() != 2 or pt.shape[0] != D:
+            raise _l.UnerfError(f"pose_jacobian: proj must be [{D},P], got {tuple(pt.shape)}")
+        P = int(pt.shape[1])
+        pj = (C.c_float * max(1, D * P))(*[float(v) for v in pt.reshape(-1)])
+    shapes = {"jac": (R, Cn, D), "proj": (R, Cn, P), "var": (R, Cn), "val": (R, Cn)}
+    out = {k: torch.empty(*shapes[k], device=dev, dtype=torch.float32) for k in want}
+    bg_mode, bg_rgb = _background(background)
+    with _ctx(dev):
+        _run("pose_jacobian", lambda: lib.unerf_pose_jacobian(_p(origins), _p(directions), _p(sbins), R, S, near, far, spacing,
+                                                              C.byref(cs), bg_mode, bg_rgb, ri, bits, pj, P, _p(out.get("jac")),
+                                                              _p(out.get("proj")), _p(out.get("var")), _p(out.get("val")),
+                                                              _stream()))
+    return out
+
+
 def pose_grad_mc(origins, directions, sbins, field: FieldDev, near: float, far: float, ray_offset: int = 0,
                  keep_masks: Optional[KeepMasks] = None, rot_inv: Optional[torch.Tensor] = None, spacing: int = 0,
                  background=None, want_rgb: bool = False):

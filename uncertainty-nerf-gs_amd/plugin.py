@@ -183,6 +183,26 @@ def _build() -> Dict[str, Any]:
             return fn(camera, **kw)
 
         @torch.no_grad()
+        def get_pose_jacobians_for_camera(self, camera, **kw):
+            """{"jacobian": [H,W,C,6|12], "values": [H,W,C]} (channels=, basis="se3"|"c2w", rays_per_launch=:
+            models._NerfactoBase.get_pose_jacobians_for_camera); the mc-dropout, Laplace and splat mirrors raise
+            NotImplementedError"""
+            fn = getattr(self._mirror, "get_pose_jacobians_for_camera", None)
+            if fn is None:
+                raise NotImplementedError(f"pose Jacobians are not built for {type(self._mirror).__name__}.")
+            return fn(camera, **kw)
+
+        @torch.no_grad()
+        def get_pose_uncertainty_for_camera(self, camera, pose_cov, **kw):
+            """a pose covariance propagated to per-pixel standard deviations (rgb_std_pose, expected_depth_std_pose,
+            accumulation_std_pose, ...: models._NerfactoBase.get_pose_uncertainty_for_camera); the mc-dropout, Laplace and
+            splat mirrors raise NotImplementedError"""
+            fn = getattr(self._mirror, "get_pose_uncertainty_for_camera", None)
+            if fn is None:
+                raise NotImplementedError(f"pose Jacobians are not built for {type(self._mirror).__name__}.")
+            return fn(camera, pose_cov, **kw)
+
+        @torch.no_grad()
         def get_mc_pose_gradients_for_camera(self, camera, **kw):
             """the pose gradient of an MC-dropout frame under a named mask draw (mask_seed=, rays_per_launch=, want_rgb=:
             models.NerfactoMCDropoutModel.get_mc_pose_gradients_for_camera); other mirrors raise NotImplementedError"""

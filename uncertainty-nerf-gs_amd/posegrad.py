@@ -75,6 +75,58 @@ def perturbed_pose(c2w: torch.Tensor, param: str, magnitude: float) -> torch.Ten
     return pose_multiply(c2w[:3, :4], exp_map_se3(p)[0])
 
 
+def tangent_basis(c2w: torch.Tensor) -> torch.Tensor:
+    """[12,6] float64: column k = d vec(pose_multiply(c2w, exp_map_se3(xi))) / d xi_k at xi = 0, POSE_PARAMS order, vec
+    row-major over the 3x4 pose.  Closed form: a translation along camera axis k moves the origin by c2w[:3,k] (column 3);
+    a rotation about camera axis k turns the 3x3 block into c2w[:3,:3] [e_k]x.  c2w[:3,:3] need not be orthogonal."""
+    c2w = torch.as_tensor(c2w).detach().cpu().to(torch.float64)
+    c2w = (c2w[0] if c2w.dim() == 3 else c2w)[:3, :4]
+    Rm = c2w[:, :3]
+    B = torch.zeros(3, 4, 6, dtype=torch.float64)
+    for k in range(3):
+        B[:, 3, k] = Rm[:, k]
+        ek = torch.zeros(3, 3, dtype=torch.float64)   # [e_k]x
+        ek[(k + 2) % 3, (k + 1) % 3] = 1.0
+        ek[(k + 1) % 3, (k + 2) % 3] = -1.0
+        B[:, :3, 3 + k] = Rm @ ek
+    return B.reshape(12, 6)
+
+
+def pose_projection(c2w: torch.Tensor, pose_cov=None) -> torch.Tensor:
+    """[12,P] float64 = tangent_basis(c2w) @ L with L L^T = the [6,6] covariance of the pose parameters (POSE_PARAMS order,
+    the camera's own frame): what ops.pose_jacobian(proj=) contracts a d/dc2w row with, so that the sum of squares over P is
+    the first-order variance row Sigma row^T.  pose_cov: None -> the basis itself (P = 6: the Jacobian in the six
+    parameters); a 6-vector of standard deviations -> a diagonal covariance; a [6,6] symmetric positive semi-definite matrix ->
+    its Cholesky factor, a zero pivot's column left out (P = its rank, at least one column)."""
+    B = tangent_basis(c2w)
+    if pose_cov is None:
+        return B
+    cov = torch.as_tensor(pose_cov).detach().cpu().to(torch.float64)
+    if cov.shape == (6,):
+        if bool((cov < 0).any()):
+            raise ValueError("pose_projection: a standard deviation is negative")
+        L = torch.diag(cov)
+    elif cov.shape == (6, 6):
+        if not torch.allclose(cov, cov.T, rtol=1e-10, atol=0.0):
+            raise ValueError("pose_projection: pose_cov is not symmetric")
+        L = torch.zeros(6, 6, dtype=torch.float64)
+        tol = 1e-14 * float(cov.diagonal().abs().max())
+        for j in range(6):   # Cholesky by columns; a pivot at rounding level ends its column (semi-definite input)
+            piv = float(cov[j, j] - (L[j, :j] ** 2).sum())
+            if piv < -1e-10 * float(cov.diagonal().abs().max()):
+                raise ValueError("pose_projection: pose_cov is not positive semi-definite")
+            if piv <= tol:
+                continue
+            L[j, j] = piv ** 0.5
+            L[j + 1:, j] = (cov[j + 1:, j] - L[j + 1:, :j] @ L[j, :j]) / L[j, j]
+    else:
+        raise ValueError(f"pose_projection: pose_cov must be None, [6] or [6,6], got {tuple(cov.shape)}")
+    keep = (L != 0).any(dim=0)
+    if not bool(keep.any()):
+        keep[0] = True   # a zero covariance: one zero column, the variance is exactly 0
+    return B @ L[:, keep]
+
+
 def export_pose_gradients(model, camera, image_idx: int, output_dir, shift_param: str = "tz", shift_magnitude: float = 0.0,
                           seed: int = 42, gradient_fn=None) -> Dict[str, Path]:
     """One image of estimate_gradient_pose_6dof.py:109-216 -> the files it writes under output_dir / f"image_{image_idx}":

@@ -384,8 +384,17 @@ def pose_gradient_camera(scene: NerfSceneDev, c2w: torch.Tensor, fx: float, fy: 
 
 def _pose_gradient_groups(what: str, scene: NerfSceneDev, c2w: torch.Tensor, fx, fy, cx, cy, H: int, W: int, rays_per_launch: int,
                           obb, distortion, camera_type: int, want_rgb: bool, launch):
-    """the loop of pose_gradient_camera / pose_gradient_camera_mc / pose_gradient_camera_laplace: rays -> proposal sampler ->
-    launch(o, d, sb, start, rot_inv) per group of rays_per_launch rays"""
+    """pose_gradient_camera / pose_gradient_camera_mc / pose_gradient_camera_laplace: _pose_group_results' loop, the groups'
+    gradients joined to [H,W,3,4]"""
+    res = _pose_group_results(what, scene, c2w, fx, fy, cx, cy, H, W, rays_per_launch, obb, distortion, camera_type, launch)
+    g = torch.cat([r[0] if want_rgb else r for r in res]).view(H, W, 3, 4)
+    return (g, torch.cat([r[1] for r in res]).view(H, W, 3)) if want_rgb else g
+
+
+def _pose_group_results(what: str, scene: NerfSceneDev, c2w: torch.Tensor, fx, fy, cx, cy, H: int, W: int, rays_per_launch: int,
+                        obb, distortion, camera_type: int, launch) -> list:
+    """the loop of the pose_gradient_camera* functions and pose_jacobian_camera: rays -> proposal sampler ->
+    launch(o, d, sb, start, rot_inv) per group of rays_per_launch rays -> the groups' results in ray order"""
     _l.require_gpu()
     if int(camera_type) == _l.CAMERA_ORTHOPHOTO:
         raise _l.UnerfError(f"{what}: an ORTHOPHOTO camera's ray origins depend on the rotation; not differentiated")
@@ -396,18 +405,39 @@ def _pose_gradient_groups(what: str, scene: NerfSceneDev, c2w: torch.Tensor, fx,
     c2w = c2w.detach().cpu().to(torch.float32)
     rot_inv = torch.linalg.inv(c2w[:3, :3].double()).to(torch.float32)
     rpl = max(1, int(rays_per_launch))
-    grads, rgbs = [], []
+    results = []
     with torch.cuda.device(dev):
         for start in range(0, total, rpl):
             o, d, _ = ops.generate_rays(c2w, fx, fy, cx, cy, H, W, dev, start, min(rpl, total - start), distortion=distortion,
                                         camera_type=camera_type)
             sb, _ = sample_rays(scene, o, d, None, start, want_prop_depth=False, image_width=W, workspace=scene.workspace)
-            res = launch(o, d, sb, start, rot_inv)
-            grads.append(res[0] if want_rgb else res)
-            if want_rgb:
-                rgbs.append(res[1])
-    g = torch.cat(grads).view(H, W, 3, 4)
-    return (g, torch.cat(rgbs).view(H, W, 3)) if want_rgb else g
+            results.append(launch(o, d, sb, start, rot_inv))
+    return results
+
+
+def pose_jacobian_camera(scene: NerfSceneDev, c2w: torch.Tensor, fx: float, fy: float, cx: float, cy: float, H: int, W: int,
+                         channels=ops.POSE_CHANNELS, proj=None, want=("jac",), rays_per_launch: int = 1 << 20, obb=None,
+                         distortion=None, camera_type: int = 1):
+    """ops.pose_jacobian for every pixel of one camera, with respect to c2w (D = 12, row-major 3x4): the loop of
+    pose_gradient_camera (bins held fixed; ORTHOPHOTO cameras and `obb` crops refused), one launch per group of
+    rays_per_launch rays, which the result does not depend on.  proj: None or [12,P] (posegrad.pose_projection).
+    -> {"jac": [H,W,C,12], "proj": [H,W,C,P], "var": [H,W,C], "val": [H,W,C]}, the entries `want` names; the C rows in
+    ops.POSE_CHANNELS order.  The expected depth is the unclipped quotient (include/unerf.h: unerf_pose_jacobian)."""
+    if scene.field.mode not in (_l.FIELD_ACTIVE, _l.FIELD_MCDROPOUT):
+        raise _l.UnerfError("pose_jacobian_camera: the scene's field is not a nerfacto / active-nerfacto field (not built for "
+                            "the Laplace field)")
+    want = (want,) if isinstance(want, str) else tuple(want)
+    res = _pose_group_results("pose_jacobian_camera", scene, c2w, fx, fy, cx, cy, H, W, rays_per_launch, obb, distortion,
+                              camera_type,
+                              lambda o, d, sb, start, rot_inv: ops.pose_jacobian(o, d, sb, scene.field, scene.near, scene.far,
+                                                                                 rot_inv=rot_inv, channels=channels, proj=proj,
+                                                                                 spacing=scene.spacing,
+                                                                                 background=scene.background, want=want))
+    out = {}
+    for k in want:
+        t = torch.cat([r[k] for r in res])
+        out[k] = t.view(H, W, *t.shape[1:])
+    return out
 
 
 def pose_gradient_camera_mc(scene: NerfSceneDev, c2w: torch.Tensor, fx: float, fy: float, cx: float, cy: float, H: int, W: int,
