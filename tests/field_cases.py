@@ -5,7 +5,9 @@ field_kernel<ACTIVE | MCDROPOUT> (VALU, one wave per 64 samples), field_kernel_m
 kernel; fused lookup and pre-gathered features, all three grid layouts), field_kernel_mfma16 in its split form ("f16x2":
 hi*hi + hi*lo + lo*hi) and its single-product form ("f16"), the three (SITES, DROP) forms, and the explicit-mask (KeepArgs)
 instantiations of each.  The LAPLACE kernels and the GGN fit have a module of their own, tests/laplace_cases.py (their
-E[x^2] - E[x]^2 outputs carry a bound that scales with the sample's own second moment).  OUT of scope: field_kernel_generic, the several-views kernels (tests/test_gpu_nerf_view_batch.py compares them bit for bit with single
+E[x^2] - E[x]^2 outputs carry a bound that scales with the sample's own second moment), and so has field_kernel_generic, the
+any-width kernel: tests/width_cases.py (it reuses `reference` and the bound routines here, which take the layer widths from the
+net).  OUT of scope: the several-views kernels (tests/test_gpu_nerf_view_batch.py compares them bit for bit with single
 launches) and the R * S >= 2^31 addressing, which is out of reach at test size.
 
 Nets (L = 16, 64 / 64 / 15 / 2, log2T 8 .. 12, a non-zero appearance embedding): the torch hash table, the tcnn layout with
@@ -157,16 +159,23 @@ def net(name):
     return c
 
 
+def widths(nt):
+    """-> (H, HC, G, AD) of a net: the trunk's and the colour head's hidden widths, the geo features and the appearance
+    embedding (nerfacto's 64 / 64 / 15 / 32 unless the net says otherwise)"""
+    return nt.w0.shape[0], nt.h1.shape[0], getattr(nt, "G", 15), nt.app.shape[0]
+
+
 def field_params(nt, mode, dtype=torch.float32, aabb="own"):
     """the net as the oracle's FieldParams"""
     t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dtype)
-    out1 = 17 if mode == ACTIVE else 16
+    G = widths(nt)[2]
+    out1 = G + 2 if mode == ACTIVE else G + 1
     box = nt.aabb if aabb == "own" else aabb
     g = O.GridMLP(table=t(nt.table), scalings=None if nt.scalings is None else t(nt.scalings), log2_T=nt.log2T,
                   weights=[t(nt.w0), t(nt.w1[:out1])], biases=[t(nt.b0), t(nt.b1[:out1])], tcnn_levels=nt.levels,
                   aabb=None if box is None else t(np.array(box, f32).reshape(2, 3)), grid_half=nt.layout == "tcnn16")
     return O.FieldParams(grid=g, head_w=[t(nt.h0), t(nt.h1), t(nt.h2)], head_b=[t(nt.hb0), t(nt.hb1), t(nt.hb2)], appearance=t(nt.app),
-                         average_init_density=AVG, beta_min=BETA_MIN, sh_remap=bool(nt.sh_remap))
+                         average_init_density=AVG, beta_min=BETA_MIN, sh_remap=bool(nt.sh_remap), geo_feat_dim=G)
 
 
 # ------------------------------------------------------------------------------------------- the fp32 list: SH inputs
@@ -308,7 +317,9 @@ def reference(nt, mode, P32, sel, shin, K, p, sites, keeps, rounded):
         s = sc if on & site else 1.0
         return _hi(packed_weight(w, s)) if rounded else d64(w) * s
 
-    out1 = 17 if mode == ACTIVE else 16
+    H, HC, G, AD = widths(nt)
+    INC = 16 + G                 # the folded first colour layer's inputs [SH16 | geo]
+    out1 = G + 2 if mode == ACTIVE else G + 1
     feat, dfeat = PC._features64(nt, d64(P32))
     sh = _sh16(d64(shin))
     dsh = 8 * U * _sh16(d64(shin), absolute=True)
@@ -316,13 +327,13 @@ def reference(nt, mode, P32, sel, shin, K, p, sites, keeps, rounded):
     a0, e0 = _layer(feat, W0, d64(nt.b0), fams)
     cons0 = {f: dfeat @ np.abs(W0).T + e0[f] for f in fams}
     h = np.maximum(a0, 0)
-    hb0 = d64(nt.hb0) + d64(nt.h0[:, 31:]) @ d64(nt.app)
+    hb0 = d64(nt.hb0) + d64(nt.h0[:, INC:]) @ d64(nt.app)
     res = SimpleNamespace(dens=np.zeros((B, N)), rgb=np.zeros((B, N, 3)), beta=None, b_dens={f: np.zeros((B, N)) for f in fams},
                           b_rgb={f: np.zeros((B, N, 3)) for f in fams}, b_beta={}, o=np.zeros((B, N)), c=np.zeros((B, N, 3)))
     for k in range(B):
-        keep = lambda site, width=64: d64(keeps[site][k][:, :width]) if site in keeps else np.ones((N, width))
+        keep = lambda site, width: d64(keeps[site][k][:, :width]) if site in keeps else np.ones((N, width))
         # trunk out
-        mT = keep(TRUNK)
+        mT = keep(TRUNK, H)
         live0, amb0 = _gate(a0, cons0, mT)
         W1 = W(nt.w1[:out1], TRUNK)
         t, e1 = _layer(h * mT, W1, d64(nt.b1[:out1]), fams)
@@ -332,23 +343,23 @@ def reference(nt, mode, P32, sel, shin, K, p, sites, keeps, rounded):
         cons_t = {f: (cons0[f] * mT) @ np.abs(W1).T + e1[f] for f in fams}
         # colour 0
         if on & HEADIN:      # the first colour layer unfolded (VALU kernel only)
-            mI = keep(HEADIN, 63)
+            mI = keep(HEADIN, INC + AD)
             H0 = W(nt.h0, HEADIN)
-            x = np.concatenate([sh, t[:, 1:16], np.broadcast_to(d64(nt.app), (N, 32))], axis=1) * mI
+            x = np.concatenate([sh, t[:, 1:1 + G], np.broadcast_to(d64(nt.app), (N, AD))], axis=1) * mI
             c0, e2 = _layer(x, H0, d64(nt.hb0), fams)
         else:
-            mI = np.ones((N, 31))
-            H0 = W(nt.h0[:, :31], 0)
-            c0, e2 = _layer(np.concatenate([sh, t[:, 1:16]], axis=1), H0, hb0, fams)
-        aH0 = np.abs(H0[:, :31])
-        cons_c0 = {f: (np.concatenate([dsh, cons_t[f][:, 1:16]], axis=1) * mI[:, :31]) @ aH0.T + e2[f] for f in fams}
+            mI = np.ones((N, INC))
+            H0 = W(nt.h0[:, :INC], 0)
+            c0, e2 = _layer(np.concatenate([sh, t[:, 1:1 + G]], axis=1), H0, hb0, fams)
+        aH0 = np.abs(H0[:, :INC])
+        cons_c0 = {f: (np.concatenate([dsh, cons_t[f][:, 1:1 + G]], axis=1) * mI[:, :INC]) @ aH0.T + e2[f] for f in fams}
         # colour 1 and 2
-        m0 = keep(HEAD0)
+        m0 = keep(HEAD0, HC)
         live1, amb1 = _gate(c0, cons_c0, m0)
         H1 = W(nt.h1, HEAD0)
         c1, e3 = _layer(np.maximum(c0, 0) * m0, H1, d64(nt.hb1), fams)
         cons_c1 = {f: (cons_c0[f] * m0) @ np.abs(H1).T + e3[f] for f in fams}
-        m1 = keep(HEAD1)
+        m1 = keep(HEAD1, HC)
         live2, amb2 = _gate(c1, cons_c1, m1)
         H2 = W(nt.h2, HEAD1)
         c2, e4 = _layer(np.maximum(c1, 0) * m1, H2, d64(nt.hb2), fams, matrix=False)
@@ -356,12 +367,12 @@ def reference(nt, mode, P32, sel, shin, K, p, sites, keeps, rounded):
         # the error passes it on exactly by its weight; |J| of the signed product, never wider than the product of |W|
         J4 = H2[None] * live2[:, None, :]                                    # c1 -> c2
         J3 = J4 @ (H1[None] * live1[:, None, :])                             # c0 -> c2
-        J2 = J3 @ (H0[None, :, 16:31] * mI[:, None, 16:31])                  # geo -> c2
+        J2 = J3 @ (H0[None, :, 16:INC] * mI[:, None, 16:INC])                # geo -> c2
         Jsh = J3 @ (H0[None, :, :16] * mI[:, None, :16])                     # SH16 -> c2
-        J1 = J2 @ Jt[:, 1:16, :]                                             # a0 -> c2
+        J1 = J2 @ Jt[:, 1:1 + G, :]                                          # a0 -> c2
         Jf = J1 @ W0
-        amb = amb2 @ np.abs(H2).T + _bm(J4 @ H1[None], amb1) + _bm(J2 @ W1[None, 1:16], amb0)
-        dc2 = {f: e4[f] + _bm(J4, e3[f]) + _bm(J3, e2[f]) + _bm(J2, e1[f][:, 1:16]) + _bm(J1, e0[f]) + _bm(Jf, dfeat) + _bm(Jsh, dsh) + amb
+        amb = amb2 @ np.abs(H2).T + _bm(J4 @ H1[None], amb1) + _bm(J2 @ W1[None, 1:1 + G], amb0)
+        dc2 = {f: e4[f] + _bm(J4, e3[f]) + _bm(J3, e2[f]) + _bm(J2, e1[f][:, 1:1 + G]) + _bm(J1, e0[f]) + _bm(Jf, dfeat) + _bm(Jsh, dsh) + amb
                for f in fams}
         o = t[:, 0]
         s = 0.5 * (1 + np.tanh(0.5 * c2))
@@ -372,11 +383,11 @@ def reference(nt, mode, P32, sel, shin, K, p, sites, keeps, rounded):
             res.b_dens[f][k] = res.dens[k] * (dt[f][:, 0] + (np.abs(o) + 1) * 2.0 ** -23 + 2 * U) + 2.0 ** -126
             res.b_rgb[f][k] = dc2[f] / 4 + s * (1 - s) * (np.abs(c2) + 1) * 2.0 ** -23 + 3 * U * s + 2.0 ** -126
         if mode == ACTIVE:
-            u = t[:, 16]
+            u = t[:, G + 1]
             sp = np.logaddexp(0.0, u)
             res.beta = sp + BETA_MIN
             sig = 0.5 * (1 + np.tanh(0.5 * u))
-            res.b_beta = {f: dt[f][:, 16] + sig * (np.abs(u) + 1) * 2.0 ** -23 + U + 3 * U * sp + U * res.beta + SOFTPLUS_JUMP for f in fams}
+            res.b_beta = {f: dt[f][:, G + 1] + sig * (np.abs(u) + 1) * 2.0 ** -23 + U + 3 * U * sp + U * res.beta + SOFTPLUS_JUMP for f in fams}
     return res
 
 

@@ -216,7 +216,7 @@ def carried_rgb(t, m, rows, f):
     it (field_cases.reference)"""
     A4 = rows[None] * t.live1[m][:, None, :]                      # c1 -> row
     A3 = A4 @ (t.H1[None] * t.live0[m][:, None, :])                # c0 -> row
-    Ag, As = A3 @ t.H0[:, 16:31], A3 @ t.H0[:, :16]                # geo, SH16 -> row
+    Ag, As = A3 @ t.H0[:, 16:], A3 @ t.H0[:, :16]                  # geo, SH16 -> row
     Ah = Ag @ t.W1                                                 # hb -> row
     Af = Ah @ t.W0                                                 # features -> row
     return (FC._bm(A4, t.e3[f][m]) + FC._bm(A3, t.e2[f][m]) + FC._bm(Ag, t.e1[f][m]) + FC._bm(As, t.dsh[m]) + FC._bm(Ah, t.e0[f][m])
@@ -227,6 +227,7 @@ def reference(c, rounded, set_shift=0):
     """-> SimpleNamespace(dens, var_d [N], rgb [N,3], var_rgb [N] float64, the UNSCALED bounds b_* {family: ...}, the logits
     pre_d [N,n], pre_c [N,nr,3]).  set_shift: every chunk evaluated with the set that many chunks earlier (set-distinctness)"""
     nt, N = c.net, c.N
+    H, HC = nt.w0.shape[0], nt.h1.shape[0]       # the inputs of the two sampled heads (64 / 64 here; tests/width_cases.py has others)
     t = trunk64(nt, c.P32, c.shin, rounded)
     hb, x, fams = t.hb, t.x, t.fams
     r = SimpleNamespace(dens=np.zeros(N), var_d=np.zeros(N), rgb=np.zeros((N, 3)), var_rgb=np.zeros(N), pre_d=np.zeros((N, c.n)),
@@ -236,7 +237,7 @@ def reference(c, rounded, set_shift=0):
         m = c.set_of == st
         use = max(int(st) - set_shift, 0)
         wd, wr = c.wsd[use], c.wsr[use][:c.nr]
-        p, dp = _head(hb[m], lambda rows, f: carried_density(t, m, rows, f), wd[:, :64], wd[:, 64], c.act, fams)
+        p, dp = _head(hb[m], lambda rows, f: carried_density(t, m, rows, f), wd[:, :H], wd[:, H], c.act, fams)
         with np.errstate(divide="ignore"):
             r.pre_d[m] = np.log(p) if c.act == "exp" else p
         for f in fams:
@@ -246,7 +247,7 @@ def reference(c, rounded, set_shift=0):
             r.dens[m], r.var_d[m], r.b_dens[f][m], r.b_var_d[f][m] = mu, var, dmu, dvar
         vsum, dvsum = {f: 0.0 for f in fams}, {f: 0.0 for f in fams}
         for ch in range(3):
-            p, dp = _head(x[m], lambda rows, f: carried_rgb(t, m, rows, f), wr[:, 64 * ch:64 * ch + 64], wr[:, 192 + ch], "sigmoid", fams)
+            p, dp = _head(x[m], lambda rows, f: carried_rgb(t, m, rows, f), wr[:, HC * ch:HC * ch + HC], wr[:, 3 * HC + ch], "sigmoid", fams)
             with np.errstate(divide="ignore"):
                 r.pre_c[m, :, ch] = np.log(p) - np.log1p(-p)
             for f in fams:
@@ -312,6 +313,7 @@ def chain(c, fam, mut=None):
     """The whole network of a case in the family's precision on the CPU ("fp32", "f16x2", "f16"), correctly rounded
     transcendentals.  mut: one of MUTATIONS.  -> {"dens", "var_d", "var_rgb" [N], "rgb" [N,3]} float32"""
     nt, N = c.net, c.N
+    H, HC = nt.w0.shape[0], nt.h1.shape[0]
     feat = PC._features32(nt, c.P32).astype(f32)
     sh = FC._sh16(c.shin).astype(f32)
     hb = FC._dense32(feat, nt.w0, nt.b0, fam)
@@ -329,7 +331,7 @@ def chain(c, fam, mut=None):
         m = set_of == st
         wd, wr = c.wsd[st], c.wsr[st]
         nr = c.n if mut == "rgb_cut_at_n_lap" else c.nr
-        mu, m2 = _head32(hb[m], wd[:, :64], wd[:, 64], c.act, fam, c.n, mut, "density")
+        mu, m2 = _head32(hb[m], wd[:, :H], wd[:, H], c.act, fam, c.n, mut, "density")
         if c.mask:
             masked = (mu * sel[m]).astype(f32)
             out["dens"][m] = mu if mut == "mask_unmasked_mean" else masked
@@ -338,7 +340,7 @@ def chain(c, fam, mut=None):
             out["dens"][m], out["var_d"][m] = mu, (m2 - (mu * mu).astype(f32)).astype(f32)
         vs = np.zeros(int(m.sum()), f32)
         for ch in range(3):
-            mu, m2 = _head32(x[m], wr[:nr, 64 * ch:64 * ch + 64], wr[:nr, 192 + ch], "sigmoid", fam, nr, mut, "rgb")
+            mu, m2 = _head32(x[m], wr[:nr, HC * ch:HC * ch + HC], wr[:nr, 3 * HC + ch], "sigmoid", fam, nr, mut, "rgb")
             out["rgb"][m, ch] = mu
             vs = (vs + np.maximum((m2 - (mu * mu).astype(f32)).astype(f32), f32(0))).astype(f32)
         out["var_rgb"][m] = (vs / f32(3)).astype(f32)

@@ -181,9 +181,11 @@ def _torch_rows(ix, iy, iz, log2T, level):
 
 
 def _features64(nt, P):
-    """P [N,3] float64 -> feat [N,2L], dfeat [N,2L] (the feature bound)"""
-    N = P.shape[0]
-    feat, dfeat = np.zeros((N, 2 * nt.L)), np.zeros((N, 2 * nt.L))
+    """P [N,3] float64 -> feat [N,F L], dfeat [N,F L] (the feature bound); F = nt.F features per row, 2 unless the net says
+    otherwise (torch layout only)"""
+    N, F = P.shape[0], getattr(nt, "F", 2)
+    assert F == 2 or nt.layout == "torch"
+    feat, dfeat = np.zeros((N, F * nt.L)), np.zeros((N, F * nt.L))
     if nt.layout == "tcnn16":
         feat[:] = O.tcnn_hash_encode_half(torch.from_numpy(P.astype(f32)), torch.from_numpy(nt.table), nt.levels).numpy()
         return feat, dfeat
@@ -220,8 +222,8 @@ def _features64(nt, P):
             coord = pos
         c = np.stack(c)                                            # [8,N,2]
         slope = np.abs(coord).sum(axis=1, keepdims=True) * (c.max(axis=0) - c.min(axis=0))
-        feat[:, 2 * l: 2 * l + 2] = val
-        dfeat[:, 2 * l: 2 * l + 2] = U * (LERP_UNITS[nt.layout] * np.abs(c).max(axis=0) + slope)
+        feat[:, F * l: F * l + F] = val
+        dfeat[:, F * l: F * l + F] = U * (LERP_UNITS[nt.layout] * np.abs(c).max(axis=0) + slope)
     return feat, dfeat
 
 
@@ -267,7 +269,9 @@ def _features32(nt, p, mut=None):
         if mut == "next_level_offset":
             levels = [lv[:2] + (levels[(i + 1) % nt.L][2],) + lv[3:] for i, lv in enumerate(levels)]
         return O.tcnn_hash_encode_half(torch.from_numpy(p), torch.from_numpy(nt.table), levels).numpy()
-    feat = np.zeros((N, 2 * nt.L), f32)
+    F = getattr(nt, "F", 2)              # features per row: 2 unless the net says otherwise (torch layout, hashed levels)
+    assert F == 2 or (nt.layout == "torch" and nt.n_dense == 0)
+    feat = np.zeros((N, F * nt.L), f32)
     for l in range(nt.L):
         lo = (l + 1) % nt.L if mut == "next_level_offset" else l
         if nt.layout == "torch":
@@ -307,7 +311,7 @@ def _features32(nt, p, mut=None):
                     (((cx & 0xFFFFFFFF) ^ ((cy * P1) & 0xFFFFFFFF) ^ ((cz * P2) & 0xFFFFFFFF)) % size)
                 wk = wxy[k & 3] * (w[:, 2] if k & 4 else m[:, 2])
                 val = _fma32(np.broadcast_to(wk[:, None], (N, 2)), nt.table[idx + offset], val)
-        feat[:, 2 * l: 2 * l + 2] = val
+        feat[:, F * l: F * l + F] = val
     return feat
 
 

@@ -419,7 +419,14 @@ class FieldDev:
             raise _l.UnerfError(f"FieldDev: inconsistent layer shapes (trunk {tuple(w0.shape)} -> {tuple(w1.shape)}, head "
                                 f"{tuple(h0.shape)} / {tuple(head_w[1].shape)} / {tuple(head_w[2].shape)}, appearance {AD}, grid {L} x {Fp})")
         headin = mode == _l.FIELD_MCDROPOUT and bool(int(kw.get("drop_sites", 0)) & _l.DROP_HEADIN)
-        generic = (H, HC, G, Fp, L) != (64, 64, 15, 2, 16) or (AD != 32 and headin)
+        # a 0 in unerf_field_params is "the default" (field_set_widths: 15 / 32), so these two cannot be told to the library
+        if G == 0:
+            raise _l.UnerfError("FieldDev: geo_feat_dim = 0 cannot be expressed (unerf_field_params.geo_dim = 0 means 15); "
+                                "the field kernels need at least one geo feature")
+        if AD == 0 and headin:
+            raise _l.UnerfError("FieldDev: appearance_embed_dim = 0 cannot be expressed under DROP_HEADIN (unerf_field_params.app_dim "
+                                "= 0 means 32, and the site's mask covers the appearance rows); drop the site or give an embedding")
+        generic =(H, HC, G, Fp, L) != (64, 64, 15, 2, 16) or (AD != 32 and headin)
         if generic:
             _warn_any_width(H, HC, G, Fp, L)
             kw.update(hidden=H, hidden_color=HC, geo_dim=G, feat_per_level=Fp, app_dim=AD)
