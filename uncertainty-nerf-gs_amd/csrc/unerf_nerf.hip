@@ -4001,6 +4001,199 @@ __device__ __forceinline__ void pg_blend_grad(const float (&v)[8], float wx, flo
     }
 }
 
+// ---- the stages every pose kernel of 5e runs (pose_grad, pose_jac, pose_grad_mc, pose_grad_laplace), each stated once.  The
+// bit equalities between those kernels (MC with K = 1 and full masks = pose_grad; the Jacobian's R/G/B values = pose_grad's
+// out_rgb) hold because they call the same statements. ----
+
+// These kernels sit at the register ceiling (256 VGPRs, spills in three of the four), and the spill counts follow the
+// SHAPE of a helper's signature, not only its statements: pg_ray_sample and pg_pose_row take the ray's values as scalars,
+// pointers and a struct by value, not the argument struct or PgSample / PgRaySums by reference: those forms moved the
+// spill counts of pose_grad_kernel, pose_jac_kernel and pose_grad_laplace_kernel (docs/experiments.md 8.6).
+
+// sample i of a ray (sb: its S + 1 bins, o / d: its origin and direction): bin width, twice the midpoint, world position
+// (x0, y0, z0), normalised position (px, py, pz) and selector
+struct PgSample {
+    float delta, t2;       // e1 - e0, e0 + e1
+    float dx, dy, dz;      // the ray's direction
+    float x0, y0, z0;
+    float px, py, pz, sel;
+};
+__device__ __forceinline__ PgSample pg_ray_sample(const float* sb, const float* o, const float* d, float s_near, float s_far, int lin,
+                                                 const unerf_norm_box& box, int i) {
+    PgSample s;
+    const float e0 = unerf_s2e(sb[i], s_near, s_far, lin), e1 = unerf_s2e(sb[i + 1], s_near, s_far, lin);
+    s.delta = e1 - e0, s.t2 = e0 + e1;
+    const float ox = o[0], oy = o[1], oz = o[2];
+    s.dx = d[0], s.dy = d[1], s.dz = d[2];
+    // (d t2) / 2, not d (t2 / 2): field_kernel's rounding
+    s.x0 = ox + s.dx * s.t2 / 2.f, s.y0 = oy + s.dy * s.t2 / 2.f, s.z0 = oz + s.dz * s.t2 / 2.f;
+    s.px = s.x0, s.py = s.y0, s.pz = s.z0;
+    s.sel = unerf_normalize_position(s.px, s.py, s.pz, box);
+    return s;
+}
+
+// grid forward: rows 2l, 2l+1 of the panel <- the two features of level l (field_kernel's arithmetic)
+template <int GRID, int UNROLL>
+__device__ __forceinline__ void pg_grid_fwd(const PoseGradArgs& a, uint32_t mask, const PgSample& s, float* A, int lane) {
+#pragma unroll UNROLL
+    for (int l = 0; l < 16; ++l) {
+        float2 f[8];
+        float wx, wy, wz, scale;
+        pg_level_corners<GRID>(a, l, mask, s.px, s.py, s.pz, f, wx, wy, wz, scale);
+        const float2 e = GRID == 0 ? unerf_blend8(f, wx, wy, wz) : unerf_tcnn_blend(f, wx, wy, wz);
+        A[(2 * l) * 64 + lane] = e.x;
+        A[(2 * l + 1) * 64 + lane] = e.y;
+    }
+}
+// grid backward: rows 2l, 2l+1 hold the adjoint of level l's features; the corner rows are fetched again and the exact
+// derivative of the trilinear blend x level scale is summed over the levels -> d / d(normalised position)
+template <int GRID, int UNROLL>
+__device__ __forceinline__ void pg_grid_bwd(const PoseGradArgs& a, uint32_t mask, const PgSample& s, const float* A, int lane,
+                                            float& gpx, float& gpy, float& gpz) {
+    gpx = gpy = gpz = 0.f;
+#pragma unroll UNROLL
+    for (int l = 0; l < 16; ++l) {
+        float2 f[8];
+        float wx, wy, wz, scale;
+        pg_level_corners<GRID>(a, l, mask, s.px, s.py, s.pz, f, wx, wy, wz, scale);
+        const float g0 = A[(2 * l) * 64 + lane], g1 = A[(2 * l + 1) * 64 + lane];
+        float v[8];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) v[k] = fmaf(g1, f[k].y, g0 * f[k].x);
+        float bx, by, bz;
+        pg_blend_grad<GRID>(v, wx, wy, wz, bx, by, bz);
+        gpx = fmaf(scale, bx, gpx);
+        gpy = fmaf(scale, by, gpy);
+        gpz = fmaf(scale, bz, gpz);
+    }
+}
+
+// SH inputs: (d + 1) / 2, mapped back to [-1, 1] by the tcnn encoding (sh_remap); du/dd = 1/2 or 1
+__device__ __forceinline__ void pg_sh_inputs(const PoseGradArgs& a, const PgSample& s, float& ux, float& uy, float& uz) {
+    ux = (s.dx + 1.f) / 2.f, uy = (s.dy + 1.f) / 2.f, uz = (s.dz + 1.f) / 2.f;
+    if (a.p.sh_remap) {
+        ux = ux * 2.f - 1.f;
+        uy = uy * 2.f - 1.f;
+        uz = uz * 2.f - 1.f;
+    }
+}
+// the SH term of d/dd: rows 0..15 of the panel hold the adjoint of the 16 SH outputs (unerf_sh16) at (ux, uy, uz)
+__device__ __forceinline__ void pg_sh16_grad(const float* A, int lane, float ux, float uy, float uz, int remap, float& gx, float& gy,
+                                             float& gz) {
+    float q[16];
+#pragma unroll
+    for (int j = 0; j < 16; ++j) q[j] = A[j * 64 + lane];
+    const float x = ux, y = uy, z = uz, xx = x * x, yy = y * y, zz = z * z;
+    const float c1 = 0.4886025119029199f, c2 = 1.0925484305920792f, c6 = 0.9461746957575601f, c8 = 0.5462742152960396f,
+                c9 = 0.5900435899266435f, c10 = 2.890611442640554f, c11 = 0.4570457994644658f, c12 = 0.3731763325901154f,
+                c14 = 1.445305721320277f;
+    const float z5 = 5.f * zz - 1.f, d3 = 3.f * (xx - yy);
+    gx = q[3] * c1 + q[4] * (c2 * y) + q[7] * (c2 * z) + q[8] * (2.f * c8 * x) + q[9] * (6.f * c9 * x * y) + q[10] * (c10 * y * z) +
+         q[13] * (c11 * z5) + q[14] * (2.f * c14 * x * z) + q[15] * (c9 * d3);
+    gy = q[1] * c1 + q[4] * (c2 * x) + q[5] * (c2 * z) - q[8] * (2.f * c8 * y) + q[9] * (c9 * d3) + q[10] * (c10 * x * z) +
+         q[11] * (c11 * z5) - q[14] * (2.f * c14 * y * z) - q[15] * (6.f * c9 * x * y);
+    gz = q[2] * c1 + q[5] * (c2 * y) + q[6] * (2.f * c6 * z) + q[7] * (c2 * x) + q[10] * (c10 * x * y) + q[11] * (10.f * c11 * y * z) +
+         q[12] * (c12 * (15.f * zz - 3.f)) + q[13] * (10.f * c11 * x * z) + q[14] * (c14 * (xx - yy));
+    const float du = remap ? 1.f : 0.5f;
+    gx *= du;
+    gy *= du;
+    gz *= du;
+}
+
+// sum_{j>i} x_j as a scan over the reversed wave, NOT total - prefix: behind an opaque sample every term of dsigma is
+// of the size of the transmittance there, and the rounding of a difference of O(1) sums (2^-24), multiplied by
+// delta sigma of a dense sample (1e3 and more), would be the whole error of the gradient
+__device__ __forceinline__ float pg_suffix_sum(float x, int lane) {
+    const int rl = 63 - lane;
+    return __shfl(group_excl_scan<64>(__shfl(x, rl, 64), lane), rl, 64);
+}
+// compositing of one ray (laplace_ggn_kernel's scans): alpha_i = 1 - em, transmittance T in front of sample i, weight w,
+// accumulation, transmittance Tf behind the ray and sw = sum_{j>i} w_j
+struct PgWeights {
+    float em, T, w, Asum, Tf, sw;
+};
+__device__ __forceinline__ PgWeights pg_transmittance(bool in, float delta, float sig, int lane) {
+    PgWeights c;
+    const float dd = in ? delta * sig : 0.f;
+    c.em = expf(-dd);
+    c.T = expf(-group_excl_scan<64>(dd, lane));
+    c.w = in ? unerf_nan_to_num((1.f - c.em) * c.T) : 0.f;
+    c.Asum = group_sum<64>(c.w);
+    c.Tf = 1.f - c.Asum;
+    c.sw = pg_suffix_sum(c.w, lane);
+    return c;
+}
+
+// d / d(normalised position) -> d / d(world position): the selector, then / box length, or / 4 and the transposed
+// Jacobian of SceneContraction(inf) at (x0, y0, z0)
+__device__ __forceinline__ void pg_world_grad(const unerf_norm_box& box, const PgSample& s, float gpx, float gpy, float gpz, float& gx,
+                                              float& gy, float& gz) {
+    const float x0 = s.x0, y0 = s.y0, z0 = s.z0;
+    gx = gpx * s.sel, gy = gpy * s.sel, gz = gpz * s.sel;
+    if (box.use_aabb) {   // uniform
+        gx /= box.len[0];
+        gy /= box.len[1];
+        gz /= box.len[2];
+    } else {
+        gx *= 0.25f;
+        gy *= 0.25f;
+        gz *= 0.25f;
+        const float ax = fabsf(x0), ay = fabsf(y0), az = fabsf(z0);
+        const float m = fmaxf(fmaxf(ax, ay), az);
+        if (!(m < 1.f)) {
+            // y = (2 - 1/m) x / m, m = |x_k|: dy_j/dx_j = (2 - 1/m)/m (j != k), dy_k/dx_k = 1/m^2,
+            // dy_j/dx_k = x_j sign(x_k) 2 (1 - m) / m^3
+            const float inv = 1.f / m, diag = (2.f - inv) * inv, cross = 2.f * (1.f - m) * inv * inv * inv;
+            const int k = (ax >= ay && ax >= az) ? 0 : (ay >= az ? 1 : 2);
+            const float dot = (k == 0 ? 0.f : gx * x0) + (k == 1 ? 0.f : gy * y0) + (k == 2 ? 0.f : gz * z0);
+            const float xk = k == 0 ? x0 : (k == 1 ? y0 : z0), gk = k == 0 ? gx : (k == 1 ? gy : gz);
+            const float along = gk * inv * inv + cross * (xk < 0.f ? -dot : dot);
+            gx = k == 0 ? along : gx * diag;
+            gy = k == 1 ? along : gy * diag;
+            gz = k == 2 ? along : gz * diag;
+        }
+    }
+}
+
+// the six sums over the ray, DPP reductions in a fixed order: g_o = sum_i dx_i, g_d = sum_i (t_i dx_i + the SH term),
+// t_i = t2 / 2 formed here, behind the backward pass
+struct PgRaySums {
+    float go0, go1, go2, gd0, gd1, gd2;
+};
+__device__ __forceinline__ PgRaySums pg_ray_sums(bool in, float t2, float gx, float gy, float gz, float gdx, float gdy, float gdz) {
+    if (!in) gx = gy = gz = gdx = gdy = gdz = 0.f;
+    const float th = t2 / 2.f;
+    PgRaySums s;
+    s.go0 = group_sum<64>(gx), s.go1 = group_sum<64>(gy), s.go2 = group_sum<64>(gz);
+    s.gd0 = group_sum<64>(fmaf(th, gx, gdx)), s.gd1 = group_sum<64>(fmaf(th, gy, gdy)), s.gd2 = group_sum<64>(fmaf(th, gz, gdz));
+    return s;
+}
+// lane j's entry of the ray's row: a.pose: the 12 entries of d/dc2w (row-major 3x4), else the 6 of (d/do, d/dd).  (dx, dy, dz):
+// the ray's direction
+__device__ __forceinline__ float pg_pose_row(const PoseGradArgs& a, int lane, float dx, float dy, float dz, PgRaySums g) {
+    if (a.pose) {
+        // d = normalize(R dir_cam): ds/dc2w[a][b] = P[a] (R^-1 d)[b] with P = (I - d d^T) g_d; ds/dc2w[:, 3] = g_o
+        const float gdd = g.gd0 * dx + g.gd1 * dy + g.gd2 * dz;
+        const float P[3] = {g.gd0 - dx * gdd, g.gd1 - dy * gdd, g.gd2 - dz * gdd};
+        const float go[3] = {g.go0, g.go1, g.go2};
+        const int row = lane >> 2, col = lane & 3;
+        const float Pa = row == 0 ? P[0] : (row == 1 ? P[1] : P[2]);
+        const float ga = row == 0 ? go[0] : (row == 1 ? go[1] : go[2]);
+        const int cb = col < 3 ? col : 0;
+        const float q = a.rinv[cb * 3 + 0] * dx + a.rinv[cb * 3 + 1] * dy + a.rinv[cb * 3 + 2] * dz;
+        return col == 3 ? ga : Pa * q;
+    }
+    return lane == 0 ? g.go0 : lane == 1 ? g.go1 : lane == 2 ? g.go2 : lane == 3 ? g.gd0 : lane == 4 ? g.gd1 : g.gd2;
+}
+// the store of that row by the three gradient kernels: a vector store of a lane-selected value
+__device__ __forceinline__ void pg_store_grad(const PoseGradArgs& a, int64_t r, int lane, float v) {
+    if (a.pose) {
+        if (lane < 12) a.out_grad[r * 12 + lane] = v;
+    } else {
+        if (lane < 6) a.out_grad[r * 6 + lane] = v;
+    }
+}
+
 template <int OUT1, int GRID>
 __global__ __launch_bounds__(256, 2) void pose_grad_kernel(PoseGradArgs a) {   // two waves per SIMD: two 64-KiB blocks per CU
     extern __shared__ float lds[];
@@ -4015,25 +4208,12 @@ __global__ __launch_bounds__(256, 2) void pose_grad_kernel(PoseGradArgs a) {   /
     const uint32_t mask = GRID == 0 ? (1u << a.p.log2T) - 1u : 0u;
     {
         // ---- sample position, normalisation ----
-        const float* sb = a.sbins + r * (S + 1);
-        const float e0 = unerf_s2e(sb[i], a.s_near, a.s_far, a.lin), e1 = unerf_s2e(sb[i + 1], a.s_near, a.s_far, a.lin);
-        const float delta = e1 - e0, t2 = e0 + e1;
-        const float ox = a.origins[r * 3 + 0], oy = a.origins[r * 3 + 1], oz = a.origins[r * 3 + 2];
-        const float dxr = a.dirs[r * 3 + 0], dyr = a.dirs[r * 3 + 1], dzr = a.dirs[r * 3 + 2];
-        const float x0 = ox + dxr * t2 / 2.f, y0 = oy + dyr * t2 / 2.f, z0 = oz + dzr * t2 / 2.f;
-        float px = x0, py = y0, pz = z0;
-        const float sel = unerf_normalize_position(px, py, pz, a.box);
+        const PgSample s = pg_ray_sample(a.sbins + r * (S + 1), a.origins + r * 3, a.dirs + r * 3, a.s_near, a.s_far, a.lin,
+                                         a.box, i);
+        const float delta = s.delta, sel = s.sel;
 
         // ---- forward: grid -> trunk -> head (field_kernel's arithmetic) ----
-#pragma unroll 2
-        for (int l = 0; l < 16; ++l) {
-            float2 f[8];
-            float wx, wy, wz, scale;
-            pg_level_corners<GRID>(a, l, mask, px, py, pz, f, wx, wy, wz, scale);
-            const float2 e = GRID == 0 ? unerf_blend8(f, wx, wy, wz) : unerf_tcnn_blend(f, wx, wy, wz);
-            A[(2 * l) * 64 + lane] = e.x;
-            A[(2 * l + 1) * 64 + lane] = e.y;
-        }
+        pg_grid_fwd<GRID, 2>(a, mask, s, A, lane);
         float acc[64];
         uint32_t m0[2], m1[2], m2[2];
         pg_dense<32, 64>(pg_const(a.p.w0t), pg_const(a.p.b0), A, lane, acc);
@@ -4042,13 +4222,8 @@ __global__ __launch_bounds__(256, 2) void pose_grad_kernel(PoseGradArgs a) {   /
         float o1[OUT1];
         pg_dense<64, OUT1>(pg_const(a.p.w1t), pg_const(a.p.b1), A, lane, o1);
         const float sig = a.p.average_init_density * expf(o1[0]) * sel;
-        // SH inputs: (d + 1) / 2, mapped back to [-1, 1] by the tcnn encoding (sh_remap); du/dd = 1/2 or 1
-        float ux = (dxr + 1.f) / 2.f, uy = (dyr + 1.f) / 2.f, uz = (dzr + 1.f) / 2.f;
-        if (a.p.sh_remap) {
-            ux = ux * 2.f - 1.f;
-            uy = uy * 2.f - 1.f;
-            uz = uz * 2.f - 1.f;
-        }
+        float ux, uy, uz;
+        pg_sh_inputs(a, s, ux, uy, uz);
         {
             float sh[16];
             unerf_sh16(ux, uy, uz, sh);
@@ -4068,23 +4243,15 @@ __global__ __launch_bounds__(256, 2) void pose_grad_kernel(PoseGradArgs a) {   /
         for (int k = 0; k < 3; ++k) c[k] = unerf_nan_to_num(unerf_sigmoid(c[k]));
 
         // ---- compositing and its adjoints (laplace_ggn_kernel's scans) ----
-        const float dd = in ? delta * sig : 0.f;
-        const float em = expf(-dd);
-        const float T = expf(-group_excl_scan<64>(dd, lane));
-        const float w = in ? unerf_nan_to_num((1.f - em) * T) : 0.f;
-        const float Tf = 1.f - group_sum<64>(w);
+        const PgWeights cw = pg_transmittance(in, delta, sig, lane);
+        const float em = cw.em, T = cw.T, w = cw.w, Tf = cw.Tf, sw = cw.sw;
         const bool last_bg = a.bg_mode == UNERF_BG_LAST_SAMPLE;
-        // sum_{j>i} x_j as a scan over the reversed wave, NOT total - prefix: behind an opaque sample every term of dsigma is
-        // of the size of the transmittance there, and the rounding of a difference of O(1) sums (2^-24), multiplied by
-        // delta sigma of a dense sample (1e3 and more), would be the whole error of the gradient
-        const int rl = 63 - lane;
-        const float sw = __shfl(group_excl_scan<64>(__shfl(w, rl, 64), lane), rl, 64);
         float dsig = 0.f, dc[3], pred[3];
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
             const float bg = last_bg ? __shfl(c[k], S - 1, 64) : a.bg[k];
             const float wc = w * c[k];
-            const float swc = __shfl(group_excl_scan<64>(__shfl(wc, rl, 64), lane), rl, 64);
+            const float swc = pg_suffix_sum(wc, lane);
             pred[k] = group_sum<64>(wc) + Tf * bg;
             const float live = (pred[k] >= 0.f && pred[k] <= 1.f && in) ? 1.f / 3.f : 0.f;
             // d pred / d(delta_i sigma_i) of pred = sum_j w_j c_j + bg (1 - sum_j w_j), w_i = (1 - em_i) T_i
@@ -4105,26 +4272,7 @@ __global__ __launch_bounds__(256, 2) void pose_grad_kernel(PoseGradArgs a) {   /
         load_masked64(A, lane, m1, d);
         pg_dense_bwd<31, 64>(pg_const(a.p.h0t), d, A, lane);   // rows 0..15: dSH, 16..30: dgeo
         float gdx, gdy, gdz;   // the SH term of ds/dd
-        {
-            float q[16];
-#pragma unroll
-            for (int j = 0; j < 16; ++j) q[j] = A[j * 64 + lane];
-            const float x = ux, y = uy, z = uz, xx = x * x, yy = y * y, zz = z * z;
-            const float c1 = 0.4886025119029199f, c2 = 1.0925484305920792f, c6 = 0.9461746957575601f, c8 = 0.5462742152960396f,
-                        c9 = 0.5900435899266435f, c10 = 2.890611442640554f, c11 = 0.4570457994644658f, c12 = 0.3731763325901154f,
-                        c14 = 1.445305721320277f;
-            const float z5 = 5.f * zz - 1.f, d3 = 3.f * (xx - yy);
-            gdx = q[3] * c1 + q[4] * (c2 * y) + q[7] * (c2 * z) + q[8] * (2.f * c8 * x) + q[9] * (6.f * c9 * x * y) + q[10] * (c10 * y * z) +
-                  q[13] * (c11 * z5) + q[14] * (2.f * c14 * x * z) + q[15] * (c9 * d3);
-            gdy = q[1] * c1 + q[4] * (c2 * x) + q[5] * (c2 * z) - q[8] * (2.f * c8 * y) + q[9] * (c9 * d3) + q[10] * (c10 * x * z) +
-                  q[11] * (c11 * z5) - q[14] * (2.f * c14 * y * z) - q[15] * (6.f * c9 * x * y);
-            gdz = q[2] * c1 + q[5] * (c2 * y) + q[6] * (2.f * c6 * z) + q[7] * (c2 * x) + q[10] * (c10 * x * y) + q[11] * (10.f * c11 * y * z) +
-                  q[12] * (c12 * (15.f * zz - 3.f)) + q[13] * (10.f * c11 * x * z) + q[14] * (c14 * (xx - yy));
-            const float du = a.p.sh_remap ? 1.f : 0.5f;
-            gdx *= du;
-            gdy *= du;
-            gdz *= du;
-        }
+        pg_sh16_grad(A, lane, ux, uy, uz, a.p.sh_remap, gdx, gdy, gdz);
         // ---- backward: trunk ----
         float d1[OUT1];
         d1[0] = dsig * sig;   // sigma = aid exp(pre) selector: dsigma/dpre = sigma (zero where the selector is)
@@ -4135,69 +4283,14 @@ __global__ __launch_bounds__(256, 2) void pose_grad_kernel(PoseGradArgs a) {   /
         load_masked64(A, lane, m0, d);
         pg_dense_bwd<32, 64>(pg_const(a.p.w0t), d, A, lane);   // rows 2l, 2l+1: adjoint of level l's features
 
-        // ---- backward: grid -> normalised position ----
-        float gpx = 0.f, gpy = 0.f, gpz = 0.f;
-#pragma unroll 2
-        for (int l = 0; l < 16; ++l) {
-            float2 f[8];
-            float wx, wy, wz, scale;
-            pg_level_corners<GRID>(a, l, mask, px, py, pz, f, wx, wy, wz, scale);
-            const float g0 = A[(2 * l) * 64 + lane], g1 = A[(2 * l + 1) * 64 + lane];
-            float v[8];
-#pragma unroll
-            for (int k = 0; k < 8; ++k) v[k] = fmaf(g1, f[k].y, g0 * f[k].x);
-            float bx, by, bz;
-            pg_blend_grad<GRID>(v, wx, wy, wz, bx, by, bz);
-            gpx = fmaf(scale, bx, gpx);
-            gpy = fmaf(scale, by, gpy);
-            gpz = fmaf(scale, bz, gpz);
-        }
-        // ---- normalised position -> world position ----
-        float gx = gpx * sel, gy = gpy * sel, gz = gpz * sel;
-        if (a.box.use_aabb) {   // uniform
-            gx /= a.box.len[0];
-            gy /= a.box.len[1];
-            gz /= a.box.len[2];
-        } else {
-            gx *= 0.25f;
-            gy *= 0.25f;
-            gz *= 0.25f;
-            const float ax = fabsf(x0), ay = fabsf(y0), az = fabsf(z0);
-            const float m = fmaxf(fmaxf(ax, ay), az);
-            if (!(m < 1.f)) {
-                // y = (2 - 1/m) x / m, m = |x_k|: dy_j/dx_j = (2 - 1/m)/m (j != k), dy_k/dx_k = 1/m^2,
-                // dy_j/dx_k = x_j sign(x_k) 2 (1 - m) / m^3
-                const float inv = 1.f / m, diag = (2.f - inv) * inv, cross = 2.f * (1.f - m) * inv * inv * inv;
-                const int k = (ax >= ay && ax >= az) ? 0 : (ay >= az ? 1 : 2);
-                const float dot = (k == 0 ? 0.f : gx * x0) + (k == 1 ? 0.f : gy * y0) + (k == 2 ? 0.f : gz * z0);
-                const float xk = k == 0 ? x0 : (k == 1 ? y0 : z0), gk = k == 0 ? gx : (k == 1 ? gy : gz);
-                const float along = gk * inv * inv + cross * (xk < 0.f ? -dot : dot);
-                gx = k == 0 ? along : gx * diag;
-                gy = k == 1 ? along : gy * diag;
-                gz = k == 2 ? along : gz * diag;
-            }
-        }
-        if (!in) gx = gy = gz = gdx = gdy = gdz = 0.f;
-        const float th = t2 / 2.f;
-        const float go0 = group_sum<64>(gx), go1 = group_sum<64>(gy), go2 = group_sum<64>(gz);
-        const float gd0 = group_sum<64>(fmaf(th, gx, gdx)), gd1 = group_sum<64>(fmaf(th, gy, gdy)), gd2 = group_sum<64>(fmaf(th, gz, gdz));
+        // ---- backward: grid -> normalised position -> world position, ray sums ----
+        float gpx, gpy, gpz, gx, gy, gz;
+        pg_grid_bwd<GRID, 2>(a, mask, s, A, lane, gpx, gpy, gpz);
+        pg_world_grad(a.box, s, gpx, gpy, gpz, gx, gy, gz);
+        const PgRaySums sums = pg_ray_sums(in, s.t2, gx, gy, gz, gdx, gdy, gdz);
 
         // ---- epilogue: every store is a vector store of a lane-selected value ----
-        if (a.pose) {
-            // d = normalize(R dir_cam): ds/dc2w[a][b] = P[a] (R^-1 d)[b] with P = (I - d d^T) g_d; ds/dc2w[:, 3] = g_o
-            const float gdd = gd0 * dxr + gd1 * dyr + gd2 * dzr;
-            const float P[3] = {gd0 - dxr * gdd, gd1 - dyr * gdd, gd2 - dzr * gdd};
-            const float go[3] = {go0, go1, go2};
-            const int row = lane >> 2, col = lane & 3;
-            const float Pa = row == 0 ? P[0] : (row == 1 ? P[1] : P[2]);
-            const float ga = row == 0 ? go[0] : (row == 1 ? go[1] : go[2]);
-            const int cb = col < 3 ? col : 0;
-            const float q = a.rinv[cb * 3 + 0] * dxr + a.rinv[cb * 3 + 1] * dyr + a.rinv[cb * 3 + 2] * dzr;
-            if (lane < 12) a.out_grad[r * 12 + lane] = col == 3 ? ga : Pa * q;
-        } else {
-            const float v6 = lane == 0 ? go0 : lane == 1 ? go1 : lane == 2 ? go2 : lane == 3 ? gd0 : lane == 4 ? gd1 : gd2;
-            if (lane < 6) a.out_grad[r * 6 + lane] = v6;
-        }
+        pg_store_grad(a, r, lane, pg_pose_row(a, lane, s.dx, s.dy, s.dz, sums));
         if (a.out_rgb && lane < 3) {
             const float pv = lane == 0 ? pred[0] : (lane == 1 ? pred[1] : pred[2]);
             a.out_rgb[r * 3 + lane] = fminf(fmaxf(pv, 0.f), 1.f);
@@ -4205,42 +4298,80 @@ __global__ __launch_bounds__(256, 2) void pose_grad_kernel(PoseGradArgs a) {   /
     }
 }
 
-extern "C" int unerf_pose_grad(const float* origins, const float* directions, const float* sbins, int64_t R, int S,
-                               float near_plane, float far_plane, int spacing, const unerf_field_params* p, int background,
-                               const float* background_rgb, const float* rot_inv, float* out_grad, float* out_rgb,
-                               void* stream) {
-    UNERF_REQUIRE(R >= 0 && S >= 1 && S <= 64, "pose_grad: S=%d outside [1,64]", S);
-    if (R == 0) return UNERF_OK;
-    UNERF_REQUIRE(origins && directions && sbins && p && out_grad, "pose_grad: null pointer");
-    UNERF_REQUIRE(p->mode == UNERF_FIELD_ACTIVE || p->mode == UNERF_FIELD_MCDROPOUT,
-                  "pose_grad: mode %d (a nerfacto / active-nerfacto field is needed: the Laplace field's sampled heads are "
-                  "not differentiated)", p->mode);
-    UNERF_REQUIRE(p->hidden == 0 && p->hidden_color == 0 && p->geo_dim == 0 && p->feat_per_level == 0 && p->L == 16,
-                  "pose_grad: nerfacto's widths only (hidden 64 / 64, geo 15, 2 features x 16 levels)");
-    UNERF_REQUIRE(p->out1 == (p->mode == UNERF_FIELD_ACTIVE ? 17 : 16), "pose_grad: trunk output %d does not fit mode %d", p->out1,
-                  p->mode);
-    UNERF_REQUIRE(p->table && p->w0t && p->b0 && p->w1t && p->b1 && p->h0t && p->hb0 && p->h1t && p->hb1 && p->h2t && p->hb2 &&
-                      (p->scalings || p->tcnn_levels),
-                  "pose_grad: null field pointer");
-    UNERF_REQUIRE(p->tcnn_levels || (p->log2T >= 1 && p->log2T <= 24), "pose_grad: bad log2T=%d", p->log2T);
-    UNERF_REQUIRE(p->tcnn_levels || !p->grid_half, "pose_grad: grid_half needs a tcnn-layout grid");
-    UNERF_REQUIRE(near_plane >= 0.f, "pose_grad: near_plane=%g (spacing-domain bins only)", (double)near_plane);
-    PoseGradArgs g;
+// ---- host side of 5e: what the four entry points check, fill and launch alike, stated once; `what` is the entry point's
+// name in front of every text.  The checks come in pieces because each entry point has checks of its own between them, and
+// the first error a call reports stays the one it was: S; (pose_jacobian: channels, projection, outputs;) nothing more for
+// R == 0 -- an empty batch has no pointers to give --; the pointers; the field's mode (it reads *p); the field. ----
+static int pose_check_samples(const char* what, int64_t R, int S) {
+    UNERF_REQUIRE(R >= 0 && S >= 1 && S <= 64, "%s: S=%d outside [1,64]", what, S);
+    return UNERF_OK;
+}
+// have_out: the entry point's output pointer is there
+static int pose_check_pointers(const char* what, const float* origins, const float* directions, const float* sbins,
+                               const unerf_field_params* p, bool have_out) {
+    UNERF_REQUIRE(origins && directions && sbins && p && have_out, "%s: null pointer", what);
+    return UNERF_OK;
+}
+// The field behind them.  out1: the trunk outputs the (checked) mode has.  sampled_heads: the Laplace field, whose trunk
+// has the 15 geo outputs only, which its widths text says, and whose last layers are the rows ws_density / ws_rgb in place
+// of h2t / hb2.  scope: what the entry point adds to the widths text.
+static int pose_check_field(const char* what, const unerf_field_params* p, float near_plane, int out1, bool sampled_heads,
+                            const char* scope) {
+    UNERF_REQUIRE(p->hidden == 0 && p->hidden_color == 0 && p->geo_dim == 0 && p->feat_per_level == 0 && p->L == 16 &&
+                      (!sampled_heads || p->out1 == out1),
+                  "%s: nerfacto's widths only (hidden 64 / 64, geo 15%s, 2 features x 16 levels)%s", what,
+                  sampled_heads ? " = trunk output 15" : "", scope);
+    UNERF_REQUIRE(p->out1 == out1, "%s: trunk output %d does not fit mode %d", what, p->out1, p->mode);
+    UNERF_REQUIRE(p->table && p->w0t && p->b0 && p->w1t && p->b1 && p->h0t && p->hb0 && p->h1t && p->hb1 &&
+                      (sampled_heads || (p->h2t && p->hb2)) && (p->scalings || p->tcnn_levels),
+                  "%s: null field pointer", what);
+    UNERF_REQUIRE(!sampled_heads || (p->ws_density && p->ws_rgb),
+                  "%s: null ws_density / ws_rgb (the sampled last layers of the named draw)", what);
+    UNERF_REQUIRE(p->tcnn_levels || (p->log2T >= 1 && p->log2T <= 24), "%s: bad log2T=%d", what, p->log2T);
+    UNERF_REQUIRE(p->tcnn_levels || !p->grid_half, "%s: grid_half needs a tcnn-layout grid", what);
+    UNERF_REQUIRE(near_plane >= 0.f, "%s: near_plane=%g (spacing-domain bins only)", what, (double)near_plane);
+    return UNERF_OK;
+}
+// PoseGradArgs of a checked call.  max_rays: what one launch of the entry point's grid takes.
+static int pose_fill_args(PoseGradArgs& g, const char* what, const float* origins, const float* directions, const float* sbins,
+                          int64_t R, int S, float near_plane, float far_plane, int spacing, const unerf_field_params* p,
+                          int background, const float* background_rgb, const float* rot_inv, float* out_grad, float* out_rgb,
+                          int64_t max_rays) {
     g.origins = origins; g.dirs = directions; g.sbins = sbins; g.R = R; g.S = S;
     if (int rc = set_spacing(g, near_plane, far_plane, spacing)) return rc;
     g.p = *p;
     g.box = make_norm_box(p->use_aabb, p->aabb);
-    if (int rc = unerf_set_background(g, background, background_rgb, "pose_grad")) return rc;
+    if (int rc = unerf_set_background(g, background, background_rgb, what)) return rc;
     g.pose = rot_inv ? 1 : 0;
     for (int k = 0; k < 9; ++k) g.rinv[k] = rot_inv ? rot_inv[k] : 0.f;
     g.out_grad = out_grad; g.out_rgb = out_rgb;
-    UNERF_REQUIRE(R < (1ll << 32), "pose_grad: R=%lld rays in one launch, split the batch", (long long)R);
-    const int64_t blocks = (R + 3) / 4;   // a wave per ray; 64 KiB of LDS per block: two blocks per CU
-    constexpr size_t lds_bytes = 4 * 64 * 64 * sizeof(float);
+    UNERF_REQUIRE(R < max_rays, "%s: R=%lld rays in one launch, split the batch", what, (long long)R);
+    return UNERF_OK;
+}
+// pose_grad_kernel's geometry, which pose_jac_kernel and pose_grad_laplace_kernel keep: a wave per ray, four rays per
+// 256-thread block, whose four 16-KiB panels are 64 KiB of LDS: two blocks per CU
+template <typename Kern, typename... Args>
+static void pose_launch_rays4(Kern kernel, int64_t R, void* stream, Args... args) {
+    hipLaunchKernelGGL(kernel, dim3((unsigned)((R + 3) / 4)), dim3(256), 4 * 64 * 64 * sizeof(float), (hipStream_t)stream, args...);
+}
+
+extern "C" int unerf_pose_grad(const float* origins, const float* directions, const float* sbins, int64_t R, int S,
+                               float near_plane, float far_plane, int spacing, const unerf_field_params* p, int background,
+                               const float* background_rgb, const float* rot_inv, float* out_grad, float* out_rgb,
+                               void* stream) {
+    if (int rc = pose_check_samples("pose_grad", R, S)) return rc;
+    if (R == 0) return UNERF_OK;
+    if (int rc = pose_check_pointers("pose_grad", origins, directions, sbins, p, out_grad != nullptr)) return rc;
+    UNERF_REQUIRE(p->mode == UNERF_FIELD_ACTIVE || p->mode == UNERF_FIELD_MCDROPOUT,
+                  "pose_grad: mode %d (a nerfacto / active-nerfacto field is needed: the Laplace field's sampled heads are "
+                  "not differentiated)", p->mode);
+    if (int rc = pose_check_field("pose_grad", p, near_plane, p->mode == UNERF_FIELD_ACTIVE ? 17 : 16, false, "")) return rc;
+    PoseGradArgs g;
+    if (int rc = pose_fill_args(g, "pose_grad", origins, directions, sbins, R, S, near_plane, far_plane, spacing, p, background,
+                                background_rgb, rot_inv, out_grad, out_rgb, 1ll << 32)) return rc;
     with_int3(tcnn_arg(g.p), [&](auto tc) {
         with_bool(g.p.out1 == 17, [&](auto wide) {
-            hipLaunchKernelGGL((pose_grad_kernel<decltype(wide)::value ? 17 : 16, decltype(tc)::value>), dim3((unsigned)blocks), dim3(256),
-                               lds_bytes, (hipStream_t)stream, g);
+            pose_launch_rays4(pose_grad_kernel<decltype(wide)::value ? 17 : 16, decltype(tc)::value>, R, stream, g);
         });
     });
     return unerf_check_launch("pose_grad");
@@ -4286,34 +4417,15 @@ __global__ __launch_bounds__(256, 2) void pose_jac_kernel(PoseJacArgs ja) {
     const bool in = lane < S;
     const int i = in ? lane : S - 1;
     const uint32_t mask = GRID == 0 ? (1u << a.p.log2T) - 1u : 0u;
-    // ---- sample position, normalisation (pose_grad_kernel's statements down to the compositing) ----
-    const float* sb = a.sbins + r * (S + 1);
-    const float e0 = unerf_s2e(sb[i], a.s_near, a.s_far, a.lin), e1 = unerf_s2e(sb[i + 1], a.s_near, a.s_far, a.lin);
-    const float delta = e1 - e0, t2 = e0 + e1;
-    const float ox = a.origins[r * 3 + 0], oy = a.origins[r * 3 + 1], oz = a.origins[r * 3 + 2];
-    const float dxr = a.dirs[r * 3 + 0], dyr = a.dirs[r * 3 + 1], dzr = a.dirs[r * 3 + 2];
-    const float x0 = ox + dxr * t2 / 2.f, y0 = oy + dyr * t2 / 2.f, z0 = oz + dzr * t2 / 2.f;
-    float px = x0, py = y0, pz = z0;
-    const float sel = unerf_normalize_position(px, py, pz, a.box);
-
-    // ---- forward: grid -> trunk -> head ----
-#pragma unroll 2
-    for (int l = 0; l < 16; ++l) {
-        float2 f[8];
-        float wx, wy, wz, scale;
-        pg_level_corners<GRID>(a, l, mask, px, py, pz, f, wx, wy, wz, scale);
-        const float2 e = GRID == 0 ? unerf_blend8(f, wx, wy, wz) : unerf_tcnn_blend(f, wx, wy, wz);
-        A[(2 * l) * 64 + lane] = e.x;
-        A[(2 * l + 1) * 64 + lane] = e.y;
-    }
+    // ---- sample position, normalisation; forward: grid -> trunk -> head (pose_grad_kernel's, down to the compositing) ----
+    const PgSample s = pg_ray_sample(a.sbins + r * (S + 1), a.origins + r * 3, a.dirs + r * 3, a.s_near, a.s_far, a.lin,
+                                     a.box, i);
+    const float delta = s.delta, sel = s.sel;
+    pg_grid_fwd<GRID, 2>(a, mask, s, A, lane);
     uint32_t m0[2], m1[2], m2[2];
     float sig, c[3];
-    float ux = (dxr + 1.f) / 2.f, uy = (dyr + 1.f) / 2.f, uz = (dzr + 1.f) / 2.f;
-    if (a.p.sh_remap) {
-        ux = ux * 2.f - 1.f;
-        uy = uy * 2.f - 1.f;
-        uz = uz * 2.f - 1.f;
-    }
+    float ux, uy, uz;
+    pg_sh_inputs(a, s, ux, uy, uz);
     {
         float acc[64];
         pg_dense<32, 64>(pg_const(a.p.w0t), pg_const(a.p.b0), A, lane, acc);
@@ -4341,29 +4453,22 @@ __global__ __launch_bounds__(256, 2) void pose_jac_kernel(PoseJacArgs ja) {
     }
 
     // ---- compositing, once: the weights, the scans and every channel's value ----
-    const float dd = in ? delta * sig : 0.f;
-    const float em = expf(-dd);
-    const float T = expf(-group_excl_scan<64>(dd, lane));
-    const float w = in ? unerf_nan_to_num((1.f - em) * T) : 0.f;
-    const float Asum = group_sum<64>(w);
-    const float Tf = 1.f - Asum;
+    const PgWeights cw = pg_transmittance(in, delta, sig, lane);
+    const float em = cw.em, T = cw.T, w = cw.w, Asum = cw.Asum, Tf = cw.Tf, sw = cw.sw;
     const bool last_bg = a.bg_mode == UNERF_BG_LAST_SAMPLE;
-    const int rl = 63 - lane;
-    const float sw = __shfl(group_excl_scan<64>(__shfl(w, rl, 64), lane), rl, 64);   // sum_{j>i} w_j (pose_grad_kernel: why a scan)
     float bg[3], swc[3], pred[3];
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
         bg[k] = last_bg ? __shfl(c[k], S - 1, 64) : a.bg[k];
         const float wc = w * c[k];
-        swc[k] = __shfl(group_excl_scan<64>(__shfl(wc, rl, 64), lane), rl, 64);
+        swc[k] = pg_suffix_sum(wc, lane);
         pred[k] = group_sum<64>(wc) + Tf * bg[k];
     }
-    const float th = t2 / 2.f;
+    const float th = s.t2 / 2.f;
     const float Tend = __shfl(em * T, S - 1, 64);              // the transmittance behind the last sample
     const float inv_a = 1.f / (Asum + 1e-10f);
     const float edep = group_sum<64>(w * th) * inv_a;          // unclipped expected depth
-    const float wu = w * (th - edep);
-    const float swu = __shfl(group_excl_scan<64>(__shfl(wu, rl, 64), lane), rl, 64);   // sum_{j>i} w_j (t_j - e)
+    const float swu = pg_suffix_sum(w * (th - edep), lane);    // sum_{j>i} w_j (t_j - e)
 
     const int D = a.pose ? 12 : 6;
     int row = 0;
@@ -4395,26 +4500,7 @@ __global__ __launch_bounds__(256, 2) void pose_jac_kernel(PoseJacArgs ja) {
             pg_dense_bwd<64, 64>(pg_const(a.p.h1t), d, A, lane);
             load_masked64(A, lane, m1, d);
             pg_dense_bwd<31, 64>(pg_const(a.p.h0t), d, A, lane);   // rows 0..15: dSH, 16..30: dgeo
-            {
-                float q[16];
-#pragma unroll
-                for (int j = 0; j < 16; ++j) q[j] = A[j * 64 + lane];
-                const float x = ux, y = uy, z = uz, xx = x * x, yy = y * y, zz = z * z;
-                const float c1 = 0.4886025119029199f, c2 = 1.0925484305920792f, c6 = 0.9461746957575601f, c8 = 0.5462742152960396f,
-                            c9 = 0.5900435899266435f, c10 = 2.890611442640554f, c11 = 0.4570457994644658f, c12 = 0.3731763325901154f,
-                            c14 = 1.445305721320277f;
-                const float z5 = 5.f * zz - 1.f, d3 = 3.f * (xx - yy);
-                gdx = q[3] * c1 + q[4] * (c2 * y) + q[7] * (c2 * z) + q[8] * (2.f * c8 * x) + q[9] * (6.f * c9 * x * y) + q[10] * (c10 * y * z) +
-                      q[13] * (c11 * z5) + q[14] * (2.f * c14 * x * z) + q[15] * (c9 * d3);
-                gdy = q[1] * c1 + q[4] * (c2 * x) + q[5] * (c2 * z) - q[8] * (2.f * c8 * y) + q[9] * (c9 * d3) + q[10] * (c10 * x * z) +
-                      q[11] * (c11 * z5) - q[14] * (2.f * c14 * y * z) - q[15] * (6.f * c9 * x * y);
-                gdz = q[2] * c1 + q[5] * (c2 * y) + q[6] * (2.f * c6 * z) + q[7] * (c2 * x) + q[10] * (c10 * x * y) + q[11] * (10.f * c11 * y * z) +
-                      q[12] * (c12 * (15.f * zz - 3.f)) + q[13] * (10.f * c11 * x * z) + q[14] * (c14 * (xx - yy));
-                const float du = a.p.sh_remap ? 1.f : 0.5f;
-                gdx *= du;
-                gdy *= du;
-                gdz *= du;
-            }
+            pg_sh16_grad(A, lane, ux, uy, uz, a.p.sh_remap, gdx, gdy, gdz);
 #pragma unroll
             for (int g = 0; g < 15; ++g) d1[1 + g] = A[(16 + g) * 64 + lane];
         } else if (ch == 3) {
@@ -4430,65 +4516,14 @@ __global__ __launch_bounds__(256, 2) void pose_jac_kernel(PoseJacArgs ja) {
         load_masked64(A, lane, m0, d);
         pg_dense_bwd<32, 64>(pg_const(a.p.w0t), d, A, lane);
 
-        // ---- backward: grid -> normalised position (the corner rows are fetched again) ----
-        float gpx = 0.f, gpy = 0.f, gpz = 0.f;
-#pragma unroll 2
-        for (int l = 0; l < 16; ++l) {
-            float2 f[8];
-            float wx, wy, wz, scale;
-            pg_level_corners<GRID>(a, l, mask, px, py, pz, f, wx, wy, wz, scale);
-            const float g0 = A[(2 * l) * 64 + lane], g1 = A[(2 * l + 1) * 64 + lane];
-            float v[8];
-#pragma unroll
-            for (int k = 0; k < 8; ++k) v[k] = fmaf(g1, f[k].y, g0 * f[k].x);
-            float bx, by, bz;
-            pg_blend_grad<GRID>(v, wx, wy, wz, bx, by, bz);
-            gpx = fmaf(scale, bx, gpx);
-            gpy = fmaf(scale, by, gpy);
-            gpz = fmaf(scale, bz, gpz);
-        }
-        // ---- normalised position -> world position (pose_grad_kernel's statements) ----
-        float gx = gpx * sel, gy = gpy * sel, gz = gpz * sel;
-        if (a.box.use_aabb) {   // uniform
-            gx /= a.box.len[0];
-            gy /= a.box.len[1];
-            gz /= a.box.len[2];
-        } else {
-            gx *= 0.25f;
-            gy *= 0.25f;
-            gz *= 0.25f;
-            const float ax = fabsf(x0), ay = fabsf(y0), az = fabsf(z0);
-            const float m = fmaxf(fmaxf(ax, ay), az);
-            if (!(m < 1.f)) {
-                const float inv = 1.f / m, diag = (2.f - inv) * inv, cross = 2.f * (1.f - m) * inv * inv * inv;
-                const int k = (ax >= ay && ax >= az) ? 0 : (ay >= az ? 1 : 2);
-                const float dot = (k == 0 ? 0.f : gx * x0) + (k == 1 ? 0.f : gy * y0) + (k == 2 ? 0.f : gz * z0);
-                const float xk = k == 0 ? x0 : (k == 1 ? y0 : z0), gk = k == 0 ? gx : (k == 1 ? gy : gz);
-                const float along = gk * inv * inv + cross * (xk < 0.f ? -dot : dot);
-                gx = k == 0 ? along : gx * diag;
-                gy = k == 1 ? along : gy * diag;
-                gz = k == 2 ? along : gz * diag;
-            }
-        }
-        if (!in) gx = gy = gz = gdx = gdy = gdz = 0.f;
-        const float go0 = group_sum<64>(gx), go1 = group_sum<64>(gy), go2 = group_sum<64>(gz);
-        const float gd0 = group_sum<64>(fmaf(th, gx, gdx)), gd1 = group_sum<64>(fmaf(th, gy, gdy)), gd2 = group_sum<64>(fmaf(th, gz, gdz));
+        // ---- backward: grid -> normalised position -> world position, ray sums ----
+        float gpx, gpy, gpz, gx, gy, gz;
+        pg_grid_bwd<GRID, 2>(a, mask, s, A, lane, gpx, gpy, gpz);
+        pg_world_grad(a.box, s, gpx, gpy, gpz, gx, gy, gz);
+        const PgRaySums sums = pg_ray_sums(in, s.t2, gx, gy, gz, gdx, gdy, gdz);
 
         // ---- epilogue: lane j holds entry j of the row; every store is a vector store of a lane-selected value ----
-        float jv;
-        if (a.pose) {
-            const float gdd = gd0 * dxr + gd1 * dyr + gd2 * dzr;
-            const float P[3] = {gd0 - dxr * gdd, gd1 - dyr * gdd, gd2 - dzr * gdd};
-            const float go[3] = {go0, go1, go2};
-            const int rw = lane >> 2, col = lane & 3;
-            const float Pa = rw == 0 ? P[0] : (rw == 1 ? P[1] : P[2]);
-            const float ga = rw == 0 ? go[0] : (rw == 1 ? go[1] : go[2]);
-            const int cb = col < 3 ? col : 0;
-            const float q = a.rinv[cb * 3 + 0] * dxr + a.rinv[cb * 3 + 1] * dyr + a.rinv[cb * 3 + 2] * dzr;
-            jv = col == 3 ? ga : Pa * q;
-        } else {
-            jv = lane == 0 ? go0 : lane == 1 ? go1 : lane == 2 ? go2 : lane == 3 ? gd0 : lane == 4 ? gd1 : gd2;
-        }
+        const float jv = pg_pose_row(a, lane, s.dx, s.dy, s.dz, sums);
         if (ja.out_jac && lane < D) ja.out_jac[rc * D + lane] = jv;
         if (ja.out_val && lane == 0) ja.out_val[rc] = val;
         if (ja.P > 0 && (ja.out_proj || ja.out_var)) {   // uniform
@@ -4514,50 +4549,31 @@ extern "C" int unerf_pose_jacobian(const float* origins, const float* directions
                                    const float* background_rgb, const float* rot_inv, int channels, const float* proj, int P,
                                    float* out_jac, float* out_proj, float* out_var, float* out_val, void* stream) {
     constexpr int CH_KNOWN = UNERF_POSE_CH_R | UNERF_POSE_CH_G | UNERF_POSE_CH_B | UNERF_POSE_CH_ACC | UNERF_POSE_CH_EDEPTH;
-    UNERF_REQUIRE(R >= 0 && S >= 1 && S <= 64, "pose_jacobian: S=%d outside [1,64]", S);
+    if (int rc = pose_check_samples("pose_jacobian", R, S)) return rc;
     UNERF_REQUIRE(channels != 0, "pose_jacobian: channels is empty (a non-empty subset of UNERF_POSE_CH_*)");
     UNERF_REQUIRE((channels & ~CH_KNOWN) == 0, "pose_jacobian: unknown bits in channels=%d", channels);
     UNERF_REQUIRE(!proj || (P >= 1 && P <= 12), "pose_jacobian: P=%d outside [1,12]", P);
     UNERF_REQUIRE(proj || (!out_proj && !out_var), "pose_jacobian: out_proj / out_var need proj");
     UNERF_REQUIRE(out_jac || out_proj || out_var || out_val, "pose_jacobian: no output requested (out_jac, out_proj, out_var and out_val are all NULL)");
     if (R == 0) return UNERF_OK;
-    UNERF_REQUIRE(origins && directions && sbins && p, "pose_jacobian: null pointer");
+    if (int rc = pose_check_pointers("pose_jacobian", origins, directions, sbins, p, true)) return rc;
     UNERF_REQUIRE(p->mode == UNERF_FIELD_ACTIVE || p->mode == UNERF_FIELD_MCDROPOUT,
                   "pose_jacobian: mode %d (a nerfacto / active-nerfacto field is needed: the Laplace field's sampled heads are "
                   "not differentiated)", p->mode);
-    UNERF_REQUIRE(p->hidden == 0 && p->hidden_color == 0 && p->geo_dim == 0 && p->feat_per_level == 0 && p->L == 16,
-                  "pose_jacobian: nerfacto's widths only (hidden 64 / 64, geo 15, 2 features x 16 levels)");
-    UNERF_REQUIRE(p->out1 == (p->mode == UNERF_FIELD_ACTIVE ? 17 : 16), "pose_jacobian: trunk output %d does not fit mode %d", p->out1,
-                  p->mode);
-    UNERF_REQUIRE(p->table && p->w0t && p->b0 && p->w1t && p->b1 && p->h0t && p->hb0 && p->h1t && p->hb1 && p->h2t && p->hb2 &&
-                      (p->scalings || p->tcnn_levels),
-                  "pose_jacobian: null field pointer");
-    UNERF_REQUIRE(p->tcnn_levels || (p->log2T >= 1 && p->log2T <= 24), "pose_jacobian: bad log2T=%d", p->log2T);
-    UNERF_REQUIRE(p->tcnn_levels || !p->grid_half, "pose_jacobian: grid_half needs a tcnn-layout grid");
-    UNERF_REQUIRE(near_plane >= 0.f, "pose_jacobian: near_plane=%g (spacing-domain bins only)", (double)near_plane);
+    if (int rc = pose_check_field("pose_jacobian", p, near_plane, p->mode == UNERF_FIELD_ACTIVE ? 17 : 16, false, "")) return rc;
     PoseJacArgs j;
-    PoseGradArgs& g = j.g;
-    g.origins = origins; g.dirs = directions; g.sbins = sbins; g.R = R; g.S = S;
-    if (int rc = set_spacing(g, near_plane, far_plane, spacing)) return rc;
-    g.p = *p;
-    g.box = make_norm_box(p->use_aabb, p->aabb);
-    if (int rc = unerf_set_background(g, background, background_rgb, "pose_jacobian")) return rc;
-    g.pose = rot_inv ? 1 : 0;
-    for (int k = 0; k < 9; ++k) g.rinv[k] = rot_inv ? rot_inv[k] : 0.f;
-    g.out_grad = nullptr; g.out_rgb = nullptr;
+    PoseGradArgs& g = j.g;   // out_grad / out_rgb are not read
+    if (int rc = pose_fill_args(g, "pose_jacobian", origins, directions, sbins, R, S, near_plane, far_plane, spacing, p, background,
+                                background_rgb, rot_inv, nullptr, nullptr, 1ll << 32)) return rc;
     j.channels = channels;
     j.C = __builtin_popcount((unsigned)channels);
     j.P = proj ? P : 0;
     const int D = rot_inv ? 12 : 6;
     for (int k = 0; k < 144; ++k) j.proj[k] = (proj && k < D * P) ? proj[k] : 0.f;
     j.out_jac = out_jac; j.out_proj = out_proj; j.out_var = out_var; j.out_val = out_val;
-    UNERF_REQUIRE(R < (1ll << 32), "pose_jacobian: R=%lld rays in one launch, split the batch", (long long)R);
-    const int64_t blocks = (R + 3) / 4;   // pose_grad_kernel's geometry
-    constexpr size_t lds_bytes = 4 * 64 * 64 * sizeof(float);
     with_int3(tcnn_arg(g.p), [&](auto tc) {
         with_bool(g.p.out1 == 17, [&](auto wide) {
-            hipLaunchKernelGGL((pose_jac_kernel<decltype(wide)::value ? 17 : 16, decltype(tc)::value>), dim3((unsigned)blocks), dim3(256),
-                               lds_bytes, (hipStream_t)stream, j);
+            pose_launch_rays4(pose_jac_kernel<decltype(wide)::value ? 17 : 16, decltype(tc)::value>, R, stream, j);
         });
     });
     return unerf_check_launch("pose_jacobian");
@@ -4641,25 +4657,13 @@ __global__ __launch_bounds__(64) void pose_grad_mc_kernel(PoseGradArgs a, PoseGr
     const uint32_t mask = GRID == 0 ? (1u << a.p.log2T) - 1u : 0u;
     const int64_t n = r * S + i;   // this lane's sample in the launch
     // ---- sample position, normalisation ----
-    const float* sb = a.sbins + r * (S + 1);
-    const float e0 = unerf_s2e(sb[i], a.s_near, a.s_far, a.lin), e1 = unerf_s2e(sb[i + 1], a.s_near, a.s_far, a.lin);
-    const float delta = e1 - e0, t2 = e0 + e1;
-    const float ox = a.origins[r * 3 + 0], oy = a.origins[r * 3 + 1], oz = a.origins[r * 3 + 2];
-    const float dxr = a.dirs[r * 3 + 0], dyr = a.dirs[r * 3 + 1], dzr = a.dirs[r * 3 + 2];
-    const float x0 = ox + dxr * t2 / 2.f, y0 = oy + dyr * t2 / 2.f, z0 = oz + dzr * t2 / 2.f;
-    float px = x0, py = y0, pz = z0;
-    const float sel = unerf_normalize_position(px, py, pz, a.box);
+    const PgSample s = pg_ray_sample(a.sbins + r * (S + 1), a.origins + r * 3, a.dirs + r * 3, a.s_near, a.s_far, a.lin,
+                                     a.box, i);
+    const float delta = s.delta, sel = s.sel;
 
     // ---- once: grid -> layer 0 ----
-#pragma unroll 4   // (one wave per SIMD: the gathers of four levels in flight; the registers are there)
-    for (int l = 0; l < 16; ++l) {
-        float2 f[8];
-        float wx, wy, wz, scale;
-        pg_level_corners<GRID>(a, l, mask, px, py, pz, f, wx, wy, wz, scale);
-        const float2 e = GRID == 0 ? unerf_blend8(f, wx, wy, wz) : unerf_tcnn_blend(f, wx, wy, wz);
-        A[(2 * l) * 64 + lane] = e.x;
-        A[(2 * l + 1) * 64 + lane] = e.y;
-    }
+    // 4 levels unrolled, not the other kernels' 2: one wave per SIMD, so the gathers of four levels in flight; the registers are there
+    pg_grid_fwd<GRID, 4>(a, mask, s, A, lane);
     uint32_t m0[2];
     {
         float acc[64];
@@ -4667,12 +4671,8 @@ __global__ __launch_bounds__(64) void pose_grad_mc_kernel(PoseGradArgs a, PoseGr
         relu_mask64(acc, m0);
         store_act<64>(H0, lane, acc, 0, true);
     }
-    float ux = (dxr + 1.f) / 2.f, uy = (dyr + 1.f) / 2.f, uz = (dzr + 1.f) / 2.f;
-    if (a.p.sh_remap) {
-        ux = ux * 2.f - 1.f;
-        uy = uy * 2.f - 1.f;
-        uz = uz * 2.f - 1.f;
-    }
+    float ux, uy, uz;
+    pg_sh_inputs(a, s, ux, uy, uz);
     uint32_t bh[2] = {0u, 0u};
     if (!m.explicit_masks) {
         const uint32_t pre = unerf_mc_pre(m.key, m.sample0 + (uint32_t)n);
@@ -4680,7 +4680,6 @@ __global__ __launch_bounds__(64) void pose_grad_mc_kernel(PoseGradArgs a, PoseGr
         bh[1] = unerf_mc_base_h(pre, 1u);
     }
     const bool last_bg = a.bg_mode == UNERF_BG_LAST_SAMPLE;
-    const int rl = 63 - lane;
     float G[64];   // running adjoint of the layer-0 pre-activation, summed over the passes
 #pragma unroll
     for (int o = 0; o < 64; ++o) G[o] = 0.f;
@@ -4724,19 +4723,15 @@ __global__ __launch_bounds__(64) void pose_grad_mc_kernel(PoseGradArgs a, PoseGr
 #pragma unroll
         for (int q = 0; q < 3; ++q) c[q] = unerf_nan_to_num(unerf_sigmoid(c[q]));
 
-        // ---- compositing and its adjoints, per pass (pose_grad_kernel's scans) ----
-        const float dd = in ? delta * sig : 0.f;
-        const float em = expf(-dd);
-        const float T = expf(-group_excl_scan<64>(dd, lane));
-        const float w = in ? unerf_nan_to_num((1.f - em) * T) : 0.f;
-        const float Tf = 1.f - group_sum<64>(w);
-        const float sw = __shfl(group_excl_scan<64>(__shfl(w, rl, 64), lane), rl, 64);
+        // ---- compositing and its adjoints, per pass ----
+        const PgWeights cw = pg_transmittance(in, delta, sig, lane);
+        const float em = cw.em, T = cw.T, w = cw.w, Tf = cw.Tf, sw = cw.sw;
         float dsig = 0.f, dc[3];
 #pragma unroll
         for (int q = 0; q < 3; ++q) {
             const float bg = last_bg ? __shfl(c[q], S - 1, 64) : a.bg[q];
             const float wc = w * c[q];
-            const float swc = __shfl(group_excl_scan<64>(__shfl(wc, rl, 64), lane), rl, 64);
+            const float swc = pg_suffix_sum(wc, lane);
             const float pred = group_sum<64>(wc) + Tf * bg;
             const float live = (pred >= 0.f && pred <= 1.f && in) ? 1.f / 3.f : 0.f;
             dsig += live * delta * (em * T * (c[q] - bg) - swc + bg * sw);
@@ -4761,24 +4756,11 @@ __global__ __launch_bounds__(64) void pose_grad_mc_kernel(PoseGradArgs a, PoseGr
         for (int o = 0; o < 64; ++o) d[o] *= m.scale[1];
         pg_dense_bwd<31, 64>(pg_const(wp.h0t), d, A, lane);   // rows 0..15: dSH, 16..30: dgeo
         {
-            float q[16];
-#pragma unroll
-            for (int j = 0; j < 16; ++j) q[j] = A[j * 64 + lane];
-            const float x = ux, y = uy, z = uz, xx = x * x, yy = y * y, zz = z * z;
-            const float c1 = 0.4886025119029199f, c2 = 1.0925484305920792f, c6 = 0.9461746957575601f, c8 = 0.5462742152960396f,
-                        c9 = 0.5900435899266435f, c10 = 2.890611442640554f, c11 = 0.4570457994644658f, c12 = 0.3731763325901154f,
-                        c14 = 1.445305721320277f;
-            const float z5 = 5.f * zz - 1.f, d3 = 3.f * (xx - yy);
-            float sx = q[3] * c1 + q[4] * (c2 * y) + q[7] * (c2 * z) + q[8] * (2.f * c8 * x) + q[9] * (6.f * c9 * x * y) + q[10] * (c10 * y * z) +
-                       q[13] * (c11 * z5) + q[14] * (2.f * c14 * x * z) + q[15] * (c9 * d3);
-            float sy = q[1] * c1 + q[4] * (c2 * x) + q[5] * (c2 * z) - q[8] * (2.f * c8 * y) + q[9] * (c9 * d3) + q[10] * (c10 * x * z) +
-                       q[11] * (c11 * z5) - q[14] * (2.f * c14 * y * z) - q[15] * (6.f * c9 * x * y);
-            float sz = q[2] * c1 + q[5] * (c2 * y) + q[6] * (2.f * c6 * z) + q[7] * (c2 * x) + q[10] * (c10 * x * y) + q[11] * (10.f * c11 * y * z) +
-                       q[12] * (c12 * (15.f * zz - 3.f)) + q[13] * (10.f * c11 * x * z) + q[14] * (c14 * (xx - yy));
-            const float du = a.p.sh_remap ? 1.f : 0.5f;
-            gdx += sx * du;
-            gdy += sy * du;
-            gdz += sz * du;
+            float sx, sy, sz;
+            pg_sh16_grad(A, lane, ux, uy, uz, a.p.sh_remap, sx, sy, sz);
+            gdx += sx;
+            gdy += sy;
+            gdz += sz;
         }
         // ---- backward: trunk layer 1, down to the layer-0 pre-activation ----
         float d1[16];
@@ -4793,66 +4775,15 @@ __global__ __launch_bounds__(64) void pose_grad_mc_kernel(PoseGradArgs a, PoseGr
 
     // ---- once: layer 0 backward, grid -> normalised position ----
     pg_dense_bwd<32, 64>(pg_const(a.p.w0t), G, A, lane);   // rows 2l, 2l+1: adjoint of level l's features
-    float gpx = 0.f, gpy = 0.f, gpz = 0.f;
-#pragma unroll 4   // (one wave per SIMD: the gathers of four levels in flight; the registers are there)
-    for (int l = 0; l < 16; ++l) {
-        float2 f[8];
-        float wx, wy, wz, scale;
-        pg_level_corners<GRID>(a, l, mask, px, py, pz, f, wx, wy, wz, scale);
-        const float g0 = A[(2 * l) * 64 + lane], g1 = A[(2 * l + 1) * 64 + lane];
-        float v[8];
-#pragma unroll
-        for (int q = 0; q < 8; ++q) v[q] = fmaf(g1, f[q].y, g0 * f[q].x);
-        float bx, by, bz;
-        pg_blend_grad<GRID>(v, wx, wy, wz, bx, by, bz);
-        gpx = fmaf(scale, bx, gpx);
-        gpy = fmaf(scale, by, gpy);
-        gpz = fmaf(scale, bz, gpz);
-    }
-    // ---- normalised position -> world position (pose_grad_kernel's statements) ----
-    float gx = gpx * sel, gy = gpy * sel, gz = gpz * sel;
-    if (a.box.use_aabb) {   // uniform
-        gx /= a.box.len[0];
-        gy /= a.box.len[1];
-        gz /= a.box.len[2];
-    } else {
-        gx *= 0.25f;
-        gy *= 0.25f;
-        gz *= 0.25f;
-        const float ax = fabsf(x0), ay = fabsf(y0), az = fabsf(z0);
-        const float mm = fmaxf(fmaxf(ax, ay), az);
-        if (!(mm < 1.f)) {
-            const float inv = 1.f / mm, diag = (2.f - inv) * inv, cross = 2.f * (1.f - mm) * inv * inv * inv;
-            const int kk = (ax >= ay && ax >= az) ? 0 : (ay >= az ? 1 : 2);
-            const float dot = (kk == 0 ? 0.f : gx * x0) + (kk == 1 ? 0.f : gy * y0) + (kk == 2 ? 0.f : gz * z0);
-            const float xk = kk == 0 ? x0 : (kk == 1 ? y0 : z0), gk = kk == 0 ? gx : (kk == 1 ? gy : gz);
-            const float along = gk * inv * inv + cross * (xk < 0.f ? -dot : dot);
-            gx = kk == 0 ? along : gx * diag;
-            gy = kk == 1 ? along : gy * diag;
-            gz = kk == 2 ? along : gz * diag;
-        }
-    }
-    if (!in) gx = gy = gz = gdx = gdy = gdz = 0.f;
-    const float th = t2 / 2.f;
-    const float go0 = group_sum<64>(gx) * m.inv_k, go1 = group_sum<64>(gy) * m.inv_k, go2 = group_sum<64>(gz) * m.inv_k;
-    const float gd0 = group_sum<64>(fmaf(th, gx, gdx)) * m.inv_k, gd1 = group_sum<64>(fmaf(th, gy, gdy)) * m.inv_k,
-                gd2 = group_sum<64>(fmaf(th, gz, gdz)) * m.inv_k;
+    float gpx, gpy, gpz, gx, gy, gz;
+    pg_grid_bwd<GRID, 4>(a, mask, s, A, lane, gpx, gpy, gpz);   // 4 levels unrolled, for the forward loop's reason
+    pg_world_grad(a.box, s, gpx, gpy, gpz, gx, gy, gz);
+    PgRaySums sums = pg_ray_sums(in, s.t2, gx, gy, gz, gdx, gdy, gdz);
+    sums.go0 *= m.inv_k, sums.go1 *= m.inv_k, sums.go2 *= m.inv_k;   // the mean over the passes: on the sums, before the row
+    sums.gd0 *= m.inv_k, sums.gd1 *= m.inv_k, sums.gd2 *= m.inv_k;
 
     // ---- epilogue: every store is a vector store of a lane-selected value ----
-    if (a.pose) {
-        const float gdd = gd0 * dxr + gd1 * dyr + gd2 * dzr;
-        const float P[3] = {gd0 - dxr * gdd, gd1 - dyr * gdd, gd2 - dzr * gdd};
-        const float go[3] = {go0, go1, go2};
-        const int row = lane >> 2, col = lane & 3;
-        const float Pa = row == 0 ? P[0] : (row == 1 ? P[1] : P[2]);
-        const float ga = row == 0 ? go[0] : (row == 1 ? go[1] : go[2]);
-        const int cb = col < 3 ? col : 0;
-        const float q = a.rinv[cb * 3 + 0] * dxr + a.rinv[cb * 3 + 1] * dyr + a.rinv[cb * 3 + 2] * dzr;
-        if (lane < 12) a.out_grad[r * 12 + lane] = col == 3 ? ga : Pa * q;
-    } else {
-        const float v6 = lane == 0 ? go0 : lane == 1 ? go1 : lane == 2 ? go2 : lane == 3 ? gd0 : lane == 4 ? gd1 : gd2;
-        if (lane < 6) a.out_grad[r * 6 + lane] = v6;
-    }
+    pg_store_grad(a, r, lane, pg_pose_row(a, lane, s.dx, s.dy, s.dz, sums));
     if (a.out_rgb && lane < 3) {
         const float pv = lane == 0 ? rgb_sum[0] : (lane == 1 ? rgb_sum[1] : rgb_sum[2]);
         a.out_rgb[r * 3 + lane] = pv * m.inv_k;
@@ -4863,24 +4794,16 @@ extern "C" int unerf_pose_grad_mc(const float* origins, const float* directions,
                                   float near_plane, float far_plane, int spacing, int64_t ray_offset, const unerf_field_params* p,
                                   const unerf_keep_masks* masks, int background, const float* background_rgb,
                                   const float* rot_inv, float* out_grad, float* out_rgb, void* stream) {
-    UNERF_REQUIRE(R >= 0 && S >= 1 && S <= 64, "pose_grad_mc: S=%d outside [1,64]", S);
+    if (int rc = pose_check_samples("pose_grad_mc", R, S)) return rc;
     if (R == 0) return UNERF_OK;
-    UNERF_REQUIRE(origins && directions && sbins && p && out_grad, "pose_grad_mc: null pointer");
+    if (int rc = pose_check_pointers("pose_grad_mc", origins, directions, sbins, p, out_grad != nullptr)) return rc;
     UNERF_REQUIRE(p->mode == UNERF_FIELD_MCDROPOUT, "pose_grad_mc: mode %d (an MCDROPOUT field is needed; unerf_pose_grad differentiates "
                   "the deterministic fields, the Laplace field's sampled heads are not differentiated)", p->mode);
     UNERF_REQUIRE(p->K >= 1, "pose_grad_mc: K=%d, the mean over passes needs K >= 1", p->K);
     UNERF_REQUIRE(p->p_drop >= 0.f && p->p_drop < 1.f, "pose_grad_mc: bad p_drop=%g", (double)p->p_drop);
     UNERF_REQUIRE((p->drop_sites & ~DROP_SITES_KNOWN) == 0, "pose_grad_mc: unknown bits in drop_sites=%d", p->drop_sites);
     UNERF_REQUIRE(!(p->drop_sites & UNERF_DROP_HEADIN), "pose_grad_mc: UNERF_DROP_HEADIN is out of scope (not built)");
-    UNERF_REQUIRE(p->hidden == 0 && p->hidden_color == 0 && p->geo_dim == 0 && p->feat_per_level == 0 && p->L == 16,
-                  "pose_grad_mc: nerfacto's widths only (hidden 64 / 64, geo 15, 2 features x 16 levels); the any-width kernel is out of scope");
-    UNERF_REQUIRE(p->out1 == 16, "pose_grad_mc: trunk output %d does not fit mode %d", p->out1, p->mode);
-    UNERF_REQUIRE(p->table && p->w0t && p->b0 && p->w1t && p->b1 && p->h0t && p->hb0 && p->h1t && p->hb1 && p->h2t && p->hb2 &&
-                      (p->scalings || p->tcnn_levels),
-                  "pose_grad_mc: null field pointer");
-    UNERF_REQUIRE(p->tcnn_levels || (p->log2T >= 1 && p->log2T <= 24), "pose_grad_mc: bad log2T=%d", p->log2T);
-    UNERF_REQUIRE(p->tcnn_levels || !p->grid_half, "pose_grad_mc: grid_half needs a tcnn-layout grid");
-    UNERF_REQUIRE(near_plane >= 0.f, "pose_grad_mc: near_plane=%g (spacing-domain bins only)", (double)near_plane);
+    if (int rc = pose_check_field("pose_grad_mc", p, near_plane, 16, false, "; the any-width kernel is out of scope")) return rc;
     const int sites = requested_drop_sites(*p);
     PoseGradMcArgs m;
     m.explicit_masks = masks ? 1 : 0;
@@ -4917,16 +4840,9 @@ extern "C" int unerf_pose_grad_mc(const float* origins, const float* directions,
         m.key = unerf_mc_key(p->seed, 0u);
         m.sample0 = (uint32_t)((uint64_t)ray_offset * (uint64_t)S);
     }
-    PoseGradArgs g;
-    g.origins = origins; g.dirs = directions; g.sbins = sbins; g.R = R; g.S = S;
-    if (int rc = set_spacing(g, near_plane, far_plane, spacing)) return rc;
-    g.p = *p;
-    g.box = make_norm_box(p->use_aabb, p->aabb);
-    if (int rc = unerf_set_background(g, background, background_rgb, "pose_grad_mc")) return rc;
-    g.pose = rot_inv ? 1 : 0;
-    for (int k = 0; k < 9; ++k) g.rinv[k] = rot_inv ? rot_inv[k] : 0.f;
-    g.out_grad = out_grad; g.out_rgb = out_rgb;
-    UNERF_REQUIRE(R < (1ll << 31), "pose_grad_mc: R=%lld rays in one launch, split the batch", (long long)R);
+    PoseGradArgs g;   // a block per ray: the grid's x is R, hence 2^31
+    if (int rc = pose_fill_args(g, "pose_grad_mc", origins, directions, sbins, R, S, near_plane, far_plane, spacing, p, background,
+                                background_rgb, rot_inv, out_grad, out_rgb, 1ll << 31)) return rc;
     constexpr size_t lds_bytes = 2 * 64 * 64 * sizeof(float);   // the working panel and layer 0's activations
     with_int3(tcnn_arg(g.p), [&](auto tc) {
         hipLaunchKernelGGL((pose_grad_mc_kernel<decltype(tc)::value>), dim3((unsigned)R), dim3(64), lds_bytes, (hipStream_t)stream, g, m);
@@ -4975,7 +4891,11 @@ __global__ __launch_bounds__(256, 2) void pose_grad_laplace_kernel(PoseGradArgs 
     const pg_cfp wd = pg_const(a.p.ws_density) + set * (size_t)nl * 65;
     const pg_cfp wc = pg_const(a.p.ws_rgb) + set * (size_t)nr * 195;
 
-    // ---- sample position, normalisation (pose_grad_kernel's statements) ----
+    // ---- sample position, normalisation: pg_ray_sample's statements, and below pg_sh_inputs' and pg_transmittance's with
+    // pg_suffix_sum's, IN LINE in this kernel alone.  With the four as calls the metadata is the parent's too (256 VGPRs, 109
+    // spilled, 440 B), but the listing is 8 to 58 instructions longer and the kernel 4 % slower at 100 sampled rows (11.65 ->
+    // 12.18 ms per 200 x 200 frame, 586 -> 611 ms at 1080p: the register allocation of the row loops moves); in line it has the
+    // time it had (docs/experiments.md 8.6).  Keep them in step with the functions.
     const float* sb = a.sbins + r * (S + 1);
     const float e0 = unerf_s2e(sb[i], a.s_near, a.s_far, a.lin), e1 = unerf_s2e(sb[i + 1], a.s_near, a.s_far, a.lin);
     const float delta = e1 - e0, t2 = e0 + e1;
@@ -4984,17 +4904,12 @@ __global__ __launch_bounds__(256, 2) void pose_grad_laplace_kernel(PoseGradArgs 
     const float x0 = ox + dxr * t2 / 2.f, y0 = oy + dyr * t2 / 2.f, z0 = oz + dzr * t2 / 2.f;
     float px = x0, py = y0, pz = z0;
     const float sel = unerf_normalize_position(px, py, pz, a.box);
+    PgSample s;   // for the shared stages below
+    s.delta = delta, s.t2 = t2, s.dx = dxr, s.dy = dyr, s.dz = dzr;
+    s.x0 = x0, s.y0 = y0, s.z0 = z0, s.px = px, s.py = py, s.pz = pz, s.sel = sel;
 
     // ---- forward: grid -> bare-Linear trunk (field_kernel's LAPLACE arithmetic) ----
-#pragma unroll 2
-    for (int l = 0; l < 16; ++l) {
-        float2 f[8];
-        float wx, wy, wz, scale;
-        pg_level_corners<GRID>(a, l, mask, px, py, pz, f, wx, wy, wz, scale);
-        const float2 e = GRID == 0 ? unerf_blend8(f, wx, wy, wz) : unerf_tcnn_blend(f, wx, wy, wz);
-        A[(2 * l) * 64 + lane] = e.x;
-        A[(2 * l + 1) * 64 + lane] = e.y;
-    }
+    pg_grid_fwd<GRID, 2>(a, mask, s, A, lane);
     float acc[64];
     pg_dense<32, 64>(pg_const(a.p.w0t), pg_const(a.p.b0), A, lane, acc);
     store_act<64>(A, lane, acc, 0, false);
@@ -5073,7 +4988,7 @@ __global__ __launch_bounds__(256, 2) void pose_grad_laplace_kernel(PoseGradArgs 
 #pragma unroll
     for (int k = 0; k < 3; ++k) c[k] = unerf_nan_to_num(c[k] / (float)nr);
 
-    // ---- compositing and its adjoints (pose_grad_kernel's scans) ----
+    // ---- compositing and its adjoints (pg_transmittance and pg_suffix_sum in line: see the prologue) ----
     const float dd = in ? delta * sig : 0.f;
     const float em = expf(-dd);
     const float T = expf(-group_excl_scan<64>(dd, lane));
@@ -5126,26 +5041,7 @@ __global__ __launch_bounds__(256, 2) void pose_grad_laplace_kernel(PoseGradArgs 
     load_masked64(A, lane, m1, d);
     pg_dense_bwd<31, 64>(pg_const(a.p.h0t), d, A, lane);   // rows 0..15: dSH, 16..30: dgeo
     float gdx, gdy, gdz;   // the SH term of ds/dd
-    {
-        float q[16];
-#pragma unroll
-        for (int j = 0; j < 16; ++j) q[j] = A[j * 64 + lane];
-        const float x = ux, y = uy, z = uz, xx = x * x, yy = y * y, zz = z * z;
-        const float c1 = 0.4886025119029199f, c2 = 1.0925484305920792f, c6 = 0.9461746957575601f, c8 = 0.5462742152960396f,
-                    c9 = 0.5900435899266435f, c10 = 2.890611442640554f, c11 = 0.4570457994644658f, c12 = 0.3731763325901154f,
-                    c14 = 1.445305721320277f;
-        const float z5 = 5.f * zz - 1.f, d3 = 3.f * (xx - yy);
-        gdx = q[3] * c1 + q[4] * (c2 * y) + q[7] * (c2 * z) + q[8] * (2.f * c8 * x) + q[9] * (6.f * c9 * x * y) + q[10] * (c10 * y * z) +
-              q[13] * (c11 * z5) + q[14] * (2.f * c14 * x * z) + q[15] * (c9 * d3);
-        gdy = q[1] * c1 + q[4] * (c2 * x) + q[5] * (c2 * z) - q[8] * (2.f * c8 * y) + q[9] * (c9 * d3) + q[10] * (c10 * x * z) +
-              q[11] * (c11 * z5) - q[14] * (2.f * c14 * y * z) - q[15] * (6.f * c9 * x * y);
-        gdz = q[2] * c1 + q[5] * (c2 * y) + q[6] * (2.f * c6 * z) + q[7] * (c2 * x) + q[10] * (c10 * x * y) + q[11] * (10.f * c11 * y * z) +
-              q[12] * (c12 * (15.f * zz - 3.f)) + q[13] * (10.f * c11 * x * z) + q[14] * (c14 * (xx - yy));
-        const float du = a.p.sh_remap ? 1.f : 0.5f;
-        gdx *= du;
-        gdy *= du;
-        gdz *= du;
-    }
+    pg_sh16_grad(A, lane, ux, uy, uz, a.p.sh_remap, gdx, gdy, gdz);
     // ---- backward: trunk (no ReLU: no masks) ----
     float d1[15];
 #pragma unroll
@@ -5156,63 +5052,12 @@ __global__ __launch_bounds__(256, 2) void pose_grad_laplace_kernel(PoseGradArgs 
     for (int o = 0; o < 64; ++o) d[o] = fmaf(dmu, J[o], A[o * 64 + lane]);
     pg_dense_bwd<32, 64>(pg_const(a.p.w0t), d, A, lane);   // rows 2l, 2l+1: adjoint of level l's features
 
-    // ---- backward: grid -> normalised position -> world position, ray sums, epilogue (pose_grad_kernel's statements) ----
-    float gpx = 0.f, gpy = 0.f, gpz = 0.f;
-#pragma unroll 2
-    for (int l = 0; l < 16; ++l) {
-        float2 f[8];
-        float wx, wy, wz, scale;
-        pg_level_corners<GRID>(a, l, mask, px, py, pz, f, wx, wy, wz, scale);
-        const float g0 = A[(2 * l) * 64 + lane], g1 = A[(2 * l + 1) * 64 + lane];
-        float v[8];
-#pragma unroll
-        for (int k = 0; k < 8; ++k) v[k] = fmaf(g1, f[k].y, g0 * f[k].x);
-        float bx, by, bz;
-        pg_blend_grad<GRID>(v, wx, wy, wz, bx, by, bz);
-        gpx = fmaf(scale, bx, gpx);
-        gpy = fmaf(scale, by, gpy);
-        gpz = fmaf(scale, bz, gpz);
-    }
-    float gx = gpx * sel, gy = gpy * sel, gz = gpz * sel;
-    if (a.box.use_aabb) {   // uniform
-        gx /= a.box.len[0];
-        gy /= a.box.len[1];
-        gz /= a.box.len[2];
-    } else {
-        gx *= 0.25f;
-        gy *= 0.25f;
-        gz *= 0.25f;
-        const float ax = fabsf(x0), ay = fabsf(y0), az = fabsf(z0);
-        const float m = fmaxf(fmaxf(ax, ay), az);
-        if (!(m < 1.f)) {
-            const float inv = 1.f / m, diag = (2.f - inv) * inv, cross = 2.f * (1.f - m) * inv * inv * inv;
-            const int k = (ax >= ay && ax >= az) ? 0 : (ay >= az ? 1 : 2);
-            const float dot = (k == 0 ? 0.f : gx * x0) + (k == 1 ? 0.f : gy * y0) + (k == 2 ? 0.f : gz * z0);
-            const float xk = k == 0 ? x0 : (k == 1 ? y0 : z0), gk = k == 0 ? gx : (k == 1 ? gy : gz);
-            const float along = gk * inv * inv + cross * (xk < 0.f ? -dot : dot);
-            gx = k == 0 ? along : gx * diag;
-            gy = k == 1 ? along : gy * diag;
-            gz = k == 2 ? along : gz * diag;
-        }
-    }
-    if (!in) gx = gy = gz = gdx = gdy = gdz = 0.f;
-    const float th = t2 / 2.f;
-    const float go0 = group_sum<64>(gx), go1 = group_sum<64>(gy), go2 = group_sum<64>(gz);
-    const float gd0 = group_sum<64>(fmaf(th, gx, gdx)), gd1 = group_sum<64>(fmaf(th, gy, gdy)), gd2 = group_sum<64>(fmaf(th, gz, gdz));
-    if (a.pose) {
-        const float gdd = gd0 * dxr + gd1 * dyr + gd2 * dzr;
-        const float P[3] = {gd0 - dxr * gdd, gd1 - dyr * gdd, gd2 - dzr * gdd};
-        const float go[3] = {go0, go1, go2};
-        const int row = lane >> 2, col = lane & 3;
-        const float Pa = row == 0 ? P[0] : (row == 1 ? P[1] : P[2]);
-        const float ga = row == 0 ? go[0] : (row == 1 ? go[1] : go[2]);
-        const int cb = col < 3 ? col : 0;
-        const float q = a.rinv[cb * 3 + 0] * dxr + a.rinv[cb * 3 + 1] * dyr + a.rinv[cb * 3 + 2] * dzr;
-        if (lane < 12) a.out_grad[r * 12 + lane] = col == 3 ? ga : Pa * q;
-    } else {
-        const float v6 = lane == 0 ? go0 : lane == 1 ? go1 : lane == 2 ? go2 : lane == 3 ? gd0 : lane == 4 ? gd1 : gd2;
-        if (lane < 6) a.out_grad[r * 6 + lane] = v6;
-    }
+    // ---- backward: grid -> normalised position -> world position, ray sums, epilogue ----
+    float gpx, gpy, gpz, gx, gy, gz;
+    pg_grid_bwd<GRID, 2>(a, mask, s, A, lane, gpx, gpy, gpz);
+    pg_world_grad(a.box, s, gpx, gpy, gpz, gx, gy, gz);
+    const PgRaySums sums = pg_ray_sums(in, s.t2, gx, gy, gz, gdx, gdy, gdz);
+    pg_store_grad(a, r, lane, pg_pose_row(a, lane, s.dx, s.dy, s.dz, sums));
     if (a.out_rgb && lane < 3) {
         const float pv = lane == 0 ? pred[0] : (lane == 1 ? pred[1] : pred[2]);
         a.out_rgb[r * 3 + lane] = fminf(fmaxf(pv, 0.f), 1.f);
@@ -5223,20 +5068,12 @@ extern "C" int unerf_pose_grad_laplace(const float* origins, const float* direct
                                        float near_plane, float far_plane, int spacing, int64_t ray_offset,
                                        const unerf_field_params* p, int background, const float* background_rgb,
                                        const float* rot_inv, float* out_grad, float* out_rgb, void* stream) {
-    UNERF_REQUIRE(R >= 0 && S >= 1 && S <= 64, "pose_grad_laplace: S=%d outside [1,64]", S);
+    if (int rc = pose_check_samples("pose_grad_laplace", R, S)) return rc;
     if (R == 0) return UNERF_OK;
-    UNERF_REQUIRE(origins && directions && sbins && p && out_grad, "pose_grad_laplace: null pointer");
+    if (int rc = pose_check_pointers("pose_grad_laplace", origins, directions, sbins, p, out_grad != nullptr)) return rc;
     UNERF_REQUIRE(p->mode == UNERF_FIELD_LAPLACE, "pose_grad_laplace: mode %d (a LAPLACE field is needed; unerf_pose_grad and "
                   "unerf_pose_grad_mc differentiate the other fields)", p->mode);
-    UNERF_REQUIRE(p->hidden == 0 && p->hidden_color == 0 && p->geo_dim == 0 && p->feat_per_level == 0 && p->L == 16 && p->out1 == 15,
-                  "pose_grad_laplace: nerfacto's widths only (hidden 64 / 64, geo 15 = trunk output 15, 2 features x 16 levels); the "
-                  "any-width kernel is out of scope");
-    UNERF_REQUIRE(p->table && p->w0t && p->b0 && p->w1t && p->b1 && p->h0t && p->hb0 && p->h1t && p->hb1 && (p->scalings || p->tcnn_levels),
-                  "pose_grad_laplace: null field pointer");
-    UNERF_REQUIRE(p->ws_density && p->ws_rgb, "pose_grad_laplace: null ws_density / ws_rgb (the sampled last layers of the named draw)");
-    UNERF_REQUIRE(p->tcnn_levels || (p->log2T >= 1 && p->log2T <= 24), "pose_grad_laplace: bad log2T=%d", p->log2T);
-    UNERF_REQUIRE(p->tcnn_levels || !p->grid_half, "pose_grad_laplace: grid_half needs a tcnn-layout grid");
-    UNERF_REQUIRE(near_plane >= 0.f, "pose_grad_laplace: near_plane=%g (spacing-domain bins only)", (double)near_plane);
+    if (int rc = pose_check_field("pose_grad_laplace", p, near_plane, 15, true, "; the any-width kernel is out of scope")) return rc;
     UNERF_REQUIRE(p->n_lap >= 1, "pose_grad_laplace: n_lap=%d, the mean over sampled rows needs n_lap >= 1", p->n_lap);
     UNERF_REQUIRE(ray_offset >= 0, "pose_grad_laplace: ray_offset=%lld < 0", (long long)ray_offset);
     UNERF_REQUIRE(p->lap_chunk_rays >= 0, "pose_grad_laplace: lap_chunk_rays=%d < 0", p->lap_chunk_rays);
@@ -5244,24 +5081,12 @@ extern "C" int unerf_pose_grad_laplace(const float* origins, const float* direct
                   "pose_grad_laplace: rays [%lld, %lld) reach past the last of lap_sets=%d sample sets of lap_chunk_rays=%d rays",
                   (long long)ray_offset, (long long)(ray_offset + R), p->lap_sets, p->lap_chunk_rays);
     PoseGradArgs g;
-    g.origins = origins; g.dirs = directions; g.sbins = sbins; g.R = R; g.S = S;
-    if (int rc = set_spacing(g, near_plane, far_plane, spacing)) return rc;
-    g.p = *p;
-    g.box = make_norm_box(p->use_aabb, p->aabb);
-    if (int rc = unerf_set_background(g, background, background_rgb, "pose_grad_laplace")) return rc;
-    g.pose = rot_inv ? 1 : 0;
-    for (int k = 0; k < 9; ++k) g.rinv[k] = rot_inv ? rot_inv[k] : 0.f;
-    g.out_grad = out_grad; g.out_rgb = out_rgb;
+    if (int rc = pose_fill_args(g, "pose_grad_laplace", origins, directions, sbins, R, S, near_plane, far_plane, spacing, p,
+                                background, background_rgb, rot_inv, out_grad, out_rgb, 1ll << 32)) return rc;
     PoseGradLapArgs la;
     la.ray_offset = ray_offset;
     la.n_rgb = p->n_lap_rgb > 0 ? p->n_lap_rgb : p->n_lap;
-    UNERF_REQUIRE(R < (1ll << 32), "pose_grad_laplace: R=%lld rays in one launch, split the batch", (long long)R);
-    const int64_t blocks = (R + 3) / 4;   // a wave per ray; 64 KiB of LDS per block: two blocks per CU
-    constexpr size_t lds_bytes = 4 * 64 * 64 * sizeof(float);
-    with_int3(tcnn_arg(g.p), [&](auto tc) {
-        hipLaunchKernelGGL((pose_grad_laplace_kernel<decltype(tc)::value>), dim3((unsigned)blocks), dim3(256), lds_bytes,
-                           (hipStream_t)stream, g, la);
-    });
+    with_int3(tcnn_arg(g.p), [&](auto tc) { pose_launch_rays4(pose_grad_laplace_kernel<decltype(tc)::value>, R, stream, g, la); });
     return unerf_check_launch("pose_grad_laplace");
 }
 

@@ -1249,6 +1249,22 @@ def laplace_ggn_diag(origins, directions, sbins, field: FieldDev, density_mean: 
                                                                    _p(ggn_rgb), _stream()))
 
 
+def _rot_inv9(name: str, rot_inv):
+    """rot_inv of a pose op (None | 9 values, e.g. [3,3]) -> None | the float[9] the library reads"""
+    if rot_inv is None:
+        return None
+    vals = [float(v) for v in torch.as_tensor(rot_inv).detach().cpu().to(torch.float32).reshape(-1)]
+    if len(vals) != 9:
+        raise _l.UnerfError(f"{name}: rot_inv must have 9 entries, got {len(vals)}")
+    return (C.c_float * 9)(*vals)
+
+
+def _pose_grad_outputs(R: int, ri, want_rgb: bool, dev):
+    """-> (grad [R,12] with rot_inv, else [R,6]; rgb [R,3] | None) of the three pose-gradient ops"""
+    grad = torch.empty(R, 6 if ri is None else 12, device=dev, dtype=torch.float32)
+    return grad, (torch.empty(R, 3, device=dev, dtype=torch.float32) if want_rgb else None)
+
+
 def pose_grad(origins, directions, sbins, field: FieldDev, near: float, far: float, rot_inv: Optional[torch.Tensor] = None,
               spacing: int = 0, background=None, want_rgb: bool = False):
     """Per-ray gradient of s = mean over channels of the eval-mode rgb, with the sample bins held fixed
@@ -1261,14 +1277,8 @@ def pose_grad(origins, directions, sbins, field: FieldDev, near: float, far: flo
     R, S = sbins.shape[0], sbins.shape[1] - 1
     dev = origins.device
     cs = field.cstruct()
-    ri = None
-    if rot_inv is not None:
-        vals = [float(v) for v in torch.as_tensor(rot_inv).detach().cpu().to(torch.float32).reshape(-1)]
-        if len(vals) != 9:
-            raise _l.UnerfError(f"pose_grad: rot_inv must have 9 entries, got {len(vals)}")
-        ri = (C.c_float * 9)(*vals)
-    grad = torch.empty(R, 6 if ri is None else 12, device=dev, dtype=torch.float32)
-    rgb = torch.empty(R, 3, device=dev, dtype=torch.float32) if want_rgb else None
+    ri = _rot_inv9("pose_grad", rot_inv)
+    grad, rgb = _pose_grad_outputs(R, ri, want_rgb, dev)
     bg_mode, bg_rgb = _background(background)
     with _ctx(dev):
         _run("pose_grad", lambda: lib.unerf_pose_grad(_p(origins), _p(directions), _p(sbins), R, S, near, far, spacing, C.byref(cs),
@@ -1316,12 +1326,7 @@ def pose_jacobian(origins, directions, sbins, field: FieldDev, near: float, far:
     R, S = sbins.shape[0], sbins.shape[1] - 1
     dev = origins.device
     cs = field.cstruct()
-    ri = None
-    if rot_inv is not None:
-        vals = [float(v) for v in torch.as_tensor(rot_inv).detach().cpu().to(torch.float32).reshape(-1)]
-        if len(vals) != 9:
-            raise _l.UnerfError(f"pose_jacobian: rot_inv must have 9 entries, got {len(vals)}")
-        ri = (C.c_float * 9)(*vals)
+    ri = _rot_inv9("pose_jacobian", rot_inv)
     D, Cn = (6 if ri is None else 12), bin(bits).count("1")
     pj, P = None, 0
     if proj is not None:
@@ -1356,14 +1361,8 @@ def pose_grad_mc(origins, directions, sbins, field: FieldDev, near: float, far: 
     dev = origins.device
     cs = field.cstruct()
     km = None if keep_masks is None else keep_masks.cstruct(field.K)
-    ri = None
-    if rot_inv is not None:
-        vals = [float(v) for v in torch.as_tensor(rot_inv).detach().cpu().to(torch.float32).reshape(-1)]
-        if len(vals) != 9:
-            raise _l.UnerfError(f"pose_grad_mc: rot_inv must have 9 entries, got {len(vals)}")
-        ri = (C.c_float * 9)(*vals)
-    grad = torch.empty(R, 6 if ri is None else 12, device=dev, dtype=torch.float32)
-    rgb = torch.empty(R, 3, device=dev, dtype=torch.float32) if want_rgb else None
+    ri = _rot_inv9("pose_grad_mc", rot_inv)
+    grad, rgb = _pose_grad_outputs(R, ri, want_rgb, dev)
     bg_mode, bg_rgb = _background(background)
     with _ctx(dev):
         _run("pose_grad_mc", lambda: lib.unerf_pose_grad_mc(_p(origins), _p(directions), _p(sbins), R, S, near, far, spacing,
@@ -1385,14 +1384,8 @@ def pose_grad_laplace(origins, directions, sbins, field: FieldDev, near: float, 
     R, S = sbins.shape[0], sbins.shape[1] - 1
     dev = origins.device
     cs = field.cstruct()
-    ri = None
-    if rot_inv is not None:
-        vals = [float(v) for v in torch.as_tensor(rot_inv).detach().cpu().to(torch.float32).reshape(-1)]
-        if len(vals) != 9:
-            raise _l.UnerfError(f"pose_grad_laplace: rot_inv must have 9 entries, got {len(vals)}")
-        ri = (C.c_float * 9)(*vals)
-    grad = torch.empty(R, 6 if ri is None else 12, device=dev, dtype=torch.float32)
-    rgb = torch.empty(R, 3, device=dev, dtype=torch.float32) if want_rgb else None
+    ri = _rot_inv9("pose_grad_laplace", rot_inv)
+    grad, rgb = _pose_grad_outputs(R, ri, want_rgb, dev)
     bg_mode, bg_rgb = _background(background)
     with _ctx(dev):
         _run("pose_grad_laplace", lambda: lib.unerf_pose_grad_laplace(_p(origins), _p(directions), _p(sbins), R, S, near, far, spacing,
