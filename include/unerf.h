@@ -879,6 +879,9 @@ typedef struct {
 #define UNERF_LPIPS_CONV_TILE_M 64   /* output pixels per workgroup of the convolution kernel (its row tile) */
 #define UNERF_LPIPS_CONV_TILE_N 64   /* output channels per workgroup: C_out must be a multiple */
 #define UNERF_LPIPS_HEAD_PIXELS 64   /* pixels per workgroup of the head kernel */
+#define UNERF_LPIPS_CONV_STEP_K 16   /* reduction terms per step of the convolution kernel; the last step may be partial */
+#define UNERF_LPIPS_EW_THREADS 256   /* threads per workgroup of the pack and max-pool kernels */
+#define UNERF_LPIPS_EW_MAX_WG 4096   /* their grid is capped here: beyond EW_THREADS * EW_MAX_WG values a thread strides */
 
 /* The input pack: pred / target [B, n, 3] float32 (HWC) -> act [2 B, n, 3]: prediction b at b, target b at B + b, each
  * ((2 x - 1) - shift[c]) / scale[c] in float32, one rounding per operation, with x = the prediction clipped to <= 1 (a

@@ -226,7 +226,9 @@ def test_new_symbols_are_exported_and_typed(lib):
     text = open(os.path.join(ROOT, "include", "unerf.h")).read()
     for macro, value in (("UNERF_LPIPS_LAYERS", lib.LPIPS_LAYERS), ("UNERF_LPIPS_ROW", lib.LPIPS_ROW), ("UNERF_LPIPS_BAD_OFF", lib.LPIPS_BAD_OFF),
                          ("UNERF_LPIPS_MIN_SIDE", lib.LPIPS_MIN_SIDE), ("UNERF_LPIPS_CONV_TILE_M", lib.LPIPS_CONV_TILE_M),
-                         ("UNERF_LPIPS_CONV_TILE_N", lib.LPIPS_CONV_TILE_N), ("UNERF_LPIPS_HEAD_PIXELS", lib.LPIPS_HEAD_PIXELS)):
+                         ("UNERF_LPIPS_CONV_TILE_N", lib.LPIPS_CONV_TILE_N), ("UNERF_LPIPS_HEAD_PIXELS", lib.LPIPS_HEAD_PIXELS),
+                         ("UNERF_LPIPS_CONV_STEP_K", lib.LPIPS_CONV_STEP_K), ("UNERF_LPIPS_EW_THREADS", lib.LPIPS_EW_THREADS),
+                         ("UNERF_LPIPS_EW_MAX_WG", lib.LPIPS_EW_MAX_WG)):
         assert f"#define {macro} {value}" in text, macro
     assert lib.LPIPS_MIN_SIDE == M.LPIPS_MIN_SIDE and lib.LPIPS_LAYERS == M.LPIPS_LAYERS
 

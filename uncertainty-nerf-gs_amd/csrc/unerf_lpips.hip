@@ -22,11 +22,11 @@
 namespace {
 
 constexpr int LP_LAYERS = UNERF_LPIPS_LAYERS;
-constexpr int CV_BM = UNERF_LPIPS_CONV_TILE_M, CV_BN = UNERF_LPIPS_CONV_TILE_N, CV_BK = 16, CV_THREADS = 256;
+constexpr int CV_BM = UNERF_LPIPS_CONV_TILE_M, CV_BN = UNERF_LPIPS_CONV_TILE_N, CV_BK = UNERF_LPIPS_CONV_STEP_K, CV_THREADS = 256;
 constexpr int CV_AROWS = CV_BM * CV_BK / CV_THREADS;     // im2col rows per thread and step (4)
 constexpr int CV_BROWS = CV_BK * CV_BN / CV_THREADS;     // weight rows per thread and step (4)
 constexpr int HD_PIX = UNERF_LPIPS_HEAD_PIXELS, HD_THREADS = 256, HD_WAVES = HD_THREADS / 64;
-constexpr int EW_THREADS = 256, EW_MAX_WG = 4096;        // the elementwise kernels stride beyond EW_MAX_WG workgroups
+constexpr int EW_THREADS = UNERF_LPIPS_EW_THREADS, EW_MAX_WG = UNERF_LPIPS_EW_MAX_WG;   // the elementwise kernels stride beyond EW_MAX_WG workgroups
 constexpr double LP_NORM_EPS = 1e-8;                     // metrics.LPIPS_NORM_EPS
 
 static_assert(CV_BM == 64 && CV_BN == 64, "lp_conv_kernel: four waves, one 32 x 32 quarter of a 64 x 64 tile each");
@@ -211,6 +211,9 @@ __global__ __launch_bounds__(HD_THREADS) void lp_head_kernel(const float* __rest
         partial[(size_t)b * gridDim.x + blockIdx.x] = v;
     }
 }
+
+// lp_sum_kernel and lp_counts_kernel have one thread per image and are launched as ONE block of 64 threads
+static_assert(UNERF_METRICS_MAX_IMAGES <= 64, "lp_sum_kernel / lp_counts_kernel: one block of 64 threads covers every image of a call");
 
 // one thread per image adds its partials in index order
 __global__ void lp_sum_kernel(const double* __restrict__ partial, uint32_t nblk, int B, double* __restrict__ out, int64_t out_stride) {

@@ -325,6 +325,7 @@ METRICS_MAX_IMAGES = 64                           # include/unerf.h: UNERF_METRI
 # include/unerf.h: UNERF_LPIPS_* (row of unerf_lpips_batch, tiles of its kernels)
 LPIPS_ROW, LPIPS_BAD_OFF, LPIPS_MIN_SIDE = 11, 10, 31
 LPIPS_CONV_TILE_M, LPIPS_CONV_TILE_N, LPIPS_HEAD_PIXELS = 64, 64, 64
+LPIPS_CONV_STEP_K, LPIPS_EW_THREADS, LPIPS_EW_MAX_WG = 16, 256, 4096
 # include/unerf.h: UNERF_ENS_* (bounds and statistics of unerf_ensemble_reduce)
 ENS_MAX_KEYS, ENS_MAX_MEMBERS, ENS_MAX_CHANNELS = 32, 64, 64
 ENS_MEAN, ENS_VAR, ENS_VAR_CMEAN, ENS_ALEA_CMEAN, ENS_EPI_ALEA, ENS_EPI_ALEA_SQRT, ENS_STD_CMEAN = range(7)
