@@ -695,11 +695,12 @@ struct PropArgs {
     float* out;
     FastDiv fd;  // by n; used when R * n < 2^31
     int small;
-    // Pixel-patch schedule (image_width hint): a workgroup = an 8x8 pixel patch x 4 consecutive sample indices,
+    // Pixel-patch schedule (image_width hint): a workgroup = an 8x8 pixel patch x a group of consecutive sample indices
+    // (prop_density_kernel: 4, one per wave; prop_patch_kernel: 16, four per wave, walked one after the other),
     // a wave = the 64 pixels of the patch at ONE sample index.  Neighbouring pixels at equal depth sit in the
     // same one or two grid cells, so a gather instruction touches a handful of cache lines instead of the
     // ~20 of 64 consecutive samples along one ray (the proposal kernels saturate the texture-address unit).
-    uint32_t img_w, pcols, nsg, nblocks;   // img_w = 0: linear schedule; nsg = ceil(n / 4) sample groups; nblocks: workgroups of the patch schedule
+    uint32_t img_w, pcols, nsg, nblocks;   // img_w = 0: linear schedule; nsg = sample groups per patch, ceil(n / 4) or ceil(n / 16), set per kernel on the host; nblocks: workgroups of the patch schedule
     FastDiv div_nsg, div_pcols;
     int64_t g0, first_row;
     int vec4;   // prop_patch_kernel: n % 4 == 0 and density_out 16-byte aligned
@@ -791,18 +792,30 @@ __global__ __launch_bounds__(256) void prop_density_kernel(PropArgs a) {
     a.out[idx] = a.avg * unerf_exp(o) * sel;
 }
 
-// Patch-schedule form of prop_density_kernel with the per-RAY traffic staged through LDS.  A workgroup is an 8x8
-// pixel patch x 4 consecutive sample indices, so its four waves need the same 64 origins / directions and five
-// consecutive bin edges of the same 64 rays, and produce 4 adjacent densities per ray.  Ray-indexed accesses cost
-// the texture path one cache line per LANE (64 rays = 64 rows of sbins / density_out): loading them once per
-// workgroup and storing one 16-byte vector per ray removes about half of the cache-line accesses of the 96-sample
-// pass (own sbins row per ray) and a quarter of the 256-sample pass (shared sbins).  Same arithmetic on
-// the same values: bit-identical to prop_density_kernel.
+// Patch-schedule form of prop_density_kernel with the per-RAY work done once per lane.  A workgroup is an 8x8 pixel
+// patch x 16 consecutive sample indices; wave wv owns samples i_base + 4 wv + q, q = 0..3, and a lane keeps ITS ray for
+// all four.  A wave is still the 64 pixels of the patch at one sample index per gather (the locality the schedule is
+// for), but the block decode, the ray, the barrier and the store are paid once per four samples instead of once per
+// sample (docs/experiments.md 8.7):
+//   * ray: one wave loads the 64 origins / directions (a ray-indexed access costs the texture path one cache line
+//     per LANE), every lane reads its own back from LDS (per sample: six more registers live across the loop cost
+//     the L = 8 instances a wave per SIMD, and measured the same at L = 5);
+//   * bin edges, own rows: every raw edge of the block is loaded once -- a lane loads the four edges its samples
+//     start at (one 16-byte load when the row allows) and takes the fifth from the next wave through LDS (the last
+//     wave loads it) -- and converted once per lane: five conversions (an IEEE division each) for four samples
+//     where a sample alone needs two; shared row: 17 lanes convert the block's edges once for the workgroup;
+//   * output: the lane's four adjacent densities leave as one 16-byte store when n % 4 == 0 and the output is
+//     aligned, as dwords otherwise; samples >= n are neither computed nor stored.
+// The sample loop is a real loop, rolled (asked for 2 or 4 copies the compiler emits this same listing, 8.7); t and the
+// density go through a lane-private LDS slot so that no register array is indexed by the loop counter.  unerf_s2e of
+// the same edge gives the same bits whoever converts it, and the per-sample arithmetic is prop_density_kernel's on the
+// same values: bit-identical to it.
+constexpr int PROP_WALK = 4;          // consecutive samples per lane
 template <int L, int HID>
 __global__ __launch_bounds__(256) void prop_patch_kernel(PropArgs a) {
     __shared__ float s_od[6][64];
-    __shared__ float s_e[5][64];
-    __shared__ float s_out[64][4];
+    __shared__ float s_e[4][64];             // own rows: [wave][lane] the first raw edge of each wave; shared row: 17 Euclidean edges
+    __shared__ float s_io[4][PROP_WALK][64];  // [wave][q][lane]: t of sample q, then its density (lane-private)
     // XCD-aware order: workgroups go to the 8 XCDs round-robin; every XCD takes a CONTIGUOUS
     // eighth of the (patch, sample group) list -- a band of the image -- instead of every eighth workgroup, so the grid lines
     // neighbouring patches share are fetched into one L2 instead of all eight.  Pure scheduling: same values per sample.
@@ -810,78 +823,107 @@ __global__ __launch_bounds__(256) void prop_patch_kernel(PropArgs a) {
     if (bid >= a.nblocks) return;
     const uint32_t patch = fastdiv(bid, a.div_nsg), sg = bid - patch * a.nsg;
     const uint32_t band = fastdiv(patch, a.div_pcols), pc = patch - band * a.pcols;
-    const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
+    const uint32_t lane = threadIdx.x & 63u, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // uniform, and known to be: the sample loop's trip count hangs on it
     const uint32_t x = pc * 8u + (lane & 7u);
     const int64_t y = a.first_row + (int64_t)band * 8 + (lane >> 3);
     int64_t r = y * (int64_t)a.img_w + x - a.g0;
     const bool ray_ok = x < a.img_w && r >= 0 && r < a.R;
     if (!ray_ok) r = 0;
-    const int i_base = (int)(sg * 4u);
-    {   // stage: wave 0 the ray, wave 1 its five raw bin edges (one 16-byte + one 4-byte load when the row allows)
+    const int i_base = (int)(sg * (4u * PROP_WALK));
+    const int i0 = i_base + (int)wv * PROP_WALK;   // this wave's first sample
+    const int nq = min(PROP_WALK, a.n - i0);       // its live samples (<= 0: none); uniform
+    float raw[PROP_WALK + 1];                      // own rows: the lane's raw edges i0 .. i0 + 4 (index clamped to n)
+    {   // stage: wave 0 the ray; the bin edges by every wave (own rows) or by 17 lanes of wave 1 (shared row)
         if (wv == 0) {
 #pragma unroll
             for (int c = 0; c < 3; ++c) {
                 s_od[c][lane] = a.origins[r * 3 + c];
                 s_od[3 + c][lane] = a.dirs[r * 3 + c];
             }
-        } else if (wv == 1 && a.sstride == 0) {
+        }
+        if (a.sstride == 0) {
             // one shared row of bin edges (the 256 initial bins): the Euclidean edges are the same for every ray, so
-            // five lanes convert them ONCE for the workgroup (one conversion stream instead of two per wave; a
-            // conversion is an IEEE division and the kernel is VALU-issue bound) and every lane reads them back
-            const float* sb = a.sbins + i_base;
-            const float e = unerf_s2e(sb[min((int)(lane < 5u ? lane : 4u), a.n - i_base)], a.s_near, a.s_far, a.lin);
-            if (lane < 5u) s_e[lane][0] = e;
-        } else if (wv == 1) {
-            const float* sb = a.sbins + r * a.sstride + i_base;
-            if (i_base + 4 <= a.n) {  // uniform
+            // 17 lanes convert the block's ONCE for the workgroup (a conversion is an IEEE division and the kernel is
+            // VALU-issue bound) and every lane reads them back
+            if (wv == 1) {
+                const float e = unerf_s2e(a.sbins[min(i_base + (int)min(lane, 16u), a.n)], a.s_near, a.s_far, a.lin);
+                if (lane <= 16u) s_e[0][lane] = e;
+            }
+        } else {
+            const float* sb = a.sbins + r * a.sstride;
+            if (i0 + PROP_WALK <= a.n) {  // uniform
                 struct __attribute__((packed, aligned(4))) Q { float x, y, z, w; };
-                const Q q = *reinterpret_cast<const Q*>(sb);
-                s_e[0][lane] = q.x; s_e[1][lane] = q.y; s_e[2][lane] = q.z; s_e[3][lane] = q.w;
-                s_e[4][lane] = sb[4];
+                const Q q = *reinterpret_cast<const Q*>(sb + i0);
+                raw[0] = q.x; raw[1] = q.y; raw[2] = q.z; raw[3] = q.w;
             } else {
 #pragma unroll
-                for (int e = 0; e < 5; ++e) s_e[e][lane] = sb[min(e, a.n - i_base)];
+                for (int e = 0; e < PROP_WALK; ++e) raw[e] = sb[min(i0 + e, a.n)];
             }
+            if (wv == 3) raw[PROP_WALK] = sb[min(i0 + PROP_WALK, a.n)];
+            s_e[wv][lane] = raw[0];
         }
     }
     __syncthreads();
-    const int i = i_base + (int)wv;
-    float dens = 0.f;
-    if (ray_ok && i < a.n) {
-        const float t = a.sstride == 0 ? s_e[wv][0] + s_e[wv + 1][0]   // uniform: already Euclidean (same bits)
-                                       : unerf_s2e(s_e[wv][lane], a.s_near, a.s_far, a.lin) + unerf_s2e(s_e[wv + 1][lane], a.s_near, a.s_far, a.lin);
-        float px = s_od[0][lane] + s_od[3][lane] * t / 2.f;
-        float py = s_od[1][lane] + s_od[4][lane] * t / 2.f;
-        float pz = s_od[2][lane] + s_od[5][lane] * t / 2.f;
+    if (nq <= 0 || !ray_ok) return;   // behind the only barrier
+    float* io = &s_io[wv][0][lane];
+    {   // t of the lane's samples: the sum of the two Euclidean edges of each, every edge converted once
+        float e[PROP_WALK + 1];
+        if (a.sstride == 0) {  // uniform: already Euclidean (same bits)
+#pragma unroll
+            for (int k = 0; k <= PROP_WALK; ++k) e[k] = s_e[0][wv * PROP_WALK + k];
+        } else {
+            if (wv != 3) raw[PROP_WALK] = s_e[wv + 1][lane];
+#pragma unroll
+            for (int k = 0; k <= PROP_WALK; ++k) e[k] = unerf_s2e(raw[k], a.s_near, a.s_far, a.lin);
+        }
+#pragma unroll
+        for (int q = 0; q < PROP_WALK; ++q) io[q * 64] = e[q] + e[q + 1];
+    }
+#pragma unroll 1
+    for (int q = 0; q < nq; ++q) {
+        // The net as this iteration sees it: read from the kernel arguments at an opaque offset 0 (an empty asm that
+        // takes q), so that its fields and what hangs on them (weight and scaling loads, level base pointers, the layout
+        // conditions) are loaded and computed where they are used, as in the straight-line form.  Hoisted in front of
+        // the loop they stay live across the whole body, spill SGPRs to a VGPR (one v_readlane per use) and cost a
+        // wave per SIMD.  The asm is not volatile and clobbers nothing: the uniform loads stay scalar loads.
+        int zero = 0;
+        asm("" : "+s"(zero) : "s"(q));
+        const unerf_density_net& net = (&a.net)[zero];
+        const float* od = &s_od[0][lane + zero];   // the ray, read here for the same reason (registers, not SGPRs)
+        const float ox = od[0], oy = od[64], oz = od[128], dx = od[192], dy = od[256], dz = od[320];
+        const float t = io[q * 64];
+        float px = ox + dx * t / 2.f;
+        float py = oy + dy * t / 2.f;
+        float pz = oz + dz * t / 2.f;
         const float sel = unerf_normalize_position(px, py, pz, a.box);
-        const uint32_t mask = (1u << a.net.log2T) - 1u;
+        const uint32_t mask = (1u << net.log2T) - 1u;
         float feat[2 * L];
 #pragma unroll
         for (int l = 0; l < L; ++l) {
             float2 f;
-            if (a.net.tcnn_levels && a.net.grid_half) {  // uniform: tcnn layout, half2 rows, tcnn's half arithmetic
-                f = unerf_tcnn_level_feat_half(a.net.table, a.net.tcnn_levels[l], px, py, pz);
-            } else if (a.net.tcnn_levels) {  // uniform: tcnn-layout grid
-                f = unerf_tcnn_level_feat(reinterpret_cast<const float2*>(a.net.table), a.net.tcnn_levels[l], px, py, pz);
-            } else if (l < a.net.n_dense) {  // wave-uniform: coarse level with a dense, x-paired copy
-                f = unerf_dense_level<true>(reinterpret_cast<const float4*>(a.net.dense) + a.net.dense_off[l], a.net.dense_dim[l],
-                                            px, py, pz, a.net.scalings[l]);
+            if (net.tcnn_levels && net.grid_half) {  // uniform: tcnn layout, half2 rows, tcnn's half arithmetic
+                f = unerf_tcnn_level_feat_half(net.table, net.tcnn_levels[l], px, py, pz);
+            } else if (net.tcnn_levels) {  // uniform: tcnn-layout grid
+                f = unerf_tcnn_level_feat(reinterpret_cast<const float2*>(net.table), net.tcnn_levels[l], px, py, pz);
+            } else if (l < net.n_dense) {  // wave-uniform: coarse level with a dense, x-paired copy
+                f = unerf_dense_level<true>(reinterpret_cast<const float4*>(net.dense) + net.dense_off[l], net.dense_dim[l],
+                                            px, py, pz, net.scalings[l]);
             } else {
-                const float2* lvl = reinterpret_cast<const float2*>(a.net.table) + ((size_t)l << a.net.log2T);
-                f = unerf_hash_level<false, true>(lvl, px, py, pz, a.net.scalings[l], mask);
+                const float2* lvl = reinterpret_cast<const float2*>(net.table) + ((size_t)l << net.log2T);
+                f = unerf_hash_level<false, true>(lvl, px, py, pz, net.scalings[l], mask);
             }
             feat[2 * l] = f.x;
             feat[2 * l + 1] = f.y;
         }
-        const float* __restrict__ w1t = a.net.w1t;
-        float o = a.net.b1[0];
+        const float* __restrict__ w1t = net.w1t;
+        float o = net.b1[0];
         if constexpr (HID == 0) {   // use_linear=True: one Linear on the grid features (see prop_density_kernel)
 #pragma unroll
             for (int k = 0; k < 2 * L; ++k) o = fmaf(feat[k], w1t[k], o);
         } else {
         static_assert(HID % 2 == 0, "hidden width must be even");
-        const unerf_v2f* __restrict__ w0p = reinterpret_cast<const unerf_v2f*>(a.net.w0t);
-        const unerf_v2f* __restrict__ b0p = reinterpret_cast<const unerf_v2f*>(a.net.b0);
+        const unerf_v2f* __restrict__ w0p = reinterpret_cast<const unerf_v2f*>(net.w0t);
+        const unerf_v2f* __restrict__ b0p = reinterpret_cast<const unerf_v2f*>(net.b0);
         unerf_v2f h2[HID / 2 + 1];
 #pragma unroll
         for (int j = 0; j < HID / 2; ++j) h2[j] = b0p[j];
@@ -899,15 +941,15 @@ __global__ __launch_bounds__(256) void prop_patch_kernel(PropArgs a) {
         }
         // [probe:prop-mlp-out end]
         }
-        dens = a.avg * unerf_exp(o) * sel;
+        io[q * 64] = a.avg * unerf_exp(o) * sel;
     }
-    if (a.vec4) {  // uniform: n % 4 == 0 and a 16-byte aligned output: the ray's 4 densities leave as one store
-        s_out[lane][wv] = dens;
-        __syncthreads();
-        if (wv == 0 && ray_ok && i_base < a.n)
-            *reinterpret_cast<float4*>(a.out + r * a.n + i_base) = *reinterpret_cast<const float4*>(&s_out[lane][0]);
-    } else if (ray_ok && i < a.n) {
-        a.out[r * a.n + i] = dens;
+    float* out = a.out + r * a.n + i0;
+    if (a.vec4) {  // uniform: n % 4 == 0 (so nq == 4) and a 16-byte aligned output: the ray's 4 densities leave as one store
+        *reinterpret_cast<float4*>(out) = make_float4(io[0], io[64], io[128], io[192]);
+    } else {
+#pragma unroll
+        for (int q = 0; q < PROP_WALK; ++q)
+            if (q < nq) out[q] = io[q * 64];
     }
 }
 
@@ -937,9 +979,12 @@ extern "C" int unerf_proposal_density(const float* origins, const float* directi
     a.img_w = 0; a.pcols = 0; a.nsg = 0; a.nblocks = 0; a.div_nsg = a.div_pcols = make_fastdiv(1); a.g0 = 0; a.first_row = 0;
     a.vec4 = (n % 4 == 0 && ((uintptr_t)density_out & 15u) == 0) ? 1 : 0;
     dim3 grid(blocks_for(R * (int64_t)n, 256)), block(256);
+    // image-ordered rays: the LDS-staged patch kernel; anything else (or UNERF_NO_PATCH_KERNEL): one thread per sample
+    const bool patch_kernel = !getenv("UNERF_NO_PATCH_KERNEL");
     if (image_width >= 8 && R >= 8 * (int64_t)image_width && ray_offset >= 0) {  // at least one full 8-row band
         const int64_t band0 = (ray_offset / image_width) / 8, band1 = ((ray_offset + R - 1) / image_width) / 8;
-        const int64_t pcols = (image_width + 7) / 8, nsg = (n + 3) / 4;
+        const int64_t per_group = patch_kernel ? 4 * PROP_WALK : 4;   // sample indices per workgroup: the kernels' own decode
+        const int64_t pcols = (image_width + 7) / 8, nsg = (n + per_group - 1) / per_group;
         const int64_t blocks = (band1 - band0 + 1) * pcols * nsg;
         if (blocks < (1ll << 31)) {
             a.img_w = (uint32_t)image_width; a.pcols = (uint32_t)pcols; a.nsg = (uint32_t)nsg;
@@ -950,8 +995,7 @@ extern "C" int unerf_proposal_density(const float* origins, const float* directi
         }
     }
     hipStream_t st = (hipStream_t)stream;
-    // image-ordered rays: the LDS-staged patch kernel; anything else: one thread per sample
-    const bool patch = a.img_w != 0 && !getenv("UNERF_NO_PATCH_KERNEL");
+    const bool patch = a.img_w != 0 && patch_kernel;
     // both kernels are built for L in {5, 8} levels x a hidden width in {16, 64, 0}; 0: use_linear=True
     bool built = false;
     with_int<5, 8>(net->L, [&](auto L) {
