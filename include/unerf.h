@@ -1139,6 +1139,42 @@ int unerf_splat_pose_grad(const int32_t* gaussian_ids_sorted, const int32_t* til
                           const float* tangents, const float* background, const float* c2w_host, int H, int W,
                           int block_width, int flags, float* out_grad, float* out_rgb, float* final_T, void* stream);
 
+/* ------------------------------------------------- splat pose Jacobian --
+ * The per-pixel Jacobian of the frame's five channels (UNERF_POSE_CH_*, rows in bit order) with respect to P pose directions,
+ * and its sum of squares (the first-order variance J Sigma J^T when the directions are a basis times a Cholesky factor).  The
+ * pose reaches a pixel linearly through the per-splat tangents, so the [12,P] projection is contracted per splat, before the
+ * walk, which then carries 5 P running tangents instead of 5 x 12.  fp32, no atomics, no global scratch: two calls return the
+ * same bits.
+ *
+ * unerf_splat_pose_tangents_proj: ptangents [N, UNERF_SPLAT_POSE_PROJ_ROWS, PW] from tangents [N,6,12] (unerf_splat_pose_tangents)
+ * and proj_host [12][P] (host, row-major; rows = the entries k = 4 r + c of V[:3,:4]), PW = UNERF_SPLAT_POSE_PW(P):
+ *   rows 0..5: out[q][p] = sum_k tangents[q][k] proj[k][p], summed over k in order;
+ *   row 6    : the tangent of the splat's camera-space depth z = V[2] . (m, 1): sum_c m[c] proj[8 + c][p], m[3] = 1; zeros where
+ *              radii == 0.
+ * Columns P .. PW-1 are written as exact zeros.  ptangents is 8-byte aligned for PW = 6, 16-byte aligned for PW = 12. */
+#define UNERF_SPLAT_POSE_PROJ_ROWS 7
+#define UNERF_SPLAT_POSE_MAX_P 12
+#define UNERF_SPLAT_POSE_PW(P) ((P) <= 6 ? 6 : 12)
+int unerf_splat_pose_tangents_proj(const float* tangents, const float* means3d, const int32_t* radii, int64_t N,
+                                   const float* proj_host, int P, float* ptangents, void* stream);
+
+/* The walk of unerf_splat_pose_grad (same lists, skip and stop decisions, UNERF_SPLAT_POSE_GRAD_BATCH records per staging
+ * round, flags as there) carrying T, pix[3], D = sum_i z_i alpha_i T_i (depths [N]: the unnormalised depth sum of the frame) and
+ * their PW tangents.  compensation [N] or NULL as there (NULL: row 5 of ptangents is not read).  background [3] DEVICE or NULL.
+ * channels: a non-empty set of UNERF_POSE_CH_*; C = its size, rows in bit order; the mask gates stores only, so a row's bits
+ * do not depend on which other channels are asked for.
+ *   R, G, B : value min(pix_c + T bg_c, 1); row live_c (dpix_c + bg_c dT), live_c = pix_c + T bg_c < 1
+ *   ACC     : value A = 1 - T; row -dT
+ *   EDEPTH  : A > 0: value D / A, row dD / A + (D / A) dT / A;  A == 0: value and row exactly 0 (the frame's max(depth) fill
+ *             of such pixels is a quantity of other pixels and is left to the caller)
+ * out_proj [H W, C, P] (the rows), out_var [H W, C] (sum_p row[p]^2 over p < P in order), out_val [H W, C]: each may be NULL,
+ * not all three.  H W == 0 or empty lists are not an error. */
+int unerf_splat_pose_jacobian(const int32_t* gaussian_ids_sorted, const int32_t* tile_bins, const float* xys,
+                              const float* conics, const float* colors, const float* depths, const float* opacities,
+                              const float* compensation, const float* ptangents, const float* background, int P, int H, int W,
+                              int block_width, int flags, int channels, float* out_proj, float* out_var, float* out_val,
+                              void* stream);
+
 #ifdef __cplusplus
 }
 #endif

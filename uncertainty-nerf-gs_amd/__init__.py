@@ -8,9 +8,11 @@ Layout
   fields.py / models.py / ensemble.py
               host-side mirrors of the reference's Field / Model / EnsemblePipeline surface
   metrics.py  ause / auce / psnr / nll (parity metrics)
-  splat.py    frame-level splat pipelines: active_splatfacto_outputs(_batch), pose_gradient_camera (the splat pose gradient)
+  splat.py    frame-level splat pipelines: active_splatfacto_outputs(_batch), pose_gradient_camera (the splat pose gradient),
+              pose_jacobian_camera (the splat pose Jacobian of r, g, b, accumulation and depth, and the pose variance)
   posegrad.py per-pixel camera-pose gradients of a frame (nerfacto and splat models), exported as the reference's
               pose-sensitivity script writes them; tangent_basis / pose_projection: the six pose parameters and a pose
-              covariance for the per-channel pose Jacobian (ops.pose_jacobian, render.pose_jacobian_camera)
+              covariance for the per-channel pose Jacobian (ops.pose_jacobian, render.pose_jacobian_camera); viewmat_jacobian: c2w -> the splat
+              models' world-to-camera rows, differentiated
 """
 __version__ = "0.1.0"

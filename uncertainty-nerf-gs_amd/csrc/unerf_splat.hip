@@ -2628,3 +2628,318 @@ extern "C" int unerf_splat_pose_grad(const int32_t* gaussian_ids_sorted, const i
     else hipLaunchKernelGGL(splat_pose_grad_kernel<false>, grid, block, 0, (hipStream_t)stream, a);
     return unerf_check_launch("splat_pose_grad");
 }
+
+// ======================================================================================
+// per-pixel pose Jacobian of a frame's five channels in P pose directions
+// ======================================================================================
+// The pose reaches a pixel linearly through the per-splat tangents, so the [12,P] projection is contracted per splat
+// (splat_pose_tangents_proj_kernel) and the walk carries PW = 6 or 12 running tangents of each of T, pix[3] and the depth sum D.
+// A row of PW floats is three vectors of PoseVec<PW>::T either way.
+template <int PW> struct PoseVec;
+template <> struct PoseVec<6> { using T = float2; static constexpr int W = 2; };
+template <> struct PoseVec<12> { using T = float4; static constexpr int W = 4; };
+__device__ __forceinline__ float pose_vec_get(const float2& v, int e) { return e == 0 ? v.x : v.y; }
+__device__ __forceinline__ float pose_vec_get(const float4& v, int e) { return e == 0 ? v.x : e == 1 ? v.y : e == 2 ? v.z : v.w; }
+__device__ __forceinline__ void pose_vec_set(float2& v, const float* s) { v = make_float2(s[0], s[1]); }
+__device__ __forceinline__ void pose_vec_set(float4& v, const float* s) { v = make_float4(s[0], s[1], s[2], s[3]); }
+
+struct PoseProjArgs {
+    const float* tan;
+    const float* means;
+    const int32_t* radii;
+    int64_t N;
+    float proj[12 * UNERF_SPLAT_POSE_MAX_P];     // [12][PW], columns P .. PW-1 zero
+    float* out;
+};
+
+template <int PW>
+__global__ __launch_bounds__(256) void splat_pose_tangents_proj_kernel(PoseProjArgs a) {
+    using VT = typename PoseVec<PW>::T;
+    constexpr int VW = PoseVec<PW>::W;
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= a.N) return;
+    VT* orow = reinterpret_cast<VT*>(a.out + i * (int64_t)(UNERF_SPLAT_POSE_PROJ_ROWS * PW));
+    const float4* trow = reinterpret_cast<const float4*>(a.tan + i * (int64_t)(UNERF_SPLAT_POSE_Q * 12));
+#pragma unroll
+    for (int q = 0; q < UNERF_SPLAT_POSE_Q; ++q) {
+        const float4 t0 = trow[q * 3], t1 = trow[q * 3 + 1], t2 = trow[q * 3 + 2];
+        const float t[12] = {t0.x, t0.y, t0.z, t0.w, t1.x, t1.y, t1.z, t1.w, t2.x, t2.y, t2.z, t2.w};
+        float o[PW];
+#pragma unroll
+        for (int p = 0; p < PW; ++p) {
+            float s = t[0] * a.proj[p];
+#pragma unroll
+            for (int k = 1; k < 12; ++k) s += t[k] * a.proj[k * PW + p];
+            o[p] = s;
+        }
+#pragma unroll
+        for (int w = 0; w < 3; ++w) pose_vec_set(orow[q * 3 + w], o + VW * w);
+    }
+    // the depth row: z = V[2] . (m, 1)
+    float o[PW];
+    const bool live = a.radii[i] != 0;
+    const float m0 = a.means[i * 3], m1 = a.means[i * 3 + 1], m2 = a.means[i * 3 + 2];
+#pragma unroll
+    for (int p = 0; p < PW; ++p)
+        o[p] = live ? ((m0 * a.proj[8 * PW + p] + m1 * a.proj[9 * PW + p]) + m2 * a.proj[10 * PW + p]) + a.proj[11 * PW + p] : 0.f;
+#pragma unroll
+    for (int w = 0; w < 3; ++w) pose_vec_set(orow[UNERF_SPLAT_POSE_Q * 3 + w], o + VW * w);
+}
+
+extern "C" int unerf_splat_pose_tangents_proj(const float* tangents, const float* means3d, const int32_t* radii, int64_t N,
+                                              const float* proj_host, int P, float* ptangents, void* stream) {
+    UNERF_REQUIRE(P >= 1 && P <= UNERF_SPLAT_POSE_MAX_P, "splat_pose_tangents_proj: P=%d outside [1,%d]", P, UNERF_SPLAT_POSE_MAX_P);
+    UNERF_REQUIRE(N >= 0, "splat_pose_tangents_proj: bad N");
+    UNERF_REQUIRE(proj_host && (N == 0 || (tangents && means3d && radii && ptangents)), "splat_pose_tangents_proj: null pointer");
+    const int PW = UNERF_SPLAT_POSE_PW(P);
+    UNERF_REQUIRE((reinterpret_cast<uintptr_t>(tangents) & 15) == 0, "splat_pose_tangents_proj: tangents must be 16-byte aligned");
+    UNERF_REQUIRE((reinterpret_cast<uintptr_t>(ptangents) & (PW == 6 ? 7 : 15)) == 0,
+                  "splat_pose_tangents_proj: ptangents must be %d-byte aligned", PW == 6 ? 8 : 16);
+    if (N == 0) return UNERF_OK;
+    PoseProjArgs a;
+    a.tan = tangents; a.means = means3d; a.radii = radii; a.N = N; a.out = ptangents;
+    for (int k = 0; k < 12; ++k)
+        for (int p = 0; p < PW; ++p) a.proj[k * PW + p] = p < P ? proj_host[k * P + p] : 0.f;
+    for (int k = 12 * PW; k < 12 * UNERF_SPLAT_POSE_MAX_P; ++k) a.proj[k] = 0.f;
+    const dim3 grid(blocks_for(N, 256)), block(256);
+    if (PW == 6) hipLaunchKernelGGL(splat_pose_tangents_proj_kernel<6>, grid, block, 0, (hipStream_t)stream, a);
+    else hipLaunchKernelGGL(splat_pose_tangents_proj_kernel<12>, grid, block, 0, (hipStream_t)stream, a);
+    return unerf_check_launch("splat_pose_tangents_proj");
+}
+
+struct PoseJacArgs {
+    const int32_t* ids;
+    const int32_t* bins;
+    const float* xys;
+    const float* conics;
+    const float* colors;
+    const float* depths;
+    const float* opac;
+    const float* comp;
+    const float* ptan;
+    const float* bg;
+    int P, H, W, bw;
+    int cull;
+    int channels, C;
+    float* proj;
+    float* var;
+    float* val;
+};
+
+// one row of a channel: out_proj [P], out_var = sum_p row[p]^2 over p < P in order
+template <int PW>
+__device__ __forceinline__ void pose_jac_store_row(const PoseJacArgs& a, int64_t p, int ci, const float* row, float value) {
+    const int64_t at = p * a.C + ci;
+    if (a.val) a.val[at] = value;
+    if (a.proj) {
+        float* o = a.proj + at * a.P;
+#pragma unroll
+        for (int k = 0; k < PW; ++k)
+            if (k < a.P) o[k] = row[k];
+    }
+    if (a.var) {
+        float s = 0.f;
+#pragma unroll
+        for (int k = 0; k < PW; ++k)
+            if (k < a.P) s += row[k] * row[k];
+        a.var[at] = s;
+    }
+}
+
+// splat_pose_grad_kernel's walk (raster_kernel's decisions on its expressions) with the contracted tangents.
+// A staged record is three 16-byte header words [x, y, o, a | b, c, r, g | b, 1 / comp, z, -] in s_hdr and NT rows of PW floats in
+// s_tan: the tangents of x, y, a, b, c (, comp: antialiased only), z.  <true, 12>: 128 x (48 + 336) B = 48 KiB, with the lists
+// 49.9 KiB (three workgroups of a CU's 160 KiB); <true, 6>: 128 x (48 + 168) B = 27 KiB, with the lists 28.9 KiB (five).
+template <bool AA, int PW>
+__global__ __launch_bounds__(256) void splat_pose_jac_kernel(PoseJacArgs a) {
+    using VT = typename PoseVec<PW>::T;
+    constexpr int VW = PoseVec<PW>::W;
+    constexpr int PG = UNERF_SPLAT_POSE_GRAD_BATCH;
+    constexpr int NT = AA ? 7 : 6;               // tangent rows per splat
+    constexpr int TQ = 3 * NT;                   // ... in vectors
+    constexpr int ZR = AA ? 6 : 5;               // the staged depth row
+    __shared__ float4 s_hdr[PG * 3];
+    __shared__ VT s_tan[PG * TQ];
+    __shared__ int32_t s_gid[PG];
+    __shared__ uint8_t s_mask[PG];
+    __shared__ uint16_t s_list[4][PG];
+    const int bw = a.bw;
+    const int tbx = (a.W + bw - 1) / bw;
+    const int bx = blockIdx.x, by = blockIdx.y;
+    const int tile = by * tbx + bx;
+    const int tr = threadIdx.x;
+    // raster_kernel's thread-to-pixel mapping: a wave is one 8 x 8 quadrant of a 16-wide tile
+    const int ly = bw == 16 ? 8 * (tr >> 7) + ((tr & 63) >> 3) : tr / bw;
+    const int lx = bw == 16 ? 8 * ((tr >> 6) & 1) + (tr & 7) : tr - (tr / bw) * bw;
+    const int i = by * bw + ly, j = bx * bw + lx;
+    const float px = (float)j + 0.5f, py = (float)i + 0.5f;
+    const bool inside = (ly < bw) && (i < a.H) && (j < a.W);
+    const int64_t p = (int64_t)i * a.W + j;
+    bool done = !inside;
+    const int r0 = a.bins[tile * 2], r1 = a.bins[tile * 2 + 1];
+    const int nbatch = (r1 - r0 + PG - 1) / PG;
+    const bool cull = a.cull && bw == 16;
+    const int wv = __builtin_amdgcn_readfirstlane(tr >> 6), lane = tr & 63;
+    const float tile_x0 = (float)(bx * bw), tile_y0 = (float)(by * bw);
+    float T = 1.f, pix[3] = {0.f, 0.f, 0.f}, D = 0.f;
+    float dT[PW], dpix[3][PW], dD[PW];
+#pragma unroll
+    for (int k = 0; k < PW; ++k) { dT[k] = 0.f; dpix[0][k] = 0.f; dpix[1][k] = 0.f; dpix[2][k] = 0.f; dD[k] = 0.f; }
+    for (int b = 0; b < nbatch; ++b) {
+        const int start = r0 + PG * b;
+        if (__syncthreads_count(done ? 1 : 0) >= 256) break;
+        const int bsz = min(PG, r1 - start);
+        if (tr < bsz) {
+            const int g = a.ids[start + tr];
+            const float x = a.xys[g * 2], y = a.xys[g * 2 + 1], op = a.opac[g];
+            const float ca = a.conics[g * 3], cb = a.conics[g * 3 + 1], cc = a.conics[g * 3 + 2];
+            const float* crow = a.colors + (int64_t)g * 3;
+            s_hdr[tr * 3] = make_float4(x, y, op, ca);
+            s_hdr[tr * 3 + 1] = make_float4(cb, cc, crow[0], crow[1]);
+            s_hdr[tr * 3 + 2] = make_float4(crow[2], AA ? 1.f / a.comp[g] : 1.f, a.depths[g], 0.f);
+            s_gid[tr] = g;
+            if (cull) s_mask[tr] = (uint8_t)raster_quad_mask(x, y, op, ca, cb, cc, tile_x0, tile_y0);
+        }
+        __syncthreads();
+        // the tangent rows, one vector per thread and trip (classic: compensation's row, the sixth of seven, is not staged)
+        for (int w = tr; w < bsz * TQ; w += 256) {
+            const int rec = w / TQ, q = w - rec * TQ;
+            const int src = (AA || q < 15) ? q : q + 3;
+            s_tan[w] = reinterpret_cast<const VT*>(a.ptan + (int64_t)s_gid[rec] * (UNERF_SPLAT_POSE_PROJ_ROWS * PW))[src];
+        }
+        __syncthreads();
+        int n_mine = bsz;
+        if (cull) {   // this wave's (order-preserving) list of the staged splats its quadrant can see
+            n_mine = 0;
+#pragma unroll
+            for (int ch = 0; ch < PG / 64; ++ch) {
+                const int t = ch * 64 + lane;
+                const bool need = t < bsz && ((s_mask[t] >> wv) & 1u);
+                const uint64_t mm = __builtin_amdgcn_ballot_w64(need);
+                if (need) s_list[wv][n_mine + __builtin_popcountll(mm & ((1ull << lane) - 1ull))] = (uint16_t)t;
+                n_mine += __builtin_popcountll(mm);
+            }
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+        }
+        for (int k0 = 0; k0 < n_mine; ++k0) {
+            if (__builtin_amdgcn_ballot_w64(!done) == 0ull) break;     // uniform: every pixel of this wave has finished
+            const int t = cull ? (int)s_list[wv][k0] : k0;
+            const float4 h0 = s_hdr[t * 3], h1 = s_hdr[t * 3 + 1], h2 = s_hdr[t * 3 + 2];
+            bool blend = false;
+            float alpha = 0.f, nT = T, dx = 0.f, dy = 0.f;
+            bool clamped = false;
+            if (!done) {
+                // raster_kernel's decisions, on its expressions
+                dx = h0.x - px; dy = h0.y - py;
+                const float op = h0.z, ca = h0.w, cb = h1.x, cc = h1.y;
+                const float sigma = 0.5f * (ca * dx * dx + cc * dy * dy) + cb * dx * dy;
+                const float raw = op * __expf(-sigma);
+                alpha = fminf(0.999f, raw);
+                clamped = raw > 0.999f;
+                if (!(sigma < 0.f || alpha < 1.f / 255.f)) {
+                    nT = T * (1.f - alpha);
+                    if (nT <= 1e-4f) done = true;
+                    else blend = true;
+                }
+            }
+            if (__builtin_amdgcn_ballot_w64(blend) == 0ull) continue;  // uniform: nobody needs this splat's tangents
+            const float ca = h0.w, cb = h1.x, cc = h1.y;
+            const float wx = ca * dx + cb * dy, wy = cc * dy + cb * dx;
+            const float wa = 0.5f * dx * dx, wb = dx * dy, wc = 0.5f * dy * dy;
+            const float col[3] = {h1.z, h1.w, h2.x};
+            const float z = h2.z;
+            const float om = 1.f - alpha, vis = alpha * T;
+            const VT* tq = &s_tan[t * TQ];
+#pragma unroll
+            for (int w = 0; w < 3; ++w) {
+                const VT vx = tq[w], vy = tq[3 + w], va = tq[6 + w], vb = tq[9 + w], vc = tq[12 + w], vz = tq[3 * ZR + w];
+                VT vo = vx;
+                if (AA) vo = tq[15 + w];
+                if (blend) {
+#pragma unroll
+                    for (int e = 0; e < VW; ++e) {
+                        const int k = VW * w + e;
+                        const float sd = (((wx * pose_vec_get(vx, e) + wy * pose_vec_get(vy, e)) + wa * pose_vec_get(va, e))
+                                          + wb * pose_vec_get(vb, e)) + wc * pose_vec_get(vc, e);
+                        const float eo = AA ? pose_vec_get(vo, e) : 0.f;
+                        const float ad = clamped ? 0.f : alpha * (h2.y * eo - sd);
+                        const float wk = ad * T + alpha * dT[k];
+                        dpix[0][k] += col[0] * wk;
+                        dpix[1][k] += col[1] * wk;
+                        dpix[2][k] += col[2] * wk;
+                        dD[k] += z * wk + pose_vec_get(vz, e) * vis;
+                        dT[k] = dT[k] * om - T * ad;
+                    }
+                }
+            }
+            if (blend) {
+                pix[0] += col[0] * vis; pix[1] += col[1] * vis; pix[2] += col[2] * vis;
+                D += z * vis;
+                T = nT;
+            }
+        }
+    }
+    if (!inside) return;
+    int ci = 0;
+    float row[PW];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const float bgc = a.bg ? a.bg[c] : 0.f;
+        const float v = pix[c] + T * bgc;
+        const bool live = v < 1.f;               // clamp(max = 1): a saturated channel has a zero row
+#pragma unroll
+        for (int k = 0; k < PW; ++k) row[k] = live ? dpix[c][k] + bgc * dT[k] : 0.f;
+        if (a.channels & (UNERF_POSE_CH_R << c)) pose_jac_store_row<PW>(a, p, ci++, row, fminf(v, 1.f));
+    }
+    const float A = 1.f - T;
+    if (a.channels & UNERF_POSE_CH_ACC) {
+#pragma unroll
+        for (int k = 0; k < PW; ++k) row[k] = -dT[k];
+        pose_jac_store_row<PW>(a, p, ci++, row, A);
+    }
+    if (a.channels & UNERF_POSE_CH_EDEPTH) {
+        const bool hit = A > 0.f;
+        const float e = hit ? D / A : 0.f;
+#pragma unroll
+        for (int k = 0; k < PW; ++k) row[k] = hit ? dD[k] / A + e * dT[k] / A : 0.f;
+        pose_jac_store_row<PW>(a, p, ci++, row, e);
+    }
+}
+
+extern "C" int unerf_splat_pose_jacobian(const int32_t* gaussian_ids_sorted, const int32_t* tile_bins, const float* xys,
+                                         const float* conics, const float* colors, const float* depths, const float* opacities,
+                                         const float* compensation, const float* ptangents, const float* background, int P,
+                                         int H, int W, int block_width, int flags, int channels, float* out_proj,
+                                         float* out_var, float* out_val, void* stream) {
+    constexpr int ALL = UNERF_POSE_CH_R | UNERF_POSE_CH_G | UNERF_POSE_CH_B | UNERF_POSE_CH_ACC | UNERF_POSE_CH_EDEPTH;
+    UNERF_REQUIRE(gaussian_ids_sorted && tile_bins && xys && conics && colors && depths && opacities && ptangents,
+                  "splat_pose_jacobian: null pointer");
+    UNERF_REQUIRE(P >= 1 && P <= UNERF_SPLAT_POSE_MAX_P, "splat_pose_jacobian: P=%d outside [1,%d]", P, UNERF_SPLAT_POSE_MAX_P);
+    UNERF_REQUIRE(channels != 0, "splat_pose_jacobian: channels is empty");
+    UNERF_REQUIRE((channels & ~ALL) == 0, "splat_pose_jacobian: unknown channel bits %d", channels & ~ALL);
+    UNERF_REQUIRE(out_proj || out_var || out_val, "splat_pose_jacobian: no output asked for (out_proj, out_var and out_val are NULL)");
+    UNERF_REQUIRE((flags & ~UNERF_RASTER_NO_CULL) == 0, "splat_pose_jacobian: unknown flags %d", flags);
+    UNERF_REQUIRE(block_width >= 1 && block_width <= 16, "splat_pose_jacobian: block_width=%d outside [1,16]", block_width);
+    UNERF_REQUIRE(H >= 0 && W >= 0, "splat_pose_jacobian: bad H/W");
+    const int PW = UNERF_SPLAT_POSE_PW(P);
+    UNERF_REQUIRE((reinterpret_cast<uintptr_t>(ptangents) & (PW == 6 ? 7 : 15)) == 0,
+                  "splat_pose_jacobian: ptangents must be %d-byte aligned for P=%d", PW == 6 ? 8 : 16, P);
+    if (H == 0 || W == 0) return UNERF_OK;
+    PoseJacArgs a;
+    a.ids = gaussian_ids_sorted; a.bins = tile_bins; a.xys = xys; a.conics = conics; a.colors = colors; a.depths = depths;
+    a.opac = opacities; a.comp = compensation; a.ptan = ptangents; a.bg = background;
+    a.P = P; a.H = H; a.W = W; a.bw = block_width; a.cull = (flags & UNERF_RASTER_NO_CULL) ? 0 : 1;
+    a.channels = channels; a.C = __builtin_popcount((unsigned)channels);
+    a.proj = out_proj; a.var = out_var; a.val = out_val;
+    const dim3 grid((W + block_width - 1) / block_width, (H + block_width - 1) / block_width), block(256);
+    const hipStream_t st = (hipStream_t)stream;
+    if (PW == 6) {
+        if (compensation) hipLaunchKernelGGL((splat_pose_jac_kernel<true, 6>), grid, block, 0, st, a);
+        else hipLaunchKernelGGL((splat_pose_jac_kernel<false, 6>), grid, block, 0, st, a);
+    } else {
+        if (compensation) hipLaunchKernelGGL((splat_pose_jac_kernel<true, 12>), grid, block, 0, st, a);
+        else hipLaunchKernelGGL((splat_pose_jac_kernel<false, 12>), grid, block, 0, st, a);
+    }
+    return unerf_check_launch("splat_pose_jacobian");
+}

@@ -316,6 +316,9 @@ SIGNATURES = {
     "unerf_splat_depth_sqdiff_batch": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i64, _vp, _vp]),
     "unerf_splat_pose_tangents": (_i, [_vp, _vp, _vp, _i64, _fp, _f, _f, _f, _f, _i, _i, _f, _vp, _vp]),
     "unerf_splat_pose_grad": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _fp, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "unerf_splat_pose_tangents_proj": (_i, [_vp, _vp, _vp, _i64, _fp, _i, _vp, _vp]),
+    "unerf_splat_pose_jacobian": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp,
+                                       _vp]),
 }
 # include/unerf.h: UNERF_METRICS_* (flags of unerf_image_metrics, layout of its row of float64 results)
 METRICS_AUSE, METRICS_AUCE, METRICS_NLL, METRICS_SSIM = 1, 2, 4, 8
@@ -335,6 +338,12 @@ SPLAT_VIEW_FLOATS = 19                            # include/unerf.h: UNERF_SPLAT
 SPLAT_BATCH_MAX_TILES = 11999                     # include/unerf.h: UNERF_SPLAT_BATCH_MAX_TILES
 SPLAT_POSE_Q = 6                                  # include/unerf.h: UNERF_SPLAT_POSE_Q
 SPLAT_POSE_GRAD_BATCH = 128                       # include/unerf.h: UNERF_SPLAT_POSE_GRAD_BATCH
+SPLAT_POSE_PROJ_ROWS, SPLAT_POSE_MAX_P = 7, 12    # include/unerf.h: UNERF_SPLAT_POSE_PROJ_ROWS, UNERF_SPLAT_POSE_MAX_P
+
+
+def splat_pose_pw(P: int) -> int:
+    """include/unerf.h: UNERF_SPLAT_POSE_PW -- the compiled column width of the contracted splat tangents"""
+    return 6 if P <= 6 else 12
 
 _lib: Optional[C.CDLL] = None
 

@@ -1167,12 +1167,62 @@ class SplatfactoModel(nn.Module, _ImageMetrics):
                                           config_sh_degree=self.config.sh_degree, want_rgb=want_rgb, **cam)
 
     def get_pose_jacobians_for_camera(self, camera, **kw):
-        raise NotImplementedError(f"{type(self).__name__}.get_pose_jacobians_for_camera: pose Jacobians are not built for "
-                                  "splat models (get_pose_gradients_for_camera gives d mean_c(rgb) / d camera_to_worlds).")
+        raise NotImplementedError(f"{type(self).__name__}.get_pose_jacobians_for_camera: the ray-sample Jacobian kernel is not "
+                                  "built for splat models; their per-channel pose Jacobian is "
+                                  "get_splat_pose_jacobians_for_camera (the depth channel and its fill differ).")
 
     def get_pose_uncertainty_for_camera(self, camera, pose_cov=None, **kw):
-        raise NotImplementedError(f"{type(self).__name__}.get_pose_uncertainty_for_camera: pose Jacobians are not built for "
-                                  "splat models.")
+        raise NotImplementedError(f"{type(self).__name__}.get_pose_uncertainty_for_camera: the ray-sample Jacobian kernel is not "
+                                  "built for splat models; use get_splat_pose_uncertainty_for_camera.")
+
+    def _splat_pose_jacobian(self, camera, proj, channels, want) -> Dict[str, torch.Tensor]:
+        """splat.pose_jacobian_camera under get_pose_gradients_for_camera's camera checks, SH degree and crop"""
+        c2w, cam = _camera_args(camera, lens=False)
+        n = min(self.step // self.config.sh_degree_interval, self.config.sh_degree) if self.config.sh_degree > 0 else 0
+        gp = {k: v.detach() for k, v in self.gauss_params.items()}
+        crop_ids = None
+        if self.crop_box is not None and not self.training:
+            crop_ids = self.crop_box.within(gp["means"]).squeeze()
+        from . import posegrad
+        return splat.pose_jacobian_camera(gp, c2w, background=self.background_color.to(gp["means"].device),
+                                          proj=proj(posegrad, c2w), channels=channels, want=want, sh_degree=n,
+                                          rasterize_mode=self.config.rasterize_mode, crop_ids=crop_ids,
+                                          config_sh_degree=self.config.sh_degree, **cam)
+
+    @torch.no_grad()
+    def get_splat_pose_jacobians_for_camera(self, camera, channels=ops.POSE_CHANNELS, basis: str = "se3") -> Dict[str, torch.Tensor]:
+        """The per-pixel Jacobian of the frame's channels with respect to the camera pose ->
+        {"jacobian": [H,W,C,6 | 12], "values": [H,W,C]} float32 on the device; the C rows in ops.POSE_CHANNELS order
+        (r, g, b, accumulation, expected_depth).  basis "se3": the six parameters of posegrad.POSE_PARAMS (tx .. angz of
+        c2w . exp(xi), the camera's own frame); "c2w": the twelve entries of camera_to_worlds, row-major 3x4.  r / g / b follow
+        get_pose_gradients_for_camera's rules (their mean over the channels is its quantity).  expected_depth is the frame's
+        depth-sum quotient D / accumulation where something was blended and 0 (value and row) elsewhere: the frame's
+        max(depth) fill is not applied here (get_splat_pose_uncertainty_for_camera's `depth` has it).  Tile lists, skips,
+        stops, the crop and the SH colours held fixed, fp32.  One PERSPECTIVE camera, as get_outputs."""
+        if basis not in ("se3", "c2w"):
+            raise ValueError(f"get_splat_pose_jacobians_for_camera: basis={basis!r} (expected 'se3' or 'c2w')")
+        proj = (lambda pg, c2w: pg.pose_projection(c2w, None)) if basis == "se3" else (lambda pg, c2w: None)
+        out = self._splat_pose_jacobian(camera, proj, channels, ("proj", "val"))
+        return {"jacobian": out["proj"], "values": out["val"]}
+
+    @torch.no_grad()
+    def get_splat_pose_uncertainty_for_camera(self, camera, pose_cov) -> Dict[str, torch.Tensor]:
+        """First-order propagation of a pose covariance to every pixel of a splat frame: var_c = J_c Sigma J_c^T per channel,
+        from one walk (posegrad.pose_projection(c2w, pose_cov) contracted per splat, squared in the walk's epilogue).
+        pose_cov: [6,6] in posegrad.POSE_PARAMS order (the camera's own frame), or a 6-vector of standard deviations.
+        -> [H,W,1] each: rgb_var_pose = mean_c var_c and rgb_std_pose = its root, accumulation_std_pose, depth_std_pose; and
+        rgb [H,W,3], accumulation, depth as the walk blended them -- depth with the frame's fill
+        where(accumulation > 0, D / accumulation, max of the unnormalised depth sums) (activesplatfacto_model.py:319)."""
+        if pose_cov is None:
+            raise ValueError("get_splat_pose_uncertainty_for_camera: pose_cov is needed ([6,6] or 6 standard deviations)")
+        out = self._splat_pose_jacobian(camera, lambda pg, c2w: pg.pose_projection(c2w, pose_cov), ops.POSE_CHANNELS,
+                                        ("var", "val"))
+        var, val = out["var"], out["val"]
+        rgb_var = var[..., :3].mean(dim=-1, keepdim=True)
+        acc, quot = val[..., 3:4], val[..., 4:5]
+        depth = torch.where(acc > 0, quot, (quot * acc).max())
+        return {"rgb_var_pose": rgb_var, "rgb_std_pose": rgb_var.sqrt(), "accumulation_std_pose": var[..., 3:4].sqrt(),
+                "depth_std_pose": var[..., 4:5].sqrt(), "rgb": val[..., :3], "accumulation": acc, "depth": depth}
 
     @torch.no_grad()
     def get_outputs_for_cameras(self, cameras, obb_box=None, max_views: int = 8) -> List[Dict[str, Optional[torch.Tensor]]]:

@@ -2120,6 +2120,53 @@ def splat_pose_grad(gaussian_ids_sorted, tile_bins, xys, conics, colors, opaciti
     return grad, rgb, fT
 
 
+def splat_pose_tangents_proj(tangents, means3d, radii, proj, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """tangents [N,6,12] (splat_pose_tangents), proj [12,P] (rows: the entries of viewmat[:3,:4], 1 <= P <= 12) ->
+    ptangents [N, 7, PW], PW = lib.splat_pose_pw(P): rows 0..5 = tangents . proj, row 6 = the tangent of the splat's
+    camera-space depth (zeros where radii == 0); columns P .. PW-1 are zeros."""
+    lib = _l.load()
+    pt = torch.as_tensor(proj).detach().cpu().to(torch.float32)
+    if pt.dim() != 2 or pt.shape[0] != 12 or not 1 <= pt.shape[1] <= _l.SPLAT_POSE_MAX_P:
+        raise _l.UnerfError(f"splat_pose_tangents_proj: proj must be [12,P] with 1 <= P <= {_l.SPLAT_POSE_MAX_P}, "
+                            f"got {tuple(pt.shape)}")
+    P = int(pt.shape[1])
+    N, dev = means3d.shape[0], means3d.device
+    ptan = torch.empty(N, _l.SPLAT_POSE_PROJ_ROWS, _l.splat_pose_pw(P), device=dev) if out is None else out
+    pj = (C.c_float * (12 * P))(*[float(v) for v in pt.reshape(-1)])
+    with _ctx(dev):
+        _run("splat_pose_tangents_proj", lambda: lib.unerf_splat_pose_tangents_proj(
+            _p(tangents), _p(means3d), _p(radii, torch.int32), N, pj, P, _p(ptan), _stream()))
+    return ptan
+
+
+def splat_pose_jacobian(gaussian_ids_sorted, tile_bins, xys, conics, colors, depths, opacities, ptangents, P: int, H: int,
+                        W: int, background: Optional[torch.Tensor] = None, compensation: Optional[torch.Tensor] = None,
+                        channels=POSE_CHANNELS, want=("proj", "val"), block_width: int = 16, cull: bool = True,
+                        out: Optional[Dict[str, torch.Tensor]] = None) -> Dict[str, torch.Tensor]:
+    """The rasteriser's walk in forward mode with contracted tangents: colors [N,3], depths [N], ptangents [N,7,PW]
+    (splat_pose_tangents_proj of a [12,P] projection) -> the requested of
+      "proj" [H,W,C,P]  the Jacobian rows     "var" [H,W,C] = sum_p proj_p^2     "val" [H,W,C]  the channels' values
+    rows in POSE_CHANNELS order whatever order `channels` names them in: r, g, b (clamped at 1; a clamped channel's row is 0),
+    accumulation = 1 - T, expected_depth = D / accumulation (value and row exactly 0 where nothing was blended).
+    compensation [N] given: "antialiased"; None: "classic".  out: optional preallocated tensors by the same keys."""
+    lib = _l.load()
+    bits = pose_channel_bits(channels)
+    want = (want,) if isinstance(want, str) else tuple(want)
+    if not want or any(w not in ("proj", "var", "val") for w in want):
+        raise _l.UnerfError(f"splat_pose_jacobian: want={want!r} (expected a non-empty subset of 'proj', 'var', 'val')")
+    dev, Cn = xys.device, bin(bits).count("1")
+    shapes = {"proj": (H, W, Cn, P), "var": (H, W, Cn), "val": (H, W, Cn)}
+    res = {k: (out[k] if out is not None and k in out else torch.empty(*shapes[k], device=dev)) for k in want}
+    if gaussian_ids_sorted.numel() == 0:
+        gaussian_ids_sorted = torch.zeros(1, device=dev, dtype=torch.int32)
+    with _ctx(dev):
+        _run("splat_pose_jacobian", lambda: lib.unerf_splat_pose_jacobian(
+            _p(gaussian_ids_sorted, torch.int32), _p(tile_bins, torch.int32), _p(xys), _p(conics), _p(colors), _p(depths),
+            _p(opacities), _p(compensation), _p(ptangents), _p(background), P, H, W, block_width,
+            0 if cull else _l.RASTER_NO_CULL, bits, _p(res.get("proj")), _p(res.get("var")), _p(res.get("val")), _stream()))
+    return res
+
+
 def splat_alpha_normalize(img: torch.Tensor, ch: int, final_T: torch.Tensor, max_ready: Optional[torch.Tensor] = None) -> None:
     """in place on channel `ch` of img [H,W,C].  max_ready: the device float a splat_rasterize(chan_max=(ch, float)) call
     that produced img left the channel's maximum in; None: the maximum is computed here."""

@@ -213,6 +213,27 @@ def _build() -> Dict[str, Any]:
             return fn(camera, **kw)
 
         @torch.no_grad()
+        def get_splat_pose_jacobians_for_camera(self, camera, **kw):
+            """{"jacobian": [H,W,C,6|12], "values": [H,W,C]} of a splat frame (channels=, basis="se3"|"c2w":
+            models.SplatfactoModel.get_splat_pose_jacobians_for_camera); other mirrors raise NotImplementedError"""
+            fn = getattr(self._mirror, "get_splat_pose_jacobians_for_camera", None)
+            if fn is None:
+                raise NotImplementedError(f"{type(self._mirror).__name__} has no splat pose Jacobian (it is not a splat "
+                                          "model; the nerfacto models have get_pose_jacobians_for_camera).")
+            return fn(camera, **kw)
+
+        @torch.no_grad()
+        def get_splat_pose_uncertainty_for_camera(self, camera, pose_cov, **kw):
+            """a pose covariance propagated to per-pixel standard deviations of a splat frame (rgb_std_pose, depth_std_pose,
+            accumulation_std_pose, ...: models.SplatfactoModel.get_splat_pose_uncertainty_for_camera); other mirrors raise
+            NotImplementedError"""
+            fn = getattr(self._mirror, "get_splat_pose_uncertainty_for_camera", None)
+            if fn is None:
+                raise NotImplementedError(f"{type(self._mirror).__name__} has no splat pose Jacobian (it is not a splat "
+                                          "model; the nerfacto models have get_pose_uncertainty_for_camera).")
+            return fn(camera, pose_cov, **kw)
+
+        @torch.no_grad()
         def get_laplace_pose_gradients_for_camera(self, camera, **kw):
             """the pose gradient of a Laplace frame under a named draw of the last layers (generator=, weight_samples=,
             use_deterministic_density=, prior_prec=, n_samples=, eps=, rays_per_launch=, want_rgb=:

@@ -4,7 +4,9 @@ The script perturbs one training camera along one of six pose parameters, render
 torch.autograd.grad(pred_rgb_j.mean(-1), c2w) once per pixel (:153-190).  Here the per-pixel gradients of a frame come from
 one kernel launch per group of rays (models.*.get_pose_gradients_for_camera -> render.pose_gradient_camera ->
 unerf_pose_grad; for the splat models -> splat.pose_gradient_camera -> unerf_splat_pose_tangents + unerf_splat_pose_grad),
-and the files the script leaves behind are written with its names, shapes and dtypes.
+and the files the script leaves behind are written with its names, shapes and dtypes.  tangent_basis / pose_projection give
+the six pose parameters and a pose covariance as a [12,P] projection for the per-channel Jacobians (render.pose_jacobian_camera;
+for the splat models splat.pose_jacobian_camera, which maps it through viewmat_jacobian first).
 
 What differs from the reference: it differentiates whatever arithmetic its checkpoint runs in (half precision for a tcnn
 field); this build differentiates the fp32 field.  Its ground-truth and rendered images are JPEG (mediapy); no JPEG encoder
@@ -90,6 +92,22 @@ def tangent_basis(c2w: torch.Tensor) -> torch.Tensor:
         ek[(k + 1) % 3, (k + 2) % 3] = -1.0
         B[:, :3, 3 + k] = Rm @ ek
     return B.reshape(12, 6)
+
+
+def viewmat_jacobian(c2w: torch.Tensor) -> torch.Tensor:
+    """[12,12] float64: d vec(V[:3,:4]) / d vec(c2w) at c2w (both row-major over 3x4) for the splat models' world-to-camera
+    rows V = [R'^T | -R'^T t], R' = R diag(1,-1,-1) -- the transposition the reference uses, not an inverse, so R need not be
+    orthogonal.  Closed form: V[a][b] = F_a R[b][a] and V[a][3] = -F_a sum_r R[r][a] t[r]."""
+    c2w = torch.as_tensor(c2w).detach().cpu().to(torch.float64)
+    c2w = (c2w[0] if c2w.dim() == 3 else c2w)[:3, :4]
+    F = (1.0, -1.0, -1.0)
+    J = torch.zeros(12, 12, dtype=torch.float64)
+    for a in range(3):
+        for r in range(3):
+            J[4 * a + r, 4 * r + a] = F[a]
+            J[4 * a + 3, 4 * r + a] = -F[a] * c2w[r, 3]
+            J[4 * a + 3, 4 * r + 3] = -F[a] * c2w[r, a]
+    return J
 
 
 def pose_projection(c2w: torch.Tensor, pose_cov=None) -> torch.Tensor:

@@ -200,6 +200,83 @@ def pose_gradient_camera(gp: Dict[str, torch.Tensor], c2w: torch.Tensor, fx: flo
     return (grad, rgb) if want_rgb else grad
 
 
+def pose_jacobian_camera(gp: Dict[str, torch.Tensor], c2w: torch.Tensor, fx: float, fy: float, cx: float, cy: float,
+                         H: int, W: int, background: torch.Tensor, proj=None, channels=ops.POSE_CHANNELS,
+                         want=("proj", "val"), sh_degree: int = 3, rasterize_mode: str = "classic", block_width: int = 16,
+                         crop_ids: Optional[torch.Tensor] = None, config_sh_degree: Optional[int] = None,
+                         tight: bool = True) -> Dict[str, torch.Tensor]:
+    """The per-pixel Jacobian of the frame's channels (ops.POSE_CHANNELS order: r, g, b, accumulation, expected_depth) with
+    respect to the camera pose, for the frame active_splatfacto_outputs renders.  proj [12,P] in c2w entries
+    (row-major 3x4), as posegrad.pose_projection gives it, 1 <= P <= 12; None: the 12 x 12 identity, i.e. d / d c2w.
+    -> the requested of  "proj" [H,W,C,P] = J . proj   "var" [H,W,C] = sum_p proj_p^2   "val" [H,W,C] the channels' values.
+    The projection, shading, count and bin-sort calls are the frame's own; then the per-splat tangent kernel, their contraction
+    with viewmat_jacobian(c2w) @ proj (fp32) and one forward-mode walk.  Held fixed as in pose_gradient_camera.  The expected
+    depth is D / accumulation where something was blended and exactly 0 (value and row) elsewhere: the frame's max(depth) fill
+    of those pixels is left to the caller.  A frame answered with empty_outputs gives zeros, and the background as the r, g, b
+    values."""
+    from . import posegrad
+    _l.require_gpu()
+    dev = gp["means"].device
+    background = background.to(dev, torch.float32)
+    bits = ops.pose_channel_bits(channels)
+    want = (want,) if isinstance(want, str) else tuple(want)
+    if not want or any(w not in ("proj", "var", "val") for w in want):
+        raise _l.UnerfError(f"pose_jacobian_camera: want={want!r} (expected a non-empty subset of 'proj', 'var', 'val')")
+    c2w = c2w.detach().to("cpu", torch.float32)
+    c2w = c2w[0] if c2w.dim() == 3 else c2w
+    M = posegrad.viewmat_jacobian(c2w)
+    if proj is not None:
+        pj = torch.as_tensor(proj).detach().cpu().to(torch.float64)
+        if pj.dim() != 2 or pj.shape[0] != 12 or not 1 <= pj.shape[1] <= _l.SPLAT_POSE_MAX_P:
+            raise _l.UnerfError(f"pose_jacobian_camera: proj must be [12,P] with 1 <= P <= {_l.SPLAT_POSE_MAX_P}, "
+                                f"got {tuple(pj.shape)}")
+        M = M @ pj
+    M = M.to(torch.float32)
+    P = int(M.shape[1])
+    rows = [k for k in range(len(ops.POSE_CHANNELS)) if bits >> k & 1]
+
+    def empty():
+        out = {"proj": torch.zeros(H, W, len(rows), P, device=dev), "var": torch.zeros(H, W, len(rows), device=dev)}
+        val = torch.zeros(H, W, len(ops.POSE_CHANNELS), device=dev)
+        val[..., :3] = background
+        out["val"] = val[..., rows].contiguous()
+        return {k: out[k] for k in want}
+
+    if gp["means"].shape[0] == 0:
+        return empty()
+    if crop_ids is not None:
+        crop_ids = crop_ids.reshape(-1).to(dev)
+        if int(crop_ids.sum().item()) == 0:
+            return empty()
+        gp = {k: v[crop_ids].contiguous() for k, v in gp.items()}
+    means = gp["means"].contiguous()
+    V = viewmat_from_c2w(c2w)
+    if rasterize_mode not in ("classic", "antialiased"):
+        raise ValueError(f"Unknown rasterize_mode: {rasterize_mode}")
+    aa = rasterize_mode == "antialiased"
+    logits = gp["opacities"].reshape(-1).contiguous()
+    pr = ops.splat_project(means, gp["scales"].contiguous(), 1.0, gp["quats"].contiguous(), V[:3], fx, fy, cx, cy, H, W,
+                           block_width, raw=True, opacity_logits=logits if tight else None, antialiased=aa)
+    xys, depths, radii, conics, comp, tiles, cov3d = pr[:7]
+    opac = pr[7] if tight else None
+    count = ops.SplatCount(tiles, defer_copy=True)
+    if config_sh_degree is not None and config_sh_degree <= 0:
+        sh_degree = -1
+    cols, opac2 = ops.splat_shade_inputs(sh_degree, means, c2w[:3, 3], gp["features_dc"].contiguous(),
+                                         gp["features_rest"].contiguous(), None, 0.0, None if tight else logits,
+                                         comp if aa else None, depths)
+    count.start_copy()
+    opac = opac if tight else opac2
+    I, _cum, _keys, gids, bins = ops.splat_bin_sort(xys, depths, radii, tiles, H, W, block_width, want_isect_ids=False,
+                                                    count=count, tight=(conics, opac) if tight else None)
+    if I == 0 and not (tight and bool((radii > 0).any())):
+        return empty()
+    tan = ops.splat_pose_tangents(means, cov3d, radii, V[:3], fx, fy, cx, cy, H, W)
+    ptan = ops.splat_pose_tangents_proj(tan, means, radii, M)
+    return ops.splat_pose_jacobian(gids, bins, xys, conics, cols[:, :3].contiguous(), depths, opac, ptan, P, H, W, background,
+                                   compensation=comp if aa else None, channels=channels, want=want, block_width=block_width)
+
+
 def _per_view(x, B: int, name: str) -> List[float]:
     """a scalar (or one-element tensor) for every view, or B values"""
     t = torch.as_tensor(x).detach().to("cpu", torch.float64).reshape(-1)
