@@ -1175,6 +1175,36 @@ int unerf_splat_pose_jacobian(const int32_t* gaussian_ids_sorted, const int32_t*
                               int block_width, int flags, int channels, float* out_proj, float* out_var, float* out_val,
                               void* stream);
 
+/* ------------------------------------------------- splat pose Jacobian, B views per call --
+ * The two stages above for B cameras of one splat set and one image size in shared launches, in the view-major layout and under
+ * the limits of "splats, B views per call" (1 <= B <= UNERF_SPLAT_MAX_VIEWS, B N < UNERF_SPLAT_MAX_BATCH_SPLATS, intersections
+ * < 2^31, at most UNERF_SPLAT_BATCH_MAX_TILES tiles).  Every view's block is BIT-identical to the single-view entry points with
+ * that view's camera and matrix.
+ *
+ * unerf_splat_pose_ptangents_batch: ptangents [B, N, UNERF_SPLAT_POSE_PROJ_ROWS, PW] <- unerf_splat_pose_tangents followed by
+ * unerf_splat_pose_tangents_proj for every (view, splat), in one launch and without the 288-byte tangent row in memory.
+ * cov3d [B,N,6], radii [B,N]: as unerf_splat_project_batch writes them (rows of splats culled in a view are zero and not read);
+ * views_host: the batch's B records (rows 0..2 of the view matrix, fx, fy are used); proj [B,12,P]: DEVICE floats, one [12][P]
+ * matrix per view (rows = the entries k = 4 r + c of V[:3,:4]) -- the se3 basis in entries of V depends on each view's pose.
+ * Rows 0..5 are summed over k in order, row 6 is the depth row, rows are zero where radii == 0, columns P .. PW-1 are exact
+ * zeros; ptangents aligned as for unerf_splat_pose_tangents_proj.  N == 0 is not an error. */
+int unerf_splat_pose_ptangents_batch(const float* means3d, const float* cov3d, const int32_t* radii, const float* views_host,
+                                     int B, int64_t N, const float* proj, int P, int H, int W, float clip_thresh,
+                                     float* ptangents, void* stream);
+
+/* unerf_splat_pose_jacobian for a batch (grid: tiles x B): gaussian_ids_sorted (ids v N + i) and tile_bins [B,tiles,2] of
+ * unerf_splat_bin_sort_batch; xys, conics, depths, opacities, compensation [B,N,...]; colors [B,N,color_stride] of which the first
+ * three floats of a row are read (color_stride >= 3: the rows of unerf_splat_shade_inputs_batch in place); ptangents
+ * [B,N,7,PW]; background [3] shared.  out_proj [B,HW,C,P], out_var [B,HW,C], out_val [B,HW,C]: each may be NULL, not all three.
+ * Channels, flags, the A == 0 rule, the clamp rules and "the mask gates stores only" as in unerf_splat_pose_jacobian; N enters
+ * the limit check only.  No atomics, no global scratch: two calls return the same bits, and a view's bits depend neither on the
+ * other views nor on its place in the batch.  H W == 0 or empty lists are not an error. */
+int unerf_splat_pose_jacobian_batch(const int32_t* gaussian_ids_sorted, const int32_t* tile_bins, const float* xys,
+                                    const float* conics, const float* colors, int color_stride, const float* depths,
+                                    const float* opacities, const float* compensation, const float* ptangents,
+                                    const float* background, int B, int64_t N, int P, int H, int W, int block_width, int flags,
+                                    int channels, float* out_proj, float* out_var, float* out_val, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2315,7 +2315,76 @@ struct PoseTanArgs {
     float* tan;
 };
 
-// the arithmetic of project_kernel behind `cov3d`, with the tangent of every intermediate for a unit change of V[r][c]
+// the arithmetic of project_kernel behind `cov3d`, with the tangent of every intermediate for a unit change of V[r][c]: the six
+// tangent rows out[q][k], k = 4 r + c, of one live splat (splat_pose_tangents_kernel stores them, splat_pose_ptangents_batch_kernel
+// contracts them in registers)
+__device__ __forceinline__ void pose_tangent_rows(const float* V, float fx, float fy, int H, int W, const float (&m)[4], float tx,
+                                                  float ty, float tz, const float* cv, float (&out)[UNERF_SPLAT_POSE_Q][12]) {
+    const float C3[9] = {cv[0], cv[1], cv[2], cv[1], cv[3], cv[4], cv[2], cv[4], cv[5]};
+    const float lim_x = 1.3f * (0.5f * (float)W / fx), lim_y = 1.3f * (0.5f * (float)H / fy);
+    const float rx = tx / tz, ry = ty / tz;
+    // torch.clamp's derivative: 1 on [-lim, lim] (the ends included), 0 outside
+    const bool clamp_x = rx > lim_x || rx < -lim_x, clamp_y = ry > lim_y || ry < -lim_y;
+    const float cxr = fminf(lim_x, fmaxf(-lim_x, rx)), cyr = fminf(lim_y, fmaxf(-lim_y, ry));
+    const float ex = tz * cxr, ey = tz * cyr;
+    const float rz = 1.f / tz, rz2 = rz * rz;
+    const float J00 = fx * rz, J02 = (-fx * ex) * rz2, J11 = fy * rz, J12 = (-fy * ey) * rz2;
+    float T0[3], T1[3], TV0[3], TV1[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        T0[c] = J00 * V[c] + J02 * V[8 + c];
+        T1[c] = J11 * V[4 + c] + J12 * V[8 + c];
+    }
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        TV0[c] = (T0[0] * C3[c] + T0[1] * C3[3 + c]) + T0[2] * C3[6 + c];
+        TV1[c] = (T1[0] * C3[c] + T1[1] * C3[3 + c]) + T1[2] * C3[6 + c];
+    }
+    const float c00 = (TV0[0] * T0[0] + TV0[1] * T0[1]) + TV0[2] * T0[2];
+    const float c01 = (TV0[0] * T1[0] + TV0[1] * T1[1]) + TV0[2] * T1[2];
+    const float c11 = (TV1[0] * T1[0] + TV1[1] * T1[1]) + TV1[2] * T1[2];
+    const float det_orig = c00 * c11 - c01 * c01;
+    const float ca = c00 + 0.3f, cb = c01, cc = c11 + 0.3f;
+    const float det = ca * cc - cb * cb;
+    const float inv_det = 1.f / det, inv_det2 = inv_det * inv_det;
+    const float ratio = det_orig / det;
+    const float comp = sqrtf(fmaxf(0.f, ratio));
+    const bool comp_live = det_orig > 0.f && ratio > 0.f;
+    const float rw = 1.f / (tz + 1e-6f), rw2 = rw * rw;
+#pragma unroll
+    for (int k = 0; k < 12; ++k) {
+        const int r = k >> 2, c = k & 3;           // the entry V[r][c] moves
+        const float dtx = r == 0 ? m[c] : 0.f, dty = r == 1 ? m[c] : 0.f, dtz = r == 2 ? m[c] : 0.f;
+        const float dex = clamp_x ? dtz * cxr : dtx, dey = clamp_y ? dtz * cyr : dty;
+        const float drz = -rz2 * dtz, drz2 = 2.f * rz * drz;
+        const float dJ00 = fx * drz, dJ11 = fy * drz;
+        const float dJ02 = -fx * (dex * rz2 + ex * drz2), dJ12 = -fy * (dey * rz2 + ey * drz2);
+        float dT0[3], dT1[3];
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            dT0[j] = dJ00 * V[j] + dJ02 * V[8 + j];
+            dT1[j] = dJ11 * V[4 + j] + dJ12 * V[8 + j];
+            if (c == j) {                          // (c == 3: the translation column enters through t only)
+                if (r == 0) dT0[j] += J00;
+                if (r == 1) dT1[j] += J11;
+                if (r == 2) { dT0[j] += J02; dT1[j] += J12; }
+            }
+        }
+        const float dc00 = 2.f * ((TV0[0] * dT0[0] + TV0[1] * dT0[1]) + TV0[2] * dT0[2]);
+        const float dc11 = 2.f * ((TV1[0] * dT1[0] + TV1[1] * dT1[1]) + TV1[2] * dT1[2]);
+        const float dc01 = ((TV1[0] * dT0[0] + TV1[1] * dT0[1]) + TV1[2] * dT0[2])
+                         + ((TV0[0] * dT1[0] + TV0[1] * dT1[1]) + TV0[2] * dT1[2]);
+        const float ddet_orig = (dc00 * c11 + c00 * dc11) - 2.f * c01 * dc01;
+        const float ddet = (dc00 * cc + ca * dc11) - 2.f * cb * dc01;
+        out[0][k] = fx * (dtx * rw - tx * rw2 * dtz);
+        out[1][k] = fy * (dty * rw - ty * rw2 * dtz);
+        out[2][k] = dc11 * inv_det - cc * ddet * inv_det2;
+        out[3][k] = cb * ddet * inv_det2 - dc01 * inv_det;
+        out[4][k] = dc00 * inv_det - ca * ddet * inv_det2;
+        out[5][k] = comp_live ? (0.5f / comp) * (ddet_orig * inv_det - det_orig * ddet * inv_det2) : 0.f;
+    }
+}
+
 __global__ __launch_bounds__(256) void splat_pose_tangents_kernel(PoseTanArgs a) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= a.N) return;
@@ -2330,72 +2399,7 @@ __global__ __launch_bounds__(256) void splat_pose_tangents_kernel(PoseTanArgs a)
     const float tx = ((V[0] * m[0] + V[1] * m[1]) + V[2] * m[2]) + V[3];
     const float ty = ((V[4] * m[0] + V[5] * m[1]) + V[6] * m[2]) + V[7];
     const float tz = ((V[8] * m[0] + V[9] * m[1]) + V[10] * m[2]) + V[11];
-    if (a.radii[i] != 0 && !(tz <= a.clip)) {
-        const float* cv = a.cov3d + i * 6;
-        const float C3[9] = {cv[0], cv[1], cv[2], cv[1], cv[3], cv[4], cv[2], cv[4], cv[5]};
-        const float lim_x = 1.3f * (0.5f * (float)a.W / a.fx), lim_y = 1.3f * (0.5f * (float)a.H / a.fy);
-        const float rx = tx / tz, ry = ty / tz;
-        // torch.clamp's derivative: 1 on [-lim, lim] (the ends included), 0 outside
-        const bool clamp_x = rx > lim_x || rx < -lim_x, clamp_y = ry > lim_y || ry < -lim_y;
-        const float cxr = fminf(lim_x, fmaxf(-lim_x, rx)), cyr = fminf(lim_y, fmaxf(-lim_y, ry));
-        const float ex = tz * cxr, ey = tz * cyr;
-        const float rz = 1.f / tz, rz2 = rz * rz;
-        const float J00 = a.fx * rz, J02 = (-a.fx * ex) * rz2, J11 = a.fy * rz, J12 = (-a.fy * ey) * rz2;
-        float T0[3], T1[3], TV0[3], TV1[3];
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            T0[c] = J00 * V[c] + J02 * V[8 + c];
-            T1[c] = J11 * V[4 + c] + J12 * V[8 + c];
-        }
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            TV0[c] = (T0[0] * C3[c] + T0[1] * C3[3 + c]) + T0[2] * C3[6 + c];
-            TV1[c] = (T1[0] * C3[c] + T1[1] * C3[3 + c]) + T1[2] * C3[6 + c];
-        }
-        const float c00 = (TV0[0] * T0[0] + TV0[1] * T0[1]) + TV0[2] * T0[2];
-        const float c01 = (TV0[0] * T1[0] + TV0[1] * T1[1]) + TV0[2] * T1[2];
-        const float c11 = (TV1[0] * T1[0] + TV1[1] * T1[1]) + TV1[2] * T1[2];
-        const float det_orig = c00 * c11 - c01 * c01;
-        const float ca = c00 + 0.3f, cb = c01, cc = c11 + 0.3f;
-        const float det = ca * cc - cb * cb;
-        const float inv_det = 1.f / det, inv_det2 = inv_det * inv_det;
-        const float ratio = det_orig / det;
-        const float comp = sqrtf(fmaxf(0.f, ratio));
-        const bool comp_live = det_orig > 0.f && ratio > 0.f;
-        const float rw = 1.f / (tz + 1e-6f), rw2 = rw * rw;
-#pragma unroll
-        for (int k = 0; k < 12; ++k) {
-            const int r = k >> 2, c = k & 3;           // the entry V[r][c] moves
-            const float dtx = r == 0 ? m[c] : 0.f, dty = r == 1 ? m[c] : 0.f, dtz = r == 2 ? m[c] : 0.f;
-            const float dex = clamp_x ? dtz * cxr : dtx, dey = clamp_y ? dtz * cyr : dty;
-            const float drz = -rz2 * dtz, drz2 = 2.f * rz * drz;
-            const float dJ00 = a.fx * drz, dJ11 = a.fy * drz;
-            const float dJ02 = -a.fx * (dex * rz2 + ex * drz2), dJ12 = -a.fy * (dey * rz2 + ey * drz2);
-            float dT0[3], dT1[3];
-#pragma unroll
-            for (int j = 0; j < 3; ++j) {
-                dT0[j] = dJ00 * V[j] + dJ02 * V[8 + j];
-                dT1[j] = dJ11 * V[4 + j] + dJ12 * V[8 + j];
-                if (c == j) {                          // (c == 3: the translation column enters through t only)
-                    if (r == 0) dT0[j] += J00;
-                    if (r == 1) dT1[j] += J11;
-                    if (r == 2) { dT0[j] += J02; dT1[j] += J12; }
-                }
-            }
-            const float dc00 = 2.f * ((TV0[0] * dT0[0] + TV0[1] * dT0[1]) + TV0[2] * dT0[2]);
-            const float dc11 = 2.f * ((TV1[0] * dT1[0] + TV1[1] * dT1[1]) + TV1[2] * dT1[2]);
-            const float dc01 = ((TV1[0] * dT0[0] + TV1[1] * dT0[1]) + TV1[2] * dT0[2])
-                             + ((TV0[0] * dT1[0] + TV0[1] * dT1[1]) + TV0[2] * dT1[2]);
-            const float ddet_orig = (dc00 * c11 + c00 * dc11) - 2.f * c01 * dc01;
-            const float ddet = (dc00 * cc + ca * dc11) - 2.f * cb * dc01;
-            out[0][k] = a.fx * (dtx * rw - tx * rw2 * dtz);
-            out[1][k] = a.fy * (dty * rw - ty * rw2 * dtz);
-            out[2][k] = dc11 * inv_det - cc * ddet * inv_det2;
-            out[3][k] = cb * ddet * inv_det2 - dc01 * inv_det;
-            out[4][k] = dc00 * inv_det - ca * ddet * inv_det2;
-            out[5][k] = comp_live ? (0.5f / comp) * (ddet_orig * inv_det - det_orig * ddet * inv_det2) : 0.f;
-        }
-    }
+    if (a.radii[i] != 0 && !(tz <= a.clip)) pose_tangent_rows(V, a.fx, a.fy, a.H, a.W, m, tx, ty, tz, a.cov3d + i * 6, out);
 #pragma unroll
     for (int q = 0; q < UNERF_SPLAT_POSE_Q; ++q)
 #pragma unroll
@@ -2652,6 +2656,20 @@ struct PoseProjArgs {
     float* out;
 };
 
+// The contraction's two statements on the matrix entries MAT(k, p) -- the padded kernel argument of one view here, the view's
+// device matrix in splat_pose_ptangents_batch_kernel: a row's sum over the entries of V in order, and the depth row
+// z = V[2] . (m, 1).  Macros: stated as functions (by accessor, or by pointer and stride) they moved this kernel's registers
+// (74 -> 60 VGPRs, 165 -> 0 spilled SGPRs at PW = 6), and the single-view kernels keep their compiled code.
+#define UNERF_POSE_PROJ_ROW(o, t, MAT)                                              \
+    _Pragma("unroll") for (int p = 0; p < PW; ++p) {                                \
+        float s = (t)[0] * MAT(0, p);                                               \
+        _Pragma("unroll") for (int k = 1; k < 12; ++k) s += (t)[k] * MAT(k, p);     \
+        (o)[p] = s;                                                                 \
+    }
+#define UNERF_POSE_PROJ_DEPTH_ROW(o, live, m0, m1, m2, MAT)                         \
+    _Pragma("unroll") for (int p = 0; p < PW; ++p)                                  \
+        (o)[p] = (live) ? (((m0) * MAT(8, p) + (m1) * MAT(9, p)) + (m2) * MAT(10, p)) + MAT(11, p) : 0.f;
+
 template <int PW>
 __global__ __launch_bounds__(256) void splat_pose_tangents_proj_kernel(PoseProjArgs a) {
     using VT = typename PoseVec<PW>::T;
@@ -2660,18 +2678,13 @@ __global__ __launch_bounds__(256) void splat_pose_tangents_proj_kernel(PoseProjA
     if (i >= a.N) return;
     VT* orow = reinterpret_cast<VT*>(a.out + i * (int64_t)(UNERF_SPLAT_POSE_PROJ_ROWS * PW));
     const float4* trow = reinterpret_cast<const float4*>(a.tan + i * (int64_t)(UNERF_SPLAT_POSE_Q * 12));
+#define UNERF_POSE_MAT_ARG(k, p) a.proj[(k) * PW + (p)]
 #pragma unroll
     for (int q = 0; q < UNERF_SPLAT_POSE_Q; ++q) {
         const float4 t0 = trow[q * 3], t1 = trow[q * 3 + 1], t2 = trow[q * 3 + 2];
         const float t[12] = {t0.x, t0.y, t0.z, t0.w, t1.x, t1.y, t1.z, t1.w, t2.x, t2.y, t2.z, t2.w};
         float o[PW];
-#pragma unroll
-        for (int p = 0; p < PW; ++p) {
-            float s = t[0] * a.proj[p];
-#pragma unroll
-            for (int k = 1; k < 12; ++k) s += t[k] * a.proj[k * PW + p];
-            o[p] = s;
-        }
+        UNERF_POSE_PROJ_ROW(o, t, UNERF_POSE_MAT_ARG)
 #pragma unroll
         for (int w = 0; w < 3; ++w) pose_vec_set(orow[q * 3 + w], o + VW * w);
     }
@@ -2679,9 +2692,8 @@ __global__ __launch_bounds__(256) void splat_pose_tangents_proj_kernel(PoseProjA
     float o[PW];
     const bool live = a.radii[i] != 0;
     const float m0 = a.means[i * 3], m1 = a.means[i * 3 + 1], m2 = a.means[i * 3 + 2];
-#pragma unroll
-    for (int p = 0; p < PW; ++p)
-        o[p] = live ? ((m0 * a.proj[8 * PW + p] + m1 * a.proj[9 * PW + p]) + m2 * a.proj[10 * PW + p]) + a.proj[11 * PW + p] : 0.f;
+    UNERF_POSE_PROJ_DEPTH_ROW(o, live, m0, m1, m2, UNERF_POSE_MAT_ARG)
+#undef UNERF_POSE_MAT_ARG
 #pragma unroll
     for (int w = 0; w < 3; ++w) pose_vec_set(orow[UNERF_SPLAT_POSE_Q * 3 + w], o + VW * w);
 }
@@ -2705,6 +2717,89 @@ extern "C" int unerf_splat_pose_tangents_proj(const float* tangents, const float
     if (PW == 6) hipLaunchKernelGGL(splat_pose_tangents_proj_kernel<6>, grid, block, 0, (hipStream_t)stream, a);
     else hipLaunchKernelGGL(splat_pose_tangents_proj_kernel<12>, grid, block, 0, (hipStream_t)stream, a);
     return unerf_check_launch("splat_pose_tangents_proj");
+}
+
+// The two kernels above for B views in one launch, the 288-byte tangent row kept in registers: one thread per (view, splat)
+// fills the six tangent rows (pose_tangent_rows) and contracts each with the view's [12,P] matrix (UNERF_POSE_PROJ_ROW), the statements
+// and so the bits of the two kernels.  blockIdx.y is the view, so the camera and the matrix are wave-uniform (scalar loads); a
+// culled splat runs the same sums on zeros.
+struct PoseTanCam { float V[12]; float fx, fy; };
+struct PosePtanBatchArgs {
+    const float* means;
+    const float* cov3d;
+    const int32_t* radii;
+    int64_t N;
+    const float* proj;                           // [B,12,P] device
+    int P, H, W;
+    float clip;
+    float* out;
+    PoseTanCam cam[UNERF_SPLAT_MAX_VIEWS];
+};
+
+template <int PW>
+__global__ __launch_bounds__(256) void splat_pose_ptangents_batch_kernel(PosePtanBatchArgs a) {
+    using VT = typename PoseVec<PW>::T;
+    constexpr int VW = PoseVec<PW>::W;
+    const int v = blockIdx.y;
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= a.N) return;
+    const int64_t g = (int64_t)v * a.N + i;
+    const int P = a.P;
+    const float* __restrict__ pj = a.proj + (int64_t)v * 12 * P;
+    const float* V = a.cam[v].V;
+    float out[UNERF_SPLAT_POSE_Q][12];
+#pragma unroll
+    for (int q = 0; q < UNERF_SPLAT_POSE_Q; ++q)
+#pragma unroll
+        for (int k = 0; k < 12; ++k) out[q][k] = 0.f;
+    const float m[4] = {a.means[i * 3], a.means[i * 3 + 1], a.means[i * 3 + 2], 1.f};
+    const float tx = ((V[0] * m[0] + V[1] * m[1]) + V[2] * m[2]) + V[3];
+    const float ty = ((V[4] * m[0] + V[5] * m[1]) + V[6] * m[2]) + V[7];
+    const float tz = ((V[8] * m[0] + V[9] * m[1]) + V[10] * m[2]) + V[11];
+    const bool live = a.radii[g] != 0;
+    if (live && !(tz <= a.clip)) pose_tangent_rows(V, a.cam[v].fx, a.cam[v].fy, a.H, a.W, m, tx, ty, tz, a.cov3d + g * 6, out);
+    VT* orow = reinterpret_cast<VT*>(a.out + g * (int64_t)(UNERF_SPLAT_POSE_PROJ_ROWS * PW));
+    float o[PW];
+#define UNERF_POSE_MAT_VIEW(k, p) ((p) < P ? pj[(k) * P + (p)] : 0.f)   /* uniform */
+#pragma unroll
+    for (int q = 0; q < UNERF_SPLAT_POSE_Q; ++q) {
+        UNERF_POSE_PROJ_ROW(o, out[q], UNERF_POSE_MAT_VIEW)
+#pragma unroll
+        for (int w = 0; w < 3; ++w) pose_vec_set(orow[q * 3 + w], o + VW * w);
+    }
+    UNERF_POSE_PROJ_DEPTH_ROW(o, live, m[0], m[1], m[2], UNERF_POSE_MAT_VIEW)
+#undef UNERF_POSE_MAT_VIEW
+#pragma unroll
+    for (int w = 0; w < 3; ++w) pose_vec_set(orow[UNERF_SPLAT_POSE_Q * 3 + w], o + VW * w);
+}
+
+extern "C" int unerf_splat_pose_ptangents_batch(const float* means3d, const float* cov3d, const int32_t* radii,
+                                                const float* views_host, int B, int64_t N, const float* proj, int P, int H,
+                                                int W, float clip_thresh, float* ptangents, void* stream) {
+    UNERF_REQUIRE(B >= 1 && B <= UNERF_SPLAT_MAX_VIEWS, "splat_pose_ptangents_batch: B=%d outside [1,%d]", B, UNERF_SPLAT_MAX_VIEWS);
+    UNERF_REQUIRE(N >= 0 && (int64_t)B * N < UNERF_SPLAT_MAX_BATCH_SPLATS, "splat_pose_ptangents_batch: B*N = %lld outside [0,2^29)",
+                  (long long)B * (long long)N);
+    UNERF_REQUIRE(P >= 1 && P <= UNERF_SPLAT_POSE_MAX_P, "splat_pose_ptangents_batch: P=%d outside [1,%d]", P, UNERF_SPLAT_POSE_MAX_P);
+    UNERF_REQUIRE(H > 0 && W > 0, "splat_pose_ptangents_batch: bad H/W");
+    UNERF_REQUIRE(views_host, "splat_pose_ptangents_batch: null pointer (views_host)");
+    UNERF_REQUIRE(N == 0 || (means3d && cov3d && radii && proj && ptangents),
+                  "splat_pose_ptangents_batch: null pointer (means3d, cov3d, radii, proj or ptangents)");
+    const int PW = UNERF_SPLAT_POSE_PW(P);
+    UNERF_REQUIRE((reinterpret_cast<uintptr_t>(ptangents) & (PW == 6 ? 7 : 15)) == 0,
+                  "splat_pose_ptangents_batch: ptangents must be %d-byte aligned for P=%d", PW == 6 ? 8 : 16, P);
+    if (N == 0) return UNERF_OK;
+    PosePtanBatchArgs a;
+    a.means = means3d; a.cov3d = cov3d; a.radii = radii; a.N = N; a.proj = proj; a.P = P; a.H = H; a.W = W;
+    a.clip = clip_thresh; a.out = ptangents;
+    for (int v = 0; v < UNERF_SPLAT_MAX_VIEWS; ++v) {
+        const float* r = views_host + (size_t)(v < B ? v : 0) * UNERF_SPLAT_VIEW_FLOATS;
+        for (int k = 0; k < 12; ++k) a.cam[v].V[k] = r[k];
+        a.cam[v].fx = r[12]; a.cam[v].fy = r[13];
+    }
+    const dim3 grid(blocks_for(N, 256), B), block(256);
+    if (PW == 6) hipLaunchKernelGGL(splat_pose_ptangents_batch_kernel<6>, grid, block, 0, (hipStream_t)stream, a);
+    else hipLaunchKernelGGL(splat_pose_ptangents_batch_kernel<12>, grid, block, 0, (hipStream_t)stream, a);
+    return unerf_check_launch("splat_pose_ptangents_batch");
 }
 
 struct PoseJacArgs {
@@ -2750,8 +2845,10 @@ __device__ __forceinline__ void pose_jac_store_row(const PoseJacArgs& a, int64_t
 // A staged record is three 16-byte header words [x, y, o, a | b, c, r, g | b, 1 / comp, z, -] in s_hdr and NT rows of PW floats in
 // s_tan: the tangents of x, y, a, b, c (, comp: antialiased only), z.  <true, 12>: 128 x (48 + 336) B = 48 KiB, with the lists
 // 49.9 KiB (three workgroups of a CU's 160 KiB); <true, 6>: 128 x (48 + 168) B = 27 KiB, with the lists 28.9 KiB (five).
-template <bool AA, int PW>
-__global__ __launch_bounds__(256) void splat_pose_jac_kernel(PoseJacArgs a) {
+// The walk is stated once: a view of a batch is the single-view walk on that view's bins and outputs (the ids of a batch
+// already index the view-major arrays); MULTI only adds the colour rows' stride.
+template <bool AA, int PW, bool MULTI>
+__device__ __forceinline__ void pose_jac_walk(const PoseJacArgs& a, int cstride) {
     using VT = typename PoseVec<PW>::T;
     constexpr int VW = PoseVec<PW>::W;
     constexpr int PG = UNERF_SPLAT_POSE_GRAD_BATCH;
@@ -2793,7 +2890,7 @@ __global__ __launch_bounds__(256) void splat_pose_jac_kernel(PoseJacArgs a) {
             const int g = a.ids[start + tr];
             const float x = a.xys[g * 2], y = a.xys[g * 2 + 1], op = a.opac[g];
             const float ca = a.conics[g * 3], cb = a.conics[g * 3 + 1], cc = a.conics[g * 3 + 2];
-            const float* crow = a.colors + (int64_t)g * 3;
+            const float* crow = a.colors + (int64_t)g * (MULTI ? cstride : 3);
             s_hdr[tr * 3] = make_float4(x, y, op, ca);
             s_hdr[tr * 3 + 1] = make_float4(cb, cc, crow[0], crow[1]);
             s_hdr[tr * 3 + 2] = make_float4(crow[2], AA ? 1.f / a.comp[g] : 1.f, a.depths[g], 0.f);
@@ -2907,6 +3004,31 @@ __global__ __launch_bounds__(256) void splat_pose_jac_kernel(PoseJacArgs a) {
     }
 }
 
+template <bool AA, int PW>
+__global__ __launch_bounds__(256) void splat_pose_jac_kernel(PoseJacArgs a) {
+    pose_jac_walk<AA, PW, false>(a, 3);
+}
+
+// grid: tiles x B.  View blockIdx.z walks tile_bins [v,tiles,2] and writes its own [HW,C(,P)] blocks; the offsets are formed in
+// 64 bits ((v HW + p) C P can pass 2^31).
+struct PoseJacBatchArgs {
+    PoseJacArgs one;
+    int cstride;
+};
+
+template <bool AA, int PW>
+__global__ __launch_bounds__(256) void splat_pose_jac_batch_kernel(PoseJacBatchArgs b) {
+    PoseJacArgs a = b.one;
+    const int64_t v = blockIdx.z;
+    const int64_t tiles = (int64_t)((a.W + a.bw - 1) / a.bw) * ((a.H + a.bw - 1) / a.bw);
+    const int64_t at = v * a.H * a.W * a.C;
+    a.bins += v * tiles * 2;
+    if (a.val) a.val += at;
+    if (a.var) a.var += at;
+    if (a.proj) a.proj += at * a.P;
+    pose_jac_walk<AA, PW, true>(a, b.cstride);
+}
+
 extern "C" int unerf_splat_pose_jacobian(const int32_t* gaussian_ids_sorted, const int32_t* tile_bins, const float* xys,
                                          const float* conics, const float* colors, const float* depths, const float* opacities,
                                          const float* compensation, const float* ptangents, const float* background, int P,
@@ -2942,4 +3064,54 @@ extern "C" int unerf_splat_pose_jacobian(const int32_t* gaussian_ids_sorted, con
         else hipLaunchKernelGGL((splat_pose_jac_kernel<false, 12>), grid, block, 0, st, a);
     }
     return unerf_check_launch("splat_pose_jacobian");
+}
+
+
+extern "C" int unerf_splat_pose_jacobian_batch(const int32_t* gaussian_ids_sorted, const int32_t* tile_bins, const float* xys,
+                                               const float* conics, const float* colors, int color_stride, const float* depths,
+                                               const float* opacities, const float* compensation, const float* ptangents,
+                                               const float* background, int B, int64_t N, int P, int H, int W, int block_width,
+                                               int flags, int channels, float* out_proj, float* out_var, float* out_val,
+                                               void* stream) {
+    constexpr int ALL = UNERF_POSE_CH_R | UNERF_POSE_CH_G | UNERF_POSE_CH_B | UNERF_POSE_CH_ACC | UNERF_POSE_CH_EDEPTH;
+    UNERF_REQUIRE(B >= 1 && B <= UNERF_SPLAT_MAX_VIEWS, "splat_pose_jacobian_batch: B=%d outside [1,%d]", B, UNERF_SPLAT_MAX_VIEWS);
+    UNERF_REQUIRE(N >= 0 && (int64_t)B * N < UNERF_SPLAT_MAX_BATCH_SPLATS, "splat_pose_jacobian_batch: B*N = %lld outside [0,2^29)",
+                  (long long)B * (long long)N);
+    UNERF_REQUIRE(gaussian_ids_sorted && tile_bins && xys && conics && colors && depths && opacities && ptangents,
+                  "splat_pose_jacobian_batch: null pointer (gaussian_ids_sorted, tile_bins, xys, conics, colors, depths, opacities "
+                  "or ptangents)");
+    UNERF_REQUIRE(color_stride >= 3, "splat_pose_jacobian_batch: color_stride=%d below 3", color_stride);
+    UNERF_REQUIRE(P >= 1 && P <= UNERF_SPLAT_POSE_MAX_P, "splat_pose_jacobian_batch: P=%d outside [1,%d]", P, UNERF_SPLAT_POSE_MAX_P);
+    UNERF_REQUIRE(channels != 0, "splat_pose_jacobian_batch: channels is empty");
+    UNERF_REQUIRE((channels & ~ALL) == 0, "splat_pose_jacobian_batch: unknown channel bits %d", channels & ~ALL);
+    UNERF_REQUIRE(out_proj || out_var || out_val,
+                  "splat_pose_jacobian_batch: no output asked for (out_proj, out_var and out_val are NULL)");
+    UNERF_REQUIRE((flags & ~UNERF_RASTER_NO_CULL) == 0, "splat_pose_jacobian_batch: unknown flags %d", flags);
+    UNERF_REQUIRE(block_width >= 1 && block_width <= 16, "splat_pose_jacobian_batch: block_width=%d outside [1,16]", block_width);
+    UNERF_REQUIRE(H >= 0 && W >= 0, "splat_pose_jacobian_batch: bad H/W");
+    const int tbx = (W + block_width - 1) / block_width, tby = (H + block_width - 1) / block_width;
+    UNERF_REQUIRE((int64_t)tbx * tby <= UNERF_SPLAT_BATCH_MAX_TILES, "splat_pose_jacobian_batch: %lld tiles, the batched lists hold %d",
+                  (long long)tbx * tby, UNERF_SPLAT_BATCH_MAX_TILES);
+    const int PW = UNERF_SPLAT_POSE_PW(P);
+    UNERF_REQUIRE((reinterpret_cast<uintptr_t>(ptangents) & (PW == 6 ? 7 : 15)) == 0,
+                  "splat_pose_jacobian_batch: ptangents must be %d-byte aligned for P=%d", PW == 6 ? 8 : 16, P);
+    if (H == 0 || W == 0) return UNERF_OK;
+    PoseJacBatchArgs b;
+    PoseJacArgs& a = b.one;
+    a.ids = gaussian_ids_sorted; a.bins = tile_bins; a.xys = xys; a.conics = conics; a.colors = colors; a.depths = depths;
+    a.opac = opacities; a.comp = compensation; a.ptan = ptangents; a.bg = background;
+    a.P = P; a.H = H; a.W = W; a.bw = block_width; a.cull = (flags & UNERF_RASTER_NO_CULL) ? 0 : 1;
+    a.channels = channels; a.C = __builtin_popcount((unsigned)channels);
+    a.proj = out_proj; a.var = out_var; a.val = out_val;
+    b.cstride = color_stride;
+    const dim3 grid(tbx, tby, B), block(256);
+    const hipStream_t st = (hipStream_t)stream;
+    if (PW == 6) {
+        if (compensation) hipLaunchKernelGGL((splat_pose_jac_batch_kernel<true, 6>), grid, block, 0, st, b);
+        else hipLaunchKernelGGL((splat_pose_jac_batch_kernel<false, 6>), grid, block, 0, st, b);
+    } else {
+        if (compensation) hipLaunchKernelGGL((splat_pose_jac_batch_kernel<true, 12>), grid, block, 0, st, b);
+        else hipLaunchKernelGGL((splat_pose_jac_batch_kernel<false, 12>), grid, block, 0, st, b);
+    }
+    return unerf_check_launch("splat_pose_jacobian_batch");
 }

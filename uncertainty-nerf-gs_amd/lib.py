@@ -319,6 +319,9 @@ SIGNATURES = {
     "unerf_splat_pose_tangents_proj": (_i, [_vp, _vp, _vp, _i64, _fp, _i, _vp, _vp]),
     "unerf_splat_pose_jacobian": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp,
                                        _vp]),
+    "unerf_splat_pose_ptangents_batch": (_i, [_vp, _vp, _vp, _fp, _i, _i64, _vp, _i, _i, _i, _f, _vp, _vp]),
+    "unerf_splat_pose_jacobian_batch": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i64, _i, _i, _i, _i, _i, _i,
+                                             _vp, _vp, _vp, _vp]),
 }
 # include/unerf.h: UNERF_METRICS_* (flags of unerf_image_metrics, layout of its row of float64 results)
 METRICS_AUSE, METRICS_AUCE, METRICS_NLL, METRICS_SSIM = 1, 2, 4, 8

@@ -112,6 +112,32 @@ def _camera_batch(cameras) -> Tuple[torch.Tensor, int, int, List[Any]]:
     return c2w[:, :3, :4], H, W, singles
 
 
+def _splat_camera_batch(cameras, max_views: int, what: str):
+    """The camera checks of the splat models' *_for_cameras methods, before anything touches the GPU: camera_to_worlds
+    [B,3|4,4], PERSPECTIVE only, one image size, fx / fy / cx / cy one value or one per camera, max_views within a batch
+    -> (c2w [B,...], B, H, W, {fx, fy, cx, cy: float64 [B]})."""
+    c2w = torch.as_tensor(cameras.camera_to_worlds)
+    c2w = c2w[None] if c2w.dim() == 2 else c2w
+    B = c2w.shape[0]
+    if not 1 <= max_views <= _lib.SPLAT_MAX_VIEWS:
+        raise ValueError(f"max_views={max_views}: a batch holds 1 to {_lib.SPLAT_MAX_VIEWS} cameras")
+    ctype = getattr(cameras, "camera_type", None)
+    if ctype is not None:
+        types = ({int(v) for v in torch.as_tensor(ctype).reshape(-1)} if torch.is_tensor(ctype)
+                 else {int(getattr(ctype, "value", ctype))})
+        bad = sorted(types - {_lib.CAMERA_PERSPECTIVE})
+        if bad:
+            raise NotImplementedError(f"camera_type {bad[0]}: the splat models project through a pinhole (PERSPECTIVE 1) only")
+    sizes = {(int(h), int(w)) for h, w in zip(torch.as_tensor(cameras.height).reshape(-1).expand(B).tolist(),
+                                              torch.as_tensor(cameras.width).reshape(-1).expand(B).tolist())}
+    if len(sizes) != 1:
+        raise ValueError(f"{what} renders one image size per batch, got {sorted(sizes)} (H, W)")
+    (H, W), = sizes
+    intr = {k: torch.as_tensor(getattr(cameras, k)).detach().to("cpu", torch.float64).reshape(-1).expand(B)
+            for k in ("fx", "fy", "cx", "cy")}
+    return c2w, B, H, W, intr
+
+
 # ------------------------------------------------------------------ configs ----------------
 
 @dataclass
@@ -1217,7 +1243,11 @@ class SplatfactoModel(nn.Module, _ImageMetrics):
             raise ValueError("get_splat_pose_uncertainty_for_camera: pose_cov is needed ([6,6] or 6 standard deviations)")
         out = self._splat_pose_jacobian(camera, lambda pg, c2w: pg.pose_projection(c2w, pose_cov), ops.POSE_CHANNELS,
                                         ("var", "val"))
-        var, val = out["var"], out["val"]
+        return self._splat_pose_uncertainty_dict(out["var"], out["val"])
+
+    @staticmethod
+    def _splat_pose_uncertainty_dict(var: torch.Tensor, val: torch.Tensor) -> Dict[str, torch.Tensor]:
+        """one view's [H,W,5] variances and values -> get_splat_pose_uncertainty_for_camera's dict"""
         rgb_var = var[..., :3].mean(dim=-1, keepdim=True)
         acc, quot = val[..., 3:4], val[..., 4:5]
         depth = torch.where(acc > 0, quot, (quot * acc).max())
@@ -1232,25 +1262,7 @@ class SplatfactoModel(nn.Module, _ImageMetrics):
         cameras one by one (scripts/eval_uncertainty.py:896-904); here they share the per-frame fixed cost.  Images of more
         than lib.SPLAT_BATCH_MAX_TILES tiles (11,999: 2560 x 1440 has 14,400) are rendered camera by camera, with the same
         results."""
-        c2w = torch.as_tensor(cameras.camera_to_worlds)
-        c2w = c2w[None] if c2w.dim() == 2 else c2w
-        B = c2w.shape[0]
-        if not 1 <= max_views <= _lib.SPLAT_MAX_VIEWS:
-            raise ValueError(f"max_views={max_views}: a batch holds 1 to {_lib.SPLAT_MAX_VIEWS} cameras")
-        ctype = getattr(cameras, "camera_type", None)
-        if ctype is not None:
-            types = ({int(v) for v in torch.as_tensor(ctype).reshape(-1)} if torch.is_tensor(ctype)
-                     else {int(getattr(ctype, "value", ctype))})
-            bad = sorted(types - {_lib.CAMERA_PERSPECTIVE})
-            if bad:
-                raise NotImplementedError(f"camera_type {bad[0]}: the splat models project through a pinhole (PERSPECTIVE 1) only")
-        sizes = {(int(h), int(w)) for h, w in zip(torch.as_tensor(cameras.height).reshape(-1).expand(B).tolist(),
-                                                  torch.as_tensor(cameras.width).reshape(-1).expand(B).tolist())}
-        if len(sizes) != 1:
-            raise ValueError(f"get_outputs_for_cameras renders one image size per batch, got {sorted(sizes)} (H, W)")
-        (H, W), = sizes
-        intr = {k: torch.as_tensor(getattr(cameras, k)).detach().to("cpu", torch.float64).reshape(-1).expand(B)
-                for k in ("fx", "fy", "cx", "cy")}
+        c2w, B, H, W, intr = _splat_camera_batch(cameras, max_views, "get_outputs_for_cameras")
         self.set_crop(obb_box)
         n = min(self.step // self.config.sh_degree_interval, self.config.sh_degree) if self.config.sh_degree > 0 else 0
         gp = {k: v.detach() for k, v in self.gauss_params.items()}
@@ -1266,6 +1278,60 @@ class SplatfactoModel(nn.Module, _ImageMetrics):
                 sh_degree=n, rasterize_mode=self.config.rasterize_mode, crop_ids=crop_ids,
                 config_sh_degree=self.config.sh_degree)
         return outs
+
+    def _splat_pose_jacobians(self, cameras, projs, pose_covs, channels, want, max_views: int, what: str):
+        """splat.pose_jacobian_cameras, max_views cameras per call, under get_outputs_for_cameras' camera checks and the
+        single-camera methods' SH degree and crop (the one set_crop / get_outputs_for_camera left)"""
+        c2w, B, H, W, intr = _splat_camera_batch(cameras, max_views, what)
+        if isinstance(pose_covs, (list, tuple)) and len(pose_covs) != B:
+            raise ValueError(f"{what}: {len(pose_covs)} pose covariances for {B} cameras (give one, or one per camera)")
+        n = min(self.step // self.config.sh_degree_interval, self.config.sh_degree) if self.config.sh_degree > 0 else 0
+        gp = {k: v.detach() for k, v in self.gauss_params.items()}
+        crop_ids = None
+        if self.crop_box is not None and not self.training:
+            crop_ids = self.crop_box.within(gp["means"]).squeeze()
+        from . import posegrad
+        outs: List[Dict[str, torch.Tensor]] = []
+        for b0 in range(0, B, max_views):
+            sl = slice(b0, min(b0 + max_views, B))
+            kw = {}
+            # each camera's projection from its own camera_to_worlds as given, as the single-camera methods build it
+            if projs == "se3":
+                kw["projs"] = [posegrad.pose_projection(c2w[v, :3, :4], None) for v in range(sl.start, sl.stop)]
+            elif pose_covs is not None:
+                kw["projs"] = [posegrad.pose_projection(c2w[v, :3, :4], pose_covs[v] if isinstance(pose_covs, (list, tuple))
+                                                        else pose_covs) for v in range(sl.start, sl.stop)]
+            outs += splat.pose_jacobian_cameras(
+                gp, c2w[sl, :3, :4], intr["fx"][sl], intr["fy"][sl], intr["cx"][sl], intr["cy"][sl], H, W,
+                background=self.background_color.to(gp["means"].device), channels=channels, want=want, sh_degree=n,
+                rasterize_mode=self.config.rasterize_mode, crop_ids=crop_ids, config_sh_degree=self.config.sh_degree, **kw)
+        return outs
+
+    @torch.no_grad()
+    def get_splat_pose_jacobians_for_cameras(self, cameras, channels=ops.POSE_CHANNELS, basis: str = "se3",
+                                             max_views: int = 8) -> List[Dict[str, torch.Tensor]]:
+        """get_splat_pose_jacobians_for_camera for every camera of a batch (the cameras of get_outputs_for_cameras:
+        PERSPECTIVE, one image size, intrinsics one value or one per camera), max_views (1 to lib.SPLAT_MAX_VIEWS) cameras per
+        shared launch (splat.pose_jacobian_cameras): element i equals get_splat_pose_jacobians_for_camera(camera i, channels,
+        basis) bit for bit."""
+        if basis not in ("se3", "c2w"):
+            raise ValueError(f"get_splat_pose_jacobians_for_cameras: basis={basis!r} (expected 'se3' or 'c2w')")
+        outs = self._splat_pose_jacobians(cameras, "se3" if basis == "se3" else None, None, channels, ("proj", "val"), max_views,
+                                          "get_splat_pose_jacobians_for_cameras")
+        return [{"jacobian": o["proj"], "values": o["val"]} for o in outs]
+
+    @torch.no_grad()
+    def get_splat_pose_uncertainty_for_cameras(self, cameras, pose_cov, max_views: int = 8) -> List[Dict[str, torch.Tensor]]:
+        """get_splat_pose_uncertainty_for_camera for every camera of a batch, max_views cameras per shared launch: element i
+        equals get_splat_pose_uncertainty_for_camera(camera i, its covariance) bit for bit.  pose_cov: one [6,6] or 6-vector
+        of standard deviations for all cameras, or a list of one per camera.  Each view's depth fill is its OWN maximum of
+        the unnormalised depth sums."""
+        if pose_cov is None:
+            raise ValueError("get_splat_pose_uncertainty_for_cameras: pose_cov is needed ([6,6] or 6 standard deviations, "
+                             "or a list of one per camera)")
+        outs = self._splat_pose_jacobians(cameras, None, pose_cov, ops.POSE_CHANNELS, ("var", "val"), max_views,
+                                          "get_splat_pose_uncertainty_for_cameras")
+        return [self._splat_pose_uncertainty_dict(o["var"], o["val"]) for o in outs]
 
     # -- the two helpers the eval script calls on splat models (scripts/eval_uncertainty.py:321-322, 676-677) --
     def get_gt_img(self, image: torch.Tensor) -> torch.Tensor:

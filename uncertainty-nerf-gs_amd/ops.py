@@ -2223,9 +2223,11 @@ def splat_view_records(viewmats, fxs, fys, cxs, cys, cam_pos) -> "C.Array":
 
 
 def splat_project_batch(means3d, log_scales, raw_quats, views, B: int, H: int, W: int, block_width: int = 16,
-                        clip_thresh: float = 0.01, opacity_logits=None, antialiased: bool = False, glob_scale: float = 1.0):
+                        clip_thresh: float = 0.01, opacity_logits=None, antialiased: bool = False, glob_scale: float = 1.0,
+                        want_cov3d: bool = False):
     """splat_project(raw=True) for the B cameras of `views` (splat_view_records) in one launch -> (xys [B,N,2], depths [B,N],
-    radii, conics [B,N,3], compensation, num_tiles_hit, opacities [B,N] | None); no cov3d"""
+    radii, conics [B,N,3], compensation, num_tiles_hit, opacities [B,N] | None); no cov3d unless want_cov3d, which appends
+    cov3d [B,N,6] (the rows of splats culled in a view are zero) as one more element"""
     lib = _l.load()
     N, dev = means3d.shape[0], means3d.device
     xys = torch.empty(B, N, 2, device=dev)
@@ -2235,11 +2237,14 @@ def splat_project_batch(means3d, log_scales, raw_quats, views, B: int, H: int, W
     comp = torch.empty(B, N, device=dev)
     tiles = torch.empty(B, N, device=dev, dtype=torch.int32)
     opac = torch.empty(B, N, device=dev) if opacity_logits is not None else None
+    cov3d = torch.empty(B, N, 6, device=dev) if want_cov3d else None
     with _ctx(dev):
         _run("splat_project_batch", lambda: lib.unerf_splat_project_batch(
             _p(means3d), _p(log_scales), glob_scale, _p(raw_quats), views, B, H, W, block_width, clip_thresh, N,
             _p(opacity_logits), 1 if antialiased else 0, _p(opac), _p(xys), _p(depths), _p(radii, torch.int32), _p(conics),
-            _p(comp), _p(tiles, torch.int32), None, _stream()))
+            _p(comp), _p(tiles, torch.int32), _p(cov3d), _stream()))
+    if want_cov3d:
+        return xys, depths, radii, conics, comp, tiles, opac, cov3d
     return xys, depths, radii, conics, comp, tiles, opac
 
 
@@ -2359,3 +2364,54 @@ def splat_depth_sqdiff_batch(xys, depths, depth_img: torch.Tensor, ch: int) -> t
         _run("splat_depth_sqdiff_batch", lambda: lib.unerf_splat_depth_sqdiff_batch(
             _p(xys), _p(depths), _p(depth_img), Cn, ch, B, H, W, N, _p(out), _stream()))
     return out
+
+
+def splat_pose_ptangents_batch(means3d, cov3d, radii, views, B: int, projs, H: int, W: int, clip_thresh: float = 0.01,
+                               out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """splat_pose_tangents + splat_pose_tangents_proj for the B cameras of `views` (splat_view_records) in one launch, the
+    raw tangents never in memory: cov3d [B,N,6], radii [B,N] (splat_project_batch(want_cov3d=True)), projs [B,12,P] -- one
+    projection per view, a device tensor is used in place -> ptangents [B, N, 7, PW], each view's block bit-identical to the
+    two single-view calls with that view's camera and matrix."""
+    lib = _l.load()
+    N, dev = means3d.shape[0], means3d.device
+    pj = torch.as_tensor(projs).detach()
+    if pj.dim() != 3 or pj.shape[0] != B or pj.shape[1] != 12 or not 1 <= pj.shape[2] <= _l.SPLAT_POSE_MAX_P:
+        raise _l.UnerfError(f"splat_pose_ptangents_batch: projs must be [{B},12,P] with 1 <= P <= {_l.SPLAT_POSE_MAX_P}, "
+                            f"got {tuple(pj.shape)}")
+    P = int(pj.shape[2])
+    pj = pj.to(dev, torch.float32).contiguous()
+    ptan = torch.empty(B, N, _l.SPLAT_POSE_PROJ_ROWS, _l.splat_pose_pw(P), device=dev) if out is None else out
+    with _ctx(dev):
+        _run("splat_pose_ptangents_batch", lambda: lib.unerf_splat_pose_ptangents_batch(
+            _p(means3d), _p(cov3d), _p(radii, torch.int32), views, B, N, _p(pj), P, H, W, clip_thresh, _p(ptan), _stream()))
+    return ptan
+
+
+def splat_pose_jacobian_batch(gaussian_ids_sorted, tile_bins, xys, conics, colors, depths, opacities, ptangents, P: int, H: int,
+                              W: int, background: Optional[torch.Tensor] = None, compensation: Optional[torch.Tensor] = None,
+                              channels=POSE_CHANNELS, want=("proj", "val"), block_width: int = 16, cull: bool = True,
+                              out: Optional[Dict[str, torch.Tensor]] = None) -> Dict[str, torch.Tensor]:
+    """splat_pose_jacobian for B views (grid: tiles x B) on the lists of splat_bin_sort_batch: xys [B,N,2], colors [B,N,>=3]
+    (the first three floats of a row are read: the rows of splat_shade_inputs_batch serve in place), ptangents [B,N,7,PW] ->
+    the requested of "proj" [B,H,W,C,P], "var" [B,H,W,C], "val" [B,H,W,C]; view v bit-identical to splat_pose_jacobian on
+    that view's own arrays."""
+    lib = _l.load()
+    bits = pose_channel_bits(channels)
+    want = (want,) if isinstance(want, str) else tuple(want)
+    if not want or any(w not in ("proj", "var", "val") for w in want):
+        raise _l.UnerfError(f"splat_pose_jacobian_batch: want={want!r} (expected a non-empty subset of 'proj', 'var', 'val')")
+    dev, Cn = xys.device, bin(bits).count("1")
+    B, N = xys.shape[0], xys.shape[1]
+    if colors.dim() != 3 or colors.shape[2] < 3:
+        raise _l.UnerfError(f"splat_pose_jacobian_batch: colors must be [B,N,>=3], got {tuple(colors.shape)}")
+    shapes = {"proj": (B, H, W, Cn, P), "var": (B, H, W, Cn), "val": (B, H, W, Cn)}
+    res = {k: (out[k] if out is not None and k in out else torch.empty(*shapes[k], device=dev)) for k in want}
+    if gaussian_ids_sorted.numel() == 0:
+        gaussian_ids_sorted = torch.zeros(1, device=dev, dtype=torch.int32)
+    with _ctx(dev):
+        _run("splat_pose_jacobian_batch", lambda: lib.unerf_splat_pose_jacobian_batch(
+            _p(gaussian_ids_sorted, torch.int32), _p(tile_bins, torch.int32), _p(xys), _p(conics), _p(colors),
+            int(colors.shape[2]), _p(depths), _p(opacities), _p(compensation), _p(ptangents), _p(background), B, N, P, H, W,
+            block_width, 0 if cull else _l.RASTER_NO_CULL, bits, _p(res.get("proj")), _p(res.get("var")), _p(res.get("val")),
+            _stream()))
+    return res

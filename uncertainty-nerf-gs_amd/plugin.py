@@ -234,6 +234,28 @@ def _build() -> Dict[str, Any]:
             return fn(camera, pose_cov, **kw)
 
         @torch.no_grad()
+        def get_splat_pose_jacobians_for_cameras(self, cameras, **kw):
+            """get_splat_pose_jacobians_for_camera for a batch of cameras of one image size in shared launches (channels=,
+            basis=, max_views=: models.SplatfactoModel.get_splat_pose_jacobians_for_cameras); other mirrors raise
+            NotImplementedError"""
+            fn = getattr(self._mirror, "get_splat_pose_jacobians_for_cameras", None)
+            if fn is None:
+                raise NotImplementedError(f"{type(self._mirror).__name__} has no splat pose Jacobian (it is not a splat "
+                                          "model; the nerfacto models have get_pose_jacobians_for_camera).")
+            return fn(cameras, **kw)
+
+        @torch.no_grad()
+        def get_splat_pose_uncertainty_for_cameras(self, cameras, pose_cov, **kw):
+            """get_splat_pose_uncertainty_for_camera for a batch of cameras (pose_cov: one for all or a list of one per
+            camera; max_views=: models.SplatfactoModel.get_splat_pose_uncertainty_for_cameras); other mirrors raise
+            NotImplementedError"""
+            fn = getattr(self._mirror, "get_splat_pose_uncertainty_for_cameras", None)
+            if fn is None:
+                raise NotImplementedError(f"{type(self._mirror).__name__} has no splat pose Jacobian (it is not a splat "
+                                          "model; the nerfacto models have get_pose_uncertainty_for_camera).")
+            return fn(cameras, pose_cov, **kw)
+
+        @torch.no_grad()
         def get_laplace_pose_gradients_for_camera(self, camera, **kw):
             """the pose gradient of a Laplace frame under a named draw of the last layers (generator=, weight_samples=,
             use_deterministic_density=, prior_prec=, n_samples=, eps=, rays_per_launch=, want_rgb=:

@@ -110,6 +110,20 @@ def viewmat_jacobian(c2w: torch.Tensor) -> torch.Tensor:
     return J
 
 
+def splat_view_projection(c2w: torch.Tensor, proj=None, max_p: int = 12) -> torch.Tensor:
+    """[12,P] float32: what the splat tangents of ONE view are contracted with -- viewmat_jacobian(c2w) @ proj in float64, then
+    rounded (proj [12,P] in c2w entries, as pose_projection gives it; None: the 12 x 12 identity, i.e. d / d c2w).  One 2-D
+    product per view, so a view's matrix has the same bits alone (splat.pose_jacobian_camera) and in a batch
+    (splat.pose_jacobian_cameras)."""
+    M = viewmat_jacobian(c2w)
+    if proj is not None:
+        pj = torch.as_tensor(proj).detach().cpu().to(torch.float64)
+        if pj.dim() != 2 or pj.shape[0] != 12 or not 1 <= pj.shape[1] <= max_p:
+            raise ValueError(f"proj must be [12,P] with 1 <= P <= {max_p}, got {tuple(pj.shape)}")
+        M = M @ pj
+    return M.to(torch.float32)
+
+
 def pose_projection(c2w: torch.Tensor, pose_cov=None) -> torch.Tensor:
     """[12,P] float64 = tangent_basis(c2w) @ L with L L^T = the [6,6] covariance of the pose parameters (POSE_PARAMS order,
     the camera's own frame): what ops.pose_jacobian(proj=) contracts a d/dc2w row with, so that the sum of squares over P is

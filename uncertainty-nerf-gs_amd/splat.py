@@ -224,23 +224,15 @@ def pose_jacobian_camera(gp: Dict[str, torch.Tensor], c2w: torch.Tensor, fx: flo
         raise _l.UnerfError(f"pose_jacobian_camera: want={want!r} (expected a non-empty subset of 'proj', 'var', 'val')")
     c2w = c2w.detach().to("cpu", torch.float32)
     c2w = c2w[0] if c2w.dim() == 3 else c2w
-    M = posegrad.viewmat_jacobian(c2w)
-    if proj is not None:
-        pj = torch.as_tensor(proj).detach().cpu().to(torch.float64)
-        if pj.dim() != 2 or pj.shape[0] != 12 or not 1 <= pj.shape[1] <= _l.SPLAT_POSE_MAX_P:
-            raise _l.UnerfError(f"pose_jacobian_camera: proj must be [12,P] with 1 <= P <= {_l.SPLAT_POSE_MAX_P}, "
-                                f"got {tuple(pj.shape)}")
-        M = M @ pj
-    M = M.to(torch.float32)
+    try:
+        M = posegrad.splat_view_projection(c2w, proj, _l.SPLAT_POSE_MAX_P)
+    except ValueError as e:
+        raise _l.UnerfError(f"pose_jacobian_camera: {e}") from None
     P = int(M.shape[1])
     rows = [k for k in range(len(ops.POSE_CHANNELS)) if bits >> k & 1]
 
     def empty():
-        out = {"proj": torch.zeros(H, W, len(rows), P, device=dev), "var": torch.zeros(H, W, len(rows), device=dev)}
-        val = torch.zeros(H, W, len(ops.POSE_CHANNELS), device=dev)
-        val[..., :3] = background
-        out["val"] = val[..., rows].contiguous()
-        return {k: out[k] for k in want}
+        return _pose_jacobian_empty(H, W, rows, P, want, background)
 
     if gp["means"].shape[0] == 0:
         return empty()
@@ -275,6 +267,16 @@ def pose_jacobian_camera(gp: Dict[str, torch.Tensor], c2w: torch.Tensor, fx: flo
     ptan = ops.splat_pose_tangents_proj(tan, means, radii, M)
     return ops.splat_pose_jacobian(gids, bins, xys, conics, cols[:, :3].contiguous(), depths, opac, ptan, P, H, W, background,
                                    compensation=comp if aa else None, channels=channels, want=want, block_width=block_width)
+
+
+def _pose_jacobian_empty(H: int, W: int, rows: List[int], P: int, want, background: torch.Tensor) -> Dict[str, torch.Tensor]:
+    """pose_jacobian_camera's answer for a frame that empty_outputs would render: zeros, the background as r, g, b"""
+    dev = background.device
+    out = {"proj": torch.zeros(H, W, len(rows), P, device=dev), "var": torch.zeros(H, W, len(rows), device=dev)}
+    val = torch.zeros(H, W, len(ops.POSE_CHANNELS), device=dev)
+    val[..., :3] = background
+    out["val"] = val[..., rows].contiguous()
+    return {k: out[k] for k in want}
 
 
 def _per_view(x, B: int, name: str) -> List[float]:
@@ -367,3 +369,120 @@ def active_splatfacto_outputs_batch(gp: Dict[str, torch.Tensor], c2ws: torch.Ten
              "uncertainty": img[v, ..., 3:4], "rgb_var": rgb_var[v], "rgb_std": img[v, ..., 3:4], "depth_var": dv[v],
              "depth_std": dstd[v]}
             for v in range(B)]
+
+
+# Cells of benchmarks/splat_pose_jacobian_batch.py in which the shared launches were slower per view than the loop of
+# pose_jacobian_camera by more than that loop's own spread: (H * W at least, views at least) -> the loop is taken.  None of the
+# 48 measured cells is (profiles/r21_splat_pose_jacobian_batch.json).
+POSE_JACOBIAN_BATCH_LOOP_CELLS: tuple = ()
+
+
+def pose_jacobian_cameras(gp: Dict[str, torch.Tensor], c2ws: torch.Tensor, fx, fy, cx, cy, H: int, W: int,
+                          background: torch.Tensor, projs=None, pose_covs=None, channels=ops.POSE_CHANNELS,
+                          want=("proj", "val"), sh_degree: int = 3, rasterize_mode: str = "classic", block_width: int = 16,
+                          crop_ids: Optional[torch.Tensor] = None, config_sh_degree: Optional[int] = None,
+                          tight: bool = True) -> List[Dict[str, torch.Tensor]]:
+    """pose_jacobian_camera for B cameras of one splat set and one image size in shared launches: c2ws [B,3|4,4]; fx, fy, cx,
+    cy: scalars or B values.  Returns B dicts, element v BIT-identical to pose_jacobian_camera with camera v.
+    projs: None (d / d c2w, 12 columns), one [12,P] for all views, or B of them ([B,12,P] or a list); pose_covs instead of
+    projs: None, one [6,6] / 6-vector or B of them -> posegrad.pose_projection(c2w_v, cov) per view (the se3 basis with
+    pose_covs=None is projs=[posegrad.pose_projection(c) for c in c2ws]).  The crop is applied once, the count is read back
+    once (SplatCountBatch), and the views share the project, shade, count, bin-sort, tangent and walk launches; a view that
+    pose_jacobian_camera answers with zeros gets them here.  B <= lib.SPLAT_MAX_VIEWS.  The per-view loop of
+    pose_jacobian_camera is taken (same results) for images of more than lib.SPLAT_BATCH_MAX_TILES tiles, for projections of
+    different widths P in one batch, and in the cells of POSE_JACOBIAN_BATCH_LOOP_CELLS."""
+    from . import posegrad
+    _l.require_gpu()
+    c2ws = c2ws.detach().to("cpu", torch.float32)
+    if c2ws.dim() == 2:
+        c2ws = c2ws[None]
+    B = c2ws.shape[0]
+    if not 1 <= B <= _l.SPLAT_MAX_VIEWS:
+        raise ValueError(f"pose_jacobian_cameras: {B} cameras, a batch holds 1 to {_l.SPLAT_MAX_VIEWS}")
+    fxs, fys, cxs, cys = (_per_view(v, B, n) for v, n in ((fx, "fx"), (fy, "fy"), (cx, "cx"), (cy, "cy")))
+    per_view = pose_view_projections(c2ws, projs, pose_covs)
+    bits = ops.pose_channel_bits(channels)
+    want = (want,) if isinstance(want, str) else tuple(want)
+    if not want or any(w not in ("proj", "var", "val") for w in want):
+        raise _l.UnerfError(f"pose_jacobian_cameras: want={want!r} (expected a non-empty subset of 'proj', 'var', 'val')")
+    if rasterize_mode not in ("classic", "antialiased"):
+        raise ValueError(f"Unknown rasterize_mode: {rasterize_mode}")
+    tiles_n = ((W + block_width - 1) // block_width) * ((H + block_width - 1) // block_width)
+    widths = {int(m.shape[1]) for _, m in per_view}
+    if (tiles_n > _l.SPLAT_BATCH_MAX_TILES or len(widths) != 1
+            or any(H * W >= hw and B >= b for hw, b in POSE_JACOBIAN_BATCH_LOOP_CELLS)):
+        return [pose_jacobian_camera(gp, c2ws[v], fxs[v], fys[v], cxs[v], cys[v], H, W, background, proj=per_view[v][0],
+                                     channels=channels, want=want, sh_degree=sh_degree, rasterize_mode=rasterize_mode,
+                                     block_width=block_width, crop_ids=crop_ids, config_sh_degree=config_sh_degree, tight=tight)
+                for v in range(B)]
+    dev = gp["means"].device
+    background = background.to(dev, torch.float32)
+    (P,) = widths
+    rows = [k for k in range(len(ops.POSE_CHANNELS)) if bits >> k & 1]
+    empties = lambda: [_pose_jacobian_empty(H, W, rows, P, want, background) for _ in range(B)]
+    if gp["means"].shape[0] == 0:
+        return empties()
+    if crop_ids is not None:
+        crop_ids = crop_ids.reshape(-1).to(dev)
+        if int(crop_ids.sum().item()) == 0:
+            return empties()
+        gp = {k: v[crop_ids].contiguous() for k, v in gp.items()}
+    means = gp["means"].contiguous()
+    aa = rasterize_mode == "antialiased"
+    views = ops.splat_view_records([viewmat_from_c2w(c) for c in c2ws], fxs, fys, cxs, cys, [c[:3, 3] for c in c2ws])
+    logits = gp["opacities"].reshape(-1).contiguous()
+    xys, depths, radii, conics, comp, tiles, opac, cov3d = ops.splat_project_batch(
+        means, gp["scales"].contiguous(), gp["quats"].contiguous(), views, B, H, W, block_width,
+        opacity_logits=logits if tight else None, antialiased=aa, want_cov3d=True)
+    count = ops.SplatCountBatch(tiles, radii if tight else None, defer_copy=True)
+    if config_sh_degree is not None and config_sh_degree <= 0:
+        sh_degree = -1
+    cols, opac2 = ops.splat_shade_inputs_batch(sh_degree, means, views, B, gp["features_dc"].contiguous(),
+                                               gp["features_rest"].contiguous(), None, 0.0, None if tight else logits,
+                                               comp if aa else None, depths)
+    count.start_copy()
+    opac = opac if tight else opac2
+    # the tangents do not wait for the count either: they run under its way to the host
+    ptan = ops.splat_pose_ptangents_batch(means, cov3d, radii, views, B, torch.stack([m for _, m in per_view]), H, W)
+    totals, visible, gids, bins = ops.splat_bin_sort_batch(xys, depths, radii, count, H, W, block_width,
+                                                           tight=(conics, opac) if tight else None)
+    empty = [totals[v] == 0 and not (tight and visible[v]) for v in range(B)]
+    if all(empty):
+        return empties()
+    res = ops.splat_pose_jacobian_batch(gids, bins, xys, conics, cols, depths, opac, ptan, P, H, W, background,
+                                        compensation=comp if aa else None, channels=channels, want=want,
+                                        block_width=block_width)
+    return [_pose_jacobian_empty(H, W, rows, P, want, background) if empty[v] else {k: res[k][v] for k in want}
+            for v in range(B)]
+
+
+def pose_view_projections(c2ws: torch.Tensor, projs=None, pose_covs=None) -> List[tuple]:
+    """per view of c2ws [B,3|4,4]: (the [12,P] projection in c2w entries or None, posegrad.splat_view_projection of it) -- the
+    matrices pose_jacobian_camera would be given and would build, camera by camera.  Host only."""
+    from . import posegrad
+    B = c2ws.shape[0]
+    if projs is not None and pose_covs is not None:
+        raise ValueError("pose_jacobian_cameras: give projs or pose_covs, not both")
+
+    def one_per_view(x, single, name: str):
+        if x is None:
+            return [None] * B
+        if not isinstance(x, (list, tuple)):
+            x = torch.as_tensor(x)
+            if single(x):
+                return [x] * B
+            x = list(x)
+        if len(x) != B:
+            raise ValueError(f"pose_jacobian_cameras: {len(x)} {name} for {B} cameras (give one, or one per camera)")
+        return list(x)
+
+    if pose_covs is not None:
+        # one tensor [6] or [6,6] is one covariance for all cameras; a list (or [B,6], [B,6,6] with B != 6) is one per camera
+        covs = one_per_view(pose_covs, lambda t: tuple(t.shape) in ((6,), (6, 6)), "pose_covs")
+        ps = [posegrad.pose_projection(c2ws[v], covs[v]) for v in range(B)]
+    else:
+        ps = one_per_view(projs, lambda t: t.dim() == 2, "projs")
+    try:
+        return [(ps[v], posegrad.splat_view_projection(c2ws[v], ps[v], _l.SPLAT_POSE_MAX_P)) for v in range(B)]
+    except ValueError as e:
+        raise _l.UnerfError(f"pose_jacobian_cameras: {e}") from None
