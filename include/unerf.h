@@ -1205,6 +1205,53 @@ int unerf_splat_pose_jacobian_batch(const int32_t* gaussian_ids_sorted, const in
                                     const float* background, int B, int64_t N, int P, int H, int W, int block_width, int flags,
                                     int channels, float* out_proj, float* out_var, float* out_val, void* stream);
 
+/* ---- Pose normal equations of a frame: the float64 reduction of a per-pixel pose Jacobian -------------------------------
+ * What a consumer of out_proj [R,C,P] (unerf_pose_jacobian, unerf_splat_pose_jacobian) and out_val asks for first, without
+ * holding the frame's Jacobian: over the pixels n and channels c of a frame
+ *   H = sum w J J^T  [P,P]   the Fisher information of the pose under the weights w (Gauss-Newton matrix)
+ *   g = sum w r J    [P]     the gradient of the weighted photometric cost 1/2 sum w r^2, r = val - target
+ *   chi2 = sum w r^2
+ * Per term, everything in float64 formed from the float32 inputs, in THIS product order:
+ *   J_k = (double)jac[n,c,k];  r = (double)val[n,c] - (double)target[n,c];  w = weight ? (double)weight[...] : 1.0
+ *   H_ab = fma(w * J_a, J_b, H_ab) for a <= b;   g_a = fma(w * r, J_a, g_a);   chi2 = fma(w * r, r, chi2)
+ * With val and target both NULL r is not formed: g and chi2 are exactly 0 and only H is accumulated.
+ * A pixel with mask[n] == 0 contributes nothing and is not counted.  A term (n, c) is SKIPPED and counted in n_skipped when
+ * one of jac[n,c,0..P-1], r or w is not finite or w < 0; every other term counts in n_used.
+ *
+ * Geometry: a workgroup of UNERF_POSE_NEQ_THREADS threads owns ONE tile of UNERF_POSE_NEQ_TILE consecutive pixels by the
+ * absolute pixel index pixel_offset + n; thread t takes pixels t, t + THREADS, ... of the tile (UNERF_POSE_NEQ_PPT of them) in
+ * that order, the channels of a pixel in order; then wave butterfly -> LDS -> the four waves in order -> ONE row of
+ * UNERF_POSE_NEQ_WS_ROW(P) doubles of the workspace (the packed upper triangle of H, g, chi2, the two counts).  No atomics.
+ * unerf_pose_normal_eq_finish sums the tile rows [0, ceil(N_frame / TILE)) in one fixed order: thread t of
+ * UNERF_POSE_NEQ_REDUCE_THREADS takes rows t, t + REDUCE_THREADS, ... in order, then butterfly -> LDS -> the waves in order.
+ * So two calls give the same bits, the bits do not depend on how the frame was cut into tile-aligned launch groups or on their
+ * order, and a tile's partial does not depend on the other tiles.  The longest chain of additions an entry passes through:
+ *   PPT * C  +  6  +  (THREADS / 64 - 1)  +  ceil(tiles / REDUCE_THREADS)  +  6  +  (REDUCE_THREADS / 64 - 1)
+ * The caller zero-fills the workspace ONCE per frame, so tiles never written add +0.0.  A tile's row is written whole by the
+ * call that covers it: a group that ends inside a tile must be the frame's last.
+ *
+ *   jac [R,C,P] device floats; val, target [R,C] both or neither; weight NULL | [R] (weight_per_channel == 0) | [R,C];
+ *   mask NULL | [R] bytes; workspace: unerf_pose_normal_eq_workspace_bytes(N_frame, P) bytes, 8-byte aligned.
+ *   out (device): UNERF_POSE_NEQ_ROW(P) doubles = H [P,P] row-major, the lower triangle copied from the upper (exactly
+ *   symmetric) | g [P] | chi2 | n_used | n_skipped.
+ * UNERF_ERR_ARG before any launch, each with its own message: P outside [1, 12]; C outside [1, 5]; R < 0 (R == 0 is
+ * UNERF_OK); exactly one of val / target; pixel_offset negative or not a multiple of the tile; pixel_offset + R > N_frame;
+ * null jac or workspace; workspace_bytes too small.  Instantiated for P <= 6 and P <= 12 (UNERF_SPLAT_POSE_PW). */
+#define UNERF_POSE_NEQ_THREADS 256
+#define UNERF_POSE_NEQ_PPT 4
+#define UNERF_POSE_NEQ_TILE (UNERF_POSE_NEQ_THREADS * UNERF_POSE_NEQ_PPT)
+#define UNERF_POSE_NEQ_REDUCE_THREADS 256
+#define UNERF_POSE_NEQ_MAX_P 12
+#define UNERF_POSE_NEQ_MAX_C 5
+#define UNERF_POSE_NEQ_ROW(P) ((P) * (P) + (P) + 3)
+#define UNERF_POSE_NEQ_WS_ROW(P) ((P) * ((P) + 1) / 2 + (P) + 3)
+size_t unerf_pose_normal_eq_workspace_bytes(int64_t N_frame, int P);
+int unerf_pose_normal_eq_accumulate(const float* jac, const float* val, const float* target, const float* weight,
+                                    int weight_per_channel, const uint8_t* mask, int64_t R, int C, int P, int64_t pixel_offset,
+                                    int64_t N_frame, void* workspace, size_t workspace_bytes, void* stream);
+int unerf_pose_normal_eq_finish(const void* workspace, size_t workspace_bytes, int64_t N_frame, int P, double* out,
+                                void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -14,6 +14,7 @@ Layout
   posegrad.py per-pixel camera-pose gradients of a frame (nerfacto and splat models), exported as the reference's
               pose-sensitivity script writes them; tangent_basis / pose_projection: the six pose parameters and a pose
               covariance for the per-channel pose Jacobian (ops.pose_jacobian, render.pose_jacobian_camera); viewmat_jacobian: c2w -> the splat
-              models' world-to-camera rows, differentiated
+              models' world-to-camera rows, differentiated; pose_step / pose_covariance / apply_pose_step / refine_pose: the
+              Gauss-Newton side of the pose normal equations (ops.pose_normal_eq_*, render / splat.pose_normal_eq_camera)
 """
 __version__ = "0.1.0"

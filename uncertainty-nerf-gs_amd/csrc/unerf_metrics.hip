@@ -24,7 +24,8 @@
 // unerf_image_metrics is the B = 1 case.
 //
 // The rendered images of the same stage (unerf_eval_images_batch: ground truth, prediction, absolute error and the
-// jet-coloured std as final 8-bit planes) are at the end of the file: ei_range / ei_pack.
+// jet-coloured std as final 8-bit planes) follow: ei_range / ei_pack.  The pose normal equations (unerf_pose_normal_eq_*:
+// the float64 reduction of a frame's pose Jacobian, on this file's wave_sum / block_sum) are at the end: pn_accumulate / pn_finish.
 #include "unerf_common.hpp"
 
 #include <algorithm>
@@ -879,5 +880,221 @@ extern "C" int unerf_eval_images_batch(const float* pred, const float* target, c
     }
     hipLaunchKernelGGL(ei_pack_kernel, grid, dim3(EI_THREADS), 0, st, pred, target, sigma, un, unc_lo, unc_span, lut, range, gt8, pred8,
                        err8, std8);
+    return unerf_check_launch(who);
+}
+
+// ---- pose normal equations: H = sum w J J^T, g = sum w r J, chi2 = sum w r^2 over a frame's [R,C,P] Jacobian -------------
+// unerf_pose_normal_eq_* (include/unerf.h states the per-term arithmetic, the geometry and the chain length).  pn_accumulate:
+// one workgroup per tile of PN_TILE consecutive pixels; thread t walks pixels t, t + 256, ... of its tile, so the lanes of a
+// wave stand on consecutive pixels and the wave's loads of one step cover one contiguous run of 64 C P floats: every cache
+// line of it is consumed whole while it is resident.  A row of P floats is read in the widest pieces its alignment allows
+// (VEC = 4 when P % 4 == 0, 2 when P % 2 == 0, the base pointer aligned to match): per wave and step C P / VEC load
+// instructions instead of C P.  The upper triangle of H, g and chi2 stay in registers (PW (PW + 1) / 2 + PW + 1 doubles;
+// columns P .. PW-1 are loaded as zeros and never leave them), then wave butterfly -> LDS -> the four waves in order -> the
+// tile's row.  pn_finish: workgroup e sums entry e of the tile rows in a fixed order and writes it where it belongs in out.
+namespace {
+
+constexpr int PN_THREADS = UNERF_POSE_NEQ_THREADS, PN_WAVES = PN_THREADS / 64, PN_PPT = UNERF_POSE_NEQ_PPT;
+constexpr int PN_TILE = UNERF_POSE_NEQ_TILE, PN_RW = UNERF_POSE_NEQ_REDUCE_THREADS;
+constexpr int PN_MAX_NE = UNERF_POSE_NEQ_WS_ROW(UNERF_POSE_NEQ_MAX_P);
+
+inline int64_t pn_tiles(int64_t n_frame) { return n_frame > 0 ? (n_frame + PN_TILE - 1) / PN_TILE : 0; }
+inline size_t pn_workspace(int64_t n_frame, int P) { return (size_t)pn_tiles(n_frame) * UNERF_POSE_NEQ_WS_ROW(P) * sizeof(double); }
+
+__device__ __forceinline__ uint32_t pn_wave_count(uint32_t v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += (uint32_t)__shfl_xor((int)v, o);
+    return v;
+}
+
+// row P floats of one term -> J[0..PW), zeros behind P
+template <int PW, int VEC>
+__device__ __forceinline__ void pn_load_row(const float* __restrict__ row, int P, float (&J)[PW]) {
+    if constexpr (VEC == 4) {
+#pragma unroll
+        for (int k = 0; k < PW; k += 4) {
+            const float4 v = k < P ? *reinterpret_cast<const float4*>(row + k) : make_float4(0.f, 0.f, 0.f, 0.f);
+            J[k] = v.x; J[k + 1] = v.y;
+            if (k + 2 < PW) { J[k + 2] = v.z; J[k + 3] = v.w; }
+        }
+    } else if constexpr (VEC == 2) {
+#pragma unroll
+        for (int k = 0; k < PW; k += 2) {
+            const float2 v = k < P ? *reinterpret_cast<const float2*>(row + k) : make_float2(0.f, 0.f);
+            J[k] = v.x; J[k + 1] = v.y;
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < PW; ++k) J[k] = k < P ? row[k] : 0.f;
+    }
+}
+
+template <int PW, int VEC>
+__global__ __launch_bounds__(PN_THREADS) void pn_accumulate_kernel(const float* __restrict__ jac, const float* __restrict__ val,
+                                                                   const float* __restrict__ target, const float* __restrict__ weight,
+                                                                   int weight_per_channel, const uint8_t* __restrict__ mask, int64_t R,
+                                                                   int C, int P, double* __restrict__ rows /* the launch's first tile */) {
+    constexpr int NT = PW * (PW + 1) / 2;
+    __shared__ double sh[PN_WAVES][PN_MAX_NE];
+    double h[NT], g[PW], chi2 = 0.0;
+#pragma unroll
+    for (int i = 0; i < NT; ++i) h[i] = 0.0;
+#pragma unroll
+    for (int i = 0; i < PW; ++i) g[i] = 0.0;
+    uint32_t used = 0u, skipped = 0u;
+    const int64_t base = (int64_t)blockIdx.x * PN_TILE + threadIdx.x;
+    for (int i = 0; i < PN_PPT; ++i) {
+        const int64_t n = base + (int64_t)i * PN_THREADS;
+        if (n >= R) break;
+        if (mask && mask[n] == 0) continue;
+        for (int c = 0; c < C; ++c) {
+            const int64_t nc = n * C + c;
+            float Jf[PW];
+            pn_load_row<PW, VEC>(jac + nc * P, P, Jf);
+            bool ok = true;
+#pragma unroll
+            for (int k = 0; k < PW; ++k) ok = ok && mt_finite(Jf[k]);
+            double w = 1.0, r = 0.0;
+            if (weight) {
+                w = (double)weight[weight_per_channel ? nc : n];
+                ok = ok && fabs(w) <= DBL_MAX && !(w < 0.0);
+            }
+            if (val) {
+                r = (double)val[nc] - (double)target[nc];
+                ok = ok && fabs(r) <= DBL_MAX;
+            }
+            if (!ok) { skipped += 1u; continue; }
+            used += 1u;
+            double J[PW];
+#pragma unroll
+            for (int k = 0; k < PW; ++k) J[k] = (double)Jf[k];
+            int idx = 0;
+#pragma unroll
+            for (int a = 0; a < PW; ++a) {
+                const double wa = w * J[a];
+#pragma unroll
+                for (int b = a; b < PW; ++b, ++idx) h[idx] = fma(wa, J[b], h[idx]);
+            }
+            if (val) {
+                const double wr = w * r;
+#pragma unroll
+                for (int a = 0; a < PW; ++a) g[a] = fma(wr, J[a], g[a]);
+                chi2 = fma(wr, r, chi2);
+            }
+        }
+    }
+    // the row's packed order: (a, b) with a <= b < P by rows, g[0..P), chi2, n_used, n_skipped
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int T = P * (P + 1) / 2;
+    {
+        int idx = 0;
+#pragma unroll
+        for (int a = 0; a < PW; ++a) {
+#pragma unroll
+            for (int b = a; b < PW; ++b, ++idx) {
+                if (b < P) {   // uniform; a <= b
+                    const double s = wave_sum(h[idx]);
+                    if (lane == 0) sh[wv][a * P - a * (a - 1) / 2 + (b - a)] = s;
+                }
+            }
+        }
+#pragma unroll
+        for (int a = 0; a < PW; ++a) {
+            if (a < P) {
+                const double s = wave_sum(g[a]);
+                if (lane == 0) sh[wv][T + a] = s;
+            }
+        }
+        const double s = wave_sum(chi2);
+        const uint32_t cu = pn_wave_count(used), cs = pn_wave_count(skipped);
+        if (lane == 0) { sh[wv][T + P] = s; sh[wv][T + P + 1] = (double)cu; sh[wv][T + P + 2] = (double)cs; }
+    }
+    __syncthreads();
+    const int ne = T + P + 3;
+    double* __restrict__ row = rows + (size_t)blockIdx.x * ne;
+    for (int e = threadIdx.x; e < ne; e += PN_THREADS) {
+        double s = sh[0][e];
+#pragma unroll
+        for (int w2 = 1; w2 < PN_WAVES; ++w2) s += sh[w2][e];
+        row[e] = s;
+    }
+}
+
+// workgroup e: entry e of the tile rows [0, tiles) -> its places in out
+__global__ __launch_bounds__(PN_RW) void pn_finish_kernel(const double* __restrict__ rows, int64_t tiles, int P, double* __restrict__ out) {
+    __shared__ double red[PN_RW / 64];
+    const int T = P * (P + 1) / 2, ne = T + P + 3, e = blockIdx.x;
+    double s = 0.0;
+    for (int64_t t = threadIdx.x; t < tiles; t += PN_RW) s += rows[(size_t)t * ne + e];
+    s = block_sum<PN_RW / 64>(s, red);
+    if (threadIdx.x != 0) return;
+    if (e < T) {
+        int a = 0, first = 0;               // row a of the packed triangle starts at first and holds P - a entries
+        while (e >= first + (P - a)) { first += P - a; ++a; }
+        const int b = a + (e - first);
+        out[a * P + b] = s;
+        out[b * P + a] = s;
+    } else {
+        out[P * P + (e - T)] = s;           // g, chi2, n_used, n_skipped follow H in the row's order
+    }
+}
+
+template <int PW>
+void pn_launch(int vec, dim3 grid, hipStream_t st, const float* jac, const float* val, const float* target, const float* weight, int wpc,
+               const uint8_t* mask, int64_t R, int C, int P, double* rows) {
+    if (vec == 4)
+        hipLaunchKernelGGL((pn_accumulate_kernel<PW, 4>), grid, dim3(PN_THREADS), 0, st, jac, val, target, weight, wpc, mask, R, C, P, rows);
+    else if (vec == 2)
+        hipLaunchKernelGGL((pn_accumulate_kernel<PW, 2>), grid, dim3(PN_THREADS), 0, st, jac, val, target, weight, wpc, mask, R, C, P, rows);
+    else
+        hipLaunchKernelGGL((pn_accumulate_kernel<PW, 1>), grid, dim3(PN_THREADS), 0, st, jac, val, target, weight, wpc, mask, R, C, P, rows);
+}
+
+}  // namespace
+
+extern "C" size_t unerf_pose_normal_eq_workspace_bytes(int64_t N_frame, int P) {
+    if (P < 1 || P > UNERF_POSE_NEQ_MAX_P) return 0;
+    return pn_workspace(N_frame, P);
+}
+
+extern "C" int unerf_pose_normal_eq_accumulate(const float* jac, const float* val, const float* target, const float* weight,
+                                               int weight_per_channel, const uint8_t* mask, int64_t R, int C, int P, int64_t pixel_offset,
+                                               int64_t N_frame, void* workspace, size_t workspace_bytes, void* stream) {
+    const char* who = "pose_normal_eq";
+    UNERF_REQUIRE(P >= 1 && P <= UNERF_POSE_NEQ_MAX_P, "%s: P = %d (expected 1..%d)", who, P, UNERF_POSE_NEQ_MAX_P);
+    UNERF_REQUIRE(C >= 1 && C <= UNERF_POSE_NEQ_MAX_C, "%s: C = %d (expected 1..%d)", who, C, UNERF_POSE_NEQ_MAX_C);
+    UNERF_REQUIRE(R >= 0, "%s: R = %lld", who, (long long)R);
+    UNERF_REQUIRE((val == nullptr) == (target == nullptr), "%s: val and target go together (%s is missing)", who, val ? "target" : "val");
+    UNERF_REQUIRE(pixel_offset >= 0 && pixel_offset % PN_TILE == 0, "%s: pixel_offset = %lld (expected a non-negative multiple of the tile, %d)",
+                  who, (long long)pixel_offset, PN_TILE);
+    UNERF_REQUIRE(N_frame >= 0 && R <= N_frame && pixel_offset <= N_frame - R, "%s: pixel_offset + R = %lld + %lld exceeds N_frame = %lld", who,
+                  (long long)pixel_offset, (long long)R, (long long)N_frame);
+    if (R == 0) return UNERF_OK;
+    UNERF_REQUIRE(jac && workspace, "%s: null pointer (jac / workspace) with R > 0", who);
+    UNERF_REQUIRE(workspace_bytes >= pn_workspace(N_frame, P), "%s: workspace of %zu bytes, unerf_pose_normal_eq_workspace_bytes(%lld, %d) = %zu",
+                  who, workspace_bytes, (long long)N_frame, P, pn_workspace(N_frame, P));
+    UNERF_REQUIRE(((uintptr_t)workspace & 7) == 0 && ((uintptr_t)jac & 3) == 0, "%s: workspace must be 8-byte, jac 4-byte aligned", who);
+    const int64_t nblk = (R + PN_TILE - 1) / PN_TILE;
+    UNERF_REQUIRE(nblk < ((int64_t)1 << 31), "%s: R = %lld (more than 2^31 tiles)", who, (long long)R);
+    const int vec = (P % 4 == 0 && ((uintptr_t)jac & 15) == 0) ? 4 : (P % 2 == 0 && ((uintptr_t)jac & 7) == 0) ? 2 : 1;
+    double* rows = (double*)workspace + (size_t)(pixel_offset / PN_TILE) * UNERF_POSE_NEQ_WS_ROW(P);
+    const dim3 grid((uint32_t)nblk);
+    hipStream_t st = (hipStream_t)stream;
+    if (P <= 6) pn_launch<6>(vec, grid, st, jac, val, target, weight, weight_per_channel, mask, R, C, P, rows);
+    else pn_launch<12>(vec, grid, st, jac, val, target, weight, weight_per_channel, mask, R, C, P, rows);
+    return unerf_check_launch(who);
+}
+
+extern "C" int unerf_pose_normal_eq_finish(const void* workspace, size_t workspace_bytes, int64_t N_frame, int P, double* out,
+                                           void* stream) {
+    const char* who = "pose_normal_eq_finish";
+    UNERF_REQUIRE(P >= 1 && P <= UNERF_POSE_NEQ_MAX_P, "%s: P = %d (expected 1..%d)", who, P, UNERF_POSE_NEQ_MAX_P);
+    UNERF_REQUIRE(N_frame >= 0, "%s: N_frame = %lld", who, (long long)N_frame);
+    UNERF_REQUIRE(out && (workspace || N_frame == 0), "%s: null pointer (workspace / out)", who);
+    UNERF_REQUIRE(workspace_bytes >= pn_workspace(N_frame, P), "%s: workspace of %zu bytes, unerf_pose_normal_eq_workspace_bytes(%lld, %d) = %zu",
+                  who, workspace_bytes, (long long)N_frame, P, pn_workspace(N_frame, P));
+    UNERF_REQUIRE(((uintptr_t)workspace & 7) == 0 && ((uintptr_t)out & 7) == 0, "%s: workspace / out must be 8-byte aligned", who);
+    hipLaunchKernelGGL(pn_finish_kernel, dim3(UNERF_POSE_NEQ_WS_ROW(P)), dim3(PN_RW), 0, (hipStream_t)stream, (const double*)workspace,
+                       pn_tiles(N_frame), P, out);
     return unerf_check_launch(who);
 }

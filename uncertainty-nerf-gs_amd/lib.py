@@ -322,6 +322,9 @@ SIGNATURES = {
     "unerf_splat_pose_ptangents_batch": (_i, [_vp, _vp, _vp, _fp, _i, _i64, _vp, _i, _i, _i, _f, _vp, _vp]),
     "unerf_splat_pose_jacobian_batch": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i64, _i, _i, _i, _i, _i, _i,
                                              _vp, _vp, _vp, _vp]),
+    "unerf_pose_normal_eq_workspace_bytes": (C.c_size_t, [_i64, _i]),
+    "unerf_pose_normal_eq_accumulate": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _i64, _i, _i, _i64, _i64, _vp, C.c_size_t, _vp]),
+    "unerf_pose_normal_eq_finish": (_i, [_vp, C.c_size_t, _i64, _i, _vp, _vp]),
 }
 # include/unerf.h: UNERF_METRICS_* (flags of unerf_image_metrics, layout of its row of float64 results)
 METRICS_AUSE, METRICS_AUCE, METRICS_NLL, METRICS_SSIM = 1, 2, 4, 8
@@ -342,6 +345,29 @@ SPLAT_BATCH_MAX_TILES = 11999                     # include/unerf.h: UNERF_SPLAT
 SPLAT_POSE_Q = 6                                  # include/unerf.h: UNERF_SPLAT_POSE_Q
 SPLAT_POSE_GRAD_BATCH = 128                       # include/unerf.h: UNERF_SPLAT_POSE_GRAD_BATCH
 SPLAT_POSE_PROJ_ROWS, SPLAT_POSE_MAX_P = 7, 12    # include/unerf.h: UNERF_SPLAT_POSE_PROJ_ROWS, UNERF_SPLAT_POSE_MAX_P
+# include/unerf.h: UNERF_POSE_NEQ_* (geometry of unerf_pose_normal_eq_accumulate / _finish)
+POSE_NEQ_THREADS, POSE_NEQ_PPT, POSE_NEQ_REDUCE_THREADS = 256, 4, 256
+POSE_NEQ_TILE = POSE_NEQ_THREADS * POSE_NEQ_PPT
+POSE_NEQ_MAX_P, POSE_NEQ_MAX_C = 12, 5
+
+
+def pose_neq_row(P: int) -> int:
+    """include/unerf.h: UNERF_POSE_NEQ_ROW -- H [P,P] | g [P] | chi2 | n_used | n_skipped"""
+    return P * P + P + 3
+
+
+def pose_neq_ws_row(P: int) -> int:
+    """include/unerf.h: UNERF_POSE_NEQ_WS_ROW -- a tile's row of partials: the packed upper triangle of H, g, chi2, two counts"""
+    return P * (P + 1) // 2 + P + 3
+
+
+def pose_neq_chain(N_frame: int, C: int) -> int:
+    """The longest chain of float64 additions an entry of H, g or chi2 passes through (include/unerf.h states the geometry):
+    a thread's PPT pixels x C channels, the wave butterfly (6), the waves of the workgroup in order; then, in the reducer, a
+    thread's share of the tile rows, its butterfly and its waves in order."""
+    tiles = -(-int(N_frame) // POSE_NEQ_TILE)
+    return (POSE_NEQ_PPT * int(C) + 6 + (POSE_NEQ_THREADS // 64 - 1)
+            + -(-tiles // POSE_NEQ_REDUCE_THREADS) + 6 + (POSE_NEQ_REDUCE_THREADS // 64 - 1))
 
 
 def splat_pose_pw(P: int) -> int:

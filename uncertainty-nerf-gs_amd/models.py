@@ -42,6 +42,30 @@ def _scalar(v) -> float:
     return float(v.reshape(-1)[0].item()) if torch.is_tensor(v) else float(v)
 
 
+def _pose_target(what: str, image, channels):
+    """the observed image of get_pose_information_for_camera -> [H,W,C] in ops.POSE_CHANNELS order of `channels`: [H,W,C] as it
+    is, [H,W,3] with its r / g / b columns picked; None stays None"""
+    if image is None:
+        return None
+    image = torch.as_tensor(image)
+    rows = [k for k, n in enumerate(ops.POSE_CHANNELS) if n in ([channels] if isinstance(channels, str) else list(channels))]
+    if image.dim() != 3 or image.shape[-1] not in (len(rows), 3):
+        raise ValueError(f"{what}: image must be [H,W,3] or [H,W,{len(rows)}] (one column per channel), got {tuple(image.shape)}")
+    if image.shape[-1] == len(rows):
+        return image
+    if any(k > 2 for k in rows):
+        raise ValueError(f"{what}: an [H,W,3] image has no column for {[ops.POSE_CHANNELS[k] for k in rows if k > 2]}")
+    return image[..., rows]
+
+
+def _with_pose_step(out: Dict[str, Any], has_image: bool) -> Dict[str, Any]:
+    """adds "step" = posegrad.pose_step(information, gradient)[0] where an image was given"""
+    if has_image:
+        from . import posegrad
+        out["step"] = posegrad.pose_step(out["information"], out["gradient"])[0]
+    return out
+
+
 def _camera_args(camera, lens: bool = True) -> Tuple[torch.Tensor, Dict[str, Any]]:
     """[UPSTREAM Cameras.generate_rays] is restated (unerf_generate_rays) for ONE camera of type PERSPECTIVE, FISHEYE,
     EQUIRECTANGULAR or ORTHOPHOTO (what CAMERA_MODEL_TO_TYPE maps a transforms.json camera_model to, as the reference's
@@ -550,6 +574,31 @@ class _NerfactoBase(nn.Module, _ImageMetrics):
             return {"jacobian": out["proj"], "values": out["val"]}
         out = render.pose_jacobian_camera(self.device_scene(), c2w, want=("jac", "val"), **kw)
         return {"jacobian": out["jac"], "values": out["val"]}
+
+    @torch.no_grad()
+    def get_pose_information_for_camera(self, camera, image=None, weights=None, mask=None, channels=("r", "g", "b"),
+                                        rays_per_launch: Optional[int] = None) -> Dict[str, Any]:
+        """How well a frame determines the camera pose, and which pose step an observed image asks for: over the pixels and
+        `channels` of the frame, in the six parameters of posegrad.POSE_PARAMS (c2w . exp(xi)),
+          information [6,6] = sum w J J^T (the Fisher information; Gauss-Newton matrix),  gradient [6] = sum w J r,
+          chi2 = sum w r^2 with r = rendered - image,  n_used / n_skipped (terms with a non-finite input or w < 0 are skipped),
+          covariance [6,6] = the pseudo-inverse of the information (posegrad.pose_covariance: a Laplace approximation of the
+          pose posterior, a valid pose_cov of get_pose_uncertainty_for_camera), rank,
+          and with an image: step [6] = posegrad.pose_step(information, gradient), to be applied with posegrad.apply_pose_step.
+        All float64 host values.  The Jacobian is get_pose_jacobians_for_camera's (basis "se3"), but it is reduced per launch
+        group on the device in float64 (render.pose_normal_eq_camera) and never held as a frame.
+        image: [H,W,3], or [H,W,C] matching channels; None: the information alone (gradient and chi2 are exactly 0).
+        weights: [H,W], [H,W,1] or [H,W,C]; the intended weight for ActiveNerfactoModel is 1 / rgb_std^2 of its own outputs.
+        mask: [H,W], 0 = left out.  rays_per_launch: a multiple of lib.POSE_NEQ_TILE (default: the model's, rounded up to one);
+        the result does not depend on it."""
+        self._require_pose_jacobian("get_pose_information_for_camera")
+        c2w, cam = _camera_args(camera)
+        tile = _lib.POSE_NEQ_TILE
+        rpl = int(rays_per_launch) if rays_per_launch else -(-int(self.rays_per_launch) // tile) * tile
+        target = _pose_target("get_pose_information_for_camera", image, channels)
+        out = render.pose_normal_eq_camera(self.device_scene(), c2w, target=target, weights=weights, mask=mask, channels=channels,
+                                           rays_per_launch=rpl, **cam)
+        return _with_pose_step(out, image is not None)
 
     @torch.no_grad()
     def get_pose_uncertainty_for_camera(self, camera, pose_cov, rays_per_launch: Optional[int] = None) -> Dict[str, torch.Tensor]:
@@ -1201,19 +1250,39 @@ class SplatfactoModel(nn.Module, _ImageMetrics):
         raise NotImplementedError(f"{type(self).__name__}.get_pose_uncertainty_for_camera: the ray-sample Jacobian kernel is not "
                                   "built for splat models; use get_splat_pose_uncertainty_for_camera.")
 
-    def _splat_pose_jacobian(self, camera, proj, channels, want) -> Dict[str, torch.Tensor]:
-        """splat.pose_jacobian_camera under get_pose_gradients_for_camera's camera checks, SH degree and crop"""
+    def _splat_pose_frame(self, camera):
+        """get_pose_gradients_for_camera's camera checks, SH degree and crop -> (gp, c2w, the frame's keyword arguments)"""
         c2w, cam = _camera_args(camera, lens=False)
         n = min(self.step // self.config.sh_degree_interval, self.config.sh_degree) if self.config.sh_degree > 0 else 0
         gp = {k: v.detach() for k, v in self.gauss_params.items()}
         crop_ids = None
         if self.crop_box is not None and not self.training:
             crop_ids = self.crop_box.within(gp["means"]).squeeze()
+        return gp, c2w, dict(background=self.background_color.to(gp["means"].device), sh_degree=n,
+                             rasterize_mode=self.config.rasterize_mode, crop_ids=crop_ids,
+                             config_sh_degree=self.config.sh_degree, **cam)
+
+    def _splat_pose_jacobian(self, camera, proj, channels, want) -> Dict[str, torch.Tensor]:
+        """splat.pose_jacobian_camera under get_pose_gradients_for_camera's camera checks, SH degree and crop"""
+        gp, c2w, kw = self._splat_pose_frame(camera)
         from . import posegrad
-        return splat.pose_jacobian_camera(gp, c2w, background=self.background_color.to(gp["means"].device),
-                                          proj=proj(posegrad, c2w), channels=channels, want=want, sh_degree=n,
-                                          rasterize_mode=self.config.rasterize_mode, crop_ids=crop_ids,
-                                          config_sh_degree=self.config.sh_degree, **cam)
+        return splat.pose_jacobian_camera(gp, c2w, proj=proj(posegrad, c2w), channels=channels, want=want, **kw)
+
+    def get_pose_information_for_camera(self, camera, image=None, **kw):
+        raise NotImplementedError(f"{type(self).__name__}.get_pose_information_for_camera: the ray-sample Jacobian kernel is not "
+                                  "built for splat models; use get_splat_pose_information_for_camera.")
+
+    @torch.no_grad()
+    def get_splat_pose_information_for_camera(self, camera, image=None, weights=None, mask=None,
+                                              channels=("r", "g", "b")) -> Dict[str, Any]:
+        """_NerfactoBase.get_pose_information_for_camera for the splat frame: the same inputs and dictionary, from
+        splat.pose_normal_eq_camera (get_splat_pose_jacobians_for_camera's Jacobian in the se3 basis -- tile lists, skips,
+        stops, the crop and the SH colours held fixed --, reduced in float64 on the device).  The intended weight for
+        ActiveSplatfactoModel is 1 / rgb_std^2 of its own outputs.  One PERSPECTIVE camera, as get_outputs."""
+        gp, c2w, kw = self._splat_pose_frame(camera)
+        target = _pose_target("get_splat_pose_information_for_camera", image, channels)
+        out = splat.pose_normal_eq_camera(gp, c2w, target=target, weights=weights, mask=mask, channels=channels, **kw)
+        return _with_pose_step(out, image is not None)
 
     @torch.no_grad()
     def get_splat_pose_jacobians_for_camera(self, camera, channels=ops.POSE_CHANNELS, basis: str = "se3") -> Dict[str, torch.Tensor]:

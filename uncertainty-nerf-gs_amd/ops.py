@@ -1346,6 +1346,82 @@ def pose_jacobian(origins, directions, sbins, field: FieldDev, near: float, far:
     return out
 
 
+@dataclass
+class PoseNormalEqWorkspace:
+    """The zero-filled tile rows of one frame's pose normal equations (pose_normal_eq_workspace)."""
+    buf: torch.Tensor       # float64 device words
+    nbytes: int
+    N_frame: int
+    P: int
+
+
+def pose_normal_eq_workspace(N_frame: int, P: int, device) -> PoseNormalEqWorkspace:
+    """The workspace of one frame of N_frame pixels and P pose parameters (unerf_pose_normal_eq_workspace_bytes), zero-filled
+    ONCE: tiles no accumulate call writes add +0.0 in pose_normal_eq_finish."""
+    lib = _l.load()
+    N_frame, P = int(N_frame), int(P)
+    if not 1 <= P <= _l.POSE_NEQ_MAX_P or N_frame < 0:
+        raise _l.UnerfError(f"pose_normal_eq_workspace: N_frame = {N_frame}, P = {P} (expected N_frame >= 0, 1 <= P <= {_l.POSE_NEQ_MAX_P})")
+    with _ctx(device):
+        nbytes = int(lib.unerf_pose_normal_eq_workspace_bytes(N_frame, P))
+        buf = torch.zeros(max(1, (nbytes + 7) // 8), device=device, dtype=torch.float64)
+    return PoseNormalEqWorkspace(buf, nbytes, N_frame, P)
+
+
+def pose_normal_eq_accumulate(ws: PoseNormalEqWorkspace, jac: torch.Tensor, values: Optional[torch.Tensor] = None,
+                              target: Optional[torch.Tensor] = None, weights: Optional[torch.Tensor] = None,
+                              mask: Optional[torch.Tensor] = None, pixel_offset: int = 0) -> None:
+    """unerf_pose_normal_eq_accumulate: the pixels [pixel_offset, pixel_offset + R) of the frame, jac [R,C,P] float32 (the "proj"
+    of pose_jacobian / splat_pose_jacobian), values / target [R,C] both or neither (r = values - target), weights None | [R] |
+    [R,1] | [R,C], mask None | [R] (bool / uint8, 0 = left out).  pixel_offset must be a multiple of lib.POSE_NEQ_TILE, and a
+    group that ends inside a tile must be the frame's last.  Asynchronous on the current stream; the tile rows land in ws."""
+    lib = _l.load()
+    if jac.dim() != 3 or jac.shape[2] != ws.P:
+        raise _l.UnerfError(f"pose_normal_eq: jac must be [R,C,{ws.P}], got {tuple(jac.shape)}")
+    R, Cn, P = (int(v) for v in jac.shape)
+    for name, t in (("values", values), ("target", target)):
+        if t is not None and t.numel() != R * Cn:
+            raise _l.UnerfError(f"pose_normal_eq: {name} {tuple(t.shape)} for jac {tuple(jac.shape)}")
+    wpc = 0
+    if weights is not None:
+        if weights.numel() == R * Cn and Cn > 1:
+            wpc = 1
+        elif weights.numel() != R:
+            raise _l.UnerfError(f"pose_normal_eq: weights {tuple(weights.shape)} for jac {tuple(jac.shape)} (expected [R] or [R,C])")
+    if mask is not None:
+        if mask.numel() != R:
+            raise _l.UnerfError(f"pose_normal_eq: mask has {mask.numel()} entries for {R} pixels")
+        if mask.dtype == torch.bool:
+            mask = mask.view(torch.uint8)
+    with _ctx(jac.device):
+        _run("pose_normal_eq", lambda: lib.unerf_pose_normal_eq_accumulate(
+            _p(jac, name="jac"), _p(values, name="values"), _p(target, name="target"), _p(weights, name="weights"), wpc,
+            _p(mask, torch.uint8, "mask"), R, Cn, P, int(pixel_offset), ws.N_frame, _p(ws.buf, torch.float64, "workspace"), ws.nbytes,
+            _stream()))
+
+
+def pose_normal_eq_finish(ws: PoseNormalEqWorkspace, N_frame: Optional[int] = None, P: Optional[int] = None) -> Dict[str, object]:
+    """unerf_pose_normal_eq_finish, then ONE copy to the host -> {"information" [P,P], "gradient" [P] (float64 numpy),
+    "chi2" float, "n_used", "n_skipped" int}.  N_frame / P default to the workspace's own (and must equal them)."""
+    lib = _l.load()
+    N_frame = ws.N_frame if N_frame is None else int(N_frame)
+    P = ws.P if P is None else int(P)
+    if N_frame != ws.N_frame or P != ws.P:
+        raise _l.UnerfError(f"pose_normal_eq_finish: N_frame = {N_frame}, P = {P}, the workspace was made for {ws.N_frame}, {ws.P}")
+    dev = ws.buf.device
+    with _ctx(dev):
+        out = torch.empty(_l.pose_neq_row(P), device=dev, dtype=torch.float64)
+        _run("pose_normal_eq_finish", lambda: lib.unerf_pose_normal_eq_finish(_p(ws.buf, torch.float64, "workspace"), ws.nbytes, N_frame, P,
+                                                                              _p(out, torch.float64, "out"), _stream()))
+    return pose_normal_eq_unpack(out.cpu().numpy(), P)
+
+
+def pose_normal_eq_unpack(row, P: int) -> Dict[str, object]:
+    """a host copy of the UNERF_POSE_NEQ_ROW(P) doubles -> the dictionary of pose_normal_eq_finish"""
+    return {"information": row[:P * P].reshape(P, P).copy(), "gradient": row[P * P:P * P + P].copy(), "chi2": float(row[P * P + P]),
+            "n_used": int(row[P * P + P + 1]), "n_skipped": int(row[P * P + P + 2])}
+
+
 def pose_grad_mc(origins, directions, sbins, field: FieldDev, near: float, far: float, ray_offset: int = 0,
                  keep_masks: Optional[KeepMasks] = None, rot_inv: Optional[torch.Tensor] = None, spacing: int = 0,
                  background=None, want_rgb: bool = False):

@@ -203,6 +203,26 @@ def _build() -> Dict[str, Any]:
             return fn(camera, pose_cov, **kw)
 
         @torch.no_grad()
+        def get_pose_information_for_camera(self, camera, image=None, **kw):
+            """the pose's Fisher information, the cost gradient against `image`, the pose covariance and the Gauss-Newton step
+            of a frame (weights=, mask=, channels=, rays_per_launch=: models._NerfactoBase.get_pose_information_for_camera);
+            the mc-dropout, Laplace and splat mirrors raise NotImplementedError"""
+            fn = getattr(self._mirror, "get_pose_information_for_camera", None)
+            if fn is None:
+                raise NotImplementedError(f"pose Jacobians are not built for {type(self._mirror).__name__}.")
+            return fn(camera, image, **kw)
+
+        @torch.no_grad()
+        def get_splat_pose_information_for_camera(self, camera, image=None, **kw):
+            """get_pose_information_for_camera of a splat frame (weights=, mask=, channels=:
+            models.SplatfactoModel.get_splat_pose_information_for_camera); other mirrors raise NotImplementedError"""
+            fn = getattr(self._mirror, "get_splat_pose_information_for_camera", None)
+            if fn is None:
+                raise NotImplementedError(f"{type(self._mirror).__name__} has no splat pose Jacobian (it is not a splat "
+                                          "model; the nerfacto models have get_pose_information_for_camera).")
+            return fn(camera, image, **kw)
+
+        @torch.no_grad()
         def get_mc_pose_gradients_for_camera(self, camera, **kw):
             """the pose gradient of an MC-dropout frame under a named mask draw (mask_seed=, rays_per_launch=, want_rgb=:
             models.NerfactoMCDropoutModel.get_mc_pose_gradients_for_camera); other mirrors raise NotImplementedError"""

@@ -159,6 +159,95 @@ def pose_projection(c2w: torch.Tensor, pose_cov=None) -> torch.Tensor:
     return B @ L[:, keep]
 
 
+def _sym_eig(information, what: str):
+    """a symmetric [P,P] host matrix -> (eigenvalues ascending, eigenvectors) in float64; the two triangles are averaged"""
+    H = np.asarray(torch.as_tensor(information).detach().cpu().numpy() if torch.is_tensor(information) else information, np.float64)
+    if H.ndim != 2 or H.shape[0] != H.shape[1]:
+        raise ValueError(f"{what}: information must be [P,P], got {H.shape}")
+    if not np.isfinite(H).all():
+        raise ValueError(f"{what}: information holds a non-finite entry")
+    return np.linalg.eigh(0.5 * (H + H.T))
+
+
+def pose_step(information, gradient, damping: float = 0.0, rcond: float = 1e-12):
+    """delta = -(H + damping diag H)^-1 g, the Gauss-Newton (damping = 0) or Levenberg-Marquardt step of the weighted
+    photometric cost on c2w . exp(xi), from the information and gradient of pose_normal_eq_finish (host, float64).  Solved
+    through a symmetric eigendecomposition of the damped matrix: directions with eigenvalue <= rcond * the largest are left at 0
+    (a pose direction the frame does not determine gets no step).  -> (delta [P] float64 numpy, numerical rank)"""
+    H = np.asarray(information, np.float64)
+    g = np.asarray(gradient, np.float64).reshape(-1)
+    if damping < 0:
+        raise ValueError(f"pose_step: damping = {damping}")
+    if H.shape != (g.size, g.size):
+        raise ValueError(f"pose_step: information {H.shape} for a gradient of {g.size}")
+    lam, Q = _sym_eig(H + float(damping) * np.diag(np.diag(H)), "pose_step")
+    keep = lam > rcond * max(float(lam.max(initial=0.0)), 0.0)
+    inv = np.where(keep, 1.0 / np.where(keep, lam, 1.0), 0.0)
+    return -(Q @ (inv * (Q.T @ g))), int(keep.sum())
+
+
+def pose_covariance(information, prior=None, rcond: float = 1e-12):
+    """The Laplace approximation of the pose posterior: the pseudo-inverse of the information (prior: an optional [P,P]
+    prior INFORMATION, the inverse of a prior covariance, added first) on pose_step's rank rule.  -> (covariance [P,P] float64
+    numpy, numerical rank).  A full-rank [6,6] result is a valid pose_cov of get_pose_uncertainty_for_camera."""
+    H = np.asarray(information, np.float64)
+    if prior is not None:
+        Pm = np.asarray(torch.as_tensor(prior).detach().cpu().numpy() if torch.is_tensor(prior) else prior, np.float64)
+        if Pm.shape != H.shape:
+            raise ValueError(f"pose_covariance: prior {Pm.shape} for an information of {H.shape}")
+        H = H + Pm
+    lam, Q = _sym_eig(H, "pose_covariance")
+    keep = lam > rcond * max(float(lam.max(initial=0.0)), 0.0)
+    inv = np.where(keep, 1.0 / np.where(keep, lam, 1.0), 0.0)
+    cov = (Q * inv) @ Q.T
+    return 0.5 * (cov + cov.T), int(keep.sum())
+
+
+def apply_pose_step(c2w: torch.Tensor, delta) -> torch.Tensor:
+    """pose_multiply(c2w, exp_map_se3(delta)): the [3,4] float32 pose after the twist delta [6] (POSE_PARAMS order, the camera's
+    own frame) -- perturbed_pose for a general twist"""
+    c2w = torch.as_tensor(c2w).detach().cpu().to(torch.float32)
+    c2w = (c2w[0] if c2w.dim() == 3 else c2w)[:3, :4]
+    d = torch.as_tensor(np.asarray(delta, np.float64).reshape(1, 6)).to(torch.float32)
+    return pose_multiply(c2w, exp_map_se3(d)[0])
+
+
+def refine_pose(info_fn, camera, image, iters: int = 10, damping: float = 1e-3, rcond: float = 1e-12, **info_kwargs):
+    """Levenberg-Marquardt on the camera pose against `image`.  info_fn(camera, image=image, **info_kwargs) -> a dictionary with
+    "information", "gradient" and "chi2" (models.*.get_pose_information_for_camera / get_splat_pose_information_for_camera).
+    Each iteration takes pose_step at the current damping and evaluates the stepped pose: the step is accepted when that
+    call's chi2 is lower (damping / 10), else rejected (damping x 10, the pose stays).  The camera is copied, never modified.
+    -> {"poses": the accepted poses [3,4] (the first is the camera's own), "chi2": the chi2 of every evaluation with its
+    "accepted" flags, "c2w": the final pose, "covariance", "rank": posegrad.pose_covariance of the final pose's information,
+    "damping": the final damping}"""
+    cam = copy.copy(camera)
+    c2w = torch.as_tensor(camera.camera_to_worlds).detach().cpu().to(torch.float32)
+    c2w = (c2w[0] if c2w.dim() == 3 else c2w)[:3, :4].clone()
+    cam.camera_to_worlds = c2w
+    cur = info_fn(cam, image=image, **info_kwargs)
+    poses, chi2, accepted = [c2w], [float(cur["chi2"])], [True]
+    lam = float(damping)
+    for _ in range(int(iters)):
+        delta, _rank = pose_step(cur["information"], cur["gradient"], lam, rcond)
+        if not np.any(delta):
+            break
+        trial = apply_pose_step(c2w, delta)
+        cam_t = copy.copy(cam)
+        cam_t.camera_to_worlds = trial
+        nxt = info_fn(cam_t, image=image, **info_kwargs)
+        ok = float(nxt["chi2"]) < float(cur["chi2"])
+        chi2.append(float(nxt["chi2"]))
+        accepted.append(ok)
+        if ok:
+            c2w, cam, cur = trial, cam_t, nxt
+            poses.append(trial)
+            lam /= 10.0
+        else:
+            lam *= 10.0
+    cov, rank = pose_covariance(cur["information"], rcond=rcond)
+    return {"poses": poses, "chi2": chi2, "accepted": accepted, "c2w": c2w, "covariance": cov, "rank": rank, "damping": lam}
+
+
 def export_pose_gradients(model, camera, image_idx: int, output_dir, shift_param: str = "tz", shift_magnitude: float = 0.0,
                           seed: int = 42, gradient_fn=None) -> Dict[str, Path]:
     """One image of estimate_gradient_pose_6dof.py:109-216 -> the files it writes under output_dir / f"image_{image_idx}":

@@ -440,6 +440,59 @@ def pose_jacobian_camera(scene: NerfSceneDev, c2w: torch.Tensor, fx: float, fy: 
     return out
 
 
+def _frame_rows(what: str, name: str, t, H: int, W: int, widths, dev, dtype=torch.float32):
+    """an [H,W] / [H,W,k] frame input (k one of `widths`) -> contiguous [H W, k] on the device, or None"""
+    if t is None:
+        return None
+    t = torch.as_tensor(t)
+    k = 1 if t.dim() == 2 else (int(t.shape[-1]) if t.dim() == 3 else -1)
+    if tuple(t.shape[:2]) != (H, W) or k not in widths:
+        raise ValueError(f"{what}: {name} must be [{H},{W}] or [{H},{W},k] with k in {sorted(widths)}, got {tuple(t.shape)}")
+    if dtype == torch.uint8:
+        t = t != 0
+    return t.to(device=dev, dtype=dtype).reshape(H * W, k).contiguous()
+
+
+def pose_normal_eq_camera(scene: NerfSceneDev, c2w: torch.Tensor, fx: float, fy: float, cx: float, cy: float, H: int, W: int,
+                          target=None, weights=None, mask=None, channels=("r", "g", "b"), pose_cov_prior=None,
+                          rays_per_launch: int = 1 << 20, obb=None, distortion=None, camera_type: int = 1):
+    """The pose normal equations of one camera's frame in the six se3 parameters (posegrad.POSE_PARAMS, c2w . exp(xi)): the loop
+    of pose_jacobian_camera with proj = posegrad.tangent_basis(c2w), but every launch group's [R,C,6] Jacobian and values are
+    reduced at once (ops.pose_normal_eq_accumulate) and dropped -- the frame's Jacobian is never held or joined.
+    target [H,W,C] (C = len(channels), in ops.POSE_CHANNELS order) or None (information only: gradient and chi2 are exactly 0);
+    weights None | [H,W] | [H,W,1] | [H,W,C]; mask None | [H,W] (0 = left out).  rays_per_launch must be a multiple of
+    lib.POSE_NEQ_TILE; the result does not depend on it, bit for bit.
+    -> {"information" [6,6], "gradient" [6], "chi2", "n_used", "n_skipped", "covariance" [6,6], "rank"}: float64 host values,
+    covariance = posegrad.pose_covariance(information, pose_cov_prior)."""
+    from . import posegrad
+    what = "pose_normal_eq_camera"
+    if scene.field.mode not in (_l.FIELD_ACTIVE, _l.FIELD_MCDROPOUT):
+        raise _l.UnerfError(f"{what}: the scene's field is not a nerfacto / active-nerfacto field (not built for the Laplace field)")
+    rpl = int(rays_per_launch)
+    if rpl < _l.POSE_NEQ_TILE or rpl % _l.POSE_NEQ_TILE:
+        raise ValueError(f"{what}: rays_per_launch = {rpl} must be a positive multiple of POSE_NEQ_TILE = {_l.POSE_NEQ_TILE}")
+    Cn = bin(ops.pose_channel_bits(channels)).count("1")
+    dev = scene.device
+    tg = _frame_rows(what, "target", target, H, W, {Cn}, dev)
+    wt = _frame_rows(what, "weights", weights, H, W, {1, Cn}, dev)
+    mk = _frame_rows(what, "mask", mask, H, W, {1}, dev, torch.uint8)
+    proj = posegrad.tangent_basis(c2w)
+    ws = ops.pose_normal_eq_workspace(H * W, 6, dev)
+
+    def launch(o, d, sb, start, rot_inv):
+        R = o.shape[0]
+        r = ops.pose_jacobian(o, d, sb, scene.field, scene.near, scene.far, rot_inv=rot_inv, channels=channels, proj=proj,
+                              spacing=scene.spacing, background=scene.background, want=("proj", "val") if tg is not None else ("proj",))
+        ops.pose_normal_eq_accumulate(ws, r["proj"], r.get("val"), None if tg is None else tg[start:start + R],
+                                      None if wt is None else wt[start:start + R], None if mk is None else mk[start:start + R],
+                                      pixel_offset=start)
+
+    _pose_group_results(what, scene, c2w, fx, fy, cx, cy, H, W, rpl, obb, distortion, camera_type, launch)
+    out = ops.pose_normal_eq_finish(ws)
+    out["covariance"], out["rank"] = posegrad.pose_covariance(out["information"], pose_cov_prior)
+    return out
+
+
 def pose_gradient_camera_mc(scene: NerfSceneDev, c2w: torch.Tensor, fx: float, fy: float, cx: float, cy: float, H: int, W: int,
                             rays_per_launch: int = 1 << 20, obb=None, distortion=None, camera_type: int = 1,
                             want_rgb: bool = False, keep_masks: Optional[ops.KeepMasks] = None):

@@ -269,6 +269,32 @@ def pose_jacobian_camera(gp: Dict[str, torch.Tensor], c2w: torch.Tensor, fx: flo
                                    compensation=comp if aa else None, channels=channels, want=want, block_width=block_width)
 
 
+def pose_normal_eq_camera(gp: Dict[str, torch.Tensor], c2w: torch.Tensor, fx: float, fy: float, cx: float, cy: float,
+                          H: int, W: int, background: torch.Tensor, target=None, weights=None, mask=None,
+                          channels=("r", "g", "b"), pose_cov_prior=None, **frame_kwargs) -> Dict[str, object]:
+    """The pose normal equations of the splat frame in the six se3 parameters (posegrad.POSE_PARAMS, c2w . exp(xi)):
+    pose_jacobian_camera(want=("proj", "val")) with proj = posegrad.tangent_basis(c2w), then ONE ops.pose_normal_eq_accumulate
+    over the frame and the finish.  target / weights / mask, the result and pose_cov_prior as render.pose_normal_eq_camera;
+    frame_kwargs go to pose_jacobian_camera (sh_degree, rasterize_mode, block_width, crop_ids, config_sh_degree, tight)."""
+    from . import posegrad
+    from .render import _frame_rows
+    what = "pose_normal_eq_camera"
+    Cn = bin(ops.pose_channel_bits(channels)).count("1")
+    dev = gp["means"].device
+    tg = _frame_rows(what, "target", target, H, W, {Cn}, dev)
+    wt = _frame_rows(what, "weights", weights, H, W, {1, Cn}, dev)
+    mk = _frame_rows(what, "mask", mask, H, W, {1}, dev, torch.uint8)
+    c2w = c2w.detach().to("cpu", torch.float32)
+    c2w = c2w[0] if c2w.dim() == 3 else c2w
+    r = pose_jacobian_camera(gp, c2w, fx, fy, cx, cy, H, W, background, proj=posegrad.tangent_basis(c2w), channels=channels,
+                             want=("proj", "val") if tg is not None else ("proj",), **frame_kwargs)
+    ws = ops.pose_normal_eq_workspace(H * W, 6, dev)
+    ops.pose_normal_eq_accumulate(ws, r["proj"].reshape(H * W, Cn, 6), None if tg is None else r["val"].reshape(H * W, Cn), tg, wt, mk)
+    out = ops.pose_normal_eq_finish(ws)
+    out["covariance"], out["rank"] = posegrad.pose_covariance(out["information"], pose_cov_prior)
+    return out
+
+
 def _pose_jacobian_empty(H: int, W: int, rows: List[int], P: int, want, background: torch.Tensor) -> Dict[str, torch.Tensor]:
     """pose_jacobian_camera's answer for a frame that empty_outputs would render: zeros, the background as r, g, b"""
     dev = background.device
