@@ -772,18 +772,20 @@ int unerf_ensemble_reduce(const float* const* table /* device */, int B, int n_k
  * the host copies it once and finishes every metric (uncertainty-nerf-gs_amd/metrics.py: finish_metrics).
  *
  * pred / target [n, C] (1 <= C <= 4, n C < 2^31), sigma [n] (std per pixel, shared by the channels), mask [n] or NULL
- * (0 = the pixel is left out of everything).  p = min(pred, pred_clip_max) (+inf: no clip; rgb: 1.0).  Per valid pixel,
- * in float32 as the host computes them: sq = sum_c (p - t)^2, ab = sum_c |p - t| (channels added left to right),
- * var = sigma^2; every sum below is float64, reduced in a fixed order (two calls on the same inputs give equal rows).
+ * (0 = the pixel is left out of everything).  p = pred as given: the reference computes every uncertainty metric from the
+ * render itself (scripts/eval_uncertainty.py:316).  pc = min(pred, pred_clip_max) (+inf: no clip; rgb: 1.0) is the copy
+ * that psnr and SSIM alone see (:681-685): slots [6], [8], [9] and [12].  Per valid pixel, in float32 as the host
+ * computes them: sq = sum_c (p - t)^2, ab = sum_c |p - t| (channels added left to right), var = sigma^2; every sum
+ * below is float64, reduced in a fixed order (two calls on the same inputs give equal rows).
  * ratios_host [n_ratios] / z_host [n_z]: HOST float64 arrays, 1..128 entries each, read during the call.
  *
  * out [UNERF_METRICS_ROW] doubles:
  *   [0] n_valid   [1] valid pixels with a non-finite pred / target / sigma (the sums then mean nothing; the host raises)
  *   [2] sum sq    [3] sum ab    [4] sum var    [5] sum sigma
- *   [6] sum over pixel-channels of ((double)t - (double)p)^2                         (psnr)
+ *   [6] sum over pixel-channels of ((double)t - (double)pc)^2                        (psnr)
  *   [7] sum over pixel-channels of (t - p)^2 / (2 s^2) + log s + log(2 pi) / 2, s = max(sigma, nll_min_sigma), all in
  *       float64                                                                      (UNERF_METRICS_NLL)
- *   [8] min p  [9] max p  [10] min target  [11] max target     (+-inf when nothing is valid)
+ *   [8] min pc  [9] max pc  [10] min target  [11] max target   (+-inf when nothing is valid)
  *   [12] sum of the SSIM index over the (H-10) x (W-10) interior pixels and the C channels, [13] their number
  *       (UNERF_METRICS_SSIM: 11x11 gaussian window, sigma 1.5, k1 0.01, k2 0.03, data_range = max([9] - [8], [11] - [10])
  *       with the differences taken in float32; window sums in float64; needs mask == NULL, H W == n, min(H, W) >= 11)

@@ -11,7 +11,7 @@ icecream ...): NerfactoLaplaceField.sample_laplace, laplace_model.ComputeWeights
 EnsemblePipeline.get_ensemble_outputs_for_camera_ray_bundle,
 NerfactoMCDropoutModel.get_outputs_for_camera_ray_bundle (aggregation part).
 
-    python tests/golden/make_golden.py
+    python tests/golden/make_golden.py [recorder ...]       # e.g. golden_eval_rows; without names: every recorder
 """
 import importlib.abc
 import importlib.machinery
@@ -564,12 +564,316 @@ def golden_eval_configs():
     json.dump(out, open(os.path.join(OUT, "eval_configs.json"), "w"), indent=1)
 
 
+# ---------------------------------------------------------------------------------------------------------------
+# [REF] tests/golden/eval_rows.npz: the reference's own per-image eval functions (scripts/eval_uncertainty.py:
+# get_unc_metrics_rgb, get_unc_metrics_depth, get_image_metrics_and_images_unc, get_average_uncertainty_metrics) run on
+# seeded images at the smallest pixel counts on either side of the metric kernels' boundaries (wave 64, workgroup 256,
+# sort tile 4096; 35 pixels: fewer than 100, where the reference's last sparsification cuts keep nothing and its AUSE is
+# NaN).  Every case is recorded twice: on float32 tensors (the reference as it runs) and on the same values as float64
+# (the anchor of the tests' yardstick).  Inputs and outputs are plain arrays.
+# Left out: a render whose shape differs from the depth GT map (the reference resizes it with torchvision's `resize`,
+# which is not installed where this runs), and the splat `background` branch (it calls upstream model code).
+# The recorder asserts that every case is well defined by the reference alone: the float32 and the float64 run count
+# the same AUCE coverages (no |r| / sigma within rounding of a threshold), and no output moves beyond the float32 -
+# float64 distance when the pixels are permuted (nothing rests on the order of tied keys); a case that fails either is
+# reseeded.
+# ---------------------------------------------------------------------------------------------------------------
+
+EVAL_SHAPES = ((5, 7), (7, 9), (8, 8), (5, 13), (15, 17), (16, 16), (1, 257), (63, 65), (64, 64), (17, 241))
+EVAL_CURVES = ("err_mse", "err_rmse", "err_mae", "err_var_mse", "err_var_rmse", "err_var_mae")
+EVAL_AUCE = ("coverage_values", "avg_length_values", "coverage_error_values", "abs_coverage_error_values",
+             "neg_coverage_error_values")
+EVAL_SCALARS = ("ause_mse", "ause_rmse", "ause_mae", "avg_var", "auc_abs_error_values", "auc_length_values",
+                "auc_neg_error_values")
+EVAL_MIN_RGB_STD, EVAL_MIN_DEPTH_STD = 3e-2, 1.0
+
+
+def _eval_module():
+    """scripts/eval_uncertainty.py behind the shim, its plotting and colour-mapping helpers replaced by pass-throughs"""
+    import nerfuncertainty.scripts.eval_uncertainty as eu
+    eu.colormaps = SimpleNamespace(apply_colormap=lambda x, **kw: x, apply_depth_colormap=lambda x, **kw: x)
+    return eu
+
+
+def _eval_pack(res, tag, r32, r64):
+    """one case's two records as arrays: per precision `_scalars` in the order of `eval_scalar_names`; the float64 run's
+    `_f64_curves` [6, 100] in the order of `eval_curve_names` and `_f64_avg_length` [99], and the float32 run's as its
+    difference from them, `_d32_curves` / `_d32_avg_length` (float32 run - float64 run, ~1e-8, kept as float32: the
+    float32 run is float64 run + difference to 1e-15); the four coverage arrays once, `_coverage` [4, 99] in the order of
+    `eval_coverage_names` -- the two runs count the same coverages, so these are equal bit for bit"""
+    names = [k for k in r64 if k not in EVAL_CURVES + EVAL_AUCE]
+    coverage = [k for k in EVAL_AUCE if k != "avg_length_values"]
+    assert res.setdefault("eval_scalar_names", names) == names
+    res["eval_curve_names"], res["eval_coverage_names"] = list(EVAL_CURVES), coverage
+    for prec, rec in (("f32", r32), ("f64", r64)):
+        res[f"{tag}_{prec}_scalars"] = np.array([rec[k] for k in names], dtype=np.float64)
+    res[f"{tag}_f64_curves"] = np.stack([r64[k] for k in EVAL_CURVES])
+    res[f"{tag}_f64_avg_length"] = r64["avg_length_values"]
+    res[f"{tag}_d32_curves"] = (np.stack([r32[k] for k in EVAL_CURVES]) - res[f"{tag}_f64_curves"]).astype(np.float32)
+    res[f"{tag}_d32_avg_length"] = (r32["avg_length_values"] - r64["avg_length_values"]).astype(np.float32)
+    assert all(np.array_equal(r32[k], r64[k]) for k in coverage)
+    res[f"{tag}_coverage"] = np.stack([r64[k] for k in coverage])
+
+
+def _eval_record(d, nll_key):
+    """what the tests read of one call's output dictionary, as float64 arrays"""
+    out = {k: np.asarray(d[k], dtype=np.float64) for k in EVAL_SCALARS + EVAL_CURVES + EVAL_AUCE}
+    out["nll"] = np.float64(d[nll_key])
+    mse_mean = d["mse"].mean().item()                      # eval_uncertainty.py:717-718, :768-769
+    out["mse"], out["rmse"] = np.float64(mse_mean), np.float64(np.sqrt(mse_mean))
+    return out
+
+
+def _eval_well_defined(r32, r64, permuted64, nll_abs_mean):
+    """the two conditions of the header comment -> None, or what failed"""
+    if not np.array_equal(r32["coverage_values"], r64["coverage_values"]):
+        return "float32 and float64 coverages differ"
+    for k, p64 in ((k, p64) for k in r64 for p64 in permuted64):
+        a, b, c = r64[k], p64[k], r32[k]
+        if not (np.array_equal(np.isnan(a), np.isnan(b)) and np.array_equal(np.isnan(a), np.isnan(c))):
+            return f"{k}: NaN pattern moves"
+        scale = nll_abs_mean if k == "nll" else np.abs(a)
+        room = np.maximum(np.abs(c - a), 2.0 ** -23 * scale)
+        if not np.all(np.nan_to_num(np.abs(b - a) - room) <= 0):
+            return f"{k}: moves by {np.nanmax(np.abs(b - a)):.3e} under a permutation of the pixels"
+    return None
+
+
+def _rgb_case(H, W, seed, variant=""):
+    """gt on the 8-bit grid, a prediction inside (0, 1), then the plants: above 1 in one channel and in all three, exactly 1,
+    below 0; sigma below the NLL floor and exactly on it; sigma 0 with a zero and with a non-zero residual.
+    variant "_b": the plants above 1 alone; "_c": every plant but those above 1"""
+    g = torch.Generator().manual_seed(seed)
+    n = H * W
+    gt = torch.round(torch.rand(n, 3, generator=g) * 255) / 255
+    std = 0.035 + 0.2 * torch.rand(n, generator=g)
+    pred = torch.clamp(gt + std[:, None] * torch.randn(n, 3, generator=g), 0.002, 0.998)
+    at = iter(torch.randperm(n, generator=g).tolist())
+    if variant != "_c":
+        pred[next(at), 1] = 1.31
+        pred[next(at), 0] = 1.0 + 2.0 ** -20
+        pred[next(at)] = torch.tensor([1.07, 1.6, 1.002])
+        pred[next(at)] = torch.tensor([2.5, 1.25, 1.125])
+    if variant == "_b":
+        return pred.view(H, W, 3), gt.view(H, W, 3), std.view(H, W, 1)
+    pred[next(at), 2] = 1.0
+    pred[next(at), 0] = -0.05
+    std[next(at)] = 0.01
+    std[next(at)] = float(np.float32(EVAL_MIN_RGB_STD))
+    plants = ["zero", "resid"] if n >= 200 else [("zero", "resid")[n % 2]]    # below 200 pixels a cut keeps one pixel: between the two
+    for kind in plants:
+        i = next(at)
+        std[i] = 0.0
+        if kind == "zero":
+            pred[i] = gt[i]
+    return pred.view(H, W, 3), gt.view(H, W, 3), std.view(H, W, 1)
+
+
+def _eval_variants(variants):
+    """(H, W, variant): every variant at one shape below, on and above the wave and on the workgroup size (they are what a
+    batch of one shape stacks), the first alone elsewhere"""
+    return [(H, W, v) for H, W in EVAL_SHAPES for v in (variants if (H, W) in ((7, 9), (8, 8), (5, 13), (16, 16)) else variants[:1])]
+
+
+def _gt_u8(gt):
+    """the 8-bit levels k of a ground truth on the 8-bit grid: gt == float32(k) / float32(255), bit for bit"""
+    k = torch.round(gt * 255).to(torch.uint8)
+    assert torch.equal(k.to(torch.float32) / 255, gt)
+    return k.numpy()
+
+
+def _permuted(tensors, H, W, seed):
+    """the pixels in reverse order (every tied pair swaps) and in a seeded random order"""
+    for perm in (torch.arange(H * W - 1, -1, -1), torch.randperm(H * W, generator=torch.Generator().manual_seed(seed))):
+        yield [t.reshape(H * W, -1)[perm].reshape(t.shape) for t in tensors]
+
+
+def _run_rgb(eu, pred, gt, std, dtype):
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")
+        d = eu.get_unc_metrics_rgb(None, 0, {"image": gt.to(dtype)}, {"rgb": pred.to(dtype), "rgb_std": std.to(dtype)}, None, None,
+                                   min_rgb_std_for_nll=EVAL_MIN_RGB_STD)
+    rec = _eval_record(d, "nll_rgb")
+    rec["nll_abs_mean"] = np.float64(d["neg_log_prob"].abs().mean().item())
+    return rec
+
+
+def golden_eval_rgb(res):
+    eu = _eval_module()
+    names = []
+    for H, W, variant in _eval_variants(("", "_b", "_c")):
+        for seed in range(1000 + H * W + 100 * len(names), 1020 + H * W + 100 * len(names)):
+            pred, gt, std = _rgb_case(H, W, seed, variant)
+            r32, r64 = _run_rgb(eu, pred, gt, std, torch.float32), _run_rgb(eu, pred, gt, std, torch.float64)
+            p64 = [_run_rgb(eu, *p, torch.float64) for p in _permuted((pred, gt, std), H, W, seed)]
+            why = _eval_well_defined(r32, r64, p64, r64["nll_abs_mean"])
+            if why is None:
+                break
+            print(f"  rgb {H}x{W}{variant} seed {seed}: {why}; reseeding")
+        else:
+            raise SystemExit(f"rgb {H}x{W}{variant}: no seed gives a well-defined case")
+        names.append(f"{H}x{W}{variant}")
+        tag = f"rgb_{names[-1]}"
+        res.update({f"{tag}_pred": pred.numpy(), f"{tag}_gt_u8": _gt_u8(gt), f"{tag}_std": std.numpy()})
+        _eval_pack(res, tag, r32, r64)
+    res["rgb_cases"] = np.array(names)
+    res["rgb_min_std"] = np.float64(EVAL_MIN_RGB_STD)
+
+
+def _depth_case(H, W, seed, sparse=False, scale=2.5):
+    """depths below 1e-3 and above max GT after scaling; GT == 0 pixels (most of them when `sparse`); a zero std"""
+    g = torch.Generator().manual_seed(seed)
+    n = H * W
+    gt = 1.0 + 4.0 * torch.rand(n, generator=g)
+    std = 0.4 + 2.0 * torch.rand(n, generator=g)
+    depth = gt + std * torch.randn(n, generator=g)
+    at = iter(torch.randperm(n, generator=g).tolist())
+    depth[next(at)] = -1.0
+    depth[next(at)] = 5e-4                                  # positive, below MIN_DEPTH
+    depth[next(at)] = 100.0
+    depth[next(at)] = float(gt.max()) + 0.5
+    std[next(at)] = 0.0
+    invalid = torch.rand(n, generator=g) < (0.7 if sparse else 0.08)
+    invalid[[next(at) for _ in range(3)]] = True
+    gt[invalid] = 0.0
+    return (depth / scale).view(H, W, 1), (std / scale).view(H, W, 1), gt.view(H, W), scale
+
+
+def _run_depth(eu, depth, std, gt, scale, dtype, min_std=EVAL_MIN_DEPTH_STD):
+    import tempfile
+    from pathlib import Path
+    with tempfile.TemporaryDirectory() as tmp, warnings.catch_warnings():
+        warnings.simplefilter("ignore")
+        Path(tmp, "scale_parameters.txt").write_text(f"{scale}\n")
+        np.save(os.path.join(tmp, "depth_gt_07.npy"), gt.to(dtype).numpy())
+        plots = Path(tmp, "plots")
+        plots.mkdir()
+        d = eu.get_unc_metrics_depth(7, {"depth": depth.to(dtype), "depth_std": std.to(dtype)}, Path(tmp), plots,
+                                     min_depth_std_for_nll=min_std)
+    rec = _eval_record(d, "nll_depth")
+    rec["nll_abs_mean"] = np.float64(d["neg_log_prob"][torch.as_tensor(gt > 0)].abs().mean().item())
+    return rec
+
+
+def golden_eval_depth(res):
+    eu = _eval_module()
+    names = []
+    for H, W, variant in _eval_variants(("", "_b")) + [(15, 17, "_sparse")]:
+        sparse = variant == "_sparse"
+        for seed in range(2000 + H * W + 100 * len(names), 2020 + H * W + 100 * len(names)):
+            depth, std, gt, scale = _depth_case(H, W, seed, sparse, 0.4 if variant == "_b" else 2.5)
+            r32, r64 = _run_depth(eu, depth, std, gt, scale, torch.float32), _run_depth(eu, depth, std, gt, scale, torch.float64)
+            p64 = [_run_depth(eu, *p, scale, torch.float64) for p in _permuted((depth, std, gt), H, W, seed)]
+            why = _eval_well_defined(r32, r64, p64, r64["nll_abs_mean"])
+            if why is None:
+                break
+            print(f"  depth {H}x{W}{variant} seed {seed}: {why}; reseeding")
+        else:
+            raise SystemExit(f"depth {H}x{W}{variant}: no seed gives a well-defined case")
+        name = f"{H}x{W}{variant}"
+        names.append(name)
+        tag = f"depth_{name}"
+        res.update({f"{tag}_depth": depth.numpy(), f"{tag}_std": std.numpy(), f"{tag}_gt": gt.numpy(), f"{tag}_scale": np.float64(scale)})
+        _eval_pack(res, tag, r32, r64)
+    res["depth_cases"] = np.array(names)
+    res["depth_min_std"] = np.float64(EVAL_MIN_DEPTH_STD)
+
+
+def golden_eval_frame(res):
+    """get_average_uncertainty_metrics over a three-image fake pipeline: the datamanager's dataloader is a list, the model's
+    psnr / ssim / lpips return the maximum, the sum and the minimum of the prediction they are handed (so the record shows
+    which copy of the prediction each metric received), the plot functions record their arguments."""
+    import tempfile
+    from pathlib import Path
+    eu = _eval_module()
+    H, W, n_img, scale, min_depth_std = 12, 16, 3, 2.5, 2.0
+    images = []
+    for i in range(n_img):
+        pred, gt, std = _rgb_case(H, W, 3000 + i)
+        depth, dstd, dgt, _ = _depth_case(H, W, 3100 + i)
+        images.append(dict(rgb=pred, rgb_std=std, image=gt, depth=depth, depth_std=dstd, depth_gt=dgt,
+                           accumulation=torch.ones(H, W, 1)))
+        res.update({f"frame_img{i}_{k}": v.numpy() for k, v in images[-1].items() if k != "image"})
+        res[f"frame_img{i}_image_u8"] = _gt_u8(gt)
+    res["frame_scale"], res["frame_min_rgb_std"], res["frame_min_depth_std"] = np.float64(scale), np.float64(EVAL_MIN_RGB_STD), np.float64(min_depth_std)
+    inner, plot_errors, plot_auce, save_rgb = eu.get_image_metrics_and_images_unc, eu.plot_errors, eu.plot_auce_curves, eu.save_imgs_rgb
+    prec, dtype = "f32", torch.float32                      # the frame is recorded in one precision: the reference as it runs
+    per_image, plots = [], {}
+
+    def record_image(*a, **kw):
+        out = inner(*a, **kw)
+        per_image.append((out[0], out[2]))
+        return out
+
+    def record_errors(ratio, err, err_by_var, err_type, scene_no, output_path, output):
+        plots[f"errors_{output}_{err_type}_err"], plots[f"errors_{output}_{err_type}_err_var"] = err, err_by_var
+
+    def record_auce(save_dir=None, output="rgb", **curves):
+        plots.update({f"auce_{output}_{k}": v for k, v in curves.items()})
+
+    eu.get_image_metrics_and_images_unc, eu.plot_errors, eu.plot_auce_curves = record_image, record_errors, record_auce
+    eu.save_imgs_rgb = lambda **kw: None
+    try:
+        with tempfile.TemporaryDirectory() as tmp, warnings.catch_warnings():
+            warnings.simplefilter("ignore")
+            Path(tmp, "scale_parameters.txt").write_text(f"{scale}\n")
+            for i, im in enumerate(images):
+                np.save(os.path.join(tmp, "depth_gt_{:02d}.npy".format(i)), im["depth_gt"].to(dtype).numpy())
+            model = SimpleNamespace(device=torch.device("cpu"), dataset_path=Path(tmp), output_path=Path(tmp, "out", "metrics.json"),
+                                    psnr=lambda image, rgb: rgb.max(), ssim=lambda image, rgb: rgb.sum(),
+                                    lpips=lambda image, rgb: rgb.min())
+            loader = [(SimpleNamespace(height=torch.tensor(H), width=torch.tensor(W), index=i), {"image": im["image"].to(dtype)})
+                      for i, im in enumerate(images)]
+            pipeline = SimpleNamespace(model=model, datamanager=SimpleNamespace(fixed_indices_eval_dataloader=loader))
+            outputs = [{k: im[k].to(dtype) for k in ("rgb", "rgb_std", "depth", "depth_std", "accumulation")} for im in images]
+            avg = eu.get_average_uncertainty_metrics(pipeline, lambda camera: outputs[camera.index], eval_depth_unc=True,
+                                                     eval_rgb_unc=True, save_rendered_images=True,
+                                                     min_rgb_std_for_nll=EVAL_MIN_RGB_STD, min_depth_std_for_nll=min_depth_std)
+    finally:
+        eu.get_image_metrics_and_images_unc, eu.plot_errors, eu.plot_auce_curves, eu.save_imgs_rgb = inner, plot_errors, plot_auce, save_rgb
+    assert len(per_image) == n_img and list(avg) == list(per_image[0][0])
+    # scalars in the order of `_keys`; curves stacked by length (100 sparsification cuts, 99 coverages) under `_keys_<n>`
+    res[f"frame_{prec}_keys"] = np.array(list(avg))
+    # the two wall-clock keys keep their place in the key order and are stored as NaN: a rerun reproduces the file
+    timed = lambda d: np.array([np.nan if k in ("num_rays_per_sec", "fps") else v for k, v in d.items()], dtype=np.float64)
+    res[f"frame_{prec}_avg"] = timed(avg)
+    for i, (md, curves) in enumerate(per_image):
+        assert list(md) == list(avg) and list(curves) == list(per_image[0][1])
+        res[f"frame_{prec}_img{i}"] = timed(md)
+        _pack_by_length(res, f"frame_{prec}_curve_keys", f"frame_{prec}_img{i}_curves", curves)
+    _pack_by_length(res, f"frame_{prec}_plot_keys", f"frame_{prec}_plot", plots)
+
+
+def _pack_by_length(res, names_tag, tag, arrays):
+    for n in (100, 99):
+        names = [k for k, v in arrays.items() if len(v) == n]
+        res[f"{names_tag}_{n}"] = np.array(names)
+        res[f"{tag}_{n}"] = np.stack([np.asarray(arrays[k], dtype=np.float64) for k in names])
+    assert all(len(v) in (100, 99) for v in arrays.values())
+
+
+def golden_eval_rows():
+    res = {}
+    for fn in (golden_eval_rgb, golden_eval_depth, golden_eval_frame):
+        fn(res)
+    np.savez_compressed(os.path.join(OUT, "eval_rows.npz"), **res)
+
+
+RECORDERS = (golden_create_mlp, golden_metrics, golden_sample_laplace, golden_get_weights, golden_ensemble,
+             golden_mc_aggregate, golden_eval_configs, golden_splat_get_outputs, golden_nerf_model_glue,
+             golden_field_glue, golden_eval_rows)
+
+
 if __name__ == "__main__":
     if not os.path.isdir(REF):
         raise SystemExit("/root/reference is not mounted: golden vectors can only be regenerated in the build container")
     install_stubs()
-    for fn in (golden_create_mlp, golden_metrics, golden_sample_laplace, golden_get_weights, golden_ensemble,
-               golden_mc_aggregate, golden_eval_configs, golden_splat_get_outputs, golden_nerf_model_glue,
-               golden_field_glue):
+    wanted = sys.argv[1:]                   # names of recorders (`golden_eval_rows`); none: all of them
+    unknown = set(wanted) - {fn.__name__ for fn in RECORDERS}
+    if unknown:
+        raise SystemExit(f"no recorder named {sorted(unknown)}")
+    for fn in RECORDERS:
+        if wanted and fn.__name__ not in wanted:
+            continue
         fn()
         print("wrote", fn.__name__)

@@ -30,9 +30,14 @@ def test_metric_keys_and_averaging(tmp_path):
     for k in ("psnr", "rgb_ause_mse", "rgb_nll", "rgb_auc_abs_error"):
         assert abs(avg[k] - np.mean([p[k] for p in per])) < 1e-12
     assert curves["rgb_all_ause_mse"].shape == (100,) and curves["rgb_all_auce_coverage_values"].shape == (99,)
-    # rgb is clipped to <= 1 before the metrics (eval_uncertainty.py:681)
+    # a copy of rgb clipped to <= 1 feeds psnr / ssim / lpips (eval_uncertainty.py:681); the uncertainty metrics take the
+    # render as it is (:316)
     o, gt = items[0]
+    assert float(o["rgb"].max()) > 1.0
     assert abs(per[0]["psnr"] - M.psnr(torch.clip(o["rgb"], max=1.0), gt)) < 1e-12
+    assert abs(per[0]["ssim"] - M.ssim(torch.clip(o["rgb"], max=1.0), gt)) < 1e-12
+    raw_mse = float(torch.sum((o["rgb"] - gt) ** 2, dim=-1).mean())
+    assert abs(per[0]["rgb_mse"] - raw_mse) < 1e-12 and raw_mse > float(torch.sum((torch.clip(o["rgb"], max=1.0) - gt) ** 2, dim=-1).mean())
     p = tmp_path / "out" / "metrics.json"
     E.write_metrics_json(str(p), "exp", "active-nerfacto", "step-000029999.ckpt", avg)
     d = json.loads(p.read_text())

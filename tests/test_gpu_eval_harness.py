@@ -27,13 +27,14 @@ def _gt(ref_rgb, seed):
 
 
 def _cpu_reference_metrics(out, gt):
-    """the reference's metric definitions (eval_uncertainty.py:676-760) with the numpy ause / auce loops"""
+    """the reference's metric definitions (eval_uncertainty.py:306-402, 676-760) with the numpy ause / auce loops: psnr on
+    the copy of the prediction clipped to <= 1 (:681), everything else on the prediction as rendered (:316)"""
     from uncertainty_nerf_gs_amd import metrics as M
-    rgb = torch.clip(out["rgb"], max=1.0)
+    rgb = out["rgb"]
     sq = torch.sum((rgb - gt) ** 2, -1).flatten()
     ab = torch.sum((rgb - gt).abs(), -1).flatten()
     var = (out["rgb_std"] ** 2).flatten()
-    md = {"psnr": M.psnr(rgb, gt), "rgb_mse": float(sq.mean()), "rgb_avg_var": float(var.mean())}
+    md = {"psnr": M.psnr(torch.clip(rgb, max=1.0), gt), "rgb_mse": float(sq.mean()), "rgb_avg_var": float(var.mean())}
     for et, err in (("mae", ab), ("mse", sq), ("rmse", sq)):
         md[f"rgb_ause_{et}"] = float(M.ause(var, err, et)[3])
     std3 = var.sqrt().unsqueeze(-1).repeat(1, 3)

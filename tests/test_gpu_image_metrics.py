@@ -64,16 +64,17 @@ def _check_row(row, ref, ex, n_z=99, n_r=100, what=""):
 
 
 def _host_metrics(pred, gt, std, mask, clip, min_sigma):
-    """the host functions on CPU tensors, as eval.image_metrics_unc / depth_metrics_unc string them together"""
+    """the host functions on CPU tensors, as eval.image_metrics_unc / depth_metrics_unc string them together: the copy of
+    the prediction clipped to `clip` feeds psnr alone, everything else takes the prediction as given"""
     from uncertainty_nerf_gs_amd import metrics as M
     Cc = pred.shape[-1]
-    p = torch.clamp(pred, max=clip).reshape(-1, Cc)
+    p = pred.reshape(-1, Cc)
     t, s = gt.reshape(-1, Cc), std.reshape(-1)
     if mask is not None:
         k = mask.reshape(-1)
         p, t, s = p[k], t[k], s[k]
     sq, ab, var = torch.sum((p - t) ** 2, -1), torch.sum((p - t).abs(), -1), s ** 2
-    out, curves = {"psnr": M.psnr(p, t), "mse": float(sq.mean()), "avg_var": float(var.mean())}, {}
+    out, curves = {"psnr": M.psnr(torch.clamp(p, max=clip), t), "mse": float(sq.mean()), "avg_var": float(var.mean())}, {}
     for et, err in (("mae", ab), ("mse", sq), ("rmse", sq)):
         _, e, ev, a = M.ause(var, err, et)
         out[f"ause_{et}"], curves[f"ause_{et}"], curves[f"var_ause_{et}"] = float(a), e, ev

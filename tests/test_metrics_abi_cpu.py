@@ -42,26 +42,29 @@ def ssim_sum_f64(p: torch.Tensor, t: torch.Tensor):
 
 def restate_row(pred, target, sigma, mask=None, clip=float("inf"), min_sigma=3e-2, ratios=None, z=None, image_hw=None):
     """The row of include/unerf.h (unerf_image_metrics), restated with torch on the CPU: float32 error definitions (channels
-    added left to right), float64 sums, `torch.sort(stable=True)` for the defined order.  -> (row, extras)"""
+    added left to right), float64 sums, `torch.sort(stable=True)` for the defined order.  The error vectors, the NLL and the
+    AUCE ratios take the prediction as given (scripts/eval_uncertainty.py:316); its copy clipped to `clip` feeds slot 6 (psnr),
+    the minimum / maximum of slots 8 / 9 and the SSIM (:681-685; pinned by tests/golden/eval_rows.npz).  -> (row, extras)"""
     from uncertainty_nerf_gs_amd import metrics as M
     r0, z0 = tables()
     ratios = r0 if ratios is None else ratios
     z = z0 if z is None else z
     Cc = pred.shape[-1]
-    p = torch.clamp(pred.detach().cpu().reshape(-1, Cc).float(), max=clip)
+    p_raw = pred.detach().cpu().reshape(-1, Cc).float()
     t = target.detach().cpu().reshape(-1, Cc).float()
     s = sigma.detach().cpu().reshape(-1).float()
     if mask is not None:
         keep = mask.detach().cpu().reshape(-1).bool()
-        p, t, s = p[keep], t[keep], s[keep]
+        p_raw, t, s = p_raw[keep], t[keep], s[keep]
+    p = torch.clamp(p_raw, max=clip)
     n = s.numel()
-    d = p - t
+    d = p_raw - t
     sq, ab = d[:, 0] * d[:, 0], d[:, 0].abs()
     for c in range(1, Cc):
         sq, ab = sq + d[:, c] * d[:, c], ab + d[:, c].abs()
     var = s * s
     p64, t64, s64 = p.double(), t.double(), s.double()
-    d64 = t64 - p64
+    d64 = t64 - p_raw.double()
     se = torch.clamp_min(s64, float(np.float32(min_sigma)))[:, None]
     nll_terms = d64 ** 2 / (2.0 * (se * se)) + torch.log(se) + 0.5 * math.log(2 * math.pi)
     r = d64.abs()
@@ -84,7 +87,7 @@ def restate_row(pred, target, sigma, mask=None, clip=float("inf"), min_sigma=3e-
     p_mm = (float(p.min()), float(p.max())) if n else (float("inf"), float("-inf"))
     t_mm = (float(t.min()), float(t.max())) if n else (float("inf"), float("-inf"))
     row = M.metrics_row_from_sums(n, float(sq.double().sum()), float(ab.double().sum()), float(var.double().sum()),
-                                  float(s64.sum()), float((d64 ** 2).sum()), float(nll_terms.sum()),
+                                  float(s64.sum()), float(((t64 - p64) ** 2).sum()), float(nll_terms.sum()),
                                   p_mm, t_mm, counts, fam, ssim_sum, ssim_cnt)
     return row, {"nll_abs_sum": float(nll_terms.abs().sum()), "n": n}
 
@@ -242,13 +245,15 @@ def test_restate_row_handles_caller_tables_like_a_brute_force_loop(lib, n, Cc, m
     row, ex = restate_row(pred, gt, std, mask, clip=clip, min_sigma=3e-2, ratios=ratios, z=z)
 
     keep = np.ones(n, bool) if mask is None else mask.numpy()
-    p = np.minimum(pred.numpy(), np.float32(clip))[keep]
+    p_raw = pred.numpy()[keep]                                              # what the errors and the ratios take
+    p = np.minimum(p_raw, np.float32(clip))                                 # what slot 6 and the minimum / maximum take
     t, s = gt.numpy()[keep], std.numpy()[keep]
     nv = int(keep.sum())
     assert p.dtype == t.dtype == s.dtype == np.float32 and row[0] == nv == ex["n"] and row[1] == 0
+    assert nv < 100 or p_raw.max() > clip                                   # the two readings differ on these pixels
     sq, ab = np.zeros(nv, np.float32), np.zeros(nv, np.float32)
     for c in range(Cc):
-        d = p[:, c] - t[:, c]
+        d = p_raw[:, c] - t[:, c]
         sq, ab = sq + d * d, ab + np.abs(d)
     var = s * s
     assert sq.dtype == ab.dtype == var.dtype == np.float32
@@ -269,7 +274,7 @@ def test_restate_row_handles_caller_tables_like_a_brute_force_loop(lib, n, Cc, m
         cnt = 0
         for i in range(nv):
             for c in range(Cc):
-                res, sg = abs(float(t[i, c]) - float(p[i, c])), float(s[i])
+                res, sg = abs(float(t[i, c]) - float(p_raw[i, c])), float(s[i])
                 ratio = res / sg if sg > 0 else (0.0 if res == 0 else math.inf)
                 cnt += ratio <= float(zk)
         assert row[a0 + k] == cnt, (k, zk)
@@ -282,7 +287,8 @@ def test_restate_row_handles_caller_tables_like_a_brute_force_loop(lib, n, Cc, m
         assert fam0[2] == fam0[3] == 0.0 and abs(fam0[1] - total) <= 1e-12 * total and fam0[1] == fam0[4]
         assert row[a0 + 2] == nv * Cc and row[a0 + 3] == row[a0 + 4] and row[a0 + 5] == row[a0 + 1]
     assert (row[8], row[9], row[10], row[11]) == (float(p.min()), float(p.max()), float(t.min()), float(t.max()))
-    for j, v in ((2, sq), (3, ab), (4, var), (5, s)):
+    sq64 = [(float(a) - float(b)) ** 2 for a, b in zip(t.reshape(-1), p.reshape(-1))]
+    for j, v in ((2, sq), (3, ab), (4, var), (5, s), (6, sq64)):
         w = math.fsum(float(x) for x in v)
         assert abs(row[j] - w) <= 1e-12 * w, j
 

@@ -190,15 +190,18 @@ __global__ __launch_bounds__(MT_THREADS) void mt_stats_kernel(const float* __res
             for (int c = 0; c < C; ++c) {
                 const float p_raw = pred[(size_t)i * C + c], t = target[(size_t)i * C + c];
                 bad = bad || !mt_finite(p_raw) || !mt_finite(t);
+                // the clipped copy is what psnr and SSIM see (eval_uncertainty.py:681); the error vectors, the NLL and the
+                // AUCE take the prediction as rendered (:316)
                 const float p = fminf(p_raw, clip);
-                const float d = p - t;
+                const float d = p_raw - t;
                 sq = sq + d * d;
                 ab = ab + fabsf(d);
                 pmin = fminf(pmin, p); pmax = fmaxf(pmax, p);
                 tmin = fminf(tmin, t); tmax = fmaxf(tmax, t);
-                const double d64 = (double)t - (double)p;
+                const double d64 = (double)t - (double)p_raw;
                 const double d2 = d64 * d64;
-                a_sq64 += d2;
+                const double dc64 = (double)t - (double)p;
+                a_sq64 += p == p_raw ? d2 : dc64 * dc64;
                 if (want_nll) a_nll += (d2 / two_s2 + log_s) + half_log_2pi;
                 if (want_auce) {
                     const double r = fabs(d64);

@@ -52,22 +52,23 @@ def image_metrics_unc(outputs: Dict[str, torch.Tensor], gt_image: torch.Tensor, 
     ops.lpips_batch when fused (its row rides in the same host copy as the metric row).  None: the key is left out."""
     if fused:
         return _image_metrics_unc_fused(outputs, gt_image, eval_rgb_unc, min_rgb_std_for_nll, composite_gt, lpips_weights)
-    rgb = torch.clip(outputs["rgb"], max=1.0)
+    rgb = outputs["rgb"]                        # as rendered: what every uncertainty metric takes (eval_uncertainty.py:316)
     image = gt_image.to(rgb.device)
     if "background" in outputs and composite_gt is not None:  # splatfacto: blend GT alpha with the background
         image = composite_gt(image, outputs["background"])
-    # psnr / ssim / lpips as at eval_uncertainty.py:683-689; lpips with the weights the checkpoint brought, else left
-    # out of the dict rather than faked
-    md: Dict[str, float] = {"psnr": M.psnr(rgb, image), "ssim": M.ssim(rgb, image[..., :3])}
+    # psnr / ssim / lpips as at eval_uncertainty.py:681-689, on a copy of the prediction clipped to <= 1 that nothing else
+    # sees; lpips with the weights the checkpoint brought, else left out of the dict rather than faked
+    clipped = torch.clip(rgb, max=1.0)
+    md: Dict[str, float] = {"psnr": M.psnr(clipped, image), "ssim": M.ssim(clipped, image[..., :3])}
     if lpips_weights is not None:
-        md["lpips"] = M.lpips(rgb, image[..., :3], lpips_weights)
+        md["lpips"] = M.lpips(clipped, image[..., :3], lpips_weights)
     curves: Dict[str, np.ndarray] = {}
     if eval_rgb_unc:
         rgb_std = outputs["rgb_std"]
         sq = torch.sum((rgb - image) ** 2, dim=-1).flatten()
         ab = torch.sum(torch.abs(rgb - image), dim=-1).flatten()
         var = (rgb_std ** 2).flatten()
-        for et, err in (("mae", ab), ("mse", sq), ("rmse", sq)):
+        for et, err in (("mse", sq), ("mae", ab), ("rmse", sq)):
             _, e, ev, a = M.ause(var, err, et)
             md[f"rgb_ause_{et}"] = float(a)
             curves[f"rgb_all_ause_{et}"], curves[f"rgb_all_var_ause_{et}"] = e, ev
@@ -88,7 +89,8 @@ def image_metrics_unc(outputs: Dict[str, torch.Tensor], gt_image: torch.Tensor, 
 
 def _image_metrics_unc_fused(outputs, gt_image, eval_rgb_unc, min_rgb_std_for_nll, composite_gt, lpips_weights=None):
     """image_metrics_unc through the kernels.  The ground-truth composition stays in torch in front of the call
-    (elementwise, no sync); the clip of the prediction to <= 1 happens inside the kernels."""
+    (elementwise, no sync); the kernels take the prediction as rendered and clip the copy that psnr and SSIM see to <= 1
+    themselves (ops.lpips_batch clips its own)."""
     from . import lib as _l, ops
     rgb, image, std, flags = _rgb_operands(outputs, gt_image, eval_rgb_unc, composite_gt)
     H, W, Cc = rgb.shape
@@ -111,6 +113,15 @@ def _with_lpips(md: Dict[str, float], value: float) -> Dict[str, float]:
         out[k] = v
         if k == "ssim":
             out["lpips"] = value
+    return out
+
+
+def _with_depth(md: Dict[str, float], dmd: Dict[str, float]) -> Dict[str, float]:
+    """one image's dictionary in the reference's key order (eval_uncertainty.py:688-776): psnr / ssim / lpips, the depth
+    keys, the rgb uncertainty keys"""
+    out = {k: md[k] for k in ("psnr", "ssim", "lpips") if k in md}
+    out.update(dmd)
+    out.update(md)
     return out
 
 
@@ -493,7 +504,7 @@ def get_average_uncertainty_metrics(get_outputs_for_camera: Callable, eval_set: 
         if depth_gt_fn is not None:
             dgt, scale = depth_gt_fn(img_num)
             dmd, dcurves = depth_metrics_unc(outputs, dgt, scale, min_depth_std_for_nll, fused=fused)
-            md.update(dmd)
+            md = _with_depth(md, dmd)
             curves.update(dcurves)
         if save is not None:
             save([img_num], [outputs], [gt])
@@ -514,9 +525,9 @@ def get_average_uncertainty_metrics(get_outputs_for_camera: Callable, eval_set: 
                     ddone = depth_metrics_unc_batch(chunk, dgts, scales, min_depth_std_for_nll, image_ids=ids)
                 else:       # maps of several shapes do not stack: this chunk's depth metrics image by image
                     ddone = [depth_metrics_unc(o, d, a, min_depth_std_for_nll, fused=True) for o, d, a in zip(chunk, dgts, scales)]
-                for (md, curves), (dmd, dcurves) in zip(done, ddone):
-                    md.update(dmd)
+                for (_, curves), (_, dcurves) in zip(done, ddone):
                     curves.update(dcurves)
+                done = [(_with_depth(md, dmd), curves) for (md, curves), (dmd, _) in zip(done, ddone)]
             scored += done
         if save is not None:
             save([img_num for img_num, _, _ in pending], outs, [gt for _, _, gt in pending])

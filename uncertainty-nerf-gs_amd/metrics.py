@@ -42,9 +42,12 @@ def _curve_of_means(means: np.ndarray, err_type: str) -> np.ndarray:
 
 def _ause_of_curves(oracle: np.ndarray, by_var: np.ndarray, ratios: np.ndarray = _RATIOS):
     """the tail of metrics/ause.py:7-44: both float32 curves normalised by the larger maximum, the area between them.
-    -> (ratio_removed, oracle_curve, by_variance_curve, ause)"""
+    -> (ratio_removed, oracle_curve, by_variance_curve, ause)
+    Fewer than 100 pixels: the last cuts keep nothing and their means are NaN.  The reference's built-in `max` walks each
+    curve from its first (finite) entry and a NaN never compares greater, so the maximum is that of the finite entries:
+    the curves are finite up to the empty cuts and NaN there, the area is NaN."""
     by_var = by_var.astype(np.float64)
-    max_val = max(float(oracle.max()), float(by_var.max()))
+    max_val = max(float(np.fmax.reduce(oracle)), float(np.fmax.reduce(by_var)))
     oracle = oracle / np.float32(max_val)
     by_var = by_var / max_val
     return ratios, oracle, by_var, _trapz(by_var - oracle, ratios)
@@ -347,7 +350,7 @@ def finish_metrics(row_host, channels: int, prefix: str = "rgb", flags: Optional
             means = np.where(keep > 0, row[_l.METRICS_AUSE_OFF:_l.METRICS_AUSE_OFF + 4 * _l.METRICS_MAX_CUTS]
                              .reshape(4, _l.METRICS_MAX_CUTS)[:, :len(ratios)] / np.maximum(keep, 1), np.nan)
         # (error type, oracle family, by-variance family): sq sorted by sq / ab by ab; sq / ab sorted by variance
-        for et, fo, fv in (("mae", 1, 3), ("mse", 0, 2), ("rmse", 0, 2)):
+        for et, fo, fv in (("mse", 0, 2), ("mae", 1, 3), ("rmse", 0, 2)):
             _, e, ev, a = _ause_of_curves(_curve_of_means(means[fo], et), _curve_of_means(means[fv], et), ratios)
             md[f"{prefix}_ause_{et}"] = float(a)
             curves[f"{prefix}_all_ause_{et}"], curves[f"{prefix}_all_var_ause_{et}"] = e, ev
