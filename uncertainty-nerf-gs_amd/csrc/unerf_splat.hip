@@ -2421,6 +2421,144 @@ extern "C" int unerf_splat_pose_tangents(const float* means3d, const float* cov3
     return unerf_check_launch("splat_pose_tangents");
 }
 
+// ---- the stages of the forward-mode walk, stated once for splat_pose_grad_kernel and pose_jac_walk ------------------------------
+// (raster_kernel keeps its own copy of the pixel mapping, the staging and the list: it is the kernel bench.py times, and its
+// compiled code is held byte for byte.)  Pointers, scalars and small structs by value: a by-reference argument struct moved the
+// callers' registers.
+
+// A row of PW = 6 or 12 running tangents is three vectors of PoseVec<PW>::T.
+template <int PW> struct PoseVec;
+template <> struct PoseVec<6> { using T = float2; static constexpr int W = 2; };
+template <> struct PoseVec<12> { using T = float4; static constexpr int W = 4; };
+__device__ __forceinline__ float pose_vec_get(const float2& v, int e) { return e == 0 ? v.x : v.y; }
+__device__ __forceinline__ float pose_vec_get(const float4& v, int e) { return e == 0 ? v.x : e == 1 ? v.y : e == 2 ? v.z : v.w; }
+__device__ __forceinline__ void pose_vec_set(float2& v, const float* s) { v = make_float2(s[0], s[1]); }
+__device__ __forceinline__ void pose_vec_set(float4& v, const float* s) { v = make_float4(s[0], s[1], s[2], s[3]); }
+
+// raster_kernel's thread-to-pixel mapping, its statements for ly, lx, i, j, px, py, inside and p: a wave is one 8 x 8 quadrant
+// of a 16-wide tile, narrower tiles are row-major
+struct PosePixel { float px, py; bool inside; int64_t p; };
+__device__ __forceinline__ PosePixel pose_walk_pixel(int tr, int bx, int by, int bw, int H, int W) {
+    const int ly = bw == 16 ? 8 * (tr >> 7) + ((tr & 63) >> 3) : tr / bw;
+    const int lx = bw == 16 ? 8 * ((tr >> 6) & 1) + (tr & 7) : tr - (tr / bw) * bw;
+    const int i = by * bw + ly, j = bx * bw + lx;
+    PosePixel q;
+    q.px = (float)j + 0.5f; q.py = (float)i + 0.5f;
+    q.inside = (ly < bw) && (i < H) && (j < W);
+    q.p = (int64_t)i * W + j;
+    return q;
+}
+
+// The per-splat arrays a staged header is read from (depths: read by the walks that carry the depth sum).
+struct PoseSplatIn {
+    const int32_t* ids;
+    const float *xys, *opac, *conics, *colors, *comp, *depths;
+};
+
+// Thread tr stages list entry `at`: raster_kernel's loads of a splat's x, y, opacity and conic, and its quadrant mask, into the
+// three header words [x, y, o, a | b, c, r, g | b, 1 / comp, z, -] at rec[tr * rec4] (AA: the staged opacity is sigmoid(.) comp,
+// and alpha's tangent needs 1 / comp; DEPTH: z, else 0), the splat's id into s_gid for the staging of its tangent rows.
+// cstride: floats per colour row.
+template <bool AA, bool DEPTH>
+__device__ __forceinline__ void pose_stage_header(PoseSplatIn in, int at, int cstride, float4* rec, int rec4, int32_t* s_gid,
+                                                  uint8_t* s_mask, int tr, bool cull, float tile_x0, float tile_y0) {
+    const int g = in.ids[at];
+    const float x = in.xys[g * 2], y = in.xys[g * 2 + 1], op = in.opac[g];
+    const float ca = in.conics[g * 3], cb = in.conics[g * 3 + 1], cc = in.conics[g * 3 + 2];
+    const float* crow = in.colors + (int64_t)g * cstride;
+    rec[tr * rec4] = make_float4(x, y, op, ca);
+    rec[tr * rec4 + 1] = make_float4(cb, cc, crow[0], crow[1]);
+    rec[tr * rec4 + 2] = make_float4(crow[2], AA ? 1.f / in.comp[g] : 1.f, DEPTH ? in.depths[g] : 0.f, 0.f);
+    s_gid[tr] = g;
+    if (cull) s_mask[tr] = (uint8_t)raster_quad_mask(x, y, op, ca, cb, cc, tile_x0, tile_y0);
+}
+
+// raster_kernel's list statements on a batch of PG: n_mine = the number of staged splats wave wv's quadrant can see (s_mask bit
+// wv), their indices in s_list[wv]: an order-preserving list, the blend is front to back.  The list is per wave because a wave is one
+// quadrant: it is written and read back by the same wave, so a wave-level fence and barrier are all it needs.  A macro: as a
+// function (the list by pointer or by reference, n_mine returned or assigned) it cost all ten kernels two SGPRs.
+#define UNERF_POSE_QUADRANT_LIST(n_mine, s_mask, s_list, bsz, wv, lane, PG)                                              \
+    {                                                                                                                    \
+        (n_mine) = 0;                                                                                                    \
+        _Pragma("unroll") for (int ch = 0; ch < (PG) / 64; ++ch) {                                                       \
+            const int t = ch * 64 + (lane);                                                                              \
+            const bool need = t < (bsz) && (((s_mask)[t] >> (wv)) & 1u);                                                 \
+            const uint64_t mm = __builtin_amdgcn_ballot_w64(need);                                                       \
+            if (need) (s_list)[wv][(n_mine) + __builtin_popcountll(mm & ((1ull << (lane)) - 1ull))] = (uint16_t)t;       \
+            (n_mine) += __builtin_popcountll(mm);                                                                        \
+        }                                                                                                                \
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");                                                           \
+        __builtin_amdgcn_wave_barrier();                                                                                 \
+    }
+
+// raster_kernel's decisions, on its expressions: the statements of its `blend` lambda from dx, dy to the test of nT (the
+// unbounded pass), so the walk skips, blends and stops at exactly the pairs the frame did.  A pixel that is done decides nothing.
+// clamped: alpha sits on the 0.999 cap, where its derivative -- and with it the splat's own tangent ad -- is 0; the splat still
+// blends, and still carries the tangents of the transmittance in front of it.
+struct PoseBlend { float alpha, nT, dx, dy; bool clamped, blend, done; };
+__device__ __forceinline__ PoseBlend pose_blend_decision(float4 h0, float4 h1, float px, float py, float T, bool done) {
+    PoseBlend r;
+    r.alpha = 0.f; r.nT = T; r.dx = 0.f; r.dy = 0.f; r.clamped = false; r.blend = false; r.done = done;
+    if (!done) {
+        r.dx = h0.x - px; r.dy = h0.y - py;
+        const float op = h0.z, ca = h0.w, cb = h1.x, cc = h1.y;
+        const float sigma = 0.5f * (ca * r.dx * r.dx + cc * r.dy * r.dy) + cb * r.dx * r.dy;
+        const float raw = op * __expf(-sigma);
+        r.alpha = fminf(0.999f, raw);
+        r.clamped = raw > 0.999f;
+        if (!(sigma < 0.f || r.alpha < 1.f / 255.f)) {
+            r.nT = T * (1.f - r.alpha);
+            if (r.nT <= 1e-4f) r.done = true;
+            else r.blend = true;
+        }
+    }
+    return r;
+}
+
+// -d sigma = -(wx dx' + wy dy' + wa a' + wb b' + wc c') for the tangents x', y' of the centre and a', b', c' of the conic
+struct PoseWeights { float wx, wy, wa, wb, wc; };
+__device__ __forceinline__ PoseWeights pose_sigma_weights(float ca, float cb, float cc, float dx, float dy) {
+    PoseWeights w;
+    w.wx = ca * dx + cb * dy; w.wy = cc * dy + cb * dx;
+    w.wa = 0.5f * dx * dx; w.wb = dx * dy; w.wc = 0.5f * dy * dy;
+    return w;
+}
+
+// One blended splat's step of the running tangents: sd -> ad -> wk -> dpix, (dD,) dT in the PW directions.  tq: the splat's staged
+// rows x, y, a, b, c (, comp: AA), three vectors each; inv_comp: the header's 1 / comp; DEPTH: the depth sum's tangents dD as well,
+// with the depth row at tq[zrow].  Every lane reads the rows (the reads are uniform), a lane that blends uses them.
+template <bool AA, bool DEPTH, int PW>
+__device__ __forceinline__ void pose_tangent_step(const typename PoseVec<PW>::T* tq, int zrow, PoseBlend bl, PoseWeights wt, float T,
+                                                  float inv_comp, const float (&col)[3], float z, float vis, float (&dT)[PW],
+                                                  float (&dpix)[3][PW], float* dD) {
+    using VT = typename PoseVec<PW>::T;
+    constexpr int VW = PoseVec<PW>::W;
+    const float om = 1.f - bl.alpha;
+#pragma unroll
+    for (int w = 0; w < 3; ++w) {
+        const VT vx = tq[w], vy = tq[3 + w], va = tq[6 + w], vb = tq[9 + w], vc = tq[12 + w];
+        VT vz = vx, vo = vx;
+        if (DEPTH) vz = tq[zrow + w];
+        if (AA) vo = tq[15 + w];
+        if (bl.blend) {
+#pragma unroll
+            for (int e = 0; e < VW; ++e) {
+                const int k = VW * w + e;
+                const float sd = (((wt.wx * pose_vec_get(vx, e) + wt.wy * pose_vec_get(vy, e)) + wt.wa * pose_vec_get(va, e))
+                                  + wt.wb * pose_vec_get(vb, e)) + wt.wc * pose_vec_get(vc, e);
+                const float eo = AA ? pose_vec_get(vo, e) : 0.f;
+                const float ad = bl.clamped ? 0.f : bl.alpha * (inv_comp * eo - sd);
+                const float wk = ad * T + bl.alpha * dT[k];
+                dpix[0][k] += col[0] * wk;
+                dpix[1][k] += col[1] * wk;
+                dpix[2][k] += col[2] * wk;
+                if (DEPTH) dD[k] += z * wk + pose_vec_get(vz, e) * vis;
+                dT[k] = dT[k] * om - T * ad;
+            }
+        }
+    }
+}
+
 struct PoseGradArgs {
     const int32_t* ids;
     const int32_t* bins;
@@ -2459,13 +2597,10 @@ __global__ __launch_bounds__(256) void splat_pose_grad_kernel(PoseGradArgs a) {
     const int bx = blockIdx.x, by = blockIdx.y;
     const int tile = by * tbx + bx;
     const int tr = threadIdx.x;
-    // raster_kernel's thread-to-pixel mapping: a wave is one 8 x 8 quadrant of a 16-wide tile
-    const int ly = bw == 16 ? 8 * (tr >> 7) + ((tr & 63) >> 3) : tr / bw;
-    const int lx = bw == 16 ? 8 * ((tr >> 6) & 1) + (tr & 7) : tr - (tr / bw) * bw;
-    const int i = by * bw + ly, j = bx * bw + lx;
-    const float px = (float)j + 0.5f, py = (float)i + 0.5f;
-    const bool inside = (ly < bw) && (i < a.H) && (j < a.W);
-    const int64_t p = (int64_t)i * a.W + j;
+    const PosePixel at = pose_walk_pixel(tr, bx, by, bw, a.H, a.W);
+    const float px = at.px, py = at.py;
+    const bool inside = at.inside;
+    const int64_t p = at.p;
     bool done = !inside;
     const int r0 = a.bins[tile * 2], r1 = a.bins[tile * 2 + 1];
     const int nbatch = (r1 - r0 + PG - 1) / PG;
@@ -2480,17 +2615,9 @@ __global__ __launch_bounds__(256) void splat_pose_grad_kernel(PoseGradArgs a) {
         const int start = r0 + PG * b;
         if (__syncthreads_count(done ? 1 : 0) >= 256) break;
         const int bsz = min(PG, r1 - start);
-        if (tr < bsz) {
-            const int g = a.ids[start + tr];
-            const float x = a.xys[g * 2], y = a.xys[g * 2 + 1], op = a.opac[g];
-            const float ca = a.conics[g * 3], cb = a.conics[g * 3 + 1], cc = a.conics[g * 3 + 2];
-            const float* crow = a.colors + (int64_t)g * 3;
-            s_rec[tr * REC4] = make_float4(x, y, op, ca);
-            s_rec[tr * REC4 + 1] = make_float4(cb, cc, crow[0], crow[1]);
-            s_rec[tr * REC4 + 2] = make_float4(crow[2], AA ? 1.f / a.comp[g] : 1.f, 0.f, 0.f);
-            s_gid[tr] = g;
-            if (cull) s_mask[tr] = (uint8_t)raster_quad_mask(x, y, op, ca, cb, cc, tile_x0, tile_y0);
-        }
+        if (tr < bsz)
+            pose_stage_header<AA, false>({a.ids, a.xys, a.opac, a.conics, a.colors, a.comp, nullptr}, start + tr, 3, s_rec, REC4, s_gid,
+                                         s_mask, tr, cull, tile_x0, tile_y0);
         __syncthreads();
         // the tangent rows, 16 bytes per thread and trip (a row is UNERF_SPLAT_POSE_Q * 12 floats; comp's 12 are its last)
         for (int w = tr; w < bsz * TQ; w += 256) {
@@ -2499,72 +2626,21 @@ __global__ __launch_bounds__(256) void splat_pose_grad_kernel(PoseGradArgs a) {
         }
         __syncthreads();
         int n_mine = bsz;
-        if (cull) {   // this wave's (order-preserving) list of the staged splats its quadrant can see
-            n_mine = 0;
-#pragma unroll
-            for (int ch = 0; ch < PG / 64; ++ch) {
-                const int t = ch * 64 + lane;
-                const bool need = t < bsz && ((s_mask[t] >> wv) & 1u);
-                const uint64_t mm = __builtin_amdgcn_ballot_w64(need);
-                if (need) s_list[wv][n_mine + __builtin_popcountll(mm & ((1ull << lane) - 1ull))] = (uint16_t)t;
-                n_mine += __builtin_popcountll(mm);
-            }
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-        }
+        if (cull) UNERF_POSE_QUADRANT_LIST(n_mine, s_mask, s_list, bsz, wv, lane, PG)
         for (int k0 = 0; k0 < n_mine; ++k0) {
             if (__builtin_amdgcn_ballot_w64(!done) == 0ull) break;     // uniform: every pixel of this wave has finished
             const int t = cull ? (int)s_list[wv][k0] : k0;
             const float4 h0 = s_rec[t * REC4], h1 = s_rec[t * REC4 + 1], h2 = s_rec[t * REC4 + 2];
-            bool blend = false;
-            float alpha = 0.f, nT = T, dx = 0.f, dy = 0.f;
-            bool clamped = false;
-            if (!done) {
-                // raster_kernel's decisions, on its expressions
-                dx = h0.x - px; dy = h0.y - py;
-                const float op = h0.z, ca = h0.w, cb = h1.x, cc = h1.y;
-                const float sigma = 0.5f * (ca * dx * dx + cc * dy * dy) + cb * dx * dy;
-                const float raw = op * __expf(-sigma);
-                alpha = fminf(0.999f, raw);
-                clamped = raw > 0.999f;
-                if (!(sigma < 0.f || alpha < 1.f / 255.f)) {
-                    nT = T * (1.f - alpha);
-                    if (nT <= 1e-4f) done = true;
-                    else blend = true;
-                }
-            }
-            if (__builtin_amdgcn_ballot_w64(blend) == 0ull) continue;  // uniform: nobody needs this splat's tangents
-            const float ca = h0.w, cb = h1.x, cc = h1.y;
-            const float wx = ca * dx + cb * dy, wy = cc * dy + cb * dx;
-            const float wa = 0.5f * dx * dx, wb = dx * dy, wc = 0.5f * dy * dy;
+            const PoseBlend bl = pose_blend_decision(h0, h1, px, py, T, done);
+            done = bl.done;
+            if (__builtin_amdgcn_ballot_w64(bl.blend) == 0ull) continue;  // uniform: nobody needs this splat's tangents
+            const PoseWeights wt = pose_sigma_weights(h0.w, h1.x, h1.y, bl.dx, bl.dy);
             const float col[3] = {h1.z, h1.w, h2.x};
-            const float om = 1.f - alpha;
-            const float4* tq = &s_rec[t * REC4 + 3];
-#pragma unroll
-            for (int w = 0; w < 3; ++w) {
-                const float4 vx = tq[w], vy = tq[3 + w], va = tq[6 + w], vb = tq[9 + w], vc = tq[12 + w];
-                const float ex[4] = {vx.x, vx.y, vx.z, vx.w}, ey[4] = {vy.x, vy.y, vy.z, vy.w};
-                const float ea[4] = {va.x, va.y, va.z, va.w}, eb[4] = {vb.x, vb.y, vb.z, vb.w}, ec[4] = {vc.x, vc.y, vc.z, vc.w};
-                float eo[4] = {0.f, 0.f, 0.f, 0.f};
-                if (AA) { const float4 vo = tq[15 + w]; eo[0] = vo.x; eo[1] = vo.y; eo[2] = vo.z; eo[3] = vo.w; }
-                if (blend) {
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        const int k = 4 * w + e;
-                        const float sd = (((wx * ex[e] + wy * ey[e]) + wa * ea[e]) + wb * eb[e]) + wc * ec[e];
-                        const float ad = clamped ? 0.f : alpha * (h2.y * eo[e] - sd);
-                        const float wk = ad * T + alpha * dT[k];
-                        dpix[0][k] += col[0] * wk;
-                        dpix[1][k] += col[1] * wk;
-                        dpix[2][k] += col[2] * wk;
-                        dT[k] = dT[k] * om - T * ad;
-                    }
-                }
-            }
-            if (blend) {
-                const float vis = alpha * T;
+            pose_tangent_step<AA, false, 12>(&s_rec[t * REC4 + 3], 0, bl, wt, T, h2.y, col, 0.f, 0.f, dT, dpix, nullptr);
+            if (bl.blend) {
+                const float vis = bl.alpha * T;
                 pix[0] += col[0] * vis; pix[1] += col[1] * vis; pix[2] += col[2] * vis;
-                T = nT;
+                T = bl.nT;
             }
         }
     }
@@ -2639,13 +2715,15 @@ extern "C" int unerf_splat_pose_grad(const int32_t* gaussian_ids_sorted, const i
 // The pose reaches a pixel linearly through the per-splat tangents, so the [12,P] projection is contracted per splat
 // (splat_pose_tangents_proj_kernel) and the walk carries PW = 6 or 12 running tangents of each of T, pix[3] and the depth sum D.
 // A row of PW floats is three vectors of PoseVec<PW>::T either way.
-template <int PW> struct PoseVec;
-template <> struct PoseVec<6> { using T = float2; static constexpr int W = 2; };
-template <> struct PoseVec<12> { using T = float4; static constexpr int W = 4; };
-__device__ __forceinline__ float pose_vec_get(const float2& v, int e) { return e == 0 ? v.x : v.y; }
-__device__ __forceinline__ float pose_vec_get(const float4& v, int e) { return e == 0 ? v.x : e == 1 ? v.y : e == 2 ? v.z : v.w; }
-__device__ __forceinline__ void pose_vec_set(float2& v, const float* s) { v = make_float2(s[0], s[1]); }
-__device__ __forceinline__ void pose_vec_set(float4& v, const float* s) { v = make_float4(s[0], s[1], s[2], s[3]); }
+
+// ptangents rows are read as PoseVec<PW>::T: 8-byte aligned at PW = 6, 16-byte at PW = 12.  with_p: the message names P.
+static int pose_ptangents_aligned(const char* what, const float* ptangents, int P, bool with_p = true) {
+    const int bytes = UNERF_SPLAT_POSE_PW(P) == 6 ? 8 : 16;
+    const bool ok = (reinterpret_cast<uintptr_t>(ptangents) & (uintptr_t)(bytes - 1)) == 0;
+    if (with_p) UNERF_REQUIRE(ok, "%s: ptangents must be %d-byte aligned for P=%d", what, bytes, P);
+    else UNERF_REQUIRE(ok, "%s: ptangents must be %d-byte aligned", what, bytes);
+    return UNERF_OK;
+}
 
 struct PoseProjArgs {
     const float* tan;
@@ -2705,8 +2783,7 @@ extern "C" int unerf_splat_pose_tangents_proj(const float* tangents, const float
     UNERF_REQUIRE(proj_host && (N == 0 || (tangents && means3d && radii && ptangents)), "splat_pose_tangents_proj: null pointer");
     const int PW = UNERF_SPLAT_POSE_PW(P);
     UNERF_REQUIRE((reinterpret_cast<uintptr_t>(tangents) & 15) == 0, "splat_pose_tangents_proj: tangents must be 16-byte aligned");
-    UNERF_REQUIRE((reinterpret_cast<uintptr_t>(ptangents) & (PW == 6 ? 7 : 15)) == 0,
-                  "splat_pose_tangents_proj: ptangents must be %d-byte aligned", PW == 6 ? 8 : 16);
+    if (int rc = pose_ptangents_aligned("splat_pose_tangents_proj", ptangents, P, false)) return rc;
     if (N == 0) return UNERF_OK;
     PoseProjArgs a;
     a.tan = tangents; a.means = means3d; a.radii = radii; a.N = N; a.out = ptangents;
@@ -2785,8 +2862,7 @@ extern "C" int unerf_splat_pose_ptangents_batch(const float* means3d, const floa
     UNERF_REQUIRE(N == 0 || (means3d && cov3d && radii && proj && ptangents),
                   "splat_pose_ptangents_batch: null pointer (means3d, cov3d, radii, proj or ptangents)");
     const int PW = UNERF_SPLAT_POSE_PW(P);
-    UNERF_REQUIRE((reinterpret_cast<uintptr_t>(ptangents) & (PW == 6 ? 7 : 15)) == 0,
-                  "splat_pose_ptangents_batch: ptangents must be %d-byte aligned for P=%d", PW == 6 ? 8 : 16, P);
+    if (int rc = pose_ptangents_aligned("splat_pose_ptangents_batch", ptangents, P)) return rc;
     if (N == 0) return UNERF_OK;
     PosePtanBatchArgs a;
     a.means = means3d; a.cov3d = cov3d; a.radii = radii; a.N = N; a.proj = proj; a.P = P; a.H = H; a.W = W;
@@ -2841,8 +2917,8 @@ __device__ __forceinline__ void pose_jac_store_row(const PoseJacArgs& a, int64_t
     }
 }
 
-// splat_pose_grad_kernel's walk (raster_kernel's decisions on its expressions) with the contracted tangents.
-// A staged record is three 16-byte header words [x, y, o, a | b, c, r, g | b, 1 / comp, z, -] in s_hdr and NT rows of PW floats in
+// splat_pose_grad_kernel's walk, on the same stages (pose_walk_pixel .. pose_tangent_step), with the contracted tangents and the
+// depth sum.  A staged record is three 16-byte header words [x, y, o, a | b, c, r, g | b, 1 / comp, z, -] in s_hdr and NT rows of PW floats in
 // s_tan: the tangents of x, y, a, b, c (, comp: antialiased only), z.  <true, 12>: 128 x (48 + 336) B = 48 KiB, with the lists
 // 49.9 KiB (three workgroups of a CU's 160 KiB); <true, 6>: 128 x (48 + 168) B = 27 KiB, with the lists 28.9 KiB (five).
 // The walk is stated once: a view of a batch is the single-view walk on that view's bins and outputs (the ids of a batch
@@ -2865,13 +2941,10 @@ __device__ __forceinline__ void pose_jac_walk(const PoseJacArgs& a, int cstride)
     const int bx = blockIdx.x, by = blockIdx.y;
     const int tile = by * tbx + bx;
     const int tr = threadIdx.x;
-    // raster_kernel's thread-to-pixel mapping: a wave is one 8 x 8 quadrant of a 16-wide tile
-    const int ly = bw == 16 ? 8 * (tr >> 7) + ((tr & 63) >> 3) : tr / bw;
-    const int lx = bw == 16 ? 8 * ((tr >> 6) & 1) + (tr & 7) : tr - (tr / bw) * bw;
-    const int i = by * bw + ly, j = bx * bw + lx;
-    const float px = (float)j + 0.5f, py = (float)i + 0.5f;
-    const bool inside = (ly < bw) && (i < a.H) && (j < a.W);
-    const int64_t p = (int64_t)i * a.W + j;
+    const PosePixel at = pose_walk_pixel(tr, bx, by, bw, a.H, a.W);
+    const float px = at.px, py = at.py;
+    const bool inside = at.inside;
+    const int64_t p = at.p;
     bool done = !inside;
     const int r0 = a.bins[tile * 2], r1 = a.bins[tile * 2 + 1];
     const int nbatch = (r1 - r0 + PG - 1) / PG;
@@ -2886,17 +2959,9 @@ __device__ __forceinline__ void pose_jac_walk(const PoseJacArgs& a, int cstride)
         const int start = r0 + PG * b;
         if (__syncthreads_count(done ? 1 : 0) >= 256) break;
         const int bsz = min(PG, r1 - start);
-        if (tr < bsz) {
-            const int g = a.ids[start + tr];
-            const float x = a.xys[g * 2], y = a.xys[g * 2 + 1], op = a.opac[g];
-            const float ca = a.conics[g * 3], cb = a.conics[g * 3 + 1], cc = a.conics[g * 3 + 2];
-            const float* crow = a.colors + (int64_t)g * (MULTI ? cstride : 3);
-            s_hdr[tr * 3] = make_float4(x, y, op, ca);
-            s_hdr[tr * 3 + 1] = make_float4(cb, cc, crow[0], crow[1]);
-            s_hdr[tr * 3 + 2] = make_float4(crow[2], AA ? 1.f / a.comp[g] : 1.f, a.depths[g], 0.f);
-            s_gid[tr] = g;
-            if (cull) s_mask[tr] = (uint8_t)raster_quad_mask(x, y, op, ca, cb, cc, tile_x0, tile_y0);
-        }
+        if (tr < bsz)
+            pose_stage_header<AA, true>({a.ids, a.xys, a.opac, a.conics, a.colors, a.comp, a.depths}, start + tr, MULTI ? cstride : 3,
+                                        s_hdr, 3, s_gid, s_mask, tr, cull, tile_x0, tile_y0);
         __syncthreads();
         // the tangent rows, one vector per thread and trip (classic: compensation's row, the sixth of seven, is not staged)
         for (int w = tr; w < bsz * TQ; w += 256) {
@@ -2906,74 +2971,22 @@ __device__ __forceinline__ void pose_jac_walk(const PoseJacArgs& a, int cstride)
         }
         __syncthreads();
         int n_mine = bsz;
-        if (cull) {   // this wave's (order-preserving) list of the staged splats its quadrant can see
-            n_mine = 0;
-#pragma unroll
-            for (int ch = 0; ch < PG / 64; ++ch) {
-                const int t = ch * 64 + lane;
-                const bool need = t < bsz && ((s_mask[t] >> wv) & 1u);
-                const uint64_t mm = __builtin_amdgcn_ballot_w64(need);
-                if (need) s_list[wv][n_mine + __builtin_popcountll(mm & ((1ull << lane) - 1ull))] = (uint16_t)t;
-                n_mine += __builtin_popcountll(mm);
-            }
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-        }
+        if (cull) UNERF_POSE_QUADRANT_LIST(n_mine, s_mask, s_list, bsz, wv, lane, PG)
         for (int k0 = 0; k0 < n_mine; ++k0) {
             if (__builtin_amdgcn_ballot_w64(!done) == 0ull) break;     // uniform: every pixel of this wave has finished
             const int t = cull ? (int)s_list[wv][k0] : k0;
             const float4 h0 = s_hdr[t * 3], h1 = s_hdr[t * 3 + 1], h2 = s_hdr[t * 3 + 2];
-            bool blend = false;
-            float alpha = 0.f, nT = T, dx = 0.f, dy = 0.f;
-            bool clamped = false;
-            if (!done) {
-                // raster_kernel's decisions, on its expressions
-                dx = h0.x - px; dy = h0.y - py;
-                const float op = h0.z, ca = h0.w, cb = h1.x, cc = h1.y;
-                const float sigma = 0.5f * (ca * dx * dx + cc * dy * dy) + cb * dx * dy;
-                const float raw = op * __expf(-sigma);
-                alpha = fminf(0.999f, raw);
-                clamped = raw > 0.999f;
-                if (!(sigma < 0.f || alpha < 1.f / 255.f)) {
-                    nT = T * (1.f - alpha);
-                    if (nT <= 1e-4f) done = true;
-                    else blend = true;
-                }
-            }
-            if (__builtin_amdgcn_ballot_w64(blend) == 0ull) continue;  // uniform: nobody needs this splat's tangents
-            const float ca = h0.w, cb = h1.x, cc = h1.y;
-            const float wx = ca * dx + cb * dy, wy = cc * dy + cb * dx;
-            const float wa = 0.5f * dx * dx, wb = dx * dy, wc = 0.5f * dy * dy;
+            const PoseBlend bl = pose_blend_decision(h0, h1, px, py, T, done);
+            done = bl.done;
+            if (__builtin_amdgcn_ballot_w64(bl.blend) == 0ull) continue;  // uniform: nobody needs this splat's tangents
+            const PoseWeights wt = pose_sigma_weights(h0.w, h1.x, h1.y, bl.dx, bl.dy);
             const float col[3] = {h1.z, h1.w, h2.x};
-            const float z = h2.z;
-            const float om = 1.f - alpha, vis = alpha * T;
-            const VT* tq = &s_tan[t * TQ];
-#pragma unroll
-            for (int w = 0; w < 3; ++w) {
-                const VT vx = tq[w], vy = tq[3 + w], va = tq[6 + w], vb = tq[9 + w], vc = tq[12 + w], vz = tq[3 * ZR + w];
-                VT vo = vx;
-                if (AA) vo = tq[15 + w];
-                if (blend) {
-#pragma unroll
-                    for (int e = 0; e < VW; ++e) {
-                        const int k = VW * w + e;
-                        const float sd = (((wx * pose_vec_get(vx, e) + wy * pose_vec_get(vy, e)) + wa * pose_vec_get(va, e))
-                                          + wb * pose_vec_get(vb, e)) + wc * pose_vec_get(vc, e);
-                        const float eo = AA ? pose_vec_get(vo, e) : 0.f;
-                        const float ad = clamped ? 0.f : alpha * (h2.y * eo - sd);
-                        const float wk = ad * T + alpha * dT[k];
-                        dpix[0][k] += col[0] * wk;
-                        dpix[1][k] += col[1] * wk;
-                        dpix[2][k] += col[2] * wk;
-                        dD[k] += z * wk + pose_vec_get(vz, e) * vis;
-                        dT[k] = dT[k] * om - T * ad;
-                    }
-                }
-            }
-            if (blend) {
+            const float z = h2.z, vis = bl.alpha * T;
+            pose_tangent_step<AA, true, PW>(&s_tan[t * TQ], 3 * ZR, bl, wt, T, h2.y, col, z, vis, dT, dpix, dD);
+            if (bl.blend) {
                 pix[0] += col[0] * vis; pix[1] += col[1] * vis; pix[2] += col[2] * vis;
                 D += z * vis;
-                T = nT;
+                T = bl.nT;
             }
         }
     }
@@ -3029,43 +3042,66 @@ __global__ __launch_bounds__(256) void splat_pose_jac_batch_kernel(PoseJacBatchA
     pose_jac_walk<AA, PW, true>(a, b.cstride);
 }
 
-extern "C" int unerf_splat_pose_jacobian(const int32_t* gaussian_ids_sorted, const int32_t* tile_bins, const float* xys,
-                                         const float* conics, const float* colors, const float* depths, const float* opacities,
-                                         const float* compensation, const float* ptangents, const float* background, int P,
-                                         int H, int W, int block_width, int flags, int channels, float* out_proj,
-                                         float* out_var, float* out_val, void* stream) {
+// ---- the two Jacobian entries' shared host side (the entry's name goes into every message) ---------------------------------------
+static int pose_jac_checks(const char* what, int P, int channels, const float* out_proj, const float* out_var, const float* out_val,
+                           int flags, int block_width, int H, int W) {
     constexpr int ALL = UNERF_POSE_CH_R | UNERF_POSE_CH_G | UNERF_POSE_CH_B | UNERF_POSE_CH_ACC | UNERF_POSE_CH_EDEPTH;
-    UNERF_REQUIRE(gaussian_ids_sorted && tile_bins && xys && conics && colors && depths && opacities && ptangents,
-                  "splat_pose_jacobian: null pointer");
-    UNERF_REQUIRE(P >= 1 && P <= UNERF_SPLAT_POSE_MAX_P, "splat_pose_jacobian: P=%d outside [1,%d]", P, UNERF_SPLAT_POSE_MAX_P);
-    UNERF_REQUIRE(channels != 0, "splat_pose_jacobian: channels is empty");
-    UNERF_REQUIRE((channels & ~ALL) == 0, "splat_pose_jacobian: unknown channel bits %d", channels & ~ALL);
-    UNERF_REQUIRE(out_proj || out_var || out_val, "splat_pose_jacobian: no output asked for (out_proj, out_var and out_val are NULL)");
-    UNERF_REQUIRE((flags & ~UNERF_RASTER_NO_CULL) == 0, "splat_pose_jacobian: unknown flags %d", flags);
-    UNERF_REQUIRE(block_width >= 1 && block_width <= 16, "splat_pose_jacobian: block_width=%d outside [1,16]", block_width);
-    UNERF_REQUIRE(H >= 0 && W >= 0, "splat_pose_jacobian: bad H/W");
-    const int PW = UNERF_SPLAT_POSE_PW(P);
-    UNERF_REQUIRE((reinterpret_cast<uintptr_t>(ptangents) & (PW == 6 ? 7 : 15)) == 0,
-                  "splat_pose_jacobian: ptangents must be %d-byte aligned for P=%d", PW == 6 ? 8 : 16, P);
-    if (H == 0 || W == 0) return UNERF_OK;
+    UNERF_REQUIRE(P >= 1 && P <= UNERF_SPLAT_POSE_MAX_P, "%s: P=%d outside [1,%d]", what, P, UNERF_SPLAT_POSE_MAX_P);
+    UNERF_REQUIRE(channels != 0, "%s: channels is empty", what);
+    UNERF_REQUIRE((channels & ~ALL) == 0, "%s: unknown channel bits %d", what, channels & ~ALL);
+    UNERF_REQUIRE(out_proj || out_var || out_val, "%s: no output asked for (out_proj, out_var and out_val are NULL)", what);
+    UNERF_REQUIRE((flags & ~UNERF_RASTER_NO_CULL) == 0, "%s: unknown flags %d", what, flags);
+    UNERF_REQUIRE(block_width >= 1 && block_width <= 16, "%s: block_width=%d outside [1,16]", what, block_width);
+    UNERF_REQUIRE(H >= 0 && W >= 0, "%s: bad H/W", what);
+    return UNERF_OK;
+}
+
+static PoseJacArgs pose_jac_args(const int32_t* gaussian_ids_sorted, const int32_t* tile_bins, const float* xys, const float* conics,
+                                 const float* colors, const float* depths, const float* opacities, const float* compensation,
+                                 const float* ptangents, const float* background, int P, int H, int W, int block_width, int flags,
+                                 int channels, float* out_proj, float* out_var, float* out_val) {
     PoseJacArgs a;
     a.ids = gaussian_ids_sorted; a.bins = tile_bins; a.xys = xys; a.conics = conics; a.colors = colors; a.depths = depths;
     a.opac = opacities; a.comp = compensation; a.ptan = ptangents; a.bg = background;
     a.P = P; a.H = H; a.W = W; a.bw = block_width; a.cull = (flags & UNERF_RASTER_NO_CULL) ? 0 : 1;
     a.channels = channels; a.C = __builtin_popcount((unsigned)channels);
     a.proj = out_proj; a.var = out_var; a.val = out_val;
-    const dim3 grid((W + block_width - 1) / block_width, (H + block_width - 1) / block_width), block(256);
-    const hipStream_t st = (hipStream_t)stream;
-    if (PW == 6) {
-        if (compensation) hipLaunchKernelGGL((splat_pose_jac_kernel<true, 6>), grid, block, 0, st, a);
-        else hipLaunchKernelGGL((splat_pose_jac_kernel<false, 6>), grid, block, 0, st, a);
-    } else {
-        if (compensation) hipLaunchKernelGGL((splat_pose_jac_kernel<true, 12>), grid, block, 0, st, a);
-        else hipLaunchKernelGGL((splat_pose_jac_kernel<false, 12>), grid, block, 0, st, a);
-    }
-    return unerf_check_launch("splat_pose_jacobian");
+    return a;
 }
 
+// K<AA, PW>::kernel is the walk's kernel for Args; the instantiation follows the compensation pointer and P's padded width
+template <bool AA, int PW> struct PoseJacOne { static constexpr auto kernel = splat_pose_jac_kernel<AA, PW>; };
+template <bool AA, int PW> struct PoseJacBatch { static constexpr auto kernel = splat_pose_jac_batch_kernel<AA, PW>; };
+template <template <bool, int> class K, typename Args>
+static void pose_jac_launch(bool aa, int P, dim3 grid, const Args& a, void* stream) {
+    const dim3 block(256);
+    const hipStream_t st = (hipStream_t)stream;
+    if (UNERF_SPLAT_POSE_PW(P) == 6) {
+        if (aa) hipLaunchKernelGGL((K<true, 6>::kernel), grid, block, 0, st, a);
+        else hipLaunchKernelGGL((K<false, 6>::kernel), grid, block, 0, st, a);
+    } else {
+        if (aa) hipLaunchKernelGGL((K<true, 12>::kernel), grid, block, 0, st, a);
+        else hipLaunchKernelGGL((K<false, 12>::kernel), grid, block, 0, st, a);
+    }
+}
+
+extern "C" int unerf_splat_pose_jacobian(const int32_t* gaussian_ids_sorted, const int32_t* tile_bins, const float* xys,
+                                         const float* conics, const float* colors, const float* depths, const float* opacities,
+                                         const float* compensation, const float* ptangents, const float* background, int P,
+                                         int H, int W, int block_width, int flags, int channels, float* out_proj,
+                                         float* out_var, float* out_val, void* stream) {
+    const char* what = "splat_pose_jacobian";
+    UNERF_REQUIRE(gaussian_ids_sorted && tile_bins && xys && conics && colors && depths && opacities && ptangents,
+                  "%s: null pointer", what);
+    if (int rc = pose_jac_checks(what, P, channels, out_proj, out_var, out_val, flags, block_width, H, W)) return rc;
+    if (int rc = pose_ptangents_aligned(what, ptangents, P)) return rc;
+    if (H == 0 || W == 0) return UNERF_OK;
+    const PoseJacArgs a = pose_jac_args(gaussian_ids_sorted, tile_bins, xys, conics, colors, depths, opacities, compensation, ptangents,
+                                        background, P, H, W, block_width, flags, channels, out_proj, out_var, out_val);
+    const dim3 grid((W + block_width - 1) / block_width, (H + block_width - 1) / block_width);
+    pose_jac_launch<PoseJacOne>(compensation != nullptr, P, grid, a, stream);
+    return unerf_check_launch(what);
+}
 
 extern "C" int unerf_splat_pose_jacobian_batch(const int32_t* gaussian_ids_sorted, const int32_t* tile_bins, const float* xys,
                                                const float* conics, const float* colors, int color_stride, const float* depths,
@@ -3073,45 +3109,23 @@ extern "C" int unerf_splat_pose_jacobian_batch(const int32_t* gaussian_ids_sorte
                                                const float* background, int B, int64_t N, int P, int H, int W, int block_width,
                                                int flags, int channels, float* out_proj, float* out_var, float* out_val,
                                                void* stream) {
-    constexpr int ALL = UNERF_POSE_CH_R | UNERF_POSE_CH_G | UNERF_POSE_CH_B | UNERF_POSE_CH_ACC | UNERF_POSE_CH_EDEPTH;
-    UNERF_REQUIRE(B >= 1 && B <= UNERF_SPLAT_MAX_VIEWS, "splat_pose_jacobian_batch: B=%d outside [1,%d]", B, UNERF_SPLAT_MAX_VIEWS);
-    UNERF_REQUIRE(N >= 0 && (int64_t)B * N < UNERF_SPLAT_MAX_BATCH_SPLATS, "splat_pose_jacobian_batch: B*N = %lld outside [0,2^29)",
+    const char* what = "splat_pose_jacobian_batch";
+    UNERF_REQUIRE(B >= 1 && B <= UNERF_SPLAT_MAX_VIEWS, "%s: B=%d outside [1,%d]", what, B, UNERF_SPLAT_MAX_VIEWS);
+    UNERF_REQUIRE(N >= 0 && (int64_t)B * N < UNERF_SPLAT_MAX_BATCH_SPLATS, "%s: B*N = %lld outside [0,2^29)", what,
                   (long long)B * (long long)N);
     UNERF_REQUIRE(gaussian_ids_sorted && tile_bins && xys && conics && colors && depths && opacities && ptangents,
-                  "splat_pose_jacobian_batch: null pointer (gaussian_ids_sorted, tile_bins, xys, conics, colors, depths, opacities "
-                  "or ptangents)");
-    UNERF_REQUIRE(color_stride >= 3, "splat_pose_jacobian_batch: color_stride=%d below 3", color_stride);
-    UNERF_REQUIRE(P >= 1 && P <= UNERF_SPLAT_POSE_MAX_P, "splat_pose_jacobian_batch: P=%d outside [1,%d]", P, UNERF_SPLAT_POSE_MAX_P);
-    UNERF_REQUIRE(channels != 0, "splat_pose_jacobian_batch: channels is empty");
-    UNERF_REQUIRE((channels & ~ALL) == 0, "splat_pose_jacobian_batch: unknown channel bits %d", channels & ~ALL);
-    UNERF_REQUIRE(out_proj || out_var || out_val,
-                  "splat_pose_jacobian_batch: no output asked for (out_proj, out_var and out_val are NULL)");
-    UNERF_REQUIRE((flags & ~UNERF_RASTER_NO_CULL) == 0, "splat_pose_jacobian_batch: unknown flags %d", flags);
-    UNERF_REQUIRE(block_width >= 1 && block_width <= 16, "splat_pose_jacobian_batch: block_width=%d outside [1,16]", block_width);
-    UNERF_REQUIRE(H >= 0 && W >= 0, "splat_pose_jacobian_batch: bad H/W");
+                  "%s: null pointer (gaussian_ids_sorted, tile_bins, xys, conics, colors, depths, opacities or ptangents)", what);
+    UNERF_REQUIRE(color_stride >= 3, "%s: color_stride=%d below 3", what, color_stride);
+    if (int rc = pose_jac_checks(what, P, channels, out_proj, out_var, out_val, flags, block_width, H, W)) return rc;
     const int tbx = (W + block_width - 1) / block_width, tby = (H + block_width - 1) / block_width;
-    UNERF_REQUIRE((int64_t)tbx * tby <= UNERF_SPLAT_BATCH_MAX_TILES, "splat_pose_jacobian_batch: %lld tiles, the batched lists hold %d",
+    UNERF_REQUIRE((int64_t)tbx * tby <= UNERF_SPLAT_BATCH_MAX_TILES, "%s: %lld tiles, the batched lists hold %d", what,
                   (long long)tbx * tby, UNERF_SPLAT_BATCH_MAX_TILES);
-    const int PW = UNERF_SPLAT_POSE_PW(P);
-    UNERF_REQUIRE((reinterpret_cast<uintptr_t>(ptangents) & (PW == 6 ? 7 : 15)) == 0,
-                  "splat_pose_jacobian_batch: ptangents must be %d-byte aligned for P=%d", PW == 6 ? 8 : 16, P);
+    if (int rc = pose_ptangents_aligned(what, ptangents, P)) return rc;
     if (H == 0 || W == 0) return UNERF_OK;
     PoseJacBatchArgs b;
-    PoseJacArgs& a = b.one;
-    a.ids = gaussian_ids_sorted; a.bins = tile_bins; a.xys = xys; a.conics = conics; a.colors = colors; a.depths = depths;
-    a.opac = opacities; a.comp = compensation; a.ptan = ptangents; a.bg = background;
-    a.P = P; a.H = H; a.W = W; a.bw = block_width; a.cull = (flags & UNERF_RASTER_NO_CULL) ? 0 : 1;
-    a.channels = channels; a.C = __builtin_popcount((unsigned)channels);
-    a.proj = out_proj; a.var = out_var; a.val = out_val;
+    b.one = pose_jac_args(gaussian_ids_sorted, tile_bins, xys, conics, colors, depths, opacities, compensation, ptangents, background,
+                          P, H, W, block_width, flags, channels, out_proj, out_var, out_val);
     b.cstride = color_stride;
-    const dim3 grid(tbx, tby, B), block(256);
-    const hipStream_t st = (hipStream_t)stream;
-    if (PW == 6) {
-        if (compensation) hipLaunchKernelGGL((splat_pose_jac_batch_kernel<true, 6>), grid, block, 0, st, b);
-        else hipLaunchKernelGGL((splat_pose_jac_batch_kernel<false, 6>), grid, block, 0, st, b);
-    } else {
-        if (compensation) hipLaunchKernelGGL((splat_pose_jac_batch_kernel<true, 12>), grid, block, 0, st, b);
-        else hipLaunchKernelGGL((splat_pose_jac_batch_kernel<false, 12>), grid, block, 0, st, b);
-    }
-    return unerf_check_launch("splat_pose_jacobian_batch");
+    pose_jac_launch<PoseJacBatch>(compensation != nullptr, P, dim3(tbx, tby, B), b, stream);
+    return unerf_check_launch(what);
 }

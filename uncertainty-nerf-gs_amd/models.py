@@ -1209,11 +1209,7 @@ class SplatfactoModel(nn.Module, _ImageMetrics):
     @torch.no_grad()
     def get_outputs(self, camera) -> Dict[str, Optional[torch.Tensor]]:
         c2w, cam = _camera_args(camera, lens=False)
-        n = min(self.step // self.config.sh_degree_interval, self.config.sh_degree) if self.config.sh_degree > 0 else 0
-        gp = {k: v.detach() for k, v in self.gauss_params.items()}
-        crop_ids = None
-        if self.crop_box is not None and not self.training:                     # :174-180
-            crop_ids = self.crop_box.within(gp["means"]).squeeze()
+        n, gp, crop_ids = self._splat_scene()
         return splat.active_splatfacto_outputs(gp, c2w, background=self.background_color.to(gp["means"].device),
                                                beta_min=getattr(self.config, "beta_min", 0.01), sh_degree=n,
                                                rasterize_mode=self.config.rasterize_mode, crop_ids=crop_ids,
@@ -1231,15 +1227,8 @@ class SplatfactoModel(nn.Module, _ImageMetrics):
         want_rgb also the colour the gradient kernel blended, [H,W,3]): the per-pixel quantity of the reference's
         estimate_gradient_pose_6dof.py:128-139, from splat.pose_gradient_camera (tile lists, skips and stops held fixed; the
         crop box set by set_crop / get_outputs_for_camera is honoured).  One PERSPECTIVE camera, as get_outputs."""
-        c2w, cam = _camera_args(camera, lens=False)
-        n = min(self.step // self.config.sh_degree_interval, self.config.sh_degree) if self.config.sh_degree > 0 else 0
-        gp = {k: v.detach() for k, v in self.gauss_params.items()}
-        crop_ids = None
-        if self.crop_box is not None and not self.training:
-            crop_ids = self.crop_box.within(gp["means"]).squeeze()
-        return splat.pose_gradient_camera(gp, c2w, background=self.background_color.to(gp["means"].device), sh_degree=n,
-                                          rasterize_mode=self.config.rasterize_mode, crop_ids=crop_ids,
-                                          config_sh_degree=self.config.sh_degree, want_rgb=want_rgb, **cam)
+        gp, c2w, kw = self._splat_pose_frame(camera)
+        return splat.pose_gradient_camera(gp, c2w, want_rgb=want_rgb, **kw)
 
     def get_pose_jacobians_for_camera(self, camera, **kw):
         raise NotImplementedError(f"{type(self).__name__}.get_pose_jacobians_for_camera: the ray-sample Jacobian kernel is not "
@@ -1250,14 +1239,20 @@ class SplatfactoModel(nn.Module, _ImageMetrics):
         raise NotImplementedError(f"{type(self).__name__}.get_pose_uncertainty_for_camera: the ray-sample Jacobian kernel is not "
                                   "built for splat models; use get_splat_pose_uncertainty_for_camera.")
 
-    def _splat_pose_frame(self, camera):
-        """get_pose_gradients_for_camera's camera checks, SH degree and crop -> (gp, c2w, the frame's keyword arguments)"""
-        c2w, cam = _camera_args(camera, lens=False)
+    def _splat_scene(self):
+        """-> the active SH degree n = min(step // interval, config.sh_degree) (:244), the detached gauss_params and the crop
+        set by set_crop (bool [N], or None; eval only, :174-180): what every frame function of the model is given"""
         n = min(self.step // self.config.sh_degree_interval, self.config.sh_degree) if self.config.sh_degree > 0 else 0
         gp = {k: v.detach() for k, v in self.gauss_params.items()}
         crop_ids = None
         if self.crop_box is not None and not self.training:
             crop_ids = self.crop_box.within(gp["means"]).squeeze()
+        return n, gp, crop_ids
+
+    def _splat_pose_frame(self, camera):
+        """get_pose_gradients_for_camera's camera checks, SH degree and crop -> (gp, c2w, the frame's keyword arguments)"""
+        c2w, cam = _camera_args(camera, lens=False)
+        n, gp, crop_ids = self._splat_scene()
         return gp, c2w, dict(background=self.background_color.to(gp["means"].device), sh_degree=n,
                              rasterize_mode=self.config.rasterize_mode, crop_ids=crop_ids,
                              config_sh_degree=self.config.sh_degree, **cam)
@@ -1333,11 +1328,7 @@ class SplatfactoModel(nn.Module, _ImageMetrics):
         results."""
         c2w, B, H, W, intr = _splat_camera_batch(cameras, max_views, "get_outputs_for_cameras")
         self.set_crop(obb_box)
-        n = min(self.step // self.config.sh_degree_interval, self.config.sh_degree) if self.config.sh_degree > 0 else 0
-        gp = {k: v.detach() for k, v in self.gauss_params.items()}
-        crop_ids = None
-        if self.crop_box is not None and not self.training:                     # :174-180, once for all cameras
-            crop_ids = self.crop_box.within(gp["means"]).squeeze()
+        n, gp, crop_ids = self._splat_scene()                                   # the crop once for all cameras
         outs: List[Dict[str, Optional[torch.Tensor]]] = []
         for b0 in range(0, B, max_views):
             sl = slice(b0, min(b0 + max_views, B))
@@ -1354,11 +1345,7 @@ class SplatfactoModel(nn.Module, _ImageMetrics):
         c2w, B, H, W, intr = _splat_camera_batch(cameras, max_views, what)
         if isinstance(pose_covs, (list, tuple)) and len(pose_covs) != B:
             raise ValueError(f"{what}: {len(pose_covs)} pose covariances for {B} cameras (give one, or one per camera)")
-        n = min(self.step // self.config.sh_degree_interval, self.config.sh_degree) if self.config.sh_degree > 0 else 0
-        gp = {k: v.detach() for k, v in self.gauss_params.items()}
-        crop_ids = None
-        if self.crop_box is not None and not self.training:
-            crop_ids = self.crop_box.within(gp["means"]).squeeze()
+        n, gp, crop_ids = self._splat_scene()
         from . import posegrad
         outs: List[Dict[str, torch.Tensor]] = []
         for b0 in range(0, B, max_views):

@@ -2215,6 +2215,20 @@ def splat_pose_tangents_proj(tangents, means3d, radii, proj, out: Optional[torch
     return ptan
 
 
+def _check_want(what: str, want) -> tuple:
+    """`want` of the splat pose Jacobian functions (one name, or several) -> the tuple of names, each of proj / var / val"""
+    want = (want,) if isinstance(want, str) else tuple(want)
+    if not want or any(w not in ("proj", "var", "val") for w in want):
+        raise _l.UnerfError(f"{what}: want={want!r} (expected a non-empty subset of 'proj', 'var', 'val')")
+    return want
+
+
+def _pose_jacobian_outputs(want, lead: tuple, Cn: int, P: int, dev, out) -> Dict[str, torch.Tensor]:
+    """the requested of "proj" [*lead,Cn,P], "var" and "val" [*lead,Cn]: the caller's tensor from `out` where it has one"""
+    shapes = {"proj": (*lead, Cn, P), "var": (*lead, Cn), "val": (*lead, Cn)}
+    return {k: (out[k] if out is not None and k in out else torch.empty(*shapes[k], device=dev)) for k in want}
+
+
 def splat_pose_jacobian(gaussian_ids_sorted, tile_bins, xys, conics, colors, depths, opacities, ptangents, P: int, H: int,
                         W: int, background: Optional[torch.Tensor] = None, compensation: Optional[torch.Tensor] = None,
                         channels=POSE_CHANNELS, want=("proj", "val"), block_width: int = 16, cull: bool = True,
@@ -2227,12 +2241,9 @@ def splat_pose_jacobian(gaussian_ids_sorted, tile_bins, xys, conics, colors, dep
     compensation [N] given: "antialiased"; None: "classic".  out: optional preallocated tensors by the same keys."""
     lib = _l.load()
     bits = pose_channel_bits(channels)
-    want = (want,) if isinstance(want, str) else tuple(want)
-    if not want or any(w not in ("proj", "var", "val") for w in want):
-        raise _l.UnerfError(f"splat_pose_jacobian: want={want!r} (expected a non-empty subset of 'proj', 'var', 'val')")
+    want = _check_want("splat_pose_jacobian", want)
     dev, Cn = xys.device, bin(bits).count("1")
-    shapes = {"proj": (H, W, Cn, P), "var": (H, W, Cn), "val": (H, W, Cn)}
-    res = {k: (out[k] if out is not None and k in out else torch.empty(*shapes[k], device=dev)) for k in want}
+    res = _pose_jacobian_outputs(want, (H, W), Cn, P, dev, out)
     if gaussian_ids_sorted.numel() == 0:
         gaussian_ids_sorted = torch.zeros(1, device=dev, dtype=torch.int32)
     with _ctx(dev):
@@ -2473,15 +2484,12 @@ def splat_pose_jacobian_batch(gaussian_ids_sorted, tile_bins, xys, conics, color
     that view's own arrays."""
     lib = _l.load()
     bits = pose_channel_bits(channels)
-    want = (want,) if isinstance(want, str) else tuple(want)
-    if not want or any(w not in ("proj", "var", "val") for w in want):
-        raise _l.UnerfError(f"splat_pose_jacobian_batch: want={want!r} (expected a non-empty subset of 'proj', 'var', 'val')")
+    want = _check_want("splat_pose_jacobian_batch", want)
     dev, Cn = xys.device, bin(bits).count("1")
     B, N = xys.shape[0], xys.shape[1]
     if colors.dim() != 3 or colors.shape[2] < 3:
         raise _l.UnerfError(f"splat_pose_jacobian_batch: colors must be [B,N,>=3], got {tuple(colors.shape)}")
-    shapes = {"proj": (B, H, W, Cn, P), "var": (B, H, W, Cn), "val": (B, H, W, Cn)}
-    res = {k: (out[k] if out is not None and k in out else torch.empty(*shapes[k], device=dev)) for k in want}
+    res = _pose_jacobian_outputs(want, (B, H, W), Cn, P, dev, out)
     if gaussian_ids_sorted.numel() == 0:
         gaussian_ids_sorted = torch.zeros(1, device=dev, dtype=torch.int32)
     with _ctx(dev):

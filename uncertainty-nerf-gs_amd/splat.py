@@ -8,12 +8,13 @@ the data-dependent depth-variance pass (it needs the finished depth image, :336)
 """
 from __future__ import annotations
 
-from typing import Dict, List, Optional
+from typing import Dict, List, NamedTuple, Optional
 
 import torch
 
 from . import lib as _l
 from . import ops
+from .ops import _check_want
 
 
 def viewmat_from_c2w(c2w: torch.Tensor) -> torch.Tensor:
@@ -52,6 +53,134 @@ def empty_outputs(W: int, H: int, background: torch.Tensor) -> Dict[str, torch.T
             "background": background}
 
 
+class _Front(NamedTuple):
+    """what the front end of a frame (_frame_front) or of a batch of views (_views_front) leaves for the passes behind it: the
+    (cropped) means, the projection's and the shading's per-splat arrays and the sorted tile lists"""
+    means: torch.Tensor
+    xys: torch.Tensor
+    depths: torch.Tensor
+    radii: torch.Tensor
+    conics: torch.Tensor
+    comp: Optional[torch.Tensor]            # the compensation factors of an antialiased frame, else None
+    cov3d: Optional[torch.Tensor]
+    cols: torch.Tensor
+    opac: torch.Tensor
+    gids: torch.Tensor
+    bins: torch.Tensor
+    c2w: Optional[torch.Tensor] = None      # single view: the pose and the view matrix on the host
+    V: Optional[torch.Tensor] = None
+    views: object = None                    # batch: ops.splat_view_records, the per-view "nothing to render" flags and, for
+    empty: Optional[List[bool]] = None      # the pose Jacobian, the contracted tangents
+    ptan: Optional[torch.Tensor] = None
+
+
+def _crop(gp: Dict[str, torch.Tensor], crop_ids: Optional[torch.Tensor]) -> Optional[Dict[str, torch.Tensor]]:
+    """gp restricted to crop_ids (bool [N] from `crop_box.within(means)`, :174-180, 202-217); None: no splat is left -- none at
+    all, or none in the box: the same picture as "nothing visible" (:176-177, 239-240)"""
+    if gp["means"].shape[0] == 0:
+        return None
+    if crop_ids is not None:
+        crop_ids = crop_ids.reshape(-1).to(gp["means"].device)
+        if int(crop_ids.sum().item()) == 0:
+            return None
+        gp = {k: v[crop_ids].contiguous() for k, v in gp.items()}
+    return gp
+
+
+def _shade_args(gp: Dict[str, torch.Tensor], sh_degree: int, config_sh_degree: Optional[int], beta_min: Optional[float]):
+    """-> the degree the shade kernel is given (config_sh_degree <= 0: -1, colours = sigmoid(features_dc), :247-248), the
+    uncertainty logits and beta_min of an active frame (beta_min None -- the pose functions -- or plain splatfacto: no beta row)"""
+    if config_sh_degree is not None and config_sh_degree <= 0:
+        sh_degree = -1
+    if beta_min is None or "log_uncertainties" not in gp:
+        return sh_degree, None, 0.0 if beta_min is None else beta_min
+    return sh_degree, gp["log_uncertainties"].reshape(-1).contiguous(), beta_min
+
+
+def _frame_front(gp: Dict[str, torch.Tensor], c2w: torch.Tensor, fx: float, fy: float, cx: float, cy: float, H: int, W: int,
+                 sh_degree: int, rasterize_mode: str, block_width: int, crop_ids: Optional[torch.Tensor],
+                 config_sh_degree: Optional[int], tight: bool, beta_min: Optional[float] = None) -> Optional[_Front]:
+    """The part every single-view frame function shares: crop, projection, intersection count, shading and the bin sort, in the
+    order that hides the frame's one host read-back.  None: the frame is the reference's get_empty_outputs (no splat, none in
+    the crop box, or nothing visible)."""
+    gp = _crop(gp, crop_ids)
+    if gp is None:
+        return None
+    means = gp["means"].contiguous()
+    # the pose goes to the host ONCE, here, before anything is queued: a device-resident camera_to_worlds (the normal
+    # nerfstudio model path) would otherwise be read back behind the projection and the scan -- a blocking stream sync
+    # exactly where the intersection count's read-back is meant to overlap the SH-colour kernel
+    c2w = c2w.detach().to("cpu", torch.float32)
+    V = viewmat_from_c2w(c2w)
+    if rasterize_mode not in ("classic", "antialiased"):
+        raise ValueError(f"Unknown rasterize_mode: {rasterize_mode}")
+    aa = rasterize_mode == "antialiased"
+    # exp(scales) and quats / quats.norm() (:221-223) are taken inside the projection kernel; with `tight` also
+    # sigmoid(opacities) [* comp] (:252-256), which the tight tile counts depend on
+    logits = gp["opacities"].reshape(-1).contiguous()
+    proj = ops.splat_project(means, gp["scales"].contiguous(), 1.0, gp["quats"].contiguous(), V[:3], fx, fy, cx, cy, H, W,
+                             block_width, raw=True, opacity_logits=logits if tight else None, antialiased=aa)
+    xys, depths, radii, conics, comp, tiles, cov3d = proj[:7]
+    # the intersection count (the frame's one host read-back) starts its way to the host now and is awaited inside
+    # splat_bin_sort; the SH colours do not depend on it and keep the GPU busy meanwhile
+    count = ops.SplatCount(tiles, defer_copy=True)
+    degree, log_unc, beta_min = _shade_args(gp, sh_degree, config_sh_degree, beta_min)
+    # the reference concatenates features_dc and features_rest first (:242-243); the kernel reads them in place.  One launch
+    # leaves the rasteriser's per-splat rows [rgb, (beta), depth] (and the opacities unless the projection made them)
+    cols, opac = ops.splat_shade_inputs(degree, means, c2w[:3, 3], gp["features_dc"].contiguous(),
+                                        gp["features_rest"].contiguous(), log_unc, beta_min, None if tight else logits,
+                                        comp if aa else None, depths)
+    count.start_copy()      # (its host-side set-up runs under the SH kernel just queued)
+    if tight:
+        opac = proj[7]
+    # (self.radii).sum() == 0 -> get_empty_outputs (:239-240).  A splat has a non-zero radius exactly when it hits at
+    # least one tile, so "no intersections" is the same test and rides on the one host read-back of the frame
+    I, _cum, _keys, gids, bins = ops.splat_bin_sort(xys, depths, radii, tiles, H, W, block_width, want_isect_ids=False,
+                                                    count=count, tight=(conics, opac) if tight else None)
+    # (tight lists can be empty while splats are "visible" by radius -- every opacity below 1/255: the reference then
+    # rasterises a frame in which nothing blends, which the empty lists give as well; the extra read-back is on that path
+    # only)
+    if I == 0 and not (tight and bool((radii > 0).any())):
+        return None
+    return _Front(means, xys, depths, radii, conics, comp if aa else None, cov3d, cols, opac, gids, bins, c2w=c2w, V=V)
+
+
+def _views_front(gp: Dict[str, torch.Tensor], c2ws: torch.Tensor, fxs, fys, cxs, cys, H: int, W: int, sh_degree: int,
+                 aa: bool, block_width: int, crop_ids: Optional[torch.Tensor], config_sh_degree: Optional[int], tight: bool,
+                 beta_min: Optional[float] = None, projs: Optional[torch.Tensor] = None) -> Optional[_Front]:
+    """_frame_front for the B views of c2ws [B,3|4,4] (on the host) in shared launches, the crop applied once and the per-view
+    intersection totals read back in one copy.  projs [B,12,P]: the pose Jacobian's contracted tangents as well -- they do not
+    wait for the count either, so they are queued under its way to the host, in front of the bin sort.  None: every view is
+    get_empty_outputs; else `empty` says which are."""
+    gp = _crop(gp, crop_ids)
+    if gp is None:
+        return None
+    B = c2ws.shape[0]
+    means = gp["means"].contiguous()
+    views = ops.splat_view_records([viewmat_from_c2w(c) for c in c2ws], fxs, fys, cxs, cys, [c[:3, 3] for c in c2ws])
+    logits = gp["opacities"].reshape(-1).contiguous()
+    proj = ops.splat_project_batch(means, gp["scales"].contiguous(), gp["quats"].contiguous(), views, B, H, W, block_width,
+                                   opacity_logits=logits if tight else None, antialiased=aa, want_cov3d=projs is not None)
+    xys, depths, radii, conics, comp, tiles, opac = proj[:7]
+    cov3d = proj[7] if projs is not None else None
+    count = ops.SplatCountBatch(tiles, radii if tight else None, defer_copy=True)
+    degree, log_unc, beta_min = _shade_args(gp, sh_degree, config_sh_degree, beta_min)
+    cols, opac2 = ops.splat_shade_inputs_batch(degree, means, views, B, gp["features_dc"].contiguous(),
+                                               gp["features_rest"].contiguous(), log_unc, beta_min, None if tight else logits,
+                                               comp if aa else None, depths)
+    count.start_copy()
+    opac = opac if tight else opac2
+    ptan = None if projs is None else ops.splat_pose_ptangents_batch(means, cov3d, radii, views, B, projs, H, W)
+    totals, visible, gids, bins = ops.splat_bin_sort_batch(xys, depths, radii, count, H, W, block_width,
+                                                           tight=(conics, opac) if tight else None)
+    # per view as the single-view call decides: no intersections and (with tight lists) no radius > 0 -> get_empty_outputs
+    empty = [totals[v] == 0 and not (tight and visible[v]) for v in range(B)]
+    if all(empty):
+        return None
+    return _Front(means, xys, depths, radii, conics, comp if aa else None, cov3d, cols, opac, gids, bins, views=views,
+                  empty=empty, ptan=ptan)
+
+
 def active_splatfacto_outputs(gp: Dict[str, torch.Tensor], c2w: torch.Tensor, fx: float, fy: float, cx: float,
                               cy: float, H: int, W: int, background: torch.Tensor, beta_min: float = 0.01,
                               sh_degree: int = 3, rasterize_mode: str = "classic",
@@ -70,61 +199,18 @@ def active_splatfacto_outputs(gp: Dict[str, torch.Tensor], c2w: torch.Tensor, fx
     False: gsplat's lists."""
     _l.require_gpu()
     background = background.to(gp["means"].device, torch.float32)
-    if gp["means"].shape[0] == 0:          # no splats at all: the same picture as "nothing visible" (:239-240)
+    f = _frame_front(gp, c2w, fx, fy, cx, cy, H, W, sh_degree, rasterize_mode, block_width, crop_ids, config_sh_degree, tight,
+                     beta_min=beta_min)
+    if f is None:
         return empty_outputs(W, H, background)
-    if crop_ids is not None:
-        crop_ids = crop_ids.reshape(-1).to(gp["means"].device)
-        if int(crop_ids.sum().item()) == 0:
-            return empty_outputs(W, H, background)
-        gp = {k: v[crop_ids].contiguous() for k, v in gp.items()}
-    means = gp["means"].contiguous()
-    dev = means.device
-    # the pose goes to the host ONCE, here, before anything is queued: a device-resident camera_to_worlds (the normal
-    # nerfstudio model path) would otherwise be read back behind the projection and the scan -- a blocking stream sync
-    # exactly where the intersection count's read-back is meant to overlap the SH-colour kernel
-    c2w = c2w.detach().to("cpu", torch.float32)
-    V = viewmat_from_c2w(c2w)
-    if rasterize_mode not in ("classic", "antialiased"):
-        raise ValueError(f"Unknown rasterize_mode: {rasterize_mode}")
-    # exp(scales) and quats / quats.norm() (:221-223) are taken inside the projection kernel; with `tight` also
-    # sigmoid(opacities) [* comp] (:252-256), which the tight tile counts depend on
-    logits = gp["opacities"].reshape(-1).contiguous()
-    proj = ops.splat_project(means, gp["scales"].contiguous(), 1.0, gp["quats"].contiguous(), V[:3], fx, fy, cx, cy, H, W,
-                             block_width, raw=True, opacity_logits=logits if tight else None,
-                             antialiased=rasterize_mode == "antialiased")
-    xys, depths, radii, conics, comp, tiles, _cov = proj[:7]
-    opac = proj[7] if tight else None
-    # the intersection count (the frame's one host read-back) starts its way to the host now and is awaited inside
-    # splat_bin_sort; the SH colours do not depend on it and keep the GPU busy meanwhile
-    count = ops.SplatCount(tiles, defer_copy=True)
-    if config_sh_degree is not None and config_sh_degree <= 0:
-        sh_degree = -1                                     # kernel: colours = sigmoid(features_dc)
-    # the reference concatenates features_dc and features_rest first (:242-243); the kernel reads them in place
-    plain = "log_uncertainties" not in gp
-    # one launch leaves the rasteriser's per-splat rows [rgb, (beta), depth] (and the opacities unless made above)
-    cols, opac2 = ops.splat_shade_inputs(sh_degree, means, c2w[:3, 3], gp["features_dc"].contiguous(),
-                                         gp["features_rest"].contiguous(),
-                                         None if plain else gp["log_uncertainties"].reshape(-1).contiguous(), beta_min,
-                                         None if tight else logits,
-                                         comp if rasterize_mode == "antialiased" else None, depths)
-    count.start_copy()      # (its host-side set-up runs under the SH kernel just queued)
-    opac = opac if tight else opac2
-    # (self.radii).sum() == 0 -> get_empty_outputs (:239-240).  A splat has a non-zero radius exactly when it hits at
-    # least one tile, so "no intersections" is the same test and rides on the one host read-back of the frame
-    I, _cum, _keys, gids, bins = ops.splat_bin_sort(xys, depths, radii, tiles, H, W, block_width, want_isect_ids=False,
-                                                    count=count, tight=(conics, opac) if tight else None)
-    if I == 0 and not (tight and bool((radii > 0).any())):
-        return empty_outputs(W, H, background)
-    # (tight lists can be empty while splats are "visible" by radius -- every opacity below 1/255: the reference then
-    # rasterises a frame in which nothing blends, which the empty lists give as well; the extra read-back is on that path
-    # only)
+    xys, depths, conics, cols, opac, gids, bins = f.xys, f.depths, f.conics, f.cols, f.opac, f.gids, f.bins
     # frame scratch: the background padded to the row length, and the two channel maxima the rasteriser passes leave for
     # their alpha normalisations
     Cn = cols.shape[1]
-    scratch = torch.zeros(Cn + 2, device=dev)
+    scratch = torch.zeros(Cn + 2, device=f.means.device)
     scratch[:3] = background
     bg, mx1, mx2 = scratch[:Cn], scratch[Cn:Cn + 1], scratch[Cn + 1:Cn + 2]
-    if plain:
+    if "log_uncertainties" not in gp:
         img, fT, _ = ops.splat_rasterize(gids, bins, xys, conics, cols, opac, H, W, bg, block_width, chan_max=(3, mx1))
         # depth = where(alpha > 0, d / alpha, max(d)), rgb clamp and accumulation in one pass over the pixels
         rgb, alpha, _, _ = ops.splat_normalize_outputs(img, 3, fT, mx1, rgb=True, acc=True)
@@ -158,45 +244,13 @@ def pose_gradient_camera(gp: Dict[str, torch.Tensor], c2w: torch.Tensor, fx: flo
     _l.require_gpu()
     dev = gp["means"].device
     background = background.to(dev, torch.float32)
-
-    def empty():
+    f = _frame_front(gp, c2w, fx, fy, cx, cy, H, W, sh_degree, rasterize_mode, block_width, crop_ids, config_sh_degree, tight)
+    if f is None:
         g = torch.zeros(H, W, 3, 4, device=dev)
         return (g, background.repeat(H, W, 1)) if want_rgb else g
-
-    if gp["means"].shape[0] == 0:
-        return empty()
-    if crop_ids is not None:
-        crop_ids = crop_ids.reshape(-1).to(dev)
-        if int(crop_ids.sum().item()) == 0:
-            return empty()
-        gp = {k: v[crop_ids].contiguous() for k, v in gp.items()}
-    means = gp["means"].contiguous()
-    c2w = c2w.detach().to("cpu", torch.float32)
-    V = viewmat_from_c2w(c2w)
-    if rasterize_mode not in ("classic", "antialiased"):
-        raise ValueError(f"Unknown rasterize_mode: {rasterize_mode}")
-    aa = rasterize_mode == "antialiased"
-    logits = gp["opacities"].reshape(-1).contiguous()
-    proj = ops.splat_project(means, gp["scales"].contiguous(), 1.0, gp["quats"].contiguous(), V[:3], fx, fy, cx, cy, H, W,
-                             block_width, raw=True, opacity_logits=logits if tight else None, antialiased=aa)
-    xys, depths, radii, conics, comp, tiles, cov3d = proj[:7]
-    opac = proj[7] if tight else None
-    count = ops.SplatCount(tiles, defer_copy=True)
-    if config_sh_degree is not None and config_sh_degree <= 0:
-        sh_degree = -1
-    cols, opac2 = ops.splat_shade_inputs(sh_degree, means, c2w[:3, 3], gp["features_dc"].contiguous(),
-                                         gp["features_rest"].contiguous(), None, 0.0, None if tight else logits,
-                                         comp if aa else None, depths)
-    count.start_copy()
-    opac = opac if tight else opac2
-    I, _cum, _keys, gids, bins = ops.splat_bin_sort(xys, depths, radii, tiles, H, W, block_width, want_isect_ids=False,
-                                                    count=count, tight=(conics, opac) if tight else None)
-    if I == 0 and not (tight and bool((radii > 0).any())):
-        return empty()
-    tan = ops.splat_pose_tangents(means, cov3d, radii, V[:3], fx, fy, cx, cy, H, W)
-    grad, rgb, _ = ops.splat_pose_grad(gids, bins, xys, conics, cols[:, :3].contiguous(), opac, tan, H, W, background,
-                                       compensation=comp if aa else None, c2w=c2w[:3, :4], block_width=block_width,
-                                       want_rgb=want_rgb)
+    tan = ops.splat_pose_tangents(f.means, f.cov3d, f.radii, f.V[:3], fx, fy, cx, cy, H, W)
+    grad, rgb, _ = ops.splat_pose_grad(f.gids, f.bins, f.xys, f.conics, f.cols[:, :3].contiguous(), f.opac, tan, H, W, background,
+                                       compensation=f.comp, c2w=f.c2w[:3, :4], block_width=block_width, want_rgb=want_rgb)
     return (grad, rgb) if want_rgb else grad
 
 
@@ -216,12 +270,9 @@ def pose_jacobian_camera(gp: Dict[str, torch.Tensor], c2w: torch.Tensor, fx: flo
     values."""
     from . import posegrad
     _l.require_gpu()
-    dev = gp["means"].device
-    background = background.to(dev, torch.float32)
+    background = background.to(gp["means"].device, torch.float32)
     bits = ops.pose_channel_bits(channels)
-    want = (want,) if isinstance(want, str) else tuple(want)
-    if not want or any(w not in ("proj", "var", "val") for w in want):
-        raise _l.UnerfError(f"pose_jacobian_camera: want={want!r} (expected a non-empty subset of 'proj', 'var', 'val')")
+    want = _check_want("pose_jacobian_camera", want)
     c2w = c2w.detach().to("cpu", torch.float32)
     c2w = c2w[0] if c2w.dim() == 3 else c2w
     try:
@@ -229,44 +280,14 @@ def pose_jacobian_camera(gp: Dict[str, torch.Tensor], c2w: torch.Tensor, fx: flo
     except ValueError as e:
         raise _l.UnerfError(f"pose_jacobian_camera: {e}") from None
     P = int(M.shape[1])
-    rows = [k for k in range(len(ops.POSE_CHANNELS)) if bits >> k & 1]
-
-    def empty():
+    f = _frame_front(gp, c2w, fx, fy, cx, cy, H, W, sh_degree, rasterize_mode, block_width, crop_ids, config_sh_degree, tight)
+    if f is None:
+        rows = [k for k in range(len(ops.POSE_CHANNELS)) if bits >> k & 1]
         return _pose_jacobian_empty(H, W, rows, P, want, background)
-
-    if gp["means"].shape[0] == 0:
-        return empty()
-    if crop_ids is not None:
-        crop_ids = crop_ids.reshape(-1).to(dev)
-        if int(crop_ids.sum().item()) == 0:
-            return empty()
-        gp = {k: v[crop_ids].contiguous() for k, v in gp.items()}
-    means = gp["means"].contiguous()
-    V = viewmat_from_c2w(c2w)
-    if rasterize_mode not in ("classic", "antialiased"):
-        raise ValueError(f"Unknown rasterize_mode: {rasterize_mode}")
-    aa = rasterize_mode == "antialiased"
-    logits = gp["opacities"].reshape(-1).contiguous()
-    pr = ops.splat_project(means, gp["scales"].contiguous(), 1.0, gp["quats"].contiguous(), V[:3], fx, fy, cx, cy, H, W,
-                           block_width, raw=True, opacity_logits=logits if tight else None, antialiased=aa)
-    xys, depths, radii, conics, comp, tiles, cov3d = pr[:7]
-    opac = pr[7] if tight else None
-    count = ops.SplatCount(tiles, defer_copy=True)
-    if config_sh_degree is not None and config_sh_degree <= 0:
-        sh_degree = -1
-    cols, opac2 = ops.splat_shade_inputs(sh_degree, means, c2w[:3, 3], gp["features_dc"].contiguous(),
-                                         gp["features_rest"].contiguous(), None, 0.0, None if tight else logits,
-                                         comp if aa else None, depths)
-    count.start_copy()
-    opac = opac if tight else opac2
-    I, _cum, _keys, gids, bins = ops.splat_bin_sort(xys, depths, radii, tiles, H, W, block_width, want_isect_ids=False,
-                                                    count=count, tight=(conics, opac) if tight else None)
-    if I == 0 and not (tight and bool((radii > 0).any())):
-        return empty()
-    tan = ops.splat_pose_tangents(means, cov3d, radii, V[:3], fx, fy, cx, cy, H, W)
-    ptan = ops.splat_pose_tangents_proj(tan, means, radii, M)
-    return ops.splat_pose_jacobian(gids, bins, xys, conics, cols[:, :3].contiguous(), depths, opac, ptan, P, H, W, background,
-                                   compensation=comp if aa else None, channels=channels, want=want, block_width=block_width)
+    tan = ops.splat_pose_tangents(f.means, f.cov3d, f.radii, f.V[:3], fx, fy, cx, cy, H, W)
+    ptan = ops.splat_pose_tangents_proj(tan, f.means, f.radii, M)
+    return ops.splat_pose_jacobian(f.gids, f.bins, f.xys, f.conics, f.cols[:, :3].contiguous(), f.depths, f.opac, ptan, P, H, W,
+                                   background, compensation=f.comp, channels=channels, want=want, block_width=block_width)
 
 
 def pose_normal_eq_camera(gp: Dict[str, torch.Tensor], c2w: torch.Tensor, fx: float, fy: float, cx: float, cy: float,
@@ -342,37 +363,12 @@ def active_splatfacto_outputs_batch(gp: Dict[str, torch.Tensor], c2ws: torch.Ten
     background = background.to(gp["means"].device, torch.float32)
     if rasterize_mode not in ("classic", "antialiased"):
         raise ValueError(f"Unknown rasterize_mode: {rasterize_mode}")
-    if gp["means"].shape[0] == 0:
+    f = _views_front(gp, c2ws, fxs, fys, cxs, cys, H, W, sh_degree, rasterize_mode == "antialiased", block_width, crop_ids,
+                     config_sh_degree, tight, beta_min=beta_min)
+    if f is None:
         return [empty_outputs(W, H, background) for _ in range(B)]
-    if crop_ids is not None:
-        crop_ids = crop_ids.reshape(-1).to(gp["means"].device)
-        if int(crop_ids.sum().item()) == 0:
-            return [empty_outputs(W, H, background) for _ in range(B)]
-        gp = {k: v[crop_ids].contiguous() for k, v in gp.items()}
-    means = gp["means"].contiguous()
-    dev = means.device
-    views = ops.splat_view_records([viewmat_from_c2w(c) for c in c2ws], fxs, fys, cxs, cys, [c[:3, 3] for c in c2ws])
-    logits = gp["opacities"].reshape(-1).contiguous()
-    xys, depths, radii, conics, comp, tiles, opac = ops.splat_project_batch(
-        means, gp["scales"].contiguous(), gp["quats"].contiguous(), views, B, H, W, block_width,
-        opacity_logits=logits if tight else None, antialiased=rasterize_mode == "antialiased")
-    count = ops.SplatCountBatch(tiles, radii if tight else None, defer_copy=True)
-    if config_sh_degree is not None and config_sh_degree <= 0:
-        sh_degree = -1
-    plain = "log_uncertainties" not in gp
-    cols, opac2 = ops.splat_shade_inputs_batch(sh_degree, means, views, B, gp["features_dc"].contiguous(),
-                                               gp["features_rest"].contiguous(),
-                                               None if plain else gp["log_uncertainties"].reshape(-1).contiguous(), beta_min,
-                                               None if tight else logits, comp if rasterize_mode == "antialiased" else None,
-                                               depths)
-    count.start_copy()
-    opac = opac if tight else opac2
-    totals, visible, gids, bins = ops.splat_bin_sort_batch(xys, depths, radii, count, H, W, block_width,
-                                                           tight=(conics, opac) if tight else None)
-    # per view as the single-view call decides: no intersections and (with tight lists) no radius > 0 -> get_empty_outputs
-    empty = [totals[v] == 0 and not (tight and visible[v]) for v in range(B)]
-    if all(empty):
-        return [empty_outputs(W, H, background) for _ in range(B)]
+    xys, depths, conics, cols, opac, gids, bins, empty = f.xys, f.depths, f.conics, f.cols, f.opac, f.gids, f.bins, f.empty
+    dev, plain = f.means.device, "log_uncertainties" not in gp
     Cn = cols.shape[2]
     bg = torch.zeros(Cn, device=dev)
     bg[:3] = background
@@ -428,9 +424,7 @@ def pose_jacobian_cameras(gp: Dict[str, torch.Tensor], c2ws: torch.Tensor, fx, f
     fxs, fys, cxs, cys = (_per_view(v, B, n) for v, n in ((fx, "fx"), (fy, "fy"), (cx, "cx"), (cy, "cy")))
     per_view = pose_view_projections(c2ws, projs, pose_covs)
     bits = ops.pose_channel_bits(channels)
-    want = (want,) if isinstance(want, str) else tuple(want)
-    if not want or any(w not in ("proj", "var", "val") for w in want):
-        raise _l.UnerfError(f"pose_jacobian_cameras: want={want!r} (expected a non-empty subset of 'proj', 'var', 'val')")
+    want = _check_want("pose_jacobian_cameras", want)
     if rasterize_mode not in ("classic", "antialiased"):
         raise ValueError(f"Unknown rasterize_mode: {rasterize_mode}")
     tiles_n = ((W + block_width - 1) // block_width) * ((H + block_width - 1) // block_width)
@@ -441,44 +435,16 @@ def pose_jacobian_cameras(gp: Dict[str, torch.Tensor], c2ws: torch.Tensor, fx, f
                                      channels=channels, want=want, sh_degree=sh_degree, rasterize_mode=rasterize_mode,
                                      block_width=block_width, crop_ids=crop_ids, config_sh_degree=config_sh_degree, tight=tight)
                 for v in range(B)]
-    dev = gp["means"].device
-    background = background.to(dev, torch.float32)
+    background = background.to(gp["means"].device, torch.float32)
     (P,) = widths
     rows = [k for k in range(len(ops.POSE_CHANNELS)) if bits >> k & 1]
-    empties = lambda: [_pose_jacobian_empty(H, W, rows, P, want, background) for _ in range(B)]
-    if gp["means"].shape[0] == 0:
-        return empties()
-    if crop_ids is not None:
-        crop_ids = crop_ids.reshape(-1).to(dev)
-        if int(crop_ids.sum().item()) == 0:
-            return empties()
-        gp = {k: v[crop_ids].contiguous() for k, v in gp.items()}
-    means = gp["means"].contiguous()
-    aa = rasterize_mode == "antialiased"
-    views = ops.splat_view_records([viewmat_from_c2w(c) for c in c2ws], fxs, fys, cxs, cys, [c[:3, 3] for c in c2ws])
-    logits = gp["opacities"].reshape(-1).contiguous()
-    xys, depths, radii, conics, comp, tiles, opac, cov3d = ops.splat_project_batch(
-        means, gp["scales"].contiguous(), gp["quats"].contiguous(), views, B, H, W, block_width,
-        opacity_logits=logits if tight else None, antialiased=aa, want_cov3d=True)
-    count = ops.SplatCountBatch(tiles, radii if tight else None, defer_copy=True)
-    if config_sh_degree is not None and config_sh_degree <= 0:
-        sh_degree = -1
-    cols, opac2 = ops.splat_shade_inputs_batch(sh_degree, means, views, B, gp["features_dc"].contiguous(),
-                                               gp["features_rest"].contiguous(), None, 0.0, None if tight else logits,
-                                               comp if aa else None, depths)
-    count.start_copy()
-    opac = opac if tight else opac2
-    # the tangents do not wait for the count either: they run under its way to the host
-    ptan = ops.splat_pose_ptangents_batch(means, cov3d, radii, views, B, torch.stack([m for _, m in per_view]), H, W)
-    totals, visible, gids, bins = ops.splat_bin_sort_batch(xys, depths, radii, count, H, W, block_width,
-                                                           tight=(conics, opac) if tight else None)
-    empty = [totals[v] == 0 and not (tight and visible[v]) for v in range(B)]
-    if all(empty):
-        return empties()
-    res = ops.splat_pose_jacobian_batch(gids, bins, xys, conics, cols, depths, opac, ptan, P, H, W, background,
-                                        compensation=comp if aa else None, channels=channels, want=want,
-                                        block_width=block_width)
-    return [_pose_jacobian_empty(H, W, rows, P, want, background) if empty[v] else {k: res[k][v] for k in want}
+    f = _views_front(gp, c2ws, fxs, fys, cxs, cys, H, W, sh_degree, rasterize_mode == "antialiased", block_width, crop_ids,
+                     config_sh_degree, tight, projs=torch.stack([m for _, m in per_view]))
+    if f is None:
+        return [_pose_jacobian_empty(H, W, rows, P, want, background) for _ in range(B)]
+    res = ops.splat_pose_jacobian_batch(f.gids, f.bins, f.xys, f.conics, f.cols, f.depths, f.opac, f.ptan, P, H, W, background,
+                                        compensation=f.comp, channels=channels, want=want, block_width=block_width)
+    return [_pose_jacobian_empty(H, W, rows, P, want, background) if f.empty[v] else {k: res[k][v] for k in want}
             for v in range(B)]
 
 
